@@ -21,7 +21,7 @@ hard-codes, calculate_optical_flow.py:735-739) on 128 pairs per call and reports
 Everything that is not GPU work (synthetic inputs, the optional `--pmc` counter passes, which run this script as a
 child under rocprofv3) happens BEFORE the first GPU call, so no process is ever started from a GPU-initialised one.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 from a plain shell: this process starts the N ranks itself)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 from a plain shell: this process starts the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -50,6 +50,9 @@ DF_KERNEL = "k_df_sor_rt"
 # shape -- and WRITE_SIZE is exact.  Round 2 took the 8-B loads of the DeepFlow kernel raw (factor 1): its read traffic was
 # under-reported by 2x.
 LOAD_BYTES_PER_LANE = {"TVL1": "16", "deepflow": "8_tile_rows"}
+# --dump-outputs: data bytes written in all (shared by the legs of a run) and the seed of the pairs sampled
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 20261015
 
 
 def fetch_factor(algo):
@@ -362,7 +365,19 @@ def run_steps_pipelined(first, n, E, nbuf, submit, collect, issue=None, retire=N
     return stats
 
 
-def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, local_rank, live_pmc=None, cpu_sample=8):
+def dump_flows(path, flows, budget):
+    """`--dump-outputs`: write a fixed, seeded sample of flows [n,H,W,2] (a torch tensor, on any device) to `path` as float32, at most
+    `budget` bytes of data: as many whole pairs as fit, or the top rows of one pair when a single pair is larger.  Returns what was written."""
+    n, H, W = flows.shape[:3]
+    k = max(1, min(n, budget // (H * W * 8)))
+    rows = min(H, budget // (k * W * 8))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    sample = flows[idx.tolist(), :rows].cpu().numpy().astype(np.float32, copy=False)
+    np.save(path, sample)
+    return {"file": os.path.basename(path), "shape": list(sample.shape), "pairs": idx.tolist(), "rows": rows}
+
+
+def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, local_rank, live_pmc=None, cpu_sample=8, dump_bytes=0):
     import tee_optical_flow_amd as T
     H = W = a.size
     frames = torch.from_numpy(np.concatenate([I0s, I1s])).to(dev)       # [2B,H,W] u8, resident in HBM
@@ -479,6 +494,12 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
         dist.all_gather_into_tensor(sums, mine)
         seg = bits(gathered[last_buf]).view(world, -1).sum(1)
         gather_ok = bool(torch.equal(seg.cpu(), sums.cpu()))
+    dumped = None
+    if dump_bytes and rank == 0:
+        # what a caller of the timed path received from the last timed step (every rank's pairs after the all-gather when N > 1), saved
+        # before the forms below solve into the same buffers
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        dumped = dump_flows(os.path.join(a.dump_outputs, f"{algo.lower()}_flows.npy"), gathered[last_buf] if world > 1 else last_flow, dump_bytes)
     # The same pairs in the two other forms, for the record beside `value` (N = 1): (i) SUB-pair calls, each split over `--lanes`
     # contiguous parts and joined at its end -- what rounds 1-3 timed; (ii) SUB-pair jobs submitted without waiting, three in flight.
     npx = H * W
@@ -720,6 +741,8 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
         out["collective"] = collective
         if gather_ok is not None:
             out["allgather_checksums_match"] = gather_ok
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
     if rank == 0 and not a.steps_only:
         # single-pair latency (BASELINE configs[1] as a latency number), outside the timed region
         lat_eng = T.DenseFlow(device_id=local_rank, max_batch=1, algo=algo)
@@ -815,7 +838,7 @@ def main():
     ap.add_argument("--algo", default="TVL1", choices=["TVL1", "deepflow"], help="BASELINE configs[1..2] (TVL1, default) or configs[3] (deepflow) as the main leg")
     ap.add_argument("--no-deepflow", action="store_true", help="skip the DeepFlow leg the default N=1 TVL1 run appends")
     ap.add_argument("--deepflow-batch", type=int, default=128, help="pairs per step of the DeepFlow leg (64 pairs: 577, 128: 601-607, 256: 608 pairs/s on one MI355X)")
-    ap.add_argument("--deepflow-steps", type=int, default=4)
+    ap.add_argument("--deepflow-steps", type=int, default=None, help="timed steps of the DeepFlow leg (default: --steps; its warm-up is --warmup)")
     ap.add_argument("--pmc", action="store_true", help="N=1 only: first run the FETCH_SIZE / WRITE_SIZE counter passes of this command as child "
                                                        "processes under rocprofv3 (adds ~1-2 min), so roofline.traffic is measured in this run")
     ap.add_argument("--pmc-dir", default=os.path.join(ROOT, "gpurun_out", "pmc_live"))
@@ -829,7 +852,12 @@ def main():
     ap.add_argument("--torch-collective", action="store_true", help="N>1: all-gather through torch.distributed instead of the library's tf_allgather_flows")
     ap.add_argument("--tuning", default="", help="experiments only: engine knobs as name=value,... (tf_set_tuning); empty = shipped defaults")
     ap.add_argument("--clock-ghz", type=float, default=2.4, help="shader clock assumed for the cycles-per-instruction figure (max clock; DESIGN.md notes 2.32 held under load)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flows each leg's last timed step returned as DIR/<algo>_flows.npy (float32; a fixed, "
+                         "seeded sample of the pairs, at most 48 MiB in all) so that two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0 or (a.deepflow_steps is not None and a.deepflow_steps < 1):
+        ap.error("--steps and --deepflow-steps must be at least 1, --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -843,12 +871,6 @@ def main():
         raise SystemExit(rc)
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
-    if world > 1:
-        # N > 1: the all-gather of step k runs on the engine's communication stream beside step k+1's solve.  With HIP's four hardware
-        # queues every queue a created stream can get is already one of the three lanes', and a collective kernel that shares a lane's
-        # queue would hold that lane up while it waits for its peers; eight queues give the communication stream (and RCCL's own) room.
-        # (Single-GPU runs leave the default: eight queues slow the latency-bound forms)  Before torch touches HIP.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
     # ---- CPU-only preparation: nothing below this block may start a process ------------------------------------
     if a.batch is None:
@@ -883,11 +905,13 @@ def main():
         else:
             dist.init_process_group(a.backend)
 
+    dump_bytes = DUMP_BYTES // (2 if want_df else 1) if a.dump_outputs else 0
     out = run_leg(a, a.algo, B, a.steps, a.warmup, I0s, I1s, torch, dist, dev, rank, world, local_rank,
-                  live_pmc=live.get(a.algo), cpu_sample=a.cpu_sample)
+                  live_pmc=live.get(a.algo), cpu_sample=a.cpu_sample, dump_bytes=dump_bytes)
     if want_df:
-        df = run_leg(a, "deepflow", DB, a.deepflow_steps, 1, I0s[:DB], I1s[:DB], torch, dist, dev, rank, world, local_rank,
-                     live_pmc=live.get("deepflow"), cpu_sample=2)
+        df_steps = a.steps if a.deepflow_steps is None else a.deepflow_steps
+        df = run_leg(a, "deepflow", DB, df_steps, a.warmup, I0s[:DB], I1s[:DB], torch, dist, dev, rank, world, local_rank,
+                     live_pmc=live.get("deepflow"), cpu_sample=2, dump_bytes=dump_bytes)
         if rank == 0:
             df["why"] = "OF_algo='deepflow' is what the reference's CLI runs (calculate_optical_flow.py:735-739); BASELINE configs[3]"
             out["deepflow"] = df

@@ -184,3 +184,23 @@ def test_pipelined_steps_failure_leaves_nothing_in_flight(E, collectives):
     import bench  # noqa: F401
     with pytest.raises(RuntimeError, match="injected failure in step 9"):
         _fake_run(E, 2, 15, collectives, fail_at=9)
+
+
+def test_dump_outputs_sample_is_fixed_bounded_and_float32(tmp_path):
+    """--dump-outputs: the same seeded pairs from run to run, whole pairs while they fit the budget, the top rows of one pair when a
+    single pair does not, float32 as the path returns it; bad --steps / --warmup values are refused before anything runs."""
+    import subprocess
+    import torch
+    import bench
+    flows = torch.arange(20 * 6 * 5 * 2, dtype=torch.float32).reshape(20, 6, 5, 2)
+    rec = bench.dump_flows(str(tmp_path / "a.npy"), flows, 4 * 6 * 5 * 8 + 7)
+    got = np.load(tmp_path / "a.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 6, 5, 2) and rec["shape"] == [4, 6, 5, 2] and rec["rows"] == 6
+    assert np.array_equal(got, flows.numpy()[rec["pairs"]]) and rec["pairs"] == sorted(set(rec["pairs"]))
+    assert bench.dump_flows(str(tmp_path / "b.npy"), flows, 4 * 6 * 5 * 8 + 7)["pairs"] == rec["pairs"]
+    assert np.array_equal(np.load(tmp_path / "b.npy"), got)
+    rec = bench.dump_flows(str(tmp_path / "c.npy"), flows, 3 * 5 * 8)
+    assert np.load(tmp_path / "c.npy").nbytes <= 3 * 5 * 8 and rec["shape"] == [1, 3, 5, 2]
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--deepflow-steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "at least" in r.stderr, (bad, r.stderr[-500:])

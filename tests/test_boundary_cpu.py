@@ -60,9 +60,13 @@ def test_default_params_are_cv2_defaults():
 
 def test_no_silent_cpu_fallback():
     """Without a GPU the product path must raise, not compute on the CPU."""
-    import torch
+    import sys
     import tee_optical_flow_amd as T
-    if torch.cuda.is_available():
+    # torch is asked in a process of its own: once the library has loaded its HIP runtime here (an earlier test may have), torch brings a
+    # second copy of the runtime into this process, and that copy sees no device even where there is one
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    if r.stdout.split()[-1] == "True":
         pytest.skip("a GPU is visible")
     with pytest.raises(T.OpticalFlowCalculationError, match="no HIP device|no CPU fallback"):
         T.DenseFlow()

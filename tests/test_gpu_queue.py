@@ -207,30 +207,32 @@ eng.close()
 """
 
 
-@pytest.mark.parametrize("queues", ["2", "4", "8"])
+@pytest.mark.parametrize("queues", ["2"])
 def test_lanes_look_for_streams_that_run_beside_each_other(queues):
-    """HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues and serialises streams that share one.  With 8 or 4 queues the three
-    lanes end up on streams that run concurrently (the probe may have to drop a few); with 2 they cannot, and the library says so
-    instead of assuming.  (The library leaves GPU_MAX_HW_QUEUES alone: with 8 the two-lane form of one-sub-batch calls measured 2276
-    against 2673 pairs/s -- DESIGN.md section 5a.)  Flows do not depend on any of it."""
+    """HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues and serialises streams that share one.  With two queues the three
+    lanes cannot all get streams that run concurrently, and the library says so instead of assuming.  With HIP's default of four queues
+    (the environment's own setting when it sets none) the probe finds such streams; the library leaves the setting alone, DESIGN.md
+    section 5a.  Flows do not depend on any of it: the probe under the environment's own setting returns the same flows."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", PROBE.replace("ROOT", repr(root))], capture_output=True, text=True, timeout=300,
-                       env={**os.environ, "GPU_MAX_HW_QUEUES": queues})
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
-    g = json.loads(r.stdout.strip().splitlines()[-1])
-    assert g["lanes"] == 3 and g["same"]
-    if queues == "2":
-        assert g["serialised"] & 1 and g["retries"] >= 8
-    else:
-        assert g["serialised"] & 1 == 0
-    if queues == "8":
-        assert g["serialised"] == 0                                       # room for the lanes' copy streams too
-    test_lanes_look_for_streams_that_run_beside_each_other.sums = getattr(test_lanes_look_for_streams_that_run_beside_each_other, "sums", set()) | {g["sum"]}
-    assert len(test_lanes_look_for_streams_that_run_beside_each_other.sums) == 1
+    runs = {}
+    for name, env in (("set", {**os.environ, "GPU_MAX_HW_QUEUES": queues}), ("environment", dict(os.environ))):
+        r = subprocess.run([sys.executable, "-c", PROBE.replace("ROOT", repr(root))], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, (name, r.stdout[-1500:], r.stderr[-3000:])
+        runs[name] = g = json.loads(r.stdout.strip().splitlines()[-1])
+        assert g["lanes"] == 3 and g["same"], name
+    assert runs["set"]["serialised"] & 1 and runs["set"]["retries"] >= 8
+    assert runs["set"]["sum"] == runs["environment"]["sum"]
+    # the environment's own run: with HIP's default of four queues (or more) the probe must find lanes that run beside each other;
+    # with two or fewer it cannot, and must say so as above (three queues: no claim either way)
+    env_queues = int(os.environ.get("GPU_MAX_HW_QUEUES") or 4)
+    if env_queues >= 4:
+        assert runs["environment"]["serialised"] & 1 == 0, runs["environment"]
+    elif env_queues <= 2:
+        assert runs["environment"]["serialised"] & 1 and runs["environment"]["retries"] >= 8, runs["environment"]
 
 
 @pytest.mark.parametrize("algo,cap", [("TVL1", 5), ("deepflow", 4)])
@@ -317,8 +319,12 @@ def test_engines_with_lanes_give_back_their_device_memory_and_threads():
     """tf_destroy ends the lanes (host threads, streams, device buffers, jobs never waited for): handles made and closed in a loop
     leave the device's free memory and the process's thread count where the first round left them."""
     import ctypes
+    from tee_optical_flow_amd import _lib
     from tee_optical_flow_amd.synth import speckle_sequence
-    hip = ctypes.CDLL("libamdhip64.so")                                   # (already in the process: the library links it; torch stays out of this test)
+    # the HIP runtime the library is bound to: symbols looked up through its handle come from its own dependencies.  (Opening
+    # libamdhip64.so by name can give torch's copy of the runtime instead, when torch was imported after the library; torch stays
+    # out of this test.)
+    hip = _lib.load()
 
     def free_bytes():
         f, t = ctypes.c_size_t(0), ctypes.c_size_t(0)

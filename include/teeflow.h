@@ -22,9 +22,10 @@
  * -- tf_calc_pairs with 1024 pairs, tf_calc_seq on a 1025-frame study -- is cut into equal sub-batches (as few as fit, a multiple of
  * the lane count of them: 1024 pairs = 9 x 114) that the
  * handle's LANES (engines of their own inside the library: stream, buffers, host thread; three for
- * DualTVL1, one for DeepFlow) take from a queue one at a time: a lane that has finished a sub-batch starts
+ * DualTVL1, two for DeepFlow) take from a queue one at a time: a lane that has finished a sub-batch starts
  * the next at once, so one sub-batch's tail (few pairs still iterating) runs under the others' full
- * launches.  The call returns when all of its sub-batches are done (if one fails, those not yet started
+ * launches.  A call of at most one sub-batch, on an idle queue, is cut into "lanes" (2) contiguous units
+ * that the lanes solve side by side (fewer while a unit would hold under 16 pairs; one: the handle alone).  The call returns when all of its sub-batches are done (if one fails, those not yet started
  * are dropped, the ones running finish, and the call returns the failure with nothing left in flight).
  * tf_submit_* queue the same job without waiting (tf_wait collects it), so that consecutive batches --
  * the studies of a folder, the steps of a stream -- keep the lanes busy across calls.  Flows and
@@ -273,9 +274,9 @@ int tf_device_count(void);
  * "sor_fuse" (sweeps per launch of the tiled register kernel), "sor_rt_shape" (region shape; 3 = chosen per launch), "sor_coop" (1 = all sweeps
  * of a fixed-point iteration in one launch of co-resident regions where a level needs several [default], 2 = always 128x64 regions, 3 = always
  * 128x32 regions for small batches, 0 = never), "sor_coop_small" (0 = small batches keep the tiled form), "sor_coop_s" (sweeps between two exchanges), "sor_coop_min_util" (per cent of its CUs such a launch must fill, else tiled), "df_fuse_ds" (form of the data/smoothness kernel).
- * Both: "lanes" (contiguous parts a call of at most one sub-batch is split into, joined at its end), "queue_lanes" (lanes that take whole
- * sub-batches of larger calls and of tf_submit_* jobs from the queue: -1 = 3 for DualTVL1, 1 for DeepFlow [default]; 0 = no queue, every call is
- * split in contiguous parts as in rounds 1-4), "queue_unit" (pairs per queued sub-batch; 0 = equal sub-batches of at most max_batch pairs, a multiple of the lane count of them). */
+ * Both: "lanes" (contiguous units a call of at most one sub-batch is split into, solved side by side on the queue lanes), "queue_lanes" (lanes
+ * that take those units, the sub-batches of larger calls and tf_submit_* jobs from the queue: -1 = 3 for DualTVL1, "lanes" for DeepFlow [default];
+ * 0 = no lanes: the handle solves every call alone, sub-batch after sub-batch -- the same flows), "queue_unit" (pairs per queued sub-batch; 0 = equal sub-batches of at most max_batch pairs, a multiple of the lane count of them). */
 int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),
  * "coop_aborts" (calls repeated with the tiled form because such a launch gave up waiting), "coop_disabled"; "queue_jobs", "queue_units_done",

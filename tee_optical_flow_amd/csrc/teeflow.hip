@@ -56,6 +56,7 @@ struct ProfEv { hipEvent_t a, b; int level = 0, warp = 0, it = 0; float ms = 0.f
 // assignment (a knob missed in a field-by-field copy would silently make the lanes differ).
 struct LanePool;
 struct QJob;
+struct CoopCounters { long long launches = 0; int aborts = 0, rearms = 0, cooldown = 0; bool disabled = false; };
 struct TfKnobs {
     int iter_variant = 2;        // 0 = 64x16 tiles (k_iter), 1 = full-width row strips (k_iter_rows), 2 = row strips with TWO
                                  // iterations per launch (k_iter2_rows); 1 and 2 need W <= max_strip_width (2048) and enough rows*pairs
@@ -95,13 +96,14 @@ struct TfKnobs {
     int strip_blocks = 2048;     // target number of strip blocks per launch (sets rows per strip)
     int lag = DEFAULT_LAG;
     int slots_override = 0;      // resident blocks the strips are sized for (0 = what the occupancy query says)
-    int lane_slots_pct = 67;     // queue lanes: per cent of the resident blocks a lane sizes its strips for.  Three lanes' launches share the GPU, so a
+    int lane_slots_pct = 67;     // queue units (not a split call's): per cent of the resident blocks a lane sizes their strips for.  Three lanes share the GPU, so a
                                  // lane that cuts its level into one round of ALL resident blocks pays the 3 halo + 2 RY fill rows of short strips for
                                  // parallelism the other lanes already provide (queue form, 384 pairs per call: 100 % 2728-2745, 67 % 2769-2772,
                                  // 50 % 2767-2769, 33 % 2706-2711 pairs/s on one box)
     int coop_test_occ16 = -1, coop_test_occ8 = -1;   // tests: pretend the occupancy query answered this
     int coop_test_mute = 0;      // tests: block 0 of every co-resident launch never raises its flag -> its neighbours give up -> the call is repeated tiled
     int profile = 0;
+    unsigned sor_coop_arm = 0;   // bumped by tf_set_tuning("sor_coop", non-zero): a lane that sees a new value in a job's knobs re-arms the form
 };
 
 struct tf_handle : TfKnobs {
@@ -154,10 +156,9 @@ struct tf_handle : TfKnobs {
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     // ---- analysis session (row f1) ----
     double* an_rad = nullptr; double* an_lon = nullptr; int anN = 0, anH = 0, anW = 0;
-    int lanes = 2;               // a batch of >= 32 pairs is split over this many independent (handle, stream, host thread) lanes:
-                                 // while one lane runs the thin tail of a stage, the other fills the GPU.  Measured at 128 pairs
+    int lanes = 2;               // an idle call of one sub-batch, >= 32 pairs, is split in this many contiguous units solved side by side on the
+                                 // queue lanes: while one runs the thin tail of a stage, the other fills the GPU.  Measured at 128 pairs
                                  // @512^2: 1 lane 2180, 2 lanes 2470, 3 lanes 2415, 4 lanes 2165 pairs/s (DeepFlow 377 vs 309)
-    std::vector<tf_handle*> twins; bool is_twin = false;   // extra lanes (own stream, buffers, host thread each)
     int num_cus = 256;
     // WASE scratch (grown on demand): compacted products, block counts / offsets, piece sums, per-flow backgrounds
     float* wa = nullptr; size_t wa_cap = 0;
@@ -165,7 +166,7 @@ struct tf_handle : TfKnobs {
     float* wsum = nullptr; size_t wsum_cap = 0;
     float* wbg = nullptr; size_t wbg_cap = 0;
     std::map<size_t, int> slots_cache;      // resident k_iter2_rows blocks on the device, by (LDS bytes, waves per block)
-    int coop_share = 0;          // CUs (= resident 1024-thread blocks) this handle may fill with such a launch; set per call (calc_entry)
+    int coop_share = 0;          // CUs (= resident 1024-thread blocks) this handle may fill with such a launch; set per call (solve_alone, lane_worker)
     bool coop_disabled = false;  // a launch of this handle gave up waiting (foreign work on the GPU): tiled form until the back-off has run out
     int coop_backoff = 0;        // tiled solves (sub-batches) to sit out before the co-resident form is tried again; doubles with every abort
     int coop_cooldown = 0;       // ... of which this many are left
@@ -183,16 +184,17 @@ struct tf_handle : TfKnobs {
     hipStream_t comm_stream = nullptr; hipEvent_t comm_ev[8] = {}; hipEvent_t comm_ready = nullptr; unsigned comm_tickets = 0;
     double warp_ms = 0, median_ms = 0;   // profiling: summed launch durations per stage of the last call
     // ---- engine lanes that pull whole sub-batches from a queue (calc_entry, tf_submit_*) ----
-    int queue_lanes = -1;        // -1 = per algorithm (3 DualTVL1, 1 DeepFlow); 0 = never: every call is cut in contiguous parts that are joined at its end
+    int queue_lanes = -1;        // -1 = per algorithm (3 DualTVL1, `lanes` DeepFlow); 0 = never: the handle solves every call alone, sub-batch after sub-batch
     int queue_unit = 0;          // pairs per queue unit (0 = equal units of at most max_batch pairs, a multiple of the lane count of them)
     int queue_test_fail_unit = -1;   // tests: the lane that takes this unit of the next queued job reports a failure instead of solving it
-    bool is_lane = false;        // this handle is a queue lane of another handle (an engine of its own: stream, buffers, host thread, its own twins)
+    bool is_lane = false;        // this handle is a queue lane of another handle (an engine of its own: stream, buffers, host thread)
+    int slots_pct = 100;         // per cent of the resident blocks this handle sizes its strips for (a lane: what its current job says)
     tf_handle* owner = nullptr;  // ... of this one
     LanePool* pool = nullptr;
     long long q_jobs = 0, q_units_done = 0, q_units_skipped = 0, q_units_failed = 0;
     std::map<int, QJob*> tickets; int next_ticket = 1;      // tf_submit_* jobs not yet waited for
-    int stream_retries = 0;      // streams made and dropped while looking for lane / twin streams that run beside each other (give_concurrent_stream)
-    int streams_serialised = 0;  // bit 0: a lane or twin had to keep a solve stream that shares a hardware queue with a sibling's; bit 1: a lane's copy stream shares one with a solve stream
+    int stream_retries = 0;      // streams made and dropped while looking for lane streams that run beside each other (pool_ensure)
+    int streams_serialised = 0;  // bit 0: a lane had to keep a solve stream that shares a hardware queue with a sibling's; bit 1: a lane's copy stream shares one with a solve stream
 };
 
 
@@ -200,19 +202,18 @@ struct tf_handle : TfKnobs {
 // A call larger than one sub-batch (and every tf_submit_* job) becomes a QJob: it is cut into units of at most `unit` pairs, and the
 // handle's lanes -- engines of their own: handle, stream, buffers, host thread -- take one unit at a time, oldest job first.  A lane
 // that has finished a unit starts the next one at once, whichever job it belongs to, so one sub-batch's tail (few pairs still
-// iterating, the fine pyramid levels done) runs under other sub-batches' full launches.  Rounds 1-4 cut such a call into L contiguous
-// parts and joined them; bench.py reached the same overlap with three engines driven by Python threads (EnginePool).
+// iterating, the fine pyramid levels done) runs under other sub-batches' full launches.  An idle call of one sub-batch becomes a job of
+// `lanes` contiguous units, solved side by side.
 struct QJob {
     int mode = 0; const uint8_t* in0 = nullptr; const uint8_t* in1 = nullptr; int n_pairs = 0, H = 0, W = 0; float scale = 1.f;
     float* out = nullptr; int device = 0; int src_f32 = 0;      // device: W_* bits
     tf_params P; tf_deepflow_params DP; TfKnobs knobs;      // the engine's settings when the job was queued
-    int split_lanes = 1;                                    // lanes each unit is split over inside its queue lane (calc_split)
+    int slots_pct = 100;                                    // the lanes size their strips for this per cent of the resident blocks
     int unit = 0, n_units = 0, next = 0, done = 0, fail_unit = -1;
     int rc = TF_OK; std::string err;
     tf_stats st; int merged = 0;
     std::vector<int> iters; size_t per_pair = 0; int nlev = 0, warps = 0;
     double t0 = 0;
-    std::function<void(QJob*)> on_done;                     // run once, by the lane that finishes the last unit, before `finished`
     void* owned_dev = nullptr;                              // device memory that lives as long as the job (tf_submit_seq_rgb: the conditioned frames)
     bool finished = false;
     ~QJob() { if (owned_dev) (void)hipFree(owned_dev); }
@@ -222,6 +223,8 @@ struct LanePool {
     std::deque<QJob*> jobs;                                 // jobs that still have units to hand out, oldest first
     std::vector<tf_handle*> lanes; std::vector<std::thread> th;
     bool stop = false; int outstanding = 0;                 // jobs queued and not finished
+    bool coop_held = false;                                 // DeepFlow: the device's co-resident claim, held while jobs are outstanding
+    std::vector<CoopCounters> coop;                         // each lane's co-resident counters, published at the end of its every unit
 };
 
 TF_API int tf_create(const tf_params* p, int device_id, tf_handle** out);
@@ -425,7 +428,7 @@ void launch_iter2(tf_handle* h, const Iter2Args& A, int B, hipStream_t s, int ac
                 f = h->slots_cache.emplace(shmem * 1024 + (size_t)threads / 64, per_cu * h->num_cus).first;
             }
             slots = f->second;
-            if (h->is_lane && h->lane_slots_pct > 0 && h->lane_slots_pct < 100) slots = slots * h->lane_slots_pct / 100;
+            if (h->slots_pct > 0 && h->slots_pct < 100) slots = slots * h->slots_pct / 100;
         }
         int items = 1;
         for (int n = 1; n <= B; ++n) {
@@ -773,12 +776,15 @@ int coop_aborted(tf_handle* h, bool* aborted)
     return TF_OK;
 }
 // Two launches of co-resident regions that each count on the same CUs can wait for each other for ever (each holds CUs the other's
-// last blocks need), so at most one call per device and process may use the form at a time; its lanes split the CUs between them.
+// last blocks need), so at most one call (or one lane pool with jobs outstanding) per device and process may use the form at a time;
+// a pool's lanes split the CUs between them.
 static std::atomic<int> g_coop_busy[64];
+bool coop_claim(int dev) { int z = 0; return dev >= 0 && dev < 64 && g_coop_busy[dev].compare_exchange_strong(z, 1); }
+void coop_release(int dev) { g_coop_busy[dev].store(0); }
 struct CoopClaim {
     int dev; bool ok;
-    explicit CoopClaim(int dev_) : dev(dev_), ok(false) { int z = 0; if (dev >= 0 && dev < 64) ok = g_coop_busy[dev].compare_exchange_strong(z, 1); }
-    ~CoopClaim() { if (ok) g_coop_busy[dev].store(0); }
+    explicit CoopClaim(int dev_) : dev(dev_), ok(coop_claim(dev_)) {}
+    ~CoopClaim() { if (ok) coop_release(dev); }
 };
 
 int df_ensure_alloc(tf_handle* h, int H, int W, int B)
@@ -1252,8 +1258,6 @@ void merge_stats(tf_stats* st, const tf_stats& sb)
     st->inner_iters_total += sb.inner_iters_total; st->outer_iters_total += sb.outer_iters_total;
 }
 
-// One sub-batch-sized call: optionally split over several lanes (this handle + twins with their own stream, buffers and host
-// thread, joined at the end): the launch gaps and thin tail launches of one lane are filled by the others.
 // Whatever went wrong, nothing of the failed call may still be in flight when the caller gets its buffers back (a D2H
 // copy into flow_out on the copy stream, kernels writing the caller's device buffer): drain every stream of the handle.
 int calc_common_guarded(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
@@ -1268,58 +1272,13 @@ int calc_common_guarded(tf_handle* h, Mode mode, const uint8_t* in0, const uint8
     return rc;
 }
 
-int calc_split(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
-               float* flow_out, int device, tf_stats* st)
+// The handle solves the call alone, sub-batch after sub-batch (calc_common cuts by capacity); DeepFlow claims the device's CUs per call
+int solve_alone(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
+                float* flow_out, int device, tf_stats* st)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    int L = h->lanes;
-    while (L > 1 && n_pairs / L < 16) --L;                   // a lane needs a batch worth its launches
-    CoopClaim claim(h->is_twin || h->P.algo != TF_ALGO_DEEPFLOW ? -1 : h->dev);
-    if (!h->is_twin) h->coop_share = claim.ok ? h->num_cus : 0;
-    if (L < 2 || h->is_twin || !in0 || !flow_out || (mode == MODE_PAIRS && !in1) || H < 1 || W < 1 || h->stream != h->own_stream)
-        return calc_common_guarded(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
-    while ((int)h->twins.size() < L - 1) {
-        tf_handle* t = nullptr;
-        int rc = h->P.algo == TF_ALGO_DEEPFLOW ? tf_create_deepflow(&h->DP, h->dev, &t) : tf_create(&h->P, h->dev, &t);
-        if (rc) return fail(h, rc, "creating lane %d failed: %s", (int)h->twins.size() + 2, tf_last_error(nullptr));
-        t->is_twin = true;
-        std::vector<hipStream_t> others{h->own_stream};
-        for (tf_handle* o : h->twins) others.push_back(o->own_stream);
-        if (!give_concurrent_stream(t, others, &h->stream_retries)) h->streams_serialised |= 1;
-        h->twins.push_back(t);
-    }
-    const size_t npx = (size_t)H * W, fpx = npx * (h->src_f32 ? 4 : 1);      // fpx in bytes
-    std::vector<tf_stats> ss((size_t)L);
-    std::vector<int> rcs((size_t)L, TF_OK), first((size_t)L + 1, 0);
-    for (int k = 0; k <= L; ++k) first[k] = (int)((long long)n_pairs * k / L);
-    std::vector<std::thread> th;
-    for (int k = 1; k < L; ++k) {
-        tf_handle* t = h->twins[k - 1];
-        t->P = h->P; t->DP = h->DP; t->src_f32 = h->src_f32;
-        static_cast<TfKnobs&>(*t) = static_cast<const TfKnobs&>(*h);          // every knob, one assignment
-        if (t->coop_flags) coop_query_occupancy(t);                           // asks again only if the test overrides have changed
-        t->coop_share = (claim.ok ? h->num_cus : 0) / L;
-        // pairs [first[k], first[k+1]); in sequence mode the lane's frames start at its first pair (one frame of overlap)
-        const uint8_t* b0 = in0 + (size_t)first[k] * fpx;
-        const uint8_t* b1 = mode == MODE_SEQ ? nullptr : in1 + (size_t)first[k] * fpx;
-        const int nb = first[k + 1] - first[k];
-        float* fo = flow_out + (size_t)first[k] * npx * 2;
-        th.emplace_back([=, &ss, &rcs] { rcs[k] = calc_common_guarded(t, mode, b0, b1, nb, H, W, scale, fo, device, &ss[k]); });
-    }
-    h->coop_share = (claim.ok ? h->num_cus : 0) / L;
-    rcs[0] = calc_common_guarded(h, mode, in0, in1, first[1], H, W, scale, flow_out, device, &ss[0]);
-    for (auto& x : th) x.join();
-    if (rcs[0]) return rcs[0];
-    for (int k = 1; k < L; ++k)
-        if (rcs[k]) return fail(h, rcs[k], "%s", h->twins[k - 1]->err.c_str());
-    for (int k = 1; k < L; ++k) h->last_iters.insert(h->last_iters.end(), h->twins[k - 1]->last_iters.begin(), h->twins[k - 1]->last_iters.end());
-    h->last_pairs = n_pairs;
-    if (st) {
-        *st = ss[0];
-        st->n_pairs = n_pairs;
-        for (int k = 1; k < L; ++k) merge_stats(st, ss[k]);
-    }
-    return TF_OK;
+    CoopClaim claim(h->P.algo == TF_ALGO_DEEPFLOW ? h->dev : -1);
+    h->coop_share = claim.ok ? h->num_cus : 0;
+    return calc_common_guarded(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
 }
 
 
@@ -1327,19 +1286,40 @@ int calc_split(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, 
 int queue_lane_count(const tf_handle* h)
 {
     if (h->queue_lanes >= 0) return h->queue_lanes > 8 ? 8 : h->queue_lanes;
-    return h->P.algo == TF_ALGO_DEEPFLOW ? 1 : 3;           // DeepFlow's co-resident SOR launches take every CU: one lane (its units are split over two twins)
+    return h->P.algo == TF_ALGO_DEEPFLOW ? h->lanes : 3;    // DeepFlow's co-resident SOR launches split the CUs between its lanes
 }
-int queue_unit_pairs(const tf_handle* h)
+// contiguous parts an idle call of one sub-batch is split over: a part needs a batch worth its launches
+int split_count(const tf_handle* h, int n_pairs)
+{
+    int L = h->lanes;
+    while (L > 1 && n_pairs / L < 16) --L;
+    return L;
+}
+int sub_batch_pairs(const tf_handle* h)
 {
     const int mb = h->P.algo == TF_ALGO_DEEPFLOW ? h->DP.max_batch : h->P.max_batch;
     const int cap = mb > 0 ? mb : DEFAULT_MAX_BATCH;
     return h->queue_unit > 0 && h->queue_unit < cap ? h->queue_unit : cap;
 }
-
-void lane_worker(tf_handle* owner, LanePool* pool, tf_handle* lane)
+// pairs per queue unit: a sub-batch; DeepFlow's is cut further into the parts an idle call of that size is split over
+int queue_unit_pairs(const tf_handle* h)
 {
+    const int sb = sub_batch_pairs(h), L = h->P.algo == TF_ALGO_DEEPFLOW ? split_count(h, sb) : 1;
+    return (sb + L - 1) / L;
+}
+
+CoopCounters coop_counters(const tf_handle* t)
+{
+    CoopCounters c;
+    c.launches = t->coop_launches; c.aborts = t->coop_aborts; c.rearms = t->coop_rearms; c.cooldown = t->coop_cooldown; c.disabled = t->coop_disabled;
+    return c;
+}
+
+void lane_worker(tf_handle* owner, LanePool* pool, int k)
+{
+    tf_handle* lane = pool->lanes[k];
     for (;;) {
-        QJob* j; int u; bool skip;
+        QJob* j; int u; bool skip; int share;
         {
             std::unique_lock<std::mutex> lk(pool->m);
             pool->cv_work.wait(lk, [&] { return pool->stop || !pool->jobs.empty(); });
@@ -1348,18 +1328,21 @@ void lane_worker(tf_handle* owner, LanePool* pool, tf_handle* lane)
             u = j->next++;
             if (j->next >= j->n_units) pool->jobs.pop_front();
             skip = j->rc != TF_OK;                           // a unit of this job has failed: the rest is not started
+            if (j->P.algo == TF_ALGO_DEEPFLOW && !pool->coop_held) pool->coop_held = coop_claim(lane->dev);
+            share = pool->coop_held ? lane->num_cus / (int)pool->lanes.size() : 0;
         }
         tf_stats us; memset(&us, 0, sizeof us);
         int rc = TF_OK;
         const int c0 = u * j->unit, nb = j->n_pairs - c0 < j->unit ? j->n_pairs - c0 : j->unit;
         if (!skip) {
             const size_t npx = (size_t)j->H * j->W, fpx = npx * (j->src_f32 ? 4 : 1);
-            lane->P = j->P; lane->DP = j->DP; lane->src_f32 = j->src_f32; lane->lanes = j->split_lanes;
+            lane->P = j->P; lane->DP = j->DP; lane->src_f32 = j->src_f32; lane->slots_pct = j->slots_pct; lane->coop_share = share;
+            if (lane->sor_coop_arm != j->knobs.sor_coop_arm) { lane->coop_disabled = false; lane->coop_backoff = lane->coop_cooldown = 0; }
             static_cast<TfKnobs&>(*lane) = j->knobs;
             if (lane->coop_flags) coop_query_occupancy(lane);        // asks again only if the test overrides have changed
             if (u == j->fail_unit) rc = fail(lane, TF_ERR_HIP, "injected failure (queue_test_fail_unit)");
-            else rc = calc_split(lane, (Mode)j->mode, j->in0 + (size_t)c0 * fpx, j->in1 ? j->in1 + (size_t)c0 * fpx : nullptr, nb, j->H, j->W, j->scale,
-                                 j->out + (size_t)c0 * npx * 2, j->device, &us);
+            else rc = calc_common_guarded(lane, (Mode)j->mode, j->in0 + (size_t)c0 * fpx, j->in1 ? j->in1 + (size_t)c0 * fpx : nullptr, nb, j->H, j->W,
+                                          j->scale, j->out + (size_t)c0 * npx * 2, j->device, &us);
             lane->src_f32 = 0;
         }
         bool last;
@@ -1377,17 +1360,16 @@ void lane_worker(tf_handle* owner, LanePool* pool, tf_handle* lane)
                 if (j->per_pair && lane->last_iters.size() == (size_t)nb * j->per_pair)
                     memcpy(j->iters.data() + (size_t)c0 * j->per_pair, lane->last_iters.data(), (size_t)nb * j->per_pair * sizeof(int));
             }
+            pool->coop[k] = coop_counters(lane);
             last = ++j->done == j->n_units;
-        }
-        if (last) {
             // every lane that worked for this job has drained its streams (a solve is host-synchronous, a failed one drains in
             // calc_common_guarded): nothing of the job is in flight any more
-            if (j->on_done) j->on_done(j);
-            std::lock_guard<std::mutex> lk(pool->m);
-            j->finished = true;
-            --pool->outstanding;
-            pool->cv_done.notify_all();                      // (the waiter may free the job from here on)
+            if (last) {
+                j->finished = true;
+                if (--pool->outstanding == 0 && pool->coop_held) { coop_release(lane->dev); pool->coop_held = false; }
+            }
         }
+        if (last) pool->cv_done.notify_all();                // (the waiter may free the job from here on)
     }
 }
 
@@ -1406,7 +1388,8 @@ void pool_destroy(tf_handle* h)
     h->pool = nullptr;
 }
 
-// the handle's lanes, made on first use (and again when the "queue_lanes" knob has changed and nothing is queued)
+// the handle's lanes, made on first use (and again when the lane count has changed and nothing is queued).  Every stream probe of the
+// library runs here, while no lane of the handle has work on the GPU.
 int pool_ensure(tf_handle* h)
 {
     const int want = queue_lane_count(h);
@@ -1454,13 +1437,15 @@ int pool_ensure(tf_handle* h)
         for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
     }
     h->pool = pool;
-    for (tf_handle* l : pool->lanes) pool->th.emplace_back(lane_worker, h, pool, l);
+    pool->coop.resize(pool->lanes.size());
+    for (int k = 0; k < want; ++k) pool->th.emplace_back(lane_worker, h, pool, k);
     return TF_OK;
 }
 
-// fills the job from the handle's current settings and hands it to the lanes
+// fills the job from the handle's current settings and hands it to the lanes.  parts > 0: an idle call of one sub-batch, cut in that many
+// near-equal contiguous units whose strips are sized for every resident block (neither "queue_unit" nor "lane_slots_pct" applies)
 int queue_submit(tf_handle* h, QJob* j, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale, float* flow_out, int device,
-                 bool balance)
+                 bool balance, int parts = 0)
 {
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
     int rc = deep ? df_validate(h, h->DP) : validate_params(h, h->P);
@@ -1470,9 +1455,9 @@ int queue_submit(tf_handle* h, QJob* j, Mode mode, const uint8_t* in0, const uin
     if (rc) return rc;
     j->mode = mode; j->in0 = in0; j->in1 = in1; j->n_pairs = n_pairs; j->H = H; j->W = W; j->scale = scale; j->out = flow_out; j->device = device;
     j->src_f32 = h->src_f32; j->P = h->P; j->DP = h->DP; j->knobs = static_cast<const TfKnobs&>(*h);
-    j->split_lanes = deep ? h->lanes : 1;
-    j->unit = queue_unit_pairs(h);
-    if (h->queue_unit <= 0 && balance) {
+    j->slots_pct = parts > 0 ? 100 : h->lane_slots_pct;
+    j->unit = parts > 0 ? (n_pairs + parts - 1) / parts : queue_unit_pairs(h);
+    if (parts <= 0 && h->queue_unit <= 0 && balance) {
         // A synchronous call on an empty queue ends with its lanes draining.  Equal units, a multiple of the lane count of them: 512 pairs as 4 x 128 leave two lanes idle while the third solves its second
         // unit; as 6 x 86 every lane gets two.  200 pairs: 2629-2646 pairs/s as 128 + 72, 2772-2796 as 3 x 67; 448: 2734-2786 -> 2780-2824;
         // 640: 2867-2877 -> 2915-2922; 1024 (8 x 128 against 9 x 114): a tie (gpurun_out/r5o).  Smaller units cost a few per cent each
@@ -1521,22 +1506,23 @@ int queue_finish(tf_handle* h, QJob* j, tf_stats* st)
     return TF_OK;
 }
 
-// Entry used by the C ABI.  A call of at most one sub-batch is solved by this handle (calc_split: contiguous parts on its twins,
-// joined).  A larger one -- or any call while tf_submit_* jobs are in flight -- goes to the queue: whole sub-batches, taken by the
-// lanes as they come free; the call returns when every lane has finished its last unit of it (a failed unit stops the job's
-// remaining units from starting; the units already running complete, so nothing of the call is in flight when it returns).
+// Entry used by the C ABI.  An idle call of at most one sub-batch is split in split_count() contiguous units that the lanes solve side
+// by side, or solved by this handle alone when that count is 1.  A larger one -- or any call while tf_submit_* jobs are in flight -- goes
+// to the queue: whole sub-batches, taken by the lanes as they come free.  Either way the call returns when every lane has finished its
+// last unit of it (a failed unit stops the job's remaining units from starting; the units already running complete, so nothing of the
+// call is in flight when it returns).  An external stream, or "queue_lanes" = 0, has the handle solve every call alone.
 int calc_entry(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
                float* flow_out, int device, tf_stats* st)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    const bool can_queue = !h->is_twin && !h->is_lane && queue_lane_count(h) > 0 && in0 && flow_out && (mode != MODE_PAIRS || in1) && H >= 1 && W >= 1 &&
+    const bool can_queue = !h->is_lane && queue_lane_count(h) > 0 && in0 && flow_out && (mode != MODE_PAIRS || in1) && H >= 1 && W >= 1 &&
                            n_pairs >= 1 && h->stream == h->own_stream;
     bool busy = false;
     if (can_queue && h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); busy = h->pool->outstanding > 0; }
-    if (!can_queue || (!busy && n_pairs <= queue_unit_pairs(h)))
-        return calc_split(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
+    const int parts = !busy && n_pairs <= sub_batch_pairs(h) ? split_count(h, n_pairs) : 0;
+    if (!can_queue || parts == 1) return solve_alone(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
     QJob j;
-    int rc = queue_submit(h, &j, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, !busy);
+    int rc = queue_submit(h, &j, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, !busy, parts);
     if (rc) return rc;
     return queue_finish(h, &j, st);
 }
@@ -1549,14 +1535,14 @@ int submit_entry(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1
     if (!h || !ticket) return TF_ERR_INVALID_ARG;
     if (!in0 || (mode == MODE_PAIRS && !in1) || !flow_out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
     if (H < 1 || W < 1 || n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", n_pairs, H, W);
-    if (h->is_twin || h->is_lane || h->stream != h->own_stream) return fail(h, TF_ERR_UNSUPPORTED, "tf_submit_* needs the handle's own stream");
+    if (h->is_lane || h->stream != h->own_stream) return fail(h, TF_ERR_UNSUPPORTED, "tf_submit_* needs the handle's own stream");
     guard.p = nullptr;                                       // from here on the job owns it
     QJob* j = new QJob();
     j->owned_dev = owned_dev;                                // (freed with the job, whatever happens below)
     int rc;
     if (queue_lane_count(h) < 1) {                           // "queue_lanes" = 0: no lanes, the job is done when the call returns
         tf_stats st;
-        rc = calc_split(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, &st);
+        rc = solve_alone(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, &st);
         if (rc) { delete j; return rc; }
         j->st = st; j->n_pairs = n_pairs; j->nlev = h->last_nlev; j->warps = h->last_warps; j->iters = h->last_iters; j->t0 = now_ms() - st.ms_total; j->finished = true;
     } else {
@@ -1699,8 +1685,6 @@ TF_API void tf_destroy(tf_handle* h)
     pool_destroy(h);                                     // the lanes finish what is queued, then go
     for (auto& kv : h->tickets) delete kv.second;
     h->tickets.clear();
-    for (tf_handle* t : h->twins) tf_destroy(t);
-    h->twins.clear();
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_buffers(h);
@@ -1801,18 +1785,13 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
     else if (n == "max_strip_width") h->max_strip_width = value < 4 ? 4 : (value > 2048 ? 2048 : value);
     else if (n == "sub_batches") h->sub_batches = value < 1 ? 1 : value;
     else if (n == "lanes") h->lanes = value < 1 ? 1 : (value > 8 ? 8 : value);
-    else if (n == "queue_lanes") h->queue_lanes = value;          // -1 = per algorithm (3 DualTVL1, 1 DeepFlow), 0 = no queue: contiguous parts, joined
+    else if (n == "queue_lanes") h->queue_lanes = value;          // -1 = per algorithm (3 DualTVL1, `lanes` DeepFlow), 0 = no lanes: the handle alone
     else if (n == "queue_unit") h->queue_unit = value < 0 ? 0 : value;
     else if (n == "queue_test_fail_unit") h->queue_test_fail_unit = value;
     else if (n == "sor_fuse") h->sor_fuse = value;
-    else if (n == "sor_coop") {                       // setting the knob re-arms the form at once and forgets the back-off
+    else if (n == "sor_coop") {                       // setting the knob re-arms the form and forgets the back-off: at once, and on a lane when it takes its next job
         h->sor_coop = value;
-        if (value) {
-            std::vector<tf_handle*> all{h};
-            for (auto* t : h->twins) all.push_back(t);
-            if (h->pool) for (auto* l : h->pool->lanes) { all.push_back(l); for (auto* t : l->twins) all.push_back(t); }
-            for (auto* t : all) { t->coop_disabled = false; t->coop_backoff = t->coop_cooldown = 0; }
-        }
+        if (value) { h->coop_disabled = false; h->coop_backoff = h->coop_cooldown = 0; ++h->sor_coop_arm; }
     }
     else if (n == "sor_coop_s") h->sor_coop_s = value;
     else if (n == "sor_coop_small") h->sor_coop_small = value ? 1 : 0;
@@ -1838,18 +1817,17 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     if (!h || !name) return -1;
     const std::string n(name);
     long long v = -1;
-    std::vector<tf_handle*> all{h};                              // this handle, its twins, its queue lanes and theirs
-    for (auto* t : h->twins) all.push_back(t);
-    if (h->pool) for (auto* l : h->pool->lanes) { all.push_back(l); for (auto* t : l->twins) all.push_back(t); }
-    if (n == "coop_launches") { v = 0; for (auto* t : all) v += t->coop_launches; }
-    else if (n == "coop_aborts") { v = 0; for (auto* t : all) v += t->coop_aborts; }
-    else if (n == "coop_disabled") { v = 0; for (auto* t : all) v |= (long long)t->coop_disabled; }
-    else if (n == "coop_rearms") { v = 0; for (auto* t : all) v += t->coop_rearms; }
-    else if (n == "coop_cooldown") { v = 0; for (auto* t : all) v = v > t->coop_cooldown ? v : t->coop_cooldown; }
+    std::vector<CoopCounters> all{coop_counters(h)};            // this handle and what its lanes published at the end of their last unit
+    if (h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); all.insert(all.end(), h->pool->coop.begin(), h->pool->coop.end()); }
+    if (n == "coop_launches") { v = 0; for (auto& c : all) v += c.launches; }
+    else if (n == "coop_aborts") { v = 0; for (auto& c : all) v += c.aborts; }
+    else if (n == "coop_disabled") { v = 0; for (auto& c : all) v |= (long long)c.disabled; }
+    else if (n == "coop_rearms") { v = 0; for (auto& c : all) v += c.rearms; }
+    else if (n == "coop_cooldown") { v = 0; for (auto& c : all) v = v > c.cooldown ? v : c.cooldown; }
     else if (n == "saliency_kernel_us") v = (long long)(h->pre_kernel_ms * 1000.0);
     else if (n == "queue_jobs") v = h->q_jobs;
-    else if (n == "stream_retries") { v = h->stream_retries; if (h->pool) for (auto* l : h->pool->lanes) v += l->stream_retries; }
-    else if (n == "streams_serialised") { v = h->streams_serialised; if (h->pool) for (auto* l : h->pool->lanes) v |= l->streams_serialised; }
+    else if (n == "stream_retries") v = h->stream_retries;
+    else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {
         v = 0;
         if (h->pool) {

@@ -48,7 +48,9 @@ def test_mixed_batch_one_lane_equals_two_and_the_oracle(oracle, n, H, W, params)
         f0, it0 = _run(eng, I0s, I1s, lanes=1)
         spread = it0[..., 0].sum(axis=(1, 2))
         assert spread.max() > 1.5 * spread.min(), "the batch should mix fast and slow pairs"
-        f2, it2 = _run(eng, I0s, I1s, lanes=2)                               # the batch cut over two independent lanes
+        jobs, units = eng.counter("queue_jobs"), eng.counter("queue_units_done")
+        f2, it2 = _run(eng, I0s, I1s, lanes=2)                               # the batch cut in two units, solved side by side on the lanes
+        assert eng.counter("queue_jobs") == jobs + 1 and eng.counter("queue_units_done") == units + 2
         assert np.array_equal(it0, it2) and np.array_equal(f0, f2)
         op = oracle.default_params(**params)
         for b in (3, 5, n - 1):                                              # a zero-flow pair, an unrelated pair, the last one

@@ -133,7 +133,7 @@ def test_two_lane_split_of_large_batches(oracle):
     must be those of the single-lane run (and of the oracle), in the caller's pair order; sequence mode overlaps one frame."""
     import tee_optical_flow_amd as T
     from tee_optical_flow_amd.synth import speckle_pairs, speckle_sequence
-    I0s, I1s = speckle_pairs(range(200, 237), 48, 64)          # 37 pairs -> lanes of 18 and 19
+    I0s, I1s = speckle_pairs(range(200, 237), 48, 64)          # 37 pairs -> units of 19 and 18
     eng = T.DenseFlow()
     f2 = eng.calc_pairs(I0s, I1s)
     it2 = eng.last_iters()

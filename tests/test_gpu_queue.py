@@ -1,6 +1,6 @@
 """The library's lane queue (calc_entry / tf_submit_* / tf_wait, include/teeflow.h "Sub-batches and lanes"): a call larger than one
 sub-batch is cut into units that the handle's lanes take one at a time.  Whatever lane solves what, flows and executed iteration
-counts are those of the contiguous-split form of rounds 1-4 (queue_lanes = 0) and of the oracle, in pair order; a failing
+counts are those of the handle solving alone (queue_lanes = 0) and of the oracle, in pair order; a failing
 sub-batch drops the ones not yet started, lets the running ones finish and leaves nothing in flight; jobs submitted without
 waiting overlap and can be collected in any order.  Reference loop: calculate_optical_flow.py:584-597 (one loop -> one call)."""
 import numpy as np
@@ -25,7 +25,7 @@ def test_queue_gives_the_split_forms_flows_and_iteration_order(oracle, n, cap, u
     I0s, I1s = _mixed(n, 72, 96)
     eng = _engine(cap)
     try:
-        eng.set_tuning("queue_lanes", 0)                                  # rounds 1-4: contiguous parts, joined
+        eng.set_tuning("queue_lanes", 0)                                  # no lanes: the handle alone, sub-batch after sub-batch
         f0 = np.array(eng.calc_pairs(I0s, I1s)); it0 = eng.last_iters().copy()
         assert eng.counter("queue_jobs") == 0
         eng.set_tuning("queue_lanes", -1)
@@ -171,7 +171,7 @@ def test_device_jobs_in_flight_and_close_with_jobs_queued():
     assert r.returncode == 0 and "device jobs ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
-def test_deepflow_through_the_queue(oracle):
+def test_deepflow_through_the_queue_on_two_lanes(oracle):
     import tee_optical_flow_amd as T
     I0s, I1s = _mixed(20, 96, 160, seed0=500)
     eng = T.DenseFlow(device_id=0, max_batch=8, algo="deepflow")
@@ -180,8 +180,12 @@ def test_deepflow_through_the_queue(oracle):
         f0 = np.array(eng.calc_pairs(I0s, I1s))
         eng.set_tuning("queue_lanes", -1)
         f1 = np.array(eng.calc_pairs(I0s, I1s))
-        assert eng.counter("queue_lanes") == 1 and eng.counter("queue_units_done") == 3
+        # two lanes ("lanes"); a sub-batch of 8 is not split further (4-pair parts are below 16), so units of 8, balanced: 4 x 5
+        assert eng.counter("queue_lanes") == 2 and eng.counter("queue_units_done") == 4
         assert np.array_equal(f0, f1)
+        eng.set_tuning("queue_lanes", 1)                                  # one lane: whole sub-batches, balanced: 3 x 7
+        assert np.array_equal(np.array(eng.calc_pairs(I0s, I1s)), f0)
+        assert eng.counter("queue_lanes") == 1 and eng.counter("queue_units_done") == 4 + 3
         eng.set_tuning("queue_lanes", 2)
         t = eng.submit_pairs(I0s, I1s)
         assert np.array_equal(eng.wait(t), f0)
@@ -200,7 +204,7 @@ from tests.test_gpu_batches import _mixed_pairs
 I0s, I1s = _mixed_pairs(40, 64, 88, seed0=11)
 eng = T.DenseFlow(device_id=0, max_batch=16)
 f = np.array(eng.calc_pairs(I0s, I1s))                       # 3 units on 3 lanes
-one = np.array(eng.calc_pairs(I0s[:16], I1s[:16]))           # one sub-batch: the handle and its twin
+one = np.array(eng.calc_pairs(I0s[:16], I1s[:16]))           # one sub-batch of 16: the handle alone
 print(json.dumps({"retries": eng.counter("stream_retries"), "serialised": eng.counter("streams_serialised"), "lanes": eng.counter("queue_lanes"),
                   "same": bool(np.array_equal(f[:16], one)), "sum": float(np.abs(f).sum())}))
 eng.close()
@@ -336,7 +340,7 @@ def test_engines_with_lanes_give_back_their_device_memory_and_threads():
     for rnd in range(7):
         for algo in ("TVL1", "deepflow"):
             eng = _engine(8, algo=algo)
-            eng.calc_pairs(I0s, I1s)                                      # three units on the lanes (DeepFlow: one lane, its twin)
+            eng.calc_pairs(I0s, I1s)                                      # three units on the lanes (DeepFlow: four on two lanes)
             assert eng.counter("queue_jobs") == 1
             t1 = eng.submit_pairs(I0s[:9], I1s[:9])
             t2 = eng.submit_pairs(I0s[9:], I1s[9:])

@@ -269,7 +269,7 @@ int tf_device_count(void);
  *      with the oracle bit for bit; not part of the drop-in surface) -------------------------------- */
 /* implementation knobs for experiments (results never change).  DualTVL1: "iter_variant" (0 = 64x16 tiles, 1 = full-width row strips,
  * 2 = row strips with two iterations per launch [default]), "min_rows_work" (rows*pairs below which tiles are used), "strip_blocks" (target
- * blocks per tvl1_iter launch), "lag" (launches the host may run ahead of the device's stop reports), "warp_margin" (pixels of flow the
+ * blocks per tvl1_iter launch of a sub-batch above 1024 pairs), "max_strip_width" (widest level the row strips take), "warp_margin" (pixels of flow the
  * LDS-staged warp covers around its tile: 0 = global gathers only, default 8).  DeepFlow: "sor_rt" (0 = one colour per launch, the plain form),
  * "sor_fuse" (sweeps per launch of the tiled register kernel), "sor_rt_shape" (region shape; 3 = chosen per launch), "sor_coop" (1 = all sweeps
  * of a fixed-point iteration in one launch of co-resident regions where a level needs several [default], 2 = always 128x64 regions, 3 = always
@@ -281,7 +281,7 @@ int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),
  * "coop_aborts" (calls repeated with the tiled form because such a launch gave up waiting), "coop_disabled"; "queue_jobs", "queue_units_done",
  * "queue_units_failed", "queue_units_skipped" (sub-batches dropped because an earlier one of their call had failed), "queue_outstanding", "queue_lanes";
- * "experimental" (1: built with the experimental tvl1_iter forms); -1 for an unknown name */
+ * -1 for an unknown name */
 long long tf_dbg_counter(tf_handle* h, const char* name);
 /* DeepFlow hooks: one cv::VariationalRefinement::calcUV on dense float images (u, v updated in place); 3x3 Gaussian blur */
 int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v);

@@ -60,17 +60,8 @@ struct CoopCounters { long long launches = 0; int aborts = 0, rearms = 0, cooldo
 struct TfKnobs {
     int iter_variant = 2;        // 0 = 64x16 tiles (k_iter), 1 = full-width row strips (k_iter_rows), 2 = row strips with TWO
                                  // iterations per launch (k_iter2_rows); 1 and 2 need W <= max_strip_width (2048) and enough rows*pairs
-    int force_ry = 0;            // 0 = floor(256/QX) rows per step
-    int adaptive_strips = 0;     // strip length from the known active-pair count: measured no gain
-    int dynamic_strips = 1;      // strips sized on the device from the exact active-pair count (one round of resident blocks)
-    int tile_max_w = 0;          // levels this narrow or narrower always take the tile kernels (experiment: see DESIGN section 8)
-    int tile2 = 1;               // launches the row strips do not take (single pair, few pairs, > 2048 px wide) run two iterations per launch on tiles
     int max_strip_width = 2048;  // widest level the full-width strip kernels take (one quad per thread: 2048 px = 512-thread blocks).
                                  // 8 pairs: 1080x1920 57.7 vs 32.6 pairs/s with the tile kernel, 768x1100 184 vs 131, 720x1280 137 vs 148
-    int sub_batches = 1;         // >1 cuts a host-pointer call that fits the capacity into that many sub-batches so the copy-out of
-                                 // one overlaps the solve of the next; measured at 128 pairs @512^2: smaller batches cost more (2099 /
-                                 // 2030 / 1886 / 1701 pairs/s for 1 / 2 / 3 / 4) than the 5 ms of D2H they hide.  Calls larger than
-                                 // the capacity are cut anyway and do overlap.
     int sor_rt = 1;              // DeepFlow SOR: 1 = register-tile kernel k_df_sor_rt (teeflow_sor_rt.hip.h), 0 = one colour per launch (k_df_sor)
     int sor_plain_div = 0;       // tests: k_df_sor_rt takes its plain-IEEE-division path (what a block with out-of-range diagonals does)
     int sor_rt_shape = 3;        // k_df_sor_rt: 1 = 16 bands x 4 rows (1024 threads), 2 = 8 bands x 4 rows (128 x 32
@@ -93,9 +84,8 @@ struct TfKnobs {
                                  // 16 (+3.4 % pairs/s).  A pixel displaced by more than M falls back to the gathers, so M only moves time.
     int min_rows_work = 8192;    // rows*pairs of a level below which the tile kernels are used (measured at 512^2 with k_iter2_tile: 16 pairs
                                  // 12.5 ms on tiles vs 13.9 ms on strips, 24 pairs 17.1 vs 17.3, 64 pairs 34.1 vs 29.5)
-    int strip_blocks = 2048;     // target number of strip blocks per launch (sets rows per strip)
-    int lag = DEFAULT_LAG;
-    int slots_override = 0;      // resident blocks the strips are sized for (0 = what the occupancy query says)
+    int strip_blocks = 2048;     // target number of strip blocks per launch of a sub-batch above 1024 pairs (sets rows per strip; smaller
+                                 // sub-batches have their strips sized on the device)
     int lane_slots_pct = 67;     // queue units (not a split call's): per cent of the resident blocks a lane sizes their strips for.  Three lanes share the GPU, so a
                                  // lane that cuts its level into one round of ALL resident blocks pays the 3 halo + 2 RY fill rows of short strips for
                                  // parallelism the other lanes already provide (queue form, 384 pairs per call: 100 % 2728-2745, 67 % 2769-2772,
@@ -380,22 +370,26 @@ struct StageTotals {
 // full-width strips need W <= max_strip_width (at most 2048: one quad per thread, 512 threads) and enough rows*pairs to fill 256 CUs; tiny launches (single-pair latency mode) keep the tiles
 bool rows_ok(const tf_handle* h, const Geom& g, int B)
 {
-    return h->iter_variant >= 1 && g.w <= h->max_strip_width && g.w > h->tile_max_w && (long long)g.h * B >= h->min_rows_work;
+    return h->iter_variant >= 1 && g.w <= h->max_strip_width && (long long)g.h * B >= h->min_rows_work;
+}
+
+// two tvl1_iter iterations per launch (k_iter2_rows / k_iter2_tile) for a stage whose medians come every `inner` iterations.
+// TF_VARIANT_CUDA always runs that form (it has no median, and its iteration count is even)
+bool two_per_launch(const tf_handle* h, bool cuda_variant, int inner)
+{
+    return cuda_variant || (h->iter_variant >= 2 && inner % 2 == 0);
 }
 
 // Block shape of the row-strip kernels: QX quads per row, RY = floor(256/QX) rows per step, 256 threads.
 // (Measured on MI355X: shapes that fill more lanes with 320-512-thread blocks, or 1-row/128-thread blocks, are 10-35 %
-// SLOWER -- more waves per barrier domain / fewer blocks per CU cost more than idle lanes; "force_ry" keeps the experiment.)
-void strip_shape(const tf_handle* h, const Geom& g, int B, int* R, int* QX, int* RY, int* threads, bool two)
+// SLOWER -- more waves per barrier domain / fewer blocks per CU cost more than idle lanes.)
+void strip_shape(const tf_handle* h, const Geom& g, int B, int* R, int* QX, int* RY, int* threads)
 {
-    (void)two;
     const int qx = (g.w + 3) / 4;
     int ry = 256 / qx;
     if (ry < 1) ry = 1;
-    const int forced = h->force_ry;
-    if (forced > 0 && qx * forced <= 512) ry = forced;
     *QX = qx; *RY = ry;
-    *threads = (qx * ry <= 256 && forced <= 0) ? 256 : (qx * ry + 63) / 64 * 64;   // forced shapes: no idle waves
+    *threads = qx * ry <= 256 ? 256 : (qx * ry + 63) / 64 * 64;
     long long n = (long long)g.h * B / ((long long)h->strip_blocks * ry);
     if (n < 2) n = 2;
     if (n > 16) n = 16;
@@ -403,7 +397,7 @@ void strip_shape(const tf_handle* h, const Geom& g, int B, int* R, int* QX, int*
 }
 
 // launch one two-iteration tvl1_iter step (k_iter2_rows)
-void launch_iter2(tf_handle* h, const Iter2Args& A, int B, hipStream_t s, int active_hint = 0)
+void launch_iter2(tf_handle* h, const Iter2Args& A, int B, hipStream_t s)
 {
     const Geom& g = A.a.g;
     if (!rows_ok(h, g, B)) {      // small launches and very wide levels: tiles
@@ -411,25 +405,21 @@ void launch_iter2(tf_handle* h, const Iter2Args& A, int B, hipStream_t s, int ac
         return;
     }
     int R, QX, RY, threads;
-    // rows per strip follow the number of pairs known to be still iterating: the thin tail launches of a stage get many
-    // short strips (latency of a few steps) instead of a few long ones
-    strip_shape(h, g, active_hint > 0 && h->adaptive_strips ? active_hint : B, &R, &QX, &RY, &threads, true);
+    strip_shape(h, g, B, &R, &QX, &RY, &threads);
     const int LW = QX * 4 + 4;
     const size_t shmem = (size_t)(32 + 8 * RY * LW + 2 * (RY + 1) * LW + 2 * RY * QX) * sizeof(float);
-    if (h->dynamic_strips && B <= 1024) {
-        // strips sized on the device from the exact number of pairs still iterating; the grid covers the largest item count
-        int slots = h->slots_override;
-        if (slots <= 0) {
-            auto f = h->slots_cache.find(shmem * 1024 + (size_t)threads / 64);
-            if (f == h->slots_cache.end()) {
-                int per_cu = 0;
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iter2_rows, threads, shmem);
-                if (per_cu < 1) per_cu = 1;
-                f = h->slots_cache.emplace(shmem * 1024 + (size_t)threads / 64, per_cu * h->num_cus).first;
-            }
-            slots = f->second;
-            if (h->slots_pct > 0 && h->slots_pct < 100) slots = slots * h->slots_pct / 100;
+    if (B <= 1024) {
+        // strips sized on the device from the exact number of pairs still iterating (one round of resident blocks); the grid covers
+        // the largest item count
+        auto f = h->slots_cache.find(shmem * 1024 + (size_t)threads / 64);
+        if (f == h->slots_cache.end()) {
+            int per_cu = 0;
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iter2_rows, threads, shmem);
+            if (per_cu < 1) per_cu = 1;
+            f = h->slots_cache.emplace(shmem * 1024 + (size_t)threads / 64, per_cu * h->num_cus).first;
         }
+        int slots = f->second;
+        if (h->slots_pct > 0 && h->slots_pct < 100) slots = slots * h->slots_pct / 100;
         int items = 1;
         for (int n = 1; n <= B; ++n) {
             int r, sn;
@@ -439,6 +429,7 @@ void launch_iter2(tf_handle* h, const Iter2Args& A, int B, hipStream_t s, int ac
         hipLaunchKernelGGL(k_iter2_rows, dim3(items, 1, 1), dim3(threads), shmem, s, A, 0, QX, RY, slots);
         return;
     }
+    // a sub-batch above 1024 pairs (max_batch > 1024): fixed strips of R rows per pair
     hipLaunchKernelGGL(k_iter2_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem, s, A, R, QX, RY, 0);
 }
 
@@ -448,7 +439,7 @@ void launch_iter(tf_handle* h, const IterArgs& ia, int B, hipStream_t s)
     const Geom& g = ia.g;
     if (rows_ok(h, g, B)) {
         int R, QX, RY, threads;
-        strip_shape(h, g, B, &R, &QX, &RY, &threads, false);
+        strip_shape(h, g, B, &R, &QX, &RY, &threads);
         const int LW = QX * 4 + 4;
         const size_t shmem = (size_t)(32 + 8 * RY * LW + 2 * RY * QX) * sizeof(float);
         hipLaunchKernelGGL(k_iter_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem, s, ia, R, QX, RY);
@@ -479,14 +470,46 @@ void launch_warp(tf_handle* h, const WarpArgs& wa, int B, hipStream_t s, const f
     }
 }
 
-ProfEv* prof_next(tf_handle* h)
+// One profiled launch (tf_set_profile): `launch` between the two events of a record.  level -4 = warp, -5 = median, >= 0 = a tvl1_iter
+// launch of (level, warp, it) or a DeepFlow SOR launch (tf_dbg_launch_profile lists these).  Without profiling: `launch` alone.
+template <class Launch>
+int profiled(tf_handle* h, hipStream_t s, int level, int warp, int it, Launch&& launch)
 {
+    if (!h->profile) { launch(); return TF_OK; }
     if (h->prof_used == h->prof_pool.size()) {
         ProfEv pe;
-        if (hipEventCreate(&pe.a) != hipSuccess || hipEventCreate(&pe.b) != hipSuccess) return nullptr;
+        hipError_t e = hipEventCreate(&pe.a);
+        if (e == hipSuccess && (e = hipEventCreate(&pe.b)) != hipSuccess) (void)hipEventDestroy(pe.a);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, TF_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(e)); }
         h->prof_pool.push_back(pe);
     }
-    return &h->prof_pool[h->prof_used++];
+    ProfEv& pe = h->prof_pool[h->prof_used++];
+    pe.level = level; pe.warp = warp; pe.it = it;
+    HIPC(h, hipEventRecord(pe.a, s));
+    launch();
+    HIPC(h, hipEventRecord(pe.b, s));
+    return TF_OK;
+}
+
+// Read back the active-pair reports of this stage's launches [*checked, q] (a launch publishes its report when it starts): never more than
+// DEFAULT_LAG launches unread.  *stop: a launch that no pair entered active -- the rest of the stage would be no-ops.
+int read_reports(tf_handle* h, hipStream_t s, unsigned q, unsigned* checked, bool* stop)
+{
+    while (*checked <= q) {
+        int v = h->slots_host[*checked % SLOT_RING];
+        if (v < 0) {
+            if (q - *checked < (unsigned)DEFAULT_LAG) break;        // not there yet, and we may still run ahead
+            const double t0 = now_ms();
+            while ((v = h->slots_host[*checked % SLOT_RING]) < 0) {
+                if (now_ms() - t0 > 20000.0) return fail(h, TF_ERR_HIP, "tvl1_iter launch %u never reported (GPU hang?)", *checked);
+                if (hipStreamQuery(s) == hipSuccess && h->slots_host[*checked % SLOT_RING] < 0)
+                    return fail(h, TF_ERR_HIP, "stream drained but launch %u did not report", *checked);
+            }
+        }
+        ++*checked;
+        if (v == 0) { *stop = true; break; }
+    }
+    return TF_OK;
 }
 
 // one (level, warp) stage for pairs [0,B)
@@ -503,14 +526,8 @@ int run_stage(tf_handle* h, int l, int wi, int B, int off0, int off1)
     WarpArgs wa;
     wa.pyr = h->pyr[l]; wa.off0 = off0; wa.off1 = off1; wa.sb = h->sb; wa.ctl = h->ctl; wa.tab = h->tab;
     wa.wx = h->cwx; wa.wy = h->cwy; wa.rho = h->crho; wa.g = g;
-    if (h->profile) {
-        ProfEv* pe = prof_next(h);
-        if (!pe) return fail(h, TF_ERR_HIP, "hipEventCreate failed");
-        pe->level = -4;
-        HIPC(h, hipEventRecord(pe->a, s));
-        launch_warp(h, wa, B, s, h->gxl[l], h->gyl[l]);
-        HIPC(h, hipEventRecord(pe->b, s));
-    } else launch_warp(h, wa, B, s, h->gxl[l], h->gyl[l]);
+    int rc = profiled(h, s, -4, 0, 0, [&] { launch_warp(h, wa, B, s, h->gxl[l], h->gyl[l]); });
+    if (rc) return rc;
     HIPC(h, hipMemsetAsync(h->errs, 0, (size_t)B * h->errstride * sizeof(u64), s));
 
     IterArgs ia;
@@ -519,122 +536,55 @@ int run_stage(tf_handle* h, int l, int wi, int B, int off0, int off1)
     ia.l_t = (float)(P.lambda * P.theta); ia.theta = (float)P.theta; ia.taut = (float)(P.tau / P.theta);
     ia.variant = P.variant; ia.thr_d = thr_d;
     const bool cuda_variant = P.variant == TF_VARIANT_CUDA;      // one loop, no median, stops only after odd iterations
+    const bool median = P.median_filtering > 1 && !cuda_variant;
     MedArgs ma;
     ma.sb = h->sb; ma.ctl = h->ctl; ma.err = h->errs; ma.errstride = h->errstride; ma.thr_q = thr_q; ma.g = g;
 
     const dim3 gm((g.w + 63) / 64, (g.h + 15) / 16, 2 * B);
     ia.B = B;
-    const bool two = cuda_variant || (h->iter_variant >= 2 && (rows_ok(h, g, B) || h->tile2) && (inner % 2 == 0));
-    if (two) {
-        // two iterations per launch; launch index it = 0,2,..,total (the last one can only hold REPLAY blocks)
-        int utog = 0, ptog = 0, utog_prev = 0, ptog_prev = 0, pzero_prev = 0;
-        bool stop = false;
-        int last_active = B;
-        const unsigned seq0 = h->launch_seq;
-        unsigned checked = seq0;
-        for (int it = 0; it <= total && !stop; it += 2) {
-            if (it < total && it % inner == 0 && P.median_filtering > 1 && !cuda_variant) {
-                ma.it = it; ma.utog = utog;
-                ProfEv* pm = h->profile ? prof_next(h) : nullptr;
-                if (pm) { pm->level = -5; HIPC(h, hipEventRecord(pm->a, s)); }
-                if (P.median_filtering == 5) hipLaunchKernelGGL(k_median2<5>, gm, dim3(256), 0, s, ma, total);
-                else hipLaunchKernelGGL(k_median2<3>, gm, dim3(256), 0, s, ma, total);
-                if (pm) HIPC(h, hipEventRecord(pm->b, s));
-                ++utog;
-            }
-            const unsigned q = h->launch_seq++;
-            h->slots_host[q % SLOT_RING] = -1;
-            Iter2Args A2;
-            A2.a = ia;
-            A2.a.host_slot = h->slots_dev + q % SLOT_RING;
-            A2.a.it = it; A2.a.utog = utog; A2.a.ptog = ptog; A2.a.pzero = (wi == 0 && it == 0) ? 1 : 0;
-            A2.utog_prev = utog_prev; A2.ptog_prev = ptog_prev; A2.pzero_prev = pzero_prev; A2.total = total;
-            if (h->profile) {
-                if (h->prof_used == h->prof_pool.size()) {
-                    ProfEv pe;
-                    HIPC(h, hipEventCreate(&pe.a)); HIPC(h, hipEventCreate(&pe.b));
-                    h->prof_pool.push_back(pe);
-                }
-                ProfEv& pe = h->prof_pool[h->prof_used++];
-                pe.level = l; pe.warp = wi; pe.it = it;
-                HIPC(h, hipEventRecord(pe.a, s));
-                launch_iter2(h, A2, B, s, last_active);
-                HIPC(h, hipEventRecord(pe.b, s));
-            } else {
-                launch_iter2(h, A2, B, s, last_active);
-            }
-            ++h->iter_launches;
-            utog_prev = utog; ptog_prev = ptog; pzero_prev = A2.a.pzero;
-            ++utog; ++ptog;
-            while (checked <= q) {
-                int v = h->slots_host[checked % SLOT_RING];
-                if (v < 0) {
-                    if (q - checked < (unsigned)h->lag) break;
-                    const double t0 = now_ms();
-                    while ((v = h->slots_host[checked % SLOT_RING]) < 0) {
-                        if (now_ms() - t0 > 20000.0) return fail(h, TF_ERR_HIP, "tvl1_iter launch %u never reported (GPU hang?)", checked);
-                        if (hipStreamQuery(s) == hipSuccess && h->slots_host[checked % SLOT_RING] < 0)
-                            return fail(h, TF_ERR_HIP, "stream drained but launch %u did not report", checked);
-                    }
-                }
-                ++checked;
-                if (v == 0) { stop = true; break; }
-                last_active = v;
-            }
-        }
-        hipLaunchKernelGGL(k_stage_end2, dim3((B + 255) / 256), dim3(256), 0, s, h->errs, h->errstride, h->ctl, h->iters_dev, B,
-                           total, inner, (P.median_filtering > 1 && !cuda_variant) ? 1 : 0, thr_q, l, wi, h->nlev, P.warps, P.variant, thr_d);
-        return TF_OK;
-    }
-    int utog = 0, ptog = 0;
+    // One or two iterations per launch.  Two: launch index it = 0,2,..,total (the last one can only hold REPLAY blocks), and each launch
+    // is also told the ping-pong state of the one before it.
+    const bool two = two_per_launch(h, cuda_variant, inner);
+    int utog = 0, ptog = 0, utog_prev = 0, ptog_prev = 0, pzero_prev = 0;
     bool stop = false;
-    const unsigned seq0 = h->launch_seq;
-    unsigned checked = seq0;          // launches [seq0, checked) have been read back
-    for (int it = 0; it < total && !stop;) {
-        if (it % inner == 0 && P.median_filtering > 1) {
+    unsigned checked = h->launch_seq;          // this stage's launches before `checked` have been read back
+    for (int it = 0; (two ? it <= total : it < total) && !stop; it += two ? 2 : 1) {
+        if (it < total && it % inner == 0 && median) {
             ma.it = it; ma.utog = utog;
-            if (P.median_filtering == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
-            else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, s, ma);
+            rc = profiled(h, s, -5, 0, 0, [&] {
+                if (two) {
+                    if (P.median_filtering == 5) hipLaunchKernelGGL(k_median2<5>, gm, dim3(256), 0, s, ma, total);
+                    else hipLaunchKernelGGL(k_median2<3>, gm, dim3(256), 0, s, ma, total);
+                } else if (P.median_filtering == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
+                else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, s, ma);
+            });
+            if (rc) return rc;
             ++utog;
         }
         const unsigned q = h->launch_seq++;
         h->slots_host[q % SLOT_RING] = -1;
         ia.host_slot = h->slots_dev + q % SLOT_RING;
         ia.it = it; ia.utog = utog; ia.ptog = ptog; ia.pzero = (wi == 0 && it == 0) ? 1 : 0;
-        if (h->profile) {
-            if (h->prof_used == h->prof_pool.size()) {
-                ProfEv pe;
-                HIPC(h, hipEventCreate(&pe.a)); HIPC(h, hipEventCreate(&pe.b));
-                h->prof_pool.push_back(pe);
-            }
-            ProfEv& pe = h->prof_pool[h->prof_used++];
-            pe.level = l; pe.warp = wi; pe.it = it;
-            HIPC(h, hipEventRecord(pe.a, s));
-            launch_iter(h, ia, B, s);
-            HIPC(h, hipEventRecord(pe.b, s));
-        } else {
-            launch_iter(h, ia, B, s);
-        }
+        rc = profiled(h, s, l, wi, it, [&] {
+            if (!two) { launch_iter(h, ia, B, s); return; }
+            Iter2Args A2;
+            A2.a = ia;
+            A2.utog_prev = utog_prev; A2.ptog_prev = ptog_prev; A2.pzero_prev = pzero_prev; A2.total = total;
+            launch_iter2(h, A2, B, s);
+        });
+        if (rc) return rc;
         ++h->iter_launches;
-        ++utog; ++ptog; ++it;
-        // read back what earlier launches of this stage published: never more than `lag` launches unread
-        while (checked <= q) {
-            int v = h->slots_host[checked % SLOT_RING];
-            if (v < 0) {
-                if (q - checked < (unsigned)h->lag) break;        // not there yet, and we may still run ahead
-                const double t0 = now_ms();
-                while ((v = h->slots_host[checked % SLOT_RING]) < 0) {
-                    if (now_ms() - t0 > 20000.0) return fail(h, TF_ERR_HIP, "tvl1_iter launch %u never reported (GPU hang?)", checked);
-                    if (hipStreamQuery(s) == hipSuccess && h->slots_host[checked % SLOT_RING] < 0)
-                        return fail(h, TF_ERR_HIP, "stream drained but launch %u did not report", checked);
-                }
-            }
-            ++checked;
-            if (v == 0) { stop = true; break; }   // nobody entered that iteration active: the rest would be no-ops
-        }
+        utog_prev = utog; ptog_prev = ptog; pzero_prev = ia.pzero;
+        ++utog; ++ptog;
+        rc = read_reports(h, s, q, &checked, &stop);
+        if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->errs, h->errstride, h->ctl, h->iters_dev, B,
-                       total, inner, P.median_filtering > 1 ? 1 : 0, thr_q, l, wi, h->nlev, P.warps);
+    if (two)
+        hipLaunchKernelGGL(k_stage_end2, dim3((B + 255) / 256), dim3(256), 0, s, h->errs, h->errstride, h->ctl, h->iters_dev, B,
+                           total, inner, median ? 1 : 0, thr_q, l, wi, h->nlev, P.warps, P.variant, thr_d);
+    else
+        hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->errs, h->errstride, h->ctl, h->iters_dev, B,
+                           total, inner, median ? 1 : 0, thr_q, l, wi, h->nlev, P.warps);
     return TF_OK;
 }
 
@@ -833,14 +783,19 @@ void df_gauss3(float sigma, float* k0, float* k1)
     *k0 = (float)(t1 * inv); *k1 = (float)(t0 * inv);
 }
 
+// regions of `size` px along one axis that cover `extent` px when neighbours overlap by a halo of hl on each side (the first region
+// holds `size` px, every further one adds size - 2 hl)
+inline int sor_regions(int extent, int size, int hl)
+{
+    return extent <= size ? 1 : 1 + (extent - size + (size - 2 * hl) - 1) / (size - 2 * hl);
+}
+
 // register-tile SOR (teeflow_sor_rt.hip.h): `sweeps` sweeps per launch on 128 x (R*NB) regions with a halo of hl = 2 * sweeps
 // (hl = 0: the region holds the whole level)
 template <int R, int NB>
 void launch_sor_rt_t(const DfBufs& d, const Geom& g, int B, float omega, int sweeps, int hl, hipStream_t s, int plain_div)
 {
-    constexpr int RW = 128, RH = R * NB;
-    const int nx = g.w <= RW ? 1 : 1 + (g.w - RW + (RW - 2 * hl) - 1) / (RW - 2 * hl);
-    const int ny = g.h <= RH ? 1 : 1 + (g.h - RH + (RH - 2 * hl) - 1) / (RH - 2 * hl);
+    const int nx = sor_regions(g.w, 128, hl), ny = sor_regions(g.h, R * NB, hl);
     hipLaunchKernelGGL((k_df_sor_rt<R, NB>), dim3(nx, ny, B), dim3(64 * NB), 0, s, d, g, omega, sweeps, hl, plain_div);
 }
 // returns the number of sweeps it ran (all of `left` when the level fits one region).
@@ -850,11 +805,7 @@ void launch_sor_rt_t(const DfBufs& d, const Geom& g, int B, float omega, int swe
 // long as they all fit one round of resident blocks.  (64 pairs @512^2 are unaffected; single pair 27.3 -> see DESIGN.md.)
 int launch_sor_rt(tf_handle* h, const DfBufs& d, const Geom& g, int B, float omega, int left, int fuse, hipStream_t s)
 {
-    auto tiles = [&](int RH, int hl) {
-        const int nx = g.w <= 128 ? 1 : 1 + (g.w - 128 + (128 - 2 * hl) - 1) / (128 - 2 * hl);
-        const int ny = g.h <= RH ? 1 : 1 + (g.h - RH + (RH - 2 * hl) - 1) / (RH - 2 * hl);
-        return nx * ny;
-    };
+    auto tiles = [&](int RH, int hl) { return sor_regions(g.w, 128, hl) * sor_regions(g.h, RH, hl); };
     int shape = h->sor_rt_shape;
     if (shape == 3 && g.w <= 62 && g.h <= 128) {
         // a level this narrow fills at most half a wave: two bands per wave (k_df_sor_rt<.., HALF>), all sweeps in one launch
@@ -887,13 +838,12 @@ int sor_coop_pairs(const tf_handle* h, const Geom& g, int B, int S, int* nx_, in
     *rows_ = 64;
     if (!h->sor_coop || h->coop_disabled || !h->coop_flags || h->sor_rt_shape != 3 || 64 - 2 * hl < 8 || 3 * hl > 64) return 0;
     if (h->coop_occ16 < 1) return 0;                        // the runtime does not promise a resident 1024-thread block per CU: no co-resident form
-    const int nx = g.w <= 128 ? 1 : 1 + (g.w - 128 + (128 - 2 * hl) - 1) / (128 - 2 * hl);
-    const int ny = g.h <= 64 ? 1 : 1 + (g.h - 64 + (64 - 2 * hl) - 1) / (64 - 2 * hl);
+    const int nx = sor_regions(g.w, 128, hl), ny = sor_regions(g.h, 64, hl);
     const int share = h->coop_share < h->coop_flag_lines / 2 ? h->coop_share : h->coop_flag_lines / 2;
     if (nx * ny < 2 || nx * ny > share) return 0;
     // few pairs: 128 x 64 regions would leave most CUs idle for the whole fixed-point iteration.  Like the tiled form (launch_sor_rt) the
     // co-resident one then takes 128 x 32 regions: 512-thread blocks, two per CU, ~2.5 x the blocks and half the sweep time per block
-    const int ny32 = g.h <= 32 ? 1 : 1 + (g.h - 32 + (32 - 2 * hl) - 1) / (32 - 2 * hl);
+    const int ny32 = sor_regions(g.h, 32, hl);
     // (a region waits for the 8 regions around it, so its halo must not reach past their cores: hl <= core, i.e. 3 hl <= 32 -- S <= 5;
     // the 64-row regions satisfy 3 hl <= 64 for every S the knob allows)
     if (h->sor_coop != 2 && 32 - 2 * hl >= 8 && 3 * hl <= 32 && nx * ny * B < h->num_cus && nx * ny32 * B <= 2 * h->num_cus) {
@@ -914,7 +864,7 @@ int sor_coop_pairs(const tf_handle* h, const Geom& g, int B, int S, int* nx_, in
 }
 
 // one cv::VariationalRefinement::calcUV for pairs [0,B) on level geometry g: W[cur] -> (avg, Iz) = W + dW
-void df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const Geom& g, int cur, int B, hipStream_t s)
+int df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const Geom& g, int cur, int B, hipStream_t s)
 {
     DfBufs d = h->df;
     const DfConst c = df_consts(h->DP);
@@ -931,18 +881,6 @@ void df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const
             hipLaunchKernelGGL(k_df_smooth, gr, bl, 0, s, d, cur, g);
         }
         int left = h->DP.sor_iterations;
-        auto prof_begin = [&]() -> ProfEv* {
-            ProfEv* pe = nullptr;
-            if (h->profile) {
-                if (h->prof_used == h->prof_pool.size()) {
-                    ProfEv ne;
-                    if (hipEventCreate(&ne.a) == hipSuccess && hipEventCreate(&ne.b) == hipSuccess) h->prof_pool.push_back(ne);
-                }
-                if (h->prof_used < h->prof_pool.size()) { pe = &h->prof_pool[h->prof_used++]; (void)hipEventRecord(pe->a, s); }
-            }
-            ++h->iter_launches;
-            return pe;
-        };
         int cnx = 0, cny = 0, crows = 64;
         const int S = h->sor_coop_s < 1 ? 1 : (h->sor_coop_s > 8 ? 8 : h->sor_coop_s);
         const int cpairs = h->sor_rt && fuse > 0 && left > S ? sor_coop_pairs(h, g, B, S, &cnx, &cny, &crows) : 0;
@@ -955,29 +893,32 @@ void df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const
             }
             for (int b0 = 0; b0 < B; b0 += cpairs) {
                 const int nb = B - b0 < cpairs ? B - b0 : cpairs;
-                ProfEv* pe = prof_begin();
-                if (crows == 32)
-                    hipLaunchKernelGGL((k_df_sor_rt_coop<4, 8>), dim3(cnx, cny, nb), dim3(512), 0, s, d, g, c.omega, left, S, h->sor_plain_div | (h->coop_test_mute ? 2 : 0), b0,
-                                       h->coop_flags, h->coop_epoch, h->coop_flags + (size_t)h->coop_flag_lines * 32);
-                else
-                    hipLaunchKernelGGL((k_df_sor_rt_coop<4, 16>), dim3(cnx, cny, nb), dim3(1024), 0, s, d, g, c.omega, left, S, h->sor_plain_div | (h->coop_test_mute ? 2 : 0), b0,
-                                       h->coop_flags, h->coop_epoch, h->coop_flags + (size_t)h->coop_flag_lines * 32);
+                const int rc = profiled(h, s, 0, 0, 0, [&] {
+                    if (crows == 32)
+                        hipLaunchKernelGGL((k_df_sor_rt_coop<4, 8>), dim3(cnx, cny, nb), dim3(512), 0, s, d, g, c.omega, left, S, h->sor_plain_div | (h->coop_test_mute ? 2 : 0), b0,
+                                           h->coop_flags, h->coop_epoch, h->coop_flags + (size_t)h->coop_flag_lines * 32);
+                    else
+                        hipLaunchKernelGGL((k_df_sor_rt_coop<4, 16>), dim3(cnx, cny, nb), dim3(1024), 0, s, d, g, c.omega, left, S, h->sor_plain_div | (h->coop_test_mute ? 2 : 0), b0,
+                                           h->coop_flags, h->coop_epoch, h->coop_flags + (size_t)h->coop_flag_lines * 32);
+                });
+                if (rc) return rc;
+                ++h->iter_launches;
                 h->coop_epoch += (unsigned)phases;
                 ++h->coop_launches;
                 h->df_sor_bytes += (double)left * g.w * g.h * nb * 40.0;
                 h->df_sor_px += (double)g.w * g.h * nb;
-                if (pe) (void)hipEventRecord(pe->b, s);
             }
             h->coop_used = true;
             if (phases & 1) { std::swap(d.du, d.du2); std::swap(d.dv, d.dv2); }
             left = 0;
         }
         while (h->sor_rt && fuse > 0 && left > 0) {
-            ProfEv* pe = prof_begin();
-            const int n = launch_sor_rt(h, d, g, B, c.omega, left, fuse > 8 ? 8 : fuse, s);
+            int n = 0;
+            const int rc = profiled(h, s, 0, 0, 0, [&] { n = launch_sor_rt(h, d, g, B, c.omega, left, fuse > 8 ? 8 : fuse, s); });
+            if (rc) return rc;
+            ++h->iter_launches;
             h->df_sor_bytes += (double)n * g.w * g.h * B * 40.0;
             h->df_sor_px += (double)g.w * g.h * B;
-            if (pe) (void)hipEventRecord(pe->b, s);
             std::swap(d.du, d.du2); std::swap(d.dv, d.dv2);
             left -= n;
         }
@@ -989,6 +930,7 @@ void df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const
         }
     }
     hipLaunchKernelGGL(k_df_sum, gr, bl, 0, s, d, cur, g);
+    return TF_OK;
 }
 
 int df_solve_resident(tf_handle* h, const uint8_t* dframes, int F, int B, int off0, int off1, float scale, float* dflow)
@@ -1013,7 +955,8 @@ int df_solve_resident(tf_handle* h, const uint8_t* dframes, int F, int B, int of
     const float mul = 1.0f / h->DP.downscale_factor;
     for (int l = L; l >= 0; --l) {
         const Geom g = h->dlv[l];
-        df_refine_level(h, h->dpyr_base + h->dpyr_off[l], off0, off1, g, cur, B, s);
+        const int rc = df_refine_level(h, h->dpyr_base + h->dpyr_off[l], off0, off1, g, cur, B, s);
+        if (rc) return rc;
         if (l == 0) break;
         const Geom gd = h->dlv[l - 1];
         const double sx = 1.0 / ((double)gd.w / g.w), sy = 1.0 / ((double)gd.h / g.h);
@@ -1041,20 +984,23 @@ enum Mode { MODE_PAIRS, MODE_SEQ };
 // where a call's buffers live: bit 0 = the frames are device memory, bit 1 = the flow destination is
 enum { W_HOST = 0, W_IN_DEV = 1, W_OUT_DEV = 2, W_DEV = 3 };
 
+// the arguments of a solve call (calc_entry, submit_entry: every call reaches calc_common and queue_submit through one of them)
+int check_call(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, const float* flow_out)
+{
+    if (!in0 || (mode == MODE_PAIRS && !in1) || !flow_out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
+    if (H < 1 || W < 1 || n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", n_pairs, H, W);
+    if ((long long)H * W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
+    return h->P.algo == TF_ALGO_DEEPFLOW ? df_validate(h, h->DP) : validate_params(h, h->P);
+}
+
 // common driver: device==true -> in/out pointers are device memory
 int calc_common(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
                 float* flow_out, int device, tf_stats* st)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (!in0 || (mode == MODE_PAIRS && !in1) || !flow_out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
-    if (H < 1 || W < 1 || n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", n_pairs, H, W);
-    if ((long long)H * W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
-    int rc = deep ? df_validate(h, h->DP) : validate_params(h, h->P);
-    if (rc) return rc;
     HIPC(h, hipSetDevice(h->dev));
     const double t0 = now_ms();
-    rc = deep ? df_ensure_alloc(h, H, W, n_pairs) : ensure_alloc(h, H, W, n_pairs);
+    int rc = deep ? df_ensure_alloc(h, H, W, n_pairs) : ensure_alloc(h, H, W, n_pairs);
     if (rc) return rc;
     if (deep) h->cap = h->dcap;
     const size_t fpx = (size_t)H * W * (h->src_f32 ? 4 : 1);   // BYTES per frame (the flow offsets below use npx)
@@ -1073,12 +1019,7 @@ int calc_common(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1,
         if (hipPointerGetAttributes(&pa, flow_out) == hipSuccess && pa.type == hipMemoryTypeHost) overlap = true;
         else (void)hipGetLastError();
     }
-    int step = h->cap;
-    if (overlap && n_pairs >= 48 && h->sub_batches > 1) {
-        step = (n_pairs + h->sub_batches - 1) / h->sub_batches;
-        if (step < 16) step = 16;
-        if (step > h->cap) step = h->cap;
-    }
+    const int step = h->cap;
     if (overlap && !h->copy_stream) HIPC(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     if (overlap && !h->cev[0])
         for (auto& e : h->cev) HIPC(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1196,12 +1137,12 @@ __global__ void k_probe_wait(int* flag, int* seen, long long ticks)
 }
 __global__ void k_probe_set(int* flag) { __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// 1 = b's kernel ran while a's was running, 0 = it did not (shared hardware queue), -1 = the probe itself failed
-int streams_concurrent(hipStream_t a, hipStream_t b)
+// 1 = b's kernel ran while a's was running, 0 = it did not (shared hardware queue), -1 = the probe itself failed.
+// d: the caller's device buffer of 2 ints (flag, seen); null fails the probe
+int streams_concurrent(hipStream_t a, hipStream_t b, int* d)
 {
     if (a == b) return 0;
-    int* d = nullptr;
-    if (hipMalloc(&d, 2 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    if (!d) return -1;
     int seen = -1;
     hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(int), a);
     if (e == hipSuccess) e = hipStreamSynchronize(a);
@@ -1213,7 +1154,6 @@ int streams_concurrent(hipStream_t a, hipStream_t b)
         if (e == hipSuccess) e = hipStreamSynchronize(a);
         if (e == hipSuccess) e = hipMemcpy(&seen, d + 1, sizeof(int), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d);
     if (e != hipSuccess) { (void)hipGetLastError(); return -1; }
     return seen == 1 ? 1 : 0;
 }
@@ -1221,10 +1161,10 @@ int streams_concurrent(hipStream_t a, hipStream_t b)
 // Give handle `t` a solve stream that runs beside every stream in `others` (new streams are tried until one does; the rejected ones are
 // kept until the search is over, so that the next one lands elsewhere, then destroyed).  Returns true when t's stream is concurrent
 // with all of them; false leaves the last stream tried (work still runs, serialised with one of the others).
-bool give_concurrent_stream(tf_handle* t, const std::vector<hipStream_t>& others, int* retries)
+bool give_concurrent_stream(tf_handle* t, const std::vector<hipStream_t>& others, int* probe, int* retries)
 {
     auto ok_with_all = [&](hipStream_t s) {
-        for (hipStream_t o : others) if (streams_concurrent(o, s) == 0) return false;
+        for (hipStream_t o : others) if (streams_concurrent(o, s, probe) == 0) return false;
         return true;
     };
     if (ok_with_all(t->own_stream)) return true;
@@ -1399,6 +1339,10 @@ int pool_ensure(tf_handle* h)
         if (idle) pool_destroy(h);
     }
     if (h->pool) return TF_OK;
+    // the probes' device buffer (streams_concurrent): if it cannot be had, every probe fails, which rejects no stream
+    HIPC(h, hipSetDevice(h->dev));
+    int* probe = nullptr;
+    if (hipMalloc(&probe, 2 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); probe = nullptr; }
     LanePool* pool = new LanePool();
     for (int k = 0; k < want; ++k) {
         tf_handle* t = nullptr;
@@ -1406,12 +1350,13 @@ int pool_ensure(tf_handle* h)
         if (rc) {
             for (tf_handle* l : pool->lanes) tf_destroy(l);
             delete pool;
+            if (probe) (void)hipFree(probe);
             return fail(h, rc, "creating queue lane %d failed: %s", k + 1, tf_last_error(nullptr));
         }
         t->is_lane = true; t->owner = h;
         std::vector<hipStream_t> others;
         for (tf_handle* o : pool->lanes) others.push_back(o->own_stream);
-        if (!give_concurrent_stream(t, others, &h->stream_retries)) h->streams_serialised |= 1;
+        if (!give_concurrent_stream(t, others, probe, &h->stream_retries)) h->streams_serialised |= 1;
         pool->lanes.push_back(t);
     }
     // A lane's copy-out (pinned host destinations: D2H of one unit under the next unit's solve) must run beside EVERY lane's solve, its own
@@ -1424,7 +1369,7 @@ int pool_ensure(tf_handle* h)
             hipStream_t cs = nullptr;
             if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); break; }
             ok = true;
-            for (tf_handle* o : pool->lanes) if (streams_concurrent(o->own_stream, cs) == 0) { ok = false; break; }
+            for (tf_handle* o : pool->lanes) if (streams_concurrent(o->own_stream, cs, probe) == 0) { ok = false; break; }
             if (ok || k == 4) {
                 l->copy_stream = cs;
                 for (auto& e : l->cev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError();
@@ -1436,6 +1381,7 @@ int pool_ensure(tf_handle* h)
         }
         for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
     }
+    if (probe) (void)hipFree(probe);
     h->pool = pool;
     pool->coop.resize(pool->lanes.size());
     for (int k = 0; k < want; ++k) pool->th.emplace_back(lane_worker, h, pool, k);
@@ -1448,10 +1394,7 @@ int queue_submit(tf_handle* h, QJob* j, Mode mode, const uint8_t* in0, const uin
                  bool balance, int parts = 0)
 {
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
-    int rc = deep ? df_validate(h, h->DP) : validate_params(h, h->P);
-    if (rc) return rc;
-    if ((long long)H * W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
-    rc = pool_ensure(h);
+    const int rc = pool_ensure(h);
     if (rc) return rc;
     j->mode = mode; j->in0 = in0; j->in1 = in1; j->n_pairs = n_pairs; j->H = H; j->W = W; j->scale = scale; j->out = flow_out; j->device = device;
     j->src_f32 = h->src_f32; j->P = h->P; j->DP = h->DP; j->knobs = static_cast<const TfKnobs&>(*h);
@@ -1515,14 +1458,15 @@ int calc_entry(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, 
                float* flow_out, int device, tf_stats* st)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    const bool can_queue = !h->is_lane && queue_lane_count(h) > 0 && in0 && flow_out && (mode != MODE_PAIRS || in1) && H >= 1 && W >= 1 &&
-                           n_pairs >= 1 && h->stream == h->own_stream;
+    int rc = check_call(h, mode, in0, in1, n_pairs, H, W, flow_out);
+    if (rc) return rc;
+    const bool can_queue = !h->is_lane && queue_lane_count(h) > 0 && h->stream == h->own_stream;
     bool busy = false;
     if (can_queue && h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); busy = h->pool->outstanding > 0; }
     const int parts = !busy && n_pairs <= sub_batch_pairs(h) ? split_count(h, n_pairs) : 0;
     if (!can_queue || parts == 1) return solve_alone(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
     QJob j;
-    int rc = queue_submit(h, &j, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, !busy, parts);
+    rc = queue_submit(h, &j, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, !busy, parts);
     if (rc) return rc;
     return queue_finish(h, &j, st);
 }
@@ -1533,13 +1477,12 @@ int submit_entry(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1
 {
     struct Guard { void* p; ~Guard() { if (p) (void)hipFree(p); } } guard{owned_dev};
     if (!h || !ticket) return TF_ERR_INVALID_ARG;
-    if (!in0 || (mode == MODE_PAIRS && !in1) || !flow_out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
-    if (H < 1 || W < 1 || n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", n_pairs, H, W);
+    int rc = check_call(h, mode, in0, in1, n_pairs, H, W, flow_out);
+    if (rc) return rc;
     if (h->is_lane || h->stream != h->own_stream) return fail(h, TF_ERR_UNSUPPORTED, "tf_submit_* needs the handle's own stream");
     guard.p = nullptr;                                       // from here on the job owns it
     QJob* j = new QJob();
     j->owned_dev = owned_dev;                                // (freed with the job, whatever happens below)
-    int rc;
     if (queue_lane_count(h) < 1) {                           // "queue_lanes" = 0: no lanes, the job is done when the call returns
         tf_stats st;
         rc = solve_alone(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, &st);
@@ -1770,20 +1713,12 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
         h->iter_variant = value;
     }
     else if (n == "strip_blocks") h->strip_blocks = value > 0 ? value : 2048;
-    else if (n == "lag") h->lag = value < 0 ? DEFAULT_LAG : (value < SLOT_RING / 2 ? value : SLOT_RING / 2);   // 0 = wait for every launch's report (it is published at the launch's start); unread slots must never be overwritten
     else if (n == "min_rows_work") h->min_rows_work = value;
-    else if (n == "force_ry") h->force_ry = value;
-    else if (n == "adaptive_strips") h->adaptive_strips = value;
-    else if (n == "dynamic_strips") h->dynamic_strips = value;
-    else if (n == "slots") h->slots_override = value;
     else if (n == "lane_slots_pct") h->lane_slots_pct = value;
-    else if (n == "tile_max_w") h->tile_max_w = value;
     else if (n == "sor_rt") h->sor_rt = value ? 1 : 0;
     else if (n == "sor_rt_shape") h->sor_rt_shape = value;
     else if (n == "sor_plain_div") h->sor_plain_div = value ? 1 : 0;
-    else if (n == "tile2") h->tile2 = value;
     else if (n == "max_strip_width") h->max_strip_width = value < 4 ? 4 : (value > 2048 ? 2048 : value);
-    else if (n == "sub_batches") h->sub_batches = value < 1 ? 1 : value;
     else if (n == "lanes") h->lanes = value < 1 ? 1 : (value > 8 ? 8 : value);
     else if (n == "queue_lanes") h->queue_lanes = value;          // -1 = per algorithm (3 DualTVL1, `lanes` DeepFlow), 0 = no lanes: the handle alone
     else if (n == "queue_unit") h->queue_unit = value < 0 ? 0 : value;
@@ -2629,10 +2564,10 @@ TF_API int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int 
     int rc = coop_ensure(h);
     if (rc) { h->df = saved; return rc; }
     if (e == hipSuccess) {
-        df_refine_level(h, fr, 0, 1, g, 0, 1, h->stream);
+        rc = df_refine_level(h, fr, 0, 1, g, 0, 1, h->stream);
         e = hipStreamSynchronize(h->stream);
         bool aborted = false;
-        if (e == hipSuccess) rc = coop_aborted(h, &aborted);
+        if (e == hipSuccess && !rc) rc = coop_aborted(h, &aborted);
         if (!rc && aborted) rc = fail(h, TF_ERR_HIP, "deepflow refine: the co-resident SOR launch gave up waiting for its neighbours");
     }
     if (e != hipSuccess) rc = fail(h, TF_ERR_HIP, "deepflow refine: %s", hipGetErrorString(e));
@@ -2693,7 +2628,7 @@ TF_API int tf_dbg_iterate(tf_handle* h, const float* I1wx, const float* I1wy, co
     }
     ia.ctl = ctl; ia.err = errs; ia.errstride = nsteps + 1; ia.thr_q = -1.0; ia.g = g; ia.host_slot = nullptr; ia.B = 1;
     ia.l_t = (float)(h->P.lambda * h->P.theta); ia.theta = (float)h->P.theta; ia.taut = (float)(h->P.tau / h->P.theta);
-    const bool two = h->iter_variant == 2 && (rows_ok(h, g, 1) || h->tile2) && nsteps % 2 == 0;
+    const bool two = two_per_launch(h, false, nsteps);     // (ia.variant = 0: these launches run the CPU form whatever the handle's variant)
     int launches = 0;
     if (two) {
         for (int it = 0; it < nsteps; it += 2, ++launches) {

@@ -167,12 +167,13 @@ class DenseFlow:
         _lib.check(self._L.tf_set_profile(self._h, int(level)), self._h, "tf_set_profile")
 
     def set_tuning(self, name, value):
-        """Implementation knobs (never change results): iter_variant, strip_blocks, probe_cadence."""
+        """Implementation knobs (never change results), e.g. iter_variant, min_rows_work, warp_margin, lanes, sor_coop; the full list is
+        tf_set_tuning's in include/teeflow.h.  An unknown name raises."""
         _lib.check(self._L.tf_set_tuning(self._h, name.encode(), int(value)), self._h, "tf_set_tuning")
 
     def counter(self, name):
         """Debug counters of the engine (tf_dbg_counter): coop_launches, coop_aborts, coop_disabled, coop_rearms, coop_cooldown, coop_occ16, coop_occ8,
-        queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, experimental."""
+        queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
     def _finish(self, st):

@@ -226,6 +226,14 @@ def test_error_behaviour(engine):
     assert engine.getLambda() == 0.15
 
 
+@pytest.mark.parametrize("knob", ["force_ry", "adaptive_strips", "dynamic_strips", "slots", "tile_max_w", "tile2", "sub_batches", "lag"])
+def test_retired_tuning_knobs_are_refused(engine, knob):
+    """Knobs whose launch paths were retired are unknown names now: tf_set_tuning refuses them instead of ignoring them."""
+    from tee_optical_flow_amd import OpticalFlowCalculationError
+    with pytest.raises(OpticalFlowCalculationError, match=f"unknown tuning knob {knob}"):
+        engine.set_tuning(knob, 1)
+
+
 def test_device_frame_conditioning_matches_reference_fixture(engine):
     """Row a1/f4: img2uint8(rgb2gray(frame)) on the device == the reference's own output (fixture) and the host restatement."""
     import os

@@ -120,17 +120,18 @@ struct tf_handle : TfKnobs {
     hipStream_t copy_stream = nullptr;           // D2H of finished sub-batches overlaps the next solve (pinned destinations)
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   // solve done [2], copy done [2]
     uint8_t* st_u8 = nullptr; size_t st_u8_bytes = 0;
-    int src_f32 = 0;                       // this call's frames are float32 in [0,1] (tf_calc_pairs_f32): 4 bytes per pixel
     float* st_flow = nullptr; size_t st_flow_bytes = 0;
     hipEvent_t ev[4] = {};
     // profiling of tvl1_iter launches
-    std::deque<ProfEv> prof_pool; size_t prof_used = 0;      // deque: records keep their address while the pool grows
-    // results of the last call
-    std::vector<int> last_iters; int last_pairs = 0, last_nlev = 0, last_warps = 0;
-    // per-call accumulators
-    unsigned long long iter_launches = 0;
-    double df_sor_bytes = 0;     // DeepFlow: algorithmic bytes of the SOR launches of the current call (40 B per pixel-sweep)
-    double df_sor_px = 0;        // DeepFlow: pixels x pairs summed over the SOR launches (a launch's compulsory traffic is 40 B per pixel: 8 planes in, 2 out)
+    std::deque<ProfEv> prof_pool;                            // deque: records keep their address while the pool grows
+    std::vector<int> last_iters;                             // tf_get_iters: the last call's iteration counts
+    // per-call tallies (calc_common starts them at zero; the repeat of an aborted sub-batch restores them)
+    struct Tally {
+        unsigned long long iter_launches = 0;
+        double df_sor_bytes = 0;     // DeepFlow: algorithmic bytes of the SOR launches of the current call (40 B per pixel-sweep)
+        double df_sor_px = 0;        // DeepFlow: pixels x pairs summed over the SOR launches (a launch's compulsory traffic is 40 B per pixel: 8 planes in, 2 out)
+        size_t prof_used = 0;        // records of prof_pool in use
+    } tally;
     // ---- DeepFlow (algo == TF_ALGO_DEEPFLOW) ----
     tf_deepflow_params DP = {};
     int dnlev = 0, dH = 0, dW = 0, dcap = 0;
@@ -156,7 +157,7 @@ struct tf_handle : TfKnobs {
     float* wsum = nullptr; size_t wsum_cap = 0;
     float* wbg = nullptr; size_t wbg_cap = 0;
     std::map<size_t, int> slots_cache;      // resident k_iter2_rows blocks on the device, by (LDS bytes, waves per block)
-    int coop_share = 0;          // CUs (= resident 1024-thread blocks) this handle may fill with such a launch; set per call (solve_alone, lane_worker)
+    int coop_share = 0;          // CUs (= resident 1024-thread blocks) this handle may fill with such a launch; set per call (start_call, lane_worker)
     bool coop_disabled = false;  // a launch of this handle gave up waiting (foreign work on the GPU): tiled form until the back-off has run out
     int coop_backoff = 0;        // tiled solves (sub-batches) to sit out before the co-resident form is tried again; doubles with every abort
     int coop_cooldown = 0;       // ... of which this many are left
@@ -172,7 +173,6 @@ struct tf_handle : TfKnobs {
     // RCCL: one communicator rank per handle, its own stream, a small ring of completion events
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 0;
     hipStream_t comm_stream = nullptr; hipEvent_t comm_ev[8] = {}; hipEvent_t comm_ready = nullptr; unsigned comm_tickets = 0;
-    double warp_ms = 0, median_ms = 0;   // profiling: summed launch durations per stage of the last call
     // ---- engine lanes that pull whole sub-batches from a queue (calc_entry, tf_submit_*) ----
     int queue_lanes = -1;        // -1 = per algorithm (3 DualTVL1, `lanes` DeepFlow); 0 = never: the handle solves every call alone, sub-batch after sub-batch
     int queue_unit = 0;          // pairs per queue unit (0 = equal units of at most max_batch pairs, a multiple of the lane count of them)
@@ -188,21 +188,39 @@ struct tf_handle : TfKnobs {
 };
 
 
+// ---- one solve call, as it travels from a C ABI entry point to the engine that solves it (or to the lanes, unit by unit) ----------
+enum Mode { MODE_PAIRS, MODE_SEQ };
+// where a call's buffers live: bit 0 = the frames are device memory, bit 1 = the flow destination is
+enum { W_HOST = 0, W_IN_DEV = 1, W_OUT_DEV = 2, W_DEV = 3 };
+// Pair b is frames (in0[b], in1[b]) (MODE_PAIRS) or (in0[b], in0[b+1]) (MODE_SEQ: in1 unused); its flow is out[b], H x W x 2 floats.
+struct Call {
+    Mode mode = MODE_PAIRS; const uint8_t* in0 = nullptr; const uint8_t* in1 = nullptr; int n_pairs = 0, H = 0, W = 0; float scale = 1.f;
+    float* out = nullptr;
+    int where = W_HOST;          // W_* bits
+    bool f32 = false;            // the frames are float32 in [0,1] (CV_32F) instead of uint8
+    size_t frame_bytes() const { return (size_t)H * W * (f32 ? 4 : 1); }
+    Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
+    {
+        Call p = *this; const size_t off = (size_t)c0 * frame_bytes();
+        p.in0 += off; if (in1) p.in1 += off; p.out += (size_t)c0 * H * W * 2; p.n_pairs = nb;
+        return p;
+    }
+};
+
 // ---- lanes that pull whole sub-batches from a queue ---------------------------------------------------------------------------
-// A call larger than one sub-batch (and every tf_submit_* job) becomes a QJob: it is cut into units of at most `unit` pairs, and the
-// handle's lanes -- engines of their own: handle, stream, buffers, host thread -- take one unit at a time, oldest job first.  A lane
-// that has finished a unit starts the next one at once, whichever job it belongs to, so one sub-batch's tail (few pairs still
-// iterating, the fine pyramid levels done) runs under other sub-batches' full launches.  An idle call of one sub-batch becomes a job of
-// `lanes` contiguous units, solved side by side.
+// Every call becomes a QJob (start_call), the record of its results whether the handle solves it alone or not.  A call larger than one
+// sub-batch (and every tf_submit_* job) is cut into units of at most `unit` pairs, and the handle's lanes -- engines of their own:
+// handle, stream, buffers, host thread -- take one unit at a time, oldest job first.  A lane that has finished a unit starts the next
+// one at once, whichever job it belongs to, so one sub-batch's tail (few pairs still iterating, the fine pyramid levels done) runs under
+// other sub-batches' full launches.  An idle call of one sub-batch becomes a job of `lanes` contiguous units, solved side by side.
 struct QJob {
-    int mode = 0; const uint8_t* in0 = nullptr; const uint8_t* in1 = nullptr; int n_pairs = 0, H = 0, W = 0; float scale = 1.f;
-    float* out = nullptr; int device = 0; int src_f32 = 0;      // device: W_* bits
+    Call call;
     tf_params P; tf_deepflow_params DP; TfKnobs knobs;      // the engine's settings when the job was queued
     int slots_pct = 100;                                    // the lanes size their strips for this per cent of the resident blocks
     int unit = 0, n_units = 0, next = 0, done = 0, fail_unit = -1;
     int rc = TF_OK; std::string err;
-    tf_stats st; int merged = 0;
-    std::vector<int> iters; size_t per_pair = 0; int nlev = 0, warps = 0;
+    tf_stats st = {};                                       // the units' stats merged (queue_finish adds what is the call's)
+    std::vector<int> iters; size_t per_pair = 0; int nlev = 0, warps = 0;   // iters: tf_get_iters order, each unit writes its own slice
     double t0 = 0;
     void* owned_dev = nullptr;                              // device memory that lives as long as the job (tf_submit_seq_rgb: the conditioned frames)
     bool finished = false;
@@ -476,14 +494,14 @@ template <class Launch>
 int profiled(tf_handle* h, hipStream_t s, int level, int warp, int it, Launch&& launch)
 {
     if (!h->profile) { launch(); return TF_OK; }
-    if (h->prof_used == h->prof_pool.size()) {
+    if (h->tally.prof_used == h->prof_pool.size()) {
         ProfEv pe;
         hipError_t e = hipEventCreate(&pe.a);
         if (e == hipSuccess && (e = hipEventCreate(&pe.b)) != hipSuccess) (void)hipEventDestroy(pe.a);
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, TF_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(e)); }
         h->prof_pool.push_back(pe);
     }
-    ProfEv& pe = h->prof_pool[h->prof_used++];
+    ProfEv& pe = h->prof_pool[h->tally.prof_used++];
     pe.level = level; pe.warp = warp; pe.it = it;
     HIPC(h, hipEventRecord(pe.a, s));
     launch();
@@ -573,7 +591,7 @@ int run_stage(tf_handle* h, int l, int wi, int B, int off0, int off1)
             launch_iter2(h, A2, B, s);
         });
         if (rc) return rc;
-        ++h->iter_launches;
+        ++h->tally.iter_launches;
         utog_prev = utog; ptog_prev = ptog; pzero_prev = ia.pzero;
         ++utog; ++ptog;
         rc = read_reports(h, s, q, &checked, &stop);
@@ -588,13 +606,13 @@ int run_stage(tf_handle* h, int l, int wi, int B, int off0, int off1)
     return TF_OK;
 }
 
-// Solve B pairs whose u8 frames are in device memory: frames[F][H][W], pair b = (off0+b, off1+b).
-int solve_resident(tf_handle* h, const uint8_t* dframes, int F, int B, int off0, int off1, float scale, float* dflow)
+// Solve B pairs whose frames are in device memory: frames[F][H][W] (uint8, or float32 in [0,1] when f32), pair b = (off0+b, off1+b).
+int solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, float* dflow)
 {
     const tf_params& P = h->P;
     hipStream_t s = h->stream;
     const Geom g0 = h->lv[0];
-    if (h->src_f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->pyr[0], g0, 1);
+    if (f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->pyr[0], g0, 1);
     else hipLaunchKernelGGL(k_u8_to_f32, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, dframes, h->pyr[0], g0);
     for (int l = 1; l < h->nlev; ++l) {
         const double sc = 1.0 / P.scale_step;   // resize(src, Size(), fx, fy): scale = 1/fx
@@ -902,11 +920,11 @@ int df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const 
                                            h->coop_flags, h->coop_epoch, h->coop_flags + (size_t)h->coop_flag_lines * 32);
                 });
                 if (rc) return rc;
-                ++h->iter_launches;
+                ++h->tally.iter_launches;
                 h->coop_epoch += (unsigned)phases;
                 ++h->coop_launches;
-                h->df_sor_bytes += (double)left * g.w * g.h * nb * 40.0;
-                h->df_sor_px += (double)g.w * g.h * nb;
+                h->tally.df_sor_bytes += (double)left * g.w * g.h * nb * 40.0;
+                h->tally.df_sor_px += (double)g.w * g.h * nb;
             }
             h->coop_used = true;
             if (phases & 1) { std::swap(d.du, d.du2); std::swap(d.dv, d.dv2); }
@@ -916,16 +934,16 @@ int df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const 
             int n = 0;
             const int rc = profiled(h, s, 0, 0, 0, [&] { n = launch_sor_rt(h, d, g, B, c.omega, left, fuse > 8 ? 8 : fuse, s); });
             if (rc) return rc;
-            ++h->iter_launches;
-            h->df_sor_bytes += (double)n * g.w * g.h * B * 40.0;
-            h->df_sor_px += (double)g.w * g.h * B;
+            ++h->tally.iter_launches;
+            h->tally.df_sor_bytes += (double)n * g.w * g.h * B * 40.0;
+            h->tally.df_sor_px += (double)g.w * g.h * B;
             std::swap(d.du, d.du2); std::swap(d.dv, d.dv2);
             left -= n;
         }
         while (left > 0) {     // sor_fuse = 0 (or sor_rt = 0): one colour per launch, in place -- the plain form the others are tested against
             hipLaunchKernelGGL(k_df_sor, gsor, bl, 0, s, d, g, 0, c.omega);
             hipLaunchKernelGGL(k_df_sor, gsor, bl, 0, s, d, g, 1, c.omega);
-            h->df_sor_bytes += (double)g.w * g.h * B * 40.0;
+            h->tally.df_sor_bytes += (double)g.w * g.h * B * 40.0;
             --left;
         }
     }
@@ -933,14 +951,14 @@ int df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const 
     return TF_OK;
 }
 
-int df_solve_resident(tf_handle* h, const uint8_t* dframes, int F, int B, int off0, int off1, float scale, float* dflow)
+int df_solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, float* dflow)
 {
     hipStream_t s = h->stream;
     const Geom g0 = h->dlv[0];
     float k0, k1;
     df_gauss3(h->DP.sigma, &k0, &k1);
     // convertTo(CV_32F) without a factor: uint8 frames keep 0..255, float frames (a saliency map in [0,1]) are taken as they are
-    if (h->src_f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->dtmp, g0, 0);
+    if (f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->dtmp, g0, 0);
     else hipLaunchKernelGGL(k_u8_to_f32, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, dframes, h->dtmp, g0);
     hipLaunchKernelGGL(k_df_blur, grid64x4(g0, F), dim3(256), 0, s, h->dtmp, h->dpyr_base + h->dpyr_off[0], g0, k0, k1);
     for (int l = 1; l < h->dnlev; ++l) {
@@ -980,43 +998,40 @@ double df_account_bytes(const tf_handle* h)
     return tb;
 }
 
-enum Mode { MODE_PAIRS, MODE_SEQ };
-// where a call's buffers live: bit 0 = the frames are device memory, bit 1 = the flow destination is
-enum { W_HOST = 0, W_IN_DEV = 1, W_OUT_DEV = 2, W_DEV = 3 };
-
-// the arguments of a solve call (calc_entry, submit_entry: every call reaches calc_common and queue_submit through one of them)
-int check_call(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, const float* flow_out)
+// the arguments of a solve call: every entry point runs this before any work (calc_entry, submit_entry; the RGB and saliency routes
+// on their host input, before conditioning it)
+int check_call(tf_handle* h, const Call& c)
 {
-    if (!in0 || (mode == MODE_PAIRS && !in1) || !flow_out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
-    if (H < 1 || W < 1 || n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", n_pairs, H, W);
-    if ((long long)H * W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
+    if (!h) return TF_ERR_INVALID_ARG;
+    if (c.mode == MODE_SEQ && c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", c.n_pairs + 1);
+    if (!c.in0 || (c.mode == MODE_PAIRS && !c.in1) || !c.out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
+    if (c.H < 1 || c.W < 1 || c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", c.n_pairs, c.H, c.W);
+    if ((long long)c.H * c.W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
     return h->P.algo == TF_ALGO_DEEPFLOW ? df_validate(h, h->DP) : validate_params(h, h->P);
 }
 
-// common driver: device==true -> in/out pointers are device memory
-int calc_common(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
-                float* flow_out, int device, tf_stats* st)
+// The handle solves call c, sub-batch after sub-batch.  DualTVL1 writes the executed iteration counts to `iters` (tf_get_iters order).
+// *st gets the solve's measurements; what describes the whole call (n_pairs, nscales_used, warps, ms_total) is the job's (queue_finish).
+int calc_common(tf_handle* h, const Call& c, int* iters, tf_stats* st)
 {
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
     HIPC(h, hipSetDevice(h->dev));
-    const double t0 = now_ms();
-    int rc = deep ? df_ensure_alloc(h, H, W, n_pairs) : ensure_alloc(h, H, W, n_pairs);
+    int rc = deep ? df_ensure_alloc(h, c.H, c.W, c.n_pairs) : ensure_alloc(h, c.H, c.W, c.n_pairs);
     if (rc) return rc;
     if (deep) h->cap = h->dcap;
-    const size_t fpx = (size_t)H * W * (h->src_f32 ? 4 : 1);   // BYTES per frame (the flow offsets below use npx)
-    const size_t npx = (size_t)H * W;
-    h->last_iters.assign(deep ? 0 : (size_t)n_pairs * h->nlev * h->P.warps * 2, 0);
-    h->last_pairs = n_pairs; h->last_nlev = deep ? h->dnlev : h->nlev; h->last_warps = deep ? 0 : h->P.warps;
-    h->iter_launches = 0; h->prof_used = 0; h->df_sor_bytes = 0; h->df_sor_px = 0;
+    const size_t fpx = c.frame_bytes();                      // BYTES per frame (the flow offsets below use npx)
+    const size_t npx = (size_t)c.H * c.W;
+    const size_t per_pair = deep ? 0 : (size_t)h->nlev * h->P.warps * 2;
+    h->tally = {};
     float ms_h2d = 0, ms_dev = 0, ms_d2h = 0;
     // Host destinations that are pinned (tf_host_alloc, hipHostMalloc, hipHostRegister) take the overlapped path: each
     // sub-batch is solved into one half of a double staging buffer and copied out on a second stream while the next one
     // is being solved.  Pageable destinations keep the simple in-order path.
     bool overlap = false;
-    const bool in_dev = device & W_IN_DEV, out_dev = device & W_OUT_DEV;
+    const bool in_dev = c.where & W_IN_DEV, out_dev = c.where & W_OUT_DEV;
     if (!out_dev) {
         hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, flow_out) == hipSuccess && pa.type == hipMemoryTypeHost) overlap = true;
+        if (hipPointerGetAttributes(&pa, c.out) == hipSuccess && pa.type == hipMemoryTypeHost) overlap = true;
         else (void)hipGetLastError();
     }
     const int step = h->cap;
@@ -1030,47 +1045,44 @@ int calc_common(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1,
     }
     int kb = 0;
     bool repeating = false;
-    for (int c0 = 0; c0 < n_pairs; c0 += step, ++kb) {
-        const int nb = n_pairs - c0 < step ? n_pairs - c0 : step;
+    for (int c0 = 0; c0 < c.n_pairs; c0 += step, ++kb) {
+        const int nb = c.n_pairs - c0 < step ? c.n_pairs - c0 : step;
+        const Call p = c.part(c0, nb);
         const uint8_t* dfr; int F, off0, off1;
         float* dfl;
         HIPC(h, hipEventRecord(h->ev[0], h->stream));
-        if (mode == MODE_SEQ) {
+        if (c.mode == MODE_SEQ) {
             F = nb + 1; off0 = 0; off1 = 1;
-            if (in_dev) dfr = in0 + (size_t)c0 * fpx;
-            else { HIPC(h, hipMemcpyAsync(h->st_u8, in0 + (size_t)c0 * fpx, (size_t)F * fpx, hipMemcpyHostToDevice, h->stream)); dfr = h->st_u8; }
+            if (in_dev) dfr = p.in0;
+            else { HIPC(h, hipMemcpyAsync(h->st_u8, p.in0, (size_t)F * fpx, hipMemcpyHostToDevice, h->stream)); dfr = h->st_u8; }
         } else {
             F = 2 * nb; off0 = 0; off1 = nb;
-            if (in_dev && n_pairs <= h->cap && in1 == in0 + (size_t)n_pairs * fpx) dfr = in0;   // already [I0s|I1s] contiguous
+            if (in_dev && c.n_pairs <= h->cap && c.in1 == c.in0 + (size_t)c.n_pairs * fpx) dfr = c.in0;   // already [I0s|I1s] contiguous
             else {
                 if (in_dev) { rc = ensure_staging(h, 2 * (size_t)h->cap * fpx, 0); if (rc) return rc; }
                 const hipMemcpyKind k = in_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-                HIPC(h, hipMemcpyAsync(h->st_u8, in0 + (size_t)c0 * fpx, (size_t)nb * fpx, k, h->stream));
-                HIPC(h, hipMemcpyAsync(h->st_u8 + (size_t)nb * fpx, in1 + (size_t)c0 * fpx, (size_t)nb * fpx, k, h->stream));
+                HIPC(h, hipMemcpyAsync(h->st_u8, p.in0, (size_t)nb * fpx, k, h->stream));
+                HIPC(h, hipMemcpyAsync(h->st_u8 + (size_t)nb * fpx, p.in1, (size_t)nb * fpx, k, h->stream));
                 dfr = h->st_u8;
             }
         }
-        dfl = out_dev ? flow_out + (size_t)c0 * npx * 2 : h->st_flow + (overlap ? (size_t)(kb & 1) * flow_half : 0);
+        dfl = out_dev ? p.out : h->st_flow + (overlap ? (size_t)(kb & 1) * flow_half : 0);
         if (overlap && kb >= 2) HIPC(h, hipStreamWaitEvent(h->stream, h->cev[2 + (kb & 1)], 0));   // that half's last copy-out
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
-        // what a repeat of this sub-batch must not count twice (an aborted co-resident attempt is void)
-        const unsigned long long snap_launches = h->iter_launches;
-        const double snap_bytes = h->df_sor_bytes, snap_px = h->df_sor_px;
-        const size_t snap_prof = h->prof_used;
-        rc = deep ? df_solve_resident(h, dfr, F, nb, off0, off1, scale, dfl)
-                  : solve_resident(h, dfr, F, nb, off0, off1, scale, dfl);
+        const tf_handle::Tally snap = h->tally;              // what a repeat of this sub-batch must not count twice (an aborted co-resident attempt is void)
+        rc = deep ? df_solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl)
+                  : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl);
         if (rc) return rc;
         HIPC(h, hipEventRecord(h->ev[2], h->stream));
         if (overlap) {
             HIPC(h, hipEventRecord(h->cev[kb & 1], h->stream));
             HIPC(h, hipStreamWaitEvent(h->copy_stream, h->cev[kb & 1], 0));
-            HIPC(h, hipMemcpyAsync(flow_out + (size_t)c0 * npx * 2, dfl, (size_t)nb * npx * 2 * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
+            HIPC(h, hipMemcpyAsync(p.out, dfl, (size_t)nb * npx * 2 * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
             HIPC(h, hipEventRecord(h->cev[2 + (kb & 1)], h->copy_stream));
         } else if (!out_dev)
-            HIPC(h, hipMemcpyAsync(flow_out + (size_t)c0 * npx * 2, h->st_flow, (size_t)nb * npx * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, hipMemcpyAsync(p.out, h->st_flow, (size_t)nb * npx * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         if (!deep)
-            HIPC(h, hipMemcpyAsync(h->last_iters.data() + (size_t)c0 * h->nlev * h->P.warps * 2, h->iters_dev,
-                                   (size_t)nb * h->nlev * h->P.warps * 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, hipMemcpyAsync(iters + (size_t)c0 * per_pair, h->iters_dev, (size_t)nb * per_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipEventRecord(h->ev[3], h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
         if (deep) {
@@ -1079,7 +1091,7 @@ int calc_common(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1,
             if (rc) return rc;
             if (aborted) {                                       // solve this sub-batch again, tiled (what was copied out is overwritten)
                 if (overlap) HIPC(h, hipStreamSynchronize(h->copy_stream));
-                h->iter_launches = snap_launches; h->df_sor_bytes = snap_bytes; h->df_sor_px = snap_px; h->prof_used = snap_prof;
+                h->tally = snap;
                 c0 -= step; --kb;
                 repeating = true;
                 continue;
@@ -1095,28 +1107,24 @@ int calc_common(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1,
     if (overlap) HIPC(h, hipStreamSynchronize(h->copy_stream));
     if (st) {
         memset(st, 0, sizeof *st);
-        st->n_pairs = n_pairs; st->nscales_used = deep ? h->dnlev : h->nlev; st->warps = deep ? 0 : h->P.warps;
         st->ms_h2d = ms_h2d; st->ms_device = ms_dev; st->ms_d2h = ms_d2h;
-        st->iter_launches = h->iter_launches;
-        if (deep) { st->total_bytes = df_account_bytes(h) * n_pairs; st->iter_bytes = h->df_sor_bytes; st->iter_pair_steps = (unsigned long long)h->df_sor_px; }
-        for (int b = 0; !deep && b < n_pairs; ++b)
-            account_bytes(h, h->last_iters.data() + (size_t)b * h->nlev * h->P.warps * 2, &st->iter_bytes, &st->total_bytes,
-                          &st->inner_iters_total, &st->outer_iters_total);
+        st->iter_launches = h->tally.iter_launches;
+        if (deep) { st->total_bytes = df_account_bytes(h) * c.n_pairs; st->iter_bytes = h->tally.df_sor_bytes; st->iter_pair_steps = (unsigned long long)h->tally.df_sor_px; }
+        for (int b = 0; !deep && b < c.n_pairs; ++b)
+            account_bytes(h, iters + (size_t)b * per_pair, &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
         if (!deep) st->iter_pair_steps = st->inner_iters_total;     // DeepFlow: pixels x pairs summed over the SOR launches (set above)
-        double ims = 0;
-        h->warp_ms = h->median_ms = 0;
-        for (size_t i = 0; i < h->prof_used; ++i) {
+        double ims = 0, warp_ms = 0, median_ms = 0;
+        for (size_t i = 0; i < h->tally.prof_used; ++i) {
             float t = 0;
             ProfEv& pe = h->prof_pool[i];
             HIPC(h, hipEventElapsedTime(&t, pe.a, pe.b));
             pe.ms = t;
-            if (pe.level == -4) h->warp_ms += t;
-            else if (pe.level == -5) h->median_ms += t;
+            if (pe.level == -4) warp_ms += t;
+            else if (pe.level == -5) median_ms += t;
             else ims += t;
         }
         st->iter_ms = ims;
-        st->ms_warp = h->warp_ms; st->ms_median = h->median_ms; st->ms_misc = 0; st->ms_sched = 0;
-        st->ms_total = now_ms() - t0;
+        st->ms_warp = warp_ms; st->ms_median = median_ms;
     }
     return TF_OK;
 }
@@ -1200,25 +1208,15 @@ void merge_stats(tf_stats* st, const tf_stats& sb)
 
 // Whatever went wrong, nothing of the failed call may still be in flight when the caller gets its buffers back (a D2H
 // copy into flow_out on the copy stream, kernels writing the caller's device buffer): drain every stream of the handle.
-int calc_common_guarded(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
-                        float* flow_out, int device, tf_stats* st)
+int calc_common_guarded(tf_handle* h, const Call& c, int* iters, tf_stats* st)
 {
-    const int rc = calc_common(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
-    if (rc != TF_OK && h) {
+    const int rc = calc_common(h, c, iters, st);
+    if (rc != TF_OK) {
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
         (void)hipGetLastError();
     }
     return rc;
-}
-
-// The handle solves the call alone, sub-batch after sub-batch (calc_common cuts by capacity); DeepFlow claims the device's CUs per call
-int solve_alone(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
-                float* flow_out, int device, tf_stats* st)
-{
-    CoopClaim claim(h->P.algo == TF_ALGO_DEEPFLOW ? h->dev : -1);
-    h->coop_share = claim.ok ? h->num_cus : 0;
-    return calc_common_guarded(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
 }
 
 
@@ -1273,17 +1271,14 @@ void lane_worker(tf_handle* owner, LanePool* pool, int k)
         }
         tf_stats us; memset(&us, 0, sizeof us);
         int rc = TF_OK;
-        const int c0 = u * j->unit, nb = j->n_pairs - c0 < j->unit ? j->n_pairs - c0 : j->unit;
+        const int c0 = u * j->unit, nb = j->call.n_pairs - c0 < j->unit ? j->call.n_pairs - c0 : j->unit;
         if (!skip) {
-            const size_t npx = (size_t)j->H * j->W, fpx = npx * (j->src_f32 ? 4 : 1);
-            lane->P = j->P; lane->DP = j->DP; lane->src_f32 = j->src_f32; lane->slots_pct = j->slots_pct; lane->coop_share = share;
+            lane->P = j->P; lane->DP = j->DP; lane->slots_pct = j->slots_pct; lane->coop_share = share;
             if (lane->sor_coop_arm != j->knobs.sor_coop_arm) { lane->coop_disabled = false; lane->coop_backoff = lane->coop_cooldown = 0; }
             static_cast<TfKnobs&>(*lane) = j->knobs;
             if (lane->coop_flags) coop_query_occupancy(lane);        // asks again only if the test overrides have changed
             if (u == j->fail_unit) rc = fail(lane, TF_ERR_HIP, "injected failure (queue_test_fail_unit)");
-            else rc = calc_common_guarded(lane, (Mode)j->mode, j->in0 + (size_t)c0 * fpx, j->in1 ? j->in1 + (size_t)c0 * fpx : nullptr, nb, j->H, j->W,
-                                          j->scale, j->out + (size_t)c0 * npx * 2, j->device, &us);
-            lane->src_f32 = 0;
+            else rc = calc_common_guarded(lane, j->call.part(c0, nb), j->iters.data() + (size_t)c0 * j->per_pair, &us);
         }
         bool last;
         {
@@ -1295,11 +1290,8 @@ void lane_worker(tf_handle* owner, LanePool* pool, int k)
                     char where[96]; snprintf(where, sizeof where, "sub-batch %d (pairs %d..%d): ", u, c0, c0 + nb - 1);
                     j->err = std::string(where) + lane->err;
                 }
-            } else if (!skip) {
-                if (!j->merged++) { const double t = j->st.ms_total; j->st = us; j->st.ms_total = t; } else merge_stats(&j->st, us);
-                if (j->per_pair && lane->last_iters.size() == (size_t)nb * j->per_pair)
-                    memcpy(j->iters.data() + (size_t)c0 * j->per_pair, lane->last_iters.data(), (size_t)nb * j->per_pair * sizeof(int));
-            }
+            } else if (!skip)
+                merge_stats(&j->st, us);
             pool->coop[k] = coop_counters(lane);
             last = ++j->done == j->n_units;
             // every lane that worked for this job has drained its streams (a solve is host-synchronous, a failed one drains in
@@ -1388,16 +1380,15 @@ int pool_ensure(tf_handle* h)
     return TF_OK;
 }
 
-// fills the job from the handle's current settings and hands it to the lanes.  parts > 0: an idle call of one sub-batch, cut in that many
-// near-equal contiguous units whose strips are sized for every resident block (neither "queue_unit" nor "lane_slots_pct" applies)
-int queue_submit(tf_handle* h, QJob* j, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale, float* flow_out, int device,
-                 bool balance, int parts = 0)
+// hands job j (its call, iteration counts and stats set up by start_call) to the lanes, with the handle's current settings.  parts > 0: an
+// idle call of one sub-batch, cut in that many near-equal contiguous units whose strips are sized for every resident block (neither
+// "queue_unit" nor "lane_slots_pct" applies)
+int queue_submit(tf_handle* h, QJob* j, bool balance, int parts)
 {
-    const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
     const int rc = pool_ensure(h);
     if (rc) return rc;
-    j->mode = mode; j->in0 = in0; j->in1 = in1; j->n_pairs = n_pairs; j->H = H; j->W = W; j->scale = scale; j->out = flow_out; j->device = device;
-    j->src_f32 = h->src_f32; j->P = h->P; j->DP = h->DP; j->knobs = static_cast<const TfKnobs&>(*h);
+    const int n_pairs = j->call.n_pairs;
+    j->P = h->P; j->DP = h->DP; j->knobs = static_cast<const TfKnobs&>(*h);
     j->slots_pct = parts > 0 ? 100 : h->lane_slots_pct;
     j->unit = parts > 0 ? (n_pairs + parts - 1) / parts : queue_unit_pairs(h);
     if (parts <= 0 && h->queue_unit <= 0 && balance) {
@@ -1411,15 +1402,6 @@ int queue_submit(tf_handle* h, QJob* j, Mode mode, const uint8_t* in0, const uin
     }   // (a submitted job's last units run beside the next job's first: whole sub-batches, which are the more efficient units)
     j->n_units = (n_pairs + j->unit - 1) / j->unit;
     j->fail_unit = h->queue_test_fail_unit; h->queue_test_fail_unit = -1;
-    memset(&j->st, 0, sizeof j->st);
-    if (deep) {
-        std::vector<Geom> lv(DF_MAXLEV);
-        j->nlev = df_levels(h->DP, H, W, lv.data()); j->warps = 0; j->per_pair = 0;
-    } else {
-        Geom lv[MAXLEV];
-        j->nlev = compute_levels(h->P, H, W, lv); j->warps = h->P.warps; j->per_pair = (size_t)j->nlev * j->warps * 2;
-    }
-    j->iters.assign((size_t)n_pairs * j->per_pair, 0);
     j->t0 = now_ms();
     {
         std::lock_guard<std::mutex> lk(h->pool->m);
@@ -1431,6 +1413,39 @@ int queue_submit(tf_handle* h, QJob* j, Mode mode, const uint8_t* in0, const uin
     return TF_OK;
 }
 
+// The one route from an entry point to a solve: call c (checked) becomes job j.  An idle call of at most one sub-batch is split in
+// split_count() contiguous units that the lanes solve side by side, or solved by this handle alone when that count is 1.  A larger one --
+// or any call while tf_submit_* jobs are in flight, and every submitted one -- goes to the queue: whole sub-batches, taken by the lanes as
+// they come free.  An external stream, or "queue_lanes" = 0, has the handle solve every call alone.  A job solved alone, or one that could
+// not be queued, is finished on return and its rc is returned; a queued one is the lanes' until queue_finish has waited for it.
+int start_call(tf_handle* h, const Call& c, QJob* j, bool submitted)
+{
+    const bool can_queue = !h->is_lane && queue_lane_count(h) > 0 && h->stream == h->own_stream;
+    bool busy = submitted;                                   // (a submitted job is cut like a call behind others: balance = false, parts = 0)
+    if (can_queue && h->pool && !busy) { std::lock_guard<std::mutex> lk(h->pool->m); busy = h->pool->outstanding > 0; }
+    const int parts = !busy && c.n_pairs <= sub_batch_pairs(h) ? split_count(h, c.n_pairs) : 0;
+    const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
+    Geom lv[DF_MAXLEV];                                      // (the pyramid calc_common will build: stats, tf_get_iters)
+    j->call = c;
+    j->nlev = deep ? df_levels(h->DP, c.H, c.W, lv) : compute_levels(h->P, c.H, c.W, lv);
+    j->warps = deep ? 0 : h->P.warps;                        // (DeepFlow has no iteration counts)
+    j->per_pair = (size_t)j->nlev * j->warps * 2;
+    j->iters.assign((size_t)c.n_pairs * j->per_pair, 0);
+    if (can_queue && parts != 1) {
+        const int rc = queue_submit(h, j, !busy, parts);
+        if (rc == TF_OK) return TF_OK;                       // the lanes' job from here on
+        j->rc = rc;
+    } else {                                                 // alone, sub-batch after sub-batch; DeepFlow claims the device's CUs per call
+        CoopClaim claim(deep ? h->dev : -1);
+        h->coop_share = claim.ok ? h->num_cus : 0;
+        j->t0 = now_ms();
+        j->rc = calc_common_guarded(h, c, j->iters.data(), &j->st);
+    }
+    if (j->rc != TF_OK) j->err = h->err;
+    j->finished = true;
+    return j->rc;
+}
+
 // waits for the job and moves its results to where a synchronous call leaves them (tf_get_iters, tf_last_error, *st)
 int queue_finish(tf_handle* h, QJob* j, tf_stats* st)
 {
@@ -1439,59 +1454,40 @@ int queue_finish(tf_handle* h, QJob* j, tf_stats* st)
         h->pool->cv_done.wait(lk, [&] { return j->finished; });
     }
     h->last_iters = std::move(j->iters);
-    h->last_pairs = j->n_pairs; h->last_nlev = j->nlev; h->last_warps = j->warps;
     if (j->rc != TF_OK) { h->err = j->err; return j->rc; }
     if (st) {
         *st = j->st;
-        st->n_pairs = j->n_pairs; st->nscales_used = j->nlev; st->warps = j->warps;
+        st->n_pairs = j->call.n_pairs; st->nscales_used = j->nlev; st->warps = j->warps;
         st->ms_total = now_ms() - j->t0;
     }
     return TF_OK;
 }
 
-// Entry used by the C ABI.  An idle call of at most one sub-batch is split in split_count() contiguous units that the lanes solve side
-// by side, or solved by this handle alone when that count is 1.  A larger one -- or any call while tf_submit_* jobs are in flight -- goes
-// to the queue: whole sub-batches, taken by the lanes as they come free.  Either way the call returns when every lane has finished its
-// last unit of it (a failed unit stops the job's remaining units from starting; the units already running complete, so nothing of the
-// call is in flight when it returns).  An external stream, or "queue_lanes" = 0, has the handle solve every call alone.
-int calc_entry(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale,
-               float* flow_out, int device, tf_stats* st)
+// Entry used by the C ABI: start_call + queue_finish.  A failed unit stops the job's remaining units from starting; the units already
+// running complete, so nothing of the call is in flight when it returns.
+int calc_entry(tf_handle* h, const Call& c, tf_stats* st)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    int rc = check_call(h, mode, in0, in1, n_pairs, H, W, flow_out);
+    const int rc = check_call(h, c);
     if (rc) return rc;
-    const bool can_queue = !h->is_lane && queue_lane_count(h) > 0 && h->stream == h->own_stream;
-    bool busy = false;
-    if (can_queue && h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); busy = h->pool->outstanding > 0; }
-    const int parts = !busy && n_pairs <= sub_batch_pairs(h) ? split_count(h, n_pairs) : 0;
-    if (!can_queue || parts == 1) return solve_alone(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, st);
     QJob j;
-    rc = queue_submit(h, &j, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, !busy, parts);
-    if (rc) return rc;
+    start_call(h, c, &j, false);
     return queue_finish(h, &j, st);
 }
 
-// tf_submit_*: the same job, not waited for.  Returns a ticket for tf_wait.
-int submit_entry(tf_handle* h, Mode mode, const uint8_t* in0, const uint8_t* in1, int n_pairs, int H, int W, float scale, float* flow_out, int device, int* ticket,
-                 void* owned_dev = nullptr)
+// tf_submit_*: the same job, not waited for.  Returns a ticket for tf_wait; a job that failed already (solved alone: "queue_lanes" = 0)
+// returns its error and no ticket.
+int submit_entry(tf_handle* h, const Call& c, int* ticket, void* owned_dev = nullptr)
 {
     struct Guard { void* p; ~Guard() { if (p) (void)hipFree(p); } } guard{owned_dev};
-    if (!h || !ticket) return TF_ERR_INVALID_ARG;
-    int rc = check_call(h, mode, in0, in1, n_pairs, H, W, flow_out);
+    int rc = check_call(h, c);
     if (rc) return rc;
+    if (!ticket) return TF_ERR_INVALID_ARG;
     if (h->is_lane || h->stream != h->own_stream) return fail(h, TF_ERR_UNSUPPORTED, "tf_submit_* needs the handle's own stream");
     guard.p = nullptr;                                       // from here on the job owns it
     QJob* j = new QJob();
     j->owned_dev = owned_dev;                                // (freed with the job, whatever happens below)
-    if (queue_lane_count(h) < 1) {                           // "queue_lanes" = 0: no lanes, the job is done when the call returns
-        tf_stats st;
-        rc = solve_alone(h, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, &st);
-        if (rc) { delete j; return rc; }
-        j->st = st; j->n_pairs = n_pairs; j->nlev = h->last_nlev; j->warps = h->last_warps; j->iters = h->last_iters; j->t0 = now_ms() - st.ms_total; j->finished = true;
-    } else {
-        rc = queue_submit(h, j, mode, in0, in1, n_pairs, H, W, scale, flow_out, device, false);
-        if (rc) { delete j; return rc; }
-    }
+    rc = start_call(h, c, j, true);
+    if (rc) { delete j; return rc; }
     *ticket = h->next_ticket++;
     h->tickets[*ticket] = j;
     return TF_OK;
@@ -1789,7 +1785,7 @@ TF_API int tf_dbg_launch_profile(tf_handle* h, int* level, int* warp, int* it, f
 {
     if (!h) return -1;
     int n = 0;
-    for (size_t i = 0; i < h->prof_used; ++i) {
+    for (size_t i = 0; i < h->tally.prof_used; ++i) {
         const ProfEv& pe = h->prof_pool[i];
         if (pe.level < 0) continue;                        // warp / median records
         if (n < max_n) {
@@ -1812,81 +1808,51 @@ TF_API int tf_set_profile(tf_handle* h, int level)
 
 TF_API int tf_calc_pair(tf_handle* h, const uint8_t* I0, const uint8_t* I1, int H, int W, float* flow_out, tf_stats* st)
 {
-    return calc_entry(h, MODE_PAIRS, I0, I1, 1, H, W, 1.0f, flow_out, W_HOST, st);
+    return calc_entry(h, {MODE_PAIRS, I0, I1, 1, H, W, 1.0f, flow_out, W_HOST}, st);
 }
-
 TF_API int tf_calc_pairs(tf_handle* h, const uint8_t* I0s, const uint8_t* I1s, int B, int H, int W, float* flow_out, tf_stats* st)
 {
-    return calc_entry(h, MODE_PAIRS, I0s, I1s, B, H, W, 1.0f, flow_out, W_HOST, st);
+    return calc_entry(h, {MODE_PAIRS, I0s, I1s, B, H, W, 1.0f, flow_out, W_HOST}, st);
 }
-
 // CV_32FC1 frames (values in [0,1]; cv2 multiplies them by 255 when it builds level 0)
 TF_API int tf_calc_pairs_f32(tf_handle* h, const float* I0s, const float* I1s, int B, int H, int W, float* flow_out, tf_stats* st)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    h->src_f32 = 1;
-    const int rc = calc_entry(h, MODE_PAIRS, (const uint8_t*)I0s, (const uint8_t*)I1s, B, H, W, 1.0f, flow_out, W_HOST, st);
-    h->src_f32 = 0;
-    return rc;
+    return calc_entry(h, {MODE_PAIRS, (const uint8_t*)I0s, (const uint8_t*)I1s, B, H, W, 1.0f, flow_out, W_HOST, true}, st);
 }
-
 TF_API int tf_calc_pair_f32(tf_handle* h, const float* I0, const float* I1, int H, int W, float* flow_out, tf_stats* st)
 {
     return tf_calc_pairs_f32(h, I0, I1, 1, H, W, flow_out, st);
 }
-
 TF_API int tf_calc_seq(tf_handle* h, const uint8_t* frames, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
 {
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
-    return calc_entry(h, MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, st);
+    return calc_entry(h, {MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST}, st);
 }
-
 TF_API int tf_calc_pairs_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s, int B, int H, int W, float scale,
                                 float* dflow_out, tf_stats* st)
 {
-    return calc_entry(h, MODE_PAIRS, dI0s, dI1s, B, H, W, scale, dflow_out, W_DEV, st);
+    return calc_entry(h, {MODE_PAIRS, dI0s, dI1s, B, H, W, scale, dflow_out, W_DEV}, st);
 }
-
 TF_API int tf_calc_seq_device(tf_handle* h, const uint8_t* dframes, int N, int H, int W, float scale, float* dflow_out, tf_stats* st)
 {
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
-    return calc_entry(h, MODE_SEQ, dframes, nullptr, N - 1, H, W, scale, dflow_out, W_DEV, st);
+    return calc_entry(h, {MODE_SEQ, dframes, nullptr, N - 1, H, W, scale, dflow_out, W_DEV}, st);
 }
 
 // ---- asynchronous forms: the job is queued on the handle's lanes and the call returns; tf_wait collects it ----------------------
 TF_API int tf_submit_pairs_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s, int B, int H, int W, float scale, float* dflow_out, int* ticket)
 {
-    return submit_entry(h, MODE_PAIRS, dI0s, dI1s, B, H, W, scale, dflow_out, W_DEV, ticket);
+    return submit_entry(h, {MODE_PAIRS, dI0s, dI1s, B, H, W, scale, dflow_out, W_DEV}, ticket);
 }
 TF_API int tf_submit_seq_device(tf_handle* h, const uint8_t* dframes, int N, int H, int W, float scale, float* dflow_out, int* ticket)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
-    return submit_entry(h, MODE_SEQ, dframes, nullptr, N - 1, H, W, scale, dflow_out, W_DEV, ticket);
+    return submit_entry(h, {MODE_SEQ, dframes, nullptr, N - 1, H, W, scale, dflow_out, W_DEV}, ticket);
 }
 TF_API int tf_submit_pairs(tf_handle* h, const uint8_t* I0s, const uint8_t* I1s, int B, int H, int W, float* flow_out, int* ticket)
 {
-    return submit_entry(h, MODE_PAIRS, I0s, I1s, B, H, W, 1.0f, flow_out, W_HOST, ticket);
+    return submit_entry(h, {MODE_PAIRS, I0s, I1s, B, H, W, 1.0f, flow_out, W_HOST}, ticket);
 }
 TF_API int tf_submit_seq(tf_handle* h, const uint8_t* frames, int N, int H, int W, float scale, float* flow_out, int* ticket)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
-    return submit_entry(h, MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, ticket);
-}
-namespace { int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t** dgray_out, uint8_t* own); }
-// tf_calc_seq_rgb without waiting: the frames are conditioned now (on the handle's stream, into a buffer the job owns), the solve is queued
-TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
-{
-    if (!h || !rgb || !flow_out || !ticket || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t* own = nullptr;
-    HIPC(h, hipMalloc(&own, (size_t)N * H * W));
-    uint8_t* dgray = nullptr;
-    int rc = condition_to_device(h, rgb, N, H, W, &dgray, own);
-    if (rc) { (void)hipFree(own); return rc; }
-    return submit_entry(h, MODE_SEQ, own, nullptr, N - 1, H, W, scale, flow_out, W_IN_DEV, ticket, own);
+    return submit_entry(h, {MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST}, ticket);
 }
 
 TF_API int tf_wait(tf_handle* h, int ticket, tf_stats* st)
@@ -1959,13 +1925,31 @@ TF_API int tf_condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, i
 
 TF_API int tf_calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
 {
-    if (!h || !rgb || !flow_out || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
+    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST};
+    int rc = check_call(h, c);
+    if (rc) return rc;
     uint8_t* dgray = nullptr;
-    int rc = condition_to_device(h, rgb, N, H, W, &dgray);
+    rc = condition_to_device(h, rgb, N, H, W, &dgray);
     if (rc) return rc;
     // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
-    return calc_entry(h, MODE_SEQ, dgray, nullptr, N - 1, H, W, scale, flow_out, W_IN_DEV, st);
+    c.in0 = dgray; c.where = W_IN_DEV;
+    return calc_entry(h, c, st);
+}
+// tf_calc_seq_rgb without waiting: the frames are conditioned now (on the handle's stream, into a buffer the job owns), the solve is queued
+TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
+{
+    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST};
+    int rc = check_call(h, c);
+    if (rc) return rc;
+    if (!ticket) return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    uint8_t* own = nullptr;
+    HIPC(h, hipMalloc(&own, (size_t)N * H * W));
+    uint8_t* dgray = nullptr;
+    rc = condition_to_device(h, rgb, N, H, W, &dgray, own);
+    if (rc) { (void)hipFree(own); return rc; }
+    c.in0 = own; c.where = W_IN_DEV;
+    return submit_entry(h, c, ticket, own);
 }
 
 namespace {
@@ -2029,16 +2013,17 @@ int saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, in
 
 int calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, float scale, float* flow_out, tf_stats* st)
 {
-    if (!h || !frames || !flow_out || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    if (!h) return TF_ERR_INVALID_ARG;
     if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
-    if (N < 2) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", N);
-    void* dsal = nullptr;
-    int rc = saliency_to_device(h, frames, N, H, W, channels, f32, &dsal);
+    // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are)
+    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, f32};
+    int rc = check_call(h, c);
     if (rc) return rc;
-    h->src_f32 = f32 ? 1 : 0;                            // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are)
-    rc = calc_entry(h, MODE_SEQ, (const uint8_t*)dsal, nullptr, N - 1, H, W, scale, flow_out, W_IN_DEV, st);
-    h->src_f32 = 0;
-    return rc;
+    void* dsal = nullptr;
+    rc = saliency_to_device(h, frames, N, H, W, channels, f32, &dsal);
+    if (rc) return rc;
+    c.in0 = (const uint8_t*)dsal; c.where = W_IN_DEV;
+    return calc_entry(h, c, st);
 }
 }  // namespace
 

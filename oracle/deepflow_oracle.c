@@ -14,7 +14,9 @@
  *
  * What is restated:
  *   OpticalFlowDeepFlow::calc : convertTo(CV_32F) (values stay 0..255); GaussianBlur(3x3, sigma 0.6, REFLECT_101);
- *       pyramid size_{l+1} = (int)(size_l*0.95f + 0.5f) while both sides > 25 (resize INTER_LINEAR to that size);
+ *       pyramid size_{l+1} = (int)(size_l*0.95f + 0.5f) while both sides > 25 (resize INTER_LINEAR to that size), at most
+ *       DFO_MAX_LEVELS levels: 200 downscales, upstream's `maxLayers` (200) AS RECALLED, NOT PINNED against OpenCV -- only a size rule
+ *       with a fixed point above min_size (64^2 with min_size 5 stays 10x10) or a very deep pyramid reaches it;
  *       W = 0 at the coarsest level; per level VariationalRefinement with alpha 4*1, delta 0.5/3, gamma 5/3,
  *       5 fixed-point iterations x 25 SOR sweeps, omega 1.6; W = resize(W, next size) * (1/0.95f).
  *   VariationalRefinement::calcUV : warp I1 by W (remap INTER_LINEAR, 1/32-px fixed point, BORDER_CONSTANT 0);
@@ -35,6 +37,9 @@
 #include <string.h>
 
 #define ORC_API __attribute__((visibility("default")))
+
+/* pyramid depth cap (see the header); the HIP engine's DF_MAXLEV is the same number */
+#define DFO_MAX_LEVELS 201
 
 typedef struct {
     float sigma; int min_size; float downscale_factor; int fixed_point_iterations; int sor_iterations;
@@ -299,6 +304,8 @@ ORC_API void dfo_variational_refine(const dfo_params* P, float alpha, float delt
     free(buf);
 }
 
+ORC_API int dfo_max_levels(void) { return DFO_MAX_LEVELS; }
+
 /* pyramid sizes of OpticalFlowDeepFlow::buildPyramid; returns the number of levels (<= cap) */
 ORC_API int dfo_pyramid_sizes(const dfo_params* P, int W, int H, int* ws, int* hs, int cap)
 {
@@ -317,9 +324,8 @@ ORC_API int dfo_pyramid_sizes(const dfo_params* P, int W, int H, int* ws, int* h
  * flow float32 [H][W][2].  Returns the number of pyramid levels. */
 static int deepflow_core(const dfo_params* P, const float* f0, const float* f1, int H, int W, float* flow)
 {
-    enum { CAP = 256 };
-    int ws[CAP], hs[CAP];
-    const int L = dfo_pyramid_sizes(P, W, H, ws, hs, CAP);
+    int ws[DFO_MAX_LEVELS], hs[DFO_MAX_LEVELS];
+    const int L = dfo_pyramid_sizes(P, W, H, ws, hs, DFO_MAX_LEVELS);
     float** p0 = (float**)calloc((size_t)L, sizeof(float*));
     float** p1 = (float**)calloc((size_t)L, sizeof(float*));
     const size_t n0 = (size_t)W * H;

@@ -258,6 +258,7 @@ def dlib():
         L.dfo_variational_refine.argtypes = [C.POINTER(DfoParams), C.c_float, C.c_float, C.c_float, fp, fp, C.c_int, C.c_int, fp, fp]
         L.dfo_pyramid_sizes.argtypes = [C.POINTER(DfoParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.dfo_pyramid_sizes.restype = C.c_int
+        L.dfo_max_levels.restype = C.c_int
         L.dfo_deepflow_calc.argtypes = [C.POINTER(DfoParams), u8p, u8p, C.c_int, C.c_int, fp]
         L.dfo_deepflow_calc_f32.argtypes = [C.POINTER(DfoParams), fp, fp, C.c_int, C.c_int, fp]
         L.dfo_deepflow_calc_f32.restype = C.c_int
@@ -275,11 +276,17 @@ def deepflow_default_params(**over):
     return p
 
 
+def deepflow_max_levels():
+    """The pyramid depth cap deepflow_calc stops at (DFO_MAX_LEVELS; the HIP engine's DF_MAXLEV is the same)."""
+    return int(dlib().dfo_max_levels())
+
+
 def deepflow_pyramid_sizes(W, H, params=None):
     p = params if params is not None else deepflow_default_params()
-    ws = np.zeros(256, np.int32)
-    hs = np.zeros(256, np.int32)
-    n = dlib().dfo_pyramid_sizes(C.byref(p), int(W), int(H), ws.ctypes.data_as(C.c_void_p), hs.ctypes.data_as(C.c_void_p), 256)
+    cap = deepflow_max_levels()
+    ws = np.zeros(cap, np.int32)
+    hs = np.zeros(cap, np.int32)
+    n = dlib().dfo_pyramid_sizes(C.byref(p), int(W), int(H), ws.ctypes.data_as(C.c_void_p), hs.ctypes.data_as(C.c_void_p), cap)
     return list(zip(ws[:n].tolist(), hs[:n].tolist()))
 
 

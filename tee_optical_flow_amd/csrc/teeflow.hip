@@ -41,7 +41,10 @@
 namespace {
 
 constexpr int MAXLEV = 64;
-constexpr int DF_MAXLEV = 160;       // x0.95 pyramid: 60 levels at 512^2, 87 at 2048^2
+// DeepFlow pyramid depth: at most 200 downscales (201 levels), upstream OpticalFlowDeepFlow's `maxLayers` (200) as recalled, not pinned
+// against OpenCV.  oracle/deepflow_oracle.c stops at the same depth (DFO_MAX_LEVELS).  Default x0.95 pyramids never reach it: 60 levels
+// at 512^2, 87 at 2048^2; a size rule with a fixed point above min_size (64^2, min_size 5: 10 x 10 for ever) does.
+constexpr int DF_MAXLEV = 201;
 constexpr int SLOT_RING = 1024;       // host-mapped words the tvl1_iter launches publish their active-pair count to
 constexpr int DEFAULT_LAG = 1;        // the host enqueues at most this many launches beyond the last answer it has read
 constexpr int DEFAULT_MAX_BATCH = 128;

@@ -48,7 +48,8 @@ extern "C" {
 #endif
 
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
-                              tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2 */
+                              tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
+                              tf_clean_masks */
 
 enum {
     TF_OK = 0,
@@ -212,6 +213,20 @@ int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int 
                          tf_stats* st);
 int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out,
                              tf_stats* st);
+
+/* Mask cleaning of the segmentor modes, `clean_mask` of the reference (calculate_optical_flow.py:90-111 moving_avg_mask, :113-182
+ * clean_mask), on the device and exact: for each label l (class id class_ids[l]) and frame,
+ *   m      = moving_avg_mask(class_map == id) with its defaults (n = 4, threshold 0.49; the reference ignores its config there),
+ *   filled = binary_fill_holes(m)                (background not 4-connected to the image border becomes foreground),
+ *   clean  = remove_small_objects(filled, min_size)   (4-connected foreground components of fewer than min_size pixels go;
+ *            min_size <= 0 removes nothing),
+ * and bkgd = not (clean of any label).  class_map: host uint8 [N][H][W].  masks_out: host [n_labels + 1][N][H][W][2] bytes of 0 / 1,
+ * the labels in class_ids' order and bkgd last; each plane is the reference's bool [N,H,W,2] array (channel duplicated).
+ * Runs on the handle's stream and never on a lane's, so it may be called while tf_submit_* jobs of the handle are in flight.  Device
+ * scratch, grown on demand and kept by the handle: N*H*W bytes for the class map plus, per chunk of frames, (12 * n_labels + 2) bytes per
+ * pixel and frame, with chunks of as many frames as fit in 512 MiB (at least one frame).  Host-synchronous. */
+int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, int W, const uint8_t* class_ids, int n_labels, long long min_size,
+                   uint8_t* masks_out);
 
 /* ---- radial / longitudinal projection + per-frame statistics of the reference's analysis step
  *      (optical_flow/analysis.py:89-212: calculate_comp_magnitude, calc_bidirectional_hist), float64, on the device.

@@ -16,6 +16,7 @@
 #include "teeflow_analysis.hip.h"
 #include "teeflow_wase.hip.h"
 #include "teeflow_saliency.hip.h"
+#include "teeflow_masks.hip.h"
 #include "../../include/teeflow.h"
 #include <rccl/rccl.h>      // types and prototypes only: librccl is loaded with dlopen when a communicator is first asked for
 #include <dlfcn.h>
@@ -145,7 +146,9 @@ struct tf_handle : TfKnobs {
     DfBufs df = {};
     // ---- frame preprocessing (conditioning, saliency): grow-only work buffers, freed with the handle ----
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
-    enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT, PRE_COUNT };
+    enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
+           PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks
+           PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     // ---- analysis session (row f1) ----
@@ -2045,6 +2048,77 @@ TF_API int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int 
 TF_API int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
 {
     return calc_seq_saliency(h, frames, N, H, W, channels, true, scale, flow_out, st);
+}
+
+namespace {
+// tf_clean_masks: frames go through in chunks so that the per-chunk scratch (10 B per pixel and label, 2 B per pixel and label + 1 of
+// output) stays within MASK_CHUNK_BYTES whatever the study's length; the class map itself (1 B per pixel) is uploaded whole.
+constexpr size_t MASK_CHUNK_BYTES = (size_t)512 << 20;
+
+int clean_masks(tf_handle* h, const uint8_t* cmap, int N, int H, int W, const uint8_t* ids, int L, long long min_size, uint8_t* out)
+{
+    using namespace msk;
+    const size_t HW = (size_t)H * W;
+    if (HW > 0x7fffffffu) return fail(h, TF_ERR_UNSUPPORTED, "tf_clean_masks: at most 2^31 - 1 pixels per frame");
+    if (L > 65535) return fail(h, TF_ERR_UNSUPPORTED, "tf_clean_masks: at most 65535 labels");
+    const size_t per_frame = HW * (10 * (size_t)L + 2 * ((size_t)L + 1));
+    size_t nf = MASK_CHUNK_BYTES / per_frame;
+    if (nf > (size_t)N) nf = (size_t)N;
+    if (nf > (size_t)(65535 / L)) nf = (size_t)(65535 / L);     // planes of a chunk are grid.y
+    if (nf < 1) nf = 1;
+    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
+    HIPC(h, hipSetDevice(h->dev));
+    uint8_t* dcls = nullptr; uint32_t* dpar = nullptr; uint32_t* daux = nullptr; uint16_t* dlr = nullptr; uint16_t* dout = nullptr;
+    uint8_t* meta = nullptr;                                   // [0, 4): error word, [64, 64 + L): class ids
+    int rc;
+    if ((rc = pre_grow(h, tf_handle::PRE_MK_CLS, (size_t)N * HW, (void**)&dcls)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_PAR, (size_t)L * nf * HW * 4, (void**)&dpar)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_AUX, (size_t)L * nf * HW * 4, (void**)&daux)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_LR, (size_t)L * nf * HW * 2, (void**)&dlr)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_OUT, (size_t)(L + 1) * nf * HW * 2, (void**)&dout)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_META, 64 + (size_t)L, (void**)&meta))) return rc;
+    unsigned* derr = (unsigned*)meta;
+    const hipStream_t s = h->stream;
+    HIPC(h, hipMemcpyAsync(dcls, cmap, (size_t)N * HW, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(meta + 64, ids, (size_t)L, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
+    for (int f0 = 0; f0 < N; f0 += (int)nf) {
+        const int n = N - f0 < (int)nf ? N - f0 : (int)nf;
+        const size_t planes = (size_t)L * n;
+        const dim3 g(tiles, (unsigned)planes), blk(256);
+        // fill holes: components of m's background; those with a pixel on the border keep their flag in aux
+        HIPC(h, hipMemsetAsync(daux, 0, planes * HW * 4, s));
+        hipLaunchKernelGGL(k_mask_local<0>, g, blk, 0, s, dcls, meta + 64, dpar, daux, dlr, N, f0, n, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_mask_flatten<0>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
+        // small objects: components of the filled mask, their sizes counted into aux
+        hipLaunchKernelGGL(k_mask_local<1>, g, blk, 0, s, dcls, meta + 64, dpar, daux, dlr, N, f0, n, H, W, tiles_x, derr);
+        HIPC(h, hipMemsetAsync(daux, 0, planes * HW * 4, s));
+        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_mask_flatten<1>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
+        hipLaunchKernelGGL(k_mask_store, dim3((unsigned)((HW + 255) / 256), (unsigned)n), blk, 0, s, dpar, daux, L, n, HW, min_size, dout);
+        HIPC(h, hipGetLastError());
+        for (int l = 0; l <= L; ++l)                           // label l's frames of this chunk are contiguous in masks_out
+            HIPC(h, hipMemcpyAsync(out + ((size_t)l * N + f0) * HW * 2, dout + (size_t)l * n * HW, (size_t)n * HW * 2, hipMemcpyDeviceToHost, s));
+        unsigned e = 0;
+        HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
+        HIPC(h, hipStreamSynchronize(s));
+        if (e) return fail(h, TF_ERR_HIP, "tf_clean_masks: a union-find loop ran out of its bound (code %u)", e);
+    }
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, int W, const uint8_t* class_ids, int n_labels, long long min_size,
+                          uint8_t* masks_out)
+{
+    if (!h || !class_map || !class_ids || !masks_out || N < 1 || H < 1 || W < 1 || n_labels < 1) return TF_ERR_INVALID_ARG;
+    const int rc = clean_masks(h, class_map, N, H, W, class_ids, n_labels, min_size, masks_out);
+    if (rc != TF_OK) {                                         // nothing of the call may still write masks_out when it returns
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        (void)hipGetLastError();
+    }
+    return rc;
 }
 
 TF_API int tf_radlong_project(tf_handle* h, const float* flow, const double* centroids, int N, int H, int W,

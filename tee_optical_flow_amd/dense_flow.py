@@ -291,6 +291,21 @@ class DenseFlow:
             out[N - 1] = out[N - 2]
         return out
 
+    def clean_masks(self, class_map, class_ids, min_size):
+        """The reference's clean_mask (calculate_optical_flow.py:90-111, :113-182) on the device, exact: class map uint8 [N,H,W] ->
+        bool [len(class_ids) + 1, N, H, W, 2], one plane per class id in the order given (moving average of `== id` with the
+        reference's defaults, fill holes, remove_small_objects(min_size), all 4-connected) and 'bkgd' last.  Each plane is a
+        C-contiguous view in pinned host memory.  May be called while submitted studies are in flight on this engine."""
+        class_map = _u8_image_stack(class_map, "class_map", 3)
+        ids = np.ascontiguousarray(class_ids, dtype=np.uint8)
+        if ids.ndim != 1 or ids.size < 1:
+            raise OpticalFlowCalculationError(f"class_ids must be a non-empty list of class ids, got {class_ids!r}")
+        N, H, W = class_map.shape
+        out = self._pool.empty((ids.size + 1, N, H, W, 2), np.uint8)
+        _lib.check(self._L.tf_clean_masks(self._h, class_map.ctypes.data, N, H, W, ids.ctypes.data, int(ids.size), int(min_size),
+                                          out.ctypes.data), self._h, "tf_clean_masks")
+        return out.view(np.bool_)
+
     def wase_compensate(self, flows, bkgd_mask, scale=1.0):
         """Reference :647-652, 659 for every flow of a study at once, on the device: returns (flows - background[p]) * scale
         and the float32 backgrounds.  flows float32 [P,H,W,2]; bkgd_mask bool [N,H,W,2] (mask_dict['bkgd'])."""

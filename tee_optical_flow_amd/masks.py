@@ -5,7 +5,8 @@ where skimage / torchvision are absent.  Mirrors /root/reference/optical_flow/ca
   :113-182  clean_mask
   :184-213  predict_movie_thres (mode='otsu')
   :215-241  predict_movie      (modes 'A4C', 'RVIO_2class')
-moving_avg_mask / predict_movie_thres are pinned by tests/golden/reference_host_side.npz.  Host-side glue, not a kernel:
+moving_avg_mask / predict_movie_thres are pinned by tests/golden/reference_host_side.npz, clean_mask by
+tests/golden/reference_clean_mask.npz (host path here, device path DenseFlow.clean_masks).  Host-side glue, not a kernel:
 the segmentor stays stock PyTorch(-ROCm), as north_star says."""
 import numpy as np
 
@@ -71,14 +72,21 @@ _MODE_LABELS = {
 }
 
 
-def clean_mask(arr, mode="A4C", verbose=False, config=None):
-    """Reference :113-182: class map [N,H,W] -> {label: bool [N,H,W,2]} + 'bkgd'; None for an unknown mode."""
+def clean_mask(arr, mode="A4C", verbose=False, config=None, *, engine=None):
+    """Reference :113-182: class map [N,H,W] -> {label: bool [N,H,W,2]} + 'bkgd'; None for an unknown mode.
+    With an `engine` that has `clean_masks` (DenseFlow) and a uint8 [N,H,W] map with N, H, W >= 2, the work runs on the device
+    (tf_clean_masks, exact); otherwise, and for the shapes where the reference's np.squeeze changes what it computes, on the host."""
     from scipy.ndimage import binary_fill_holes
     if config is None:
         config = default_optical_flow_config()
     if mode not in _MODE_LABELS:
         return None
     arr = np.asarray(arr)
+    if (engine is not None and hasattr(engine, "clean_masks") and arr.dtype == np.uint8 and arr.ndim == 3
+            and min(arr.shape) >= 2):
+        labels = _MODE_LABELS[mode]
+        planes = engine.clean_masks(arr, list(labels.values()), config.min_mask_size)
+        return dict(zip(list(labels) + ["bkgd"], planes))
     out = {}
     aggregate = np.zeros(arr.shape, dtype=bool)
     for k, cls in _MODE_LABELS[mode].items():
@@ -118,9 +126,9 @@ def evaluate_1_slice(frame, model):
     return np.asarray(pil_mask, dtype=np.uint8)
 
 
-def predict_movie(nparr, model, mode="A4C", verbose=False, config=None):
-    """Reference :215-241: every frame through the segmentor, then clean_mask."""
+def predict_movie(nparr, model, mode="A4C", verbose=False, config=None, *, engine=None):
+    """Reference :215-241: every frame through the segmentor, then clean_mask (on `engine`'s device when it has clean_masks)."""
     if config is None:
         config = default_optical_flow_config()
     preds = [evaluate_1_slice(nparr[i], model) for i in range(nparr.shape[0])]
-    return clean_mask(np.stack(preds), mode, verbose, config=config)
+    return clean_mask(np.stack(preds), mode, verbose, config=config, engine=engine)

@@ -177,14 +177,16 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             if segmentor_model is None:
                 raise ConfigurationError(f"mode={mode} needs segmentor_model (a module with image_encoder / prompt_encoder / "
                                          "mask_decoder, reference :47-88) or a precomputed mask_dict=")
-            from .masks import predict_movie
-            mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config)   # reference :549-550
         else:
             raise ConfigurationError(f"Input for mode must be [A4C, otsu, RVIO_2class], not {mode}.")
     own = flow_model is None
     model = make_flow_model(OF_algo, config) if own else flow_model
     collect = None                                # () -> the study's flow array
     try:
+        if mask_dict is None:
+            # reference :549-550; the masks are cleaned on the flow model's device when it offers it (DenseFlow.clean_masks)
+            from .masks import predict_movie
+            mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config, engine=model)
         rgb_u8 = nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8
         if not no_saliency:
             # the reference's default branch (:559-560, :586): cv2.saliency.StaticSaliencyFineGrained on every frame

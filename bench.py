@@ -9,19 +9,21 @@ with the next step's compute.  value = pairs all ranks solved / max-over-ranks w
 
 Inside the call the LIBRARY cuts the batch into 128-pair sub-batches that its three lanes (engines of their own: stream, buffers, host
 thread) take from a queue, so one sub-batch's tail runs under the others' full launches (include/teeflow.h "Sub-batches and lanes").
-Round 4 reached that overlap with three engines driven by Python threads in this file; rounds 1-3 timed 128-pair calls that were split
-in two contiguous halves and joined -- the default N=1 run still times that form right after and reports it as "steps_joined", and
-the same 128-pair batches submitted without waiting (tf_submit_pairs_device, three in flight) as "jobs_in_flight".  `--in-flight E`
-(E > 1) makes the timed region itself use tf_submit_* with E steps in flight.  Every pair's flow is bit-identical in all forms
-(tests/test_gpu_queue.py, tools/queue_forms.py).
+`--in-flight E` (E > 1) makes the timed region itself use tf_submit_* with E steps in flight.  Every pair's flow is bit-identical in all
+forms (tests/test_gpu_queue.py, tools/queue_forms.py).
 
-The default N=1 run then measures BASELINE configs[3] (OF_algo='deepflow', the algorithm the reference's own CLI
-hard-codes, calculate_optical_flow.py:735-739) on 128 pairs per call and reports it under "deepflow" in the same JSON line.
+A plain run does only what the headline needs: inputs, one set-up call, W warm-up steps, K timed steps, `--dump-outputs` if asked, the
+line.  `--full` adds everything else, as runs of their own after the timed steps: the forms rounds 1-4 timed ("steps_joined": 128-pair
+calls split in two contiguous halves and joined; "jobs_in_flight": the same batches through tf_submit_pairs_device, three in flight), the
+roofline from instrumented single-lane repeats, single-pair latency, the saliency branch, the host-pointer (PCIe) step, the CPU
+baselines with their parity check, and -- N = 1 -- BASELINE configs[3] (OF_algo='deepflow', the
+algorithm the reference's own CLI hard-codes, calculate_optical_flow.py:735-739) on 128 pairs per call, under "deepflow".  With N > 1 the
+all-gather is part of the timed step, and every run checks that it delivered each rank's shard intact ("allgather_checksums_match").
 
 Everything that is not GPU work (synthetic inputs, the optional `--pmc` counter passes, which run this script as a
 child under rocprofv3) happens BEFORE the first GPU call, so no process is ever started from a GPU-initialised one.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 from a plain shell: this process starts the N ranks itself)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1 from a plain shell: this process starts the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -157,13 +159,14 @@ def under_profiler():
     return "rocprof" in pre or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
 
 
-def make_inputs(seeds, H, W, allow_pool=True):
-    """[I0s, I1s] uint8 [B,H,W].  Cached under $TMPDIR (the generator is deterministic); a process pool only when
-    nothing in this process has touched the GPU and no profiler is attached."""
+def make_inputs(seeds, H, W, allow_pool=True, cache=True):
+    """[I0s, I1s] uint8 [B,H,W].  Cached under $TMPDIR (the generator is deterministic) unless `cache` is False, as it is for
+    a benchmark run, which generates its inputs afresh; a process pool only when nothing in this process has touched the GPU
+    and no profiler is attached."""
     seeds = list(seeds)
     key = hashlib.sha1(repr((seeds, H, W, "speckle-warp v1")).encode()).hexdigest()[:16]
-    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"teeflow_bench_inputs_{key}.npz")
-    if os.path.exists(cache):
+    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"teeflow_bench_inputs_{key}.npz") if cache else None
+    if cache and os.path.exists(cache):
         try:
             z = np.load(cache)
             if z["I0s"].shape == (len(seeds), H, W):
@@ -178,12 +181,13 @@ def make_inputs(seeds, H, W, allow_pool=True):
     else:
         res = [_gen_pair((s, H, W)) for s in seeds]
     I0s, I1s = np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
-    try:
-        tmp = cache + f".{os.getpid()}.npz"     # np.savez appends nothing: the name already ends in .npz
-        np.savez(tmp, I0s=I0s, I1s=I1s)
-        os.replace(tmp, cache)
-    except OSError:
-        pass
+    if cache:
+        try:
+            tmp = cache + f".{os.getpid()}.npz"     # np.savez appends nothing: the name already ends in .npz
+            np.savez(tmp, I0s=I0s, I1s=I1s)
+            os.replace(tmp, cache)
+        except OSError:
+            pass
     return I0s, I1s
 
 
@@ -377,6 +381,181 @@ def dump_flows(path, flows, budget):
     return {"file": os.path.basename(path), "shape": list(sample.shape), "pairs": idx.tolist(), "rows": rows}
 
 
+def leg_engine(a, algo, B, local_rank):
+    """(engine, engine knobs of `--tuning`) as a leg of B pairs uses it: max_batch = the sub-batch size, `--lanes`, then the knobs."""
+    import tee_optical_flow_amd as T
+    tuning = [kv.split("=") for kv in a.tuning.split(",") if kv]
+    eng = T.DenseFlow(device_id=local_rank, max_batch=min(a.sub_batch, B), algo=algo)
+    eng.set_tuning("lanes", a.lanes)
+    for k, v in tuning:
+        eng.set_tuning(k, int(v))
+    return eng, tuning
+
+
+def dump_untimed_leg(a, algo, B, I0s, I1s, torch, dev, local_rank, dump_bytes):
+    """`--dump-outputs` of a leg that this run does not time (the DeepFlow leg without --full): ONE call of the leg's B pairs on the engine
+    the leg would time them on.  Every step of a leg solves the same pairs, and its flows do not depend on which step or lane solves them,
+    so this is what the leg's last timed step returns.  Returns what was written."""
+    H = W = a.size
+    frames = torch.from_numpy(np.concatenate([I0s, I1s])).to(dev)
+    flows = torch.empty((B, H, W, 2), dtype=torch.float32, device=dev)
+    eng, _ = leg_engine(a, algo, B, local_rank)
+    try:
+        eng.calc_pairs_device(frames.data_ptr(), frames.data_ptr() + B * H * W, B, H, W, flows.data_ptr())
+        torch.cuda.synchronize(dev)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        return dump_flows(os.path.join(a.dump_outputs, f"{algo.lower()}_flows.npy"), flows, dump_bytes)
+    finally:
+        eng.close()
+
+
+def roofline_record(a, algo, acc, steps, SUB, H, W, live_pmc, prof):
+    """--full: the `roofline` object of a leg -- its dominant kernel against the HBM (and vector-ALU) roof, from the instrumented
+    single-lane repeats (`acc` iter_* and p_* sums, `prof` launch records) and the counter records of this build."""
+    unit_bytes = 60.0 if algo == "TVL1" else 40.0          # bytes tf_stats.iter_bytes charges per px-iteration / px-sweep
+    launches = max(acc["iter_launches"], 1)
+    avg_launch_ms = acc["iter_ms"] / launches if acc["iter_ms"] > 0 else None
+    units_per_launch = acc["iter_bytes"] / unit_bytes / launches           # px-iterations (px-sweeps) per launch, averaged
+    kern = TVL1_KERNEL if algo == "TVL1" else DF_KERNEL
+    # ---- HBM traffic of the dominant kernel: live PMC passes (--pmc) or the stored passes of THIS build --------
+    traffic = None
+    traffic_source = None
+    ffac, ffac_src = fetch_factor(algo)
+    if live_pmc and "fetch_kb" in live_pmc and "write_kb" in live_pmc:
+        traffic = (ffac * live_pmc["fetch_kb"] + live_pmc["write_kb"]) * 1024.0
+        traffic_source = {"kind": "live", "command": live_pmc.get("command"), "launches_profiled": live_pmc.get("launches"),
+                          "fetch_size_kb_mean": live_pmc["fetch_kb"], "write_size_kb_mean": live_pmc["write_kb"],
+                          "fetch_size_factor": ffac, "fetch_size_factor_source": ffac_src}
+    else:
+        rec, why = stored_record("hbm_traffic.json", kern)
+        if rec:
+            traffic = rec["bytes_per_launch"]
+            traffic_source = {"kind": "stored", "file": "profiles/hbm_traffic.json", "round": rec.get("round"),
+                              "source_fingerprint": rec.get("source_fingerprint"), "command": rec.get("command"),
+                              "launches_profiled": rec.get("launches_profiled"), "note": "PMC passes of this same kernel build, not of this run"}
+        else:
+            traffic_source = {"kind": "none", "why": (live_pmc or {}).get("error") or why}
+    # compulsory bytes of the kernel that is launched: tvl1_iter 9 plane reads + 6 writes once per TWO iterations = 30 B per
+    # px-iteration; SOR 8 plane reads + 2 writes per launch of `sor_fuse` sweeps = 40 B per pixel and launch (tf_stats.iter_bytes
+    # charges 40 B per px-SWEEP, so the per-launch figure is iter_bytes / sweeps per launch)
+    comp_per_launch = units_per_launch * 30.0 if algo == "TVL1" else acc["sor_px"] * 40.0 / launches
+    secs = avg_launch_ms / 1e3 if avg_launch_ms else None
+    if traffic is not None and secs:
+        achieved, basis = traffic / 1e9 / secs, (f"measured HBM bytes per launch (PMC: {ffac:g} x FETCH_SIZE + WRITE_SIZE; factor from {ffac_src}) / mean launch time")
+    elif secs:
+        achieved, basis = comp_per_launch / 1e9 / secs, ("no PMC pass of this build: compulsory bytes of the launched kernel ("
+                                                         + ("30 B per px-iteration" if algo == "TVL1" else "40 B per pixel and launch") + ") / mean launch time")
+    else:
+        achieved, basis = None, "profiling off"
+    limiter, limiter_evidence = classify_limiter(kern, achieved / HBM_STREAM_GBS if achieved else None)
+    roof = {"bound": "hbm", "limiter": limiter, "limiter_evidence": limiter_evidence,
+            "kernel": kern + (" (tvl1_iter: two inner iterations per launch, full-width row strips)" if algo == "TVL1" else
+                              " and k_df_sor_rt_coop (red-black SOR on 128x64 regions held in registers: all 25 sweeps of a fixed-point iteration per launch -- "
+                              "co-resident regions that trade du, dv every 5 sweeps, or one region per pair on the small levels)"),
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS if achieved else None,
+            "frac_of_streaming_ceiling": achieved / HBM_STREAM_GBS if achieved else None,
+            "traffic": traffic, "traffic_source": traffic_source, "achieved_basis": basis,
+            "avg_launch_ms": avg_launch_ms, "launches": acc["iter_launches"], "launches_per_step": acc["iter_launches"] / max(steps, 1),
+            ("px_iterations_per_launch" if algo == "TVL1" else "px_sweeps_per_launch"): units_per_launch,
+            "measured_on": f"{steps} instrumented repeats of the timed steps' pairs as single-lane {SUB}-pair calls (one HIP event pair per launch, engine stream; the GPU to itself)"}
+    rate = units_per_launch / secs if secs else None
+    roof["algorithmic_bytes_per_launch"] = comp_per_launch
+    roof["algorithmic_GBps"] = comp_per_launch / 1e9 / secs if secs else None
+    roof["algorithmic_frac"] = comp_per_launch / 1e9 / secs / HBM_PEAK_GBS if secs else None
+    roof["traffic_over_algorithmic"] = traffic / comp_per_launch if traffic and comp_per_launch else None
+    if algo != "TVL1":
+        # With all sweeps of a fixed-point iteration in one launch the kernel reads its 8 planes once per 25 sweeps: ~25 x 56 flop per
+        # 40 B = 35 flop/B, above the ~20 flop/B ridge of the (non-matrix) fp32 vector pipes -- the HBM object above is what the bench
+        # contract asks for, the vector ALU is what bounds the launch.  Executed instructions from the stored counter passes of this build.
+        valu = {"px_sweeps_per_s": rate, "flop_per_byte_per_launch_approx": 35.0, "fp32_vector_ridge_flop_per_byte_approx": 19.7}
+        sqf = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_sq_counters.json")))
+        for f in reversed(sqf):
+            try:
+                with open(f) as fh:
+                    rec = json.load(fh).get(kern)
+            except (OSError, ValueError):
+                rec = None
+            if rec and rec.get("source_fingerprint") == kernel_source_fingerprint() and "SQ_INSTS_VALU" in rec.get("totals_all_dispatches", {}):
+                # the counter pass profiles whole steps of this same workload (--steps-only): all its dispatches against the
+                # pixel-sweeps of as many steps as its dispatch count says (accepted only if that is a whole number)
+                lps = acc["iter_launches"] / max(steps, 1)
+                nst = rec["dispatches"] / lps if lps else 0.0
+                whole = abs(nst - round(nst)) < 0.02 and round(nst) >= 1
+                wi = rec["totals_all_dispatches"]["SQ_INSTS_VALU"]
+                # the vector-ALU roof: lane-instructions per second against CUs x 4 SIMDs x 16 lanes x clock
+                peak = SIMDS * 16 * a.clock_ghz * 1e9
+                t_all = round(nst) * lps * secs if whole and secs else None
+                valu.update({"peak_lane_instructions_per_s": peak, "clock_ghz_assumed": a.clock_ghz,
+                             "frac_executed": (wi * 64.0 / t_all / peak) if t_all else None,
+                             "frac_useful": (rate * 40.0 / peak) if rate else None,
+                             "frac_note": "executed = SQ_INSTS_VALU x 64 lanes / launch time; useful = 40 instructions per pixel-sweep x pixel-sweeps / launch time"})
+                valu.update({"source": f"profiles/{os.path.basename(f)}", "valu_wave_instructions_all_dispatches": wi,
+                             "dispatches_in_the_counter_pass": rec["dispatches"], "steps_in_the_counter_pass": nst,
+                             "valu_lane_instructions_per_px_sweep": (wi * 64.0 / (round(nst) * lps * units_per_launch)) if whole and units_per_launch else None,
+                             "valu_lane_instructions_per_update_in_the_loop": 40,
+                             "valu_pipe_busy_per_simd": rec.get("derived", {}).get("valu_pipe_busy_per_simd_all_launches"),
+                             "simd_cycles_per_valu_inst_all_launches": rec.get("derived", {}).get("simd_cycles_per_valu_inst_all_launches")})
+                break
+        roof["valu"] = valu
+        # the classifier's word: HBM is this launch's bound only if it runs near the streaming ceiling
+        if limiter and not limiter.startswith("hbm"):
+            roof["bound"] = "valu"
+            roof["bound_note"] = ("set from the counter-derived limiter: the launch keeps its system in registers for 25 sweeps (~35 flop per compulsory byte), "
+                                  "HBM traffic is far from the roof; the hbm figures above stay for the record, roofline.valu holds the fractions of the vector-ALU roof")
+    if algo == "TVL1":
+        # The regime `value` is measured in (three lanes' kernels sharing the GPU), from a stored kernel trace of THIS build's timed steps
+        # (tools/timed_regime.py): the kernel's mean duration while it shares the GPU, the kernels in flight beside it, and its
+        # share-adjusted duration -- the figures above are from launches that had the GPU to themselves.
+        tr_files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_timed_regime.json")))
+        tr = None
+        for f in reversed(tr_files):
+            try:
+                with open(f) as fh:
+                    rec = json.load(fh).get(kern)
+            except (OSError, ValueError):
+                rec = None
+            if rec and rec.get("source_fingerprint") == kernel_source_fingerprint():
+                tr = dict(rec, source=f"profiles/{os.path.basename(f)}")
+                break
+        if tr is not None:
+            sad = tr["mean_share_adjusted_duration_us"] * 1e-6
+            bytes_launch = traffic if traffic is not None else comp_per_launch
+            tr["bytes_per_launch_used"] = bytes_launch
+            tr["bytes_basis"] = "measured HBM bytes per launch (PMC)" if traffic is not None else "compulsory bytes per launch (30 B per px-iteration)"
+            tr["GBps_at_mean_duration"] = bytes_launch / (tr["mean_duration_us"] * 1e-6) / 1e9
+            tr["GBps_share_adjusted"] = bytes_launch / sad / 1e9
+            tr["frac_of_peak_share_adjusted"] = bytes_launch / sad / 1e9 / HBM_PEAK_GBS
+            tr["compulsory_frac_of_peak_share_adjusted"] = comp_per_launch / sad / 1e9 / HBM_PEAK_GBS
+            roof["timed_regime"] = tr
+        else:
+            roof["timed_regime"] = {"note": "no kernel trace of this build's timed steps under profiles/ (tools/timed_regime.py); the figures above describe launches that had the GPU to themselves"}
+        # algorithmic (compulsory) bytes of the kernel that is actually launched: 9 plane reads + 6 writes once per TWO iterations
+        roof["algorithmic_GBps_30B"] = rate * 30.0 / 1e9 if rate else None
+        roof["algorithmic_bytes_per_launch_30B"] = units_per_launch * 30.0
+        roof["notional_GBps_60B"] = rate * 60.0 / 1e9 if rate else None     # one-iteration-per-pass kernel's compulsory traffic
+        roof["notional_GBps_88B"] = rate * 88.0 / 1e9 if rate else None     # SURVEY.md section 8(d): two-kernel K_A/K_B formulation
+        roof["notional_note"] = ("what kernels that make one HBM pass per inner iteration would have had to move at this rate; the shipped kernel "
+                                 "makes one pass per TWO iterations, so these exceed its real traffic and are not roofline fractions")
+        full = None
+        if prof is not None and len(prof[3]):
+            lv, wp, it, ms = prof
+            m = (lv == 0) & (it == 0) & (ms > 0)             # first launch of a level-0 stage: all B pairs iterate, 2 iterations
+            if m.any():
+                full = float(np.median(SUB * H * W * 2.0 / (ms[m] * 1e-3)))      # (the instrumented calls hold SUB pairs each)
+        isa, why = stored_record("isa_stats.json", kern)
+        valu = {"px_iterations_per_s_all_launches": rate, "px_iterations_per_s_full_launches": full}
+        if isa:
+            ipp = isa["valu_insts_per_wave_step"] / isa["px_iterations_per_wave_step"]
+            valu.update({"valu_insts_per_px_iteration": ipp, "vgprs": isa.get("vgprs"), "waves_per_simd": isa.get("waves_per_simd"),
+                         "isa_source": "profiles/isa_stats.json (disassembly of this build's main loop)",
+                         "simd_cycles_per_valu_inst_full_launches": (a.clock_ghz * 1e9 * SIMDS / (full * ipp) if full else None),
+                         "clock_ghz_assumed": a.clock_ghz})
+        else:
+            valu["isa_source"] = why
+        roof["valu"] = valu
+    return roof
+
+
 def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, local_rank, live_pmc=None, cpu_sample=8, dump_bytes=0):
     import tee_optical_flow_amd as T
     H = W = a.size
@@ -391,11 +570,7 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
     flows = [torch.empty((B, H, W, 2), dtype=torch.float32, device=dev) for _ in range(NBUF)]
     gdev = dev if a.backend == "nccl" else torch.device("cpu")
     gathered = [torch.empty((world * B, H, W, 2), dtype=torch.float32, device=gdev) for _ in range(NBUF)] if world > 1 else None
-    tuning = [kv.split("=") for kv in a.tuning.split(",") if kv]
-    eng = T.DenseFlow(device_id=local_rank, max_batch=SUB, algo=algo)
-    eng.set_tuning("lanes", a.lanes)
-    for k, v in tuning:
-        eng.set_tuning(k, int(v))
+    eng, tuning = leg_engine(a, algo, B, local_rank)
     # Every tf_calc_* is host-synchronous (its lanes have drained when it returns) and tf_wait likewise: a step's flows are complete
     # when its all-gather is issued, on whatever stream they were produced.  The opposite direction needs an explicit host wait: before
     # a buffer is solved into again the host waits (tf_comm_wait) until the all-gather that read it has really finished.
@@ -486,8 +661,8 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
                     "copy_stream_shares_a_hardware_queue_with_a_solve_stream": bool(eng.counter("streams_serialised") & 2)}
     gather_ok = None
     if world > 1:
-        # every rank's shard must have arrived intact everywhere: compare checksums of the gathered segments with the
-        # checksums the owning ranks computed locally (last timed step)
+        # part of every N > 1 run, plain or --full (the all-gather is part of the timed step): every rank's shard must have arrived
+        # intact everywhere: compare checksums of the gathered segments with the checksums the owning ranks computed locally (last timed step)
         bits = lambda t: t.contiguous().view(torch.int32).to(torch.int64)        # exact, order-independent: sum of the bit patterns
         mine = bits(last_flow).sum().reshape(1).to(gdev)
         sums = torch.empty(world, dtype=torch.int64, device=gdev)
@@ -500,12 +675,12 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
         # before the forms below solve into the same buffers
         os.makedirs(a.dump_outputs, exist_ok=True)
         dumped = dump_flows(os.path.join(a.dump_outputs, f"{algo.lower()}_flows.npy"), gathered[last_buf] if world > 1 else last_flow, dump_bytes)
-    # The same pairs in the two other forms, for the record beside `value` (N = 1): (i) SUB-pair calls, each split over `--lanes`
+    # --full: the same pairs in the two other forms, for the record beside `value` (N = 1): (i) SUB-pair calls, each split over `--lanes`
     # contiguous parts and joined at its end -- what rounds 1-3 timed; (ii) SUB-pair jobs submitted without waiting, three in flight.
     npx = H * W
     subs = [(c, min(SUB, B - c)) for c in range(0, B, SUB)]
     joined = inflight = None
-    if world == 1 and B > SUB and not a.steps_only:
+    if world == 1 and B > SUB and a.full and not a.steps_only:
         def sub_call(c, nb, buf, fn):
             return fn(p0 + c * npx, p1 + c * npx, nb, H, W, flows[buf].data_ptr() + c * npx * 8)
         for c, nb in subs:
@@ -532,11 +707,11 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
         dj = time.perf_counter() - tj
         inflight = {"value": B * steps / dj, "unit": "frame-pairs/s", "pairs_per_job": SUB, "jobs_in_flight": 3,
                     "note": f"tf_submit_pairs_device of {SUB}-pair jobs, three in flight, one host thread (the library's lanes take whole jobs)"}
-    # Roofline leg: the SAME pairs again as SUB-pair calls on ONE lane (no queue, no split), with every launch of the dominant kernel
-    # bracketed by a HIP event pair on the engine's stream.  Kept out of the timed region above (the event records cost a few % of a
+    # Roofline leg (--full): the SAME pairs again as SUB-pair calls on ONE lane (no queue, no split), with every launch of the dominant
+    # kernel bracketed by a HIP event pair on the engine's stream.  Kept out of the timed region above (the event records cost a few % of a
     # step); roofline.timed_regime describes the kernel in the regime the timed region runs in.
     prof = None
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         eng.set_tuning("lanes", 1)      # one lane: a launch's event-pair time must not include another lane's kernels
         eng.set_profile(1)
         for k in range(steps):
@@ -558,146 +733,6 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
     if rank == 0:
         pairs = world * B * steps
         unit_bytes = 60.0 if algo == "TVL1" else 40.0          # bytes tf_stats.iter_bytes charges per px-iteration / px-sweep
-        launches = max(acc["iter_launches"], 1)
-        avg_launch_ms = acc["iter_ms"] / launches if acc["iter_ms"] > 0 else None
-        units_per_launch = acc["iter_bytes"] / unit_bytes / launches           # px-iterations (px-sweeps) per launch, averaged
-        kern = TVL1_KERNEL if algo == "TVL1" else DF_KERNEL
-        # ---- HBM traffic of the dominant kernel: live PMC passes (--pmc) or the stored passes of THIS build --------
-        traffic = None
-        traffic_source = None
-        ffac, ffac_src = fetch_factor(algo)
-        if live_pmc and "fetch_kb" in live_pmc and "write_kb" in live_pmc:
-            traffic = (ffac * live_pmc["fetch_kb"] + live_pmc["write_kb"]) * 1024.0
-            traffic_source = {"kind": "live", "command": live_pmc.get("command"), "launches_profiled": live_pmc.get("launches"),
-                              "fetch_size_kb_mean": live_pmc["fetch_kb"], "write_size_kb_mean": live_pmc["write_kb"],
-                              "fetch_size_factor": ffac, "fetch_size_factor_source": ffac_src}
-        else:
-            rec, why = stored_record("hbm_traffic.json", kern)
-            if rec:
-                traffic = rec["bytes_per_launch"]
-                traffic_source = {"kind": "stored", "file": "profiles/hbm_traffic.json", "round": rec.get("round"),
-                                  "source_fingerprint": rec.get("source_fingerprint"), "command": rec.get("command"),
-                                  "launches_profiled": rec.get("launches_profiled"), "note": "PMC passes of this same kernel build, not of this run"}
-            else:
-                traffic_source = {"kind": "none", "why": (live_pmc or {}).get("error") or why}
-        # compulsory bytes of the kernel that is launched: tvl1_iter 9 plane reads + 6 writes once per TWO iterations = 30 B per
-        # px-iteration; SOR 8 plane reads + 2 writes per launch of `sor_fuse` sweeps = 40 B per pixel and launch (tf_stats.iter_bytes
-        # charges 40 B per px-SWEEP, so the per-launch figure is iter_bytes / sweeps per launch)
-        comp_per_launch = units_per_launch * 30.0 if algo == "TVL1" else acc["sor_px"] * 40.0 / launches
-        secs = avg_launch_ms / 1e3 if avg_launch_ms else None
-        if traffic is not None and secs:
-            achieved, basis = traffic / 1e9 / secs, (f"measured HBM bytes per launch (PMC: {ffac:g} x FETCH_SIZE + WRITE_SIZE; factor from {ffac_src}) / mean launch time")
-        elif secs:
-            achieved, basis = comp_per_launch / 1e9 / secs, ("no PMC pass of this build: compulsory bytes of the launched kernel ("
-                                                             + ("30 B per px-iteration" if algo == "TVL1" else "40 B per pixel and launch") + ") / mean launch time")
-        else:
-            achieved, basis = None, "profiling off"
-        limiter, limiter_evidence = classify_limiter(kern, achieved / HBM_STREAM_GBS if achieved else None)
-        roof = {"bound": "hbm", "limiter": limiter, "limiter_evidence": limiter_evidence,
-                "kernel": kern + (" (tvl1_iter: two inner iterations per launch, full-width row strips)" if algo == "TVL1" else
-                                  " and k_df_sor_rt_coop (red-black SOR on 128x64 regions held in registers: all 25 sweeps of a fixed-point iteration per launch -- "
-                                  "co-resident regions that trade du, dv every 5 sweeps, or one region per pair on the small levels)"),
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS if achieved else None,
-                "frac_of_streaming_ceiling": achieved / HBM_STREAM_GBS if achieved else None,
-                "traffic": traffic, "traffic_source": traffic_source, "achieved_basis": basis,
-                "avg_launch_ms": avg_launch_ms, "launches": acc["iter_launches"], "launches_per_step": acc["iter_launches"] / max(steps, 1),
-                ("px_iterations_per_launch" if algo == "TVL1" else "px_sweeps_per_launch"): units_per_launch,
-                "measured_on": f"{steps} instrumented repeats of the timed steps' pairs as single-lane {SUB}-pair calls (one HIP event pair per launch, engine stream; the GPU to itself)"}
-        rate = units_per_launch / secs if secs else None
-        roof["algorithmic_bytes_per_launch"] = comp_per_launch
-        roof["algorithmic_GBps"] = comp_per_launch / 1e9 / secs if secs else None
-        roof["algorithmic_frac"] = comp_per_launch / 1e9 / secs / HBM_PEAK_GBS if secs else None
-        roof["traffic_over_algorithmic"] = traffic / comp_per_launch if traffic and comp_per_launch else None
-        if algo != "TVL1":
-            # With all sweeps of a fixed-point iteration in one launch the kernel reads its 8 planes once per 25 sweeps: ~25 x 56 flop per
-            # 40 B = 35 flop/B, above the ~20 flop/B ridge of the (non-matrix) fp32 vector pipes -- the HBM object above is what the bench
-            # contract asks for, the vector ALU is what bounds the launch.  Executed instructions from the stored counter passes of this build.
-            valu = {"px_sweeps_per_s": rate, "flop_per_byte_per_launch_approx": 35.0, "fp32_vector_ridge_flop_per_byte_approx": 19.7}
-            sqf = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_sq_counters.json")))
-            for f in reversed(sqf):
-                try:
-                    with open(f) as fh:
-                        rec = json.load(fh).get(kern)
-                except (OSError, ValueError):
-                    rec = None
-                if rec and rec.get("source_fingerprint") == kernel_source_fingerprint() and "SQ_INSTS_VALU" in rec.get("totals_all_dispatches", {}):
-                    # the counter pass profiles whole steps of this same workload (--steps-only): all its dispatches against the
-                    # pixel-sweeps of as many steps as its dispatch count says (accepted only if that is a whole number)
-                    lps = acc["iter_launches"] / max(steps, 1)
-                    nst = rec["dispatches"] / lps if lps else 0.0
-                    whole = abs(nst - round(nst)) < 0.02 and round(nst) >= 1
-                    wi = rec["totals_all_dispatches"]["SQ_INSTS_VALU"]
-                    # the vector-ALU roof: lane-instructions per second against CUs x 4 SIMDs x 16 lanes x clock
-                    peak = SIMDS * 16 * a.clock_ghz * 1e9
-                    t_all = round(nst) * lps * secs if whole and secs else None
-                    valu.update({"peak_lane_instructions_per_s": peak, "clock_ghz_assumed": a.clock_ghz,
-                                 "frac_executed": (wi * 64.0 / t_all / peak) if t_all else None,
-                                 "frac_useful": (rate * 40.0 / peak) if rate else None,
-                                 "frac_note": "executed = SQ_INSTS_VALU x 64 lanes / launch time; useful = 40 instructions per pixel-sweep x pixel-sweeps / launch time"})
-                    valu.update({"source": f"profiles/{os.path.basename(f)}", "valu_wave_instructions_all_dispatches": wi,
-                                 "dispatches_in_the_counter_pass": rec["dispatches"], "steps_in_the_counter_pass": nst,
-                                 "valu_lane_instructions_per_px_sweep": (wi * 64.0 / (round(nst) * lps * units_per_launch)) if whole and units_per_launch else None,
-                                 "valu_lane_instructions_per_update_in_the_loop": 40,
-                                 "valu_pipe_busy_per_simd": rec.get("derived", {}).get("valu_pipe_busy_per_simd_all_launches"),
-                                 "simd_cycles_per_valu_inst_all_launches": rec.get("derived", {}).get("simd_cycles_per_valu_inst_all_launches")})
-                    break
-            roof["valu"] = valu
-            # the classifier's word: HBM is this launch's bound only if it runs near the streaming ceiling
-            if limiter and not limiter.startswith("hbm"):
-                roof["bound"] = "valu"
-                roof["bound_note"] = ("set from the counter-derived limiter: the launch keeps its system in registers for 25 sweeps (~35 flop per compulsory byte), "
-                                      "HBM traffic is far from the roof; the hbm figures above stay for the record, roofline.valu holds the fractions of the vector-ALU roof")
-        if algo == "TVL1":
-            # The regime `value` is measured in (three lanes' kernels sharing the GPU), from a stored kernel trace of THIS build's timed steps
-            # (tools/timed_regime.py): the kernel's mean duration while it shares the GPU, the kernels in flight beside it, and its
-            # share-adjusted duration -- the figures above are from launches that had the GPU to themselves.
-            tr_files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_timed_regime.json")))
-            tr = None
-            for f in reversed(tr_files):
-                try:
-                    with open(f) as fh:
-                        rec = json.load(fh).get(kern)
-                except (OSError, ValueError):
-                    rec = None
-                if rec and rec.get("source_fingerprint") == kernel_source_fingerprint():
-                    tr = dict(rec, source=f"profiles/{os.path.basename(f)}")
-                    break
-            if tr is not None:
-                sad = tr["mean_share_adjusted_duration_us"] * 1e-6
-                bytes_launch = traffic if traffic is not None else comp_per_launch
-                tr["bytes_per_launch_used"] = bytes_launch
-                tr["bytes_basis"] = "measured HBM bytes per launch (PMC)" if traffic is not None else "compulsory bytes per launch (30 B per px-iteration)"
-                tr["GBps_at_mean_duration"] = bytes_launch / (tr["mean_duration_us"] * 1e-6) / 1e9
-                tr["GBps_share_adjusted"] = bytes_launch / sad / 1e9
-                tr["frac_of_peak_share_adjusted"] = bytes_launch / sad / 1e9 / HBM_PEAK_GBS
-                tr["compulsory_frac_of_peak_share_adjusted"] = comp_per_launch / sad / 1e9 / HBM_PEAK_GBS
-                roof["timed_regime"] = tr
-            else:
-                roof["timed_regime"] = {"note": "no kernel trace of this build's timed steps under profiles/ (tools/timed_regime.py); the figures above describe launches that had the GPU to themselves"}
-            # algorithmic (compulsory) bytes of the kernel that is actually launched: 9 plane reads + 6 writes once per TWO iterations
-            roof["algorithmic_GBps_30B"] = rate * 30.0 / 1e9 if rate else None
-            roof["algorithmic_bytes_per_launch_30B"] = units_per_launch * 30.0
-            roof["notional_GBps_60B"] = rate * 60.0 / 1e9 if rate else None     # one-iteration-per-pass kernel's compulsory traffic
-            roof["notional_GBps_88B"] = rate * 88.0 / 1e9 if rate else None     # two-kernel K_A/K_B formulation
-            roof["notional_note"] = ("what kernels that make one HBM pass per inner iteration would have had to move at this rate; the shipped kernel "
-                                     "makes one pass per TWO iterations, so these exceed its real traffic and are not roofline fractions")
-            full = None
-            if prof is not None and len(prof[3]):
-                lv, wp, it, ms = prof
-                m = (lv == 0) & (it == 0) & (ms > 0)             # first launch of a level-0 stage: all B pairs iterate, 2 iterations
-                if m.any():
-                    full = float(np.median(SUB * H * W * 2.0 / (ms[m] * 1e-3)))      # (the instrumented calls hold SUB pairs each)
-            isa, why = stored_record("isa_stats.json", kern)
-            valu = {"px_iterations_per_s_all_launches": rate, "px_iterations_per_s_full_launches": full}
-            if isa:
-                ipp = isa["valu_insts_per_wave_step"] / isa["px_iterations_per_wave_step"]
-                valu.update({"valu_insts_per_px_iteration": ipp, "vgprs": isa.get("vgprs"), "waves_per_simd": isa.get("waves_per_simd"),
-                             "isa_source": "profiles/isa_stats.json (disassembly of this build's main loop)",
-                             "simd_cycles_per_valu_inst_full_launches": (a.clock_ghz * 1e9 * SIMDS / (full * ipp) if full else None),
-                             "clock_ghz_assumed": a.clock_ghz})
-            else:
-                valu["isa_source"] = why
-            roof["valu"] = valu
         out = {
             "metric": "frame-pairs/sec @512x512 " + ("DualTVL1" if algo == "TVL1" else "DeepFlow"), "value": pairs / dt, "unit": "frame-pairs/s",
             "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
@@ -717,12 +752,13 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
                        "lanes_per_sub_batch_call": a.lanes if B <= SUB and E == 1 else (a.lanes if algo != "TVL1" else 1)},
             # data-independent rate of the whole job: executed pixel-iterations (pixel-sweeps) per second of the timed region
             ("px_iterations_per_s" if algo == "TVL1" else "px_sweeps_per_s"): world * acc["timed_iter_bytes"] / unit_bytes / dt,
-            "roofline": roof,
             # NOT a bandwidth: the bytes a one-HBM-pass-per-iteration (per-sweep) formulation would move, over the device time.  The shipped
             # kernels make one pass per two iterations / per 25 sweeps, so this exceeds their traffic (and may exceed the HBM peak).
             "notional_whole_solve_GBps_one_pass_per_iteration": acc["total_bytes"] / 1e9 / (acc["ms_device"] / 1e3) if acc["ms_device"] else None,
         }
-        if not a.no_profile and algo == "TVL1":
+        if a.full:
+            out["roofline"] = roofline_record(a, algo, acc, steps, SUB, H, W, live_pmc, prof)
+        if a.full and not a.no_profile and algo == "TVL1":
             # where a step's device time goes, from the library's own event pairs (instrumented single-lane repeats)
             out["stage_ms_per_step"] = {"tvl1_iter": acc["iter_ms"] / steps, "warp": acc.get("p_ms_warp", 0.0) / steps,
                                         "median": acc.get("p_ms_median", 0.0) / steps, "device_total": acc.get("p_ms_device", 0.0) / steps,
@@ -732,7 +768,7 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
             out["executed_outer_iterations_per_pair"] = acc["outer"] / (B * steps)
             out["data_dependence_note"] = ("pairs/s depends on how early the synthetic pairs converge (executed inner iterations per pair above, of a "
                                            "possible 7500); px_iterations_per_s does not")
-        if algo != "TVL1":
+        if a.full and algo != "TVL1":
             # the co-resident SOR form: launches since the engine was made, and calls that had to be repeated tiled because a launch gave up waiting
             out["sor_coresident"] = {"launches": eng.counter("coop_launches"), "calls_repeated_tiled": eng.counter("coop_aborts")}
         if joined is not None:
@@ -743,8 +779,8 @@ def run_leg(a, algo, B, steps, warmup, I0s, I1s, torch, dist, dev, rank, world, 
             out["allgather_checksums_match"] = gather_ok
         if dumped is not None:
             out["dumped_outputs"] = dumped
-    if rank == 0 and not a.steps_only:
-        # single-pair latency (BASELINE configs[1] as a latency number), outside the timed region
+    if rank == 0 and a.full and not a.steps_only:
+        # --full: single-pair latency (BASELINE configs[1] as a latency number), outside the timed region
         lat_eng = T.DenseFlow(device_id=local_rank, max_batch=1, algo=algo)
         for k, v in tuning:
             lat_eng.set_tuning(k, int(v))
@@ -832,18 +868,21 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="frame pairs per GPU per step = per call of the boundary (default 384 DualTVL1, 128 DeepFlow)")
     ap.add_argument("--sub-batch", type=int, default=128, help="pairs per sub-batch = the engine's max_batch (BASELINE configs[2]'s per-GPU shard size)")
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, measure and check everything else: the other forms of the step, the roofline, "
+                                                        "latency, saliency, the PCIe step, the CPU baselines and the DeepFlow leg "
+                                                        "(the options below that trim these apply to a --full run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=8)
     ap.add_argument("--no-profile", action="store_true", help="do not bracket tvl1_iter launches with HIP events")
     ap.add_argument("--algo", default="TVL1", choices=["TVL1", "deepflow"], help="BASELINE configs[1..2] (TVL1, default) or configs[3] (deepflow) as the main leg")
-    ap.add_argument("--no-deepflow", action="store_true", help="skip the DeepFlow leg the default N=1 TVL1 run appends")
+    ap.add_argument("--no-deepflow", action="store_true", help="skip the DeepFlow leg a --full N=1 TVL1 run appends (and its --dump-outputs file)")
     ap.add_argument("--deepflow-batch", type=int, default=128, help="pairs per step of the DeepFlow leg (64 pairs: 577, 128: 601-607, 256: 608 pairs/s on one MI355X)")
     ap.add_argument("--deepflow-steps", type=int, default=None, help="timed steps of the DeepFlow leg (default: --steps; its warm-up is --warmup)")
-    ap.add_argument("--pmc", action="store_true", help="N=1 only: first run the FETCH_SIZE / WRITE_SIZE counter passes of this command as child "
+    ap.add_argument("--pmc", action="store_true", help="N=1 only, implies --full: first run the FETCH_SIZE / WRITE_SIZE counter passes of this command as child "
                                                        "processes under rocprofv3 (adds ~1-2 min), so roofline.traffic is measured in this run")
     ap.add_argument("--pmc-dir", default=os.path.join(ROOT, "gpurun_out", "pmc_live"))
     ap.add_argument("--round-tag", default="r05")
-    ap.add_argument("--steps-only", action="store_true", help="only the timed steps: no single-pair latency, no PCIe step (what the counter passes profile)")
+    ap.add_argument("--steps-only", action="store_true", help="--full without the single-pair latency, saliency, PCIe steps, CPU baselines and other forms of the step")
     ap.add_argument("--in-flight", type=int, default=1, help="1 = every step is one synchronous call (default); E > 1 = steps are submitted with tf_submit_pairs_device, "
                                                              "E in flight (the library's lanes overlap them; one host thread)")
     ap.add_argument("--lanes", type=int, default=2, help="contiguous parts a call of at most one sub-batch is split over (joined at its end); 1 for clean per-kernel profiles")
@@ -854,8 +893,10 @@ def main():
     ap.add_argument("--clock-ghz", type=float, default=2.4, help="shader clock assumed for the cycles-per-instruction figure (max clock; DESIGN.md notes 2.32 held under load)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the flows each leg's last timed step returned as DIR/<algo>_flows.npy (float32; a fixed, "
-                         "seeded sample of the pairs, at most 48 MiB in all) so that two builds can be compared output for output")
+                         "seeded sample of the pairs, at most 48 MiB in all) so that two builds can be compared output for output; without --full "
+                         "the DeepFlow leg is not timed and its file holds the flows of one call of its pairs")
     a = ap.parse_args()
+    a.full = a.full or a.pmc
     if a.steps < 1 or a.warmup < 0 or (a.deepflow_steps is not None and a.deepflow_steps < 1):
         ap.error("--steps and --deepflow-steps must be at least 1, --warmup at least 0")
 
@@ -876,8 +917,8 @@ def main():
     if a.batch is None:
         a.batch = 384 if a.algo == "TVL1" else 128
     B, H, W = a.batch, a.size, a.size
-    I0s, I1s = make_inputs(range(rank * B, (rank + 1) * B), H, W)          # rank r owns pairs [rB, (r+1)B): no data-path exchange
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not under_profiler():
+    I0s, I1s = make_inputs(range(rank * B, (rank + 1) * B), H, W, cache=False)    # rank r owns pairs [rB, (r+1)B): no data-path exchange
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not under_profiler():
         from oracle import oracle as O
         err = O.build_o3()                      # the timed baseline build is machine-specific: compile it here, before any GPU call
         if err:
@@ -908,7 +949,10 @@ def main():
     dump_bytes = DUMP_BYTES // (2 if want_df else 1) if a.dump_outputs else 0
     out = run_leg(a, a.algo, B, a.steps, a.warmup, I0s, I1s, torch, dist, dev, rank, world, local_rank,
                   live_pmc=live.get(a.algo), cpu_sample=a.cpu_sample, dump_bytes=dump_bytes)
-    if want_df:
+    if want_df and a.dump_outputs and not a.full:
+        out["deepflow"] = {"dumped_outputs": dump_untimed_leg(a, "deepflow", DB, I0s[:DB], I1s[:DB], torch, dev, local_rank, dump_bytes),
+                           "note": f"not timed without --full: the flows of one call of the leg's {DB} pairs"}
+    elif want_df and a.full:
         df_steps = a.steps if a.deepflow_steps is None else a.deepflow_steps
         df = run_leg(a, "deepflow", DB, df_steps, a.warmup, I0s[:DB], I1s[:DB], torch, dist, dev, rank, world, local_rank,
                      live_pmc=live.get("deepflow"), cpu_sample=2, dump_bytes=dump_bytes)
@@ -917,6 +961,7 @@ def main():
             out["deepflow"] = df
     if rank == 0:
         out["kernel_source_fingerprint"] = kernel_source_fingerprint()
+        out["full"] = a.full
         if live:
             # the counter passes of this run, in the form profiles/hbm_traffic.json keeps (copy it there to have later
             # runs of the SAME build report the traffic without --pmc)

@@ -52,6 +52,23 @@ def test_profiler_detection_and_input_cache(tmp_path, monkeypatch):
     assert np.array_equal(a0[1], speckle_pair(4, 40, 48)[0])
 
 
+def test_bench_run_inputs_do_not_come_from_an_earlier_run(tmp_path, monkeypatch):
+    """A benchmark run (make_inputs(..., cache=False)) generates its pairs afresh: it neither reads a cache file an earlier run left
+    under $TMPDIR, however wrong that file is, nor leaves one for a later run."""
+    import bench
+    monkeypatch.setenv("TMPDIR", str(tmp_path))
+    a0, a1 = bench.make_inputs([3, 4], 40, 48, allow_pool=False)          # fills the cache
+    (cached,) = os.listdir(tmp_path)
+    np.savez(tmp_path / cached, I0s=np.zeros_like(a0), I1s=np.zeros_like(a1))
+    b0, b1 = bench.make_inputs([3, 4], 40, 48, allow_pool=False, cache=False)
+    assert np.array_equal(a0, b0) and np.array_equal(a1, b1)
+    assert os.listdir(tmp_path) == [cached]
+    c0, _ = bench.make_inputs([5], 40, 48, allow_pool=False, cache=False)
+    assert os.listdir(tmp_path) == [cached]
+    from tee_optical_flow_amd.synth import speckle_pair
+    assert np.array_equal(c0[0], speckle_pair(5, 40, 48)[0])
+
+
 def test_fetch_factors_and_committed_records_are_well_formed():
     import bench
     for algo in ("TVL1", "deepflow"):                            # calibrated on the GPU (profiles/r03_fetch_calibration.json): 2.0 at every width

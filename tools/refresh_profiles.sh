@@ -35,11 +35,11 @@ timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/regime -o
 echo "regime trace rc=$?"
 python3 $GRAFT_REPO_ROOT/tools/timed_regime.py $OUT/regime $TAG --steps 6 --out $GRAFT_REPO_ROOT/gpurun_out/collected_$TAG > $OUT/timed_regime.log 2>&1; tail -1 $OUT/timed_regime.log
 [ -f $GRAFT_REPO_ROOT/gpurun_out/collected_$TAG/${TAG}_timed_regime.json ] && cp $GRAFT_REPO_ROOT/gpurun_out/collected_$TAG/${TAG}_timed_regime.json $GRAFT_REPO_ROOT/profiles/
-run_stats default
-run_stats lanes1 --batch 128 --lanes 1 --no-cpu-baseline
+run_stats default --full
+run_stats lanes1 --full --batch 128 --lanes 1 --no-cpu-baseline
 # one algorithm per profiled command (the combined tables need arithmetic to read per-algorithm shares)
-run_stats tvl1_lanes1 --batch 128 --lanes 1 --no-cpu-baseline --no-deepflow
-run_stats deepflow_lanes1 --lanes 1 --no-cpu-baseline --algo deepflow
+run_stats tvl1_lanes1 --full --batch 128 --lanes 1 --no-cpu-baseline --no-deepflow
+run_stats deepflow_lanes1 --full --lanes 1 --no-cpu-baseline --algo deepflow
 # the no_saliency=False preprocessing by itself
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/saliency -o saliency -- python3 $GRAFT_REPO_ROOT/tools/saliency_bench.py > $OUT/${TAG}_saliency_bench.txt 2> $OUT/saliency.err
 echo "saliency rc=$?"

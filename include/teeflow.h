@@ -49,7 +49,7 @@ extern "C" {
 
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
-                              tf_clean_masks */
+                              tf_clean_masks, tf_av_centroids and tf_radlong_project_param */
 
 enum {
     TF_OK = 0,
@@ -241,6 +241,31 @@ int tf_radlong_project(tf_handle* h, const float* flow, const double* centroids,
                        double* rad_out, double* long_out, double* minmax, long long* nonzero);
 int tf_radlong_hist(tf_handle* h, int which, const double* edges, int nbins, long long* freq_out);
 int tf_radlong_select(tf_handle* h, int which, const long long* ranks, double* values_out);
+
+/* ---- the steps before the projection in calculate_3dhist_radlong(ds, param) (optical_flow/analyze_optical_flow.py:320-343), on the
+ *      device.  Both run on the handle's stream and never on a lane's, so they may be called while tf_submit_* jobs of the handle are
+ *      in flight; both are host-synchronous; every argument is checked before any GPU work.
+ * tf_av_centroids: calc_AV_centroid's per-frame loop (optical_flow/analyze_optical_flow.py:202-232, find_correct_centroid :202-211).
+ *   masks: host uint8 [N][H][W][C], C = 1 or 2; frame n's set is masks[n][.][.][0] != 0, labelled with 8-connectivity
+ *   (skimage.measure.label of a bool image).  centroids_out[n] = (row, col) centroid of the largest component (on a tie in area: the
+ *   one whose first pixel in raster order comes first), exactly regionprops' coords.mean(axis=0); area_out[n] = its area, 0 for an
+ *   empty frame (centroid (0, 0): the caller applies the reference's empty-frame rule, and the Savitzky-Golay filter).  Device
+ *   scratch, grown on demand and kept by the handle: (26 + C) bytes per pixel of a chunk of frames of at most 512 MiB (at least one).
+ * tf_radlong_project_param: tf_radlong_project of the parameter field OpticalFlowDataset builds (optical_flow/optical_flow_dataset.py:57,
+ *   100-101, 182-228): vel = float32(flow); accel = np.gradient(vel, spacing, axis=0) over all N frames; pwr = vel * accel; each
+ *   multiplied by the mask, all float32 as numpy keeps them.  flow: host [N][H][W][2], float16 (flow_is_f16, as the study file holds it)
+ *   or float32; only the frames the first n_used need are read.  mask: host uint8 [>= n_used][H][W][mask_C] (mask_C = 1: channel 0 for
+ *   both components).  grad_f64 = 1 when the gradient's division runs in float64 in the caller's numpy (a np.float64 spacing under
+ *   NEP 50), 0 for float32; spacing must be finite and non-zero for acceleration and PWR, which need N >= 2.  centroids: [n_used][2].
+ *   Outputs as tf_radlong_project, for frames [0, n_used); the projections stay resident for tf_radlong_hist / tf_radlong_select.
+ *   The resident planes and the upload scratch are grown on demand and kept by the handle. */
+#define TF_PARAM_VELOCITY 0
+#define TF_PARAM_ACCELERATION 1
+#define TF_PARAM_PWR 2
+int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* centroids_out, long long* area_out);
+int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
+                             int mask_C, int param, double spacing, int grad_f64, const double* centroids, double* rad_out,
+                             double* long_out, double* minmax, long long* nonzero);
 
 /* ---- multi-GPU: the single exchange step of the path.  The reference's loop is sequential
  *      (calculate_optical_flow.py:584-597); here pairs shard over the GPUs of a node with no data-path traffic during the

@@ -17,6 +17,7 @@
 #include "teeflow_wase.hip.h"
 #include "teeflow_saliency.hip.h"
 #include "teeflow_masks.hip.h"
+#include "teeflow_centroid.hip.h"
 #include "../../include/teeflow.h"
 #include <rccl/rccl.h>      // types and prototypes only: librccl is loaded with dlopen when a communicator is first asked for
 #include <dlfcn.h>
@@ -148,11 +149,14 @@ struct tf_handle : TfKnobs {
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
            PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks
+           PRE_CT_MASK, PRE_CT_PAR, PRE_CT_LR, PRE_CT_AREA, PRE_CT_SUM, PRE_CT_OUT,  // tf_av_centroids
+           PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // tf_radlong_project_param
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     // ---- analysis session (row f1) ----
     double* an_rad = nullptr; double* an_lon = nullptr; int anN = 0, anH = 0, anW = 0;
+    size_t an_cap = 0;           // doubles an_rad and an_lon each hold (tf_radlong_project_param grows them, never shrinks)
     int lanes = 2;               // an idle call of one sub-batch, >= 32 pairs, is split in this many contiguous units solved side by side on the
                                  // queue lanes: while one runs the thin tail of a stage, the other fills the GPU.  Measured at 128 pairs
                                  // @512^2: 1 lane 2180, 2 lanes 2470, 3 lanes 2415, 4 lanes 2165 pairs/s (DeepFlow 377 vs 309)
@@ -313,7 +317,7 @@ void free_buffers(tf_handle* h)
     F(h->ctl); F(h->errs); F(h->iters_dev);
     F(h->st_u8); F(h->st_flow);
     F(h->dpyr_base); F(h->dtmp); F(h->dplanes); F(h->coop_flags); h->coop_flag_lines = 0;
-    F(h->an_rad); F(h->an_lon); h->anN = 0;
+    F(h->an_rad); F(h->an_lon); h->anN = 0; h->an_cap = 0;
     h->dnlev = h->dH = h->dW = h->dcap = 0;
     h->st_u8_bytes = h->st_flow_bytes = 0;
     h->H = h->W = h->cap = h->nlev = 0; h->iters_cap = 0;
@@ -2130,8 +2134,10 @@ TF_API int tf_radlong_project(tf_handle* h, const float* flow, const double* cen
     if (h->an_rad) { (void)hipFree(h->an_rad); h->an_rad = nullptr; }
     if (h->an_lon) { (void)hipFree(h->an_lon); h->an_lon = nullptr; }
     h->anN = 0;
+    h->an_cap = 0;
     HIPC(h, hipMalloc(&h->an_rad, tot * sizeof(double)));
     HIPC(h, hipMalloc(&h->an_lon, tot * sizeof(double)));
+    h->an_cap = tot;
     float* dflow = nullptr; double* dcent = nullptr; u64* mm = nullptr; unsigned long long* cnt = nullptr;
     hipError_t e = hipMalloc(&dflow, tot * 2 * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&dcent, (size_t)N * 2 * sizeof(double));
@@ -2215,6 +2221,154 @@ TF_API int tf_radlong_select(tf_handle* h, int which, const long long* ranks, do
     if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_radlong_select: %s", hipGetErrorString(e));
     for (int i = 0; i < NS; ++i) values_out[i] = act[i] ? f64_unkey(keys[i]) : 0.0;
     return TF_OK;
+}
+
+namespace {
+// tf_av_centroids: frames go through in chunks so that the per-chunk scratch (26 B per pixel + the mask bytes) stays within
+// MASK_CHUNK_BYTES whatever the study's length
+int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* cent_out, long long* area_out)
+{
+    using namespace cen;
+    const size_t HW = (size_t)H * W;
+    if (HW > 0x7fffffffu) return fail(h, TF_ERR_UNSUPPORTED, "tf_av_centroids: at most 2^31 - 1 pixels per frame");
+    const size_t per_frame = HW * (26 + (size_t)C);
+    size_t nf = MASK_CHUNK_BYTES / per_frame;
+    if (nf > (size_t)N) nf = (size_t)N;
+    if (nf > 65535) nf = 65535;                                // frames of a chunk are grid.y
+    if (nf < 1) nf = 1;
+    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
+    HIPC(h, hipSetDevice(h->dev));
+    uint8_t* dm = nullptr; uint32_t* dpar = nullptr; uint16_t* dlr = nullptr; uint32_t* darea = nullptr; unsigned long long* dsum = nullptr;
+    uint8_t* out = nullptr;                                    // [0, 64): error word, then centroids [N][2] f64, then areas [N] i64
+    int rc;
+    if ((rc = pre_grow(h, tf_handle::PRE_CT_MASK, nf * HW * C, (void**)&dm)) ||
+        (rc = pre_grow(h, tf_handle::PRE_CT_PAR, nf * HW * 4, (void**)&dpar)) ||
+        (rc = pre_grow(h, tf_handle::PRE_CT_LR, nf * HW * 2, (void**)&dlr)) ||
+        (rc = pre_grow(h, tf_handle::PRE_CT_AREA, nf * HW * 4, (void**)&darea)) ||
+        (rc = pre_grow(h, tf_handle::PRE_CT_SUM, nf * HW * 16, (void**)&dsum)) ||
+        (rc = pre_grow(h, tf_handle::PRE_CT_OUT, 64 + (size_t)N * 24, (void**)&out))) return rc;
+    unsigned* derr = (unsigned*)out;
+    double* dcent = (double*)(out + 64);
+    long long* dar = (long long*)(out + 64 + (size_t)N * 16);
+    const hipStream_t s = h->stream;
+    HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
+    for (int f0 = 0; f0 < N; f0 += (int)nf) {
+        const int n = N - f0 < (int)nf ? N - f0 : (int)nf;
+        const dim3 g(tiles, (unsigned)n), blk(256);
+        HIPC(h, hipMemcpyAsync(dm, masks + (size_t)f0 * HW * C, (size_t)n * HW * C, hipMemcpyHostToDevice, s));
+        HIPC(h, hipMemsetAsync(darea, 0, (size_t)n * HW * 4, s));
+        HIPC(h, hipMemsetAsync(dsum, 0, (size_t)n * HW * 16, s));
+        hipLaunchKernelGGL(k_cent_local, g, blk, 0, s, dm, C, dpar, dlr, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_cent_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_cent_flatten, g, blk, 0, s, dpar, dlr, darea, dsum, H, W, tiles_x);
+        hipLaunchKernelGGL(k_cent_pick, dim3((unsigned)n), blk, 0, s, dpar, darea, dsum, HW, dcent + 2 * (size_t)f0, dar + f0);
+        HIPC(h, hipGetLastError());
+    }
+    unsigned e = 0;
+    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(cent_out, dcent, (size_t)N * 16, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(area_out, dar, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    if (e) return fail(h, TF_ERR_HIP, "tf_av_centroids: a union-find loop ran out of its bound (code %u)", e);
+    return TF_OK;
+}
+
+template <int PARAM, typename FT>
+void launch_project_param(dim3 g, hipStream_t s, const void* flow, int N, const uint8_t* mask, int C, double sp, int grad_f64, const double* cent,
+                          int H, int W, double* rad, double* lon, u64* mm, unsigned long long* cnt)
+{
+    if (grad_f64)
+        hipLaunchKernelGGL((k_radlong_project_param<PARAM, FT, double>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, cent, H, W, rad, lon, mm, cnt);
+    else
+        hipLaunchKernelGGL((k_radlong_project_param<PARAM, FT, float>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, cent, H, W, rad, lon, mm, cnt);
+}
+
+int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
+                          double spacing, int grad_f64, const double* centroids, double* rad_out, double* long_out, double* minmax,
+                          long long* nonzero)
+{
+    const size_t npx = (size_t)H * W, tot = (size_t)n_used * npx;
+    const int nflow = param == RL_PARAM_VELOCITY ? n_used : (n_used + 1 < N ? n_used + 1 : N);   // frames the gradient of [0, n_used) reads
+    const size_t flow_bytes = (size_t)nflow * npx * 2 * (f16 ? 2 : 4);
+    HIPC(h, hipSetDevice(h->dev));
+    h->anN = 0;
+    if (h->an_cap < tot) {
+        HIPC(h, hipStreamSynchronize(h->stream));
+        if (h->an_rad) { (void)hipFree(h->an_rad); h->an_rad = nullptr; }
+        if (h->an_lon) { (void)hipFree(h->an_lon); h->an_lon = nullptr; }
+        h->an_cap = 0;
+        HIPC(h, hipMalloc(&h->an_rad, tot * sizeof(double)));
+        HIPC(h, hipMalloc(&h->an_lon, tot * sizeof(double)));
+        h->an_cap = tot;
+    }
+    void* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr;   // meta: min/max keys [4], counts [n_used][2], centroids [n_used][2]
+    int rc;
+    if ((rc = pre_grow(h, tf_handle::PRE_AN_FLOW, flow_bytes, &dflow)) ||
+        (rc = pre_grow(h, tf_handle::PRE_AN_MASK, tot * C, (void**)&dmask)) ||
+        (rc = pre_grow(h, tf_handle::PRE_AN_META, 32 + (size_t)n_used * 32, (void**)&meta))) return rc;
+    u64* mm = (u64*)meta;
+    unsigned long long* cnt = (unsigned long long*)(meta + 32);
+    double* dcent = (double*)(meta + 32 + (size_t)n_used * 16);
+    const u64 mm0[4] = {~0ull, 0ull, ~0ull, 0ull};
+    u64 mmh[4];
+    std::vector<unsigned long long> ch((size_t)n_used * 2);
+    const hipStream_t s = h->stream;
+    HIPC(h, hipMemcpyAsync(dflow, flow, flow_bytes, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(dmask, mask, tot * C, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(dcent, centroids, (size_t)n_used * 16, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(mm, mm0, sizeof mm0, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemsetAsync(cnt, 0, (size_t)n_used * 16, s));
+    const int gx = (int)((npx + 255) / 256);
+    const dim3 g(gx < 256 ? gx : 256, n_used);
+#define TF_PP(P) (f16 ? launch_project_param<P, _Float16>(g, s, dflow, N, dmask, C, spacing, grad_f64, dcent, H, W, h->an_rad, h->an_lon, mm, cnt) \
+                      : launch_project_param<P, float>(g, s, dflow, N, dmask, C, spacing, grad_f64, dcent, H, W, h->an_rad, h->an_lon, mm, cnt))
+    if (param == RL_PARAM_VELOCITY) TF_PP(RL_PARAM_VELOCITY);
+    else if (param == RL_PARAM_ACCELERATION) TF_PP(RL_PARAM_ACCELERATION);
+    else TF_PP(RL_PARAM_PWR);
+#undef TF_PP
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(mmh, mm, sizeof mmh, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (rad_out) HIPC(h, hipMemcpyAsync(rad_out, h->an_rad, tot * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (long_out) HIPC(h, hipMemcpyAsync(long_out, h->an_lon, tot * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    for (int j = 0; j < 4; ++j) minmax[j] = f64_unkey(mmh[j]);
+    for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
+    h->anN = n_used; h->anH = H; h->anW = W;
+    return TF_OK;
+}
+
+// a failed call leaves nothing of it running: its destinations are host memory the caller may free at once
+int finish_host_call(tf_handle* h, int rc)
+{
+    if (rc != TF_OK) {
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+}  // namespace
+
+static_assert(TF_PARAM_VELOCITY == RL_PARAM_VELOCITY && TF_PARAM_ACCELERATION == RL_PARAM_ACCELERATION && TF_PARAM_PWR == RL_PARAM_PWR,
+              "param codes of the header and the kernel differ");
+
+// Argument checks return before the handle is touched (no message: the Python layer checks the same first and says why).
+TF_API int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* centroids_out, long long* area_out)
+{
+    if (!h || !masks || !centroids_out || !area_out || N < 1 || H < 1 || W < 1 || (C != 1 && C != 2)) return TF_ERR_INVALID_ARG;
+    return finish_host_call(h, av_centroids(h, masks, N, H, W, C, centroids_out, area_out));
+}
+
+TF_API int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
+                                    int mask_C, int param, double spacing, int grad_f64, const double* centroids, double* rad_out,
+                                    double* long_out, double* minmax, long long* nonzero)
+{
+    if (!h || !flow || !mask || !centroids || !minmax || !nonzero || N < 1 || n_used < 1 || H < 1 || W < 1 || n_used > N) return TF_ERR_INVALID_ARG;
+    if ((mask_C != 1 && mask_C != 2) || param < TF_PARAM_VELOCITY || param > TF_PARAM_PWR) return TF_ERR_INVALID_ARG;
+    if (param != TF_PARAM_VELOCITY && (N < 2 || !std::isfinite(spacing) || spacing == 0.0)) return TF_ERR_INVALID_ARG;   // np.gradient needs 2 frames
+    if (n_used > 65535) return TF_ERR_UNSUPPORTED;                                                                     // frames are grid.y
+    return finish_host_call(h, radlong_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
+                                                     centroids, rad_out, long_out, minmax, nonzero));
 }
 
 // pinned host memory for results: a destination allocated here makes the host-pointer entry points copy out at PCIe

@@ -20,34 +20,31 @@ __host__ __device__ inline double f64_unkey(u64 k)
     return c.d;
 }
 
-// rad/long planes [N][H][W] (f64), global min/max keys of both, per-frame non-zero counts
-__global__ __launch_bounds__(256) void k_radlong_project(const float* __restrict__ flow, const double* __restrict__ cent, int H, int W,
-                                                         double* __restrict__ rad, double* __restrict__ lon, u64* __restrict__ mm /* [4]: rad min,max, long min,max */,
-                                                         unsigned long long* __restrict__ cnt /* [N][2] */)
+// one pixel of the projection: rad/long of the float32 field (fx, fy) at pixel i of frame n around the centroid (cH, cW), folded into
+// the thread's min/max keys and non-zero counts
+__device__ __forceinline__ void radlong_px(float fx, float fy, double cH, double cW, int W, int n, size_t npx, size_t i, double* __restrict__ rad,
+                                           double* __restrict__ lon, u64 (&k)[4], unsigned& c0, unsigned& c1)
+{
+    const int hh = (int)(i / W), ww = (int)(i - (size_t)hh * W);
+    const double dh = cH - (double)hh, dw = cW - (double)ww;
+    const double nrm = sqrt(dh * dh + dw * dw);
+    double u0 = dh / nrm, u1 = dw / nrm;
+    u0 = u0 == u0 ? u0 : 0.0; u1 = u1 == u1 ? u1 : 0.0;         // nan_to_num(nan=0): the centroid pixel itself
+    const double r = (double)fx * u0 + (double)fy * u1;           // sum(OF * unitvec): note OF[...,0] (x) meets the ROW component
+    const double l = (double)fx * u1 + (double)fy * (-1.0 * u0);
+    rad[(size_t)n * npx + i] = r;
+    lon[(size_t)n * npx + i] = l;
+    const u64 kr = f64_key(r), kl = f64_key(l);
+    k[0] = kr < k[0] ? kr : k[0]; k[1] = kr > k[1] ? kr : k[1];
+    k[2] = kl < k[2] ? kl : k[2]; k[3] = kl > k[3] ? kl : k[3];
+    c0 += r != 0.0; c1 += l != 0.0;
+}
+
+// the block's min/max keys and non-zero counts into the global ones (256 threads)
+__device__ __forceinline__ void radlong_reduce(u64 (&k)[4], unsigned c0, unsigned c1, int n, u64* __restrict__ mm, unsigned long long* __restrict__ cnt)
 {
     __shared__ u64 s[4][4];
     __shared__ unsigned sc[4][2];
-    const int n = blockIdx.y;
-    const size_t npx = (size_t)H * W;
-    const double cH = cent[2 * n], cW = cent[2 * n + 1];
-    u64 k[4] = {~0ull, 0ull, ~0ull, 0ull};
-    unsigned c0 = 0, c1 = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
-        const int hh = (int)(i / W), ww = (int)(i - (size_t)hh * W);
-        const double dh = cH - (double)hh, dw = cW - (double)ww;
-        const double nrm = sqrt(dh * dh + dw * dw);
-        double u0 = dh / nrm, u1 = dw / nrm;
-        u0 = u0 == u0 ? u0 : 0.0; u1 = u1 == u1 ? u1 : 0.0;         // nan_to_num(nan=0): the centroid pixel itself
-        const float2 f = reinterpret_cast<const float2*>(flow)[(size_t)n * npx + i];
-        const double r = (double)f.x * u0 + (double)f.y * u1;         // sum(OF * unitvec): note OF[...,0] (x) meets the ROW component
-        const double l = (double)f.x * u1 + (double)f.y * (-1.0 * u0);
-        rad[(size_t)n * npx + i] = r;
-        lon[(size_t)n * npx + i] = l;
-        const u64 kr = f64_key(r), kl = f64_key(l);
-        k[0] = kr < k[0] ? kr : k[0]; k[1] = kr > k[1] ? kr : k[1];
-        k[2] = kl < k[2] ? kl : k[2]; k[3] = kl > k[3] ? kl : k[3];
-        c0 += r != 0.0; c1 += l != 0.0;
-    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
@@ -68,6 +65,65 @@ __global__ __launch_bounds__(256) void k_radlong_project(const float* __restrict
         atomicMin(&mm[0], k[0]); atomicMax(&mm[1], k[1]); atomicMin(&mm[2], k[2]); atomicMax(&mm[3], k[3]);
         atomicAdd(&cnt[2 * n], (unsigned long long)c0); atomicAdd(&cnt[2 * n + 1], (unsigned long long)c1);
     }
+}
+
+// rad/long planes [N][H][W] (f64), global min/max keys of both, per-frame non-zero counts
+__global__ __launch_bounds__(256) void k_radlong_project(const float* __restrict__ flow, const double* __restrict__ cent, int H, int W,
+                                                         double* __restrict__ rad, double* __restrict__ lon, u64* __restrict__ mm /* [4]: rad min,max, long min,max */,
+                                                         unsigned long long* __restrict__ cnt /* [N][2] */)
+{
+    const int n = blockIdx.y;
+    const size_t npx = (size_t)H * W;
+    const double cH = cent[2 * n], cW = cent[2 * n + 1];
+    u64 k[4] = {~0ull, 0ull, ~0ull, 0ull};
+    unsigned c0 = 0, c1 = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
+        const float2 f = reinterpret_cast<const float2*>(flow)[(size_t)n * npx + i];
+        radlong_px(f.x, f.y, cH, cW, W, n, npx, i, rad, lon, k, c0, c1);
+    }
+    radlong_reduce(k, c0, c1, n, mm, cnt);
+}
+
+// The parameter field of OpticalFlowDataset (/root/reference/optical_flow/optical_flow_dataset.py:57, 100-101, 182-228) fused into the
+// projection: vel = flow.astype(float32); accel = np.gradient(vel, h, axis=0); pwr = vel * accel; field = param * mask.
+// np.gradient's output has vel's dtype (float32); T is the type its division runs in (numpy's promotion of float32 by the caller's
+// spacing h: float, or double for a np.float64 h under NEP 50): interior (v[n+1] - v[n-1]) / (2.0 * h), frames 0 and N-1 the one-sided
+// difference / h (edge_order 1), each difference in float32 and each quotient rounded to float32.  pwr and the mask product are float32
+// (a bool mask multiplies by 0 or 1).  Frames [0, n_used) are projected; the gradient sees all N.
+enum { RL_PARAM_VELOCITY = 0, RL_PARAM_ACCELERATION = 1, RL_PARAM_PWR = 2 };
+
+template <typename FT>
+__device__ __forceinline__ float2 rl_ld(const FT* __restrict__ f, size_t j) { return make_float2((float)f[2 * j], (float)f[2 * j + 1]); }
+
+template <int PARAM, typename FT, typename T>
+__global__ __launch_bounds__(256) void k_radlong_project_param(const FT* __restrict__ flow /* [>= n_used (+1)][H][W][2] */, int N,
+                                                               const uint8_t* __restrict__ mask /* [n_used][H][W][C] */, int C, double h,
+                                                               const double* __restrict__ cent, int H, int W, double* __restrict__ rad,
+                                                               double* __restrict__ lon, u64* __restrict__ mm, unsigned long long* __restrict__ cnt)
+{
+    const int n = blockIdx.y;
+    const size_t npx = (size_t)H * W;
+    const double cH = cent[2 * n], cW = cent[2 * n + 1];
+    u64 k[4] = {~0ull, 0ull, ~0ull, 0ull};
+    unsigned c0 = 0, c1 = 0;
+    const bool edge = n == 0 || n == N - 1;
+    const int lo = edge ? (n == 0 ? 0 : N - 2) : n - 1, hi = edge ? lo + 1 : n + 1;
+    const T den = edge ? (T)h : (T)(2.0 * h);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
+        const float2 v = rl_ld(flow, (size_t)n * npx + i);
+        float fx = v.x, fy = v.y;
+        if (PARAM != RL_PARAM_VELOCITY) {
+            const float2 a = rl_ld(flow, (size_t)lo * npx + i), b = rl_ld(flow, (size_t)hi * npx + i);
+            const float gx = (float)((T)(b.x - a.x) / den), gy = (float)((T)(b.y - a.y) / den);
+            fx = PARAM == RL_PARAM_PWR ? v.x * gx : gx;
+            fy = PARAM == RL_PARAM_PWR ? v.y * gy : gy;
+        }
+        const uint8_t* mp = mask + ((size_t)n * npx + i) * C;
+        fx = fx * (float)mp[0];
+        fy = fy * (float)mp[C - 1];                                // C == 1: channel 0 for both components (numpy broadcasting)
+        radlong_px(fx, fy, cH, cW, W, n, npx, i, rad, lon, k, c0, c1);
+    }
+    radlong_reduce(k, c0, c1, n, mm, cnt);
 }
 
 // np.histogram(frame[frame != 0], bins=nbins, range=(first, last)) per frame: estimate, then numpy's edge fix-ups

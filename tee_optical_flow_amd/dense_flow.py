@@ -28,6 +28,16 @@ def _u8_image_stack(a, name, ndim, allow_f32=False):
     return np.ascontiguousarray(a)
 
 
+def _mask_stack(a, name):
+    """bool or uint8 [N,H,W,C], C = 1 or 2, as C-contiguous uint8 (a bool array is viewed, not copied)"""
+    a = np.asarray(a)
+    if a.dtype not in (np.bool_, np.uint8):
+        raise OpticalFlowCalculationError(f"{name} must be bool or uint8, got {a.dtype}")
+    if a.ndim != 4 or a.shape[3] not in (1, 2) or min(a.shape) < 1:
+        raise OpticalFlowCalculationError(f"{name} must be [N,H,W,C] with C = 1 or 2 and no empty side, got shape {a.shape}")
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
 class _PinnedPool:
     """Result arrays backed by pinned host memory (tf_host_alloc): the library then copies flows out at PCIe speed while
     the next sub-batch is still being solved.  A buffer returns to the pool when the numpy array that owns it is garbage
@@ -305,6 +315,51 @@ class DenseFlow:
         _lib.check(self._L.tf_clean_masks(self._h, class_map.ctypes.data, N, H, W, ids.ctypes.data, int(ids.size), int(min_size),
                                           out.ctypes.data), self._h, "tf_clean_masks")
         return out.view(np.bool_)
+
+    def av_centroids(self, masks):
+        """calc_AV_centroid's per-frame step (analyze_optical_flow.py:202-232) on the device, exact: masks bool or uint8 [N,H,W,C]
+        (C = 1 or 2; the set is channel 0 != 0, 8-connected) -> (centroids float64 [N,2] (row, col) of the largest component, areas
+        int64 [N], 0 for an empty frame).  May be called while submitted studies are in flight on this engine."""
+        m = _mask_stack(masks, "masks")
+        N, H, W, Cm = m.shape
+        cent = np.zeros((N, 2), np.float64)
+        area = np.zeros(N, np.int64)
+        _lib.check(self._L.tf_av_centroids(self._h, m.ctypes.data, N, H, W, Cm, cent.ctypes.data, area.ctypes.data), self._h, "tf_av_centroids")
+        return cent, area
+
+    def radlong_project_param(self, flow, mask, param, spacing, grad_f64, n_used, centroids, return_arrays=False):
+        """tf_radlong_project_param: the rad/long projection of OpticalFlowDataset's param field (param 0 velocity, 1 acceleration,
+        2 PWR) for frames [0, n_used), resident on the device for tf_radlong_hist / _select.  flow float16 or float32 [N,H,W,2],
+        mask bool or uint8 [>= n_used,H,W,C].  Returns (minmax float64 [4], nonzero int64 [n_used, 2], rad, long): rad / long are
+        float64 [n_used,H,W] with return_arrays, else None."""
+        flow = np.asarray(flow)
+        if flow.dtype not in (np.float16, np.float32):
+            flow = flow.astype(np.float32)
+        flow = np.ascontiguousarray(flow)
+        if flow.ndim != 4 or flow.shape[3] != 2:
+            raise OpticalFlowCalculationError(f"flow must be [N,H,W,2], got {flow.shape}")
+        N, H, W, _ = flow.shape
+        n_used = int(n_used)
+        if not 1 <= n_used <= N:
+            raise OpticalFlowCalculationError(f"n_used must be in [1, {N}], got {n_used}")
+        if param not in (0, 1, 2):
+            raise OpticalFlowCalculationError(f"param must be 0 (velocity), 1 (acceleration) or 2 (PWR), got {param!r}")
+        if param != 0 and N < 2:
+            raise OpticalFlowCalculationError("the gradient needs at least 2 flow frames")
+        m = _mask_stack(np.asarray(mask)[:n_used], "mask")
+        if m.shape[:3] != (n_used, H, W):
+            raise OpticalFlowCalculationError(f"mask must be [>= {n_used},{H},{W},C], got {np.shape(mask)}")
+        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(n_used, 2)
+        rad = np.empty((n_used, H, W), np.float64) if return_arrays else None
+        lon = np.empty((n_used, H, W), np.float64) if return_arrays else None
+        mm = np.zeros(4, np.float64)
+        nz = np.zeros((n_used, 2), np.int64)
+        _lib.check(self._L.tf_radlong_project_param(self._h, flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W,
+                                                    m.ctypes.data, m.shape[3], int(param), float(spacing), 1 if grad_f64 else 0,
+                                                    cent.ctypes.data, rad.ctypes.data if return_arrays else None,
+                                                    lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data),
+                   self._h, "tf_radlong_project_param")
+        return mm, nz, rad, lon
 
     def wase_compensate(self, flows, bkgd_mask, scale=1.0):
         """Reference :647-652, 659 for every flow of a study at once, on the device: returns (flows - background[p]) * scale

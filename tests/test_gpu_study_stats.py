@@ -1,0 +1,192 @@
+"""The consumer's rad/long call of a study on the device (tf_av_centroids, tf_radlong_project_param; DenseFlow.av_centroids /
+radlong_project_param; analysis.calculate_3dhist_radlong(..., engine=)): bit-identical to tests/golden/reference_study_stats.npz, which
+the reference's own calc_AV_centroid and calculate_3dhist_radlong produced, and to the host twins at study sizes.  The labelling is
+checked against scipy.ndimage.label with the 3x3 structure on shapes made to break a tiled 8-connected labeller."""
+import os
+
+import numpy as np
+import pytest
+from scipy import ndimage
+
+from tee_optical_flow_amd import analysis as A
+
+pytestmark = pytest.mark.gpu
+
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_study_stats.npz")
+COMPS = ("radial", "longitudinal")
+
+
+@pytest.fixture(scope="module")
+def z():
+    with np.load(FIX) as f:
+        return {k: f[k] for k in f.files}
+
+
+def _same_stats(a, b, what=""):
+    for comp in COMPS:
+        for i in range(4):
+            assert np.array_equal(np.asarray(a[comp][i]), np.asarray(b[comp][i])), (what, comp, i)
+
+
+def _scipy_largest(frame):
+    """(centroid, area) of the largest 3x3-connected component (first label on a tie) straight from scipy, or None"""
+    lab, n = ndimage.label(frame, structure=np.ones((3, 3), bool))
+    if n == 0:
+        return None
+    areas = ndimage.sum_labels(np.ones_like(lab), lab, np.arange(1, n + 1))
+    k = 1 + int(np.argmax(areas))
+    rr, cc = np.nonzero(lab == k)
+    return (rr.mean(), cc.mean()), len(rr)
+
+
+def test_device_centroids_equal_the_reference(engine, z):
+    n = int(z["nframes"])
+    got = A.av_centroids(z["av"], n, filter=False, engine=engine)
+    assert np.array_equal(np.asarray(got, np.float64), z["cent_nofilter"])
+    cent, area = engine.av_centroids(z["av"][:n])
+    for i in range(n):
+        want = A._largest_component(z["av"][i, :, :, 0])
+        assert (area[i] == 0) if want is None else (area[i] == want[1] and tuple(cent[i]) == want[0]), i
+
+
+def test_device_radlong_equals_the_reference_for_every_param(engine, z):
+    st = A.FlowStudy(z["flow"], {"rv": z["rv"], "av": z["av"]}, float(z["frame_rate"]))      # float: the fixture's float32 gradient
+    for param in A.PARAMS:
+        got = A.calculate_3dhist_radlong(st, param, av_filter_flag=False, engine=engine)
+        want = {c: tuple(z[f"{param}/{c}/{k}"] for k in ("freq", "edges", "hi", "lo")) for c in COMPS}
+        _same_stats(got, want, param)
+    # the reference's defaults (Savitzky-Golay, window 10): equal to the host twin in this process
+    for param in A.PARAMS:
+        _same_stats(A.calculate_3dhist_radlong(st, param, engine=engine), A.calculate_3dhist_radlong(st, param), param)
+
+
+def _study(seed, N, H, W):
+    """speckle flow (float16 as a study file holds it), an rv mask of drifting discs, an av mask of random blobs with empty frames"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[:H, :W]
+    flow = rng.normal(0, 4, (N, H, W, 2)).astype(np.float16)
+    rv = np.zeros((N, H, W), bool)
+    av = np.zeros((N, H, W), bool)
+    for f in range(N):
+        rv[f] = ((yy - H / 2 - f) / (0.35 * H)) ** 2 + ((xx - W / 2 + f) / (0.4 * W)) ** 2 < 1
+        for _ in range(int(rng.integers(0, 6))):
+            cy, cx = rng.uniform(0, H), rng.uniform(0, W)
+            ry, rx = rng.uniform(2, H / 6), rng.uniform(2, W / 6)
+            av[f] |= ((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1
+        av[f] ^= rng.random((H, W)) < 0.002                                   # specks, and holes
+    av[0] = False
+    av[N // 2] = False
+    return flow, np.stack([rv, rv], -1), np.stack([av, av], -1)
+
+
+@pytest.mark.parametrize("N,H,W", [(65, 512, 512), (65, 600, 800)])
+def test_study_sized_device_equals_host(engine, N, H, W):
+    flow, rv, av = _study(N + H + W, N, H, W)
+    n = N - 2
+    cent_h = A.av_centroids(av, n)
+    cent_d = A.av_centroids(av, n, engine=engine)
+    assert np.array_equal(cent_d, cent_h)                                     # filtered (window 10) from equal raw centroids
+    raw_h = A.av_centroids(av, n, filter=False)
+    assert A.av_centroids(av, n, filter=False, engine=engine) == raw_h
+    for param in A.PARAMS:
+        host = A.param_radlong_stats(flow, rv, param, 50.0, n, cent_h, return_arrays=True)
+        dev = A.param_radlong_stats(flow, rv, param, 50.0, n, cent_h, return_arrays=True, engine=engine)
+        _same_stats(dev, host, param)
+        assert np.array_equal(dev["rad_arr"], host["rad_arr"]) and np.array_equal(dev["long_arr"], host["long_arr"])
+        f32 = A.param_radlong_stats(flow.astype(np.float32), rv, param, 50.0, n, cent_h, engine=engine)
+        _same_stats(f32, host, param + " f32 input")
+    # a np.float64 frame_rate: the gradient divides in float64 under numpy 2 (and in float32 under numpy 1.x); both paths follow numpy
+    fr = np.float64(49.9)
+    for param in ("acceleration", "PWR"):
+        host = A.param_radlong_stats(flow, rv[..., :1], param, fr, n, cent_h, return_arrays=True)
+        dev = A.param_radlong_stats(flow, rv[..., :1], param, fr, n, cent_h, return_arrays=True, engine=engine)
+        _same_stats(dev, host, param + " f64")
+        assert np.array_equal(dev["rad_arr"], host["rad_arr"])
+
+
+def test_gradient_edges_and_n_used_equal_to_n(engine):
+    """n_used = N: the last projected frame takes the one-sided difference; N = 2: both frames do"""
+    rng = np.random.default_rng(5)
+    for N, H, W in ((7, 33, 70), (2, 17, 65)):
+        flow = rng.normal(0, 2, (N, H, W, 2)).astype(np.float32)
+        mask = rng.random((N, H, W, 2)) < 0.8
+        cent = [(rng.uniform(0, H), rng.uniform(0, W)) for _ in range(N)]
+        for param in A.PARAMS:
+            for fr in (30.0, np.float64(29.97)):
+                host = A.param_radlong_stats(flow, mask, param, fr, N, cent, nbins=50, return_arrays=True)
+                dev = A.param_radlong_stats(flow, mask, param, fr, N, cent, nbins=50, return_arrays=True, engine=engine)
+                _same_stats(dev, host, (N, param))
+                assert np.array_equal(dev["rad_arr"], host["rad_arr"]) and np.array_equal(dev["long_arr"], host["long_arr"])
+
+
+def _stress_frames():
+    out = []
+    out.append(np.ones((40, 130), bool))                                       # full-frame foreground
+    one = np.zeros((37, 70), bool); one[20, 66] = True; out.append(one)        # a single pixel in a ragged tile
+    yy, xx = np.mgrid[:50, :140]
+    out.append((yy + xx) % 2 == 0)                                            # checkerboard: one component
+    snake = np.zeros((61, 200), bool)                                         # a one-pixel-wide snake through many tiles
+    for r in range(0, 61, 4):
+        snake[r, 1:199] = True
+        snake[r:r + 4, 198 if (r // 4) % 2 == 0 else 1] = True
+    snake[60:, :] = False
+    snake[59, :] = False
+    out.append(snake)
+    stair = np.zeros((70, 200), bool)                                         # diagonal staircases across tile corners
+    for k in range(70):
+        stair[k, 64 - 16 + k] = True
+        stair[69 - k, 150 - k] = True
+    out.append(stair)
+    anti = np.zeros((48, 192), bool)                                          # pixels that meet only at tile corners
+    for ty in range(1, 3):
+        for tx in range(1, 3):
+            anti[16 * ty - 1, 64 * tx - 1] = anti[16 * ty, 64 * tx] = True
+            anti[16 * ty - 1, 64 * tx] = anti[16 * ty, 64 * tx - 1] = True
+    anti[15, 63] = anti[16, 64] = anti[16, 63] = False
+    out.append(anti)
+    rng = np.random.default_rng(3)
+    for H, W in ((1, 300), (300, 1), (1, 1), (17, 65), (129, 63), (100, 257)):
+        out.append(rng.random((H, W)) < 0.45)
+    out.append(np.zeros((20, 20), bool))
+    return out
+
+
+def test_labelling_stress_equals_scipy(engine):
+    for j, fr in enumerate(_stress_frames()):
+        H, W = fr.shape
+        for C in (1, 2):
+            m = np.repeat(fr[None, :, :, None], C, axis=3)
+            m = np.concatenate([m, m[:, ::-1, ::-1]], axis=0) if H > 1 or W > 1 else m
+            cent, area = engine.av_centroids(m)
+            for f in range(m.shape[0]):
+                want = _scipy_largest(m[f, :, :, 0])
+                host = A._largest_component(m[f, :, :, 0])
+                if want is None:
+                    assert area[f] == 0 and host is None, j
+                else:
+                    assert area[f] == want[1] == host[1], (j, f, area[f], want[1])
+                    assert tuple(cent[f]) == host[0], (j, f)
+                    np.testing.assert_allclose(cent[f], want[0], rtol=0, atol=1e-9)
+
+
+def test_beside_a_submitted_study(z):
+    """both calls run on the handle's stream while a submitted study solves on the lanes: same results, same flows"""
+    import tee_optical_flow_amd as T
+    from tee_optical_flow_amd.synth import speckle_sequence
+    g = speckle_sequence(21, 40, 128, 160)
+    rgb = np.repeat(g[..., None], 3, axis=3)
+    st = A.FlowStudy(z["flow"], {"rv": z["rv"], "av": z["av"]}, float(z["frame_rate"]))
+    eng = T.DenseFlow(device_id=0)
+    try:
+        serial = eng.calc_study(rgb).copy()
+        alone = {p: A.calculate_3dhist_radlong(st, p, av_filter_flag=False, engine=eng) for p in A.PARAMS}
+        t = eng.submit_study(rgb)
+        beside = {p: A.calculate_3dhist_radlong(st, p, av_filter_flag=False, engine=eng) for p in A.PARAMS}
+        flows = eng.wait(t)
+    finally:
+        eng.close()
+    for p in A.PARAMS:
+        _same_stats(beside[p], alone[p], p)
+        want = {c: tuple(z[f"{p}/{c}/{k}"] for k in ("freq", "edges", "hi", "lo")) for c in COMPS}
+        _same_stats(beside[p], want, p)
+    assert np.array_equal(flows, serial)

@@ -49,7 +49,7 @@ extern "C" {
 
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
-                              tf_clean_masks, tf_av_centroids and tf_radlong_project_param */
+                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param and tf_polar_project_param */
 
 enum {
     TF_OK = 0,
@@ -236,7 +236,9 @@ int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, int W, 
  *   stay resident for the two calls below (which: 0 = radial, 1 = longitudinal).
  * tf_radlong_hist: np.histogram(frame[frame != 0], bins=nbins, range=(edges[0], edges[nbins])) per frame, RAW counts.
  * tf_radlong_select: exact order statistics: values[n][j] = sorted(frame n's non-zero values)[ranks[n][j]] for up to 4
- *   ranks per frame (rank < 0 = skip) -- what np.percentile interpolates between. */
+ *   ranks per frame (rank < 0 = skip) -- what np.percentile interpolates between.
+ * tf_radlong_hist and tf_radlong_select act on the planes of the LAST projection call of the handle: tf_radlong_project or
+ *   tf_radlong_project_param (which 0 = radial, 1 = longitudinal), or tf_polar_project_param (which 0 = magnitude, 1 = angle). */
 int tf_radlong_project(tf_handle* h, const float* flow, const double* centroids, int N, int H, int W,
                        double* rad_out, double* long_out, double* minmax, long long* nonzero);
 int tf_radlong_hist(tf_handle* h, int which, const double* edges, int nbins, long long* freq_out);
@@ -266,6 +268,22 @@ int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int
 int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
                              int mask_C, int param, double spacing, int grad_f64, const double* centroids, double* rad_out,
                              double* long_out, double* minmax, long long* nonzero);
+
+/* ---- the polar steps of the same consumer, on the device: calculate_3dhist(ds, param, label) (optical_flow/analyze_optical_flow.py:
+ *      909-966) and the per-frame angle mode of AngleDetector.detect (optical_flow/cardiac_cycle_detection.py:100-120).
+ * tf_polar_project_param: cv2.cartToPolar (CV_32F, radians, as OpenCV 4.x's AVX2 / NEON body computes it) of
+ *   the param field tf_radlong_project_param builds (flow, N, n_used, mask, mask_C, param, spacing, grad_f64 as there), for frames
+ *   [0, n_used).  mag_out / ang_out: host float32 [n_used][H][W], may be NULL.  minmax[4] = mag min, mag max, ang min, ang max over
+ *   the frames (zeros included, as np.min / np.max); nonzero[n_used][2] = per frame count of non-zero mag / ang.  ang_mode[n_used]
+ *   = scipy.stats.mode of the frame's non-zero np.round(ang, 2): k / 100.f for the most frequent k = rint(ang * 100.f) in 1..628
+ *   (the smallest on a tie), NaN for a frame without any.  mag and ang stay resident, as float64 (exact), for tf_radlong_hist /
+ *   tf_radlong_select (which 0 = magnitude, 1 = angle).  Runs on the handle's stream and never on a lane's, so it may be called
+ *   while tf_submit_* jobs of the handle are in flight; host-synchronous; every argument is checked before any GPU work.  The
+ *   resident planes and the scratch (the uploads, 2.5 KiB per frame, and 8 bytes per pixel when mag_out or ang_out is asked
+ *   for) are grown on demand and kept by the handle. */
+int tf_polar_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
+                           int mask_C, int param, double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax,
+                           long long* nonzero, float* ang_mode);
 
 /* ---- multi-GPU: the single exchange step of the path.  The reference's loop is sequential
  *      (calculate_optical_flow.py:584-597); here pairs shard over the GPUs of a node with no data-path traffic during the

@@ -15,6 +15,14 @@ The steps before the projection are here too, so that the consumer's call runs w
 With engine= the labelling (tf_av_centroids) and the param field fused into the projection (tf_radlong_project_param) run on the device;
 without, a numpy/scipy twin gives the same bits.  Pinned by tests/golden/reference_study_stats.npz (the reference's own functions on a
 study file opened by its own OpticalFlowDataset).
+
+And the polar steps of the same consumer:
+  analyze_optical_flow.py:909-966  calculate_3dhist(ds, param, label)                                 -> calculate_3dhist
+  cardiac_cycle_detection.py:100-120  AngleDetector.detect's per-frame mode of np.round(ang, 2)        -> angle_mode_series
+both on cv2.cartToPolar, restated here as cart_to_polar (OpenCV 4.x's AVX2 / NEON arithmetic; parity with cv2 unpinned, DESIGN.md
+section 2).  With engine= the field, the transform, the angle histogram and mode run fused on the device (tf_polar_project_param) and
+the magnitude / angle statistics come from tf_radlong_hist / tf_radlong_select; without, numpy.  Pinned by
+tests/golden/reference_polar.npz (the reference's own calculate_3dhist and AngleDetector.detect, with cart_to_polar as cv2).
 """
 import ctypes as C
 import logging
@@ -308,3 +316,207 @@ class FlowStudy:
             frame_rate = a["frame_rate"] if a["units_converted"] else 1
             masks = {str(k): f[k][()] for k in a["labels"]}
             return cls(flow, masks, frame_rate, nframes=a["nframes"] - 2, mode=a["mode"])
+
+
+# ---- the polar steps: cv2.cartToPolar, calculate_3dhist, the angle detector's per-frame mode --------------------------------
+_DEG = 180 / np.pi                                            # 180 / CV_PI (CV_PI is the double nearest pi, as np.pi)
+_P1, _P3 = np.float32(0.9997878412794807) * np.float32(_DEG), np.float32(-0.3258083974640975) * np.float32(_DEG)
+_P5, _P7 = np.float32(0.1555786518463281) * np.float32(_DEG), np.float32(-0.04432655554792128) * np.float32(_DEG)
+_EPS32 = np.float32(np.finfo(np.float64).eps)                 # (float)DBL_EPSILON
+_RAD32 = np.float32(np.pi / 180)                              # (float)(CV_PI / 180)
+
+
+def fma32(a, b, c):
+    """float32 fma(a, b, c) with one rounding, in numpy (which has no fma): a*b is exact in float64; s = p + c in float64 with its
+    TwoSum error; s is made round-to-odd (stepped one ulp toward zero if it overshot the exact sum, then its lowest bit set, when
+    the error is not zero), so that the final cast to float32 rounds the exact sum once (53 >= 24 + 2 bits)."""
+    p = np.asarray(a, np.float32).astype(np.float64) * np.asarray(b, np.float32).astype(np.float64)
+    c = np.asarray(c, np.float32).astype(np.float64)
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    inexact = err != 0
+    if np.any(inexact):
+        s = np.array(s, np.float64, copy=True)
+        over = inexact & ((err < 0) == (s > 0))                 # |s| > |exact sum|: truncate toward zero first
+        s[over] = np.nextafter(s[over], 0.0)
+        v = s.view(np.int64)
+        v[inexact] |= 1
+    return s.astype(np.float32)
+
+
+def cart_to_polar(x, y):
+    """cv2.cartToPolar(x, y) for float32 in radians, as OpenCV 4.x's SIMD body computes it on an AVX2 (FMA3) or NEON build
+    (modules/core/src/mathfuncs_core.simd.hpp: magnitude32f, fastAtan32f / v_atan_f32): (mag, ang), float32.  The same formula
+    runs on the device (teeflow_polar.hip.h).  A restatement, not cv2: parity with cv2 is unpinned."""
+    x = np.asarray(x, np.float32)
+    y = np.asarray(y, np.float32)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        mag = np.sqrt(fma32(x, x, y * y))                          # v_muladd(x, x, y*y): y*y rounded first
+        ax, ay = np.abs(x), np.abs(y)
+        c = np.minimum(ax, ay) / (np.maximum(ax, ay) + _EPS32)
+        cc = c * c
+        a = fma32(fma32(fma32(cc, _P7, _P5), cc, _P3), cc, _P1) * c
+        a = np.where(ax >= ay, a, np.float32(90) - a)
+        a = np.where(x < 0, np.float32(180) - a, a)                # -0.0 is not < 0
+        a = np.where(y < 0, np.float32(360) - a, a)
+        ang = (a * _RAD32).astype(np.float32)
+    return mag.astype(np.float32), ang
+
+
+def polar_field(flow, mask, param, frame_rate, n_used):
+    """cv2.cartToPolar of every frame of get_masked_arr(param, label): (mag, ang) float32 [n_used,H,W]"""
+    field = param_field(flow, mask, param, frame_rate, n_used)
+    return cart_to_polar(field[..., 0], field[..., 1])
+
+
+def percentile_index(n, q, dtype=np.float32):
+    """(prev, next, gamma) of np.percentile(a, q) for n values of float dtype: method 'linear' as numpy >= 2 computes it, q / 100
+    and the virtual index (n - 1) * q in the data's dtype (numpy 1.x computes both in float64).  The result is
+    _lerp32(sorted(a)[prev], sorted(a)[next], gamma)."""
+    qq = np.asarray(np.true_divide(q, np.dtype(dtype).type(100)))
+    vi = np.asarray((n - 1) * qq)
+    prev = int(np.floor(vi))
+    nxt = prev + 1
+    if vi >= n - 1:                                            # above the last index: both are the maximum
+        prev = nxt = -1
+    gamma = np.asarray(vi - prev, dtype=vi.dtype)              # numpy's _get_gamma: from the clipped previous index
+    return (prev % n, nxt % n, gamma[()])
+
+
+def _lerp32(a, b, t):
+    """numpy's _lerp in the data's dtype: a + (b - a) * t, or b - (b - a) * (1 - t) for t >= 0.5"""
+    d = b - a
+    return b - d * (1 - t) if t >= 0.5 else a + d * t
+
+
+def _polar_edges(mn, mx, nbins):
+    """np.histogram's bin edges for range=(mn, mx) (np.float32 scalars, as np.min / np.max return them) of float32 data, from the
+    numpy of this process (numpy 2 runs linspace in float32)"""
+    return np.histogram_bin_edges(np.empty(0, np.float32), bins=nbins, range=(mn, mx))
+
+
+def _study_arrays(ds, label):
+    flow = getattr(ds, "flow", None)
+    if flow is None:
+        flow = ds.vel_array
+    return flow, ds.get_mask(label)
+
+
+def _valid(ds, param, label):
+    if param not in PARAMS:
+        log.error("%r is not a valid optical flow parameter, choose from %s", param, list(PARAMS))
+        return False
+    if label not in list(ds.accepted_labels):
+        log.error("%r not a valid key, choose from %s", label, list(ds.accepted_labels))
+        return False
+    return True
+
+
+def _hist_host(mag, ang, n, nbins, percentile):
+    """the reference's two loops (analyze_optical_flow.py:927-961) on float32 planes, numpy as it runs them"""
+    mag_freq, hi, mag_edges = [], [], []
+    mag_max, mag_min = np.max(mag), np.min(mag)
+    for i in range(n):
+        flat = np.ravel(mag[i])
+        nz = flat[flat != 0]
+        if len(nz) == 0:
+            hi.append(hi[-1])                                  # IndexError on an empty first frame, as the reference
+            mag_freq.append(mag_freq[-1])
+        else:
+            hi.append(np.percentile(nz, percentile))
+            freq, mag_edges = np.histogram(nz, bins=nbins, range=(mag_min, mag_max))
+            mag_freq.append(freq + 1)
+    ang_freq, ang_edges = [], []
+    ang_max, ang_min = np.max(ang), np.min(ang)
+    for i in range(n):
+        flat = np.ravel(ang[i])
+        nz = flat[flat != 0]
+        if len(nz) == 0:
+            ang_freq.append(mag_freq[-1])                      # the reference's quirk: the LAST frame's magnitude row
+        else:
+            freq, ang_edges = np.histogram(nz, bins=nbins, range=(ang_min, ang_max))
+            ang_freq.append(freq + 1)
+    return np.stack(mag_freq), np.stack(ang_freq), mag_edges[:-1], ang_edges[:-1], np.asarray(hi)
+
+
+def _hist_device(engine, n, mm, nz, nbins, percentile):
+    """the same from the planes tf_polar_project_param left resident: tf_radlong_hist over numpy's float32 edges (passed as float64,
+    exactly) and tf_radlong_select for the order statistics np.percentile interpolates between"""
+    L = engine._L
+    mn, mx, amn, amx = (np.float32(v) for v in mm)
+    cnt, acnt = nz[:, 0], nz[:, 1]
+    if cnt[0] == 0:
+        raise IndexError("list index out of range")           # the reference's perc_hi[-1] on an empty first frame
+    mag_edges = _polar_edges(mn, mx, nbins)
+    e64 = mag_edges.astype(np.float64)                         # exact; held here while the library reads it
+    freq = np.zeros((n, nbins), np.int64)
+    # k_radlong_hist estimates the bin in float64 and fixes it up by one against these edges, as numpy fixes up its float32
+    # estimate: both estimates lie within one bin of the edge-defined one, so both end in the same bin
+    _lib.check(L.tf_radlong_hist(engine._h, 0, e64.ctypes.data, nbins, freq.ctypes.data), engine._h, "tf_radlong_hist")
+    ranks = np.full((n, 4), -1, np.int64)
+    gam = [None] * n
+    for i in range(n):
+        if cnt[i] > 0:
+            ranks[i, 0], ranks[i, 1], gam[i] = percentile_index(int(cnt[i]), percentile)
+    vals = np.zeros((n, 4), np.float64)
+    _lib.check(L.tf_radlong_select(engine._h, 0, ranks.ctypes.data, vals.ctypes.data), engine._h, "tf_radlong_select")
+    mag_freq, hi = [], []
+    for i in range(n):
+        if cnt[i] == 0:
+            hi.append(hi[-1]); mag_freq.append(mag_freq[-1])
+        else:
+            hi.append(_lerp32(np.float32(vals[i, 0]), np.float32(vals[i, 1]), gam[i]))
+            mag_freq.append(freq[i] + 1)
+    ang_edges = []
+    if acnt.any():
+        ang_edges = _polar_edges(amn, amx, nbins)
+        a64 = ang_edges.astype(np.float64)
+        afreq = np.zeros((n, nbins), np.int64)
+        _lib.check(L.tf_radlong_hist(engine._h, 1, a64.ctypes.data, nbins, afreq.ctypes.data), engine._h, "tf_radlong_hist")
+    ang_freq = [afreq[i] + 1 if acnt[i] > 0 else mag_freq[-1] for i in range(n)]
+    return np.stack(mag_freq), np.stack(ang_freq), mag_edges[:-1], ang_edges[:-1], np.asarray(hi)
+
+
+def calculate_3dhist(ds, param, label, nbins=1000, percentile=99, *, engine=None):
+    """The reference's calculate_3dhist(ds, param, label) (analyze_optical_flow.py:909-966): (mag_freq, ang_freq, mag_edges[:-1],
+    ang_edges[:-1], hi_arr) for frames [0, ds.nframes) of cv2.cartToPolar(get_masked_arr(param, label)), quirks kept: freq + 1; an
+    empty frame copies the previous row and hi; an empty angle frame takes the magnitude row of the study's last frame; an empty
+    first frame raises IndexError; an unknown param or label is logged and gives None.  float32 statistics as numpy >= 2 computes
+    them.  `ds` is the reference's OpticalFlowDataset or a FlowStudy.  With `engine` (a DenseFlow) every per-pixel step runs on the
+    device, with the same bits."""
+    if not _valid(ds, param, label):
+        return None
+    flow, mask = _study_arrays(ds, label)
+    n = int(ds.nframes)
+    if engine is None:
+        mag, ang = polar_field(flow, mask, param, ds.frame_rate, n)
+        return _hist_host(mag, ang, n, nbins, percentile)
+    mm, nz, _, _, _ = engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+    return _hist_device(engine, n, mm, nz, nbins, percentile)
+
+
+def _mode_of_rounded(ang):
+    """scipy.stats.mode of np.round(ang, 2)'s non-zero values: the smallest of the most frequent, np.float32(nan) if none"""
+    flat = np.ravel(np.round(ang, decimals=2))
+    nz = flat[flat != 0]
+    if len(nz) == 0:
+        return np.float32(np.nan)
+    vals, counts = np.unique(nz, return_counts=True)
+    return vals[np.argmax(counts)]
+
+
+def angle_mode_series(ds, param, label, *, engine=None):
+    """The per-frame series AngleDetector.detect (cardiac_cycle_detection.py:100-120) hands to its SpectralSmoother: for frames
+    [0, ds.nframes), scipy.stats.mode of the non-zero np.round(ang, 2) of cv2.cartToPolar(get_masked_arr(param, label)), float32,
+    NaN for a frame without any.  With `engine` (a DenseFlow) it runs on the device (tf_polar_project_param), with the same bits."""
+    if param not in PARAMS:
+        raise ValueError(f"param must be one of {PARAMS}, got {param!r}")
+    if label not in list(ds.accepted_labels):
+        raise ValueError(f"{label!r} not a valid key, choose from {list(ds.accepted_labels)}")
+    flow, mask = _study_arrays(ds, label)
+    n = int(ds.nframes)
+    if engine is None:
+        _, ang = polar_field(flow, mask, param, ds.frame_rate, n)
+        return np.asarray([_mode_of_rounded(ang[i]) for i in range(n)], np.float32)
+    return engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)[2]

@@ -18,12 +18,14 @@
 #include "teeflow_saliency.hip.h"
 #include "teeflow_masks.hip.h"
 #include "teeflow_centroid.hip.h"
+#include "teeflow_polar.hip.h"
 #include "../../include/teeflow.h"
 #include <rccl/rccl.h>      // types and prototypes only: librccl is loaded with dlopen when a communicator is first asked for
 #include <dlfcn.h>
 
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -150,7 +152,8 @@ struct tf_handle : TfKnobs {
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
            PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks
            PRE_CT_MASK, PRE_CT_PAR, PRE_CT_LR, PRE_CT_AREA, PRE_CT_SUM, PRE_CT_OUT,  // tf_av_centroids
-           PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // tf_radlong_project_param
+           PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // tf_radlong_project_param (the first two also
+           PRE_PO_META, PRE_PO_OUT,                                               //   tf_polar_project_param's uploads)
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
@@ -2273,6 +2276,23 @@ int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C,
     return TF_OK;
 }
 
+// the resident analysis planes hold at least tot doubles each (grown, never shrunk); they are invalid until the caller's projection
+// has run (anN = 0)
+int grow_an_planes(tf_handle* h, size_t tot)
+{
+    h->anN = 0;
+    if (h->an_cap < tot) {
+        HIPC(h, hipStreamSynchronize(h->stream));
+        if (h->an_rad) { (void)hipFree(h->an_rad); h->an_rad = nullptr; }
+        if (h->an_lon) { (void)hipFree(h->an_lon); h->an_lon = nullptr; }
+        h->an_cap = 0;
+        HIPC(h, hipMalloc(&h->an_rad, tot * sizeof(double)));
+        HIPC(h, hipMalloc(&h->an_lon, tot * sizeof(double)));
+        h->an_cap = tot;
+    }
+    return TF_OK;
+}
+
 template <int PARAM, typename FT>
 void launch_project_param(dim3 g, hipStream_t s, const void* flow, int N, const uint8_t* mask, int C, double sp, int grad_f64, const double* cent,
                           int H, int W, double* rad, double* lon, u64* mm, unsigned long long* cnt)
@@ -2291,18 +2311,9 @@ int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_
     const int nflow = param == RL_PARAM_VELOCITY ? n_used : (n_used + 1 < N ? n_used + 1 : N);   // frames the gradient of [0, n_used) reads
     const size_t flow_bytes = (size_t)nflow * npx * 2 * (f16 ? 2 : 4);
     HIPC(h, hipSetDevice(h->dev));
-    h->anN = 0;
-    if (h->an_cap < tot) {
-        HIPC(h, hipStreamSynchronize(h->stream));
-        if (h->an_rad) { (void)hipFree(h->an_rad); h->an_rad = nullptr; }
-        if (h->an_lon) { (void)hipFree(h->an_lon); h->an_lon = nullptr; }
-        h->an_cap = 0;
-        HIPC(h, hipMalloc(&h->an_rad, tot * sizeof(double)));
-        HIPC(h, hipMalloc(&h->an_lon, tot * sizeof(double)));
-        h->an_cap = tot;
-    }
-    void* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr;   // meta: min/max keys [4], counts [n_used][2], centroids [n_used][2]
     int rc;
+    if ((rc = grow_an_planes(h, tot))) return rc;
+    void* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr;   // meta: min/max keys [4], counts [n_used][2], centroids [n_used][2]
     if ((rc = pre_grow(h, tf_handle::PRE_AN_FLOW, flow_bytes, &dflow)) ||
         (rc = pre_grow(h, tf_handle::PRE_AN_MASK, tot * C, (void**)&dmask)) ||
         (rc = pre_grow(h, tf_handle::PRE_AN_META, 32 + (size_t)n_used * 32, (void**)&meta))) return rc;
@@ -2338,6 +2349,72 @@ int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_
     return TF_OK;
 }
 
+template <int PARAM, typename FT>
+void launch_polar_param(dim3 g, hipStream_t s, const void* flow, int N, const uint8_t* mask, int C, double sp, int grad_f64, int H, int W,
+                        double* magp, double* angp, float* mag32, float* ang32, u64* mm, unsigned long long* cnt, unsigned* bins)
+{
+    if (grad_f64)
+        hipLaunchKernelGGL((k_polar_project_param<PARAM, FT, double>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, H, W, magp, angp, mag32, ang32, mm, cnt, bins);
+    else
+        hipLaunchKernelGGL((k_polar_project_param<PARAM, FT, float>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, H, W, magp, angp, mag32, ang32, mm, cnt, bins);
+}
+
+int polar_project_param(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
+                        double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax, long long* nonzero, float* ang_mode)
+{
+    const size_t npx = (size_t)H * W, tot = (size_t)n_used * npx;
+    const int nflow = param == RL_PARAM_VELOCITY ? n_used : (n_used + 1 < N ? n_used + 1 : N);   // frames the gradient of [0, n_used) reads
+    const size_t flow_bytes = (size_t)nflow * npx * 2 * (f16 ? 2 : 4);
+    const bool arrays = mag_out || ang_out;
+    HIPC(h, hipSetDevice(h->dev));
+    int rc;
+    if ((rc = grow_an_planes(h, tot))) return rc;
+    void* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr; float* d32 = nullptr;
+    // meta: min/max keys [4], counts [n_used][2], mode k [n_used], angle bins [n_used][PO_NBINS]
+    const size_t meta_bytes = 32 + (size_t)n_used * 16 + (size_t)n_used * 4 + (size_t)n_used * PO_NBINS * 4;
+    if ((rc = pre_grow(h, tf_handle::PRE_AN_FLOW, flow_bytes, &dflow)) ||
+        (rc = pre_grow(h, tf_handle::PRE_AN_MASK, tot * C, (void**)&dmask)) ||
+        (rc = pre_grow(h, tf_handle::PRE_PO_META, meta_bytes, (void**)&meta)) ||
+        (arrays && (rc = pre_grow(h, tf_handle::PRE_PO_OUT, tot * 2 * sizeof(float), (void**)&d32)))) return rc;
+    u64* mm = (u64*)meta;
+    unsigned long long* cnt = (unsigned long long*)(meta + 32);
+    int* dmode = (int*)(meta + 32 + (size_t)n_used * 16);
+    unsigned* bins = (unsigned*)(meta + 32 + (size_t)n_used * 20);
+    const u64 mm0[4] = {~0ull, 0ull, ~0ull, 0ull};
+    u64 mmh[4];
+    std::vector<unsigned long long> ch((size_t)n_used * 2);
+    std::vector<int> kh((size_t)n_used);
+    const hipStream_t s = h->stream;
+    HIPC(h, hipMemcpyAsync(dflow, flow, flow_bytes, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(dmask, mask, tot * C, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(mm, mm0, sizeof mm0, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemsetAsync(cnt, 0, meta_bytes - 32, s));
+    // each block takes >= 4096 pixels of a frame: its angle bins go to global memory once per block
+    const int gx = (int)((npx + 4095) / 4096);
+    const dim3 g(gx < 64 ? gx : 64, n_used);
+    float* m32 = arrays ? d32 : nullptr;
+    float* a32 = arrays ? d32 + tot : nullptr;
+#define TF_PO(P) (f16 ? launch_polar_param<P, _Float16>(g, s, dflow, N, dmask, C, spacing, grad_f64, H, W, h->an_rad, h->an_lon, m32, a32, mm, cnt, bins) \
+                      : launch_polar_param<P, float>(g, s, dflow, N, dmask, C, spacing, grad_f64, H, W, h->an_rad, h->an_lon, m32, a32, mm, cnt, bins))
+    if (param == RL_PARAM_VELOCITY) TF_PO(RL_PARAM_VELOCITY);
+    else if (param == RL_PARAM_ACCELERATION) TF_PO(RL_PARAM_ACCELERATION);
+    else TF_PO(RL_PARAM_PWR);
+#undef TF_PO
+    hipLaunchKernelGGL(k_polar_mode, dim3((unsigned)n_used), dim3(256), 0, s, bins, dmode);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(mmh, mm, sizeof mmh, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(kh.data(), dmode, kh.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (mag_out) HIPC(h, hipMemcpyAsync(mag_out, m32, tot * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (ang_out) HIPC(h, hipMemcpyAsync(ang_out, a32, tot * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    for (int j = 0; j < 4; ++j) minmax[j] = (float)f64_unkey(mmh[j]);        // exact: the planes hold float32 values
+    for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
+    for (int i = 0; i < n_used; ++i) ang_mode[i] = kh[i] ? (float)kh[i] / 100.f : std::numeric_limits<float>::quiet_NaN();
+    h->anN = n_used; h->anH = H; h->anW = W;
+    return TF_OK;
+}
+
 // a failed call leaves nothing of it running: its destinations are host memory the caller may free at once
 int finish_host_call(tf_handle* h, int rc)
 {
@@ -2369,6 +2446,18 @@ TF_API int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_
     if (n_used > 65535) return TF_ERR_UNSUPPORTED;                                                                     // frames are grid.y
     return finish_host_call(h, radlong_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
                                                      centroids, rad_out, long_out, minmax, nonzero));
+}
+
+TF_API int tf_polar_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
+                                  int mask_C, int param, double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax,
+                                  long long* nonzero, float* ang_mode)
+{
+    if (!h || !flow || !mask || !minmax || !nonzero || !ang_mode || N < 1 || n_used < 1 || H < 1 || W < 1 || n_used > N) return TF_ERR_INVALID_ARG;
+    if ((mask_C != 1 && mask_C != 2) || param < TF_PARAM_VELOCITY || param > TF_PARAM_PWR) return TF_ERR_INVALID_ARG;
+    if (param != TF_PARAM_VELOCITY && (N < 2 || !std::isfinite(spacing) || spacing == 0.0)) return TF_ERR_INVALID_ARG;   // np.gradient needs 2 frames
+    if (n_used > 65535 || (size_t)H * W > 0xFFFFFFFFu) return TF_ERR_UNSUPPORTED;       // frames are grid.y; a frame's counts are 32-bit
+    return finish_host_call(h, polar_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
+                                                   mag_out, ang_out, minmax, nonzero, ang_mode));
 }
 
 // pinned host memory for results: a destination allocated here makes the host-pointer entry points copy out at PCIe

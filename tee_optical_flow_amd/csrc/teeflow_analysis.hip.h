@@ -95,6 +95,37 @@ enum { RL_PARAM_VELOCITY = 0, RL_PARAM_ACCELERATION = 1, RL_PARAM_PWR = 2 };
 template <typename FT>
 __device__ __forceinline__ float2 rl_ld(const FT* __restrict__ f, size_t j) { return make_float2((float)f[2 * j], (float)f[2 * j + 1]); }
 
+// frame n's gradient neighbours lo / hi and divisor den (np.gradient, edge_order 1)
+template <typename T>
+struct ParamFrame { int lo, hi; T den; };
+
+template <typename T>
+__device__ __forceinline__ ParamFrame<T> param_frame(int n, int N, double h)
+{
+    const bool edge = n == 0 || n == N - 1;
+    const int lo = edge ? (n == 0 ? 0 : N - 2) : n - 1;
+    return {lo, edge ? lo + 1 : n + 1, edge ? (T)h : (T)(2.0 * h)};
+}
+
+// the param field times the mask at pixel i of frame n (float32, as numpy keeps it); shared by every kernel that reads the field
+template <int PARAM, typename FT, typename T>
+__device__ __forceinline__ float2 param_px(const FT* __restrict__ flow, const uint8_t* __restrict__ mask, int C, size_t npx, int n,
+                                           const ParamFrame<T>& pf, size_t i)
+{
+    const float2 v = rl_ld(flow, (size_t)n * npx + i);
+    float fx = v.x, fy = v.y;
+    if (PARAM != RL_PARAM_VELOCITY) {
+        const float2 a = rl_ld(flow, (size_t)pf.lo * npx + i), b = rl_ld(flow, (size_t)pf.hi * npx + i);
+        const float gx = (float)((T)(b.x - a.x) / pf.den), gy = (float)((T)(b.y - a.y) / pf.den);
+        fx = PARAM == RL_PARAM_PWR ? v.x * gx : gx;
+        fy = PARAM == RL_PARAM_PWR ? v.y * gy : gy;
+    }
+    const uint8_t* mp = mask + ((size_t)n * npx + i) * C;
+    fx = fx * (float)mp[0];
+    fy = fy * (float)mp[C - 1];                                    // C == 1: channel 0 for both components (numpy broadcasting)
+    return make_float2(fx, fy);
+}
+
 template <int PARAM, typename FT, typename T>
 __global__ __launch_bounds__(256) void k_radlong_project_param(const FT* __restrict__ flow /* [>= n_used (+1)][H][W][2] */, int N,
                                                                const uint8_t* __restrict__ mask /* [n_used][H][W][C] */, int C, double h,
@@ -106,22 +137,10 @@ __global__ __launch_bounds__(256) void k_radlong_project_param(const FT* __restr
     const double cH = cent[2 * n], cW = cent[2 * n + 1];
     u64 k[4] = {~0ull, 0ull, ~0ull, 0ull};
     unsigned c0 = 0, c1 = 0;
-    const bool edge = n == 0 || n == N - 1;
-    const int lo = edge ? (n == 0 ? 0 : N - 2) : n - 1, hi = edge ? lo + 1 : n + 1;
-    const T den = edge ? (T)h : (T)(2.0 * h);
+    const ParamFrame<T> pf = param_frame<T>(n, N, h);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
-        const float2 v = rl_ld(flow, (size_t)n * npx + i);
-        float fx = v.x, fy = v.y;
-        if (PARAM != RL_PARAM_VELOCITY) {
-            const float2 a = rl_ld(flow, (size_t)lo * npx + i), b = rl_ld(flow, (size_t)hi * npx + i);
-            const float gx = (float)((T)(b.x - a.x) / den), gy = (float)((T)(b.y - a.y) / den);
-            fx = PARAM == RL_PARAM_PWR ? v.x * gx : gx;
-            fy = PARAM == RL_PARAM_PWR ? v.y * gy : gy;
-        }
-        const uint8_t* mp = mask + ((size_t)n * npx + i) * C;
-        fx = fx * (float)mp[0];
-        fy = fy * (float)mp[C - 1];                                // C == 1: channel 0 for both components (numpy broadcasting)
-        radlong_px(fx, fy, cH, cW, W, n, npx, i, rad, lon, k, c0, c1);
+        const float2 f = param_px<PARAM, FT, T>(flow, mask, C, npx, n, pf, i);
+        radlong_px(f.x, f.y, cH, cW, W, n, npx, i, rad, lon, k, c0, c1);
     }
     radlong_reduce(k, c0, c1, n, mm, cnt);
 }

@@ -49,7 +49,7 @@ extern "C" {
 
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
-                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param and tf_polar_project_param */
+                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param and tf_otsu_masks */
 
 enum {
     TF_OK = 0,
@@ -227,6 +227,23 @@ int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, 
  * pixel and frame, with chunks of as many frames as fit in 512 MiB (at least one frame).  Host-synchronous. */
 int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, int W, const uint8_t* class_ids, int n_labels, long long min_size,
                    uint8_t* masks_out);
+
+/* The Otsu segmentation mode, `predict_movie_thres` of the reference (calculate_optical_flow.py:184-213), on the device and exact: for
+ * each uint8 RGB frame,
+ *   g      = rgb2gray(frame)                  (float64: ((R/255)*0.2125 + (G/255)*0.7154) + (B/255)*0.0721),
+ *   thr    = skimage.filters.threshold_otsu(g)    (256-bin np.histogram over [min g, max g], bin centres, the first maximum of the
+ *            between-class variance; a frame of one luma value gets that value, so its mask is empty),
+ *   clean  = remove_small_objects(binary_fill_holes(g > thr), min_size)   (both 4-connected; min_size <= 0 removes nothing),
+ * and then, over the stack of cleaned planes, moving_avg_mask with its defaults (n = 4, threshold 0.49; the reference ignores its config
+ * there).  rgb: host uint8 [N][H][W][3].  masks_out: host [N][H][W][2] bytes of 0 / 1, the reference's bool array 'otsu' (channel
+ * duplicated).  thresholds_out: host float64 [N], the per-frame thresholds, or NULL.
+ * TF_ERR_INVALID_ARG for a null pointer (thresholds_out excepted) or N < 2, H < 2 or W < 2 (the reference's np.squeeze changes meaning
+ * or raises there); TF_ERR_UNSUPPORTED for frames of more than 2^31 - 1 pixels or more than 65535 frames; both before any GPU work.
+ * Runs on the handle's stream and never on a lane's, so it may be called while tf_submit_* jobs of the handle are in flight; works on a
+ * DualTVL1 or a DeepFlow handle.  Device scratch, grown on demand and kept by the handle: 6 bytes per pixel and frame for the study
+ * (frames, cleaned planes, output) plus, per chunk of frames, tf_clean_masks' 10 bytes per pixel and frame of labelling scratch, with
+ * chunks of as many frames as fit in 512 MiB (at least one frame).  Host-synchronous. */
+int tf_otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* masks_out, double* thresholds_out);
 
 /* ---- radial / longitudinal projection + per-frame statistics of the reference's analysis step
  *      (optical_flow/analysis.py:89-212: calculate_comp_magnitude, calc_bidirectional_hist), float64, on the device.

@@ -17,6 +17,7 @@
 #include "teeflow_wase.hip.h"
 #include "teeflow_saliency.hip.h"
 #include "teeflow_masks.hip.h"
+#include "teeflow_otsu.hip.h"
 #include "teeflow_centroid.hip.h"
 #include "teeflow_polar.hip.h"
 #include "../../include/teeflow.h"
@@ -150,7 +151,8 @@ struct tf_handle : TfKnobs {
     // ---- frame preprocessing (conditioning, saliency): grow-only work buffers, freed with the handle ----
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
-           PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks
+           PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks (PAR, AUX, LR also tf_otsu_masks)
+           PRE_OT_RGB, PRE_OT_CLEAN, PRE_OT_OUT, PRE_OT_META,                        // tf_otsu_masks
            PRE_CT_MASK, PRE_CT_PAR, PRE_CT_LR, PRE_CT_AREA, PRE_CT_SUM, PRE_CT_OUT,  // tf_av_centroids
            PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // tf_radlong_project_param (the first two also
            PRE_PO_META, PRE_PO_OUT,                                               //   tf_polar_project_param's uploads)
@@ -2095,11 +2097,12 @@ int clean_masks(tf_handle* h, const uint8_t* cmap, int N, int H, int W, const ui
         const dim3 g(tiles, (unsigned)planes), blk(256);
         // fill holes: components of m's background; those with a pixel on the border keep their flag in aux
         HIPC(h, hipMemsetAsync(daux, 0, planes * HW * 4, s));
-        hipLaunchKernelGGL(k_mask_local<0>, g, blk, 0, s, dcls, meta + 64, dpar, daux, dlr, N, f0, n, H, W, tiles_x, derr);
+        const ClassWindowBackground set{dcls, meta + 64, N, f0, n, HW};
+        hipLaunchKernelGGL((k_mask_local<0, ClassWindowBackground>), g, blk, 0, s, set, dpar, daux, dlr, H, W, tiles_x, derr);
         hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
         hipLaunchKernelGGL(k_mask_flatten<0>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
         // small objects: components of the filled mask, their sizes counted into aux
-        hipLaunchKernelGGL(k_mask_local<1>, g, blk, 0, s, dcls, meta + 64, dpar, daux, dlr, N, f0, n, H, W, tiles_x, derr);
+        hipLaunchKernelGGL((k_mask_local<1, NoSet>), g, blk, 0, s, NoSet{}, dpar, daux, dlr, H, W, tiles_x, derr);
         HIPC(h, hipMemsetAsync(daux, 0, planes * HW * 4, s));
         hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
         hipLaunchKernelGGL(k_mask_flatten<1>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
@@ -2122,6 +2125,86 @@ TF_API int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, 
     if (!h || !class_map || !class_ids || !masks_out || N < 1 || H < 1 || W < 1 || n_labels < 1) return TF_ERR_INVALID_ARG;
     const int rc = clean_masks(h, class_map, N, H, W, class_ids, n_labels, min_size, masks_out);
     if (rc != TF_OK) {                                         // nothing of the call may still write masks_out when it returns
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        (void)hipGetLastError();
+    }
+    return rc;
+}
+
+namespace {
+// tf_otsu_masks: the frames, one byte per pixel of the cleaned planes and the output stay on the device for the whole study (6 B per
+// pixel and frame); the labelling scratch (10 B per pixel and frame: parents, flags / sizes, tile-local roots) is tf_clean_masks' own,
+// in chunks of as many frames as fit in MASK_CHUNK_BYTES.  The temporal window runs over all cleaned planes after the last chunk.
+int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* out, double* thr_out)
+{
+    using namespace msk;
+    const size_t HW = (size_t)H * W;
+    size_t nf = MASK_CHUNK_BYTES / (HW * 10);
+    if (nf > (size_t)N) nf = (size_t)N;
+    if (nf < 1) nf = 1;
+    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
+    HIPC(h, hipSetDevice(h->dev));
+    uint8_t* drgb = nullptr; uint8_t* dclean = nullptr; uint16_t* dout = nullptr; uint8_t* meta = nullptr;
+    uint32_t* dpar = nullptr; uint32_t* daux = nullptr; uint16_t* dlr = nullptr;
+    // meta: [0, 64) error word; then min / max [N][2] u64, thresholds [N] f64, histograms [N][256] u32
+    const size_t off_mm = 64, off_thr = off_mm + (size_t)N * 16, off_hist = off_thr + (size_t)N * 8, meta_bytes = off_hist + (size_t)N * otsu::NBINS * 4;
+    int rc;
+    if ((rc = pre_grow(h, tf_handle::PRE_OT_RGB, (size_t)N * HW * 3, (void**)&drgb)) ||
+        (rc = pre_grow(h, tf_handle::PRE_OT_CLEAN, (size_t)N * HW, (void**)&dclean)) ||
+        (rc = pre_grow(h, tf_handle::PRE_OT_OUT, (size_t)N * HW * 2, (void**)&dout)) ||
+        (rc = pre_grow(h, tf_handle::PRE_OT_META, meta_bytes, (void**)&meta)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_PAR, nf * HW * 4, (void**)&dpar)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_AUX, nf * HW * 4, (void**)&daux)) ||
+        (rc = pre_grow(h, tf_handle::PRE_MK_LR, nf * HW * 2, (void**)&dlr))) return rc;
+    unsigned* derr = (unsigned*)meta;
+    u64* mm = (u64*)(meta + off_mm);
+    double* dthr = (double*)(meta + off_thr);
+    uint32_t* dhist = (uint32_t*)(meta + off_hist);
+    const hipStream_t s = h->stream;
+    std::vector<u64> init((size_t)N * 2);
+    for (int f = 0; f < N; ++f) { init[2 * f] = ~0ull; init[2 * f + 1] = 0ull; }
+    HIPC(h, hipMemcpyAsync(drgb, rgb, (size_t)N * HW * 3, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemsetAsync(meta, 0, meta_bytes, s));
+    HIPC(h, hipMemcpyAsync(mm, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+    const dim3 blk(256);
+    const unsigned gx = (unsigned)((HW + 255) / 256), gr = gx < 512 ? gx : 512;
+    hipLaunchKernelGGL(k_cond_minmax, dim3(gr, N), blk, 0, s, drgb, HW, mm);
+    hipLaunchKernelGGL(otsu::k_otsu_hist, dim3(gr, N), blk, 0, s, drgb, HW, mm, dhist);
+    hipLaunchKernelGGL(otsu::k_otsu_thr, dim3(N), blk, 0, s, mm, dhist, dthr);
+    for (int f0 = 0; f0 < N; f0 += (int)nf) {
+        const int n = N - f0 < (int)nf ? N - f0 : (int)nf;
+        const dim3 g(tiles, (unsigned)n);
+        const otsu::LumaNotAbove set{drgb, dthr, f0, HW};
+        // fill holes, then small objects: the passes of tf_clean_masks, one plane per frame
+        HIPC(h, hipMemsetAsync(daux, 0, (size_t)n * HW * 4, s));
+        hipLaunchKernelGGL((k_mask_local<0, otsu::LumaNotAbove>), g, blk, 0, s, set, dpar, daux, dlr, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_mask_flatten<0>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
+        hipLaunchKernelGGL((k_mask_local<1, NoSet>), g, blk, 0, s, NoSet{}, dpar, daux, dlr, H, W, tiles_x, derr);
+        HIPC(h, hipMemsetAsync(daux, 0, (size_t)n * HW * 4, s));
+        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
+        hipLaunchKernelGGL(k_mask_flatten<1>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
+        hipLaunchKernelGGL(otsu::k_otsu_keep, dim3(gx, (unsigned)n), blk, 0, s, dpar, daux, HW, min_size, dclean + (size_t)f0 * HW);
+        HIPC(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(otsu::k_otsu_window, dim3(gx, N), blk, 0, s, dclean, N, HW, dout);
+    HIPC(h, hipGetLastError());
+    unsigned e = 0;
+    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(out, dout, (size_t)N * HW * 2, hipMemcpyDeviceToHost, s));
+    if (thr_out) HIPC(h, hipMemcpyAsync(thr_out, dthr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    if (e) return fail(h, TF_ERR_HIP, "tf_otsu_masks: a union-find loop ran out of its bound (code %u)", e);
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* masks_out, double* thresholds_out)
+{
+    if (!h || !rgb || !masks_out || N < 2 || H < 2 || W < 2) return TF_ERR_INVALID_ARG;
+    if ((size_t)H * W > 0x7fffffffu || N > 65535) return TF_ERR_UNSUPPORTED;   // (frames are a grid dimension)
+    const int rc = otsu_masks(h, rgb, N, H, W, min_size, masks_out, thresholds_out);
+    if (rc != TF_OK) {                                         // nothing of the call may still write the outputs when it returns
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         (void)hipGetLastError();
     }

@@ -54,14 +54,33 @@ __device__ __forceinline__ bool unite(uint32_t* par, uint32_t a, uint32_t b, uin
     return false;
 }
 
-// grid (tiles, planes); plane q = label q / nf, frame f0 + q % nf of the chunk.
-// PASS 0: the set is the background of m (computed here from the class map: the temporal window is fused into the load).
+// The set that the first labelling of a plane works on, as a functor in(q, p): plane q of the chunk, pixel p of the frame.
+// clean_mask: the background of m, computed from the class map (the temporal window is fused into the load); plane q = label q / nf,
+// frame f0 + q % nf of the chunk.
+struct ClassWindowBackground {
+    const uint8_t* __restrict__ cls; const uint8_t* __restrict__ ids;
+    int N, f0, nf; size_t HW;
+    __device__ __forceinline__ bool operator()(int q, size_t p) const
+    {
+        const int l = q / nf, f = f0 + q % nf;
+        const uint8_t c = ids[l];
+        const int fa = f > 0 ? f - 1 : 0, fc = f + 1 < N ? f + 1 : N - 1, fd = f + 2 < N ? f + 2 : N - 1;
+        const int count = (cls[(size_t)fa * HW + p] == c) + (cls[(size_t)f * HW + p] == c) + (cls[(size_t)fc * HW + p] == c) +
+                          (cls[(size_t)fd * HW + p] == c);
+        return !((double)count / 4.0 > 0.49);          // numpy: float64 window sum / n > threshold; the set is m's background
+    }
+};
+struct NoSet {                                         // PASS 1 derives its set from PASS 0's labelling, not from an input
+    __device__ __forceinline__ bool operator()(int, size_t) const { return false; }
+};
+
+// grid (tiles, planes).
+// PASS 0: the set is the background of m, as `set` gives it.
 // PASS 1: the set is filled = m or background not flagged as touching the border: par[p] == NONE (p in m) or aux[par[p]] == 0.  Also
 //         writes lr[p] = p's root inside the tile (tile-local index) for the size count of k_mask_flatten<1>.
-template <int PASS>
-__global__ __launch_bounds__(256) void k_mask_local(const uint8_t* __restrict__ cls, const uint8_t* __restrict__ ids, uint32_t* __restrict__ par,
-                                                   const uint32_t* __restrict__ aux, uint16_t* __restrict__ lr, int N, int f0, int nf, int H,
-                                                   int W, int tiles_x, unsigned* err)
+template <int PASS, class Set>
+__global__ __launch_bounds__(256) void k_mask_local(const Set set, uint32_t* __restrict__ par, const uint32_t* __restrict__ aux,
+                                                   uint16_t* __restrict__ lr, int H, int W, int tiles_x, unsigned* err)
 {
     __shared__ uint32_t lp[TPX];
     const int q = blockIdx.y;
@@ -76,12 +95,7 @@ __global__ __launch_bounds__(256) void k_mask_local(const uint8_t* __restrict__ 
         if (x < W && y < H) {
             const size_t p = (size_t)y * W + x;
             if (PASS == 0) {
-                const int l = q / nf, f = f0 + q % nf;
-                const uint8_t c = ids[l];
-                const int fa = f > 0 ? f - 1 : 0, fc = f + 1 < N ? f + 1 : N - 1, fd = f + 2 < N ? f + 2 : N - 1;
-                const int count = (cls[(size_t)fa * HW + p] == c) + (cls[(size_t)f * HW + p] == c) + (cls[(size_t)fc * HW + p] == c) +
-                                  (cls[(size_t)fd * HW + p] == c);
-                v = !((double)count / 4.0 > 0.49);     // numpy: float64 window sum / n > threshold; the set is m's background
+                v = set(q, p);
             } else {
                 const uint32_t r = P[p];
                 v = r == NONE || aux[(size_t)q * HW + r] == 0u;

@@ -316,6 +316,22 @@ class DenseFlow:
                                           out.ctypes.data), self._h, "tf_clean_masks")
         return out.view(np.bool_)
 
+    def otsu_masks(self, nparr, min_size, return_thresholds=False):
+        """The reference's predict_movie_thres (calculate_optical_flow.py:184-213) on the device, exact: RGB frames uint8 [N,H,W,3]
+        (N, H, W >= 2) -> bool [N,H,W,2]: per frame rgb2gray, skimage's threshold_otsu, fill holes, remove_small_objects(min_size), then
+        the moving average with the reference's defaults over the cleaned planes.  A C-contiguous array in pinned host memory.  With
+        `return_thresholds` also the per-frame Otsu thresholds, float64 [N].  May be called while submitted studies are in flight on
+        this engine."""
+        nparr = _u8_image_stack(nparr, "nparr", 4)
+        if nparr.shape[3] != 3 or min(nparr.shape[:3]) < 2:
+            raise OpticalFlowCalculationError(f"nparr must be [N>=2,H>=2,W>=2,3], got {nparr.shape}")
+        N, H, W = nparr.shape[:3]
+        out = self._pool.empty((N, H, W, 2), np.uint8)
+        thr = np.empty(N, np.float64) if return_thresholds else None
+        _lib.check(self._L.tf_otsu_masks(self._h, nparr.ctypes.data, N, H, W, int(min_size), out.ctypes.data,
+                                         thr.ctypes.data if return_thresholds else None), self._h, "tf_otsu_masks")
+        return (out.view(np.bool_), thr) if return_thresholds else out.view(np.bool_)
+
     def av_centroids(self, masks):
         """calc_AV_centroid's per-frame step (analyze_optical_flow.py:202-232) on the device, exact: masks bool or uint8 [N,H,W,C]
         (C = 1 or 2; the set is channel 0 != 0, 8-connected) -> (centroids float64 [N,2] (row, col) of the largest component, areas

@@ -6,7 +6,8 @@ where skimage / torchvision are absent.  Mirrors /root/reference/optical_flow/ca
   :184-213  predict_movie_thres (mode='otsu')
   :215-241  predict_movie      (modes 'A4C', 'RVIO_2class')
 moving_avg_mask / predict_movie_thres are pinned by tests/golden/reference_host_side.npz, clean_mask by
-tests/golden/reference_clean_mask.npz (host path here, device path DenseFlow.clean_masks).  Host-side glue, not a kernel:
+tests/golden/reference_clean_mask.npz (host path here, device path DenseFlow.clean_masks), predict_movie_thres also by
+tests/golden/reference_otsu.npz (host path here, device path DenseFlow.otsu_masks).  Host-side glue, not a kernel:
 the segmentor stays stock PyTorch(-ROCm), as north_star says."""
 import numpy as np
 
@@ -17,6 +18,9 @@ from .frames import rgb2gray
 def threshold_otsu(image, nbins=256):
     """skimage.filters.threshold_otsu for a float image (histogram over [min, max], bin centres)."""
     image = np.asarray(image, dtype=np.float64)
+    first = image.ravel()[0]
+    if np.all(image == first):                          # skimage: a one-valued image has no histogram to split
+        return first
     hist, edges = np.histogram(image.ravel(), bins=nbins, range=(image.min(), image.max()))
     centers = (edges[:-1] + edges[1:]) / 2.0
     hist = hist.astype(np.float64)
@@ -51,11 +55,17 @@ def moving_avg_mask(arr, n=4, threshold=0.49, config=None):
     return s[n - 1:] / n > threshold
 
 
-def predict_movie_thres(nparr, verbose=False, config=None):
-    """{'otsu': bool [N,H,W,2]} -- NB the reference calls moving_avg_mask WITHOUT config (Appendix C.5)."""
+def predict_movie_thres(nparr, verbose=False, config=None, *, engine=None):
+    """{'otsu': bool [N,H,W,2]} -- NB the reference calls moving_avg_mask WITHOUT config (Appendix C.5).
+    With an `engine` that has `otsu_masks` (DenseFlow) and uint8 [N,H,W,3] frames with N, H, W >= 2, the work runs on the device
+    (tf_otsu_masks, exact); otherwise, and for the shapes where the reference's np.squeeze changes what it computes, on the host."""
     from scipy.ndimage import binary_fill_holes
     if config is None:
         config = default_optical_flow_config()
+    arr = np.asarray(nparr)
+    if (engine is not None and hasattr(engine, "otsu_masks") and arr.dtype == np.uint8 and arr.ndim == 4 and arr.shape[3] == 3
+            and min(arr.shape[:3]) >= 2):
+        return {"otsu": engine.otsu_masks(arr, config.min_mask_size)}
     masks = []
     for i in range(nparr.shape[0]):
         g = rgb2gray(np.squeeze(nparr[i]))

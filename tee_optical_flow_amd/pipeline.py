@@ -169,11 +169,8 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     nparr = _prep_frames(nparr, flipLR)
     ps, fr = metadata["pixel_spacing"], metadata["frame_rate"]
     conversion_factor = 1.0 if ps is None or fr is None else ps * fr
-    if mask_dict is None:
-        if mode == "otsu":
-            from .masks import predict_movie_thres
-            mask_dict = predict_movie_thres(nparr, verbose=verbose, config=config)
-        elif mode in ("A4C", "RVIO_2class"):
+    if mask_dict is None and mode != "otsu":      # (otsu: made below, once the flow model exists -- on its device when it offers otsu_masks)
+        if mode in ("A4C", "RVIO_2class"):
             if segmentor_model is None:
                 raise ConfigurationError(f"mode={mode} needs segmentor_model (a module with image_encoder / prompt_encoder / "
                                          "mask_decoder, reference :47-88) or a precomputed mask_dict=")
@@ -183,7 +180,11 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     model = make_flow_model(OF_algo, config) if own else flow_model
     collect = None                                # () -> the study's flow array
     try:
-        if mask_dict is None:
+        if mask_dict is None and mode == "otsu":
+            # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
+            from .masks import predict_movie_thres
+            mask_dict = predict_movie_thres(nparr, verbose=verbose, config=config, engine=model)
+        elif mask_dict is None:
             # reference :549-550; the masks are cleaned on the flow model's device when it offers it (DenseFlow.clean_masks)
             from .masks import predict_movie
             mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config, engine=model)
@@ -396,9 +397,9 @@ def _shm_unlink_names(descs):
                 pass
 
 
-def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo):
+def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True):
     """_prepare_study in a worker process, the big arrays returned as shared-memory descriptors."""
-    nparr, md, pid, hr, masks_ahead, echo = _prepare_study(reader, path, mode, flipLR, config, want_echo)
+    nparr, md, pid, hr, masks_ahead, echo = _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead)
     made = []
     try:
         nparr = _shm_put(nparr); made.append(nparr)
@@ -472,7 +473,7 @@ class StudyWorkers:
         self.close()
 
 
-def _prepare_study(reader, path, mode, flipLR, config, want_echo):
+def _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True):
     """Reader stage of process_folder (module level: it also runs in worker processes).  Reads the study and -- for the Otsu mode,
     which is pure numpy/scipy -- computes its masks one study ahead of the GPU; with the solver at milliseconds per pair, this host
     work and the gzip-9 write are what a study costs.  `want_echo`: also the `echo` dataset (rgb2gray of the frames as float16,
@@ -480,7 +481,7 @@ def _prepare_study(reader, path, mode, flipLR, config, want_echo):
     nparr, md, pid, hr = reader(path)
     masks_ahead = None
     prepped = _prep_frames(nparr, flipLR)
-    if mode == "otsu":
+    if mode == "otsu" and otsu_ahead:               # (process_folder(otsu_masks="device"): the walk makes them on the engine instead)
         from .masks import predict_movie_thres
         masks_ahead = predict_movie_thres(prepped, verbose=False, config=config)
     echo = None
@@ -542,7 +543,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                    flipLR=False, verbose=True, recalculate=False, no_saliency=True, OF_algo="TVL1", save_mask_subset=None,
                    include_waveforms=False, waveform_folder=None, pixel_spacing=None, frame_rate=None, process_subset=False,
                    file_subset_list=(), *, rank=0, world=1, extensions=("dcm",), reader=read_study, flow_model=None, config=None,
-                   device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2):
+                   device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host"):
     """Drop-in for the reference's process_folder (:243-290), same positional signature and the same rules:
       * the folder listing is cut into `nchunks` slices of len // nchunks files, this call takes slice `chunk_index`
         (the remainder files are dropped, as the reference does -- SURVEY.md Appendix C.8);
@@ -561,7 +562,12 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     initialised the GPU yet as far as this function can tell) and more than one study is to do.  `studies_in_flight` (2): a study's flow solve is
     submitted to the engine's lanes (tf_submit_seq_rgb) and collected only when the NEXT study's has been submitted, so the GPU goes from one
     study's solve to the next without waiting for this thread (1 = solve and collect study by study, as rounds 2-4 did).
+    `otsu_masks` (mode="otsu" only): "host" (default) has the reader stage compute the Otsu masks one study ahead with numpy / scipy;
+    "device" has the reader stage skip them, and the walk makes them on the flow model (DenseFlow.otsu_masks, tf_otsu_masks; a model
+    without that method computes them on the host, in the caller's thread).  The files are the same either way.
     Returns the list of (filename, error string)."""
+    if otsu_masks not in ("host", "device"):
+        raise ConfigurationError(f"otsu_masks must be 'host' or 'device', not {otsu_masks!r}")
     os.makedirs(save_folder, exist_ok=True)
     file_list = sorted(os.listdir(dcm_folder))                      # os.listdir order is arbitrary; sorted = same slices on every rank
     errors = []
@@ -674,7 +680,8 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
         def submit(k):
             if k < len(todo) and k not in futs:
                 futs[k] = state["reader_pool"].submit(_prepare_study_shm if state["proc"] else _prepare_study, reader,
-                                                      os.path.join(dcm_folder, todo[k][0]), mode, flipLR, cfg_masks, state["proc"])
+                                                      os.path.join(dcm_folder, todo[k][0]), mode, flipLR, cfg_masks, state["proc"],
+                                                      otsu_masks == "host")
 
         def pools_to_threads(e, k):
             # The worker pools are unusable (a worker died while starting, something would not pickle): the stages go on in threads,

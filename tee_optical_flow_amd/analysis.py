@@ -96,9 +96,31 @@ def _lerp(a, b, t):
     return b - d * (1 - t) if t >= 0.5 else a + d * t
 
 
+def percentile_rank64(count, q):
+    """(prev, next, frac) of np.percentile(a, q) for `count` float64 values: method 'linear', the virtual index (count - 1) * (q / 100)
+    in float64, the next index clipped at count - 1.  The result is _lerp(sorted(a)[prev], sorted(a)[next], frac)."""
+    vi = (count - 1) * np.true_divide(q, 100)
+    prev = int(np.floor(vi))
+    return prev, min(prev + 1, count - 1), vi - prev
+
+
+def _check_finite_range(mn, mx):
+    """np.histogram's refusal of a non-finite range, raised before any device histogram runs.  f64_key orders a positive NaN above
+    +inf and a negative NaN below -inf, so the min/max a projection returns are finite exactly when every plane value is."""
+    if not (np.isfinite(mn) and np.isfinite(mx)):
+        raise ValueError(f"supplied range of [{mn}, {mx}] is not finite")
+
+
+def _check_bins(edges, nbins):
+    """np.histogram's refusal of edges that do not increase (a range too narrow for nbins bins)"""
+    if np.any(edges[:-1] >= edges[1:]):
+        raise ValueError(f"Too many bins for data range. Cannot create {nbins} finite-sized bins.")
+
+
 def radlong_stats_device(engine, OF_arr, centroid_list, perc_lo=1, perc_hi=99, nbins=1000, return_arrays=False):
     """{'radial': (freq, edges[:-1], hi, lo), 'longitudinal': (...)} as calculate_3dhist_radlong (:289-327) returns after its
-    centroid step, computed on the device behind `engine` (a DenseFlow).  return_arrays adds 'rad_arr' / 'long_arr'."""
+    centroid step, computed on the device behind `engine` (a DenseFlow).  return_arrays adds 'rad_arr' / 'long_arr'.  A NaN or
+    inf in a plane raises ValueError, as np.histogram does for the host twin."""
     L = engine._L
     n = len(centroid_list)
     OF = np.ascontiguousarray(np.asarray(OF_arr)[:n], dtype=np.float32)
@@ -115,15 +137,21 @@ def radlong_stats_device(engine, OF_arr, centroid_list, perc_lo=1, perc_hi=99, n
 
 def _radlong_stats_resident(engine, N, mm, nz, perc_lo, perc_hi, nbins, rad=None, lon=None):
     """The statistics of the projections resident on the device after tf_radlong_project(_param): per frame histogram, the exact
-    order statistics np.percentile interpolates between, and the reference's per-frame loop.  mm / nz as the projection returned."""
+    order statistics np.percentile interpolates between, and the reference's per-frame loop.  mm / nz as the projection returned.
+    Raises the ValueError np.histogram raises in the host twin (a non-finite range, or one too narrow for nbins bins) before the
+    device histogram of that component runs."""
     L = engine._L
     nz = np.asarray(nz).reshape(-1)
     out = {}
     for which, name in ((0, "radial"), (1, "longitudinal")):
         mn, mx = mm[2 * which], mm[2 * which + 1]
         cnt = nz[which::2]
+        if cnt.any():                                                         # the host calls np.histogram for a non-empty frame only
+            _check_finite_range(mn, mx)
         first, last = (mn, mx) if mn != mx else (mn - 0.5, mx + 0.5)          # np.histogram's degenerate-range rule
         edges = np.linspace(first, last, nbins + 1)
+        if cnt.any():
+            _check_bins(edges, nbins)
         freq = np.zeros((N, nbins), np.int64)
         _lib.check(L.tf_radlong_hist(engine._h, which, edges.ctypes.data, nbins, freq.ctypes.data), engine._h, "tf_radlong_hist")
         ranks = np.full((N, 4), -1, np.int64)
@@ -131,11 +159,7 @@ def _radlong_stats_resident(engine, N, mm, nz, perc_lo, perc_hi, nbins, rad=None
         for i in range(N):
             if cnt[i] > 0:
                 for j, q in enumerate((perc_hi, perc_lo)):
-                    vi = (cnt[i] - 1) * np.true_divide(q, 100)
-                    lo_i = int(np.floor(vi))
-                    ranks[i, 2 * j] = lo_i
-                    ranks[i, 2 * j + 1] = min(lo_i + 1, cnt[i] - 1)
-                    frac[i, j] = vi - lo_i
+                    ranks[i, 2 * j], ranks[i, 2 * j + 1], frac[i, j] = percentile_rank64(cnt[i], q)
         vals = np.zeros((N, 4), np.float64)
         _lib.check(L.tf_radlong_select(engine._h, which, ranks.ctypes.data, vals.ctypes.data), engine._h, "tf_radlong_select")
         per = [None if cnt[i] == 0 else (_lerp(vals[i, 0], vals[i, 1], frac[i, 0]), _lerp(vals[i, 2], vals[i, 3], frac[i, 1]), freq[i])
@@ -448,6 +472,7 @@ def _hist_device(engine, n, mm, nz, nbins, percentile):
     cnt, acnt = nz[:, 0], nz[:, 1]
     if cnt[0] == 0:
         raise IndexError("list index out of range")           # the reference's perc_hi[-1] on an empty first frame
+    _check_finite_range(mn, mx)                                # np.histogram's ValueError, before tf_radlong_hist runs
     mag_edges = _polar_edges(mn, mx, nbins)
     e64 = mag_edges.astype(np.float64)                         # exact; held here while the library reads it
     freq = np.zeros((n, nbins), np.int64)
@@ -470,6 +495,7 @@ def _hist_device(engine, n, mm, nz, nbins, percentile):
             mag_freq.append(freq[i] + 1)
     ang_edges = []
     if acnt.any():
+        _check_finite_range(amn, amx)
         ang_edges = _polar_edges(amn, amx, nbins)
         a64 = ang_edges.astype(np.float64)
         afreq = np.zeros((n, nbins), np.int64)
@@ -482,8 +508,9 @@ def calculate_3dhist(ds, param, label, nbins=1000, percentile=99, *, engine=None
     """The reference's calculate_3dhist(ds, param, label) (analyze_optical_flow.py:909-966): (mag_freq, ang_freq, mag_edges[:-1],
     ang_edges[:-1], hi_arr) for frames [0, ds.nframes) of cv2.cartToPolar(get_masked_arr(param, label)), quirks kept: freq + 1; an
     empty frame copies the previous row and hi; an empty angle frame takes the magnitude row of the study's last frame; an empty
-    first frame raises IndexError; an unknown param or label is logged and gives None.  float32 statistics as numpy >= 2 computes
-    them.  `ds` is the reference's OpticalFlowDataset or a FlowStudy.  With `engine` (a DenseFlow) every per-pixel step runs on the
+    first frame raises IndexError; an unknown param or label is logged and gives None; a NaN or inf in the field (or a magnitude that
+    overflows float32) raises np.histogram's ValueError.  float32 statistics as numpy >= 2 computes them.
+    `ds` is the reference's OpticalFlowDataset or a FlowStudy.  With `engine` (a DenseFlow) every per-pixel step runs on the
     device, with the same bits."""
     if not _valid(ds, param, label):
         return None
@@ -509,7 +536,10 @@ def _mode_of_rounded(ang):
 def angle_mode_series(ds, param, label, *, engine=None):
     """The per-frame series AngleDetector.detect (cardiac_cycle_detection.py:100-120) hands to its SpectralSmoother: for frames
     [0, ds.nframes), scipy.stats.mode of the non-zero np.round(ang, 2) of cv2.cartToPolar(get_masked_arr(param, label)), float32,
-    NaN for a frame without any.  With `engine` (a DenseFlow) it runs on the device (tf_polar_project_param), with the same bits."""
+    NaN for a frame without any.  With `engine` (a DenseFlow) it runs on the device (tf_polar_project_param), with the same bits.
+    Non-finite input: the host twin lets np.unique count NaN angles; the device path does not imitate that (its bins drop a NaN
+    angle, and fminf / fmaxf in its cart_to_polar drop a NaN operand where numpy propagates it) and raises ValueError instead
+    whenever a magnitude or an angle of the field is NaN or inf, so it never returns a mode where the twin's differs."""
     if param not in PARAMS:
         raise ValueError(f"param must be one of {PARAMS}, got {param!r}")
     if label not in list(ds.accepted_labels):
@@ -519,4 +549,7 @@ def angle_mode_series(ds, param, label, *, engine=None):
     if engine is None:
         _, ang = polar_field(flow, mask, param, ds.frame_rate, n)
         return np.asarray([_mode_of_rounded(ang[i]) for i in range(n)], np.float32)
-    return engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)[2]
+    mm, _, mode, _, _ = engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+    if not np.isfinite(mm).all():
+        raise ValueError(f"the field holds NaN or inf (magnitude range [{mm[0]}, {mm[1]}], angle range [{mm[2]}, {mm[3]}])")
+    return mode

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tee_optical_flow_amd import analysis as A
+from tests.stats_cases import device_hist_rule as _device_hist_rule
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 OUTS = ("mag_freq", "ang_freq", "mag_edges", "ang_edges", "hi")
@@ -104,19 +105,6 @@ def test_float32_percentile_mirror_equals_numpy():
             got = A._lerp32(srt[p], srt[nx], g)
             want = np.percentile(a, q)
             assert type(got) is type(want) and got.view(np.int32) == want.view(np.int32), (n, q, got, want)
-
-
-def _device_hist_rule(x, edges):
-    """k_radlong_hist's rule in numpy: the float64 estimate, then one step of numpy's fix-up against the float32 edges"""
-    e = edges.astype(np.float64)
-    nb = len(e) - 1
-    x = x.astype(np.float64)
-    x = x[(x != 0) & (x >= e[0]) & (x <= e[nb])]
-    idx = np.clip((((x - e[0]) / (e[nb] - e[0])) * nb).astype(np.int64), 0, nb - 1)
-    idx -= x < e[idx]
-    up = (idx != nb - 1) & (x >= e[np.minimum(idx + 1, nb)])
-    idx += up
-    return np.bincount(idx, minlength=nb)
 
 
 def test_histogram_rule_of_the_device_equals_numpy_on_float32_edges():

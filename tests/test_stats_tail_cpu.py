@@ -1,0 +1,329 @@
+"""The device statistics tail without a GPU (tests/stats_cases.py): every generated case has the property its name claims and is
+accepted by numpy; numpy models of the two device algorithms (the histogram rule of k_radlong_hist, the 4-pass radix select of
+k_radlong_sel_hist / k_radlong_sel_scan) equal np.histogram and np.sort on every case; the Python glue (percentile_rank64,
+percentile_index, _lerp, _lerp32) equals np.percentile; and the host twins run every case, so that the expected values of
+tests/test_gpu_stats_tail.py exist."""
+import numpy as np
+import pytest
+
+from tee_optical_flow_amd import analysis as A
+from tests import stats_cases as S
+
+RAD = S.radlong_cases()
+POL = S.polar_cases()
+ALL = RAD + POL
+NONFINITE = S.nonfinite_cases()
+
+
+def _ids(cases):
+    return [c.name for c in cases]
+
+
+def _tagged(tag, cases=ALL):
+    got = [c for c in cases if tag in c.tags]
+    assert got, tag
+    return got
+
+
+def _frames(case):
+    """(plane index, frame, the frame's non-zero values, the plane's min, max) for every non-empty frame of both planes"""
+    for w, arr in enumerate(case.planes()):
+        mn, mx = arr.min(), arr.max()
+        for f in range(case.n_used):
+            fl = arr[f].ravel()
+            nz = fl[fl != 0]
+            if len(nz):
+                yield w, f, nz, mn, mx
+
+
+def _ranks(case, n):
+    qs = (case.perc_lo, case.perc_hi) if case.path == "radlong" else (case.percentile,)
+    r = {0, n - 1, n // 2}
+    for q in qs:
+        r.update(A.percentile_rank64(n, q)[:2] if case.path == "radlong" else A.percentile_index(n, q)[:2])
+    return sorted(r)
+
+
+def test_case_names_are_unique_and_sizes_are_as_the_kernels_need():
+    names = _ids(ALL + NONFINITE)
+    assert len(set(names)) == len(names)
+    px = [c.flow.shape[1] * c.flow.shape[2] for c in ALL]
+    assert all(c.n_used <= 65 for c in ALL)                               # the select's scratch: 4 * 65536 * 4 B per frame
+    for path in ("radlong", "polar"):
+        mine = [c for c in ALL if c.path == path]
+        assert any(c.flow.shape[1] * c.flow.shape[2] > 65536 for c in mine)                   # the grid cap: a second trip of the stride loop
+        assert any((c.flow.shape[1] * c.flow.shape[2]) % 256 for c in mine)
+        assert {c.param for c in _tagged("ties", mine)} == set(A.PARAMS) == {c.param for c in _tagged("empty", mine)}
+        assert {c.flow.dtype for c in _tagged("ties", mine)} == {np.dtype(np.float16), np.dtype(np.float32)}
+        assert {c.mask.shape[3] for c in _tagged("ties", mine)} == {1, 2}
+        assert {type(c.frame_rate) for c in _tagged("ties", mine)} == {float, np.float64}
+        assert {c.nbins for c in _tagged("nbins", mine)} == set(S.NBINS)
+        assert {(c.perc_lo, c.perc_hi) for c in _tagged("percentiles", mine)} == set(S.PERC_PAIRS)
+    assert sum(p <= 65536 for p in px) > len(px) * 0.9
+    assert any(c.perc_lo == c.perc_hi for c in RAD) and any(c.perc_lo > c.perc_hi for c in RAD)
+
+
+def test_one_column_studies_plant_the_flow_in_the_planes():
+    for c in RAD:
+        if c.flow.shape[2] == 1 and c.param == "velocity" and c.cent[0] == S.CENT:
+            rad, lon = c.planes()
+            m = c.mask[:c.n_used, :, 0, 0]
+            assert np.array_equal(rad[..., 0], -c.flow[:c.n_used, :, 0, 0].astype(np.float64) * m), c.name
+            assert np.array_equal(lon[..., 0], c.flow[:c.n_used, :, 0, 1].astype(np.float64) * m[..., None][..., 0]), c.name
+    for c in POL:
+        if c.flow.shape[2] == 1 and c.param == "velocity" and not c.flow[..., 1].any():
+            mag, _ = c.planes()
+            assert np.array_equal(mag[..., 0], np.abs(c.flow[:c.n_used, :, 0, 0].astype(np.float32)) * c.mask[:c.n_used, :, 0, 0]), c.name
+
+
+def test_ties_cases_hold_ties():
+    for c in _tagged("ties"):
+        n = 0
+        for w, f, nz, _, _ in _frames(c):
+            if c.path == "polar" and w == 1:
+                continue                                                     # the magnitudes carry the case
+            assert len(np.unique(nz)) < len(nz), (c.name, w, f)
+            n += 1
+        assert n
+        if "distinct" in c.info and c.path == "radlong":
+            assert all(len(np.unique(nz)) == c.info["distinct"] for _, _, nz, _, _ in _frames(c))
+    c = next(c for c in RAD if c.name == "r_ties_one_value_but_a_handful")
+    for _, _, nz, _, _ in _frames(c):
+        v, k = np.unique(nz, return_counts=True)
+        assert 1 < len(v) <= 6 and k.max() >= len(nz) - 5
+
+
+def _edges(case, mn, mx):
+    if case.path == "polar":
+        return A._polar_edges(mn, mx, case.nbins)
+    return np.linspace(mn, mx, case.nbins + 1)
+
+
+def test_edge_cases_sit_on_the_edges():
+    for c in _tagged("edges"):
+        for w, f, nz, mn, mx in _frames(c):
+            if c.path == "polar" and w == 1:
+                continue                                                     # the angles of fy = 0 are 0 or pi
+            assert (mn, mx) == (c.info["lo"], c.info["hi"]), (c.name, mn, mx)
+            e = _edges(c, mn, mx)
+            on = np.isin(nz, e)
+            assert e[-1] in nz, c.name                                       # the last edge belongs to the last bin
+            assert on.sum() >= 10 or (c.path == "radlong" and "ragged" in c.name), c.name    # (float32 data beside float64 edges)
+            if "every_datum_on_an_edge" in c.tags:
+                assert on.all() and np.isin(e[1:], nz).all() and np.array_equal(e, np.arange(c.nbins + 1) * (mx / c.nbins))
+            if "own_edges" in c.tags:
+                assert e[0] in nz and np.nextafter(np.float32(e[0]), np.float32(np.inf)) in nz
+                assert np.nextafter(np.float32(e[-1]), np.float32(-np.inf)) in nz
+                e32 = e.astype(np.float32)
+                inner = e32[1:-1]
+                assert np.isin(inner, nz).all() and np.isin(np.nextafter(inner, np.float32(np.inf)), nz).all()
+                assert np.isin(np.nextafter(inner, np.float32(-np.inf)), nz).all()
+                if c.path == "polar" or "dyadic" in c.name:
+                    assert np.array_equal(e32.astype(np.float64), e.astype(np.float64))      # the data equal the edges themselves
+
+
+def test_percentile_cases_reach_integer_half_and_clipped_indices():
+    seen = set()
+    for c in _tagged("percentiles"):
+        counts = [len(nz) for w, _, nz, _, _ in _frames(c) if w == 0]
+        assert tuple(counts) == S.COUNTS, (c.name, counts)
+        for n in counts:
+            for q in (c.perc_lo, c.perc_hi):
+                vi = (n - 1) * (q / 100)
+                p, nx, g = A.percentile_rank64(n, q)
+                seen.add("integer" if vi == int(vi) else "half" if vi - int(vi) == 0.5 else "other")
+                if p == nx == n - 1 and n > 1:
+                    seen.add("clipped")
+                if p == 0 and g == 0:
+                    seen.add("rank0")
+    assert seen >= {"integer", "half", "other", "clipped", "rank0"}
+
+
+def test_key_cases_have_the_keys_they_name():
+    def keys(case, w=0):
+        return np.unique(np.concatenate([S.f64_key(nz) for ww, _, nz, _, _ in _frames(case) if ww == w]))
+
+    for c in _tagged("top_digit"):
+        k = keys(c)
+        low = k & np.uint64(0xFFFFFFFFFFFF)                                  # a negative value's key is the complement of its bits
+        assert set(low.tolist()) <= {0, 0xFFFFFFFFFFFF} and len(np.unique(k >> np.uint64(48))) == len(k) >= 17, c.name
+    for c in _tagged("cluster32"):
+        k = keys(c)
+        hi32 = k >> np.uint64(32)
+        assert len(k) >= 30 and max(np.unique(hi32, return_counts=True)[1]) == 8, c.name      # a float32 ulp is 2^29 float64 ulps
+        assert set((k & np.uint64(0xFFFF)).tolist()) <= {0, 0xFFFF}          # float32 data: the lowest digit never differs
+    for c in _tagged("cluster48"):
+        for w in (0, 1):
+            k = keys(c, w)
+            grp, cnt = np.unique(k >> np.uint64(16), return_counts=True)
+            assert cnt.max() >= 2 and len(np.unique(k & np.uint64(0xFFFF))) > 20, c.name    # only the select's last pass tells them apart
+        # and a rank the case asks for lies inside such a group
+        hit = False
+        for w, f, nz, _, _ in _frames(c):
+            srt = np.sort(nz)
+            ks = S.f64_key(srt) >> np.uint64(16)
+            for r in _ranks(c, len(nz)):
+                hit |= bool((r > 0 and ks[r - 1] == ks[r] and srt[r - 1] != srt[r]) or (r + 1 < len(nz) and ks[r + 1] == ks[r] and srt[r + 1] != srt[r]))
+        assert hit
+    c = next(c for c in RAD if "extremes" in c.tags)
+    v = np.abs(c.flow[c.flow != 0].astype(np.float64))
+    assert v.min() < np.finfo(np.float32).tiny and v.max() > 1e38 and np.isfinite(np.concatenate([p.ravel() for p in c.planes()])).all()
+    for c in _tagged("signed_zeros"):
+        z = c.flow[:c.n_used, :, 0, 0]
+        assert (np.signbit(z) & (z == 0)).any() and (~np.signbit(z) & (z == 0)).any()
+        assert {bool(x) for x in np.signbit(z[z != 0])} == ({True, False} if c.path == "radlong" else {False})
+    assert any((np.concatenate([nz for _, _, nz, _, _ in _frames(c)]) < 0).any() and (np.concatenate([nz for _, _, nz, _, _ in _frames(c)]) > 0).any()
+               for c in RAD)
+
+
+def test_empty_and_degenerate_cases():
+    for c in _tagged("empty"):
+        planes = c.planes()
+        if "empty" in c.info:
+            for f in range(c.n_used):
+                assert all(bool(p[f].any()) == (f not in c.info["empty"]) for p in planes[:1]), (c.name, f)
+        else:
+            assert any(not planes[0][f].any() for f in range(c.n_used)) and planes[0].any()
+    for which in ("first", "middle", "last", "all"):
+        assert len(_tagged("empty_" + which, RAD)) == 3 == len(_tagged("empty_" + which, POL))
+    for c in _tagged("min_eq_max"):
+        p = c.planes()[0]
+        assert p.min() == p.max() != 0
+    for c in _tagged("min_zero"):
+        p = c.planes()[0]
+        assert p.min() == 0 and len(np.unique(p[p != 0])) == 1
+
+
+def test_angle_cases_hold_the_tie_that_was_meant():
+    pool = S.angle_pool()
+    assert sorted(pool) == list(range(629))                                  # the sweep reaches every bin
+    for c in S.angle_cases():
+        _, ang = c.planes()
+        for f in range(c.n_used):
+            a = ang[f][ang[f] != 0]
+            k, cnt = np.unique(np.rint(a * np.float32(100)).astype(int), return_counts=True)
+            cnt = cnt[k != 0]
+            k = k[k != 0]
+            want = c.info["want_k"][f]
+            got = A._mode_of_rounded(ang[f])
+            if want == 0:
+                assert np.isnan(got) and len(k) == 0, (c.name, f)
+            else:
+                assert got == np.float32(want) / np.float32(100) and k[np.argmax(cnt)] == want, (c.name, f)
+            top = set(k[cnt == cnt.max()]) if len(k) else set()
+            if "tie_stride" in c.tags:
+                assert len(top) >= 2 and len({t % 256 for t in top}) == 1 and min(top) == want      # one thread of the stride loop sees them all
+            if "tie_waves" in c.tags:
+                assert len(top) >= 2 and len({((t - 1) % 256) // 64 for t in top}) >= 2 and min(top) == want
+            if "all_equal" in c.tags:
+                assert len(top) == len(k) >= 623 and min(top) == want
+            if "only_628" in c.tags:
+                assert list(k) == [628]
+            if "round_to_zero" in c.tags and want == 0:
+                assert len(a) > 0                                            # non-zero angles, none of which survives the rounding
+    assert {t for c in S.angle_cases() for t in c.tags} >= {"tie_stride", "tie_waves", "all_equal", "only_628", "round_to_zero", "single_pixel", "big"}
+
+
+@pytest.mark.parametrize("case", ALL, ids=_ids(ALL))
+def test_host_twins_run_every_case(case):
+    """numpy accepts every case: nothing raises but the cases made to (an empty first polar frame; too many bins)"""
+    def run():
+        if case.path == "radlong":
+            return S.host_radlong(case)
+        A.angle_mode_series(case.study(), case.param, "m")
+        return A.calculate_3dhist(case.study(), case.param, "m", nbins=case.nbins, percentile=case.percentile)
+
+    if case.raises is None:
+        run()
+        return
+    with pytest.raises(case.raises) as ei:
+        run()
+    assert ("too_many_bins" in case.tags) == (S.TOO_MANY_BINS in str(ei.value)), case.name
+
+
+@pytest.mark.parametrize("case", NONFINITE, ids=_ids(NONFINITE))
+def test_host_twins_refuse_a_non_finite_range(case):
+    with np.errstate(invalid="ignore"):
+        assert not np.isfinite(np.concatenate([p.ravel() for p in case.planes()])).all()
+    with pytest.raises(ValueError, match="is not finite"), np.errstate(invalid="ignore"):
+        if case.path == "radlong":
+            S.host_radlong(case)
+        else:
+            A.calculate_3dhist(case.study(), case.param, "m", nbins=case.nbins, percentile=case.percentile)
+
+
+def test_finite_range_check_is_the_key_order():
+    """f64_key puts a positive NaN above +inf and a negative NaN below -inf: the min / max of the keys are finite exactly when every
+    value is, which is what analysis._check_finite_range relies on"""
+    nnan = np.copysign(np.nan, -1.0)
+    v = np.float64([-np.inf, -1e308, -5e-324, 5e-324, 1e308, np.inf])
+    assert np.all(np.diff(S.f64_key(v).astype(object)) > 0)
+    assert S.f64_key([np.nan])[0] > S.f64_key([np.inf])[0] and S.f64_key([nnan])[0] < S.f64_key([-np.inf])[0]
+    for bad in (np.nan, nnan, np.inf, -np.inf):
+        k = S.f64_key(np.float64([1.0, bad, -2.0]))
+        mn, mx = S.f64_unkey(k.min()), S.f64_unkey(k.max())
+        assert not (np.isfinite(mn) and np.isfinite(mx))
+        with pytest.raises(ValueError):
+            A._check_finite_range(mn, mx)
+    A._check_finite_range(-1e308, 1e308)
+
+
+HISTABLE = [c for c in ALL if "too_many_bins" not in c.tags]               # numpy makes no edges for those
+
+
+@pytest.mark.parametrize("case", HISTABLE, ids=_ids(HISTABLE))
+def test_histogram_rule_of_the_device_equals_numpy(case):
+    """on the case's own edges (float64 linspace for rad/long, numpy's float32 edges for polar), and the polar magnitudes on float64
+    edges as well"""
+    n = 0
+    for w, f, nz, mn, mx in _frames(case):
+        freq, e = np.histogram(nz, bins=case.nbins, range=(mn, mx))
+        if case.path == "polar":
+            assert e.dtype == np.float32 and np.array_equal(e, A._polar_edges(mn, mx, case.nbins))
+        assert np.array_equal(S.device_hist_rule(nz, e), freq), (case.name, w, f)
+        assert freq.sum() == len(nz)
+        if case.path == "polar":
+            nz64 = nz.astype(np.float64)
+            f64, e64 = np.histogram(nz64, bins=case.nbins, range=(np.float64(mn), np.float64(mx)))
+            assert e64.dtype == np.float64 and np.array_equal(S.device_hist_rule(nz64, e64), f64), (case.name, w, f, "f64")
+        n += 1
+    assert n or "empty_all" in case.tags
+
+
+@pytest.mark.parametrize("case", ALL, ids=_ids(ALL))
+def test_select_model_equals_sort(case):
+    for w, f, nz, _, _ in _frames(case):
+        if case.path == "polar" and w == 1:
+            continue                                                         # the select serves the magnitudes only
+        srt = np.sort(nz.astype(np.float64))
+        for r in _ranks(case, len(nz)):
+            got = S.select_model(nz, r)
+            assert got.view(np.uint64) == srt[r].view(np.uint64), (case.name, w, f, r, got, srt[r])
+
+
+def test_select_model_on_the_digit_boundaries():
+    """ranks at both ends of a bucket and of a 256-bucket group, where `<= r` and `< r` part ways"""
+    v = np.float64([1.0] * 3 + [2.0] * 2 + [-1.0] * 4 + [np.nextafter(2.0, 3)] + [0.0, -0.0])
+    srt = np.sort(v[v != 0])
+    for r in range(len(srt)):
+        assert S.select_model(v, r) == srt[r]
+
+
+def test_percentile_glue_equals_numpy():
+    rng = np.random.default_rng(17)
+    counts = list(range(1, 301)) + sorted({len(nz) for c in ALL if "image" not in c.tags or "single_pixel" in c.tags for _, _, nz, _, _ in _frames(c)})
+    qs = sorted(set(S.PERCENTILES) | {q for c in ALL for q in (c.perc_lo, c.perc_hi, c.percentile)})
+    for n in counts:
+        a = (rng.standard_normal(n) * 9).astype(np.float16).astype(np.float64) if n % 2 else rng.standard_normal(n) * rng.uniform(0.01, 50)
+        a32 = a.astype(np.float32)
+        s64, s32 = np.sort(a), np.sort(a32)
+        for q in qs:
+            p, nx, g = A.percentile_rank64(n, q)
+            assert 0 <= p <= nx <= n - 1
+            got = A._lerp(s64[p], s64[nx], g)
+            want = np.percentile(a, q)
+            assert type(got) is type(want) and got.view(np.uint64) == want.view(np.uint64), (n, q, got, want)
+            p, nx, g = A.percentile_index(n, q)
+            got = A._lerp32(s32[p], s32[nx], g)
+            want = np.percentile(a32, q)
+            assert type(got) is type(want) and got.view(np.int32) == want.view(np.int32), (n, q, got, want)

@@ -49,7 +49,8 @@ extern "C" {
 
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
-                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param and tf_otsu_masks */
+                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param, tf_otsu_masks and
+                              tf_radlong_overlay */
 
 enum {
     TF_OK = 0,
@@ -302,6 +303,31 @@ int tf_polar_project_param(tf_handle* h, const void* flow, int flow_is_f16, int 
                            int mask_C, int param, double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax,
                            long long* nonzero, float* ang_mode);
 
+/* ---- the per-pixel part of visualize_radlong (optical_flow/analyze_optical_flow.py:488-560; visualization.py:241-297, 1045-1051 for
+ *      other colormaps), on the device: the radial / longitudinal overlay frames.
+ * tf_radlong_overlay acts on the planes of the handle's last tf_radlong_project / tf_radlong_project_param call; n, H and W are theirs.
+ *   half = max |rad[0]| (ONE CenteredNorm, frozen by its first call: frame 0 of the radial plane, used for every frame of both
+ *   components); t = (a + half) / (2 * half) in float64, 0 everywhere if half == 0, not clipped; LUT index clip(floor(t * 256), 0, 255)
+ *   (matplotlib's lookup with under = entry 0, over = entry 255); m2 = the largest channel value among the LUT entries either
+ *   component used; out = uint8(((0.5 * (echo / echo max)) + (0.5 * (lut[index] / m2))) * 255), truncating, radial in columns [0, W),
+ *   longitudinal in [W, 2W).  echo: host [>= n][H][W], TF_ECHO_F16 (the study file's float16: quotient and its half are float16
+ *   operations, as numpy runs them: computed in float32, rounded to half to nearest-even, subnormals kept) or TF_ECHO_U8 (float64
+ *   division); the maximum is over the first n frames.  lut_rad / lut_long: float64 [256][3] RGB, finite and >= 0.
+ *   out: host uint8 [n][H][2W][3].  info[3] = half, echo max, m2.
+ *   TF_ERR_INVALID_ARG with a message: no projection yet; the last projection was tf_polar_project_param; planes that hold NaN or inf;
+ *   a negative or non-finite echo value; an echo maximum of 0; a LUT entry that is negative or not finite; 2 * half overflowing;
+ *   m2 == 0 (the reference's result in all of these is an undefined cast).  Runs on the handle's stream and never on a lane's, so it may
+ *   be called while tf_submit_* jobs of the handle are in flight; host-synchronous; every argument is checked before any GPU work.
+ *   Device scratch, grown on demand and kept by the handle: 2 bytes per pixel of the study (the indices), and 8 (float16 echo) or 7 bytes
+ *   per pixel of a chunk of frames of at most 512 MiB (at least one frame): the echo and the output. */
+#define TF_ECHO_F16 0
+#define TF_ECHO_U8  1
+int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const double* lut_rad, const double* lut_long, uint8_t* out,
+                       double* info);
+/* shape[3] = n, H, W of the rad/long planes tf_radlong_overlay would act on (what sizes its echo and out); all 0 when there are none
+ * or the last projection was tf_polar_project_param.  No GPU work. */
+int tf_radlong_shape(tf_handle* h, int* shape);
+
 /* ---- multi-GPU: the single exchange step of the path.  The reference's loop is sequential
  *      (calculate_optical_flow.py:584-597); here pairs shard over the GPUs of a node with no data-path traffic during the
  *      solve, and ONE RCCL all-gather of the (u,v) fields over xGMI assembles the result on every rank.  librccl is loaded
@@ -351,12 +377,12 @@ int tf_device_count(void);
  * 128x32 regions for small batches, 0 = never), "sor_coop_small" (0 = small batches keep the tiled form), "sor_coop_s" (sweeps between two exchanges), "sor_coop_min_util" (per cent of its CUs such a launch must fill, else tiled), "df_fuse_ds" (form of the data/smoothness kernel).
  * Both: "lanes" (contiguous units a call of at most one sub-batch is split into, solved side by side on the queue lanes), "queue_lanes" (lanes
  * that take those units, the sub-batches of larger calls and tf_submit_* jobs from the queue: -1 = 3 for DualTVL1, "lanes" for DeepFlow [default];
- * 0 = no lanes: the handle solves every call alone, sub-batch after sub-batch -- the same flows), "queue_unit" (pairs per queued sub-batch; 0 = equal sub-batches of at most max_batch pairs, a multiple of the lane count of them). */
+ * 0 = no lanes: the handle solves every call alone, sub-batch after sub-batch -- the same flows), "queue_unit" (pairs per queued sub-batch; 0 = equal sub-batches of at most max_batch pairs, a multiple of the lane count of them).
+ * tf_radlong_overlay: "overlay_chunk_kib" (tests: the echo and output of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]). */
 int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),
  * "coop_aborts" (calls repeated with the tiled form because such a launch gave up waiting), "coop_disabled"; "queue_jobs", "queue_units_done",
- * "queue_units_failed", "queue_units_skipped" (sub-batches dropped because an earlier one of their call had failed), "queue_outstanding", "queue_lanes";
- * -1 for an unknown name */
+ * "queue_units_failed", "queue_units_skipped" (sub-batches dropped because an earlier one of their call had failed), "queue_outstanding", "queue_lanes"; -1 for an unknown name */
 long long tf_dbg_counter(tf_handle* h, const char* name);
 /* DeepFlow hooks: one cv::VariationalRefinement::calcUV on dense float images (u, v updated in place); 3x3 Gaussian blur */
 int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v);

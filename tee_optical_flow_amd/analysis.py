@@ -23,9 +23,17 @@ both on cv2.cartToPolar, restated here as cart_to_polar (OpenCV 4.x's AVX2 / NEO
 section 2).  With engine= the field, the transform, the angle histogram and mode run fused on the device (tf_polar_project_param) and
 the magnitude / angle statistics come from tf_radlong_hist / tf_radlong_select; without, numpy.  Pinned by
 tests/golden/reference_polar.npz (the reference's own calculate_3dhist and AngleDetector.detect, with cart_to_polar as cv2).
+
+And the overlay video of the rad/long projections:
+  analyze_optical_flow.py:488-560  overlay3, visualize_radlong(ds, param, save_dir)                   -> radlong_overlay, visualize_radlong
+  visualization.py:241-297, 1045-1051  VisualizationManager.visualize_radlong (other colormaps)       -> the colormap_rad / colormap_long keywords
+With engine= the frames are rendered on the device from the planes tf_radlong_project_param left resident (tf_radlong_overlay), 6 bytes
+per pixel downloaded; without, a numpy twin that keeps index planes instead of RGBA float64 arrays.  Pinned by
+tests/golden/reference_overlay.npz (the frames the reference's own functions handed to their video writer).
 """
 import ctypes as C
 import logging
+import os
 
 import numpy as np
 
@@ -306,9 +314,12 @@ def calculate_3dhist_radlong(ds, param, nbins=1000, perc_lo=1, perc_hi=99, av_fi
 class FlowStudy:
     """What calculate_3dhist_radlong reads of a study, built from arrays: flow [N,H,W,2] as given (float16 as the study file holds
     it: the device upload is then 2 bytes per component), masks {label: [N,H,W,C]}, frame_rate, nframes (default N - 2, as
-    OpticalFlowDataset reads attrs['nframes'] - 2 of a file whose flow has attrs['nframes'] frames), mode."""
+    OpticalFlowDataset reads attrs['nframes'] - 2 of a file whose flow has attrs['nframes'] frames), mode; and, for the overlay
+    video, echo [>= nframes,H,W] as the study file holds it (float16) and filename (the stem of the video's name)."""
 
-    def __init__(self, flow, masks, frame_rate, nframes=None, mode="RVIO_2class"):
+    def __init__(self, flow, masks, frame_rate, nframes=None, mode="RVIO_2class", echo=None, filename="study"):
+        self.echo = None if echo is None else np.asarray(echo)
+        self.filename = filename
         self.flow = np.asarray(flow)
         if self.flow.ndim != 4 or self.flow.shape[3] != 2:
             raise ValueError(f"flow must be [N,H,W,2], got {self.flow.shape}")
@@ -328,6 +339,9 @@ class FlowStudy:
             return None
         return self.masks[label]
 
+    def get_echo(self):
+        return self.echo
+
     @classmethod
     def from_hdf5(cls, path):
         """A study file in the reference's layout (hdf5_out.py), read as OpticalFlowDataset reads it, the flow kept float16.
@@ -339,7 +353,9 @@ class FlowStudy:
             a = d.attrs
             frame_rate = a["frame_rate"] if a["units_converted"] else 1
             masks = {str(k): f[k][()] for k in a["labels"]}
-            return cls(flow, masks, frame_rate, nframes=a["nframes"] - 2, mode=a["mode"])
+            echo = f["echo"][()] if "echo" in f else None
+            # (OpticalFlowDataset's filename: the base name less its last four characters, whatever the extension)
+            return cls(flow, masks, frame_rate, nframes=a["nframes"] - 2, mode=a["mode"], echo=echo, filename=os.path.basename(path)[:-4])
 
 
 # ---- the polar steps: cv2.cartToPolar, calculate_3dhist, the angle detector's per-frame mode --------------------------------
@@ -553,3 +569,181 @@ def angle_mode_series(ds, param, label, *, engine=None):
     if not np.isfinite(mm).all():
         raise ValueError(f"the field holds NaN or inf (magnitude range [{mm[0]}, {mm[1]}], angle range [{mm[2]}, {mm[3]}])")
     return mode
+
+
+# ---- the rad/long overlay video: visualize_radlong ---------------------------------------------------------------------------
+COLORMAP_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "colormap_luts.json")  # tools/make_colormap_luts.py writes it
+
+
+def committed_colormap_luts():
+    """{name: float64 [256,3]} from colormap_luts.json: text, each float64 written with the shortest decimal string that reads back as the
+    same bits (Python's repr), so the tables are matplotlib's exactly.  (Text rather than an .npz: package data that can be read and
+    diffed; the repository's binary files are the test vectors under tests/golden/ alone.)"""
+    import json
+    with open(COLORMAP_FILE) as f:
+        return {name: np.array(rows, np.float64).reshape(256, 3) for name, rows in json.load(f)["luts"].items()}
+
+
+def colormap_lut(name):
+    """The 256-entry RGB table of matplotlib's colormap `name`, float64 [256,3]: from matplotlib when it is importable (a colormap
+    with N != 256 is refused), else from the committed colormap_luts.json (bwr, BrBG, PiYG, viridis: matplotlib's own tables).  An
+    unknown name raises ValueError."""
+    try:
+        import matplotlib
+        from matplotlib import cm
+    except ImportError:
+        matplotlib = None
+    if matplotlib is None:
+        luts = committed_colormap_luts()
+        if name not in luts:
+            raise ValueError(f"{name!r} is not among the committed colormaps {sorted(luts)} and matplotlib is not importable")
+        return luts[name]
+    try:
+        cmap = matplotlib.colormaps[name] if hasattr(matplotlib, "colormaps") else cm.get_cmap(name)
+    except (KeyError, ValueError) as e:
+        raise ValueError(f"{name!r} is not a matplotlib colormap") from e
+    if cmap.N != 256:
+        raise ValueError(f"colormap {name!r} has {cmap.N} entries; the overlay takes 256-entry colormaps")
+    return np.array(cmap(np.arange(256))[:, :3], np.float64)      # integer input indexes the table itself
+
+
+def _check_lut(lut, name):
+    lut = np.ascontiguousarray(lut, dtype=np.float64)
+    if lut.shape != (256, 3):
+        raise ValueError(f"{name} must be [256,3], got shape {lut.shape}")
+    if not (np.isfinite(lut).all() and (lut >= 0).all()):
+        raise ValueError(f"{name} holds a negative or non-finite entry")
+    return lut
+
+
+def overlay_host(rad, lon, echo, lut_rad, lut_long):
+    """The per-pixel part of visualize_radlong in numpy, as the reference computes it but without its RGBA float64 arrays:
+    (out uint8 [n,H,2W,3], info float64 [3] = (half, echo max, m2)) from the float64 planes rad / lon [n,H,W], the echo [>= n,H,W]
+    (float16 or uint8) and two [256,3] tables.
+      half = max|rad[0]|: the reference makes ONE CenteredNorm, which autoscales on its first call only (frame 0, radial) and then
+             serves every frame of both components; t = (a + half) / (2 half), 0 everywhere when half == 0, not clipped;
+      index = clip(floor(t * 256), 0, 255): matplotlib's lookup, under = entry 0, over = entry 255;
+      overlay3: ((0.5 * (echo / max echo)) + (0.5 * (colour / m2))) * 255, cast to uint8 (truncation); m2 = the largest channel among
+             the colours actually produced; a float16 echo keeps float16 through its quotient and the product with 0.5.
+    ValueError where the reference's cast is undefined: NaN or inf in a plane, a negative or non-finite echo value, an echo maximum
+    of 0, 2 * half overflowing, m2 == 0."""
+    rad, lon = np.asarray(rad, np.float64), np.asarray(lon, np.float64)
+    n, H, W = rad.shape
+    lut_rad, lut_long = _check_lut(lut_rad, "lut_rad"), _check_lut(lut_long, "lut_long")
+    echo = np.asarray(echo)
+    if echo.dtype not in (np.float16, np.uint8):
+        raise ValueError(f"echo must be float16 or uint8, got {echo.dtype}")
+    if echo.ndim != 3 or echo.shape[0] < n or echo.shape[1:] != (H, W):
+        raise ValueError(f"echo must be [>= {n},{H},{W}], got shape {echo.shape}")
+    echo = echo[:n]
+    if not (np.isfinite(rad).all() and np.isfinite(lon).all()):
+        raise ValueError("the rad/long planes hold NaN or inf")
+    if echo.dtype == np.float16 and not (np.isfinite(echo).all() and (echo >= 0).all()):
+        raise ValueError("the echo holds a negative or non-finite value")
+    emax = np.max(echo)
+    if emax == 0:
+        raise ValueError("the echo's maximum is 0")
+    half = np.max(np.abs(rad[0]))
+    with np.errstate(over="ignore"):
+        two_half = half - (-half)                                   # vmax - vmin
+    if not np.isfinite(two_half):
+        raise ValueError(f"the norm's range 2 * {half} overflows")
+
+    def index(a):
+        if half == 0:
+            return np.zeros(a.shape, np.uint8)
+        idx = np.empty(a.shape, np.uint8)
+        with np.errstate(over="ignore"):
+            for i in range(a.shape[0]):                             # frame by frame: the float64 temporaries stay one frame large
+                idx[i] = np.clip(((a[i] + half) / two_half) * 256, 0, 255).astype(np.uint8)
+        return idx
+    ir, il = index(rad), index(lon)
+    used_r = np.bincount(ir.ravel(), minlength=256) > 0
+    used_l = np.bincount(il.ravel(), minlength=256) > 0
+    m2 = max(lut_rad[used_r].max(), lut_long[used_l].max())
+    if m2 == 0:
+        raise ValueError("every colour used is black (the colour maximum is 0)")
+    col_r, col_l = 0.5 * (lut_rad / m2), 0.5 * (lut_long / m2)
+    out = np.empty((n, H, 2 * W, 3), np.uint8)
+    for i in range(n):
+        e = (0.5 * (echo[i] / emax)).astype(np.float64)[..., None]  # float16 / float16 and 0.5 * float16 stay float16; uint8 / uint8 is float64
+        out[i, :, :W] = ((e + col_r[ir[i]]) * 255).astype(np.uint8)
+        out[i, :, W:] = ((e + col_l[il[i]]) * 255).astype(np.uint8)
+    return out, np.array([half, emax, m2], np.float64)
+
+
+def radlong_overlay(ds, param, av_filter_flag=True, av_savgol_window=10, av_savgol_poly=4, colormap_rad="bwr", colormap_long="BrBG", *,
+                    engine=None, centroids=None, return_info=False):
+    """The frames visualize_radlong (analyze_optical_flow.py:496-560) hands to its video writer: uint8 [ds.nframes,H,2W,3], the radial
+    projection of get_masked_arr(param, 'rv') through `colormap_rad` on the left, the longitudinal one through `colormap_long` on the
+    right, each blended half-and-half with the echo image; or None (logged) for an unknown param or a mode without 'RVIO', the
+    reference's own refusals.  The colormaps are names (colormap_lut) or [256,3] tables; the defaults are the reference's, and
+    VisualizationManager.visualize_radlong (visualization.py:241-297) is the same with other names.  `ds` is the reference's
+    OpticalFlowDataset or a FlowStudy with an echo; `centroids` (what av_centroids returned) skips the centroid step.
+    Without `engine`, numpy (overlay_host); with `engine` (a DenseFlow) the projection and the rendering run on the device
+    (tf_radlong_project_param, tf_radlong_overlay) and only the frames come back.  Both give the same bytes.  Both raise ValueError for
+    NaN or inf in the projections, a negative or non-finite echo value, an echo maximum of 0, a norm range that overflows and a colour
+    maximum of 0: the reference casts NaN or out-of-range values to uint8 there, which is undefined and differs between machines.
+    return_info adds (half, echo max, m2) as a second result."""
+    if param not in PARAMS:
+        log.error("%r is not a valid optical flow parameter, choose from %s", param, list(PARAMS))
+        return None
+    if "RVIO" not in ds.mode:
+        log.error("only RVIO modes are supported for radlong visualization, got mode=%s", ds.mode)
+        return None
+    lut_rad = colormap_lut(colormap_rad) if isinstance(colormap_rad, str) else colormap_rad
+    lut_long = colormap_lut(colormap_long) if isinstance(colormap_long, str) else colormap_long
+    lut_rad, lut_long = _check_lut(lut_rad, "colormap_rad"), _check_lut(lut_long, "colormap_long")
+    echo = ds.get_echo()
+    if echo is None:
+        raise ValueError("the study has no echo frames")
+    echo = np.asarray(echo)
+    if echo.dtype not in (np.float16, np.uint8):
+        raise ValueError(f"echo must be float16 (the study file's) or uint8, got {echo.dtype}")
+    n = int(ds.nframes)
+    flow, mask = _study_arrays(ds, "rv")
+    if echo.ndim != 3 or echo.shape[0] < n or echo.shape[1:] != np.shape(flow)[1:3]:
+        raise ValueError(f"echo must be [>= {n},{np.shape(flow)[1]},{np.shape(flow)[2]}], got shape {echo.shape}")
+    if centroids is None:
+        centroids = av_centroids(ds.get_mask("av"), n, filter=av_filter_flag, savgol_window=av_savgol_window, savgol_poly=av_savgol_poly,
+                                 engine=engine)
+    if len(centroids) != n:
+        raise ValueError(f"{len(centroids)} centroids for {n} frames")
+    if engine is None:
+        rad, lon = calculate_comp_magnitude(param_field(flow, mask, param, ds.frame_rate, n), centroids)
+        out, info = overlay_host(rad, lon, echo, lut_rad, lut_long)
+    else:
+        from .exceptions import OpticalFlowCalculationError
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"the device path takes a bool or uint8 mask (the study file's), got {mask.dtype}")
+        engine.radlong_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n, centroids)
+        try:
+            out, info = engine.radlong_overlay(echo, lut_rad, lut_long)
+        except OpticalFlowCalculationError as e:
+            if getattr(e, "code", None) == _lib.TF_ERR_INVALID_ARG:    # the library's refusals of the data are the twin's ValueErrors
+                raise ValueError(str(e)) from e
+            raise
+    return (out, info) if return_info else out
+
+
+def visualize_radlong(ds, param, save_dir, fps=30, av_filter_flag=True, av_savgol_window=10, av_savgol_poly=4, colormap_rad="bwr",
+                      colormap_long="BrBG", *, engine=None, centroids=None, writer_factory=None):
+    """The reference's visualize_radlong(ds, param, save_dir) (analyze_optical_flow.py:496-560): renders radlong_overlay's frames and
+    writes them to <save_dir>/<ds.filename>_<param>_radlong_overlay.mp4, one append_data call per frame, then close.  Returns the
+    path, or None under radlong_overlay's refusals (nothing is written then).  writer_factory(path, fps=) makes the writer; the default
+    is imageio.v2.get_writer, imported when needed.  The encoding itself is the writer's."""
+    frames = radlong_overlay(ds, param, av_filter_flag=av_filter_flag, av_savgol_window=av_savgol_window, av_savgol_poly=av_savgol_poly,
+                             colormap_rad=colormap_rad, colormap_long=colormap_long, engine=engine, centroids=centroids)
+    if frames is None:
+        return None
+    if writer_factory is None:
+        import imageio.v2 as iio
+        writer_factory = iio.get_writer
+    os.makedirs(save_dir, exist_ok=True)
+    save_path = os.path.join(save_dir, f"{ds.filename}_{param}_radlong_overlay.mp4")
+    writer = writer_factory(save_path, fps=fps)
+    for i in range(frames.shape[0]):
+        writer.append_data(frames[i])
+    writer.close()
+    return save_path

@@ -20,6 +20,7 @@
 #include "teeflow_otsu.hip.h"
 #include "teeflow_centroid.hip.h"
 #include "teeflow_polar.hip.h"
+#include "teeflow_overlay.hip.h"
 #include "../../include/teeflow.h"
 #include <rccl/rccl.h>      // types and prototypes only: librccl is loaded with dlopen when a communicator is first asked for
 #include <dlfcn.h>
@@ -101,6 +102,7 @@ struct TfKnobs {
     int coop_test_occ16 = -1, coop_test_occ8 = -1;   // tests: pretend the occupancy query answered this
     int coop_test_mute = 0;      // tests: block 0 of every co-resident launch never raises its flag -> its neighbours give up -> the call is repeated tiled
     int profile = 0;
+    int overlay_chunk_kib = 0;   // tests: tf_radlong_overlay's chunk of frames holds at most this many KiB instead of MASK_CHUNK_BYTES (0: that)
     unsigned sor_coop_arm = 0;   // bumped by tf_set_tuning("sor_coop", non-zero): a lane that sees a new value in a job's knobs re-arms the form
 };
 
@@ -156,12 +158,15 @@ struct tf_handle : TfKnobs {
            PRE_CT_MASK, PRE_CT_PAR, PRE_CT_LR, PRE_CT_AREA, PRE_CT_SUM, PRE_CT_OUT,  // tf_av_centroids
            PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // tf_radlong_project_param (the first two also
            PRE_PO_META, PRE_PO_OUT,                                               //   tf_polar_project_param's uploads)
+           PRE_OV_IDX, PRE_OV_ECHO, PRE_OV_OUT, PRE_OV_META,                      // tf_radlong_overlay
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     // ---- analysis session (row f1) ----
     double* an_rad = nullptr; double* an_lon = nullptr; int anN = 0, anH = 0, anW = 0;
     size_t an_cap = 0;           // doubles an_rad and an_lon each hold (tf_radlong_project_param grows them, never shrinks)
+    bool an_polar = false;       // the resident planes are tf_polar_project_param's magnitude / angle, not rad / long
+    bool an_finite = false;      // ... and hold no NaN or inf (their min / max are finite)
     int lanes = 2;               // an idle call of one sub-batch, >= 32 pairs, is split in this many contiguous units solved side by side on the
                                  // queue lanes: while one runs the thin tail of a stage, the other fills the GPU.  Measured at 128 pairs
                                  // @512^2: 1 lane 2180, 2 lanes 2470, 3 lanes 2415, 4 lanes 2165 pairs/s (DeepFlow 377 vs 309)
@@ -1748,6 +1753,7 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
     else if (n == "coop_backoff") { h->coop_backoff = value < 0 ? 0 : value; }        // tests: next abort sits out 2 x this (0: the default 16)
     else if (n == "df_fuse_ds") h->df_fuse_ds = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (n == "warp_margin") h->warp_margin = value < 0 ? 0 : (value > 40 ? 40 : value);
+    else if (n == "overlay_chunk_kib") h->overlay_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);   // never above the 512 MiB rule
     else return fail(h, TF_ERR_INVALID_ARG, "unknown tuning knob %s", name);
     return TF_OK;
 }
@@ -2250,6 +2256,8 @@ TF_API int tf_radlong_project(tf_handle* h, const float* flow, const double* cen
     for (int j = 0; j < 4; ++j) minmax[j] = f64_unkey(mmh[j]);
     for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
     h->anN = N; h->anH = H; h->anW = W;
+    h->an_polar = false;
+    h->an_finite = std::isfinite(minmax[0]) && std::isfinite(minmax[1]) && std::isfinite(minmax[2]) && std::isfinite(minmax[3]);
     return TF_OK;
 }
 
@@ -2429,6 +2437,8 @@ int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_
     for (int j = 0; j < 4; ++j) minmax[j] = f64_unkey(mmh[j]);
     for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
     h->anN = n_used; h->anH = H; h->anW = W;
+    h->an_polar = false;
+    h->an_finite = std::isfinite(minmax[0]) && std::isfinite(minmax[1]) && std::isfinite(minmax[2]) && std::isfinite(minmax[3]);
     return TF_OK;
 }
 
@@ -2495,6 +2505,82 @@ int polar_project_param(tf_handle* h, const void* flow, int f16, int N, int n_us
     for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
     for (int i = 0; i < n_used; ++i) ang_mode[i] = kh[i] ? (float)kh[i] / 100.f : std::numeric_limits<float>::quiet_NaN();
     h->anN = n_used; h->anH = H; h->anW = W;
+    h->an_polar = true;
+    return TF_OK;
+}
+
+// tf_radlong_overlay: the indices (2 B per pixel of the study, an eighth of the resident planes) are made for all frames at once, since
+// m2 needs every frame's; the echo upload and the output (eb + 6 B per pixel) go through in chunks of as many frames as fit in
+// MASK_CHUNK_BYTES.  A study of one chunk uploads its echo once; a longer one uploads it a second time for the compose pass.
+template <int KIND>
+int radlong_overlay(tf_handle* h, const void* echo_v, const double* lut_rad, const double* lut_long, uint8_t* out, double* info)
+{
+    using namespace ovl;
+    using ET = typename Echo<KIND>::T;
+    const ET* echo = (const ET*)echo_v;
+    const int n = h->anN, H = h->anH, W = h->anW;
+    const size_t HW = (size_t)H * W, tot = (size_t)n * HW, eb = sizeof(ET);
+    const size_t chunk_bytes = h->overlay_chunk_kib > 0 ? (size_t)h->overlay_chunk_kib << 10 : MASK_CHUNK_BYTES;
+    size_t nf = chunk_bytes / (HW * (eb + 6));
+    if (nf > (size_t)n) nf = (size_t)n;
+    if (nf < 1) nf = 1;
+    const size_t out_dwords = (nf * HW * 2 + 3) / 4 * 3;      // 3 dwords per run of 4 slots, whole runs: what k_ov_compose stores
+    HIPC(h, hipSetDevice(h->dev));
+    uint16_t* didx = nullptr; ET* decho = nullptr; unsigned* dout = nullptr; uint8_t* meta = nullptr;
+    // meta: [0, 8) half bits, [8, 16) echo max bits + bad flag, [16, 80) used bitsets [2][8], [128, 128 + 12288) colour terms [2][256][3] f64
+    int rc;
+    if ((rc = pre_grow(h, tf_handle::PRE_OV_IDX, tot * 2, (void**)&didx)) ||
+        (rc = pre_grow(h, tf_handle::PRE_OV_ECHO, nf * HW * eb, (void**)&decho)) ||
+        (rc = pre_grow(h, tf_handle::PRE_OV_OUT, out_dwords * 4, (void**)&dout)) ||
+        (rc = pre_grow(h, tf_handle::PRE_OV_META, 128 + 2 * 256 * 3 * sizeof(double), (void**)&meta))) return rc;
+    u64* dhalf = (u64*)meta;
+    unsigned* demax = (unsigned*)(meta + 8);
+    unsigned* dused = (unsigned*)(meta + 16);
+    double* dcol = (double*)(meta + 128);
+    const hipStream_t s = h->stream;
+    const dim3 blk(256);
+    auto grid = [](size_t work, size_t cap) { const size_t g = (work + 255) / 256; return dim3((unsigned)(g < cap ? g : cap)); };
+    HIPC(h, hipMemsetAsync(meta, 0, 128, s));
+    hipLaunchKernelGGL(k_ov_half, grid(HW, 256), blk, 0, s, h->an_rad, HW, dhalf);
+    hipLaunchKernelGGL(k_ov_index, grid(tot, 2048), blk, 0, s, h->an_rad, h->an_lon, tot, dhalf, didx, dused);
+    HIPC(h, hipGetLastError());
+    for (int f0 = 0; f0 < n; f0 += (int)nf) {
+        const size_t c = (size_t)(n - f0 < (int)nf ? n - f0 : (int)nf) * HW;
+        HIPC(h, hipMemcpyAsync(decho, echo + (size_t)f0 * HW, c * eb, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_ov_echo<KIND>, grid(c, 1024), blk, 0, s, decho, c, demax);
+        HIPC(h, hipGetLastError());
+    }
+    struct { u64 half; unsigned emax, bad; unsigned used[16]; } m;
+    static_assert(sizeof m == 80, "layout of the overlay's meta words");
+    HIPC(h, hipMemcpyAsync(&m, meta, sizeof m, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    union { u64 u; double d; } hb; hb.u = m.half;
+    union { unsigned u; float f; } em; em.u = m.emax;
+    const double half = hb.d, emax = (double)em.f;
+    if (m.bad) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the echo holds a negative or non-finite value");
+    if (emax == 0.0) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the echo's maximum is 0");
+    if (!std::isfinite(half - (-half))) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the norm's range 2 * %g overflows", half);
+    double m2 = 0.0;
+    for (int c = 0; c < 2; ++c)
+        for (int j = 0; j < 256; ++j)
+            if ((m.used[8 * c + (j >> 5)] >> (j & 31)) & 1u)
+                for (int ch = 0; ch < 3; ++ch) { const double v = (c ? lut_long : lut_rad)[3 * j + ch]; m2 = v > m2 ? v : m2; }
+    if (m2 == 0.0) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: every colour used is black (the colour maximum is 0)");
+    std::vector<double> col(2 * 256 * 3);
+    for (int c = 0; c < 2; ++c)
+        for (int j = 0; j < 256 * 3; ++j) col[(size_t)c * 768 + j] = 0.5 * ((c ? lut_long : lut_rad)[j] / m2);
+    HIPC(h, hipMemcpyAsync(dcol, col.data(), col.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int f0 = 0; f0 < n; f0 += (int)nf) {
+        const int nc = n - f0 < (int)nf ? n - f0 : (int)nf;
+        const size_t c = (size_t)nc * HW, slots = 2 * c;                                // nc <= nf: the runs of `slots` fit out_dwords
+        if ((size_t)n > nf) HIPC(h, hipMemcpyAsync(decho, echo + (size_t)f0 * HW, c * eb, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_ov_compose<KIND>, dim3((unsigned)((slots + 1023) / 1024)), blk, 0, s, didx + (size_t)f0 * HW, decho, emax, dcol,
+                           (size_t)nc * H, W, dout);
+        HIPC(h, hipGetLastError());
+        HIPC(h, hipMemcpyAsync(out + (size_t)f0 * HW * 6, dout, c * 6, hipMemcpyDeviceToHost, s));
+    }
+    HIPC(h, hipStreamSynchronize(s));
+    info[0] = half; info[1] = emax; info[2] = m2;
     return TF_OK;
 }
 
@@ -2541,6 +2627,31 @@ TF_API int tf_polar_project_param(tf_handle* h, const void* flow, int flow_is_f1
     if (n_used > 65535 || (size_t)H * W > 0xFFFFFFFFu) return TF_ERR_UNSUPPORTED;       // frames are grid.y; a frame's counts are 32-bit
     return finish_host_call(h, polar_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
                                                    mag_out, ang_out, minmax, nonzero, ang_mode));
+}
+
+static_assert(TF_ECHO_F16 == ovl::ECHO_F16 && TF_ECHO_U8 == ovl::ECHO_U8, "echo kinds of the header and the kernel differ");
+
+TF_API int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const double* lut_rad, const double* lut_long, uint8_t* out,
+                              double* info)
+{
+    if (!h || !echo || !lut_rad || !lut_long || !out || !info || (echo_kind != TF_ECHO_F16 && echo_kind != TF_ECHO_U8)) return TF_ERR_INVALID_ARG;
+    for (int j = 0; j < 256 * 3; ++j)
+        if (!(lut_rad[j] >= 0.0 && std::isfinite(lut_rad[j]) && lut_long[j] >= 0.0 && std::isfinite(lut_long[j])))
+            return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: a colormap entry is negative or not finite");
+    if (h->anN < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay needs a preceding tf_radlong_project or tf_radlong_project_param");
+    if (h->an_polar) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the handle's last projection was tf_polar_project_param, not a rad/long one");
+    if (!h->an_finite) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the rad/long planes hold NaN or inf");
+    if ((size_t)h->anH * h->anW > 0x7fffffffu / 8) return fail(h, TF_ERR_UNSUPPORTED, "tf_radlong_overlay: at most 2^28 - 1 pixels per frame");
+    return finish_host_call(h, echo_kind == TF_ECHO_F16 ? radlong_overlay<ovl::ECHO_F16>(h, echo, lut_rad, lut_long, out, info)
+                                                        : radlong_overlay<ovl::ECHO_U8>(h, echo, lut_rad, lut_long, out, info));
+}
+
+TF_API int tf_radlong_shape(tf_handle* h, int* shape)
+{
+    if (!h || !shape) return TF_ERR_INVALID_ARG;
+    const bool have = h->anN >= 1 && !h->an_polar;
+    shape[0] = have ? h->anN : 0; shape[1] = have ? h->anH : 0; shape[2] = have ? h->anW : 0;
+    return TF_OK;
 }
 
 // pinned host memory for results: a destination allocated here makes the host-pointer entry points copy out at PCIe

@@ -415,6 +415,38 @@ class DenseFlow:
                    self._h, "tf_polar_project_param")
         return mm, nz, mode, mag, ang
 
+    def radlong_overlay(self, echo, lut_rad, lut_long):
+        """tf_radlong_overlay: the radial / longitudinal overlay frames of visualize_radlong (analyze_optical_flow.py:488-560) from the
+        planes the last radlong_project_param (or tf_radlong_project) call left on the device; n, H and W are that call's.  echo float16
+        (the study file's) or uint8 [>= n,H,W]; lut_rad / lut_long float64 [256,3] (analysis.colormap_lut).  Returns (out uint8
+        [n,H,2W,3] in pinned host memory, info float64 [3] = (half, echo max, m2)).  May be called while submitted studies are in
+        flight on this engine."""
+        echo = np.asarray(echo)
+        if echo.dtype not in (np.float16, np.uint8):
+            raise OpticalFlowCalculationError(f"echo must be float16 or uint8, got {echo.dtype}")
+        if echo.ndim != 3 or min(echo.shape) < 1:
+            raise OpticalFlowCalculationError(f"echo must be [N,H,W] with no empty side, got shape {echo.shape}")
+        luts = []
+        for name, lut in (("lut_rad", lut_rad), ("lut_long", lut_long)):
+            lut = np.ascontiguousarray(lut, dtype=np.float64)
+            if lut.shape != (256, 3):
+                raise OpticalFlowCalculationError(f"{name} must be [256,3], got shape {lut.shape}")
+            luts.append(lut)
+        # the library knows the planes' shape; the echo's must be checked against it before the library reads n * H * W values of it
+        shape = (C.c_int * 3)()
+        _lib.check(self._L.tf_radlong_shape(self._h, C.byref(shape)), self._h, "tf_radlong_shape")
+        n, H, W = shape
+        if n >= 1 and (echo.shape[0] < n or echo.shape[1:] != (H, W)):
+            raise OpticalFlowCalculationError(f"echo must be [>= {n},{H},{W}] (the projection's frames), got shape {echo.shape}")
+        echo = np.ascontiguousarray(echo[:max(n, 1)])
+        # (without rad/long planes the library refuses, and says why, before it reads the echo or writes out)
+        out = self._pool.empty((n, H, 2 * W, 3), np.uint8) if n >= 1 else np.empty(1, np.uint8)
+        info = np.zeros(3, np.float64)
+        _lib.check(self._L.tf_radlong_overlay(self._h, echo.ctypes.data, _lib.ECHO_F16 if echo.dtype == np.float16 else _lib.ECHO_U8,
+                                              luts[0].ctypes.data, luts[1].ctypes.data, out.ctypes.data, info.ctypes.data),
+                   self._h, "tf_radlong_overlay")
+        return out, info
+
     def wase_compensate(self, flows, bkgd_mask, scale=1.0):
         """Reference :647-652, 659 for every flow of a study at once, on the device: returns (flows - background[p]) * scale
         and the float32 backgrounds.  flows float32 [P,H,W,2]; bkgd_mask bool [N,H,W,2] (mask_dict['bkgd'])."""

@@ -107,29 +107,22 @@ def load():
     L.tf_calc_pair_f32.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(TfStats)]
     L.tf_calc_pairs_device.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
     L.tf_calc_seq_device.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_wait"):                # (an older A/B build may lack the round-5 entry points)
-        L.tf_submit_pairs_device.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
-        L.tf_submit_seq_device.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
-        L.tf_submit_pairs.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.POINTER(i32)]
-        L.tf_submit_seq.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
-        L.tf_submit_seq_rgb.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
-        L.tf_wait.argtypes = [vp, i32, C.POINTER(TfStats)]
+    L.tf_submit_pairs_device.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
+    L.tf_submit_seq_device.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
+    L.tf_submit_pairs.argtypes = [vp, vp, vp, i32, i32, i32, vp, C.POINTER(i32)]
+    L.tf_submit_seq.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
+    L.tf_submit_seq_rgb.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(i32)]
+    L.tf_wait.argtypes = [vp, i32, C.POINTER(TfStats)]
     L.tf_condition_frames.argtypes = [vp, vp, i32, i32, i32, vp]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_saliency_frames"):     # (an older A/B build may lack the round-4 entry points)
-        L.tf_saliency_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-        L.tf_calc_seq_saliency.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_saliency_frames_f32"):
-        L.tf_saliency_frames_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-        L.tf_calc_seq_saliency_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_clean_masks"):         # (an older A/B build may lack it)
-        L.tf_clean_masks.argtypes = [vp, vp, i32, i32, i32, vp, i32, C.c_longlong, vp]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_otsu_masks"):          # (an older A/B build may lack it)
-        L.tf_otsu_masks.argtypes = [vp, vp, i32, i32, i32, C.c_longlong, vp, vp]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_av_centroids"):        # (an older A/B build may lack them)
-        L.tf_av_centroids.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-        L.tf_radlong_project_param.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
-    if "TEEFLOW_LIB" not in os.environ or hasattr(L, "tf_polar_project_param"):  # (an older A/B build may lack it)
-        L.tf_polar_project_param.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.tf_saliency_frames.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    L.tf_calc_seq_saliency.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
+    L.tf_saliency_frames_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    L.tf_calc_seq_saliency_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
+    L.tf_clean_masks.argtypes = [vp, vp, i32, i32, i32, vp, i32, C.c_longlong, vp]
+    L.tf_otsu_masks.argtypes = [vp, vp, i32, i32, i32, C.c_longlong, vp, vp]
+    L.tf_av_centroids.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+    L.tf_radlong_project_param.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.tf_polar_project_param.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.tf_calc_seq_rgb.argtypes = [vp, vp, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
     L.tf_radlong_project.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.tf_radlong_hist.argtypes = [vp, i32, vp, i32, vp]

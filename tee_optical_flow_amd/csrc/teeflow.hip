@@ -150,32 +150,30 @@ struct tf_handle : TfKnobs {
     float* dtmp = nullptr;                                          // unblurred level-0 frames
     float* dplanes = nullptr;                                       // 21 state planes x cap pairs
     DfBufs df = {};
-    // ---- frame preprocessing (conditioning, saliency): grow-only work buffers, freed with the handle ----
+    // ---- study tail (conditioning, saliency, masks, centroids, projections, statistics, overlay, WASE): every piece of its device
+    // scratch is one of these grow-only slots, freed with the handle (teeflow_tail.hip.h) ----
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
            PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks (PAR, AUX, LR also tf_otsu_masks)
            PRE_OT_RGB, PRE_OT_CLEAN, PRE_OT_OUT, PRE_OT_META,                        // tf_otsu_masks
            PRE_CT_MASK, PRE_CT_PAR, PRE_CT_LR, PRE_CT_AREA, PRE_CT_SUM, PRE_CT_OUT,  // tf_av_centroids
-           PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // tf_radlong_project_param (the first two also
-           PRE_PO_META, PRE_PO_OUT,                                               //   tf_polar_project_param's uploads)
+           PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // the projections' uploads (also tf_wase_compensate's) and
+           PRE_PO_META, PRE_PO_OUT,                                               //   meta words: rad/long's, polar's
+           PRE_AN_HIST, PRE_AN_SEL,                                               // tf_radlong_hist, tf_radlong_select
            PRE_OV_IDX, PRE_OV_ECHO, PRE_OV_OUT, PRE_OV_META,                      // tf_radlong_overlay
-           PRE_COUNT };
+           PRE_WA_VALS, PRE_WA_CNT, PRE_WA_OFF, PRE_WA_SUM, PRE_WA_BG,            // WASE: compacted products, block counts / offsets, piece
+           PRE_COUNT };                                                           //   sums, per-flow backgrounds
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     // ---- analysis session (row f1) ----
     double* an_rad = nullptr; double* an_lon = nullptr; int anN = 0, anH = 0, anW = 0;
-    size_t an_cap = 0;           // doubles an_rad and an_lon each hold (tf_radlong_project_param grows them, never shrinks)
+    size_t an_cap = 0;           // doubles an_rad and an_lon each hold (grow_an_planes grows them, never shrinks)
     bool an_polar = false;       // the resident planes are tf_polar_project_param's magnitude / angle, not rad / long
     bool an_finite = false;      // ... and hold no NaN or inf (their min / max are finite)
     int lanes = 2;               // an idle call of one sub-batch, >= 32 pairs, is split in this many contiguous units solved side by side on the
                                  // queue lanes: while one runs the thin tail of a stage, the other fills the GPU.  Measured at 128 pairs
                                  // @512^2: 1 lane 2180, 2 lanes 2470, 3 lanes 2415, 4 lanes 2165 pairs/s (DeepFlow 377 vs 309)
     int num_cus = 256;
-    // WASE scratch (grown on demand): compacted products, block counts / offsets, piece sums, per-flow backgrounds
-    float* wa = nullptr; size_t wa_cap = 0;
-    unsigned* wcnt = nullptr; u64* woff = nullptr; size_t wcnt_cap = 0;
-    float* wsum = nullptr; size_t wsum_cap = 0;
-    float* wbg = nullptr; size_t wbg_cap = 0;
     std::map<size_t, int> slots_cache;      // resident k_iter2_rows blocks on the device, by (LDS bytes, waves per block)
     int coop_share = 0;          // CUs (= resident 1024-thread blocks) this handle may fill with such a launch; set per call (start_call, lane_worker)
     bool coop_disabled = false;  // a launch of this handle gave up waiting (foreign work on the GPU): tiled form until the back-off has run out
@@ -1655,11 +1653,6 @@ TF_API void tf_destroy(tf_handle* h)
     (void)tf_comm_destroy(h);
     for (auto& e : h->cev) if (e) (void)hipEventDestroy(e);
     for (auto& b : h->pre) if (b.p) (void)hipFree(b.p);
-    if (h->wa) (void)hipFree(h->wa);
-    if (h->wcnt) (void)hipFree(h->wcnt);
-    if (h->woff) (void)hipFree(h->woff);
-    if (h->wsum) (void)hipFree(h->wsum);
-    if (h->wbg) (void)hipFree(h->wbg);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
@@ -1897,862 +1890,8 @@ TF_API int tf_wait(tf_handle* h, int ticket, tf_stats* st)
     return rc;
 }
 
-namespace {
-int pre_grow(tf_handle* h, int which, size_t bytes, void** out)
-{
-    tf_handle::GrowBuf& b = h->pre[which];
-    if (b.cap < bytes) {
-        if (b.p) { HIPC(h, hipStreamSynchronize(h->stream)); (void)hipFree(b.p); }
-        b.p = nullptr; b.cap = 0;
-        HIPC(h, hipMalloc(&b.p, bytes));
-        b.cap = bytes;
-    }
-    *out = b.p;
-    return TF_OK;
-}
-
-// rgb (host) -> conditioned gray frames in the handle's preprocessing buffer (valid until the handle's next preprocessing call)
-// (`own`: into that caller-owned buffer instead -- a submitted job's frames must outlive the handle's next preprocessing call)
-int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t** dgray_out, uint8_t* own = nullptr)
-{
-    const size_t npx = (size_t)H * W;
-    uint8_t* drgb = nullptr; uint8_t* dgray = own; u64* mm = nullptr;
-    HIPC(h, hipSetDevice(h->dev));
-    int rc;
-    if ((rc = pre_grow(h, tf_handle::PRE_SRC, (size_t)N * npx * 3, (void**)&drgb)) || (!own && (rc = pre_grow(h, tf_handle::PRE_OUT, (size_t)N * npx, (void**)&dgray))) ||
-        (rc = pre_grow(h, tf_handle::PRE_MX, (size_t)N * 2 * sizeof(u64), (void**)&mm))) return rc;
-    std::vector<u64> init((size_t)N * 2);
-    for (int f = 0; f < N; ++f) { init[2 * f] = ~0ull; init[2 * f + 1] = 0ull; }
-    HIPC(h, hipMemcpyAsync(drgb, rgb, (size_t)N * npx * 3, hipMemcpyHostToDevice, h->stream));
-    HIPC(h, hipMemcpyAsync(mm, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-    const int gx = (int)((npx + 255) / 256);
-    hipLaunchKernelGGL(k_cond_minmax, dim3(gx < 512 ? gx : 512, N), dim3(256), 0, h->stream, drgb, npx, mm);
-    hipLaunchKernelGGL(k_cond_norm, dim3(gx, N), dim3(256), 0, h->stream, drgb, npx, mm, dgray);
-    HIPC(h, hipStreamSynchronize(h->stream));            // `init` leaves scope; the solve may run on other streams (lanes)
-    *dgray_out = dgray;
-    return TF_OK;
-}
-}  // namespace
-
-TF_API int tf_condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t* gray_out)
-{
-    if (!h || !rgb || !gray_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    uint8_t* dgray = nullptr;
-    int rc = condition_to_device(h, rgb, N, H, W, &dgray);
-    if (rc) return rc;
-    HIPC(h, hipMemcpy(gray_out, dgray, (size_t)N * H * W, hipMemcpyDeviceToHost));
-    return TF_OK;
-}
-
-TF_API int tf_calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
-{
-    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    uint8_t* dgray = nullptr;
-    rc = condition_to_device(h, rgb, N, H, W, &dgray);
-    if (rc) return rc;
-    // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
-    c.in0 = dgray; c.where = W_IN_DEV;
-    return calc_entry(h, c, st);
-}
-// tf_calc_seq_rgb without waiting: the frames are conditioned now (on the handle's stream, into a buffer the job owns), the solve is queued
-TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
-{
-    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    if (!ticket) return TF_ERR_INVALID_ARG;
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t* own = nullptr;
-    HIPC(h, hipMalloc(&own, (size_t)N * H * W));
-    uint8_t* dgray = nullptr;
-    rc = condition_to_device(h, rgb, N, H, W, &dgray, own);
-    if (rc) { (void)hipFree(own); return rc; }
-    c.in0 = own; c.where = W_IN_DEV;
-    return submit_entry(h, c, ticket, own);
-}
-
-namespace {
-// frames (host, uint8 [N][H][W][channels]) -> fine-grained saliency maps [N][H][W] in the handle's preprocessing buffer: uint8, or
-// (f32) float = map * (1/255), what computeSaliency() returns in opencv-contrib 4.x.  Frames go through in chunks so that the work
-// buffers (17 B per pixel) stay below ~2.3 GB whatever the study's length; the buffers are the handle's and only ever grow.
-int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, void** dout)
-{
-    const size_t npx = (size_t)H * W, ipx = (size_t)(H + 1) * (W + 1);
-    if (H > 65535 || N > 65535) return fail(h, TF_ERR_UNSUPPORTED, "saliency: at most 65535 rows and 65535 frames per call");
-    size_t F = ((size_t)1 << 27) / npx;
-    F = F < 1 ? 1 : (F > (size_t)N ? (size_t)N : F);
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t *src, *g0, *g1, *ion, *ioff, *out; int* P; float* I; uint16_t *mon, *moff; int* mx;
-    int rc;
-    if ((rc = pre_grow(h, tf_handle::PRE_SRC, F * npx * channels, (void**)&src)) || (rc = pre_grow(h, tf_handle::PRE_G0, F * npx, (void**)&g0)) ||
-        (rc = pre_grow(h, tf_handle::PRE_G1, F * npx, (void**)&g1)) || (rc = pre_grow(h, tf_handle::PRE_ION, F * npx, (void**)&ion)) ||
-        (rc = pre_grow(h, tf_handle::PRE_IOFF, F * npx, (void**)&ioff)) || (rc = pre_grow(h, tf_handle::PRE_P, F * npx * sizeof(int), (void**)&P)) ||
-        (rc = pre_grow(h, tf_handle::PRE_I, F * ipx * sizeof(float), (void**)&I)) || (rc = pre_grow(h, tf_handle::PRE_MON, F * npx * sizeof(uint16_t), (void**)&mon)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MOFF, F * npx * sizeof(uint16_t), (void**)&moff)) || (rc = pre_grow(h, tf_handle::PRE_MX, F * SAL_MX * sizeof(int), (void**)&mx)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OUT, (size_t)N * npx * (f32 ? sizeof(float) : 1), (void**)&out))) return rc;
-    h->pre_kernel_ms = 0;
-    for (size_t f0 = 0; f0 < (size_t)N; f0 += F) {
-        const int nf = (int)((size_t)N - f0 < F ? (size_t)N - f0 : F);
-        const size_t n = (size_t)nf * npx;
-        const dim3 g2((W + 255) / 256, H, nf), blk(256);
-        HIPC(h, hipMemcpyAsync(src, frames + f0 * npx * channels, n * channels, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipEventRecord(h->ev[0], h->stream));       // the eight kernels of the chunk, without the upload
-        HIPC(h, hipMemsetAsync(mx, 0, (size_t)nf * SAL_MX * sizeof(int), h->stream));
-        hipLaunchKernelGGL(sal::k_sal_gray, dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, src, channels, n, g0);
-        hipLaunchKernelGGL(sal::k_sal_blur3, g2, blk, 0, h->stream, g0, g1, H, W);
-        hipLaunchKernelGGL(sal::k_sal_blur3, g2, blk, 0, h->stream, g1, g0, H, W);
-        hipLaunchKernelGGL(sal::k_sal_rowprefix, dim3(H, nf), dim3(64), 0, h->stream, g0, H, W, P);
-        hipLaunchKernelGGL(sal::k_sal_integral, dim3((W + 1 + 255) / 256, nf), blk, 0, h->stream, P, H, W, I);
-        const dim3 g8((W + 255) / 256, (H + SAL_ROWS - 1) / SAL_ROWS, nf);
-        hipLaunchKernelGGL(sal::k_sal_scales, g8, blk, 0, h->stream, g0, I, H, W, mon, moff, mx);
-        hipLaunchKernelGGL(sal::k_sal_mix_scales, g8, blk, 0, h->stream, mon, moff, H, W, ion, ioff, mx);
-        hipLaunchKernelGGL(sal::k_sal_mix_onoff, g2, blk, 0, h->stream, ion, ioff, H, W, mx, f32 ? nullptr : out + f0 * npx,
-                           f32 ? (float*)out + f0 * npx : nullptr);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipEventRecord(h->ev[1], h->stream));
-        HIPC(h, hipStreamSynchronize(h->stream));        // (one chunk holds 2^27 pixels: a study is one chunk; the event pair is read per chunk)
-        float t = 0;
-        HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        h->pre_kernel_ms += t;
-    }
-    *dout = out;
-    return TF_OK;
-}
-
-int saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, void* out)
-{
-    if (!h || !frames || !out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
-    void* d = nullptr;
-    int rc = saliency_to_device(h, frames, N, H, W, channels, f32, &d);
-    if (rc) return rc;
-    HIPC(h, hipMemcpy(out, d, (size_t)N * H * W * (f32 ? sizeof(float) : 1), hipMemcpyDeviceToHost));
-    return TF_OK;
-}
-
-int calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, float scale, float* flow_out, tf_stats* st)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
-    // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are)
-    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, f32};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    void* dsal = nullptr;
-    rc = saliency_to_device(h, frames, N, H, W, channels, f32, &dsal);
-    if (rc) return rc;
-    c.in0 = (const uint8_t*)dsal; c.where = W_IN_DEV;
-    return calc_entry(h, c, st);
-}
-}  // namespace
-
-TF_API int tf_saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, uint8_t* saliency_out)
-{
-    return saliency_frames(h, frames, N, H, W, channels, false, saliency_out);
-}
-TF_API int tf_saliency_frames_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float* saliency_out)
-{
-    return saliency_frames(h, frames, N, H, W, channels, true, saliency_out);
-}
-TF_API int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
-{
-    return calc_seq_saliency(h, frames, N, H, W, channels, false, scale, flow_out, st);
-}
-TF_API int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
-{
-    return calc_seq_saliency(h, frames, N, H, W, channels, true, scale, flow_out, st);
-}
-
-namespace {
-// tf_clean_masks: frames go through in chunks so that the per-chunk scratch (10 B per pixel and label, 2 B per pixel and label + 1 of
-// output) stays within MASK_CHUNK_BYTES whatever the study's length; the class map itself (1 B per pixel) is uploaded whole.
-constexpr size_t MASK_CHUNK_BYTES = (size_t)512 << 20;
-
-int clean_masks(tf_handle* h, const uint8_t* cmap, int N, int H, int W, const uint8_t* ids, int L, long long min_size, uint8_t* out)
-{
-    using namespace msk;
-    const size_t HW = (size_t)H * W;
-    if (HW > 0x7fffffffu) return fail(h, TF_ERR_UNSUPPORTED, "tf_clean_masks: at most 2^31 - 1 pixels per frame");
-    if (L > 65535) return fail(h, TF_ERR_UNSUPPORTED, "tf_clean_masks: at most 65535 labels");
-    const size_t per_frame = HW * (10 * (size_t)L + 2 * ((size_t)L + 1));
-    size_t nf = MASK_CHUNK_BYTES / per_frame;
-    if (nf > (size_t)N) nf = (size_t)N;
-    if (nf > (size_t)(65535 / L)) nf = (size_t)(65535 / L);     // planes of a chunk are grid.y
-    if (nf < 1) nf = 1;
-    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t* dcls = nullptr; uint32_t* dpar = nullptr; uint32_t* daux = nullptr; uint16_t* dlr = nullptr; uint16_t* dout = nullptr;
-    uint8_t* meta = nullptr;                                   // [0, 4): error word, [64, 64 + L): class ids
-    int rc;
-    if ((rc = pre_grow(h, tf_handle::PRE_MK_CLS, (size_t)N * HW, (void**)&dcls)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_PAR, (size_t)L * nf * HW * 4, (void**)&dpar)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_AUX, (size_t)L * nf * HW * 4, (void**)&daux)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_LR, (size_t)L * nf * HW * 2, (void**)&dlr)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_OUT, (size_t)(L + 1) * nf * HW * 2, (void**)&dout)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_META, 64 + (size_t)L, (void**)&meta))) return rc;
-    unsigned* derr = (unsigned*)meta;
-    const hipStream_t s = h->stream;
-    HIPC(h, hipMemcpyAsync(dcls, cmap, (size_t)N * HW, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(meta + 64, ids, (size_t)L, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
-    for (int f0 = 0; f0 < N; f0 += (int)nf) {
-        const int n = N - f0 < (int)nf ? N - f0 : (int)nf;
-        const size_t planes = (size_t)L * n;
-        const dim3 g(tiles, (unsigned)planes), blk(256);
-        // fill holes: components of m's background; those with a pixel on the border keep their flag in aux
-        HIPC(h, hipMemsetAsync(daux, 0, planes * HW * 4, s));
-        const ClassWindowBackground set{dcls, meta + 64, N, f0, n, HW};
-        hipLaunchKernelGGL((k_mask_local<0, ClassWindowBackground>), g, blk, 0, s, set, dpar, daux, dlr, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_mask_flatten<0>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
-        // small objects: components of the filled mask, their sizes counted into aux
-        hipLaunchKernelGGL((k_mask_local<1, NoSet>), g, blk, 0, s, NoSet{}, dpar, daux, dlr, H, W, tiles_x, derr);
-        HIPC(h, hipMemsetAsync(daux, 0, planes * HW * 4, s));
-        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_mask_flatten<1>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
-        hipLaunchKernelGGL(k_mask_store, dim3((unsigned)((HW + 255) / 256), (unsigned)n), blk, 0, s, dpar, daux, L, n, HW, min_size, dout);
-        HIPC(h, hipGetLastError());
-        for (int l = 0; l <= L; ++l)                           // label l's frames of this chunk are contiguous in masks_out
-            HIPC(h, hipMemcpyAsync(out + ((size_t)l * N + f0) * HW * 2, dout + (size_t)l * n * HW, (size_t)n * HW * 2, hipMemcpyDeviceToHost, s));
-        unsigned e = 0;
-        HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
-        HIPC(h, hipStreamSynchronize(s));
-        if (e) return fail(h, TF_ERR_HIP, "tf_clean_masks: a union-find loop ran out of its bound (code %u)", e);
-    }
-    return TF_OK;
-}
-}  // namespace
-
-TF_API int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, int W, const uint8_t* class_ids, int n_labels, long long min_size,
-                          uint8_t* masks_out)
-{
-    if (!h || !class_map || !class_ids || !masks_out || N < 1 || H < 1 || W < 1 || n_labels < 1) return TF_ERR_INVALID_ARG;
-    const int rc = clean_masks(h, class_map, N, H, W, class_ids, n_labels, min_size, masks_out);
-    if (rc != TF_OK) {                                         // nothing of the call may still write masks_out when it returns
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-
-namespace {
-// tf_otsu_masks: the frames, one byte per pixel of the cleaned planes and the output stay on the device for the whole study (6 B per
-// pixel and frame); the labelling scratch (10 B per pixel and frame: parents, flags / sizes, tile-local roots) is tf_clean_masks' own,
-// in chunks of as many frames as fit in MASK_CHUNK_BYTES.  The temporal window runs over all cleaned planes after the last chunk.
-int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* out, double* thr_out)
-{
-    using namespace msk;
-    const size_t HW = (size_t)H * W;
-    size_t nf = MASK_CHUNK_BYTES / (HW * 10);
-    if (nf > (size_t)N) nf = (size_t)N;
-    if (nf < 1) nf = 1;
-    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t* drgb = nullptr; uint8_t* dclean = nullptr; uint16_t* dout = nullptr; uint8_t* meta = nullptr;
-    uint32_t* dpar = nullptr; uint32_t* daux = nullptr; uint16_t* dlr = nullptr;
-    // meta: [0, 64) error word; then min / max [N][2] u64, thresholds [N] f64, histograms [N][256] u32
-    const size_t off_mm = 64, off_thr = off_mm + (size_t)N * 16, off_hist = off_thr + (size_t)N * 8, meta_bytes = off_hist + (size_t)N * otsu::NBINS * 4;
-    int rc;
-    if ((rc = pre_grow(h, tf_handle::PRE_OT_RGB, (size_t)N * HW * 3, (void**)&drgb)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OT_CLEAN, (size_t)N * HW, (void**)&dclean)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OT_OUT, (size_t)N * HW * 2, (void**)&dout)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OT_META, meta_bytes, (void**)&meta)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_PAR, nf * HW * 4, (void**)&dpar)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_AUX, nf * HW * 4, (void**)&daux)) ||
-        (rc = pre_grow(h, tf_handle::PRE_MK_LR, nf * HW * 2, (void**)&dlr))) return rc;
-    unsigned* derr = (unsigned*)meta;
-    u64* mm = (u64*)(meta + off_mm);
-    double* dthr = (double*)(meta + off_thr);
-    uint32_t* dhist = (uint32_t*)(meta + off_hist);
-    const hipStream_t s = h->stream;
-    std::vector<u64> init((size_t)N * 2);
-    for (int f = 0; f < N; ++f) { init[2 * f] = ~0ull; init[2 * f + 1] = 0ull; }
-    HIPC(h, hipMemcpyAsync(drgb, rgb, (size_t)N * HW * 3, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemsetAsync(meta, 0, meta_bytes, s));
-    HIPC(h, hipMemcpyAsync(mm, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, s));
-    const dim3 blk(256);
-    const unsigned gx = (unsigned)((HW + 255) / 256), gr = gx < 512 ? gx : 512;
-    hipLaunchKernelGGL(k_cond_minmax, dim3(gr, N), blk, 0, s, drgb, HW, mm);
-    hipLaunchKernelGGL(otsu::k_otsu_hist, dim3(gr, N), blk, 0, s, drgb, HW, mm, dhist);
-    hipLaunchKernelGGL(otsu::k_otsu_thr, dim3(N), blk, 0, s, mm, dhist, dthr);
-    for (int f0 = 0; f0 < N; f0 += (int)nf) {
-        const int n = N - f0 < (int)nf ? N - f0 : (int)nf;
-        const dim3 g(tiles, (unsigned)n);
-        const otsu::LumaNotAbove set{drgb, dthr, f0, HW};
-        // fill holes, then small objects: the passes of tf_clean_masks, one plane per frame
-        HIPC(h, hipMemsetAsync(daux, 0, (size_t)n * HW * 4, s));
-        hipLaunchKernelGGL((k_mask_local<0, otsu::LumaNotAbove>), g, blk, 0, s, set, dpar, daux, dlr, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_mask_flatten<0>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
-        hipLaunchKernelGGL((k_mask_local<1, NoSet>), g, blk, 0, s, NoSet{}, dpar, daux, dlr, H, W, tiles_x, derr);
-        HIPC(h, hipMemsetAsync(daux, 0, (size_t)n * HW * 4, s));
-        hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_mask_flatten<1>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
-        hipLaunchKernelGGL(otsu::k_otsu_keep, dim3(gx, (unsigned)n), blk, 0, s, dpar, daux, HW, min_size, dclean + (size_t)f0 * HW);
-        HIPC(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(otsu::k_otsu_window, dim3(gx, N), blk, 0, s, dclean, N, HW, dout);
-    HIPC(h, hipGetLastError());
-    unsigned e = 0;
-    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(out, dout, (size_t)N * HW * 2, hipMemcpyDeviceToHost, s));
-    if (thr_out) HIPC(h, hipMemcpyAsync(thr_out, dthr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    if (e) return fail(h, TF_ERR_HIP, "tf_otsu_masks: a union-find loop ran out of its bound (code %u)", e);
-    return TF_OK;
-}
-}  // namespace
-
-TF_API int tf_otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* masks_out, double* thresholds_out)
-{
-    if (!h || !rgb || !masks_out || N < 2 || H < 2 || W < 2) return TF_ERR_INVALID_ARG;
-    if ((size_t)H * W > 0x7fffffffu || N > 65535) return TF_ERR_UNSUPPORTED;   // (frames are a grid dimension)
-    const int rc = otsu_masks(h, rgb, N, H, W, min_size, masks_out, thresholds_out);
-    if (rc != TF_OK) {                                         // nothing of the call may still write the outputs when it returns
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-
-TF_API int tf_radlong_project(tf_handle* h, const float* flow, const double* centroids, int N, int H, int W,
-                              double* rad_out, double* long_out, double* minmax, long long* nonzero)
-{
-    if (!h || !flow || !centroids || !minmax || !nonzero || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    HIPC(h, hipSetDevice(h->dev));
-    const size_t npx = (size_t)H * W, tot = (size_t)N * npx;
-    if (h->an_rad) { (void)hipFree(h->an_rad); h->an_rad = nullptr; }
-    if (h->an_lon) { (void)hipFree(h->an_lon); h->an_lon = nullptr; }
-    h->anN = 0;
-    h->an_cap = 0;
-    HIPC(h, hipMalloc(&h->an_rad, tot * sizeof(double)));
-    HIPC(h, hipMalloc(&h->an_lon, tot * sizeof(double)));
-    h->an_cap = tot;
-    float* dflow = nullptr; double* dcent = nullptr; u64* mm = nullptr; unsigned long long* cnt = nullptr;
-    hipError_t e = hipMalloc(&dflow, tot * 2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&dcent, (size_t)N * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&mm, 4 * sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc(&cnt, (size_t)N * 2 * sizeof(unsigned long long));
-    const u64 mm0[4] = {~0ull, 0ull, ~0ull, 0ull};
-    u64 mmh[4];
-    std::vector<unsigned long long> ch((size_t)N * 2);
-    if (e == hipSuccess) e = hipMemcpyAsync(dflow, flow, tot * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dcent, centroids, (size_t)N * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(mm, mm0, sizeof mm0, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)N * 2 * sizeof(unsigned long long), h->stream);
-    if (e == hipSuccess) {
-        const int gx = (int)((npx + 255) / 256);
-        hipLaunchKernelGGL(k_radlong_project, dim3(gx < 256 ? gx : 256, N), dim3(256), 0, h->stream, dflow, dcent, H, W, h->an_rad, h->an_lon, mm, cnt);
-        e = hipMemcpyAsync(mmh, mm, sizeof mmh, hipMemcpyDeviceToHost, h->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && rad_out) e = hipMemcpyAsync(rad_out, h->an_rad, tot * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && long_out) e = hipMemcpyAsync(long_out, h->an_lon, tot * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(dflow); (void)hipFree(dcent); (void)hipFree(mm); (void)hipFree(cnt);
-    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_radlong_project: %s", hipGetErrorString(e));
-    for (int j = 0; j < 4; ++j) minmax[j] = f64_unkey(mmh[j]);
-    for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
-    h->anN = N; h->anH = H; h->anW = W;
-    h->an_polar = false;
-    h->an_finite = std::isfinite(minmax[0]) && std::isfinite(minmax[1]) && std::isfinite(minmax[2]) && std::isfinite(minmax[3]);
-    return TF_OK;
-}
-
-TF_API int tf_radlong_hist(tf_handle* h, int which, const double* edges, int nbins, long long* freq_out)
-{
-    if (!h || !edges || !freq_out || nbins < 1 || which < 0 || which > 1) return TF_ERR_INVALID_ARG;
-    if (h->anN < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_hist needs a preceding tf_radlong_project");
-    HIPC(h, hipSetDevice(h->dev));
-    const size_t npx = (size_t)h->anH * h->anW;
-    double* de = nullptr; unsigned long long* df = nullptr;
-    HIPC(h, hipMalloc(&de, (size_t)(nbins + 1) * sizeof(double)));
-    hipError_t e = hipMalloc(&df, (size_t)h->anN * nbins * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpyAsync(de, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(df, 0, (size_t)h->anN * nbins * sizeof(unsigned long long), h->stream);
-    if (e == hipSuccess) {
-        const int gx = (int)((npx + 255) / 256);
-        hipLaunchKernelGGL(k_radlong_hist, dim3(gx < 256 ? gx : 256, h->anN), dim3(256), 0, h->stream, which ? h->an_lon : h->an_rad, npx, de, nbins, df);
-        e = hipMemcpyAsync(freq_out, df, (size_t)h->anN * nbins * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(de); (void)hipFree(df);
-    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_radlong_hist: %s", hipGetErrorString(e));
-    return TF_OK;
-}
-
-TF_API int tf_radlong_select(tf_handle* h, int which, const long long* ranks, double* values_out)
-{
-    if (!h || !ranks || !values_out || which < 0 || which > 1) return TF_ERR_INVALID_ARG;
-    if (h->anN < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_select needs a preceding tf_radlong_project");
-    HIPC(h, hipSetDevice(h->dev));
-    const int N = h->anN, NS = N * RL_NSLOT;
-    const size_t npx = (size_t)h->anH * h->anW;
-    u64* pf = nullptr; long long* rk = nullptr; int* ac = nullptr; unsigned* hist = nullptr;
-    std::vector<int> act((size_t)NS);
-    for (int i = 0; i < NS; ++i) act[i] = ranks[i] >= 0;
-    HIPC(h, hipMalloc(&pf, (size_t)NS * sizeof(u64)));
-    hipError_t e = hipMalloc(&rk, (size_t)NS * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&ac, (size_t)NS * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&hist, (size_t)NS * 65536 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemsetAsync(pf, 0, (size_t)NS * sizeof(u64), h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rk, ranks, (size_t)NS * sizeof(long long), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ac, act.data(), (size_t)NS * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    const double* v = which ? h->an_lon : h->an_rad;
-    const int gx = (int)((npx + 255) / 256);
-    for (int shift = 48; shift >= 0 && e == hipSuccess; shift -= 16) {
-        e = hipMemsetAsync(hist, 0, (size_t)NS * 65536 * sizeof(unsigned), h->stream);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_radlong_sel_hist, dim3(gx < 256 ? gx : 256, N), dim3(256), 0, h->stream, v, npx, shift, pf, ac, hist);
-        hipLaunchKernelGGL(k_radlong_sel_scan, dim3(NS), dim3(256), 0, h->stream, hist, shift, pf, rk, ac);
-    }
-    std::vector<u64> keys((size_t)NS);
-    if (e == hipSuccess) e = hipMemcpyAsync(keys.data(), pf, (size_t)NS * sizeof(u64), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(pf); (void)hipFree(rk); (void)hipFree(ac); (void)hipFree(hist);
-    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_radlong_select: %s", hipGetErrorString(e));
-    for (int i = 0; i < NS; ++i) values_out[i] = act[i] ? f64_unkey(keys[i]) : 0.0;
-    return TF_OK;
-}
-
-namespace {
-// tf_av_centroids: frames go through in chunks so that the per-chunk scratch (26 B per pixel + the mask bytes) stays within
-// MASK_CHUNK_BYTES whatever the study's length
-int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* cent_out, long long* area_out)
-{
-    using namespace cen;
-    const size_t HW = (size_t)H * W;
-    if (HW > 0x7fffffffu) return fail(h, TF_ERR_UNSUPPORTED, "tf_av_centroids: at most 2^31 - 1 pixels per frame");
-    const size_t per_frame = HW * (26 + (size_t)C);
-    size_t nf = MASK_CHUNK_BYTES / per_frame;
-    if (nf > (size_t)N) nf = (size_t)N;
-    if (nf > 65535) nf = 65535;                                // frames of a chunk are grid.y
-    if (nf < 1) nf = 1;
-    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t* dm = nullptr; uint32_t* dpar = nullptr; uint16_t* dlr = nullptr; uint32_t* darea = nullptr; unsigned long long* dsum = nullptr;
-    uint8_t* out = nullptr;                                    // [0, 64): error word, then centroids [N][2] f64, then areas [N] i64
-    int rc;
-    if ((rc = pre_grow(h, tf_handle::PRE_CT_MASK, nf * HW * C, (void**)&dm)) ||
-        (rc = pre_grow(h, tf_handle::PRE_CT_PAR, nf * HW * 4, (void**)&dpar)) ||
-        (rc = pre_grow(h, tf_handle::PRE_CT_LR, nf * HW * 2, (void**)&dlr)) ||
-        (rc = pre_grow(h, tf_handle::PRE_CT_AREA, nf * HW * 4, (void**)&darea)) ||
-        (rc = pre_grow(h, tf_handle::PRE_CT_SUM, nf * HW * 16, (void**)&dsum)) ||
-        (rc = pre_grow(h, tf_handle::PRE_CT_OUT, 64 + (size_t)N * 24, (void**)&out))) return rc;
-    unsigned* derr = (unsigned*)out;
-    double* dcent = (double*)(out + 64);
-    long long* dar = (long long*)(out + 64 + (size_t)N * 16);
-    const hipStream_t s = h->stream;
-    HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
-    for (int f0 = 0; f0 < N; f0 += (int)nf) {
-        const int n = N - f0 < (int)nf ? N - f0 : (int)nf;
-        const dim3 g(tiles, (unsigned)n), blk(256);
-        HIPC(h, hipMemcpyAsync(dm, masks + (size_t)f0 * HW * C, (size_t)n * HW * C, hipMemcpyHostToDevice, s));
-        HIPC(h, hipMemsetAsync(darea, 0, (size_t)n * HW * 4, s));
-        HIPC(h, hipMemsetAsync(dsum, 0, (size_t)n * HW * 16, s));
-        hipLaunchKernelGGL(k_cent_local, g, blk, 0, s, dm, C, dpar, dlr, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_cent_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_cent_flatten, g, blk, 0, s, dpar, dlr, darea, dsum, H, W, tiles_x);
-        hipLaunchKernelGGL(k_cent_pick, dim3((unsigned)n), blk, 0, s, dpar, darea, dsum, HW, dcent + 2 * (size_t)f0, dar + f0);
-        HIPC(h, hipGetLastError());
-    }
-    unsigned e = 0;
-    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(cent_out, dcent, (size_t)N * 16, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(area_out, dar, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    if (e) return fail(h, TF_ERR_HIP, "tf_av_centroids: a union-find loop ran out of its bound (code %u)", e);
-    return TF_OK;
-}
-
-// the resident analysis planes hold at least tot doubles each (grown, never shrunk); they are invalid until the caller's projection
-// has run (anN = 0)
-int grow_an_planes(tf_handle* h, size_t tot)
-{
-    h->anN = 0;
-    if (h->an_cap < tot) {
-        HIPC(h, hipStreamSynchronize(h->stream));
-        if (h->an_rad) { (void)hipFree(h->an_rad); h->an_rad = nullptr; }
-        if (h->an_lon) { (void)hipFree(h->an_lon); h->an_lon = nullptr; }
-        h->an_cap = 0;
-        HIPC(h, hipMalloc(&h->an_rad, tot * sizeof(double)));
-        HIPC(h, hipMalloc(&h->an_lon, tot * sizeof(double)));
-        h->an_cap = tot;
-    }
-    return TF_OK;
-}
-
-template <int PARAM, typename FT>
-void launch_project_param(dim3 g, hipStream_t s, const void* flow, int N, const uint8_t* mask, int C, double sp, int grad_f64, const double* cent,
-                          int H, int W, double* rad, double* lon, u64* mm, unsigned long long* cnt)
-{
-    if (grad_f64)
-        hipLaunchKernelGGL((k_radlong_project_param<PARAM, FT, double>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, cent, H, W, rad, lon, mm, cnt);
-    else
-        hipLaunchKernelGGL((k_radlong_project_param<PARAM, FT, float>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, cent, H, W, rad, lon, mm, cnt);
-}
-
-int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
-                          double spacing, int grad_f64, const double* centroids, double* rad_out, double* long_out, double* minmax,
-                          long long* nonzero)
-{
-    const size_t npx = (size_t)H * W, tot = (size_t)n_used * npx;
-    const int nflow = param == RL_PARAM_VELOCITY ? n_used : (n_used + 1 < N ? n_used + 1 : N);   // frames the gradient of [0, n_used) reads
-    const size_t flow_bytes = (size_t)nflow * npx * 2 * (f16 ? 2 : 4);
-    HIPC(h, hipSetDevice(h->dev));
-    int rc;
-    if ((rc = grow_an_planes(h, tot))) return rc;
-    void* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr;   // meta: min/max keys [4], counts [n_used][2], centroids [n_used][2]
-    if ((rc = pre_grow(h, tf_handle::PRE_AN_FLOW, flow_bytes, &dflow)) ||
-        (rc = pre_grow(h, tf_handle::PRE_AN_MASK, tot * C, (void**)&dmask)) ||
-        (rc = pre_grow(h, tf_handle::PRE_AN_META, 32 + (size_t)n_used * 32, (void**)&meta))) return rc;
-    u64* mm = (u64*)meta;
-    unsigned long long* cnt = (unsigned long long*)(meta + 32);
-    double* dcent = (double*)(meta + 32 + (size_t)n_used * 16);
-    const u64 mm0[4] = {~0ull, 0ull, ~0ull, 0ull};
-    u64 mmh[4];
-    std::vector<unsigned long long> ch((size_t)n_used * 2);
-    const hipStream_t s = h->stream;
-    HIPC(h, hipMemcpyAsync(dflow, flow, flow_bytes, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(dmask, mask, tot * C, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(dcent, centroids, (size_t)n_used * 16, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(mm, mm0, sizeof mm0, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemsetAsync(cnt, 0, (size_t)n_used * 16, s));
-    const int gx = (int)((npx + 255) / 256);
-    const dim3 g(gx < 256 ? gx : 256, n_used);
-#define TF_PP(P) (f16 ? launch_project_param<P, _Float16>(g, s, dflow, N, dmask, C, spacing, grad_f64, dcent, H, W, h->an_rad, h->an_lon, mm, cnt) \
-                      : launch_project_param<P, float>(g, s, dflow, N, dmask, C, spacing, grad_f64, dcent, H, W, h->an_rad, h->an_lon, mm, cnt))
-    if (param == RL_PARAM_VELOCITY) TF_PP(RL_PARAM_VELOCITY);
-    else if (param == RL_PARAM_ACCELERATION) TF_PP(RL_PARAM_ACCELERATION);
-    else TF_PP(RL_PARAM_PWR);
-#undef TF_PP
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(mmh, mm, sizeof mmh, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (rad_out) HIPC(h, hipMemcpyAsync(rad_out, h->an_rad, tot * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (long_out) HIPC(h, hipMemcpyAsync(long_out, h->an_lon, tot * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    for (int j = 0; j < 4; ++j) minmax[j] = f64_unkey(mmh[j]);
-    for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
-    h->anN = n_used; h->anH = H; h->anW = W;
-    h->an_polar = false;
-    h->an_finite = std::isfinite(minmax[0]) && std::isfinite(minmax[1]) && std::isfinite(minmax[2]) && std::isfinite(minmax[3]);
-    return TF_OK;
-}
-
-template <int PARAM, typename FT>
-void launch_polar_param(dim3 g, hipStream_t s, const void* flow, int N, const uint8_t* mask, int C, double sp, int grad_f64, int H, int W,
-                        double* magp, double* angp, float* mag32, float* ang32, u64* mm, unsigned long long* cnt, unsigned* bins)
-{
-    if (grad_f64)
-        hipLaunchKernelGGL((k_polar_project_param<PARAM, FT, double>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, H, W, magp, angp, mag32, ang32, mm, cnt, bins);
-    else
-        hipLaunchKernelGGL((k_polar_project_param<PARAM, FT, float>), g, dim3(256), 0, s, (const FT*)flow, N, mask, C, sp, H, W, magp, angp, mag32, ang32, mm, cnt, bins);
-}
-
-int polar_project_param(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
-                        double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax, long long* nonzero, float* ang_mode)
-{
-    const size_t npx = (size_t)H * W, tot = (size_t)n_used * npx;
-    const int nflow = param == RL_PARAM_VELOCITY ? n_used : (n_used + 1 < N ? n_used + 1 : N);   // frames the gradient of [0, n_used) reads
-    const size_t flow_bytes = (size_t)nflow * npx * 2 * (f16 ? 2 : 4);
-    const bool arrays = mag_out || ang_out;
-    HIPC(h, hipSetDevice(h->dev));
-    int rc;
-    if ((rc = grow_an_planes(h, tot))) return rc;
-    void* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr; float* d32 = nullptr;
-    // meta: min/max keys [4], counts [n_used][2], mode k [n_used], angle bins [n_used][PO_NBINS]
-    const size_t meta_bytes = 32 + (size_t)n_used * 16 + (size_t)n_used * 4 + (size_t)n_used * PO_NBINS * 4;
-    if ((rc = pre_grow(h, tf_handle::PRE_AN_FLOW, flow_bytes, &dflow)) ||
-        (rc = pre_grow(h, tf_handle::PRE_AN_MASK, tot * C, (void**)&dmask)) ||
-        (rc = pre_grow(h, tf_handle::PRE_PO_META, meta_bytes, (void**)&meta)) ||
-        (arrays && (rc = pre_grow(h, tf_handle::PRE_PO_OUT, tot * 2 * sizeof(float), (void**)&d32)))) return rc;
-    u64* mm = (u64*)meta;
-    unsigned long long* cnt = (unsigned long long*)(meta + 32);
-    int* dmode = (int*)(meta + 32 + (size_t)n_used * 16);
-    unsigned* bins = (unsigned*)(meta + 32 + (size_t)n_used * 20);
-    const u64 mm0[4] = {~0ull, 0ull, ~0ull, 0ull};
-    u64 mmh[4];
-    std::vector<unsigned long long> ch((size_t)n_used * 2);
-    std::vector<int> kh((size_t)n_used);
-    const hipStream_t s = h->stream;
-    HIPC(h, hipMemcpyAsync(dflow, flow, flow_bytes, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(dmask, mask, tot * C, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(mm, mm0, sizeof mm0, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemsetAsync(cnt, 0, meta_bytes - 32, s));
-    // each block takes >= 4096 pixels of a frame: its angle bins go to global memory once per block
-    const int gx = (int)((npx + 4095) / 4096);
-    const dim3 g(gx < 64 ? gx : 64, n_used);
-    float* m32 = arrays ? d32 : nullptr;
-    float* a32 = arrays ? d32 + tot : nullptr;
-#define TF_PO(P) (f16 ? launch_polar_param<P, _Float16>(g, s, dflow, N, dmask, C, spacing, grad_f64, H, W, h->an_rad, h->an_lon, m32, a32, mm, cnt, bins) \
-                      : launch_polar_param<P, float>(g, s, dflow, N, dmask, C, spacing, grad_f64, H, W, h->an_rad, h->an_lon, m32, a32, mm, cnt, bins))
-    if (param == RL_PARAM_VELOCITY) TF_PO(RL_PARAM_VELOCITY);
-    else if (param == RL_PARAM_ACCELERATION) TF_PO(RL_PARAM_ACCELERATION);
-    else TF_PO(RL_PARAM_PWR);
-#undef TF_PO
-    hipLaunchKernelGGL(k_polar_mode, dim3((unsigned)n_used), dim3(256), 0, s, bins, dmode);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(mmh, mm, sizeof mmh, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(ch.data(), cnt, ch.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(kh.data(), dmode, kh.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (mag_out) HIPC(h, hipMemcpyAsync(mag_out, m32, tot * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (ang_out) HIPC(h, hipMemcpyAsync(ang_out, a32, tot * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    for (int j = 0; j < 4; ++j) minmax[j] = (float)f64_unkey(mmh[j]);        // exact: the planes hold float32 values
-    for (size_t i = 0; i < ch.size(); ++i) nonzero[i] = (long long)ch[i];
-    for (int i = 0; i < n_used; ++i) ang_mode[i] = kh[i] ? (float)kh[i] / 100.f : std::numeric_limits<float>::quiet_NaN();
-    h->anN = n_used; h->anH = H; h->anW = W;
-    h->an_polar = true;
-    return TF_OK;
-}
-
-// tf_radlong_overlay: the indices (2 B per pixel of the study, an eighth of the resident planes) are made for all frames at once, since
-// m2 needs every frame's; the echo upload and the output (eb + 6 B per pixel) go through in chunks of as many frames as fit in
-// MASK_CHUNK_BYTES.  A study of one chunk uploads its echo once; a longer one uploads it a second time for the compose pass.
-template <int KIND>
-int radlong_overlay(tf_handle* h, const void* echo_v, const double* lut_rad, const double* lut_long, uint8_t* out, double* info)
-{
-    using namespace ovl;
-    using ET = typename Echo<KIND>::T;
-    const ET* echo = (const ET*)echo_v;
-    const int n = h->anN, H = h->anH, W = h->anW;
-    const size_t HW = (size_t)H * W, tot = (size_t)n * HW, eb = sizeof(ET);
-    const size_t chunk_bytes = h->overlay_chunk_kib > 0 ? (size_t)h->overlay_chunk_kib << 10 : MASK_CHUNK_BYTES;
-    size_t nf = chunk_bytes / (HW * (eb + 6));
-    if (nf > (size_t)n) nf = (size_t)n;
-    if (nf < 1) nf = 1;
-    const size_t out_dwords = (nf * HW * 2 + 3) / 4 * 3;      // 3 dwords per run of 4 slots, whole runs: what k_ov_compose stores
-    HIPC(h, hipSetDevice(h->dev));
-    uint16_t* didx = nullptr; ET* decho = nullptr; unsigned* dout = nullptr; uint8_t* meta = nullptr;
-    // meta: [0, 8) half bits, [8, 16) echo max bits + bad flag, [16, 80) used bitsets [2][8], [128, 128 + 12288) colour terms [2][256][3] f64
-    int rc;
-    if ((rc = pre_grow(h, tf_handle::PRE_OV_IDX, tot * 2, (void**)&didx)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OV_ECHO, nf * HW * eb, (void**)&decho)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OV_OUT, out_dwords * 4, (void**)&dout)) ||
-        (rc = pre_grow(h, tf_handle::PRE_OV_META, 128 + 2 * 256 * 3 * sizeof(double), (void**)&meta))) return rc;
-    u64* dhalf = (u64*)meta;
-    unsigned* demax = (unsigned*)(meta + 8);
-    unsigned* dused = (unsigned*)(meta + 16);
-    double* dcol = (double*)(meta + 128);
-    const hipStream_t s = h->stream;
-    const dim3 blk(256);
-    auto grid = [](size_t work, size_t cap) { const size_t g = (work + 255) / 256; return dim3((unsigned)(g < cap ? g : cap)); };
-    HIPC(h, hipMemsetAsync(meta, 0, 128, s));
-    hipLaunchKernelGGL(k_ov_half, grid(HW, 256), blk, 0, s, h->an_rad, HW, dhalf);
-    hipLaunchKernelGGL(k_ov_index, grid(tot, 2048), blk, 0, s, h->an_rad, h->an_lon, tot, dhalf, didx, dused);
-    HIPC(h, hipGetLastError());
-    for (int f0 = 0; f0 < n; f0 += (int)nf) {
-        const size_t c = (size_t)(n - f0 < (int)nf ? n - f0 : (int)nf) * HW;
-        HIPC(h, hipMemcpyAsync(decho, echo + (size_t)f0 * HW, c * eb, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ov_echo<KIND>, grid(c, 1024), blk, 0, s, decho, c, demax);
-        HIPC(h, hipGetLastError());
-    }
-    struct { u64 half; unsigned emax, bad; unsigned used[16]; } m;
-    static_assert(sizeof m == 80, "layout of the overlay's meta words");
-    HIPC(h, hipMemcpyAsync(&m, meta, sizeof m, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    union { u64 u; double d; } hb; hb.u = m.half;
-    union { unsigned u; float f; } em; em.u = m.emax;
-    const double half = hb.d, emax = (double)em.f;
-    if (m.bad) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the echo holds a negative or non-finite value");
-    if (emax == 0.0) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the echo's maximum is 0");
-    if (!std::isfinite(half - (-half))) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the norm's range 2 * %g overflows", half);
-    double m2 = 0.0;
-    for (int c = 0; c < 2; ++c)
-        for (int j = 0; j < 256; ++j)
-            if ((m.used[8 * c + (j >> 5)] >> (j & 31)) & 1u)
-                for (int ch = 0; ch < 3; ++ch) { const double v = (c ? lut_long : lut_rad)[3 * j + ch]; m2 = v > m2 ? v : m2; }
-    if (m2 == 0.0) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: every colour used is black (the colour maximum is 0)");
-    std::vector<double> col(2 * 256 * 3);
-    for (int c = 0; c < 2; ++c)
-        for (int j = 0; j < 256 * 3; ++j) col[(size_t)c * 768 + j] = 0.5 * ((c ? lut_long : lut_rad)[j] / m2);
-    HIPC(h, hipMemcpyAsync(dcol, col.data(), col.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    for (int f0 = 0; f0 < n; f0 += (int)nf) {
-        const int nc = n - f0 < (int)nf ? n - f0 : (int)nf;
-        const size_t c = (size_t)nc * HW, slots = 2 * c;                                // nc <= nf: the runs of `slots` fit out_dwords
-        if ((size_t)n > nf) HIPC(h, hipMemcpyAsync(decho, echo + (size_t)f0 * HW, c * eb, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ov_compose<KIND>, dim3((unsigned)((slots + 1023) / 1024)), blk, 0, s, didx + (size_t)f0 * HW, decho, emax, dcol,
-                           (size_t)nc * H, W, dout);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(out + (size_t)f0 * HW * 6, dout, c * 6, hipMemcpyDeviceToHost, s));
-    }
-    HIPC(h, hipStreamSynchronize(s));
-    info[0] = half; info[1] = emax; info[2] = m2;
-    return TF_OK;
-}
-
-// a failed call leaves nothing of it running: its destinations are host memory the caller may free at once
-int finish_host_call(tf_handle* h, int rc)
-{
-    if (rc != TF_OK) {
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        (void)hipGetLastError();
-    }
-    return rc;
-}
-}  // namespace
-
-static_assert(TF_PARAM_VELOCITY == RL_PARAM_VELOCITY && TF_PARAM_ACCELERATION == RL_PARAM_ACCELERATION && TF_PARAM_PWR == RL_PARAM_PWR,
-              "param codes of the header and the kernel differ");
-
-// Argument checks return before the handle is touched (no message: the Python layer checks the same first and says why).
-TF_API int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* centroids_out, long long* area_out)
-{
-    if (!h || !masks || !centroids_out || !area_out || N < 1 || H < 1 || W < 1 || (C != 1 && C != 2)) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, av_centroids(h, masks, N, H, W, C, centroids_out, area_out));
-}
-
-TF_API int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
-                                    int mask_C, int param, double spacing, int grad_f64, const double* centroids, double* rad_out,
-                                    double* long_out, double* minmax, long long* nonzero)
-{
-    if (!h || !flow || !mask || !centroids || !minmax || !nonzero || N < 1 || n_used < 1 || H < 1 || W < 1 || n_used > N) return TF_ERR_INVALID_ARG;
-    if ((mask_C != 1 && mask_C != 2) || param < TF_PARAM_VELOCITY || param > TF_PARAM_PWR) return TF_ERR_INVALID_ARG;
-    if (param != TF_PARAM_VELOCITY && (N < 2 || !std::isfinite(spacing) || spacing == 0.0)) return TF_ERR_INVALID_ARG;   // np.gradient needs 2 frames
-    if (n_used > 65535) return TF_ERR_UNSUPPORTED;                                                                     // frames are grid.y
-    return finish_host_call(h, radlong_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
-                                                     centroids, rad_out, long_out, minmax, nonzero));
-}
-
-TF_API int tf_polar_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
-                                  int mask_C, int param, double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax,
-                                  long long* nonzero, float* ang_mode)
-{
-    if (!h || !flow || !mask || !minmax || !nonzero || !ang_mode || N < 1 || n_used < 1 || H < 1 || W < 1 || n_used > N) return TF_ERR_INVALID_ARG;
-    if ((mask_C != 1 && mask_C != 2) || param < TF_PARAM_VELOCITY || param > TF_PARAM_PWR) return TF_ERR_INVALID_ARG;
-    if (param != TF_PARAM_VELOCITY && (N < 2 || !std::isfinite(spacing) || spacing == 0.0)) return TF_ERR_INVALID_ARG;   // np.gradient needs 2 frames
-    if (n_used > 65535 || (size_t)H * W > 0xFFFFFFFFu) return TF_ERR_UNSUPPORTED;       // frames are grid.y; a frame's counts are 32-bit
-    return finish_host_call(h, polar_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
-                                                   mag_out, ang_out, minmax, nonzero, ang_mode));
-}
-
-static_assert(TF_ECHO_F16 == ovl::ECHO_F16 && TF_ECHO_U8 == ovl::ECHO_U8, "echo kinds of the header and the kernel differ");
-
-TF_API int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const double* lut_rad, const double* lut_long, uint8_t* out,
-                              double* info)
-{
-    if (!h || !echo || !lut_rad || !lut_long || !out || !info || (echo_kind != TF_ECHO_F16 && echo_kind != TF_ECHO_U8)) return TF_ERR_INVALID_ARG;
-    for (int j = 0; j < 256 * 3; ++j)
-        if (!(lut_rad[j] >= 0.0 && std::isfinite(lut_rad[j]) && lut_long[j] >= 0.0 && std::isfinite(lut_long[j])))
-            return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: a colormap entry is negative or not finite");
-    if (h->anN < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay needs a preceding tf_radlong_project or tf_radlong_project_param");
-    if (h->an_polar) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the handle's last projection was tf_polar_project_param, not a rad/long one");
-    if (!h->an_finite) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the rad/long planes hold NaN or inf");
-    if ((size_t)h->anH * h->anW > 0x7fffffffu / 8) return fail(h, TF_ERR_UNSUPPORTED, "tf_radlong_overlay: at most 2^28 - 1 pixels per frame");
-    return finish_host_call(h, echo_kind == TF_ECHO_F16 ? radlong_overlay<ovl::ECHO_F16>(h, echo, lut_rad, lut_long, out, info)
-                                                        : radlong_overlay<ovl::ECHO_U8>(h, echo, lut_rad, lut_long, out, info));
-}
-
-TF_API int tf_radlong_shape(tf_handle* h, int* shape)
-{
-    if (!h || !shape) return TF_ERR_INVALID_ARG;
-    const bool have = h->anN >= 1 && !h->an_polar;
-    shape[0] = have ? h->anN : 0; shape[1] = have ? h->anH : 0; shape[2] = have ? h->anW : 0;
-    return TF_OK;
-}
-
-// pinned host memory for results: a destination allocated here makes the host-pointer entry points copy out at PCIe
-// speed, overlapped with the solve of the next sub-batch
-TF_API void* tf_host_alloc(size_t bytes)
-{
-    void* p = nullptr;
-    if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    return p;
-}
-TF_API void tf_host_free(void* p)
-{
-    if (p) (void)hipHostFree(p);
-}
-
-// ---- WASE background compensation (rows a7 / f2) ---------------------------------------------------------------
-namespace {
-int wase_grow(tf_handle* h, size_t na, size_t ncnt, size_t nsum, size_t nbg)
-{
-    if (h->wa_cap < na) { if (h->wa) (void)hipFree(h->wa); h->wa = nullptr; h->wa_cap = 0; HIPC(h, hipMalloc(&h->wa, na * sizeof(float))); h->wa_cap = na; }
-    if (h->wcnt_cap < ncnt) {
-        if (h->wcnt) (void)hipFree(h->wcnt);
-        if (h->woff) (void)hipFree(h->woff);
-        h->wcnt = nullptr; h->woff = nullptr; h->wcnt_cap = 0;
-        HIPC(h, hipMalloc(&h->wcnt, ncnt * sizeof(unsigned))); HIPC(h, hipMalloc(&h->woff, (ncnt + 1) * sizeof(u64)));
-        h->wcnt_cap = ncnt;
-    }
-    if (h->wsum_cap < nsum) { if (h->wsum) (void)hipFree(h->wsum); h->wsum = nullptr; h->wsum_cap = 0; HIPC(h, hipMalloc(&h->wsum, nsum * sizeof(float))); h->wsum_cap = nsum; }
-    if (h->wbg_cap < nbg) { if (h->wbg) (void)hipFree(h->wbg); h->wbg = nullptr; h->wbg_cap = 0; HIPC(h, hipMalloc(&h->wbg, nbg * sizeof(float))); h->wbg_cap = nbg; }
-    return TF_OK;
-}
-
-// flows, bkgd: device.  Leaves the backgrounds in h->wbg[0..P) and (if apply) the compensated, scaled flows in place.
-int wase_device(tf_handle* h, float* flows, const uint8_t* bkgd, int P, int N, int H, int W, float scale, bool apply)
-{
-    const size_t hw2 = (size_t)H * W * 2;
-    const int C = (int)((hw2 + WASE_CHUNK - 1) / WASE_CHUNK);
-    const size_t ncnt = (size_t)N * C, na = (size_t)N * hw2, npieces = (na + NP_BUFSIZE - 1) / NP_BUFSIZE;
-    int rc = wase_grow(h, na, ncnt, npieces, (size_t)P);
-    if (rc) return rc;
-    hipStream_t s = h->stream;
-    for (int p = 0; p < P; ++p) {
-        const float* f = flows + (size_t)p * hw2;
-        hipLaunchKernelGGL(k_wase_count, dim3(C, N), dim3(256), 0, s, f, bkgd, hw2, C, h->wcnt);
-        hipLaunchKernelGGL(k_wase_scan, dim3(1), dim3(1024), 0, s, h->wcnt, ncnt, h->woff);
-        hipLaunchKernelGGL(k_wase_scatter, dim3(C, N), dim3(256), 0, s, f, bkgd, hw2, C, h->woff, h->wa);
-        hipLaunchKernelGGL(k_wase_piece_sums, dim3((unsigned)npieces), dim3(512), 0, s, h->wa, h->woff + ncnt, h->wsum);
-        hipLaunchKernelGGL(k_wase_finish, dim3(1), dim3(64), 0, s, h->wsum, h->woff + ncnt, h->wbg + p);
-    }
-    if (apply) {
-        const unsigned gx = (unsigned)std::min<size_t>((hw2 + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_wase_apply, dim3(gx, P), dim3(256), 0, s, flows, h->wbg, hw2, scale);
-    }
-    HIPC(h, hipGetLastError());
-    return TF_OK;
-}
-}  // namespace
-
-TF_API int tf_wase_compensate_device(tf_handle* h, float* flows, int n_flows, const uint8_t* bkgd, int n_frames, int H, int W, float scale,
-                                     float* background_out)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (!flows || !bkgd || n_flows < 1 || n_frames < 1 || H < 1 || W < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_wase_compensate: bad argument");
-    HIPC(h, hipSetDevice(h->dev));
-    int rc = wase_device(h, flows, bkgd, n_flows, n_frames, H, W, scale, true);
-    if (rc) return rc;
-    if (background_out) HIPC(h, hipMemcpyAsync(background_out, h->wbg, (size_t)n_flows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    return TF_OK;
-}
-
-TF_API int tf_wase_compensate(tf_handle* h, float* flows, int n_flows, const uint8_t* bkgd, int n_frames, int H, int W, float scale,
-                              float* background_out)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (!flows || !bkgd || n_flows < 1 || n_frames < 1 || H < 1 || W < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_wase_compensate: bad argument");
-    HIPC(h, hipSetDevice(h->dev));
-    const size_t hw2 = (size_t)H * W * 2;
-    float* df = nullptr; uint8_t* dm = nullptr;
-    HIPC(h, hipMalloc(&dm, (size_t)n_frames * hw2));
-    hipError_t e = hipMemcpyAsync(dm, bkgd, (size_t)n_frames * hw2, hipMemcpyHostToDevice, h->stream);
-    const int chunk = 64;                                   // flows per round trip
-    if (e == hipSuccess) e = hipMalloc(&df, (size_t)std::min(chunk, n_flows) * hw2 * sizeof(float));
-    int rc = TF_OK;
-    for (int p0 = 0; p0 < n_flows && e == hipSuccess && rc == TF_OK; p0 += chunk) {
-        const int np = std::min(chunk, n_flows - p0);
-        e = hipMemcpyAsync(df, flows + (size_t)p0 * hw2, (size_t)np * hw2 * sizeof(float), hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) break;
-        rc = wase_device(h, df, dm, np, n_frames, H, W, scale, true);
-        if (rc) break;
-        e = hipMemcpyAsync(flows + (size_t)p0 * hw2, df, (size_t)np * hw2 * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && background_out)
-            e = hipMemcpyAsync(background_out + p0, h->wbg, (size_t)np * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(df); (void)hipFree(dm);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_wase_compensate: %s", hipGetErrorString(e));
-    return TF_OK;
-}
+// the study tail: everything around the solver, from frame conditioning to WASE (host code; its kernels are in the kernel headers)
+#include "teeflow_tail.hip.h"
 
 TF_API int tf_get_iters(tf_handle* h, int* out, size_t capacity_ints, size_t* written)
 {

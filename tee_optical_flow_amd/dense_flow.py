@@ -343,47 +343,9 @@ class DenseFlow:
         _lib.check(self._L.tf_av_centroids(self._h, m.ctypes.data, N, H, W, Cm, cent.ctypes.data, area.ctypes.data), self._h, "tf_av_centroids")
         return cent, area
 
-    def radlong_project_param(self, flow, mask, param, spacing, grad_f64, n_used, centroids, return_arrays=False):
-        """tf_radlong_project_param: the rad/long projection of OpticalFlowDataset's param field (param 0 velocity, 1 acceleration,
-        2 PWR) for frames [0, n_used), resident on the device for tf_radlong_hist / _select.  flow float16 or float32 [N,H,W,2],
-        mask bool or uint8 [>= n_used,H,W,C].  Returns (minmax float64 [4], nonzero int64 [n_used, 2], rad, long): rad / long are
-        float64 [n_used,H,W] with return_arrays, else None."""
-        flow = np.asarray(flow)
-        if flow.dtype not in (np.float16, np.float32):
-            flow = flow.astype(np.float32)
-        flow = np.ascontiguousarray(flow)
-        if flow.ndim != 4 or flow.shape[3] != 2:
-            raise OpticalFlowCalculationError(f"flow must be [N,H,W,2], got {flow.shape}")
-        N, H, W, _ = flow.shape
-        n_used = int(n_used)
-        if not 1 <= n_used <= N:
-            raise OpticalFlowCalculationError(f"n_used must be in [1, {N}], got {n_used}")
-        if param not in (0, 1, 2):
-            raise OpticalFlowCalculationError(f"param must be 0 (velocity), 1 (acceleration) or 2 (PWR), got {param!r}")
-        if param != 0 and N < 2:
-            raise OpticalFlowCalculationError("the gradient needs at least 2 flow frames")
-        m = _mask_stack(np.asarray(mask)[:n_used], "mask")
-        if m.shape[:3] != (n_used, H, W):
-            raise OpticalFlowCalculationError(f"mask must be [>= {n_used},{H},{W},C], got {np.shape(mask)}")
-        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(n_used, 2)
-        rad = np.empty((n_used, H, W), np.float64) if return_arrays else None
-        lon = np.empty((n_used, H, W), np.float64) if return_arrays else None
-        mm = np.zeros(4, np.float64)
-        nz = np.zeros((n_used, 2), np.int64)
-        _lib.check(self._L.tf_radlong_project_param(self._h, flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W,
-                                                    m.ctypes.data, m.shape[3], int(param), float(spacing), 1 if grad_f64 else 0,
-                                                    cent.ctypes.data, rad.ctypes.data if return_arrays else None,
-                                                    lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data),
-                   self._h, "tf_radlong_project_param")
-        return mm, nz, rad, lon
-
-    def polar_project_param(self, flow, mask, param, spacing, grad_f64, n_used, return_arrays=False):
-        """tf_polar_project_param: cv2.cartToPolar (analysis.cart_to_polar's arithmetic) of OpticalFlowDataset's param field (param 0
-        velocity, 1 acceleration, 2 PWR) for frames [0, n_used); magnitude and angle stay resident on the device for tf_radlong_hist /
-        _select (which 0 / 1).  flow float16 or float32 [N,H,W,2], mask bool or uint8 [>= n_used,H,W,C].  Returns (minmax float32 [4]
-        (mag min, max, ang min, max), nonzero int64 [n_used, 2] (non-zero mag, ang per frame), ang_mode float32 [n_used] (the angle
-        detector's per-frame mode, NaN if none), mag, ang): mag / ang are float32 [n_used,H,W] with return_arrays, else None.  May
-        be called while submitted studies are in flight on this engine."""
+    @staticmethod
+    def _project_param_inputs(flow, mask, param, spacing, n_used):
+        """what both *_project_param calls check and lay out: -> (flow [N,H,W,2] float16 / float32, mask [n_used,H,W,C] uint8, n_used)"""
         flow = np.asarray(flow)
         if flow.dtype not in (np.float16, np.float32):
             flow = flow.astype(np.float32)
@@ -403,6 +365,36 @@ class DenseFlow:
         m = _mask_stack(np.asarray(mask)[:n_used], "mask")
         if m.shape[:3] != (n_used, H, W):
             raise OpticalFlowCalculationError(f"mask must be [>= {n_used},{H},{W},C], got {np.shape(mask)}")
+        return flow, m, n_used
+
+    def radlong_project_param(self, flow, mask, param, spacing, grad_f64, n_used, centroids, return_arrays=False):
+        """tf_radlong_project_param: the rad/long projection of OpticalFlowDataset's param field (param 0 velocity, 1 acceleration,
+        2 PWR) for frames [0, n_used), resident on the device for tf_radlong_hist / _select.  flow float16 or float32 [N,H,W,2],
+        mask bool or uint8 [>= n_used,H,W,C].  Returns (minmax float64 [4], nonzero int64 [n_used, 2], rad, long): rad / long are
+        float64 [n_used,H,W] with return_arrays, else None."""
+        flow, m, n_used = self._project_param_inputs(flow, mask, param, spacing, n_used)
+        N, H, W, _ = flow.shape
+        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(n_used, 2)
+        rad = np.empty((n_used, H, W), np.float64) if return_arrays else None
+        lon = np.empty((n_used, H, W), np.float64) if return_arrays else None
+        mm = np.zeros(4, np.float64)
+        nz = np.zeros((n_used, 2), np.int64)
+        _lib.check(self._L.tf_radlong_project_param(self._h, flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W,
+                                                    m.ctypes.data, m.shape[3], int(param), float(spacing), 1 if grad_f64 else 0,
+                                                    cent.ctypes.data, rad.ctypes.data if return_arrays else None,
+                                                    lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data),
+                   self._h, "tf_radlong_project_param")
+        return mm, nz, rad, lon
+
+    def polar_project_param(self, flow, mask, param, spacing, grad_f64, n_used, return_arrays=False):
+        """tf_polar_project_param: cv2.cartToPolar (analysis.cart_to_polar's arithmetic) of OpticalFlowDataset's param field (param 0
+        velocity, 1 acceleration, 2 PWR) for frames [0, n_used); magnitude and angle stay resident on the device for tf_radlong_hist /
+        _select (which 0 / 1).  flow float16 or float32 [N,H,W,2], mask bool or uint8 [>= n_used,H,W,C].  Returns (minmax float32 [4]
+        (mag min, max, ang min, max), nonzero int64 [n_used, 2] (non-zero mag, ang per frame), ang_mode float32 [n_used] (the angle
+        detector's per-frame mode, NaN if none), mag, ang): mag / ang are float32 [n_used,H,W] with return_arrays, else None.  May
+        be called while submitted studies are in flight on this engine."""
+        flow, m, n_used = self._project_param_inputs(flow, mask, param, spacing, n_used)
+        N, H, W, _ = flow.shape
         mag = np.empty((n_used, H, W), np.float32) if return_arrays else None
         ang = np.empty((n_used, H, W), np.float32) if return_arrays else None
         mm = np.zeros(4, np.float32)

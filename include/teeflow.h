@@ -49,8 +49,8 @@ extern "C" {
 
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
-                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param, tf_otsu_masks and
-                              tf_radlong_overlay */
+                              tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param, tf_otsu_masks,
+                              tf_radlong_overlay, tf_segmentor_input and tf_segmentor_classmap */
 
 enum {
     TF_OK = 0,
@@ -245,6 +245,33 @@ int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, int W, 
  * (frames, cleaned planes, output) plus, per chunk of frames, tf_clean_masks' 10 bytes per pixel and frame of labelling scratch, with
  * chunks of as many frames as fit in 512 MiB (at least one frame).  Host-synchronous. */
 int tf_otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* masks_out, double* thresholds_out);
+
+/* The frame glue around the SAM segmentor, `evaluate_1_slice` of the reference (calculate_optical_flow.py:47-88), on the device and
+ * exact.  The network itself stays the caller's (PyTorch); these two calls stand before and behind it.
+ *
+ * tf_segmentor_input: for each uint8 RGB frame, PIL's Image.resize((out_w, out_h), BILINEAR) -- its two passes with 22-bit fixed-point
+ * coefficients and the uint8 rounding between them -- then ToTensor and Normalize as a table look-up: d_out[n][c][y][x] =
+ * lut[c][resized[n][y][x][c]].  rgb: host uint8 [N][H][W][3].  lut: host float32 [3][256], the caller's ((b / 255) - mean[c]) / std[c]
+ * (tee_optical_flow_amd.masks.segmentor_lut builds it with the reference's torch expression).  d_out: DEVICE float32
+ * [N][3][out_h][out_w] on the handle's device, 16-byte aligned when out_w % 4 == 0.
+ * Runs on hip_stream (NULL: the handle's stream) and does NOT wait for its kernel: work the caller queues on that stream afterwards is
+ * ordered behind it, and d_out must not be read from another stream without such an order.  rgb and lut are copied before the call
+ * returns, so the caller may free them at once.  Device scratch and pinned staging, grown on demand and kept by the handle: 3 bytes per
+ * pixel and frame of the call plus the tables, each.
+ *
+ * tf_segmentor_classmap: class_map_out[n][y][x] = argmax over c of d_logits[n][c][iy[y]][ix[x]] with (iy, ix) the source indices of
+ * PIL's Image.resize((W, H), NEAREST) from h x w -- the reference's argmax, uint8 cast and NEAREST resize.  The argmax is torch's on
+ * the CPU: the lowest index of equal maxima, a NaN counts as the maximum and the first NaN wins.  d_logits: DEVICE float32
+ * [N][C][h][w], written by work queued on hip_stream (NULL: the handle's stream) or finished.  class_map_out: host uint8 [N][H][W].
+ * Host-synchronous.  Device scratch: N*H*W bytes and the two index tables.
+ *
+ * Both: TF_ERR_INVALID_ARG for a null pointer or a non-positive dimension; TF_ERR_UNSUPPORTED for C > 256 or a plane (H*W, out_h*out_w,
+ * h*w) of more than 2^31 - 1 elements; both before any GPU work.  They work on a DualTVL1 or a DeepFlow handle and never use a lane's
+ * stream, so they may be called while tf_submit_* jobs of the handle are in flight. */
+int tf_segmentor_input(tf_handle* h, const uint8_t* rgb, int N, int H, int W, int out_h, int out_w, const float* lut, float* d_out,
+                       void* hip_stream);
+int tf_segmentor_classmap(tf_handle* h, const float* d_logits, int N, int C, int h_in, int w_in, int H, int W, uint8_t* class_map_out,
+                          void* hip_stream);
 
 /* ---- radial / longitudinal projection + per-frame statistics of the reference's analysis step
  *      (optical_flow/analysis.py:89-212: calculate_comp_magnitude, calc_bidirectional_hist), float64, on the device.

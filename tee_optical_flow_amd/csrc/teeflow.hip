@@ -21,6 +21,8 @@
 #include "teeflow_centroid.hip.h"
 #include "teeflow_polar.hip.h"
 #include "teeflow_overlay.hip.h"
+#include "teeflow_segmentor.hip.h"
+#include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include <rccl/rccl.h>      // types and prototypes only: librccl is loaded with dlopen when a communicator is first asked for
 #include <dlfcn.h>
@@ -162,9 +164,14 @@ struct tf_handle : TfKnobs {
            PRE_AN_HIST, PRE_AN_SEL,                                               // tf_radlong_hist, tf_radlong_select
            PRE_OV_IDX, PRE_OV_ECHO, PRE_OV_OUT, PRE_OV_META,                      // tf_radlong_overlay
            PRE_WA_VALS, PRE_WA_CNT, PRE_WA_OFF, PRE_WA_SUM, PRE_WA_BG,            // WASE: compacted products, block counts / offsets, piece
-           PRE_COUNT };                                                           //   sums, per-flow backgrounds
+                                                                                  //   sums, per-flow backgrounds
+           PRE_SG_IN, PRE_SG_IDX, PRE_SG_MAP,                                     // tf_segmentor_input (tables, LUT, frames), tf_segmentor_classmap
+           PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
+    // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
+    // ([0]: upload done) and the device scratch ([1]: kernel done) of the last call may be written again
+    void* seg_stage = nullptr; size_t seg_stage_cap = 0; hipEvent_t seg_ev[2] = {};
     // ---- analysis session (row f1) ----
     double* an_rad = nullptr; double* an_lon = nullptr; int anN = 0, anH = 0, anW = 0;
     size_t an_cap = 0;           // doubles an_rad and an_lon each hold (grow_an_planes grows them, never shrinks)
@@ -1652,6 +1659,8 @@ TF_API void tf_destroy(tf_handle* h)
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     (void)tf_comm_destroy(h);
     for (auto& e : h->cev) if (e) (void)hipEventDestroy(e);
+    for (auto& ev : h->seg_ev) if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+    if (h->seg_stage) (void)hipHostFree(h->seg_stage);
     for (auto& b : h->pre) if (b.p) (void)hipFree(b.p);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;

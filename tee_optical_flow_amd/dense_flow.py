@@ -332,6 +332,64 @@ class DenseFlow:
                                          thr.ctypes.data if return_thresholds else None), self._h, "tf_otsu_masks")
         return (out.view(np.bool_), thr) if return_thresholds else out.view(np.bool_)
 
+    def _torch_stream(self, torch):
+        """(stream to hand the library, stream torch is on): torch's current stream of this engine's device -- or, where that is the
+        legacy default stream (handle 0, which the C ABI reads as "the handle's own"), a side stream ordered behind it."""
+        cur = torch.cuda.current_stream(self.device_id)
+        if cur.cuda_stream:
+            return cur, cur
+        side = getattr(self, "_seg_side_stream", None)
+        if side is None:
+            side = self._seg_side_stream = torch.cuda.Stream(self.device_id)
+        side.wait_stream(cur)
+        return side, cur
+
+    def segmentor_input(self, frames, out_size=(1024, 1024), out=None):
+        """evaluate_1_slice's model input (reference calculate_optical_flow.py:47-70) for a stack of frames, on the device and exact: RGB
+        frames uint8 [N,H,W,3] -> float32 torch tensor [N,3,out_h,out_w] on cuda:<device_id> = PIL's BILINEAR resize to out_size =
+        (out_h, out_w), ToTensor, ImageNet normalisation (masks.segmentor_lut).  `out`: a float32 contiguous tensor on that device with
+        room for the result is reused (its first N frames are returned).  Runs on torch's current stream and does not wait for it.
+        torch and the library must share one HIP runtime, i.e. torch was imported before the first engine of the process was made
+        (a process that made the engine first finds no GPU in torch; a model that sits on the GPU is proof of the right order)."""
+        import torch
+        from .masks import segmentor_lut
+        frames = _u8_image_stack(frames, "frames", 4)
+        if frames.shape[3] != 3:
+            raise OpticalFlowCalculationError(f"frames must be [N,H,W,3], got {frames.shape}")
+        N, H, W, _ = frames.shape
+        oh, ow = int(out_size[0]), int(out_size[1])
+        dev = torch.device("cuda", self.device_id)
+        if (out is not None and out.dtype == torch.float32 and out.device == dev and out.is_contiguous() and out.dim() == 4
+                and tuple(out.shape[1:]) == (3, oh, ow) and out.shape[0] >= N):
+            x = out[:N]
+        else:
+            x = torch.empty((max(N, 0), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=dev)
+        lut = segmentor_lut()
+        s, cur = self._torch_stream(torch)
+        _lib.check(self._L.tf_segmentor_input(self._h, frames.ctypes.data, N, H, W, oh, ow, lut.ctypes.data, x.data_ptr(),
+                                              C.c_void_p(s.cuda_stream)), self._h, "tf_segmentor_input")
+        if s is not cur:
+            x.record_stream(s)
+            cur.wait_stream(s)
+        return x
+
+    def segmentor_classmap(self, logits, size):
+        """evaluate_1_slice's way back (reference :84-88) for a stack of frames, on the device and exact: logits torch tensor [n,C,h,w] on
+        cuda:<device_id> (made float32 and contiguous with torch if they are not) -> class map uint8 [n,H,W], size = (H, W): torch's CPU
+        argmax over C (lowest index of equal maxima, NaN is the maximum), then PIL's NEAREST resize.  Waits for the result."""
+        import torch
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.device != torch.device("cuda", self.device_id):
+            raise OpticalFlowCalculationError(f"logits must be a torch tensor [n,C,h,w] on cuda:{self.device_id}")
+        if logits.dtype != torch.float32 or not logits.is_contiguous():
+            logits = logits.float().contiguous()
+        n, Cn, h, w = logits.shape
+        H, W = int(size[0]), int(size[1])
+        out = np.empty((max(n, 0), max(H, 0), max(W, 0)), np.uint8)
+        s, _ = self._torch_stream(torch)
+        _lib.check(self._L.tf_segmentor_classmap(self._h, logits.data_ptr(), n, Cn, h, w, H, W, out.ctypes.data, C.c_void_p(s.cuda_stream)),
+                   self._h, "tf_segmentor_classmap")
+        return out
+
     def av_centroids(self, masks):
         """calc_AV_centroid's per-frame step (analyze_optical_flow.py:202-232) on the device, exact: masks bool or uint8 [N,H,W,C]
         (C = 1 or 2; the set is channel 0 != 0, 8-connected) -> (centroids float64 [N,2] (row, col) of the largest component, areas

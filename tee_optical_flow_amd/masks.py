@@ -7,8 +7,10 @@ where skimage / torchvision are absent.  Mirrors /root/reference/optical_flow/ca
   :215-241  predict_movie      (modes 'A4C', 'RVIO_2class')
 moving_avg_mask / predict_movie_thres are pinned by tests/golden/reference_host_side.npz, clean_mask by
 tests/golden/reference_clean_mask.npz (host path here, device path DenseFlow.clean_masks), predict_movie_thres also by
-tests/golden/reference_otsu.npz (host path here, device path DenseFlow.otsu_masks).  Host-side glue, not a kernel:
-the segmentor stays stock PyTorch(-ROCm), as north_star says."""
+tests/golden/reference_otsu.npz (host path here, device path DenseFlow.otsu_masks).  The segmentor itself stays stock
+PyTorch(-ROCm), as north_star says; the frame glue around it (PIL's two resizes, the normalised tensor, the argmax) has a device path
+(DenseFlow.segmentor_input / segmentor_classmap, predict_movie's `engine=`) whose CPU statement is pil_resize_bilinear,
+pil_nearest_index and segmentor_lut below, pinned to PIL by tests/test_segmentor_glue_cpu.py and tests/golden/segmentor_glue.npz."""
 import numpy as np
 
 from .config import default_optical_flow_config
@@ -136,9 +138,132 @@ def evaluate_1_slice(frame, model):
     return np.asarray(pil_mask, dtype=np.uint8)
 
 
-def predict_movie(nparr, model, mode="A4C", verbose=False, config=None, *, engine=None):
-    """Reference :215-241: every frame through the segmentor, then clean_mask (on `engine`'s device when it has clean_masks)."""
+PIL_PRECISION_BITS = 22                 # Pillow's fixed point for 8-bit resampling: 32 - 8 - 2
+
+
+def pil_bilinear_coeffs(n_in, n_out):
+    """The tables of one pass of Image.resize(..., BILINEAR) along an axis of n_in samples resized to n_out:
+    (ksize, bounds int32 [n_out,2] = (first source index, taps), coeff int32 [n_out,ksize]).  Python floats are C doubles and the
+    operations come in Pillow's order, so the tables are Pillow's (csrc/pil_resample_tables.h is the same text in C++)."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    bounds = np.zeros((n_out, 2), np.int32)
+    coeff = np.zeros((n_out, ksize), np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), n_in) - xmin
+        w, ww = [], 0.0
+        for x in range(n):
+            a = abs((x + xmin - center + 0.5) / fs)
+            w.append(1.0 - a if a < 1.0 else 0.0)
+            ww += w[-1]
+        for x in range(n):
+            coeff[xx, x] = int(0.5 + (w[x] / ww if ww != 0.0 else w[x]) * (1 << PIL_PRECISION_BITS))
+        bounds[xx] = (xmin, n)
+    return ksize, bounds, coeff
+
+
+def _pil_bilinear_pass(img, n_out):
+    """one pass along axis 1 of a uint8 array [A, n_in, ...] -> uint8 [A, n_out, ...]"""
+    _, bounds, coeff = pil_bilinear_coeffs(img.shape[1], n_out)
+    out = np.empty((img.shape[0], n_out) + img.shape[2:], np.uint8)
+    for xx in range(n_out):
+        x0, n = bounds[xx]
+        acc = np.full((img.shape[0],) + img.shape[2:], 1 << (PIL_PRECISION_BITS - 1), np.int32)
+        for t in range(n):
+            acc += img[:, x0 + t].astype(np.int32) * coeff[xx, t]
+        out[:, xx] = np.clip(acc >> PIL_PRECISION_BITS, 0, 255)
+    return out
+
+
+def pil_resize_bilinear(img, size):
+    """np.asarray(Image.fromarray(img).resize((out_w, out_h), Image.BILINEAR)) for a uint8 image [H,W] or [H,W,C], bit for bit, with
+    `size` = (out_h, out_w) in numpy's order: the horizontal pass, a uint8 image, the vertical pass; an axis that keeps its length is
+    left alone, as Pillow does."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError(f"pil_resize_bilinear takes a uint8 image [H,W] or [H,W,C], got {img.dtype} {img.shape}")
+    out_h, out_w = int(size[0]), int(size[1])
+    if out_w != img.shape[1]:
+        img = _pil_bilinear_pass(img, out_w)
+    if out_h != img.shape[0]:
+        img = _pil_bilinear_pass(img.swapaxes(0, 1), out_h).swapaxes(0, 1)
+    return np.ascontiguousarray(img)
+
+
+def pil_nearest_index(n_in, n_out):
+    """Source index of every output index along one axis of Image.resize(..., NEAREST): int32 [n_out].  Pillow adds the step up as it
+    goes (a running double sum, not a product); the clamp to n_in - 1 never acts on the sizes checked and keeps a gather in bounds."""
+    a = n_in / n_out
+    xo = a * 0.5
+    idx = np.empty(n_out, np.int32)
+    for x in range(n_out):
+        idx[x] = min(int(xo), n_in - 1)
+        xo += a
+    return idx
+
+
+_SEGMENTOR_LUT = None
+
+
+def segmentor_lut():
+    """float32 [3,256]: the value evaluate_1_slice's tensor holds in channel c for byte b -- ((b / 255) - mean[c]) / std[c] in float32,
+    computed once with the very torch CPU expression evaluate_1_slice uses, so it is exact by construction."""
+    global _SEGMENTOR_LUT
+    if _SEGMENTOR_LUT is None:
+        import torch
+        x = torch.arange(256, dtype=torch.uint8).view(1, 256, 1).repeat(3, 1, 1).float().div(255.0)
+        mean = torch.tensor([0.485, 0.456, 0.406]).view(3, 1, 1)
+        std = torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
+        _SEGMENTOR_LUT = np.ascontiguousarray(((x - mean) / std).view(3, 256).numpy())
+    return _SEGMENTOR_LUT
+
+
+def _model_device(model):
+    try:
+        return next(model.parameters()).device
+    except (StopIteration, AttributeError):
+        return None
+
+
+def _predict_classmaps_device(nparr, model, engine, chunk):
+    """The frames' class maps uint8 [N,H,W] with the glue on `engine`'s device: per chunk one segmentor_input into a reused tensor, the
+    three sub-modules one frame at a time on views of it (exactly evaluate_1_slice's calls), one segmentor_classmap."""
+    import torch
+    N, H, W = nparr.shape[:3]
+    chunk = max(1, min(int(chunk), N))
+    x = None
+    maps = []
+    with torch.no_grad():
+        for f0 in range(0, N, chunk):
+            n = min(chunk, N - f0)
+            x = engine.segmentor_input(nparr[f0:f0 + n], (1024, 1024), out=x)
+            logits = []
+            for i in range(n):
+                emb = model.image_encoder(x[i:i + 1])
+                sparse, dense = model.prompt_encoder(points=None, boxes=None, masks=None)
+                pred, _ = model.mask_decoder(image_embeddings=emb, image_pe=model.prompt_encoder.get_dense_pe(),
+                                             sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense, multimask_output=True)
+                logits.append(pred)
+            maps.append(engine.segmentor_classmap(torch.cat(logits, dim=0), (H, W)))
+    return np.concatenate(maps)
+
+
+def predict_movie(nparr, model, mode="A4C", verbose=False, config=None, *, engine=None, chunk=16):
+    """Reference :215-241: every frame through the segmentor, then clean_mask (on `engine`'s device when it has clean_masks).
+    With an `engine` that has `segmentor_input` (DenseFlow), uint8 [N,H,W,3] frames and a model whose parameters sit on that engine's
+    GPU, the glue around the model -- both resizes, the normalised tensor, the argmax -- runs on the device too, `chunk` frames per
+    call (exact: tf_segmentor_input, tf_segmentor_classmap); in every other case evaluate_1_slice runs frame by frame on the host."""
     if config is None:
         config = default_optical_flow_config()
-    preds = [evaluate_1_slice(nparr[i], model) for i in range(nparr.shape[0])]
-    return clean_mask(np.stack(preds), mode, verbose, config=config, engine=engine)
+    arr = np.asarray(nparr)
+    dev = _model_device(model)
+    if (engine is not None and hasattr(engine, "segmentor_input") and arr.dtype == np.uint8 and arr.ndim == 4 and arr.shape[3] == 3
+            and min(arr.shape[:3]) >= 1 and dev is not None and dev.type == "cuda" and dev.index == engine.device_id):   # (a bare "cuda": host path)
+        preds = _predict_classmaps_device(arr, model, engine, chunk)
+    else:
+        preds = np.stack([evaluate_1_slice(nparr[i], model) for i in range(nparr.shape[0])])
+    return clean_mask(preds, mode, verbose, config=config, engine=engine)

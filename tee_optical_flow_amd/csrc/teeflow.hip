@@ -16,6 +16,7 @@
 #include "teeflow_analysis.hip.h"
 #include "teeflow_wase.hip.h"
 #include "teeflow_saliency.hip.h"
+#include "teeflow_ccl.hip.h"
 #include "teeflow_masks.hip.h"
 #include "teeflow_otsu.hip.h"
 #include "teeflow_centroid.hip.h"
@@ -156,9 +157,11 @@ struct tf_handle : TfKnobs {
     // scratch is one of these grow-only slots, freed with the handle (teeflow_tail.hip.h) ----
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
-           PRE_MK_CLS, PRE_MK_PAR, PRE_MK_AUX, PRE_MK_LR, PRE_MK_OUT, PRE_MK_META,   // tf_clean_masks (PAR, AUX, LR also tf_otsu_masks)
-           PRE_OT_RGB, PRE_OT_CLEAN, PRE_OT_OUT, PRE_OT_META,                        // tf_otsu_masks
-           PRE_CT_MASK, PRE_CT_PAR, PRE_CT_LR, PRE_CT_AREA, PRE_CT_SUM, PRE_CT_OUT,  // tf_av_centroids
+           PRE_LB_PAR, PRE_LB_AUX, PRE_LB_LR,                                     // the labelling's parents, per-root flags / sizes / areas and
+                                                                                  //   tile-local roots: tf_clean_masks, tf_otsu_masks, tf_av_centroids
+           PRE_MK_CLS, PRE_MK_OUT, PRE_MK_META,                                   // tf_clean_masks
+           PRE_OT_RGB, PRE_OT_CLEAN, PRE_OT_OUT, PRE_OT_META,                     // tf_otsu_masks
+           PRE_CT_MASK, PRE_CT_SUM, PRE_CT_OUT,                                   // tf_av_centroids
            PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // the projections' uploads (also tf_wase_compensate's) and
            PRE_PO_META, PRE_PO_OUT,                                               //   meta words: rad/long's, polar's
            PRE_AN_HIST, PRE_AN_SEL,                                               // tf_radlong_hist, tf_radlong_select

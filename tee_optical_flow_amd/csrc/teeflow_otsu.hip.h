@@ -3,7 +3,7 @@
 //   g      = rgb2gray(frame)                      float64 luma, luma_f64 of teeflow_kernels.hip.h (never stored: recomputed from the bytes)
 //   thr    = skimage.filters.threshold_otsu(g)    256-bin np.histogram over [min g, max g], bin centres, first maximum of var12
 //   m      = g > thr
-//   clean  = remove_small_objects(binary_fill_holes(m), min_size)     the labelling passes of teeflow_masks.hip.h, the set from LumaNotAbove
+//   clean  = remove_small_objects(binary_fill_holes(m), min_size)     the two labellings of clean_mask, the first set from LumaNotAbove
 // and over the stack of cleaned planes, last, moving_avg_mask with its defaults; the store duplicates the channel (0x0101 per pixel).
 //   k_cond_minmax   (teeflow_kernels.hip.h) per-frame min / max of g
 //   k_otsu_hist     np.histogram's index rule, counts privatised in LDS per wave, one global atomic add per non-empty bin and block
@@ -20,7 +20,7 @@ namespace otsu {
 
 constexpr int NBINS = 256;
 
-// PASS 0 set of k_mask_local: the background of m = g > thr[frame]; plane q of the chunk is frame f0 + q
+// the first labelling's set (k_ccl_local): the background of m = g > thr[frame]; plane q of the chunk is frame f0 + q
 struct LumaNotAbove {
     const uint8_t* __restrict__ rgb; const double* __restrict__ thr;
     int f0; size_t HW;

@@ -226,26 +226,41 @@ TF_API int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, 
 }
 
 namespace {
-// The labelling passes tf_clean_masks and tf_otsu_masks share, on `planes` planes of H x W whose set is `set`: fill holes, then small
-// objects.  Leaves each pixel's root in dpar and each root's component size in daux (10 B of scratch per pixel and plane).
-template <typename Set>
-int label_planes(tf_handle* h, const Set& set, size_t planes, int H, int W, uint32_t* dpar, uint32_t* daux, uint16_t* dlr, unsigned* derr)
+// One labelling of `planes` planes of H x W (teeflow_ccl.hip.h): the set's components, CONN-connected, each pixel's root in dpar and
+// what `acc` collects per root in its totals.  dlr is written only with LR and read only by an accumulator that counts per tile.
+// The totals are zeroed after the local kernel: the masks' second set reads the first labelling's flags from the words its sizes go to.
+template <int CONN, bool LR, typename Set, typename Acc>
+int label_planes(tf_handle* h, const Set& set, const Acc& acc, size_t planes, int H, int W, uint32_t* dpar, uint16_t* dlr, unsigned* derr)
 {
-    using namespace msk;
+    using namespace ccl;
     const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
     const dim3 g(tiles, (unsigned)planes), blk(256);
-    const size_t aux_bytes = planes * H * W * 4;
     const hipStream_t s = h->stream;
-    // fill holes: components of the set's background; those with a pixel on the border keep their flag in aux
-    HIPC(h, hipMemsetAsync(daux, 0, aux_bytes, s));
-    hipLaunchKernelGGL((k_mask_local<0, Set>), g, blk, 0, s, set, dpar, daux, dlr, H, W, tiles_x, derr);
-    hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-    hipLaunchKernelGGL(k_mask_flatten<0>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
-    // small objects: components of the filled mask, their sizes counted into aux
-    hipLaunchKernelGGL((k_mask_local<1, NoSet>), g, blk, 0, s, NoSet{}, dpar, daux, dlr, H, W, tiles_x, derr);
-    HIPC(h, hipMemsetAsync(daux, 0, aux_bytes, s));
-    hipLaunchKernelGGL(k_mask_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-    hipLaunchKernelGGL(k_mask_flatten<1>, g, blk, 0, s, dpar, daux, dlr, H, W, tiles_x);
+    hipLaunchKernelGGL((k_ccl_local<CONN, LR, Set>), g, blk, 0, s, set, dpar, dlr, H, W, tiles_x, derr);
+    HIPC(h, acc.clear(planes * H * W, s));
+    hipLaunchKernelGGL(k_ccl_merge<CONN>, g, blk, 0, s, dpar, H, W, tiles_x, derr);
+    hipLaunchKernelGGL(k_ccl_flatten<Acc>, g, blk, 0, s, dpar, dlr, acc, H, W, tiles_x);
+    return TF_OK;
+}
+
+// The two labellings tf_clean_masks and tf_otsu_masks share, on planes whose background is `set`: fill holes (components of the
+// background; those with a pixel on the border keep their flag in daux), then small objects (components of the filled mask, their
+// sizes counted into daux).  Leaves each pixel's root in dpar and each root's component size in daux (10 B of scratch per pixel and plane).
+template <typename Set>
+int fill_and_size_planes(tf_handle* h, const Set& set, size_t planes, int H, int W, uint32_t* dpar, uint32_t* daux, uint16_t* dlr, unsigned* derr)
+{
+    int rc = label_planes<4, false>(h, set, msk::BorderFlag{daux}, planes, H, W, dpar, dlr, derr);
+    if (rc) return rc;
+    return label_planes<4, true>(h, msk::FilledByLabels{dpar, daux, (size_t)H * W}, msk::ComponentSize{daux}, planes, H, W, dpar, dlr, derr);
+}
+
+// the labelling's error word, read back behind what the caller has queued on the stream; waits for the stream
+int label_errors(tf_handle* h, const unsigned* derr, const char* who)
+{
+    unsigned e = 0;
+    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (e) return fail(h, TF_ERR_HIP, "%s: a union-find loop ran out of its bound (code %u)", who, e);
     return TF_OK;
 }
 
@@ -261,9 +276,9 @@ int clean_masks(tf_handle* h, const uint8_t* cmap, int N, int H, int W, const ui
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
     auto* dcls = pre.get<uint8_t>(tf_handle::PRE_MK_CLS, (size_t)N * HW);
-    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_MK_PAR, (size_t)L * nf * HW);
-    auto* daux = pre.get<uint32_t>(tf_handle::PRE_MK_AUX, (size_t)L * nf * HW);
-    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_MK_LR, (size_t)L * nf * HW);
+    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_LB_PAR, (size_t)L * nf * HW);
+    auto* daux = pre.get<uint32_t>(tf_handle::PRE_LB_AUX, (size_t)L * nf * HW);
+    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_LB_LR, (size_t)L * nf * HW);
     auto* dout = pre.get<uint16_t>(tf_handle::PRE_MK_OUT, (size_t)(L + 1) * nf * HW);
     auto* meta = pre.get<uint8_t>(tf_handle::PRE_MK_META, 64 + (size_t)L);   // [0, 4): error word, [64, 64 + L): class ids
     if (pre.rc) return pre.rc;
@@ -274,16 +289,14 @@ int clean_masks(tf_handle* h, const uint8_t* cmap, int N, int H, int W, const ui
     HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
     for (int f0 = 0; f0 < N; f0 += nf) {
         const int n = std::min(nf, N - f0);
-        int rc = label_planes(h, ClassWindowBackground{dcls, meta + 64, N, f0, n, HW}, (size_t)L * n, H, W, dpar, daux, dlr, derr);
+        int rc = fill_and_size_planes(h, ClassWindowBackground{dcls, meta + 64, N, f0, n, HW}, (size_t)L * n, H, W, dpar, daux, dlr, derr);
         if (rc) return rc;
         hipLaunchKernelGGL(k_mask_store, dim3((unsigned)((HW + 255) / 256), (unsigned)n), dim3(256), 0, s, dpar, daux, L, n, HW, min_size, dout);
         HIPC(h, hipGetLastError());
         for (int l = 0; l <= L; ++l)                           // label l's frames of this chunk are contiguous in masks_out
             HIPC(h, hipMemcpyAsync(out + ((size_t)l * N + f0) * HW * 2, dout + (size_t)l * n * HW, (size_t)n * HW * 2, hipMemcpyDeviceToHost, s));
-        unsigned e = 0;
-        HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
-        HIPC(h, hipStreamSynchronize(s));
-        if (e) return fail(h, TF_ERR_HIP, "tf_clean_masks: a union-find loop ran out of its bound (code %u)", e);
+        rc = label_errors(h, derr, "tf_clean_masks");
+        if (rc) return rc;
     }
     return TF_OK;
 }
@@ -298,8 +311,8 @@ TF_API int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, 
 
 namespace {
 // tf_otsu_masks: the frames, one byte per pixel of the cleaned planes and the output stay on the device for the whole study (6 B per
-// pixel and frame); the labelling scratch (10 B per pixel and frame: parents, flags / sizes, tile-local roots) is tf_clean_masks' own,
-// in chunks of as many frames as fit in MASK_CHUNK_BYTES.  The temporal window runs over all cleaned planes after the last chunk.
+// pixel and frame); the labelling scratch (10 B per pixel and frame: parents, flags / sizes, tile-local roots) is the PRE_LB_* slots
+// that every labelling call uses, in chunks of as many frames as fit in MASK_CHUNK_BYTES.  The temporal window runs over all cleaned planes after the last chunk.
 int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* out, double* thr_out)
 {
     const size_t HW = (size_t)H * W;
@@ -312,9 +325,9 @@ int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long 
     auto* dclean = pre.get<uint8_t>(tf_handle::PRE_OT_CLEAN, (size_t)N * HW);
     auto* dout = pre.get<uint16_t>(tf_handle::PRE_OT_OUT, (size_t)N * HW);
     auto* meta = pre.get<uint8_t>(tf_handle::PRE_OT_META, meta_bytes);
-    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_MK_PAR, (size_t)nf * HW);
-    auto* daux = pre.get<uint32_t>(tf_handle::PRE_MK_AUX, (size_t)nf * HW);
-    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_MK_LR, (size_t)nf * HW);
+    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_LB_PAR, (size_t)nf * HW);
+    auto* daux = pre.get<uint32_t>(tf_handle::PRE_LB_AUX, (size_t)nf * HW);
+    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_LB_LR, (size_t)nf * HW);
     if (pre.rc) return pre.rc;
     unsigned* derr = (unsigned*)meta;
     u64* mm = (u64*)(meta + off_mm);
@@ -332,20 +345,16 @@ int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long 
     hipLaunchKernelGGL(otsu::k_otsu_thr, dim3(N), blk, 0, s, mm, dhist, dthr);
     for (int f0 = 0; f0 < N; f0 += nf) {                       // one plane per frame
         const int n = std::min(nf, N - f0);
-        int rc = label_planes(h, otsu::LumaNotAbove{drgb, dthr, f0, HW}, (size_t)n, H, W, dpar, daux, dlr, derr);
+        int rc = fill_and_size_planes(h, otsu::LumaNotAbove{drgb, dthr, f0, HW}, (size_t)n, H, W, dpar, daux, dlr, derr);
         if (rc) return rc;
         hipLaunchKernelGGL(otsu::k_otsu_keep, dim3(gx, (unsigned)n), blk, 0, s, dpar, daux, HW, min_size, dclean + (size_t)f0 * HW);
         HIPC(h, hipGetLastError());
     }
     hipLaunchKernelGGL(otsu::k_otsu_window, dim3(gx, N), blk, 0, s, dclean, N, HW, dout);
     HIPC(h, hipGetLastError());
-    unsigned e = 0;
-    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
     HIPC(h, hipMemcpyAsync(out, dout, (size_t)N * HW * 2, hipMemcpyDeviceToHost, s));
     if (thr_out) HIPC(h, hipMemcpyAsync(thr_out, dthr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    if (e) return fail(h, TF_ERR_HIP, "tf_otsu_masks: a union-find loop ran out of its bound (code %u)", e);
-    return TF_OK;
+    return label_errors(h, derr, "tf_otsu_masks");
 }
 }  // namespace
 
@@ -596,21 +605,20 @@ TF_API int tf_radlong_select(tf_handle* h, int which, const long long* ranks, do
 }
 
 namespace {
-// tf_av_centroids: frames go through in chunks so that the per-chunk scratch (26 B per pixel + the mask bytes) stays within
-// MASK_CHUNK_BYTES whatever the study's length
+// tf_av_centroids: frames go through in chunks so that the per-chunk scratch (26 B per pixel + the mask bytes: 10 B of them the
+// PRE_LB_* slots every labelling call uses, the areas in the sizes' place) stays within MASK_CHUNK_BYTES whatever the study's length
 int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* cent_out, long long* area_out)
 {
     using namespace cen;
     const size_t HW = (size_t)H * W;
     if (HW > 0x7fffffffu) return fail(h, TF_ERR_UNSUPPORTED, "tf_av_centroids: at most 2^31 - 1 pixels per frame");
     const int nf = chunk_frames(HW * (26 + (size_t)C), N);     // frames of a chunk are grid.y
-    const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
     auto* dm = pre.get<uint8_t>(tf_handle::PRE_CT_MASK, (size_t)nf * HW * C);
-    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_CT_PAR, (size_t)nf * HW);
-    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_CT_LR, (size_t)nf * HW);
-    auto* darea = pre.get<uint32_t>(tf_handle::PRE_CT_AREA, (size_t)nf * HW);
+    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_LB_PAR, (size_t)nf * HW);
+    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_LB_LR, (size_t)nf * HW);
+    auto* darea = pre.get<uint32_t>(tf_handle::PRE_LB_AUX, (size_t)nf * HW);
     auto* dsum = pre.get<unsigned long long>(tf_handle::PRE_CT_SUM, (size_t)nf * HW * 2);
     auto* out = pre.get<uint8_t>(tf_handle::PRE_CT_OUT, 64 + (size_t)N * 24);   // [0, 64): error word, then centroids [N][2] f64, then areas [N] i64
     if (pre.rc) return pre.rc;
@@ -621,23 +629,15 @@ int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C,
     HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
     for (int f0 = 0; f0 < N; f0 += nf) {
         const int n = std::min(nf, N - f0);
-        const dim3 g(tiles, (unsigned)n), blk(256);
         HIPC(h, hipMemcpyAsync(dm, masks + (size_t)f0 * HW * C, (size_t)n * HW * C, hipMemcpyHostToDevice, s));
-        HIPC(h, hipMemsetAsync(darea, 0, (size_t)n * HW * 4, s));
-        HIPC(h, hipMemsetAsync(dsum, 0, (size_t)n * HW * 16, s));
-        hipLaunchKernelGGL(k_cent_local, g, blk, 0, s, dm, C, dpar, dlr, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_cent_merge, g, blk, 0, s, dpar, H, W, tiles_x, derr);
-        hipLaunchKernelGGL(k_cent_flatten, g, blk, 0, s, dpar, dlr, darea, dsum, H, W, tiles_x);
-        hipLaunchKernelGGL(k_cent_pick, dim3((unsigned)n), blk, 0, s, dpar, darea, dsum, HW, dcent + 2 * (size_t)f0, dar + f0);
+        int rc = label_planes<8, true>(h, ChannelZeroSet{dm, C, HW}, AreaAndSums{darea, dsum}, (size_t)n, H, W, dpar, dlr, derr);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_cent_pick, dim3((unsigned)n), dim3(256), 0, s, dpar, darea, dsum, HW, dcent + 2 * (size_t)f0, dar + f0);
         HIPC(h, hipGetLastError());
     }
-    unsigned e = 0;
-    HIPC(h, hipMemcpyAsync(&e, derr, sizeof e, hipMemcpyDeviceToHost, s));
     HIPC(h, hipMemcpyAsync(cent_out, dcent, (size_t)N * 16, hipMemcpyDeviceToHost, s));
     HIPC(h, hipMemcpyAsync(area_out, dar, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
-    if (e) return fail(h, TF_ERR_HIP, "tf_av_centroids: a union-find loop ran out of its bound (code %u)", e);
-    return TF_OK;
+    return label_errors(h, derr, "tf_av_centroids");
 }
 
 // calls f(param, flow element, gradient element) with values of the static types that the three run-time codes select: the

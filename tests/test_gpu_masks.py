@@ -1,11 +1,13 @@
 """clean_mask on the device (tf_clean_masks, DenseFlow.clean_masks): byte-equal to the reference's own clean_mask
-(tests/golden/reference_clean_mask.npz) and to the host path at study sizes, beside submitted solves on the same engine, and
-through process_video's segmentor branch."""
+(tests/golden/reference_clean_mask.npz) and to the host path at study sizes, beside submitted solves on the same engine,
+through process_video's segmentor branch, and in turns with the other calls that label in the same device scratch."""
 import numpy as np
 import pytest
 
-from tee_optical_flow_amd import masks
+from tee_optical_flow_amd import analysis, masks
+from tests.labelling_cases import stress_frames
 from tests.test_masks_cpu import _Cfg, fixture_cases
+from tests.test_otsu_cpu import fixture_cases as otsu_fixture_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +49,38 @@ def test_device_equals_reference_fixture(engine, case):
     planes = engine.clean_masks(arr, list(masks._MODE_LABELS[mode].values()), min_size)
     assert planes.shape == (len(keys),) + arr.shape + (2,)
     assert np.array_equal(planes.view(np.uint8)[..., 0], np.stack([ref[k] for k in keys]).astype(np.uint8))   # bytes 0 / 1
+
+
+def test_calls_that_share_the_labelling_scratch_do_not_see_each_other(engine):
+    """tf_av_centroids, tf_clean_masks and tf_otsu_masks label in the same parents, sizes / areas and tile-local roots of the handle.
+    Large, small, large on one engine: a smaller call finds another call's stale words beyond and inside its own extent."""
+    frames = stress_frames()
+    mask_cases = {c[0]: c for c in fixture_cases()}
+
+    def centroids(fr, flipped=False):
+        m = np.repeat(fr[None, :, :, None], 2, axis=3)
+        m = np.concatenate([m, m[:, ::-1, ::-1]], axis=0) if flipped else m
+        cent, area = engine.av_centroids(m)
+        for f in range(m.shape[0]):
+            want = analysis._largest_component(m[f, :, :, 0])
+            assert (area[f] == 0) if want is None else (area[f] == want[1] and tuple(cent[f]) == want[0]), f
+
+    def clean(name):
+        _, arr, mode, min_size, keys, ref = mask_cases[name]
+        got = masks.clean_mask(arr, mode, config=_Cfg(min_size), engine=engine)
+        assert list(got) == keys
+        for k in keys:
+            assert np.array_equal(got[k][..., 0], ref[k]) and np.array_equal(got[k][..., 1], ref[k]), (name, k)
+
+    centroids(frames["snake"], flipped=True)                                  # 2 x 61 x 200
+    clean("hard_checker1_min5")                                               # 3 x 150 x 170, two labels
+    centroids(frames["single_pixel"])                                         # 37 x 70
+    centroids(frames["empty"])                                                # 20 x 20
+    _, rgb, min_size, ref, thr = min(otsu_fixture_cases(), key=lambda c: c[1].size)
+    got, got_thr = engine.otsu_masks(rgb, min_size, return_thresholds=True)
+    assert np.array_equal(got_thr, thr) and np.array_equal(got[..., 0], ref) and np.array_equal(got[..., 1], ref)
+    clean("rvio_9x37x53_min5")
+    centroids(frames["staircase"])                                            # 70 x 200
 
 
 @pytest.mark.parametrize("N,H,W,mode,min_size", [

@@ -9,6 +9,7 @@ import pytest
 from scipy import ndimage
 
 from tee_optical_flow_amd import analysis as A
+from tests.labelling_cases import stress_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -119,40 +120,8 @@ def test_gradient_edges_and_n_used_equal_to_n(engine):
                 assert np.array_equal(dev["rad_arr"], host["rad_arr"]) and np.array_equal(dev["long_arr"], host["long_arr"])
 
 
-def _stress_frames():
-    out = []
-    out.append(np.ones((40, 130), bool))                                       # full-frame foreground
-    one = np.zeros((37, 70), bool); one[20, 66] = True; out.append(one)        # a single pixel in a ragged tile
-    yy, xx = np.mgrid[:50, :140]
-    out.append((yy + xx) % 2 == 0)                                            # checkerboard: one component
-    snake = np.zeros((61, 200), bool)                                         # a one-pixel-wide snake through many tiles
-    for r in range(0, 61, 4):
-        snake[r, 1:199] = True
-        snake[r:r + 4, 198 if (r // 4) % 2 == 0 else 1] = True
-    snake[60:, :] = False
-    snake[59, :] = False
-    out.append(snake)
-    stair = np.zeros((70, 200), bool)                                         # diagonal staircases across tile corners
-    for k in range(70):
-        stair[k, 64 - 16 + k] = True
-        stair[69 - k, 150 - k] = True
-    out.append(stair)
-    anti = np.zeros((48, 192), bool)                                          # pixels that meet only at tile corners
-    for ty in range(1, 3):
-        for tx in range(1, 3):
-            anti[16 * ty - 1, 64 * tx - 1] = anti[16 * ty, 64 * tx] = True
-            anti[16 * ty - 1, 64 * tx] = anti[16 * ty, 64 * tx - 1] = True
-    anti[15, 63] = anti[16, 64] = anti[16, 63] = False
-    out.append(anti)
-    rng = np.random.default_rng(3)
-    for H, W in ((1, 300), (300, 1), (1, 1), (17, 65), (129, 63), (100, 257)):
-        out.append(rng.random((H, W)) < 0.45)
-    out.append(np.zeros((20, 20), bool))
-    return out
-
-
 def test_labelling_stress_equals_scipy(engine):
-    for j, fr in enumerate(_stress_frames()):
+    for j, fr in stress_frames().items():
         H, W = fr.shape
         for C in (1, 2):
             m = np.repeat(fr[None, :, :, None], C, axis=3)

@@ -2,7 +2,8 @@
 """The consumer's rad/long call of one 65-frame study, calculate_3dhist_radlong(ds, param) for velocity, acceleration and PWR with the
 AV centroids computed once and shared: on the host (numpy / scipy, the same work as the reference's numpy / skimage path) against the
 device (tf_av_centroids + tf_radlong_project_param + tf_radlong_hist / _select, host arrays in and out, transfers included), at
-512x512 and 600x800, float16 flow as the study file holds it.  Alternates the two after a warm-up and checks bit-equality.
+512x512 and 600x800, float16 flow as the study file holds it.  Alternates the two after a warm-up and checks bit-equality; the
+engine's av_centroids call is also timed on its own (centroids_device_ms: it is a small share of device_ms).
 Prints one JSON line (and writes it to --out when given).
     python tools/study_stats_bench.py [--reps 3] [--out profiles/r07_study_stats.json]"""
 import argparse
@@ -62,9 +63,12 @@ def main():
             t = time.perf_counter(); h = run(st, None); th.append(time.perf_counter() - t)
             t = time.perf_counter(); d = run(st, eng); td.append(time.perf_counter() - t)
             equal = equal and same(h, d)
+        tc = []
+        for _ in range(a.reps):
+            t = time.perf_counter(); eng.av_centroids(av[:st.nframes]); tc.append(time.perf_counter() - t)
         mh, md = float(np.median(th)) * 1e3, float(np.median(td)) * 1e3
         res["sizes"][f"{H}x{W}"] = {"host_ms": round(mh, 1), "device_ms": round(md, 1), "device_ms_min": round(min(td) * 1e3, 1),
-                                    "device_ms_max": round(max(td) * 1e3, 1), "speedup": round(mh / md, 1), "bit_equal": bool(equal)}
+                                    "device_ms_max": round(max(td) * 1e3, 1), "centroids_device_ms": round(float(np.median(tc)) * 1e3, 2), "speedup": round(mh / md, 1), "bit_equal": bool(equal)}
     eng.close()
     line = json.dumps(res)
     print(line, flush=True)

@@ -16,11 +16,10 @@
 //   * np.mean divides in float64 (float32 sum / intp count) and casts the quotient to float32.
 #pragma once
 #include "teeflow_kernels.hip.h"
+#include "wase_tree.h"
 
 #define WASE_CHUNK 2048        // elements per compaction block (256 threads x 8 consecutive elements)
 #define NP_BUFSIZE 8192        // np.getbufsize(): elements per inner-loop call of the reduction
-#define NP_PW_BLOCK 128        // numpy's PW_BLOCKSIZE
-#define WASE_MAX_LEAVES 128    // a piece of <= 8192 elements has at most 8192/64 leaves
 
 __device__ __forceinline__ float wase_product(float f, uint8_t m) { return f * (m ? 1.0f : 0.0f); }
 
@@ -103,10 +102,9 @@ __global__ __launch_bounds__(256) void k_wase_scatter(const float* __restrict__ 
         if (v[i] != 0.0f) a[p++] = v[i];
 }
 
-TF_HD inline int np_pw_split(int n) { int n2 = n / 2; return n2 - n2 % 8; }
-
 // pass 4: numpy's pairwise sum of every 8192-element piece of the compacted array.  Thread 0 lists the leaves of the
-// piece's split tree, 8-lane groups sum the leaves (one lane per strided accumulator), thread 0 adds them up the tree.
+// piece's split tree, 8-lane groups sum the leaves (one lane per strided accumulator), thread 0 adds them up the tree
+// (both walks: wase_tree.h).
 __global__ __launch_bounds__(512) void k_wase_piece_sums(const float* __restrict__ a, const u64* __restrict__ total, float* __restrict__ s)
 {
     __shared__ int loff[WASE_MAX_LEAVES], ln[WASE_MAX_LEAVES];
@@ -117,19 +115,7 @@ __global__ __launch_bounds__(512) void k_wase_piece_sums(const float* __restrict
     if (p0 >= M) return;                                              // block-uniform
     const int n = (int)(M - p0 < NP_BUFSIZE ? M - p0 : NP_BUFSIZE);
     const float* piece = a + p0;
-    if (threadIdx.x == 0) {
-        int so[16], sn[16], sp = 0, nl = 0;
-        so[0] = 0; sn[0] = n; sp = 1;
-        while (sp > 0) {
-            --sp;
-            const int o = so[sp], m = sn[sp];
-            if (m <= NP_PW_BLOCK) { loff[nl] = o; ln[nl] = m; ++nl; continue; }
-            const int n2 = np_pw_split(m);
-            so[sp] = o + n2; sn[sp] = m - n2; ++sp;                   // right child below the left one: left is listed first
-            so[sp] = o; sn[sp] = n2; ++sp;
-        }
-        nleaves = nl;
-    }
+    if (threadIdx.x == 0) nleaves = wase_tree_leaves(n, loff, ln);
     __syncthreads();
     const int grp = threadIdx.x >> 3, j = threadIdx.x & 7;
     for (int l0 = 0; l0 < nleaves; l0 += 64) {                        // every lane takes part in the shuffles
@@ -153,26 +139,7 @@ __global__ __launch_bounds__(512) void k_wase_piece_sums(const float* __restrict
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        // post-order walk of the same tree; leaves are consumed left to right
-        int sn[16], st[16], sp = 0, k = 0;
-        float sl[16];
-        float val = 0.f;
-        bool have = false;
-        sn[0] = n; st[0] = 0; sp = 1;
-        while (sp > 0) {
-            const int t = sp - 1;
-            if (have) {                                               // a child of the node on top has just been evaluated
-                have = false;
-                if (st[t] == 1) { sl[t] = val; st[t] = 2; sn[sp] = sn[t] - np_pw_split(sn[t]); st[sp] = 0; ++sp; }
-                else { val = sl[t] + val; have = true; --sp; }
-                continue;
-            }
-            if (sn[t] <= NP_PW_BLOCK) { val = lsum[k++]; have = true; --sp; continue; }
-            st[t] = 1; sn[sp] = np_pw_split(sn[t]); st[sp] = 0; ++sp;
-        }
-        s[blockIdx.x] = val;
-    }
+    if (threadIdx.x == 0) s[blockIdx.x] = wase_tree_combine(n, lsum);   // post-order walk of the same tree
 }
 
 // pass 5: running float32 total over the pieces, mean in float64, cast to float32 (np.mean of an empty selection: nan)

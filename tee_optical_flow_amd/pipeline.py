@@ -14,7 +14,10 @@ Reference: /root/reference/optical_flow/calculate_optical_flow.py
 import logging
 import os
 import traceback
+from collections import deque
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import suppress
+from functools import partial
 
 import numpy as np
 
@@ -330,17 +333,16 @@ def _shm_room(nbytes):
 def _shm_put(arr):
     """ndarray -> ("shm", name, shape, dtype) with the data in a new shared-memory block (this process's mapping is closed, the block
     stays), or the array itself when it is small / there is no room."""
-    from multiprocessing import shared_memory
     arr = np.ascontiguousarray(arr)
-    if arr.nbytes < _SHM_MIN or not _shm_room(arr.nbytes):
+    view, blk, desc = _shm_new(arr.shape, arr.dtype)
+    if blk is None:
         return arr
-    blk = shared_memory.SharedMemory(create=True, size=arr.nbytes)
     try:
-        np.ndarray(arr.shape, arr.dtype, buffer=blk.buf)[...] = arr
+        view[...] = arr
     except BaseException:
-        blk.close(); blk.unlink()
+        _shm_release([blk], unlink=True)
         raise
-    desc = ("shm", blk.name, arr.shape, arr.dtype.str)
+    del view
     blk.close()
     return desc
 
@@ -373,15 +375,11 @@ def _shm_get(x, blocks):
 
 def _shm_release(blocks, unlink):
     for blk in blocks:
-        try:
+        with suppress(OSError, BufferError):                 # a view is still alive somewhere: the mapping goes with it
             blk.close()
-        except (OSError, BufferError):                       # a view is still alive somewhere: the mapping goes with it
-            pass
         if unlink:
-            try:
+            with suppress(OSError):
                 blk.unlink()                                  # by name: works whatever is still mapped
-            except OSError:
-                pass
     del blocks[:]
 
 
@@ -390,11 +388,8 @@ def _shm_unlink_names(descs):
     from multiprocessing import shared_memory
     for d in descs:
         if _is_shm(d):
-            try:
-                blk = shared_memory.SharedMemory(name=d[1])
-                blk.close(); blk.unlink()
-            except OSError:
-                pass
+            with suppress(OSError):
+                _shm_release([shared_memory.SharedMemory(name=d[1])], unlink=True)
 
 
 def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True):
@@ -447,20 +442,23 @@ class StudyWorkers:
     """Worker processes for process_folder's reader/mask and deflate/write stages, for callers that hold a flow model (or a segmentor on
     the GPU) across many calls: create this object BEFORE anything in the process touches the GPU -- starting a process from a
     GPU-initialised one is not safe on ROCm hosts -- and hand it to process_folder(workers=...).  process_folder(workers="process" /
-    "auto") makes its own for one call."""
+    "auto") makes its own for one call, the same way: this class is the only place where worker processes are started."""
 
     def __init__(self, n_readers=None, n_writers=None):
         import multiprocessing as mp
+        from concurrent.futures import ProcessPoolExecutor
         n_readers = _default_stage_workers() if n_readers is None else n_readers
         n_writers = _default_stage_workers() if n_writers is None else n_writers
-        from concurrent.futures import ProcessPoolExecutor
         ctx = mp.get_context("spawn")
         self.n_readers, self.n_writers = max(1, n_readers), max(1, n_writers)
         self.readers = ProcessPoolExecutor(self.n_readers, mp_context=ctx)
         self.writers = ProcessPoolExecutor(self.n_writers, mp_context=ctx)
-        # make the pools start their processes now (they are created lazily on first submit)
-        for f in [self.readers.submit(os.getpid) for _ in range(self.n_readers)] + [self.writers.submit(os.getpid) for _ in range(self.n_writers)]:
-            f.result()
+        try:                                              # make the pools start their processes now (an executor starts them lazily, on submit)
+            for f in [self.readers.submit(os.getpid) for _ in range(self.n_readers)] + [self.writers.submit(os.getpid) for _ in range(self.n_writers)]:
+                f.result()
+        except BaseException:
+            self.close()
+            raise
 
     def close(self):
         self.readers.shutdown(wait=True)
@@ -471,6 +469,16 @@ class StudyWorkers:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class _StageThreads:
+    """process_folder's stages in one thread each, in StudyWorkers' shape: reader 1 study ahead, n_writers + 1 = 2 waiting for the writer."""
+    n_readers = n_writers = 1
+
+    def __init__(self):
+        self.readers, self.writers = ThreadPoolExecutor(1), ThreadPoolExecutor(1)
+
+    close = StudyWorkers.close
 
 
 def _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True):
@@ -532,13 +540,6 @@ def _spawn_unsafe_reason(reader):
             "`if __name__ == '__main__':` block, which a spawned worker would run again")
 
 
-def _is_pool_failure(e):
-    """An exception that condemns the worker pools, not the study: a worker died or an argument / result would not pickle."""
-    import pickle
-    from concurrent.futures.process import BrokenProcessPool
-    return isinstance(e, (BrokenProcessPool, pickle.PicklingError)) or (isinstance(e, (AttributeError, TypeError)) and "pickle" in str(e).lower())
-
-
 def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, chunk_index=0, mode="RVIO_2class", bkgd_comp="none",
                    flipLR=False, verbose=True, recalculate=False, no_saliency=True, OF_algo="TVL1", save_mask_subset=None,
                    include_waveforms=False, waveform_folder=None, pixel_spacing=None, frame_rate=None, process_subset=False,
@@ -570,232 +571,231 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
         raise ConfigurationError(f"otsu_masks must be 'host' or 'device', not {otsu_masks!r}")
     os.makedirs(save_folder, exist_ok=True)
     file_list = sorted(os.listdir(dcm_folder))                      # os.listdir order is arbitrary; sorted = same slices on every rank
-    errors = []
     if process_subset:
         if len(file_subset_list) == 0:
             logger.error("ERROR! File subset list is empty!")
-            return errors
+            return []
         file_list = [f for f in file_list if f in file_subset_list]
     if include_waveforms and waveform_folder is None:
         logger.error("ERROR if include_waveform is selected, must define waveform_folder!")
-        return errors
-    split = len(file_list) // nchunks
-    mine = file_list[chunk_index * split:(chunk_index + 1) * split][rank::world]
-    own = flow_model is None
-    model = None
-    pending = []
-    cfg_masks = config if config is not None else default_optical_flow_config()
-    shared = workers if isinstance(workers, StudyWorkers) else None
-    if shared is not None:
-        n_readers, n_writers = shared.n_readers, shared.n_writers
-    n_readers = _default_stage_workers() if n_readers is None else n_readers
-    n_writers = _default_stage_workers() if n_writers is None else n_writers
-    use_proc = workers == "process" or (workers == "auto" and flow_model is None and segmentor_model is None)
-    state = {"writer": None, "reader_pool": None, "proc": False, "fallback": None, "depth": 1}
-    studies = {}                # save_path -> what of a study lives in shared memory until its writer is done
-    begun_ref = []
-    futs = {}
+        return []
+    split, todo = len(file_list) // nchunks, []
+    for filename in file_list[chunk_index * split:(chunk_index + 1) * split][rank::world]:
+        stem, ext = os.path.splitext(filename)
+        save_path = os.path.join(save_folder, stem + ".hdf5")
+        if os.path.exists(save_path) and not recalculate:
+            if verbose:
+                logger.debug(f"File {save_path} exists! Skipping file {filename}")
+            continue
+        if ext.lower().lstrip(".") not in extensions:
+            logger.warning(f"File extension must be one of {extensions}, found {ext}, skipping")
+            continue
+        todo.append((filename, save_path))
+    use_proc = (workers == "process" or (workers == "auto" and flow_model is None and segmentor_model is None)) and len(todo) > 1
+    walk = _FolderWalk(dcm_folder, todo, reader, workers, use_proc, n_readers, n_writers, flow_model, (OF_algo, config, device_id),
+                       studies_in_flight, verbose, otsu_ahead=otsu_masks == "host",
+                       prepare_args=(mode, flipLR, config if config is not None else default_optical_flow_config()),
+                       video_args=dict(segmentor_model=segmentor_model, verbose=verbose, mode=mode, bkgd_comp=bkgd_comp, flipLR=flipLR,
+                                       no_saliency=no_saliency, OF_algo=OF_algo, save_mask_subset=save_mask_subset,
+                                       include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config))
+    try:
+        walk.run()
+    finally:
+        walk.close()
+    return walk.errors
 
-    def start_pools(n_todo):
-        # worker processes only make sense for more than one study, and they must exist before the first GPU call of this function
-        if shared is not None:
-            state["reader_pool"], state["writer"], state["proc"] = shared.readers, shared.writers, True
-        elif use_proc and n_todo > 1 and (why := _spawn_unsafe_reason(reader)) is not None:
-            # (the :=-bound reason is logged; the walk is the same, its reader and writer stages run in one thread each)
-            logger.warning(f"process_folder: worker processes not used, threads instead: {why}")
-            state["fallback"] = why
-            state["reader_pool"] = ThreadPoolExecutor(1)
-            state["writer"] = ThreadPoolExecutor(1)
-        elif use_proc and n_todo > 1:
-            import multiprocessing as mp
-            from concurrent.futures import ProcessPoolExecutor
-            ctx = mp.get_context("spawn")
-            state["reader_pool"] = ProcessPoolExecutor(max(1, min(n_readers, n_todo)), mp_context=ctx)
-            state["writer"] = ProcessPoolExecutor(max(1, n_writers), mp_context=ctx)
-            state["proc"] = True
-        else:
-            state["reader_pool"] = ThreadPoolExecutor(1)
-            state["writer"] = ThreadPoolExecutor(1)
 
-    def defer(job):
+class _Study:
+    """One study of a folder walk: the reader stage's result, what of it this process holds in shared memory, what goes on to the writer."""
+
+    def __init__(self, filename, save_path):
+        self.filename, self.save_path = filename, save_path
+        self.descs, self.blocks = [], []                  # the reader stage's shared-memory descriptors; the mappings this process holds
+        self.nparr = self.masks = self.echo = None        # frames, Otsu masks, `echo`: views into `blocks`, or plain arrays
+        self.mask_descs = self.echo_desc = None           # what the writer stage gets in their place
+        self.md = self.pid = self.hr = self.finish = None  # metadata, patient id, heart rate; _process_video_begin's second half
+
+    def take(self, prepared, mapped):
+        """Unpack what _prepare_study / _prepare_study_shm returned (nothing else knows its layout); `mapped`: and map its blocks."""
+        nparr, self.md, self.pid, self.hr, masks, echo = prepared
+        self.descs = [d for d in [nparr, echo] + list((masks or {}).values()) if _is_shm(d)]
+        if mapped:
+            self.echo_desc, self.mask_descs = echo, masks if masks is not None and any(_is_shm(v) for v in masks.values()) else None
+            nparr = _shm_get(nparr, self.blocks)
+            if masks is not None:
+                masks = {k: _shm_get(v, self.blocks) for k, v in masks.items()}
+            echo = _shm_get(echo, self.blocks)
+        self.nparr, self.masks, self.echo = nparr, masks, echo
+        return self
+
+    def release(self):
+        """Give the study's shared memory up: close and unlink what this process mapped or created, unlink by name what it never mapped."""
+        held = {blk.name for blk in self.blocks}
+        self.nparr = self.masks = self.echo = self.finish = None
+        _shm_release(self.blocks, unlink=True)
+        _shm_unlink_names([d for d in self.descs if d[1] not in held])
+        self.descs = []
+
+
+class _FolderWalk:
+    """process_folder's three-stage walk over `todo` = [(filename, save_path)]: the reader stage is `stages.n_readers` studies ahead, this
+    thread begins (submits) a study's solve and finishes the oldest of `in_flight`, the writer stage takes what finish() defers.
+    Worker processes (`use_proc`: asked for, and more than one study to do) are started here, before run() creates the flow model."""
+
+    def __init__(self, dcm_folder, todo, reader, workers, use_proc, n_readers, n_writers, flow_model, model_args, in_flight, verbose,
+                 otsu_ahead, prepare_args, video_args):
+        self.dcm_folder, self.todo, self.reader, self.in_flight, self.verbose = dcm_folder, todo, reader, in_flight, verbose
+        self.otsu_ahead, self.prepare_args, self.video_args = otsu_ahead, prepare_args, video_args
+        self.model, self.own_model, self.model_args = flow_model, flow_model is None, model_args
+        self.errors = []            # (filename, error string), process_folder's result
+        self.futs = {}              # index into todo -> reader stage future nobody has taken yet
+        self.studies = {}           # save_path -> _Study, from its reader result until its release
+        self.begun = deque()        # studies whose solve is submitted and not yet collected
+        self.pending = []           # (study, writer stage future)
+        # stages: StudyWorkers or _StageThreads; owned: the walk's to give up for threads and to close; fallback: why threads after all
+        self.stages, self.owned, self.fallback = workers, not isinstance(workers, StudyWorkers), None
+        if self.owned:
+            self.stages = _StageThreads()
+            if use_proc and (why := _spawn_unsafe_reason(reader)) is not None:
+                logger.warning(f"process_folder: worker processes not used, threads instead: {why}")
+                self.fallback = why
+            elif use_proc:
+                try:
+                    self.stages = StudyWorkers(min(_default_stage_workers() if n_readers is None else n_readers, len(todo)), n_writers)
+                except Exception as e:
+                    self.pools_failed(e)
+        self.proc = isinstance(self.stages, StudyWorkers)
+
+    def failed(self, name, e, trace=False):
+        logger.error(f"Error processing {name}: {e}")
+        if trace and self.verbose:
+            traceback.print_exc()
+        self.errors.append((name, f"{type(e).__name__}: {e}"))
+
+    def pools_failed(self, e):
+        """Called under `except`: raise on unless `e` condemns worker pools of the walk's own, not the study -- a worker died, an
+        argument or a result would not pickle; then the stages go on in threads, as rounds 2-3 ran them."""
+        import pickle
+        from concurrent.futures.process import BrokenProcessPool
+        if not (self.owned and (isinstance(e, (BrokenProcessPool, pickle.PicklingError))
+                                or (isinstance(e, (AttributeError, TypeError)) and "pickle" in str(e).lower()))):
+            raise
+        self.fallback = f"{type(e).__name__}: {e}"
+        logger.warning(f"process_folder: worker processes failed ({self.fallback}); the reader and writer stages continue in threads")
+
+    def submit(self, k):
+        if k < len(self.todo) and k not in self.futs:
+            self.futs[k] = self.stages.readers.submit(_prepare_study_shm if self.proc else _prepare_study, self.reader,
+                                                      os.path.join(self.dcm_folder, self.todo[k][0]), *self.prepare_args, self.proc, self.otsu_ahead)
+
+    def read(self, k, study):
+        try:
+            return study.take(self.futs.pop(k).result(), self.proc)
+        except Exception as e:
+            if not self.proc:
+                raise
+            self.pools_failed(e)
+        # studies already handed to the writer pool are reaped (and reported) as they are, what the reader pool has ready is freed
+        self.reap(block=True)
+        self.drop_read_ahead(wait=False)
+        for pool in (self.stages.writers, self.stages.readers):
+            pool.shutdown(wait=False, cancel_futures=True)
+        self.stages, self.proc = _StageThreads(), False
+        self.submit(k)
+        return study.take(self.futs.pop(k).result(), False)
+
+    def drop_read_ahead(self, wait):
+        """Reader results nobody took: free their blocks (`wait`: for every one of them; else only those that are there already)."""
+        for k, fut in list(self.futs.items()):
+            del self.futs[k]
+            with suppress(Exception):
+                if wait or (not fut.cancel() and fut.done()):
+                    _Study(*self.todo[k]).take(fut.result(), mapped=False).release()
+
+    def defer(self, study, job):
         from .hdf5_out import save_optical_flow_to_hdf5
-        if state["proc"]:
+        if not self.proc:
+            fut = self.stages.writers.submit(save_optical_flow_to_hdf5, *job)
+        else:
             # the writer process needs neither the RGB frames (the reader stage made `echo` from them) nor float32 flow (the file holds
             # float16); what is big travels as shared-memory names: the flow is cast straight into a new block, the masks and `echo`
             # stay in the blocks the reader stage filled
             save_path, flow_arr, nparr, mask_dict, *rest = job
-            study = studies.get(save_path, {})
-            echo = study.get("echo")
             flow_arr = np.asarray(flow_arr)
-            view, blk, desc = _shm_new(flow_arr.shape, np.float16)
+            view, blk, flow16 = _shm_new(flow_arr.shape, np.float16)
             if blk is not None:
-                study.setdefault("blocks", []).append(blk)
+                study.blocks.append(blk)
                 view[...] = flow_arr                                # float32 -> float16 while copying
                 del view
-                flow16 = desc
             else:
                 flow16 = flow_arr.astype(np.float16)
-            masks = study.get("mask_descs") if study.get("mask_descs") is not None and mask_dict is study.get("mask_views") else mask_dict
-            echo_d = study.get("echo_desc", echo)
-            job = (save_path, flow16, None if echo_d is not None else nparr, masks, *rest)
-            pending.append((save_path, state["writer"].submit(_save_study_shm, job, echo_d, int(np.asarray(nparr).shape[0]))))
-        else:
-            pending.append((job[0], state["writer"].submit(save_optical_flow_to_hdf5, *job)))
+            masks = study.mask_descs if study.mask_descs is not None and mask_dict is study.masks else mask_dict
+            job = (save_path, flow16, None if study.echo_desc is not None else nparr, masks, *rest)
+            fut = self.stages.writers.submit(_save_study_shm, job, study.echo_desc, int(np.asarray(nparr).shape[0]))
+        self.pending.append((study, fut))
 
-    def drop_study(save_path):
-        study = studies.pop(save_path, None)
-        if study is not None:
-            for k in ("nparr", "mask_views", "echo"):
-                study.pop(k, None)
-            _shm_release(study.get("blocks", []), unlink=True)
+    def drop(self, study):
+        self.studies.pop(study.save_path, None)
+        study.release()
 
-    def reap(block):
+    def reap(self, block):
         # at most a few studies wait for the writer: a faster solver must not pile finished studies up in host memory
-        while pending and (block or len(pending) > (n_writers + 1 if state["proc"] else 2) or pending[0][1].done()):
-            path, fut = pending.pop(0)
+        while self.pending and (block or len(self.pending) > self.stages.n_writers + 1 or self.pending[0][1].done()):
+            study, fut = self.pending.pop(0)
             try:
                 fut.result()
             except Exception as e:                                   # the writer's failure belongs to that study
-                logger.error(f"Error processing {os.path.basename(path)}: {e}")
-                errors.append((os.path.basename(path), f"{type(e).__name__}: {e}"))
-            drop_study(path)
+                self.failed(os.path.basename(study.save_path), e)
+            self.drop(study)
 
-    try:
-        todo = []
-        for filename in mine:
-            stem, ext = os.path.splitext(filename)
-            save_path = os.path.join(save_folder, stem + ".hdf5")
-            if os.path.exists(save_path) and not recalculate:
-                if verbose:
-                    logger.debug(f"File {save_path} exists! Skipping file {filename}")
-                continue
-            if ext.lower().lstrip(".") not in extensions:
-                logger.warning(f"File extension must be one of {extensions}, found {ext}, skipping")
-                continue
-            todo.append((filename, stem, save_path))
-        start_pools(len(todo))
-        state["depth"] = n_readers if state["proc"] else 1      # studies the reader stage may be ahead of the solver
-        futs = {}
+    def finish_oldest(self):
+        study, deferred = self.begun.popleft(), len(self.pending)
+        try:
+            study.finish()
+        except Exception as e:
+            self.failed(study.filename, e, trace=True)
+        if len(self.pending) == deferred:                             # nothing was handed to the writer stage: the study's blocks go now
+            self.drop(study)
+        self.reap(block=False)
 
-        def submit(k):
-            if k < len(todo) and k not in futs:
-                futs[k] = state["reader_pool"].submit(_prepare_study_shm if state["proc"] else _prepare_study, reader,
-                                                      os.path.join(dcm_folder, todo[k][0]), mode, flipLR, cfg_masks, state["proc"],
-                                                      otsu_masks == "host")
-
-        def pools_to_threads(e, k):
-            # The worker pools are unusable (a worker died while starting, something would not pickle): the stages go on in threads,
-            # as rounds 2-3 ran them.  Studies already handed to the writer pool are reaped (and reported) as they are.
-            why = f"{type(e).__name__}: {e}"
-            logger.warning(f"process_folder: worker processes failed ({why}); the reader and writer stages continue in threads")
-            state["fallback"] = why
-            reap(block=True)
-            for kk, fut in list(futs.items()):
-                fut.cancel()
-                try:
-                    res = fut.result(timeout=0) if fut.done() and not fut.cancelled() else None
-                    if res is not None:
-                        _shm_unlink_names([res[0], res[5]] + list((res[4] or {}).values()))
-                except Exception:
-                    pass
-                del futs[kk]
-            for pool in (state["writer"], state["reader_pool"]):
-                pool.shutdown(wait=False, cancel_futures=True)
-            state["reader_pool"], state["writer"], state["proc"], state["depth"] = ThreadPoolExecutor(1), ThreadPoolExecutor(1), False, 1
-            submit(k)
-        from collections import deque
-        begun = deque()                                               # studies whose solve is submitted and not yet collected
-        begun_ref.append(begun)
-
-        def finish_oldest():
-            filename, save_path, fin = begun.popleft()
-            deferred = len(pending)
-            try:
-                fin()
-            except Exception as e:
-                logger.error(f"Error processing {filename}: {e}")
-                if verbose:
-                    traceback.print_exc()
-                errors.append((filename, f"{type(e).__name__}: {e}"))
-            del fin
-            if len(pending) == deferred:                              # nothing was handed to the writer stage: the study's blocks go now
-                if save_path in studies and not studies[save_path]["blocks"]:
-                    _shm_unlink_names(studies[save_path].get("descs", []))
-                drop_study(save_path)
-            reap(block=False)
-        for k in range(min(state["depth"], len(todo))):
-            submit(k)
-        for k, (filename, stem, save_path) in enumerate(todo):
-            if verbose:
+    def run(self):
+        for k in range(min(self.stages.n_readers, len(self.todo))):
+            self.submit(k)
+        for k, (filename, save_path) in enumerate(self.todo):
+            if self.verbose:
                 logger.info(f"Processing file: {filename}...")
-            submit(k)                                                 # (already there unless the pools have just been rebuilt)
-            submit(k + state["depth"])
-            nparr = masks_ahead = echo = None
+            self.submit(k)                                            # (already there unless the pools have just been given up)
+            self.submit(k + self.stages.n_readers)
+            study = self.studies[save_path] = _Study(filename, save_path)
             try:
-                try:
-                    prepared = futs.pop(k).result()
-                except Exception as e:
-                    if not (state["proc"] and shared is None and _is_pool_failure(e)):
-                        raise
-                    pools_to_threads(e, k)
-                    prepared = futs.pop(k).result()
-                nparr, md, pid, hr, masks_ahead, echo = prepared
-                if state["proc"]:
-                    # map what the reader stage left in shared memory; the descriptors go on to the writer stage as they are
-                    study = studies[save_path] = {"blocks": [], "descs": [nparr, echo] + list((masks_ahead or {}).values())}
-                    study["echo_desc"] = echo
-                    study["mask_descs"] = masks_ahead if masks_ahead is not None and any(_is_shm(v) for v in masks_ahead.values()) else None
-                    nparr = _shm_get(nparr, study["blocks"])
-                    if masks_ahead is not None:
-                        masks_ahead = {mk: _shm_get(mv, study["blocks"]) for mk, mv in masks_ahead.items()}
-                    study["mask_views"] = masks_ahead
-                    study["echo"] = echo = _shm_get(echo, study["blocks"]) if _is_shm(echo) else echo
-                if model is None:
-                    model = flow_model if flow_model is not None else make_flow_model(OF_algo, config, device_id)
-                waveforms = None                                       # process_video loads and validates them (reference :602-620)
-                fin = _process_video_begin(os.path.join(dcm_folder, filename), save_path, segmentor_model, verbose=verbose, mode=mode,
-                                           bkgd_comp=bkgd_comp, flipLR=flipLR, no_saliency=no_saliency, OF_algo=OF_algo,
-                                           save_mask_subset=save_mask_subset, include_waveforms=include_waveforms, waveform_folder=waveform_folder,
-                                           config=config, nparr=nparr, metadata=md, patient_id=pid, heart_rate=hr, waveforms=waveforms,
-                                           flow_model=model, mask_dict=masks_ahead, _defer_save=defer, _submit=studies_in_flight > 1)
-                begun.append((filename, save_path, fin))
-                del fin
+                self.read(k, study)
+                if self.model is None:
+                    self.model = make_flow_model(*self.model_args)
+                study.finish = _process_video_begin(os.path.join(self.dcm_folder, filename), save_path, nparr=study.nparr, metadata=study.md,
+                                                    patient_id=study.pid, heart_rate=study.hr, flow_model=self.model, mask_dict=study.masks,
+                                                    _defer_save=partial(self.defer, study), _submit=self.in_flight > 1, **self.video_args)
+                self.begun.append(study)
             except Exception as e:
-                logger.error(f"Error processing {filename}: {e}")
-                if verbose:
-                    traceback.print_exc()
-                errors.append((filename, f"{type(e).__name__}: {e}"))
-                if save_path in studies and not studies[save_path]["blocks"]:
-                    _shm_unlink_names(studies[save_path].get("descs", []))
-                drop_study(save_path)
-            del nparr, masks_ahead, echo
-            while len(begun) >= max(1, studies_in_flight):
-                finish_oldest()
-        while begun:
-            finish_oldest()
-        reap(block=True)
-    finally:
-        while begun_ref and begun_ref[0]:                             # (an exception above) submitted solves are collected before the model goes
-            try:
-                begun_ref[0].popleft()[2]()
-            except Exception:
-                pass
-        for _path, fut in pending:                                    # (same case) writers still at work keep their study's blocks until done
-            try:
+                self.failed(filename, e, trace=True)
+                self.drop(study)
+            while len(self.begun) >= max(1, self.in_flight):
+                self.finish_oldest()
+        while self.begun:
+            self.finish_oldest()
+        self.reap(block=True)
+
+    def close(self):
+        """What is left when run() ended or raised, in this order."""
+        while self.begun:                                             # submitted solves are collected before the model goes
+            with suppress(Exception):
+                self.begun.popleft().finish()
+        for _study, fut in self.pending:                              # writers still at work keep their study's blocks until done
+            with suppress(Exception):
                 fut.result()
-            except Exception:
-                pass
-        for k, fut in futs.items():                                   # reader results nobody took (an exception above): free their blocks
-            try:
-                res = fut.result()
-                _shm_unlink_names([res[0], res[5]] + list((res[4] or {}).values()))
-            except Exception:
-                pass
-        for path in list(studies):
-            drop_study(path)
-        for pool in (state["writer"], state["reader_pool"]):
-            if pool is not None and shared is None:
-                pool.shutdown(wait=True)
-        if own and model is not None:
-            model.close()
-    return errors
+        self.drop_read_ahead(wait=True)
+        for study in list(self.studies.values()):
+            self.drop(study)
+        if self.owned:
+            self.stages.close()
+        if self.own_model and self.model is not None:
+            self.model.close()

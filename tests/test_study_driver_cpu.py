@@ -383,3 +383,56 @@ def test_process_folder_keeps_the_next_solve_in_flight_and_blames_the_right_stud
                              ["submit", 72], ["wait", 64], ["wait", 72]]
     assert g["1"]["log"] == [["calc", h] for h in (48, 40, 56, 64, 72)]
     assert g["3"]["log"][:4] == [["submit", 48], ["submit", 40], ["submit", 56], ["wait", 48]]
+
+
+WARM_DRIVER = r"""
+import sys, json, os, multiprocessing, numpy as np
+sys.path.insert(0, ROOT)
+from tee_optical_flow_amd import pipeline
+from tee_optical_flow_amd.synth import speckle_sequence
+
+seen = {"create": None, "solve": []}
+
+def children():
+    return sorted(p.pid for p in multiprocessing.active_children())
+
+class FakeModel:                        # cv2-protocol stand-in, tests only; notes which child processes exist at every solve
+    def calc_batch(self, frames, scale=1.0):
+        seen["solve"].append(children())
+        d = (frames[1:].astype(np.float32) - frames[:-1].astype(np.float32)) / 64
+        return np.stack([d, -0.5 * d], -1) * np.float32(scale)
+    def close(self): pass
+
+def fake_make_flow_model(*args, **kwargs):      # stands where the walk's first GPU call would be
+    seen["create"] = children()
+    return FakeModel()
+
+if __name__ == "__main__":
+    pipeline.make_flow_model = fake_make_flow_model
+    src, dst = os.path.join(TMP, "in"), os.path.join(TMP, "out")
+    os.makedirs(src)
+    for k in range(3):
+        g = speckle_sequence(300 + k, 4, 40, 48)
+        np.savez(os.path.join(src, f"s{k}.npz"), nparr=np.repeat(g[..., None], 3, axis=3), pixel_spacing=0.05, frame_rate=40.0)
+    kw = dict(workers="process", n_readers=2, n_writers=2) if sys.argv[1] == "process" else dict(workers="auto")
+    errs = pipeline.process_folder(src, dst, None, nchunks=1, chunk_index=0, mode="otsu", verbose=False, extensions=("npz",), **kw)
+    print(json.dumps({"errors": errs, "files": sorted(os.listdir(dst)), "create": seen["create"], "solve": seen["solve"],
+                      "default": pipeline._default_stage_workers()}))
+"""
+
+
+@pytest.mark.parametrize("workers", ["process", "auto"])
+def test_process_folder_has_all_its_worker_processes_before_it_creates_the_flow_model(tmp_path, workers):
+    """A process must not be started from one that has initialised the GPU: when the walk creates its flow model (its first GPU call),
+    every reader and writer process of the call exists already -- min(n_readers, studies) + n_writers of them -- and none is started later."""
+    if not os.path.exists(PY_H5):
+        pytest.skip("no interpreter with h5py")
+    script = tmp_path / "warm.py"
+    script.write_text(WARM_DRIVER.replace("ROOT", repr(ROOT)).replace("TMP", repr(str(tmp_path))))
+    r = subprocess.run([PY_H5, str(script), workers], capture_output=True, text=True, timeout=300, env={**os.environ, "PYTHONDONTWRITEBYTECODE": "1"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    g = json.loads(r.stdout.strip().splitlines()[-1])
+    assert g["errors"] == [] and g["files"] == ["s0.hdf5", "s1.hdf5", "s2.hdf5"], g
+    n_readers, n_writers = (2, 2) if workers == "process" else (g["default"], g["default"])
+    assert len(g["create"]) == min(n_readers, 3) + n_writers, g
+    assert len(g["solve"]) == 3 and all(s == g["create"] for s in g["solve"]), g

@@ -50,7 +50,8 @@ extern "C" {
 #define TF_ABI_VERSION 2   /* 2: tf_stats grew the per-stage times ms_warp .. ms_sched.  Round 5 ADDED entry points (tf_submit_*, tf_wait,
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
                               tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param, tf_otsu_masks,
-                              tf_radlong_overlay, tf_segmentor_input and tf_segmentor_classmap */
+                              tf_radlong_overlay, tf_segmentor_input, tf_segmentor_classmap, and the float16 payload calls
+                              (tf_calc_seq_rgb_f16, tf_submit_seq_rgb_f16, tf_calc_seq_saliency_f16, tf_echo_frames, tf_dbg_f16_round) */
 
 enum {
     TF_OK = 0,
@@ -214,6 +215,26 @@ int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int 
                          tf_stats* st);
 int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out,
                              tf_stats* st);
+
+/* The study file's payload from the device: `flow` and `echo` are stored as float16 (calculate_optical_flow.py:400-404,
+ * `flow_arr.astype(np.float16)` and `rgb2gray(nparr).astype(np.float16)`).  The *_f16 calls are tf_calc_seq_rgb, tf_submit_seq_rgb and
+ * tf_calc_seq_saliency / _f32 (map_f32 != 0) with the flows written as float16 bits: the output kernel multiplies by `scale` in float32,
+ * rounds that product to float32 as today, then rounds the float32 to half (nearest-even, subnormal halves kept, overflow to inf) --
+ * numpy's `(flows * np.float32(scale)).astype(np.float16)`, bit for bit.  flow16_out: host [N-1][H][W][2] halves; pinned destinations
+ * take the overlapped copy-out, pageable ones the in-order path, as for float32 (half the bytes either way).
+ * echo16_out (host [N][H][W] halves, or NULL): float16(rgb2gray(frame)) of every frame, the float64 luma rounded ONCE to half (through
+ * float32 it differs at 1057 of the 2^24 RGB triples), computed from the upload the conditioning / saliency pass reads anyway.  It is
+ * complete when the call -- tf_submit_seq_rgb_f16 included -- returns; the flows of a submitted job are complete at tf_wait.
+ * tf_calc_seq_saliency_f16: echo16_out needs channels == 3 (TF_ERR_INVALID_ARG otherwise).  tf_echo_frames is the echo alone
+ * (rgb: host uint8 [N][H][W][3]); it runs on the handle's stream and never on a lane's.  Device-pointer float16 destinations are not
+ * offered. */
+int tf_calc_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
+                        tf_stats* st);
+int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
+                          int* ticket);
+int tf_calc_seq_saliency_f16(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, float scale,
+                             uint16_t* flow16_out, uint16_t* echo16_out, tf_stats* st);
+int tf_echo_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint16_t* echo16_out);
 
 /* Mask cleaning of the segmentor modes, `clean_mask` of the reference (calculate_optical_flow.py:90-111 moving_avg_mask, :113-182
  * clean_mask), on the device and exact: for each label l (class id class_ids[l]) and frame,
@@ -414,6 +435,8 @@ long long tf_dbg_counter(tf_handle* h, const char* name);
 /* DeepFlow hooks: one cv::VariationalRefinement::calcUV on dense float images (u, v updated in place); 3x3 Gaussian blur */
 int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v);
 int tf_dbg_df_blur(tf_handle* h, const float* src, int w, int hgt, float* dst);
+/* the float16 output kernels' value function on caller-chosen values: out[i] = bits of half(float32(in[i] * scale)), n <= 2^30 */
+int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale, uint16_t* out);
 /* Pinned host memory for flow results.  The reference gets a fresh numpy array from cv2 (`flow = OF_model.calc(...)`,
  * calculate_optical_flow.py:631,642); handing tf_calc_pair/_seq/_pairs a destination from tf_host_alloc (or any pinned
  * host pointer) lets the library copy results out at PCIe speed while the next sub-batch is being solved.  Pageable

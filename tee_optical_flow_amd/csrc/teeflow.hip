@@ -133,7 +133,7 @@ struct tf_handle : TfKnobs {
     hipStream_t copy_stream = nullptr;           // D2H of finished sub-batches overlaps the next solve (pinned destinations)
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   // solve done [2], copy done [2]
     uint8_t* st_u8 = nullptr; size_t st_u8_bytes = 0;
-    float* st_flow = nullptr; size_t st_flow_bytes = 0;
+    uint8_t* st_flow = nullptr; size_t st_flow_bytes = 0;     // flow staging, in the call's output element type
     hipEvent_t ev[4] = {};
     // profiling of tvl1_iter launches
     std::deque<ProfEv> prof_pool;                            // deque: records keep their address while the pool grows
@@ -169,6 +169,7 @@ struct tf_handle : TfKnobs {
            PRE_WA_VALS, PRE_WA_CNT, PRE_WA_OFF, PRE_WA_SUM, PRE_WA_BG,            // WASE: compacted products, block counts / offsets, piece
                                                                                   //   sums, per-flow backgrounds
            PRE_SG_IN, PRE_SG_IDX, PRE_SG_MAP,                                     // tf_segmentor_input (tables, LUT, frames), tf_segmentor_classmap
+           PRE_ECHO,                                                              // the study's float16 `echo` (tf_echo_frames, the *_f16 calls)
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
@@ -220,17 +221,20 @@ struct tf_handle : TfKnobs {
 enum Mode { MODE_PAIRS, MODE_SEQ };
 // where a call's buffers live: bit 0 = the frames are device memory, bit 1 = the flow destination is
 enum { W_HOST = 0, W_IN_DEV = 1, W_OUT_DEV = 2, W_DEV = 3 };
-// Pair b is frames (in0[b], in1[b]) (MODE_PAIRS) or (in0[b], in0[b+1]) (MODE_SEQ: in1 unused); its flow is out[b], H x W x 2 floats.
+// Pair b is frames (in0[b], in1[b]) (MODE_PAIRS) or (in0[b], in0[b+1]) (MODE_SEQ: in1 unused); its flow is H x W x 2 elements of the
+// call's output type -- float32, or float16 (out_f16) -- at out + b * flow_bytes().
 struct Call {
     Mode mode = MODE_PAIRS; const uint8_t* in0 = nullptr; const uint8_t* in1 = nullptr; int n_pairs = 0, H = 0, W = 0; float scale = 1.f;
-    float* out = nullptr;
+    void* out = nullptr;
     int where = W_HOST;          // W_* bits
     bool f32 = false;            // the frames are float32 in [0,1] (CV_32F) instead of uint8
+    bool out_f16 = false;        // the flows are written as float16 (the study file's type) instead of float32
     size_t frame_bytes() const { return (size_t)H * W * (f32 ? 4 : 1); }
+    size_t flow_bytes() const { return (size_t)H * W * 2 * (out_f16 ? 2 : 4); }      // BYTES of one pair's flow
     Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
     {
         Call p = *this; const size_t off = (size_t)c0 * frame_bytes();
-        p.in0 += off; if (in1) p.in1 += off; p.out += (size_t)c0 * H * W * 2; p.n_pairs = nb;
+        p.in0 += off; if (in1) p.in1 += off; p.out = (uint8_t*)out + (size_t)c0 * flow_bytes(); p.n_pairs = nb;
         return p;
     }
 };
@@ -635,7 +639,7 @@ int run_stage(tf_handle* h, int l, int wi, int B, int off0, int off1)
 }
 
 // Solve B pairs whose frames are in device memory: frames[F][H][W] (uint8, or float32 in [0,1] when f32), pair b = (off0+b, off1+b).
-int solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, float* dflow)
+int solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16)
 {
     const tf_params& P = h->P;
     hipStream_t s = h->stream;
@@ -667,7 +671,8 @@ int solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B,
                            P.variant == TF_VARIANT_CUDA ? 1 : 0);
         hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->ctl, B, 1);
     }
-    hipLaunchKernelGGL(k_output, grid64x4(g0, B), dim3(256), 0, s, h->sb, h->ctl, g0, scale, dflow);
+    if (out_f16) hipLaunchKernelGGL(k_output<uint16_t>, out_grid<uint16_t>(g0, B), dim3(256), 0, s, h->sb, h->ctl, g0, scale, (uint16_t*)dflow);
+    else hipLaunchKernelGGL(k_output<float>, out_grid<float>(g0, B), dim3(256), 0, s, h->sb, h->ctl, g0, scale, (float*)dflow);
     HIPC(h, hipGetLastError());
     return TF_OK;
 }
@@ -979,7 +984,7 @@ int df_refine_level(tf_handle* h, const float* pyr_l, int off0, int off1, const 
     return TF_OK;
 }
 
-int df_solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, float* dflow)
+int df_solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16)
 {
     hipStream_t s = h->stream;
     const Geom g0 = h->dlv[0];
@@ -1009,7 +1014,8 @@ int df_solve_resident(tf_handle* h, const uint8_t* dframes, bool f32, int F, int
         hipLaunchKernelGGL(k_df_up, grid64x4(gd, B), dim3(256), 0, s, h->df, cur, g, gd, sx, sy, mul);
         cur ^= 1;
     }
-    hipLaunchKernelGGL(k_df_out, grid64x4(g0, B), dim3(256), 0, s, h->df, g0, scale, dflow);
+    if (out_f16) hipLaunchKernelGGL(k_df_out<uint16_t>, out_grid<uint16_t>(g0, B), dim3(256), 0, s, h->df, g0, scale, (uint16_t*)dflow);
+    else hipLaunchKernelGGL(k_df_out<float>, out_grid<float>(g0, B), dim3(256), 0, s, h->df, g0, scale, (float*)dflow);
     HIPC(h, hipGetLastError());
     return TF_OK;
 }
@@ -1035,6 +1041,7 @@ int check_call(tf_handle* h, const Call& c)
     if (!c.in0 || (c.mode == MODE_PAIRS && !c.in1) || !c.out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
     if (c.H < 1 || c.W < 1 || c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", c.n_pairs, c.H, c.W);
     if ((long long)c.H * c.W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
+    if (c.out_f16 && (c.where & W_OUT_DEV)) return fail(h, TF_ERR_UNSUPPORTED, "float16 flows go to host destinations only");
     return h->P.algo == TF_ALGO_DEEPFLOW ? df_validate(h, h->DP) : validate_params(h, h->P);
 }
 
@@ -1047,8 +1054,8 @@ int calc_common(tf_handle* h, const Call& c, int* iters, tf_stats* st)
     int rc = deep ? df_ensure_alloc(h, c.H, c.W, c.n_pairs) : ensure_alloc(h, c.H, c.W, c.n_pairs);
     if (rc) return rc;
     if (deep) h->cap = h->dcap;
-    const size_t fpx = c.frame_bytes();                      // BYTES per frame (the flow offsets below use npx)
-    const size_t npx = (size_t)c.H * c.W;
+    const size_t fpx = c.frame_bytes();                      // BYTES per frame
+    const size_t flb = c.flow_bytes();                       // BYTES per pair's flow, in the call's output element type
     const size_t per_pair = deep ? 0 : (size_t)h->nlev * h->P.warps * 2;
     h->tally = {};
     float ms_h2d = 0, ms_dev = 0, ms_d2h = 0;
@@ -1066,9 +1073,9 @@ int calc_common(tf_handle* h, const Call& c, int* iters, tf_stats* st)
     if (overlap && !h->copy_stream) HIPC(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     if (overlap && !h->cev[0])
         for (auto& e : h->cev) HIPC(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const size_t flow_half = (size_t)step * npx * 2;          // floats per staging half
+    const size_t flow_half = (size_t)step * flb;              // BYTES per staging half
     if (!in_dev || !out_dev) {
-        rc = ensure_staging(h, in_dev ? 0 : 2 * (size_t)h->cap * fpx, out_dev ? 0 : (overlap ? 2 : 1) * flow_half * sizeof(float));
+        rc = ensure_staging(h, in_dev ? 0 : 2 * (size_t)h->cap * fpx, out_dev ? 0 : (overlap ? 2 : 1) * flow_half);
         if (rc) return rc;
     }
     int kb = 0;
@@ -1077,7 +1084,7 @@ int calc_common(tf_handle* h, const Call& c, int* iters, tf_stats* st)
         const int nb = c.n_pairs - c0 < step ? c.n_pairs - c0 : step;
         const Call p = c.part(c0, nb);
         const uint8_t* dfr; int F, off0, off1;
-        float* dfl;
+        void* dfl;
         HIPC(h, hipEventRecord(h->ev[0], h->stream));
         if (c.mode == MODE_SEQ) {
             F = nb + 1; off0 = 0; off1 = 1;
@@ -1094,21 +1101,21 @@ int calc_common(tf_handle* h, const Call& c, int* iters, tf_stats* st)
                 dfr = h->st_u8;
             }
         }
-        dfl = out_dev ? p.out : h->st_flow + (overlap ? (size_t)(kb & 1) * flow_half : 0);
+        dfl = out_dev ? p.out : (void*)(h->st_flow + (overlap ? (size_t)(kb & 1) * flow_half : 0));
         if (overlap && kb >= 2) HIPC(h, hipStreamWaitEvent(h->stream, h->cev[2 + (kb & 1)], 0));   // that half's last copy-out
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
         const tf_handle::Tally snap = h->tally;              // what a repeat of this sub-batch must not count twice (an aborted co-resident attempt is void)
-        rc = deep ? df_solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl)
-                  : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl);
+        rc = deep ? df_solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16)
+                  : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16);
         if (rc) return rc;
         HIPC(h, hipEventRecord(h->ev[2], h->stream));
         if (overlap) {
             HIPC(h, hipEventRecord(h->cev[kb & 1], h->stream));
             HIPC(h, hipStreamWaitEvent(h->copy_stream, h->cev[kb & 1], 0));
-            HIPC(h, hipMemcpyAsync(p.out, dfl, (size_t)nb * npx * 2 * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
+            HIPC(h, hipMemcpyAsync(p.out, dfl, (size_t)nb * flb, hipMemcpyDeviceToHost, h->copy_stream));
             HIPC(h, hipEventRecord(h->cev[2 + (kb & 1)], h->copy_stream));
         } else if (!out_dev)
-            HIPC(h, hipMemcpyAsync(p.out, h->st_flow, (size_t)nb * npx * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, hipMemcpyAsync(p.out, h->st_flow, (size_t)nb * flb, hipMemcpyDeviceToHost, h->stream));
         if (!deep)
             HIPC(h, hipMemcpyAsync(iters + (size_t)c0 * per_pair, h->iters_dev, (size_t)nb * per_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipEventRecord(h->ev[3], h->stream));
@@ -2181,6 +2188,23 @@ TF_API int tf_dbg_df_blur(tf_handle* h, const float* src, int w, int hgt, float*
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_df_blur: %s", hipGetErrorString(e));
     return dbg_down(h, dst, b.p, g);
+}
+
+TF_API int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale, uint16_t* out)
+{
+    if (!h || !in || !out || n < 1) return TF_ERR_INVALID_ARG;
+    if (n > ((size_t)1 << 30)) return fail(h, TF_ERR_UNSUPPORTED, "tf_dbg_f16_round: at most 2^30 values");
+    HIPC(h, hipSetDevice(h->dev));
+    DBuf a, b;
+    HIPC(h, hipMalloc(&a.p, n * sizeof(float)));
+    HIPC(h, hipMalloc(&b.p, (n + 1) / 2 * sizeof(float)));
+    HIPC(h, hipMemcpyAsync(a.p, in, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_dbg_f16_round, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a.p, n, scale, (uint16_t*)b.p);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(out, b.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_dbg_f16_round: %s", hipGetErrorString(e));
+    return TF_OK;
 }
 
 TF_API int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v)

@@ -346,9 +346,19 @@ __global__ __launch_bounds__(256) void k_df_sum(DfBufs d, int cur, Geom g)
     d.Iz[i] = d.Wv[cur][i] + d.dv[i];
 }
 
-__global__ __launch_bounds__(256) void k_df_out(DfBufs d, Geom g, float scale, float* __restrict__ out)
+// T = float, or uint16_t for float16 bits (store_flow_row_f16, teeflow_kernels.hip.h: two pixels per thread, out_grid<T>)
+template <typename T>
+__global__ __launch_bounds__(256) void k_df_out(DfBufs d, Geom g, float scale, T* __restrict__ out)
 {
-    DF_XY();
-    const size_t i = (size_t)b * g.splane + j;
-    reinterpret_cast<float2*>(out)[((size_t)b * g.h + y) * g.w + x] = make_float2(d.avg[i] * scale, d.Iz[i] * scale);
+    if constexpr (sizeof(T) == 4) {
+        DF_XY();
+        const size_t i = (size_t)b * g.splane + j;
+        reinterpret_cast<float2*>(out)[((size_t)b * g.h + y) * g.w + x] = make_float2(d.avg[i] * scale, d.Iz[i] * scale);
+    } else {
+        const int t = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
+        if (y >= g.h) return;
+        const float* u = d.avg + (size_t)b * g.splane + (size_t)y * g.pitch;
+        const float* v = d.Iz + (size_t)b * g.splane + (size_t)y * g.pitch;
+        store_flow_row_f16(out + ((size_t)b * g.h + y) * g.w * 2, g.w, t, scale, [&](int px) { return make_float2(u[px], v[px]); });
+    }
 }

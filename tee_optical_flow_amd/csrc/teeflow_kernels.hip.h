@@ -1740,16 +1740,72 @@ __global__ void k_ctl_set(PairCtl* ctl, int B, int mode)
     else { ctl[b].ubase ^= 1; ctl[b].pbase = 0; }
 }
 
-// merge(u1,u2) -> interleaved [B][H][W][2], times the caller's unit scale (reference :600)
+// ---- float16 forms of a study's payload (reference :400-404: the file stores `flow` and `echo` as float16) -----------------------
+// One value of the flow output: the float32 product, rounded to float32 as numpy rounds `flows * np.float32(scale)`, then -- for a
+// float16 destination -- that float32 rounded to half, nearest-even, subnormal halves kept (v_cvt_f16_f32; the library is built with
+// -ffp-contract=off and there is no half arithmetic here): two roundings, numpy's `(flows * np.float32(scale)).astype(np.float16)`.
+// The empty asm keeps the product in a register as a float32 of its own: without it the compiler folds multiply and conversion into one
+// v_fma_mixlo_f16.  The guard is tests/test_gpu_payload.py::test_rounding_multiplies_in_float32_then_converts (scale 0.1 on 10^5 values,
+// where one rounding and two differ): should a compiler fold the two again in spite of the asm, that test fails.
+__device__ __forceinline__ uint32_t scaled_half_bits(float v, float scale)
+{
+    float prod = v * scale;
+    asm volatile("" : "+v"(prod));
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)prod);
+}
+
+// A row of the float16 flow output, [w][2] halves from `row` on: thread t of the row takes the two pixels x0 = 2t - par and x0 + 1,
+// par = the row's first pixel sitting on an odd 4-byte word -- so that a pair's four halves are one aligned 8-byte store whatever the
+// width and the row (an odd width shifts every other row by one pixel); the pixel left over at either end of a row is a 4-byte store.
+// w / 2 + 1 threads cover a row.  load(x) gives pixel x's (u, v).
+template <typename Load>
+__device__ __forceinline__ void store_flow_row_f16(uint16_t* __restrict__ row, int w, int t, float scale, Load load)
+{
+    const int par = (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 1);
+    const int x0 = 2 * t - par;
+    if (x0 >= w) return;
+    const bool has0 = x0 >= 0, has1 = x0 + 1 < w;
+    uint32_t p0 = 0, p1 = 0;
+    if (has0) { const float2 a = load(x0); p0 = scaled_half_bits(a.x, scale) | (scaled_half_bits(a.y, scale) << 16); }
+    if (has1) { const float2 b = load(x0 + 1); p1 = scaled_half_bits(b.x, scale) | (scaled_half_bits(b.y, scale) << 16); }
+    uint32_t* dst = reinterpret_cast<uint32_t*>(row) + x0;
+    if (has0 && has1) *reinterpret_cast<uint2*>(dst) = make_uint2(p0, p1);
+    else if (has0) dst[0] = p0;
+    else if (has1) dst[1] = p1;
+}
+// grid of the output kernels for element type T: float32 one pixel per thread, float16 two
+template <typename T> inline dim3 out_grid(const Geom& g, int z)
+{
+    const int tx = sizeof(T) == 2 ? g.w / 2 + 1 : g.w;
+    return dim3((tx + 63) / 64, (g.h + 3) / 4, z);
+}
+
+// merge(u1,u2) -> interleaved [B][H][W][2], times the caller's unit scale (reference :600); T = float, or uint16_t for float16 bits
+template <typename T>
 __global__ __launch_bounds__(256) void k_output(StateBufs sb, const PairCtl* __restrict__ ctl, Geom g, float scale,
-                                                float* __restrict__ out)
+                                                T* __restrict__ out)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
-    if (x >= g.w || y >= g.h) return;
-    const int uc = ctl[b].ubase & 1;
-    const size_t i = (size_t)b * g.splane + (size_t)y * g.pitch + x;
-    float2 v = make_float2(sb.u1[uc][i] * scale, sb.u2[uc][i] * scale);
-    reinterpret_cast<float2*>(out)[((size_t)b * g.h + y) * g.w + x] = v;
+    if constexpr (sizeof(T) == 4) {
+        if (x >= g.w || y >= g.h) return;
+        const int uc = ctl[b].ubase & 1;
+        const size_t i = (size_t)b * g.splane + (size_t)y * g.pitch + x;
+        float2 v = make_float2(sb.u1[uc][i] * scale, sb.u2[uc][i] * scale);
+        reinterpret_cast<float2*>(out)[((size_t)b * g.h + y) * g.w + x] = v;
+    } else {
+        if (y >= g.h) return;
+        const int uc = ctl[b].ubase & 1;
+        const float* u1 = sb.u1[uc] + (size_t)b * g.splane + (size_t)y * g.pitch;
+        const float* u2 = sb.u2[uc] + (size_t)b * g.splane + (size_t)y * g.pitch;
+        store_flow_row_f16(out + ((size_t)b * g.h + y) * g.w * 2, g.w, x, scale, [&](int px) { return make_float2(u1[px], u2[px]); });
+    }
+}
+
+// tf_dbg_f16_round: the output kernels' value function on caller-chosen values
+__global__ __launch_bounds__(256) void k_dbg_f16_round(const float* __restrict__ in, size_t n, float scale, uint16_t* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (uint16_t)scaled_half_bits(in[i], scale);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1800,4 +1856,39 @@ __global__ __launch_bounds__(256) void k_cond_norm(const uint8_t* __restrict__ r
     double v = rint(((g - mn) / mx) * 255.0);
     v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);          // NaN (all-black frame: 0/0) falls through to 0 below
     out[(size_t)f * npx + i] = (uint8_t)(v == v ? (int)v : 0);
+}
+
+// ---- `echo` of the study file (reference :400-402): rgb2gray(frame).astype(np.float16), per pixel half(luma_f64(rgb)) ----------------
+// float64 -> float16 in ONE rounding (nearest-even, subnormal halves kept, overflow to inf), with integer operations: a conversion
+// through float32 rounds twice and differs from numpy's at 1057 of the 2^24 RGB triples.
+__host__ __device__ inline uint16_t f64_to_f16_bits(double d)
+{
+    const u64 b = (u64)__builtin_bit_cast(unsigned long long, d);
+    const uint32_t sign = (uint32_t)(b >> 48) & 0x8000u;
+    const u64 a = b & 0x7fffffffffffffffull;
+    const int e = (int)(a >> 52);                                       // biased by 1023
+    if (e == 0x7ff) return (uint16_t)(sign | 0x7c00u | ((a & 0xfffffffffffffull) ? 0x200u : 0u));
+    if (e > 1023 + 15) return (uint16_t)(sign | 0x7c00u);               // >= 2^16
+    if (e < 1023 - 25) return (uint16_t)sign;                           // < 2^-25: below half of the smallest subnormal half
+    const u64 m = (a & 0xfffffffffffffull) | (1ull << 52);              // 53-bit significand (e >= 998: a normal double)
+    const bool normal = e >= 1023 - 14;
+    const int shift = normal ? 42 : 1051 - e;                           // subnormal half: units of 2^-24, shift in [43, 53]
+    const u64 r = m >> shift, rem = m & ((1ull << shift) - 1), half = 1ull << (shift - 1);
+    uint32_t hb = normal ? ((uint32_t)(e - 1008) << 10) + (uint32_t)(r & 0x3ff) : (uint32_t)r;
+    if (rem > half || (rem == half && (r & 1))) ++hb;                   // a carry runs into the exponent, up to 0x7c00 = inf
+    return (uint16_t)(sign | hb);
+}
+
+// n pixels of RGB (frames back to back) -> n halves; a thread takes 4 pixels: 12 bytes in, one 8-byte store
+__global__ __launch_bounds__(256) void k_echo_f16(const uint8_t* __restrict__ rgb, size_t n, uint16_t* __restrict__ out)
+{
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (i + 4 <= n && (reinterpret_cast<uintptr_t>(out + i) & 7) == 0) {
+        uint32_t hb[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hb[k] = f64_to_f16_bits(luma_f64(rgb + (i + k) * 3));
+        *reinterpret_cast<uint2*>(out + i) = make_uint2(hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16));
+    } else
+        for (size_t k = i; k < n && k < i + 4; ++k) out[k] = f64_to_f16_bits(luma_f64(rgb + k * 3));
 }

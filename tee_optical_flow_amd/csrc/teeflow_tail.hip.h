@@ -61,9 +61,21 @@ std::vector<u64> minmax_seed(size_t pairs)
     return init;
 }
 
+// n pixels of uploaded RGB (device) -> their float16 `echo` values in the caller's host buffer, behind what is queued on the handle's
+// stream; the copy is done when the stream has been waited for.  decho: device scratch of at least n halves.
+int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* decho, uint16_t* echo16_out)
+{
+    hipLaunchKernelGGL(k_echo_f16, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, drgb, n, decho);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(echo16_out, decho, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    return TF_OK;
+}
+
 // rgb (host) -> conditioned gray frames in the handle's preprocessing buffer (valid until the handle's next preprocessing call)
 // (`own`: into that caller-owned buffer instead -- a submitted job's frames must outlive the handle's next preprocessing call)
-int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t** dgray_out, uint8_t* own = nullptr)
+// echo16_out (host, [N][H][W] halves, or null): also the study's `echo`, from the same upload; complete on return
+int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t** dgray_out, uint8_t* own = nullptr,
+                        uint16_t* echo16_out = nullptr)
 {
     const size_t npx = (size_t)H * W;
     HIPC(h, hipSetDevice(h->dev));
@@ -71,6 +83,7 @@ int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, u
     auto* drgb = pre.get<uint8_t>(tf_handle::PRE_SRC, (size_t)N * npx * 3);
     auto* dgray = own ? own : pre.get<uint8_t>(tf_handle::PRE_OUT, (size_t)N * npx);
     auto* mm = pre.get<u64>(tf_handle::PRE_MX, (size_t)N * 2);
+    auto* decho = echo16_out ? pre.get<uint16_t>(tf_handle::PRE_ECHO, (size_t)N * npx) : nullptr;
     if (pre.rc) return pre.rc;
     const std::vector<u64> init = minmax_seed((size_t)N);
     HIPC(h, hipMemcpyAsync(drgb, rgb, (size_t)N * npx * 3, hipMemcpyHostToDevice, h->stream));
@@ -78,6 +91,7 @@ int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, u
     const int gx = (int)((npx + 255) / 256);
     hipLaunchKernelGGL(k_cond_minmax, dim3(gx < 512 ? gx : 512, N), dim3(256), 0, h->stream, drgb, npx, mm);
     hipLaunchKernelGGL(k_cond_norm, dim3(gx, N), dim3(256), 0, h->stream, drgb, npx, mm, dgray);
+    if (echo16_out) { const int rc = echo_from_device_rgb(h, drgb, (size_t)N * npx, decho, echo16_out); if (rc) return rc; }
     HIPC(h, hipStreamSynchronize(h->stream));            // `init` leaves scope; the solve may run on other streams (lanes)
     *dgray_out = dgray;
     return TF_OK;
@@ -99,22 +113,24 @@ TF_API int tf_condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, i
     return finish_host_call(h, condition_frames(h, rgb, N, H, W, gray_out));
 }
 
-TF_API int tf_calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
+namespace {
+// flows of an RGB study in the call's output type (out_f16: float16, and the study's `echo` to echo16_out if that is given)
+int calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, void* flow_out, bool out_f16, uint16_t* echo16_out, tf_stats* st)
 {
-    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST};
+    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST, false, out_f16};
     int rc = check_call(h, c);
     if (rc) return rc;
     uint8_t* dgray = nullptr;
-    rc = condition_to_device(h, rgb, N, H, W, &dgray);
+    rc = finish_host_call(h, condition_to_device(h, rgb, N, H, W, &dgray, nullptr, echo16_out));
     if (rc) return rc;
     // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
     c.in0 = dgray; c.where = W_IN_DEV;
     return calc_entry(h, c, st);
 }
-// tf_calc_seq_rgb without waiting: the frames are conditioned now (on the handle's stream, into a buffer the job owns), the solve is queued
-TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
+// the same without waiting: the frames are conditioned now (on the handle's stream, into a buffer the job owns), the solve is queued
+int submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, void* flow_out, bool out_f16, uint16_t* echo16_out, int* ticket)
 {
-    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST};
+    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST, false, out_f16};
     int rc = check_call(h, c);
     if (rc) return rc;
     if (!ticket) return TF_ERR_INVALID_ARG;
@@ -122,17 +138,58 @@ TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int
     uint8_t* own = nullptr;
     HIPC(h, hipMalloc(&own, (size_t)N * H * W));
     uint8_t* dgray = nullptr;
-    rc = condition_to_device(h, rgb, N, H, W, &dgray, own);
+    rc = finish_host_call(h, condition_to_device(h, rgb, N, H, W, &dgray, own, echo16_out));
     if (rc) { (void)hipFree(own); return rc; }
     c.in0 = own; c.where = W_IN_DEV;
     return submit_entry(h, c, ticket, own);
+}
+}  // namespace
+
+TF_API int tf_calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
+{
+    return calc_seq_rgb(h, rgb, N, H, W, scale, flow_out, false, nullptr, st);
+}
+TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
+{
+    return submit_seq_rgb(h, rgb, N, H, W, scale, flow_out, false, nullptr, ticket);
+}
+TF_API int tf_calc_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
+                               tf_stats* st)
+{
+    return calc_seq_rgb(h, rgb, N, H, W, scale, flow16_out, true, echo16_out, st);
+}
+TF_API int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
+                                 int* ticket)
+{
+    return submit_seq_rgb(h, rgb, N, H, W, scale, flow16_out, true, echo16_out, ticket);
+}
+// the echo alone: rgb uint8 [N][H][W][3] -> float16 [N][H][W] = half(rgb2gray), one rounding
+TF_API int tf_echo_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint16_t* echo16_out)
+{
+    if (!h || !rgb || !echo16_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    const size_t n = (size_t)N * H * W;
+    auto run = [&]() -> int {
+        HIPC(h, hipSetDevice(h->dev));
+        Pre pre(h);
+        auto* drgb = pre.get<uint8_t>(tf_handle::PRE_SRC, n * 3);
+        auto* decho = pre.get<uint16_t>(tf_handle::PRE_ECHO, n);
+        if (pre.rc) return pre.rc;
+        HIPC(h, hipMemcpyAsync(drgb, rgb, n * 3, hipMemcpyHostToDevice, h->stream));
+        const int rc = echo_from_device_rgb(h, drgb, n, decho, echo16_out);
+        if (rc) return rc;
+        HIPC(h, hipStreamSynchronize(h->stream));
+        return TF_OK;
+    };
+    return finish_host_call(h, run());
 }
 
 namespace {
 // frames (host, uint8 [N][H][W][channels]) -> fine-grained saliency maps [N][H][W] in the handle's preprocessing buffer: uint8, or
 // (f32) float = map * (1/255), what computeSaliency() returns in opencv-contrib 4.x.  Frames go through in chunks so that the work
 // buffers (17 B per pixel) stay below ~2.3 GB whatever the study's length; the buffers are the handle's and only ever grow.
-int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, void** dout)
+// echo16_out (host, or null; channels == 3 only): also the study's float16 `echo`, from each chunk's upload; complete on return
+int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, void** dout,
+                       uint16_t* echo16_out = nullptr)
 {
     const size_t npx = (size_t)H * W, ipx = (size_t)(H + 1) * (W + 1);
     if (H > 65535 || N > 65535) return fail(h, TF_ERR_UNSUPPORTED, "saliency: at most 65535 rows and 65535 frames per call");
@@ -151,6 +208,7 @@ int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W,
     auto* moff = pre.get<uint16_t>(tf_handle::PRE_MOFF, F * npx);
     auto* mx = pre.get<int>(tf_handle::PRE_MX, F * SAL_MX);
     auto* out = pre.get<uint8_t>(tf_handle::PRE_OUT, (size_t)N * npx * (f32 ? sizeof(float) : 1));
+    auto* decho = echo16_out ? pre.get<uint16_t>(tf_handle::PRE_ECHO, F * npx) : nullptr;
     if (pre.rc) return pre.rc;
     h->pre_kernel_ms = 0;
     for (size_t f0 = 0; f0 < (size_t)N; f0 += F) {
@@ -172,6 +230,7 @@ int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W,
                            f32 ? (float*)out + f0 * npx : nullptr);
         HIPC(h, hipGetLastError());
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
+        if (echo16_out) { const int rc = echo_from_device_rgb(h, src, n, decho, echo16_out + f0 * npx); if (rc) return rc; }
         HIPC(h, hipStreamSynchronize(h->stream));        // (one chunk holds 2^27 pixels: a study is one chunk; the event pair is read per chunk)
         float t = 0;
         HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
@@ -192,16 +251,18 @@ int saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, in
     return TF_OK;
 }
 
-int calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, float scale, float* flow_out, tf_stats* st)
+int calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, float scale, void* flow_out, tf_stats* st,
+                      bool out_f16 = false, uint16_t* echo16_out = nullptr)
 {
     if (!h) return TF_ERR_INVALID_ARG;
     if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
+    if (echo16_out && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "the echo needs RGB frames (channels == 3), got %d", channels);
     // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are)
-    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, f32};
+    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, f32, out_f16};
     int rc = check_call(h, c);
     if (rc) return rc;
     void* dsal = nullptr;
-    rc = saliency_to_device(h, frames, N, H, W, channels, f32, &dsal);
+    rc = finish_host_call(h, saliency_to_device(h, frames, N, H, W, channels, f32, &dsal, echo16_out));
     if (rc) return rc;
     c.in0 = (const uint8_t*)dsal; c.where = W_IN_DEV;
     return calc_entry(h, c, st);
@@ -223,6 +284,11 @@ TF_API int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int 
 TF_API int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
 {
     return calc_seq_saliency(h, frames, N, H, W, channels, true, scale, flow_out, st);
+}
+TF_API int tf_calc_seq_saliency_f16(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, float scale,
+                                    uint16_t* flow16_out, uint16_t* echo16_out, tf_stats* st)
+{
+    return calc_seq_saliency(h, frames, N, H, W, channels, map_f32 != 0, scale, flow16_out, st, true, echo16_out);
 }
 
 namespace {

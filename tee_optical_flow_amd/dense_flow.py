@@ -12,6 +12,7 @@ C ABI in include/teeflow.h; there is no CPU path.
 """
 import ctypes as C
 import weakref
+from collections import namedtuple
 
 import numpy as np
 
@@ -36,6 +37,11 @@ def _mask_stack(a, name):
     if a.ndim != 4 or a.shape[3] not in (1, 2) or min(a.shape) < 1:
         raise OpticalFlowCalculationError(f"{name} must be [N,H,W,C] with C = 1 or 2 and no empty side, got shape {a.shape}")
     return np.ascontiguousarray(a).view(np.uint8)
+
+
+# What a submitted job leaves for wait(): the result array, the frame count whose last flow wait() repeats (0: no repeat), whether
+# the job is a payload one (wait() then returns (out, echo), echo an array or None), and the input arrays the library reads until then
+_Job = namedtuple("_Job", "out pad_n payload echo inputs", defaults=(0, False, None, ()))
 
 
 class _PinnedPool:
@@ -83,6 +89,7 @@ class DenseFlow:
     """MI355X DualTVL1 solver with the cv2.DenseOpticalFlow calling convention."""
 
     device_unit_scale = True        # calc_study(scale=, pad_last=) applies the unit scale in the output kernel (pipeline.flow_for_study)
+    device_payload = True           # calc_study_payload & co. hand over the study file's float16 `flow` and `echo` (process_folder(payload="device"))
 
     _SETTERS = {"Tau": "tau", "Lambda": "lambda", "Theta": "theta", "ScalesNumber": "nscales",
                 "WarpingsNumber": "warps", "Epsilon": "epsilon", "InnerIterations": "inner_iterations",
@@ -254,6 +261,69 @@ class DenseFlow:
         if pad_last:
             out[N - 1] = out[N - 2]
         return out
+
+    # ---- the study file's float16 payload, made on the device (reference :400-404 casts on the host at write time) -------------
+    @staticmethod
+    def _rgb_study(nparr, min_frames=2):
+        nparr = _u8_image_stack(nparr, "nparr", 4)
+        if nparr.shape[3] != 3 or nparr.shape[0] < min_frames:
+            raise OpticalFlowCalculationError(f"nparr must be [N>={min_frames},H,W,3], got {nparr.shape}")
+        return nparr
+
+    def _payload_out(self, N, H, W, pad_last, echo):
+        """(flow16 [N or N-1,H,W,2], echo16 [N,H,W] or None), both float16 in pinned host memory"""
+        return (self._pool.empty((N if pad_last else N - 1, H, W, 2), np.float16),
+                self._pool.empty((N, H, W), np.float16) if echo else None)
+
+    def echo_frames(self, nparr):
+        """The study file's `echo` dataset on the device: RGB frames uint8 [N,H,W,3] -> float16 [N,H,W] =
+        frames.rgb2gray(nparr).astype(np.float16), bit for bit (the float64 luma rounded once to half)."""
+        nparr = self._rgb_study(nparr, 1)
+        N, H, W, _ = nparr.shape
+        out = self._pool.empty((N, H, W), np.float16)
+        _lib.check(self._L.tf_echo_frames(self._h, nparr.ctypes.data, N, H, W, out.ctypes.data), self._h, "tf_echo_frames")
+        return out
+
+    def calc_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True):
+        """calc_study with the flows rounded to float16 by the output kernel: RGB study uint8 [N,H,W,3] -> (flow16, echo16).  flow16 has
+        the bits of calc_study(nparr, scale, pad_last).astype(np.float16) -- the study file's `flow` dataset with `scale` = pixel_spacing
+        * frame_rate and `pad_last` -- at half the download; echo16 is echo_frames(nparr), made from the same upload, or None."""
+        nparr = self._rgb_study(nparr)
+        N, H, W, _ = nparr.shape
+        out, e16 = self._payload_out(N, H, W, pad_last, echo)
+        st = _lib.TfStats()
+        _lib.check(self._L.tf_calc_seq_rgb_f16(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data,
+                                               e16.ctypes.data if echo else None, C.byref(st)), self._h, "tf_calc_seq_rgb_f16")
+        self._finish(st)
+        if pad_last:
+            out[N - 1] = out[N - 2]
+        return out, e16
+
+    def calc_study_saliency_payload(self, nparr, scale=1.0, pad_last=True, echo=True, map_dtype="f32"):
+        """calc_study_saliency with float16 flows, and the `echo` of the RGB frames: -> (flow16, echo16 | None), as calc_study_payload."""
+        nparr = self._rgb_study(nparr)
+        N, H, W, _ = nparr.shape
+        out, e16 = self._payload_out(N, H, W, pad_last, echo)
+        st = _lib.TfStats()
+        _lib.check(self._L.tf_calc_seq_saliency_f16(self._h, nparr.ctypes.data, N, H, W, 3, 1 if self._map_is_f32(map_dtype) else 0, float(scale),
+                                                    out.ctypes.data, e16.ctypes.data if echo else None, C.byref(st)),
+                   self._h, "tf_calc_seq_saliency_f16")
+        self._finish(st)
+        if pad_last:
+            out[N - 1] = out[N - 2]
+        return out, e16
+
+    def submit_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True):
+        """calc_study_payload without waiting: -> ticket; `wait(ticket)` returns the (flow16, echo16 | None) pair.  The frames are
+        conditioned and the echo is complete before this returns (nparr may be reused at once)."""
+        nparr = self._rgb_study(nparr)
+        N, H, W, _ = nparr.shape
+        out, e16 = self._payload_out(N, H, W, pad_last, echo)
+        t = C.c_int(-1)
+        _lib.check(self._L.tf_submit_seq_rgb_f16(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data,
+                                                 e16.ctypes.data if echo else None, C.byref(t)), self._h, "tf_submit_seq_rgb_f16")
+        self._jobs[t.value] = _Job(out, pad_n=N if pad_last else 0, payload=True, echo=e16)
+        return t.value
 
     def saliency_frames(self, nparr, dtype=np.float32):
         """cv2.saliency.StaticSaliencyFineGrained_create().computeSaliency(frame)[1] for every frame, on the device (reference
@@ -555,7 +625,7 @@ class DenseFlow:
         out = self._out((N - 1, H, W, 2))
         t = C.c_int(-1)
         _lib.check(self._L.tf_submit_seq(self._h, frames.ctypes.data, N, H, W, float(scale), out.ctypes.data, C.byref(t)), self._h, "tf_submit_seq")
-        self._jobs[t.value] = (out, frames)                 # the library reads `frames` and writes `out` until the wait
+        self._jobs[t.value] = _Job(out, inputs=(frames,))               # the library reads `frames` and writes `out` until the wait
         return t.value
 
     def submit_study(self, nparr, scale=1.0, pad_last=False):
@@ -568,7 +638,7 @@ class DenseFlow:
         out = self._out((N if pad_last else N - 1, H, W, 2))
         t = C.c_int(-1)
         _lib.check(self._L.tf_submit_seq_rgb(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data, C.byref(t)), self._h, "tf_submit_seq_rgb")
-        self._jobs[t.value] = (out, ("pad_last", N) if pad_last else None)
+        self._jobs[t.value] = _Job(out, pad_n=N if pad_last else 0)
         return t.value
 
     def submit_pairs(self, I0s, I1s):
@@ -581,7 +651,7 @@ class DenseFlow:
         out = self._out((B, H, W, 2))
         t = C.c_int(-1)
         _lib.check(self._L.tf_submit_pairs(self._h, I0s.ctypes.data, I1s.ctypes.data, B, H, W, out.ctypes.data, C.byref(t)), self._h, "tf_submit_pairs")
-        self._jobs[t.value] = (out, I0s, I1s)
+        self._jobs[t.value] = _Job(out, inputs=(I0s, I1s))
         return t.value
 
     def wait(self, ticket):
@@ -589,15 +659,15 @@ class DenseFlow:
         describe that job.  A failed job raises here."""
         if ticket not in self._jobs:
             raise OpticalFlowCalculationError(f"unknown ticket {ticket!r} (already waited for?)")
-        keep = self._jobs.pop(ticket)
+        job = self._jobs.pop(ticket)
         st = _lib.TfStats()
         _lib.check(self._L.tf_wait(self._h, int(ticket), C.byref(st)), self._h, "tf_wait")
         self._finish(st)
-        if keep is None:
+        if job is None:                                                # the device form: nothing of the host's to hand back
             return self.last_stats
-        if len(keep) == 2 and isinstance(keep[1], tuple) and keep[1][0] == "pad_last":
-            keep[0][keep[1][1] - 1] = keep[0][keep[1][1] - 2]          # the last flow repeated (reference :599), inside the pinned buffer
-        return keep[0]
+        if job.pad_n:
+            job.out[job.pad_n - 1] = job.out[job.pad_n - 2]            # the last flow repeated (reference :599), inside the pinned buffer
+        return (job.out, job.echo) if job.payload else job.out         # submit_study_payload: (flow16, echo16 | None)
 
     def calc_seq_device(self, dframes_ptr, N, H, W, dflow_ptr, scale=1.0):
         st = _lib.TfStats()

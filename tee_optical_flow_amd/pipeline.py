@@ -120,6 +120,35 @@ def flow_for_study(frames_u8, OF_model, mask_dict=None, bkgd_comp="none", conver
     return flows if scaled else flows * conversion_factor         # (:600)
 
 
+_PAYLOADS = ("host", "device")
+_payload_fallbacks = set()          # kinds of reason already logged ("model", "bkgd_comp", "frames")
+
+
+def _check_payload(payload):
+    if payload not in _PAYLOADS:
+        raise ConfigurationError(f"payload must be 'host' or 'device', not {payload!r}")
+
+
+def _device_payload_refused(model, bkgd_comp, nparr=None):
+    """Why payload="device" cannot serve, as (kind, message) (None: it can): the model must offer the float16 study calls (DenseFlow.device_payload), the
+    study must need no background compensation (WASE works on float32 flows), and its frames -- once read -- must be uint8 RGB."""
+    if model is not None and not getattr(model, "device_payload", False):
+        return "model", f"the flow model ({type(model).__name__}) does not offer the float16 study calls"
+    if bkgd_comp != "none":
+        return "bkgd_comp", f"bkgd_comp={bkgd_comp!r} works on float32 flows"
+    if nparr is not None and not (nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8):
+        return "frames", f"the frames are not uint8 RGB [N,H,W,3] but {nparr.dtype} {nparr.shape}"
+    return None
+
+
+def _payload_fallback(refused):
+    """One message per kind of reason, whatever the shapes or names in it: a folder of gray studies of many sizes says it once."""
+    kind, reason = refused
+    if kind not in _payload_fallbacks:
+        _payload_fallbacks.add(kind)
+        logger.warning(f"payload='device' not used, the host casts flow and echo to float16 instead: {reason}")
+
+
 def _prep_frames(nparr, flipLR):
     """Reference :533-548: greyscale stacks become RGB, optional left-right flip."""
     nparr = np.asarray(nparr)
@@ -133,24 +162,27 @@ def _prep_frames(nparr, flipLR):
 def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                   no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                   config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                  mask_dict=None, _defer_save=None, saliency_map="f32"):
+                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host"):
     """Same positional signature as the reference (:478-483).  Keyword-only extras let a caller inject what the
     offline image cannot provide: `nparr` (frames instead of a DICOM), `metadata`, `mask_dict` (segmentation result),
-    `flow_model`.  Returns the float32 flow array [N,H,W,2] that was written."""
+    `flow_model`.  Returns the float32 flow array [N,H,W,2] that was written.  `payload="device"`: the engine hands over the file's
+    float16 `flow` and `echo` (DenseFlow.calc_study_payload; uint8 RGB frames, bkgd_comp="none", a model with `device_payload` --
+    otherwise the host path, with one logged reason) and the float16 array that was written is returned; the file is the same."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
-                                saliency_map=saliency_map)()
+                                saliency_map=saliency_map, payload=payload)()
 
 
 def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                          no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                          config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False):
+                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host"):
     """process_video in two halves: everything up to the flow solve, then a callable that collects the flows and does the rest (waveforms,
     hand-over to the HDF5 writer) and returns the flow array.  `_submit` (process_folder): where the engine offers it (gray-frame branch,
     no background compensation, a model the caller holds) the solve is only SUBMITTED here -- DenseFlow.submit_study, tf_submit_seq_rgb --
     so that the next study's solve is on the GPU while this one finishes."""
+    _check_payload(payload)
     if config is None:
         config = default_optical_flow_config()
     if mode == "otsu":
@@ -181,7 +213,8 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             raise ConfigurationError(f"Input for mode must be [A4C, otsu, RVIO_2class], not {mode}.")
     own = flow_model is None
     model = make_flow_model(OF_algo, config) if own else flow_model
-    collect = None                                # () -> the study's flow array
+    collect = None                                # () -> the study's flow array; payload="device": -> (float16 flow array, float16 echo or None)
+    from_device = False
     try:
         if mask_dict is None and mode == "otsu":
             # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
@@ -192,7 +225,26 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             from .masks import predict_movie
             mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config, engine=model)
         rgb_u8 = nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8
-        if not no_saliency:
+        if payload == "device":
+            refused = _device_payload_refused(model, bkgd_comp, nparr)
+            if refused is not None:
+                _payload_fallback(refused)
+            from_device = refused is None
+        if from_device:
+            # the file's float16 `flow` (unit scale and rounding in the output kernel, last flow repeated in the pinned buffer) and `echo`
+            # (from the upload the conditioning / saliency pass reads) come from the engine; the echo only where a file is written
+            kw = dict(scale=conversion_factor, pad_last=True, echo=save_path is not None)
+            rgb = np.ascontiguousarray(nparr)
+            if not no_saliency:
+                pair = model.calc_study_saliency_payload(rgb, map_dtype=saliency_map, **kw)
+                collect = lambda: pair
+            elif _submit and not own and hasattr(model, "submit_study_payload"):
+                ticket = model.submit_study_payload(rgb, **kw)
+                collect = lambda: model.wait(ticket)
+            else:
+                pair = model.calc_study_payload(rgb, **kw)
+                collect = lambda: pair
+        elif not no_saliency:
             # the reference's default branch (:559-560, :586): cv2.saliency.StaticSaliencyFineGrained on every frame
             if not rgb_u8:
                 raise OpticalFlowCalculationError(f"no_saliency=False needs uint8 RGB frames [N,H,W,3], got {nparr.dtype} {nparr.shape}")
@@ -216,7 +268,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
         collect = lambda: flow_arr
 
     def finish():
-        flows = collect()
+        flows, echo16 = collect() if from_device else (collect(), None)
         # waveforms (reference :602-620): loaded and validated by the reference's rules unless the caller injected a result dict;
         # without a valid ECG and a valid arterial waveform the whole block is dropped (waveforms_present = False)
         waveform_results, with_waveforms = {}, include_waveforms
@@ -229,10 +281,12 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             job = (save_path, flows, nparr, mask_dict, metadata, waveform_results, patient_id, heart_rate,
                    config, mode, no_saliency, with_waveforms, save_mask_subset)
             if _defer_save is not None:
-                _defer_save(job)                  # process_folder: the writer stage takes it while the next study is solved
+                # process_folder: the writer stage takes it while the next study is solved.  The hook is called with the job alone, as
+                # ever, unless the engine made the echo (payload="device"): only then does it get a second argument
+                _defer_save(job) if echo16 is None else _defer_save(job, echo16)
             else:
                 from .hdf5_out import save_optical_flow_to_hdf5
-                save_optical_flow_to_hdf5(*job)
+                save_optical_flow_to_hdf5(*job, echo=echo16)
         return flows
     return finish
 
@@ -544,7 +598,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                    flipLR=False, verbose=True, recalculate=False, no_saliency=True, OF_algo="TVL1", save_mask_subset=None,
                    include_waveforms=False, waveform_folder=None, pixel_spacing=None, frame_rate=None, process_subset=False,
                    file_subset_list=(), *, rank=0, world=1, extensions=("dcm",), reader=read_study, flow_model=None, config=None,
-                   device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host"):
+                   device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host", payload="host"):
     """Drop-in for the reference's process_folder (:243-290), same positional signature and the same rules:
       * the folder listing is cut into `nchunks` slices of len // nchunks files, this call takes slice `chunk_index`
         (the remainder files are dropped, as the reference does -- SURVEY.md Appendix C.8);
@@ -566,9 +620,16 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     `otsu_masks` (mode="otsu" only): "host" (default) has the reader stage compute the Otsu masks one study ahead with numpy / scipy;
     "device" has the reader stage skip them, and the walk makes them on the flow model (DenseFlow.otsu_masks, tf_otsu_masks; a model
     without that method computes them on the host, in the caller's thread).  The files are the same either way.
+    `payload`: "host" (default) receives float32 flows and casts them to the file's float16 on the host (while copying them to the writer
+    stage), and makes `echo` in the reader stage or the writer; "device" has the engine hand over both float16 arrays
+    (DenseFlow.submit_study_payload / calc_study_payload / calc_study_saliency_payload: rounded by the output kernel, half the download;
+    the echo from the frames the conditioning pass uploads anyway) -- the reader stage then makes no echo and the hand-over to the
+    writer stage is a plain copy.  It needs a model with `device_payload`, uint8 RGB frames and bkgd_comp="none"; otherwise the host
+    path serves, and the reason is logged once.  The files are the same either way.
     Returns the list of (filename, error string)."""
     if otsu_masks not in ("host", "device"):
         raise ConfigurationError(f"otsu_masks must be 'host' or 'device', not {otsu_masks!r}")
+    _check_payload(payload)
     os.makedirs(save_folder, exist_ok=True)
     file_list = sorted(os.listdir(dcm_folder))                      # os.listdir order is arbitrary; sorted = same slices on every rank
     if process_subset:
@@ -593,11 +654,11 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
         todo.append((filename, save_path))
     use_proc = (workers == "process" or (workers == "auto" and flow_model is None and segmentor_model is None)) and len(todo) > 1
     walk = _FolderWalk(dcm_folder, todo, reader, workers, use_proc, n_readers, n_writers, flow_model, (OF_algo, config, device_id),
-                       studies_in_flight, verbose, otsu_ahead=otsu_masks == "host",
+                       studies_in_flight, verbose, otsu_ahead=otsu_masks == "host", payload=payload,
                        prepare_args=(mode, flipLR, config if config is not None else default_optical_flow_config()),
                        video_args=dict(segmentor_model=segmentor_model, verbose=verbose, mode=mode, bkgd_comp=bkgd_comp, flipLR=flipLR,
                                        no_saliency=no_saliency, OF_algo=OF_algo, save_mask_subset=save_mask_subset,
-                                       include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config))
+                                       include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config, payload=payload))
     try:
         walk.run()
     finally:
@@ -643,7 +704,7 @@ class _FolderWalk:
     Worker processes (`use_proc`: asked for, and more than one study to do) are started here, before run() creates the flow model."""
 
     def __init__(self, dcm_folder, todo, reader, workers, use_proc, n_readers, n_writers, flow_model, model_args, in_flight, verbose,
-                 otsu_ahead, prepare_args, video_args):
+                 otsu_ahead, payload, prepare_args, video_args):
         self.dcm_folder, self.todo, self.reader, self.in_flight, self.verbose = dcm_folder, todo, reader, in_flight, verbose
         self.otsu_ahead, self.prepare_args, self.video_args = otsu_ahead, prepare_args, video_args
         self.model, self.own_model, self.model_args = flow_model, flow_model is None, model_args
@@ -665,6 +726,14 @@ class _FolderWalk:
                 except Exception as e:
                     self.pools_failed(e)
         self.proc = isinstance(self.stages, StudyWorkers)
+        # payload="device": the engine makes the echo, so the reader stage is asked for none (a study whose frames turn out not to be
+        # uint8 RGB still takes the host path: its frames then travel to the writer, which makes the echo)
+        self.device_echo = False
+        if payload == "device":
+            refused = _device_payload_refused(flow_model, video_args["bkgd_comp"])
+            if refused is not None:
+                _payload_fallback(refused)
+            self.device_echo = refused is None
 
     def failed(self, name, e, trace=False):
         logger.error(f"Error processing {name}: {e}")
@@ -686,7 +755,8 @@ class _FolderWalk:
     def submit(self, k):
         if k < len(self.todo) and k not in self.futs:
             self.futs[k] = self.stages.readers.submit(_prepare_study_shm if self.proc else _prepare_study, self.reader,
-                                                      os.path.join(self.dcm_folder, self.todo[k][0]), *self.prepare_args, self.proc, self.otsu_ahead)
+                                                      os.path.join(self.dcm_folder, self.todo[k][0]), *self.prepare_args, self.proc and not self.device_echo,
+                                                      self.otsu_ahead)
 
     def read(self, k, study):
         try:
@@ -712,26 +782,31 @@ class _FolderWalk:
                 if wait or (not fut.cancel() and fut.done()):
                     _Study(*self.todo[k]).take(fut.result(), mapped=False).release()
 
-    def defer(self, study, job):
+    def to_block(self, study, arr):
+        """float16 copy of `arr` for the writer process: the descriptor of a new shared-memory block of the study's, or a plain array"""
+        arr = np.asarray(arr)
+        view, blk, desc = _shm_new(arr.shape, np.float16)
+        if blk is None:
+            return arr.astype(np.float16, copy=False)
+        study.blocks.append(blk)
+        view[...] = arr                                             # float32 -> float16 while copying; float16: a plain copy
+        return desc
+
+    def defer(self, study, job, echo16=None):
+        """`echo16`: the study's float16 echo from the engine (payload="device"), else None: the reader stage's, or the writer makes it"""
         from .hdf5_out import save_optical_flow_to_hdf5
         if not self.proc:
-            fut = self.stages.writers.submit(save_optical_flow_to_hdf5, *job)
+            fut = self.stages.writers.submit(save_optical_flow_to_hdf5, *job, echo=echo16)
         else:
-            # the writer process needs neither the RGB frames (the reader stage made `echo` from them) nor float32 flow (the file holds
-            # float16); what is big travels as shared-memory names: the flow is cast straight into a new block, the masks and `echo`
-            # stay in the blocks the reader stage filled
+            # the writer process needs neither the RGB frames (the reader stage or the engine made `echo` from them) nor float32 flow (the
+            # file holds float16); what is big travels as shared-memory names: the flow goes straight into a new block (cast on the way
+            # if the engine handed float32 over), so does the engine's echo; the masks and the reader stage's `echo` stay in its blocks
             save_path, flow_arr, nparr, mask_dict, *rest = job
-            flow_arr = np.asarray(flow_arr)
-            view, blk, flow16 = _shm_new(flow_arr.shape, np.float16)
-            if blk is not None:
-                study.blocks.append(blk)
-                view[...] = flow_arr                                # float32 -> float16 while copying
-                del view
-            else:
-                flow16 = flow_arr.astype(np.float16)
+            flow16 = self.to_block(study, flow_arr)
+            echo = self.to_block(study, echo16) if echo16 is not None else study.echo_desc
             masks = study.mask_descs if study.mask_descs is not None and mask_dict is study.masks else mask_dict
-            job = (save_path, flow16, None if study.echo_desc is not None else nparr, masks, *rest)
-            fut = self.stages.writers.submit(_save_study_shm, job, study.echo_desc, int(np.asarray(nparr).shape[0]))
+            job = (save_path, flow16, None if echo is not None else nparr, masks, *rest)
+            fut = self.stages.writers.submit(_save_study_shm, job, echo, int(np.asarray(nparr).shape[0]))
         self.pending.append((study, fut))
 
     def drop(self, study):

@@ -2,7 +2,9 @@
 """Row f3 as a measurement: studies per second through process_folder (reference calculate_optical_flow.py:243-290) on the
 GPU box, HDF5 writing included, with the writer thread beside the next solve and without it.  h5py lives in the image's
 second interpreter, so run it there:
-    LD_PRELOAD=/usr/lib/x86_64-linux-gnu/libstdc++.so.6 /opt/conda/bin/python3.9 tools/study_throughput.py [--studies 6] [--frames 65] [--size 512]"""
+    LD_PRELOAD=/usr/lib/x86_64-linux-gnu/libstdc++.so.6 /opt/conda/bin/python3.9 tools/study_throughput.py [--studies 6] [--frames 65] [--size 512]
+--payload host|device: who makes the file's float16 `flow` and `echo` (process_folder(payload=)).  --compare-payloads R: only the
+worker-process walk, R rounds for each payload, interleaved in one process (same box, same folder), with the caller's thread's times."""
 import argparse
 import os
 import shutil
@@ -24,6 +26,9 @@ def main():
     ap.add_argument("--readers", type=int, default=2)
     ap.add_argument("--writers", type=int, default=2)
     ap.add_argument("--stages", action="store_true", help="also print where the caller's thread spends a study in the worker-process walk")
+    ap.add_argument("--payload", choices=("host", "device"), default="host", help="process_folder(payload=): who casts flow and echo to float16")
+    ap.add_argument("--compare-payloads", type=int, default=0, metavar="R",
+                    help="R rounds of the worker-process walk for payload host and device, interleaved; nothing else is run")
     a = ap.parse_args()
     from tee_optical_flow_amd import pipeline as P
     from tee_optical_flow_amd import hdf5_out
@@ -37,7 +42,7 @@ def main():
     # the worker processes must exist before anything in this process touches the GPU
     workers = P.StudyWorkers(a.readers, a.writers)
     model = P.make_flow_model(a.algo)
-    kw = dict(nchunks=1, chunk_index=0, mode="otsu", verbose=False, extensions=("npz",), OF_algo=a.algo, flow_model=model)
+    kw = dict(nchunks=1, chunk_index=0, mode="otsu", verbose=False, extensions=("npz",), OF_algo=a.algo, flow_model=model, payload=a.payload)
     P.process_folder(src, os.path.join(tmp, "warm"), None, process_subset=True, file_subset_list=["study00.npz"], workers="thread", **kw)   # warm-up: allocations, masks code paths
     P.process_folder(src, os.path.join(tmp, "warm2"), None, process_subset=True, file_subset_list=["study00.npz", "study01.npz"], workers=workers, **kw)
     # where the caller's thread spends a study in the worker-process walk: solve (flow_for_study), hand-over to the writer (defer),
@@ -48,8 +53,8 @@ def main():
     def timed_begin(*args, **kwargs):
         d = kwargs.get("_defer_save")
         if d is not None:
-            def timed_defer(job):
-                t = time.perf_counter(); d(job); acc["defer"] += time.perf_counter() - t
+            def timed_defer(job, echo16=None):
+                t = time.perf_counter(); d(job, echo16); acc["defer"] += time.perf_counter() - t
             kwargs["_defer_save"] = timed_defer
         t = time.perf_counter()
         fin = real_begin(*args, **kwargs)                   # masks are ready; conditions the frames and SUBMITS the solve (studies_in_flight=2)
@@ -62,6 +67,31 @@ def main():
             finally:
                 acc["finish"] += time.perf_counter() - t2
         return timed_finish
+    if a.compare_payloads > 0:
+        # flows of N - 1 pairs (the last one is repeated on the host), float32 or float16; device payload: plus the echo's N frames of halves
+        px = a.size * a.size
+        d2h = {"host": (a.frames - 1) * px * 2 * 4, "device": (a.frames - 1) * px * 2 * 2 + a.frames * px * 2}
+        P._process_video_begin = timed_begin
+        print(f"{a.algo}: {a.studies} studies of {a.frames} frames {a.size}x{a.size}, {a.readers} reader + {a.writers} writer processes, Otsu masks")
+        for payload in ("host", "device"):                  # one more warm-up each: the payload's own buffers (pinned pool, staging, echo)
+            P.process_folder(src, os.path.join(tmp, f"warm_{payload}"), None, process_subset=True, file_subset_list=["study00.npz", "study01.npz"],
+                             workers=workers, **{**kw, "payload": payload})
+        for r in range(a.compare_payloads):
+            for payload in ("host", "device"):
+                acc.update(begin=0.0, finish=0.0, defer=0.0)
+                t0 = time.perf_counter()
+                errs = P.process_folder(src, os.path.join(tmp, f"cmp_{payload}{r}"), None, workers=workers, **{**kw, "payload": payload})
+                t = time.perf_counter() - t0
+                n = a.studies
+                print(f"  round {r} payload={payload:6s}: {t / n * 1e3:7.1f} ms per study; caller's thread per study: submit {acc['begin'] / n * 1e3:6.1f} ms, "
+                      f"collect + hand-over {acc['finish'] / n * 1e3:6.1f} ms (hand-over to the writer {acc['defer'] / n * 1e3:6.1f} ms); "
+                      f"D2H {d2h[payload] / 1e6:.1f} MB per study (errors: {errs})", flush=True)
+                shutil.rmtree(os.path.join(tmp, f"cmp_{payload}{r}"), ignore_errors=True)
+        P._process_video_begin = real_begin
+        workers.close()
+        model.close()
+        shutil.rmtree(tmp, ignore_errors=True)
+        return
     if a.stages:
         P._process_video_begin = timed_begin
     t0 = time.perf_counter()
@@ -93,7 +123,7 @@ def main():
         for f in files:
             nparr, md, pid, hr = P.read_study(os.path.join(args[0], f))
             P.process_video(None, os.path.join(args[1], f[:-4] + ".hdf5"), None, verbose=False, mode="otsu", no_saliency=True, OF_algo=a.algo,
-                            nparr=nparr, metadata=md, patient_id=pid, heart_rate=hr, flow_model=model)
+                            nparr=nparr, metadata=md, patient_id=pid, heart_rate=hr, flow_model=model, payload=a.payload)
     t0 = time.perf_counter()
     serial_folder(src, os.path.join(tmp, "serial"))
     t_serial = time.perf_counter() - t0

@@ -1,0 +1,249 @@
+// teeflow_dbg.hip.h -- the tf_dbg_* hooks: single kernels and single stages on caller-supplied planes, for the tests that pin them
+// against the oracle; included by teeflow.hip last (one translation unit)
+namespace {
+// small RAII device buffer of the hooks
+template <class T> struct DevBuf { T* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
+using DBuf = DevBuf<float>;
+
+int dbg_up(tf_handle* h, DBuf& d, const float* src, const Geom& g)
+{
+    HIPC(h, hipMalloc(&d.p, (size_t)g.plane * sizeof(float)));
+    // stream-ordered on the handle's (non-blocking) stream: legacy-stream copies would race with its kernels
+    HIPC(h, hipMemsetAsync(d.p, 0, (size_t)g.plane * sizeof(float), h->stream));
+    if (src) HIPC(h, hipMemcpy2DAsync(d.p, (size_t)g.pitch * 4, src, (size_t)g.w * 4, (size_t)g.w * 4, g.h, hipMemcpyHostToDevice, h->stream));
+    return TF_OK;
+}
+int dbg_down(tf_handle* h, float* dst, const float* d, const Geom& g)
+{
+    HIPC(h, hipMemcpy2DAsync(dst, (size_t)g.w * 4, d, (size_t)g.pitch * 4, (size_t)g.w * 4, g.h, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return TF_OK;
+}
+
+// frames [I0, I1] in one allocation, so that pair 0 = (frame 0, frame 1)
+int dbg_up2(tf_handle* h, DBuf& fr, const float* I0, const float* I1, const Geom& g)
+{
+    HIPC(h, hipMalloc(&fr.p, 2 * (size_t)g.plane * sizeof(float)));
+    HIPC(h, hipMemsetAsync(fr.p, 0, 2 * (size_t)g.plane * sizeof(float), h->stream));
+    HIPC(h, hipMemcpy2DAsync(fr.p, (size_t)g.pitch * 4, I0, (size_t)g.w * 4, (size_t)g.w * 4, g.h, hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpy2DAsync(fr.p + g.plane, (size_t)g.pitch * 4, I1, (size_t)g.w * 4, (size_t)g.w * 4, g.h, hipMemcpyHostToDevice, h->stream));
+    return TF_OK;
+}
+}  // namespace
+
+// ---- kernel-level hooks --------------------------------------------------------------------------
+TF_API int tf_dbg_resize(tf_handle* h, const float* src, int sw, int sh, float* dst, int dw, int dh,
+                         double inv_scale_x, double inv_scale_y, float mul)
+{
+    if (!h || !src || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1) return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom gs = make_geom(sw, sh), gd = make_geom(dw, dh);
+    DBuf s, d;
+    int rc;
+    if ((rc = dbg_up(h, s, src, gs)) || (rc = dbg_up(h, d, nullptr, gd))) return rc;
+    hipLaunchKernelGGL(k_pyr_down, grid64x4(gd, 1), dim3(256), 0, h->stream, s.p, gs, d.p, gd, 1.0 / inv_scale_x, 1.0 / inv_scale_y);
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if ((rc = dbg_down(h, dst, d.p, gd))) return rc;
+    if (mul != 1.0f) for (size_t i = 0; i < (size_t)dw * dh; ++i) dst[i] *= mul;
+    return TF_OK;
+}
+
+TF_API int tf_dbg_pyramid(tf_handle* h, const uint8_t* img, int H, int W, int level, float* out, int* ow, int* oh)
+{
+    if (!h || !img || !ow || !oh || H < 1 || W < 1 || level < 0 || level >= MAXLEV) return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    Geom g = make_geom(W, H);
+    DevBuf<uint8_t> d8;
+    HIPC(h, hipMalloc(&d8.p, (size_t)H * W));
+    HIPC(h, hipMemcpyAsync(d8.p, img, (size_t)H * W, hipMemcpyHostToDevice, h->stream));
+    DBuf cur;
+    int rc = dbg_up(h, cur, nullptr, g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_u8_to_f32, dim3((g.w + 255) / 256, g.h, 1), dim3(256), 0, h->stream, d8.p, cur.p, g);
+    for (int s = 1; s <= level; ++s) {
+        Geom gn = make_geom(cv_round_d(g.w * h->P.scale_step), cv_round_d(g.h * h->P.scale_step));
+        if (gn.w < 1 || gn.h < 1) return fail(h, TF_ERR_INVALID_ARG, "pyramid level %d is empty", s);
+        DBuf nxt;
+        if ((rc = dbg_up(h, nxt, nullptr, gn))) return rc;
+        const double sc = 1.0 / h->P.scale_step;
+        hipLaunchKernelGGL(k_pyr_down, grid64x4(gn, 1), dim3(256), 0, h->stream, cur.p, g, nxt.p, gn, sc, sc);
+        HIPC(h, hipStreamSynchronize(h->stream));
+        std::swap(cur.p, nxt.p);
+        g = gn;
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    *ow = g.w; *oh = g.h;
+    if (out) return dbg_down(h, out, cur.p, g);
+    return TF_OK;
+}
+
+TF_API int tf_dbg_warp(tf_handle* h, const float* I0, const float* I1, const float* u1, const float* u2, int w, int hgt,
+                       float* I1wx, float* I1wy, float* rho_c)
+{
+    if (!h || !I0 || !I1 || !u1 || !u2 || !I1wx || !I1wy || !rho_c || w < 1 || hgt < 1) return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(w, hgt);
+    DBuf fr, du1, du2, dwx, dwy, drho;
+    int rc;
+    if ((rc = dbg_up2(h, fr, I0, I1, g)) || (rc = dbg_up(h, du1, u1, g)) || (rc = dbg_up(h, du2, u2, g)) || (rc = dbg_up(h, dwx, nullptr, g)) ||
+        (rc = dbg_up(h, dwy, nullptr, g)) || (rc = dbg_up(h, drho, nullptr, g))) return rc;
+    DevBuf<PairCtl> ctl;
+    HIPC(h, hipMalloc(&ctl.p, sizeof(PairCtl)));
+    HIPC(h, hipMemsetAsync(ctl.p, 0, sizeof(PairCtl), h->stream));
+    WarpArgs wa = {};
+    wa.pyr = fr.p; wa.off0 = 0; wa.off1 = 1; wa.sb.u1[0] = du1.p; wa.sb.u2[0] = du2.p; wa.ctl = ctl.p; wa.tab = h->tv.tab;
+    wa.wx = dwx.p; wa.wy = dwy.p; wa.rho = drho.p; wa.g = g;
+    DBuf dgx, dgy;
+    if (h->P.variant == TF_VARIANT_CUDA) {
+        HIPC(h, hipMalloc(&dgx.p, 2 * (size_t)g.plane * sizeof(float))); HIPC(h, hipMalloc(&dgy.p, 2 * (size_t)g.plane * sizeof(float)));
+        hipLaunchKernelGGL(k_grad, grid64x4(g, 2), dim3(256), 0, h->stream, fr.p, dgx.p, dgy.p, g);
+    }
+    launch_warp(h, wa, 1, h->stream, dgx.p, dgy.p);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_warp: %s", hipGetErrorString(e));
+    if ((rc = dbg_down(h, I1wx, dwx.p, g)) || (rc = dbg_down(h, I1wy, dwy.p, g)) || (rc = dbg_down(h, rho_c, drho.p, g))) return rc;
+    return TF_OK;
+}
+
+TF_API int tf_dbg_df_blur(tf_handle* h, const float* src, int w, int hgt, float* dst)
+{
+    if (!h || !src || !dst || w < 1 || hgt < 1) return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(w, hgt);
+    DBuf a, b;
+    int rc;
+    if ((rc = dbg_up(h, a, src, g)) || (rc = dbg_up(h, b, nullptr, g))) return rc;
+    float k0, k1;
+    df_gauss3(h->DP.sigma > 0 ? h->DP.sigma : 0.6f, &k0, &k1);
+    hipLaunchKernelGGL(k_df_blur, grid64x4(g, 1), dim3(256), 0, h->stream, a.p, b.p, g, k0, k1);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_df_blur: %s", hipGetErrorString(e));
+    return dbg_down(h, dst, b.p, g);
+}
+
+TF_API int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale, uint16_t* out)
+{
+    if (!h || !in || !out || n < 1) return TF_ERR_INVALID_ARG;
+    if (n > ((size_t)1 << 30)) return fail(h, TF_ERR_UNSUPPORTED, "tf_dbg_f16_round: at most 2^30 values");
+    HIPC(h, hipSetDevice(h->dev));
+    DBuf a, b;
+    HIPC(h, hipMalloc(&a.p, n * sizeof(float)));
+    HIPC(h, hipMalloc(&b.p, (n + 1) / 2 * sizeof(float)));
+    HIPC(h, hipMemcpyAsync(a.p, in, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_dbg_f16_round, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a.p, n, scale, (uint16_t*)b.p);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(out, b.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_dbg_f16_round: %s", hipGetErrorString(e));
+    return TF_OK;
+}
+
+TF_API int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v)
+{
+    if (!h || !I0 || !I1 || !u || !v || w < 1 || hgt < 1) return TF_ERR_INVALID_ARG;
+    if (h->P.algo != TF_ALGO_DEEPFLOW) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_df_refine needs a handle from tf_create_deepflow");
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(w, hgt);
+    DBuf fr, planes;
+    int rc = dbg_up2(h, fr, I0, I1, g);
+    if (rc) return rc;
+    HIPC(h, hipMalloc(&planes.p, DF_PLANES * (size_t)g.plane * sizeof(float)));
+    HIPC(h, hipMemsetAsync(planes.p, 0, DF_PLANES * (size_t)g.plane * sizeof(float), h->stream));
+    const DfBufs saved = h->df.bufs;
+    df_carve(h->df.bufs, planes.p, (size_t)g.plane);
+    hipError_t e = hipMemcpy2DAsync(h->df.bufs.Wu[0], (size_t)g.pitch * 4, u, (size_t)w * 4, (size_t)w * 4, hgt, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(h->df.bufs.Wv[0], (size_t)g.pitch * 4, v, (size_t)w * 4, (size_t)w * 4, hgt, hipMemcpyHostToDevice, h->stream);
+    CoopClaim claim(h->dev);
+    h->coop.share = claim.ok ? h->num_cus : 0;
+    rc = h->coop.ensure(h);
+    if (rc) { h->df.bufs = saved; return rc; }
+    if (e == hipSuccess) {
+        rc = df_refine_level(h, fr.p, 0, 1, g, 0, 1, h->stream);
+        e = hipStreamSynchronize(h->stream);
+        bool aborted = false;
+        if (e == hipSuccess && !rc) rc = h->coop.aborted(h, &aborted);
+        if (!rc && aborted) rc = fail(h, TF_ERR_HIP, "deepflow refine: the co-resident SOR launch gave up waiting for its neighbours");
+    }
+    if (e != hipSuccess) rc = fail(h, TF_ERR_HIP, "deepflow refine: %s", hipGetErrorString(e));
+    if (!rc) rc = dbg_down(h, u, h->df.bufs.avg, g);
+    if (!rc) rc = dbg_down(h, v, h->df.bufs.Iz, g);
+    h->df.bufs = saved;
+    return rc;
+}
+
+TF_API int tf_dbg_median(tf_handle* h, const float* src, int w, int hgt, int ksize, float* dst)
+{
+    if (!h || !src || !dst || w < 1 || hgt < 1 || (ksize != 3 && ksize != 5)) return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(w, hgt);
+    DBuf a0, a1, b0, b1;
+    int rc;
+    if ((rc = dbg_up(h, a0, src, g)) || (rc = dbg_up(h, a1, nullptr, g)) || (rc = dbg_up(h, b0, src, g)) || (rc = dbg_up(h, b1, nullptr, g))) return rc;
+    DevBuf<PairCtl> ctl;
+    HIPC(h, hipMalloc(&ctl.p, sizeof(PairCtl)));
+    HIPC(h, hipMemsetAsync(ctl.p, 0, sizeof(PairCtl), h->stream));
+    MedArgs ma = {};
+    ma.sb.u1[0] = a0.p; ma.sb.u1[1] = a1.p; ma.sb.u2[0] = b0.p; ma.sb.u2[1] = b1.p;
+    ma.ctl = ctl.p; ma.err = nullptr; ma.errstride = 0; ma.it = 0; ma.thr_q = 0; ma.utog = 0; ma.g = g;
+    const dim3 gm((g.w + 63) / 64, (g.h + 15) / 16, 2);
+    if (ksize == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, h->stream, ma);
+    else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, h->stream, ma);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_median: %s", hipGetErrorString(e));
+    return dbg_down(h, dst, a1.p, g);
+}
+
+TF_API int tf_dbg_iterate(tf_handle* h, const float* I1wx, const float* I1wy, const float* rho_c,
+                          float* u1, float* u2, float* p11, float* p12, float* p21, float* p22,
+                          int w, int hgt, int nsteps, int p_is_zero, unsigned long long* err_q)
+{
+    if (!h || !I1wx || !I1wy || !rho_c || !u1 || !u2 || !p11 || !p12 || !p21 || !p22 || w < 1 || hgt < 1 || nsteps < 0)
+        return TF_ERR_INVALID_ARG;
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(w, hgt);
+    DBuf cx, cy, cr, s[12];
+    int rc;
+    if ((rc = dbg_up(h, cx, I1wx, g)) || (rc = dbg_up(h, cy, I1wy, g)) || (rc = dbg_up(h, cr, rho_c, g))) return rc;
+    float* hostp[6] = {u1, u2, p11, p12, p21, p22};
+    for (int k = 0; k < 6; ++k) {
+        if ((rc = dbg_up(h, s[2 * k], hostp[k], g)) || (rc = dbg_up(h, s[2 * k + 1], nullptr, g))) return rc;
+    }
+    DevBuf<PairCtl> ctl; DevBuf<u64> errs;
+    HIPC(h, hipMalloc(&ctl.p, sizeof(PairCtl)));
+    HIPC(h, hipMemsetAsync(ctl.p, 0, sizeof(PairCtl), h->stream));
+    HIPC(h, hipMalloc(&errs.p, (size_t)(nsteps + 1) * sizeof(u64)));
+    HIPC(h, hipMemsetAsync(errs.p, 0, (size_t)(nsteps + 1) * sizeof(u64), h->stream));
+    IterArgs ia = {};
+    ia.wx = cx.p; ia.wy = cy.p; ia.rho = cr.p;
+    for (int k = 0; k < 2; ++k) {
+        ia.sb.u1[k] = s[0 + k].p; ia.sb.u2[k] = s[2 + k].p; ia.sb.p11[k] = s[4 + k].p;
+        ia.sb.p12[k] = s[6 + k].p; ia.sb.p21[k] = s[8 + k].p; ia.sb.p22[k] = s[10 + k].p;
+    }
+    ia.ctl = ctl.p; ia.err = errs.p; ia.errstride = nsteps + 1; ia.thr_q = -1.0; ia.g = g; ia.host_slot = nullptr; ia.B = 1;
+    ia.l_t = (float)(h->P.lambda * h->P.theta); ia.theta = (float)h->P.theta; ia.taut = (float)(h->P.tau / h->P.theta);
+    const bool two = two_per_launch(h, false, nsteps);     // (ia.variant = 0: these launches run the CPU form whatever the handle's variant)
+    int launches = 0;
+    if (two) {
+        for (int it = 0; it < nsteps; it += 2, ++launches) {
+            Iter2Args A2;
+            A2.a = ia; A2.a.it = it; A2.a.utog = launches; A2.a.ptog = launches; A2.a.pzero = (p_is_zero && it == 0) ? 1 : 0;
+            A2.utog_prev = A2.ptog_prev = A2.pzero_prev = 0; A2.total = nsteps;
+            launch_iter2(h, A2, 1, h->stream);
+        }
+    } else {
+        for (int it = 0; it < nsteps; ++it, ++launches) {
+            ia.it = it; ia.utog = it; ia.ptog = it; ia.pzero = (p_is_zero && it == 0) ? 1 : 0;
+            launch_iter(h, ia, 1, h->stream);
+        }
+    }
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && err_q && nsteps > 0) {
+        e = hipMemcpyAsync(err_q, errs.p, (size_t)nsteps * sizeof(u64), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_iter: %s", hipGetErrorString(e));
+    const int cur = launches & 1;
+    for (int k = 0; k < 6; ++k)
+        if ((rc = dbg_down(h, hostp[k], s[2 * k + cur].p, g))) return rc;
+    return TF_OK;
+}

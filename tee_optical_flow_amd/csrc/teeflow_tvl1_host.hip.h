@@ -1,0 +1,354 @@
+// teeflow_tvl1_host.hip.h -- DualTVL1's host side: parameters, pyramid geometry, Tvl1State's buffers, the launch rules of its
+// kernels, the stage loop and a solve's byte accounting; included by teeflow.hip after teeflow_engine.hip.h (one translation unit)
+namespace {
+int validate_params(Engine* h, const tf_params& p)
+{
+    if (p.algo != TF_ALGO_TVL1) return fail(h, TF_ERR_UNSUPPORTED, "algo %d not implemented (only TF_ALGO_TVL1)", p.algo);
+    if (p.nscales < 1 || p.nscales > MAXLEV) return fail(h, TF_ERR_INVALID_ARG, "nscales must be in [1,%d], got %d", MAXLEV, p.nscales);
+    if (p.warps < 1) return fail(h, TF_ERR_INVALID_ARG, "warps must be >= 1, got %d", p.warps);
+    if (p.inner_iterations < 1 || p.outer_iterations < 1)
+        return fail(h, TF_ERR_INVALID_ARG, "inner/outer iterations must be >= 1, got %d/%d", p.inner_iterations, p.outer_iterations);
+    if ((long long)p.inner_iterations * p.outer_iterations > 100000)
+        return fail(h, TF_ERR_INVALID_ARG, "inner*outer iterations too large");
+    if (p.median_filtering != 1 && p.median_filtering != 3 && p.median_filtering != 5)
+        return fail(h, TF_ERR_UNSUPPORTED, "medianFiltering must be 1, 3 or 5 (cv::medianBlur on CV_32F), got %d", p.median_filtering);
+    if (p.gamma != 0.0) return fail(h, TF_ERR_UNSUPPORTED, "gamma != 0 (illumination term u3) is not implemented");
+    if (p.variant != TF_VARIANT_CPU && p.variant != TF_VARIANT_CUDA) return fail(h, TF_ERR_INVALID_ARG, "variant must be TF_VARIANT_CPU or TF_VARIANT_CUDA, got %d", p.variant);
+    if (p.variant == TF_VARIANT_CUDA && (p.inner_iterations * p.outer_iterations) % 2 != 0)
+        return fail(h, TF_ERR_UNSUPPORTED, "TF_VARIANT_CUDA needs an even iteration count (inner*outer), got %d", p.inner_iterations * p.outer_iterations);
+    if (p.use_initial_flow) return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is not implemented");
+    if (!(p.scale_step > 0.0 && p.scale_step < 1.0)) return fail(h, TF_ERR_INVALID_ARG, "scaleStep must be in (0,1), got %g", p.scale_step);
+    // cv::resize silently runs INTER_AREA instead of INTER_LINEAR when both scale factors are exactly 2 (imgproc/resize.cpp, "in
+    // case of scale_x && scale_y is equal to 2"): same value mathematically, not the same float as the bilinear form k_pyr_down
+    // computes.  That branch is not restated, so the one scaleStep that takes it is refused rather than silently different.
+    if (p.scale_step == 0.5) return fail(h, TF_ERR_UNSUPPORTED, "scaleStep == 0.5 makes cv::resize take its INTER_AREA fast path for the pyramid, which is not implemented");
+    if (!(p.theta > 0.0) || !(p.tau > 0.0) || !(p.lambda > 0.0) || !(p.epsilon >= 0.0))
+        return fail(h, TF_ERR_INVALID_ARG, "tau, lambda, theta must be > 0 and epsilon >= 0");
+    return TF_OK;
+}
+
+// pyramid geometry of DualTVL1::calc: dsize = cvRound(size*scaleStep); stop before a level < 16 px
+int compute_levels(const tf_params& P, int H, int W, Geom* lv)
+{
+    int n = 1;
+    lv[0] = make_geom(W, H);
+    for (int s = 1; s < P.nscales; ++s) {
+        const int w = cv_round_d(lv[s - 1].w * P.scale_step), hh = cv_round_d(lv[s - 1].h * P.scale_step);
+        if (w < 16 || hh < 16) break;
+        lv[s] = make_geom(w, hh);
+        lv[s].splane = lv[0].plane;
+        n = s + 1;
+    }
+    return n;
+}
+
+void Tvl1State::release()
+{
+    for (int l = 0; l < MAXLEV; ++l) { dev_free(pyr[l]); dev_free(gxl[l]); dev_free(gyl[l]); }
+    dev_free(cwx); dev_free(cwy); dev_free(crho);
+    for (int k = 0; k < 2; ++k) { dev_free(sb.u1[k]); dev_free(sb.u2[k]); dev_free(sb.p11[k]); dev_free(sb.p12[k]); dev_free(sb.p21[k]); dev_free(sb.p22[k]); }
+    dev_free(ctl); dev_free(errs); dev_free(iters_dev);
+    H = W = cap = nlev = 0; iters_cap = 0;
+}
+
+// buffers for B pairs (at most a sub-batch) of H x W frames under the engine's current parameters; kept while they fit
+int Tvl1State::ensure(Engine* e, int H_, int W_, int B)
+{
+    const tf_params& P = e->P;
+    const int mb = P.max_batch > 0 ? P.max_batch : DEFAULT_MAX_BATCH;
+    const int want_cap = B < mb ? B : mb;
+    const int total = P.inner_iterations * P.outer_iterations;
+    if (H == H_ && W == W_ && cap >= want_cap && scale_step == P.scale_step && nscales == P.nscales && errstride >= total &&
+        variant == P.variant && iters_cap >= (size_t)cap * (size_t)nlev * (size_t)P.warps * 2)
+        return TF_OK;
+    HIPC(e, hipStreamSynchronize(e->stream));
+    release(); release_staging(e);
+    nlev = compute_levels(P, H_, W_, lv);
+    const size_t ncap = (size_t)want_cap, fcap = 2 * ncap;
+    for (int l = 0; l < nlev; ++l) HIPC(e, hipMalloc(&pyr[l], fcap * lv[l].plane * sizeof(float)));
+    if (P.variant == TF_VARIANT_CUDA)
+        for (int l = 0; l < nlev; ++l) {
+            HIPC(e, hipMalloc(&gxl[l], fcap * lv[l].plane * sizeof(float)));
+            HIPC(e, hipMalloc(&gyl[l], fcap * lv[l].plane * sizeof(float)));
+        }
+    variant = P.variant;
+    const size_t pl = (size_t)lv[0].plane * ncap * sizeof(float);
+    HIPC(e, hipMalloc(&cwx, pl)); HIPC(e, hipMalloc(&cwy, pl)); HIPC(e, hipMalloc(&crho, pl));
+    for (int k = 0; k < 2; ++k) {
+        HIPC(e, hipMalloc(&sb.u1[k], pl)); HIPC(e, hipMalloc(&sb.u2[k], pl));
+        HIPC(e, hipMalloc(&sb.p11[k], pl)); HIPC(e, hipMalloc(&sb.p12[k], pl));
+        HIPC(e, hipMalloc(&sb.p21[k], pl)); HIPC(e, hipMalloc(&sb.p22[k], pl));
+    }
+    HIPC(e, hipMalloc(&ctl, ncap * sizeof(PairCtl)));
+    errstride = total;
+    HIPC(e, hipMalloc(&errs, ncap * (size_t)errstride * sizeof(u64)));
+    iters_cap = ncap * (size_t)nlev * (size_t)P.warps * 2;
+    HIPC(e, hipMalloc(&iters_dev, iters_cap * sizeof(int)));
+    H = H_; W = W_; cap = want_cap;
+    scale_step = P.scale_step; nscales = P.nscales;
+    return TF_OK;
+}
+
+inline dim3 grid64x4(const Geom& g, int z) { return dim3((g.w + 63) / 64, (g.h + 3) / 4, z); }
+
+// full-width strips need W <= max_strip_width (at most 2048: one quad per thread, 512 threads) and enough rows*pairs to fill 256 CUs; tiny launches (single-pair latency mode) keep the tiles
+bool rows_ok(const Engine* h, const Geom& g, int B)
+{
+    return h->iter_variant >= 1 && g.w <= h->max_strip_width && (long long)g.h * B >= h->min_rows_work;
+}
+
+// two tvl1_iter iterations per launch (k_iter2_rows / k_iter2_tile) for a stage whose medians come every `inner` iterations.
+// TF_VARIANT_CUDA always runs that form (it has no median, and its iteration count is even)
+bool two_per_launch(const Engine* h, bool cuda_variant, int inner)
+{
+    return cuda_variant || (h->iter_variant >= 2 && inner % 2 == 0);
+}
+
+// Block shape of the row-strip kernels: QX quads per row, RY = floor(256/QX) rows per step, 256 threads.
+// (Measured on MI355X: shapes that fill more lanes with 320-512-thread blocks, or 1-row/128-thread blocks, are 10-35 %
+// SLOWER -- more waves per barrier domain / fewer blocks per CU cost more than idle lanes.)
+void strip_shape(const Engine* h, const Geom& g, int B, int* R, int* QX, int* RY, int* threads)
+{
+    const int qx = (g.w + 3) / 4;
+    int ry = 256 / qx;
+    if (ry < 1) ry = 1;
+    *QX = qx; *RY = ry;
+    *threads = qx * ry <= 256 ? 256 : (qx * ry + 63) / 64 * 64;
+    long long n = (long long)g.h * B / ((long long)h->strip_blocks * ry);
+    if (n < 2) n = 2;
+    if (n > 16) n = 16;
+    *R = ry * (int)n;
+}
+
+// launch one two-iteration tvl1_iter step (k_iter2_rows)
+void launch_iter2(Engine* h, const Iter2Args& A, int B, hipStream_t s)
+{
+    const Geom& g = A.a.g;
+    if (!rows_ok(h, g, B)) {      // small launches and very wide levels: tiles
+        hipLaunchKernelGGL(k_iter2_tile, dim3((g.w + T2_OW - 1) / T2_OW, (g.h + T2_OH - 1) / T2_OH, B), dim3(256), 0, s, A);
+        return;
+    }
+    int R, QX, RY, threads;
+    strip_shape(h, g, B, &R, &QX, &RY, &threads);
+    const int LW = QX * 4 + 4;
+    const size_t shmem = (size_t)(32 + 8 * RY * LW + 2 * (RY + 1) * LW + 2 * RY * QX) * sizeof(float);
+    if (B <= 1024) {
+        // strips sized on the device from the exact number of pairs still iterating (one round of resident blocks); the grid covers
+        // the largest item count
+        auto f = h->tv.slots_cache.find(shmem * 1024 + (size_t)threads / 64);
+        if (f == h->tv.slots_cache.end()) {
+            int per_cu = 0;
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iter2_rows, threads, shmem);
+            if (per_cu < 1) per_cu = 1;
+            f = h->tv.slots_cache.emplace(shmem * 1024 + (size_t)threads / 64, per_cu * h->num_cus).first;
+        }
+        int slots = f->second;
+        if (h->slots_pct > 0 && h->slots_pct < 100) slots = slots * h->slots_pct / 100;
+        int items = 1;
+        for (int n = 1; n <= B; ++n) {
+            int r, sn;
+            strip_rule(n, g.h, RY, slots, &r, &sn);
+            if (n * sn > items) items = n * sn;
+        }
+        hipLaunchKernelGGL(k_iter2_rows, dim3(items, 1, 1), dim3(threads), shmem, s, A, 0, QX, RY, slots);
+        return;
+    }
+    // a sub-batch above 1024 pairs (max_batch > 1024): fixed strips of R rows per pair
+    hipLaunchKernelGGL(k_iter2_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem, s, A, R, QX, RY, 0);
+}
+
+// launch one tvl1_iter step for pairs [0,B) in the configured kernel form
+void launch_iter(Engine* h, const IterArgs& ia, int B, hipStream_t s)
+{
+    const Geom& g = ia.g;
+    if (rows_ok(h, g, B)) {
+        int R, QX, RY, threads;
+        strip_shape(h, g, B, &R, &QX, &RY, &threads);
+        const int LW = QX * 4 + 4;
+        const size_t shmem = (size_t)(32 + 8 * RY * LW + 2 * RY * QX) * sizeof(float);
+        hipLaunchKernelGGL(k_iter_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem, s, ia, R, QX, RY);
+    } else {
+        const dim3 gi((g.w + IT_OW - 1) / IT_OW, (g.h + IT_OH - 1) / IT_OH, B);
+        hipLaunchKernelGGL(k_iter, gi, dim3(256), 0, s, ia);
+    }
+}
+
+// k_warp_lds is instantiated for a few margins (the staged width is a compile-time constant)
+inline int warp_margin_class(int m) { return m <= 0 ? 0 : (m <= 4 ? 4 : (m <= 8 ? 8 : 16)); }
+void launch_warp(Engine* h, const WarpArgs& wa, int B, hipStream_t s, const float* gx = nullptr, const float* gy = nullptr)
+{
+    const Geom& g = wa.g;
+    if (h->P.variant == TF_VARIANT_CUDA) {
+        WarpCudaArgs ca; ca.w = wa; ca.gx = gx; ca.gy = gy;
+        hipLaunchKernelGGL(k_warp_cuda, dim3((g.w + 63) / 64, (g.h + 3) / 4, B), dim3(256), 0, s, ca);
+        return;
+    }
+    const int M = warp_margin_class(h->warp_margin);
+    const dim3 grid((g.w + WL_TW - 1) / WL_TW, (g.h + WL_TH - 1) / WL_TH, B);
+    const size_t shm = (size_t)(128 + (WL_TW + 2 * (M + 4)) * (WL_TH + 2 * M + 7)) * sizeof(float);
+    switch (M) {
+        case 4: hipLaunchKernelGGL(k_warp_lds<4>, grid, dim3(256), shm, s, wa); break;
+        case 8: hipLaunchKernelGGL(k_warp_lds<8>, grid, dim3(256), shm, s, wa); break;
+        case 16: hipLaunchKernelGGL(k_warp_lds<16>, grid, dim3(256), shm, s, wa); break;
+        default: hipLaunchKernelGGL(k_warp, dim3((g.w + 63) / 64, (g.h + 3) / 4, B), dim3(256), 0, s, wa); break;
+    }
+}
+
+// Read back the active-pair reports of this stage's launches [*checked, q] (a launch publishes its report when it starts): never more than
+// DEFAULT_LAG launches unread.  *stop: a launch that no pair entered active -- the rest of the stage would be no-ops.
+int read_reports(Engine* h, hipStream_t s, unsigned q, unsigned* checked, bool* stop)
+{
+    while (*checked <= q) {
+        int v = h->tv.slots_host[*checked % SLOT_RING];
+        if (v < 0) {
+            if (q - *checked < (unsigned)DEFAULT_LAG) break;        // not there yet, and we may still run ahead
+            const double t0 = now_ms();
+            while ((v = h->tv.slots_host[*checked % SLOT_RING]) < 0) {
+                if (now_ms() - t0 > 20000.0) return fail(h, TF_ERR_HIP, "tvl1_iter launch %u never reported (GPU hang?)", *checked);
+                if (hipStreamQuery(s) == hipSuccess && h->tv.slots_host[*checked % SLOT_RING] < 0)
+                    return fail(h, TF_ERR_HIP, "stream drained but launch %u did not report", *checked);
+            }
+        }
+        ++*checked;
+        if (v == 0) { *stop = true; break; }
+    }
+    return TF_OK;
+}
+
+// one (level, warp) stage for pairs [0,B)
+int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
+{
+    const tf_params& P = h->P;
+    const Geom g = h->tv.lv[l];
+    const int inner = P.inner_iterations, total = P.inner_iterations * P.outer_iterations;
+    const float thr_f = (float)(P.epsilon * P.epsilon * (double)(g.w * g.h));
+    const double thr_q = (double)thr_f * 1073741824.0;
+    const double thr_d = P.epsilon * P.epsilon * (double)(g.w * g.h);     // TF_VARIANT_CUDA compares in double
+    hipStream_t s = h->stream;
+
+    WarpArgs wa;
+    wa.pyr = h->tv.pyr[l]; wa.off0 = off0; wa.off1 = off1; wa.sb = h->tv.sb; wa.ctl = h->tv.ctl; wa.tab = h->tv.tab;
+    wa.wx = h->tv.cwx; wa.wy = h->tv.cwy; wa.rho = h->tv.crho; wa.g = g;
+    int rc = profiled(h, s, -4, 0, 0, [&] { launch_warp(h, wa, B, s, h->tv.gxl[l], h->tv.gyl[l]); });
+    if (rc) return rc;
+    HIPC(h, hipMemsetAsync(h->tv.errs, 0, (size_t)B * h->tv.errstride * sizeof(u64), s));
+
+    IterArgs ia;
+    ia.wx = h->tv.cwx; ia.wy = h->tv.cwy; ia.rho = h->tv.crho; ia.sb = h->tv.sb; ia.ctl = h->tv.ctl; ia.err = h->tv.errs;
+    ia.errstride = h->tv.errstride; ia.thr_q = thr_q; ia.g = g;
+    ia.l_t = (float)(P.lambda * P.theta); ia.theta = (float)P.theta; ia.taut = (float)(P.tau / P.theta);
+    ia.variant = P.variant; ia.thr_d = thr_d;
+    const bool cuda_variant = P.variant == TF_VARIANT_CUDA;      // one loop, no median, stops only after odd iterations
+    const bool median = P.median_filtering > 1 && !cuda_variant;
+    MedArgs ma;
+    ma.sb = h->tv.sb; ma.ctl = h->tv.ctl; ma.err = h->tv.errs; ma.errstride = h->tv.errstride; ma.thr_q = thr_q; ma.g = g;
+
+    const dim3 gm((g.w + 63) / 64, (g.h + 15) / 16, 2 * B);
+    ia.B = B;
+    // One or two iterations per launch.  Two: launch index it = 0,2,..,total (the last one can only hold REPLAY blocks), and each launch
+    // is also told the ping-pong state of the one before it.
+    const bool two = two_per_launch(h, cuda_variant, inner);
+    int utog = 0, ptog = 0, utog_prev = 0, ptog_prev = 0, pzero_prev = 0;
+    bool stop = false;
+    unsigned checked = h->tv.launch_seq;          // this stage's launches before `checked` have been read back
+    for (int it = 0; (two ? it <= total : it < total) && !stop; it += two ? 2 : 1) {
+        if (it < total && it % inner == 0 && median) {
+            ma.it = it; ma.utog = utog;
+            rc = profiled(h, s, -5, 0, 0, [&] {
+                if (two) {
+                    if (P.median_filtering == 5) hipLaunchKernelGGL(k_median2<5>, gm, dim3(256), 0, s, ma, total);
+                    else hipLaunchKernelGGL(k_median2<3>, gm, dim3(256), 0, s, ma, total);
+                } else if (P.median_filtering == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
+                else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, s, ma);
+            });
+            if (rc) return rc;
+            ++utog;
+        }
+        const unsigned q = h->tv.launch_seq++;
+        h->tv.slots_host[q % SLOT_RING] = -1;
+        ia.host_slot = h->tv.slots_dev + q % SLOT_RING;
+        ia.it = it; ia.utog = utog; ia.ptog = ptog; ia.pzero = (wi == 0 && it == 0) ? 1 : 0;
+        rc = profiled(h, s, l, wi, it, [&] {
+            if (!two) { launch_iter(h, ia, B, s); return; }
+            Iter2Args A2;
+            A2.a = ia;
+            A2.utog_prev = utog_prev; A2.ptog_prev = ptog_prev; A2.pzero_prev = pzero_prev; A2.total = total;
+            launch_iter2(h, A2, B, s);
+        });
+        if (rc) return rc;
+        ++h->tally.iter_launches;
+        utog_prev = utog; ptog_prev = ptog; pzero_prev = ia.pzero;
+        ++utog; ++ptog;
+        rc = read_reports(h, s, q, &checked, &stop);
+        if (rc) return rc;
+    }
+    if (two)
+        hipLaunchKernelGGL(k_stage_end2, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, h->tv.iters_dev, B,
+                           total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps, P.variant, thr_d);
+    else
+        hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, h->tv.iters_dev, B,
+                           total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps);
+    return TF_OK;
+}
+
+// Solve B pairs whose frames are in device memory: frames[F][H][W] (uint8, or float32 in [0,1] when f32), pair b = (off0+b, off1+b).
+int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16)
+{
+    const tf_params& P = h->P;
+    hipStream_t s = h->stream;
+    const Geom g0 = h->tv.lv[0];
+    if (f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->tv.pyr[0], g0, 1);
+    else hipLaunchKernelGGL(k_u8_to_f32, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, dframes, h->tv.pyr[0], g0);
+    for (int l = 1; l < h->tv.nlev; ++l) {
+        const double sc = 1.0 / P.scale_step;   // resize(src, Size(), fx, fy): scale = 1/fx
+        hipLaunchKernelGGL(k_pyr_down, grid64x4(h->tv.lv[l], F), dim3(256), 0, s, h->tv.pyr[l - 1], h->tv.lv[l - 1], h->tv.pyr[l], h->tv.lv[l], sc, sc,
+                           P.variant == TF_VARIANT_CUDA ? 1 : 0);
+    }
+    if (P.variant == TF_VARIANT_CUDA)
+        for (int l = 0; l < h->tv.nlev; ++l)
+            hipLaunchKernelGGL(k_grad, grid64x4(h->tv.lv[l], F), dim3(256), 0, s, h->tv.pyr[l], h->tv.gxl[l], h->tv.gyl[l], h->tv.lv[l]);
+    const int L = h->tv.nlev - 1;
+    hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.ctl, B, 0);
+    HIPC(h, hipMemset2DAsync(h->tv.sb.u1[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
+    HIPC(h, hipMemset2DAsync(h->tv.sb.u2[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
+    for (int l = L; l >= 0; --l) {
+        for (int wi = 0; wi < P.warps; ++wi) {
+            int rc = run_stage(h, l, wi, B, off0, off1);
+            if (rc) return rc;
+        }
+        if (l == 0) break;
+        const Geom gs = h->tv.lv[l], gd = h->tv.lv[l - 1];
+        // resize(u, size(I0s[s-1])): inv_scale = dsize/ssize, scale = 1/inv_scale
+        const double sx = 1.0 / ((double)gd.w / gs.w), sy = 1.0 / ((double)gd.h / gs.h);
+        hipLaunchKernelGGL(k_flow_up, grid64x4(gd, B), dim3(256), 0, s, h->tv.sb, h->tv.ctl, gs, gd, sx, sy, (float)(1 / P.scale_step),
+                           P.variant == TF_VARIANT_CUDA ? 1 : 0);
+        hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.ctl, B, 1);
+    }
+    if (out_f16) hipLaunchKernelGGL(k_output<uint16_t>, out_grid<uint16_t>(g0, B), dim3(256), 0, s, h->tv.sb, h->tv.ctl, g0, scale, (uint16_t*)dflow);
+    else hipLaunchKernelGGL(k_output<float>, out_grid<float>(g0, B), dim3(256), 0, s, h->tv.sb, h->tv.ctl, g0, scale, (float*)dflow);
+    HIPC(h, hipGetLastError());
+    return TF_OK;
+}
+
+// algorithmic (compulsory) HBM bytes of one solved pair from its executed iteration counts
+void account_bytes(const Engine* h, const int* it /* [nlev][warps][2] */, double* iter_bytes, double* total_bytes,
+                   unsigned long long* n_in, unsigned long long* n_out)
+{
+    const int warps = h->P.warps;
+    double ib = 0, tb = 0;
+    for (int l = 0; l < h->tv.nlev; ++l) {
+        const double px = (double)h->tv.lv[l].w * h->tv.lv[l].h;
+        for (int w = 0; w < warps; ++w) {
+            const int ni = it[(l * warps + w) * 2], no = it[(l * warps + w) * 2 + 1];
+            *n_in += ni; *n_out += no;
+            ib += px * 60.0 * ni;                                   // tvl1_iter: 9 reads + 6 writes
+            tb += px * (16.0 * (h->P.median_filtering > 1 ? no : 0)  // median: read+write u1,u2
+                        + 28.0);                                    // warp: read I0,I1,u1,u2; write I1wx,I1wy,rho_c
+        }
+        if (l > 0) tb += px * 8.0 + (double)h->tv.lv[l - 1].w * h->tv.lv[l - 1].h * 8.0;          // flow upsample
+        if (l > 0) tb += 2.0 * (px * 4.0 + (double)h->tv.lv[l - 1].w * h->tv.lv[l - 1].h * 4.0);  // pyramid level (2 frames)
+    }
+    tb += (double)h->tv.lv[0].w * h->tv.lv[0].h * (2.0 * (1 + 4) + 8.0 + 8.0);  // u8->f32 of 2 frames, output interleave
+    *iter_bytes += ib; *total_bytes += tb + ib;
+}
+}  // namespace

@@ -126,6 +126,6 @@ def test_deep_pyramid_solve_stops_at_the_cap(oracle):
 
 def test_hip_engine_caps_the_pyramid_at_the_same_depth(oracle):
     """The engine's DF_MAXLEV and the oracle's cap are one rule written in two files."""
-    src = open(os.path.join(ROOT, "tee_optical_flow_amd", "csrc", "teeflow.hip")).read()
+    src = open(os.path.join(ROOT, "tee_optical_flow_amd", "csrc", "teeflow_engine.hip.h")).read()
     m = re.search(r"constexpr int DF_MAXLEV = (\d+);", src)
     assert m and int(m.group(1)) == oracle.deepflow_max_levels()

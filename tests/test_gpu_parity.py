@@ -128,6 +128,72 @@ def test_every_iteration_kernel_form_end_to_end(oracle, variant, params):
     eng.close()
 
 
+def test_one_engine_through_reallocations(oracle):
+    """One engine that solves every call alone ("queue_lanes" 0, sub-batches of 2) is taken through every reason its solver has to
+    give its buffers back and allocate again -- another frame size, a larger capacity, three sub-batches in one call, another pyramid
+    depth, the CUDA-class variant's gradient planes, and the same for DeepFlow -- and gives the oracle's flow (and iteration counts)
+    bit for bit each time.  A second round of the same engines, made and closed, leaves the device's free memory where the first did."""
+    import ctypes
+    import tee_optical_flow_amd as T
+    from tee_optical_flow_amd import _lib
+    from tee_optical_flow_amd.synth import speckle_pairs
+    hip = _lib.load()                                            # (the HIP runtime the library is bound to, as in test_gpu_queue.py)
+
+    def free_bytes():
+        f, t = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert hip.hipDeviceSynchronize() == 0 and hip.hipMemGetInfo(ctypes.byref(f), ctypes.byref(t)) == 0
+        return f.value
+    A0, A1 = speckle_pairs(range(300, 305), 48, 64)
+    B0, B1 = speckle_pairs(range(310, 312), 40, 56)
+    C0, C1 = speckle_pairs(range(320, 325), 40, 52)
+    D0, D1 = speckle_pairs(range(330, 331), 64, 64)
+    refs = {}                                                    # computed once, in the first round
+
+    def ref(key, fn):
+        if key not in refs:
+            refs[key] = fn()
+        return refs[key]
+
+    def tvl1(eng, name, I0s, I1s, **op):
+        flows, iters = eng.calc_pairs(I0s, I1s), eng.last_iters()
+        assert iters.shape[0] == len(I0s)
+        for b in range(len(I0s)):
+            r, r_it, nl = ref((name, b), lambda: oracle.tvl1_calc(I0s[b], I1s[b], oracle.default_params(**op), return_iters=True))
+            assert np.array_equal(iters[b], r_it[:nl]), f"{name}: pair {b} iteration counts"
+            assert np.array_equal(flows[b], r), f"{name}: pair {b} flow"
+
+    def deep(eng, name, I0s, I1s):
+        flows = eng.calc_pairs(I0s, I1s)
+        for b in range(len(I0s)):
+            assert np.array_equal(flows[b], ref((name, b), lambda: oracle.deepflow_calc(I0s[b], I1s[b]))), f"{name}: pair {b} flow"
+
+    free = []
+    for rnd in range(2):
+        eng = T.DenseFlow(max_batch=2)
+        eng.set_tuning("queue_lanes", 0)
+        tvl1(eng, "48x64", A0[:2], A1[:2])
+        tvl1(eng, "40x56", B0[:1], B1[:1])                       # another size, a smaller capacity
+        tvl1(eng, "48x64", A0, A1)                               # back, and three sub-batches (2 + 2 + 1)
+        assert eng.counter("queue_jobs") == 0 and eng.last_stats["nscales_used"] == 5
+        eng.setScalesNumber(3)
+        tvl1(eng, "48x64 nscales 3", A0, A1, nscales=3)          # same size and capacity, another pyramid
+        assert eng.last_stats["nscales_used"] == 3
+        cud = T.DenseFlow(max_batch=2, variant="cuda")
+        cud.set_tuning("queue_lanes", 0)
+        tvl1(cud, "cuda 48x64", A0[:2], A1[:2], variant=1)
+        tvl1(cud, "cuda 40x56", B0, B1, variant=1)
+        dfl = T.DenseFlow(max_batch=2, algo="deepflow")
+        dfl.set_tuning("queue_lanes", 0)
+        deep(dfl, "40x52", C0[:2], C1[:2])
+        deep(dfl, "64x64", D0, D1)
+        deep(dfl, "40x52", C0, C1)
+        assert dfl.counter("queue_jobs") == 0
+        for e in (eng, cud, dfl):
+            e.close()
+        free.append(free_bytes())
+    assert free[1] >= free[0] - (8 << 20), [f >> 20 for f in free]  # MiB free after each round
+
+
 def test_two_lane_split_of_large_batches(oracle):
     """Batches of >= 32 pairs are split over two (handle, stream, host thread) lanes; results and per-pair iteration counts
     must be those of the single-lane run (and of the oracle), in the caller's pair order; sequence mode overlaps one frame."""

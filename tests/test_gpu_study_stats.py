@@ -159,3 +159,34 @@ def test_beside_a_submitted_study(z):
         want = {c: tuple(z[f"{p}/{c}/{k}"] for k in ("freq", "edges", "hi", "lo")) for c in COMPS}
         _same_stats(beside[p], want, p)
     assert np.array_equal(flows, serial)
+
+
+def test_analysis_session_survives_a_solve():
+    """The planes a projection leaves on the device belong to the handle, not to its solver: a solve on the same engine -- here one that
+    makes the solver allocate, on an engine without lanes -- leaves tf_radlong_hist's answer and tf_radlong_shape's as they were."""
+    import ctypes as C
+    import tee_optical_flow_amd as T
+    from tee_optical_flow_amd import _lib
+    from tee_optical_flow_amd.synth import speckle_pair
+    rng = np.random.default_rng(14)
+    flow = rng.normal(0, 2, (3, 24, 32, 2)).astype(np.float32)
+    cent = [(11.5, 15.25), (12.0, 16.0), (3.75, 30.5)]
+    edges = np.linspace(-6.0, 6.0, 41)
+    eng = T.DenseFlow(device_id=0)
+    eng.set_tuning("queue_lanes", 0)
+
+    def session():
+        freq, shape = np.zeros((3, 40), np.int64), (C.c_int * 3)()
+        _lib.check(eng._L.tf_radlong_hist(eng._h, 0, edges.ctypes.data, 40, freq.ctypes.data), eng._h, "tf_radlong_hist")
+        _lib.check(eng._L.tf_radlong_shape(eng._h, C.byref(shape)), eng._h, "tf_radlong_shape")
+        return freq, tuple(shape)
+    try:
+        A.radlong_stats_device(eng, flow, cent)
+        before, shape = session()
+        assert shape == (3, 24, 32) and before.sum() > 0
+        I0, I1, _ = speckle_pair(9, 48, 64)
+        assert eng.calc(I0, I1, None).shape == (48, 64, 2)
+        after, shape = session()
+    finally:
+        eng.close()
+    assert np.array_equal(after, before) and shape == (3, 24, 32)

@@ -51,7 +51,8 @@ extern "C" {
                               tf_saliency_frames_f32, tf_calc_seq_saliency_f32) and changed no struct and no signature: still 2; so did
                               tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param, tf_otsu_masks,
                               tf_radlong_overlay, tf_segmentor_input, tf_segmentor_classmap, and the float16 payload calls
-                              (tf_calc_seq_rgb_f16, tf_submit_seq_rgb_f16, tf_calc_seq_saliency_f16, tf_echo_frames, tf_dbg_f16_round) */
+                              (tf_calc_seq_rgb_f16, tf_submit_seq_rgb_f16, tf_calc_seq_saliency_f16, tf_echo_frames, tf_dbg_f16_round)
+                              and the WASE study calls (tf_calc_seq_rgb_wase, tf_calc_seq_saliency_wase) */
 
 enum {
     TF_OK = 0,
@@ -235,6 +236,26 @@ int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W,
 int tf_calc_seq_saliency_f16(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, float scale,
                              uint16_t* flow16_out, uint16_t* echo16_out, tf_stats* st);
 int tf_echo_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint16_t* echo16_out);
+
+/* A study with "WASE" background compensation (tf_wase_compensate, below) in ONE call: tf_calc_seq_rgb / tf_calc_seq_saliency (map_f32:
+ * the maps reach the solver as float32) at scale 1, the compensation of all N-1 flows against the bkgd mask, the unit scale and the
+ * output type, without the flows leaving the device in between:
+ *   F[p]          = the solver's float32 flow of frames p, p+1                          (resident, never copied out)
+ *   background[p] = np.mean(masked[masked != 0]),  masked = F[p] * bkgd                  (numpy's summation order, as tf_wase_compensate)
+ *   flow_out[p]   = (F[p] - background[p]) * scale
+ * with three roundings: the difference to float32, the product to float32 (never contracted), and -- out_f16 != 0 -- that float32
+ * to half, nearest-even, subnormal halves kept: numpy's `((F[p] - bg) * np.float32(scale))` and its `.astype(np.float16)`, bit for bit.
+ * bkgd: host bool bytes [n_frames][H][W][2], n_frames >= 1 and free of N.  flow_out: host [N-1][H][W][2], float32 or (out_f16) halves;
+ * echo16_out: host [N][H][W] halves as for the *_f16 calls, or NULL (the saliency form: channels == 3 only); background_out: host
+ * float32 [N-1], or NULL.  An empty selection gives a NaN background and NaN flows, as numpy does.  Arguments are checked as by the
+ * calls combined here (TF_ERR_INVALID_ARG: null pointers, N < 2, sizes < 1, n_frames < 1, an echo of non-RGB frames; TF_ERR_UNSUPPORTED:
+ * more than 65535 frames or mask frames); a refused call has done no work.  Device memory per study, grown on demand and kept with
+ * the handle: (N-1) H W 8 bytes of flows, n_frames H W 8 of compacted products, n_frames H W 2 of mask, and the output. */
+int tf_calc_seq_rgb_wase(tf_handle* h, const uint8_t* rgb, int N, int H, int W, const uint8_t* bkgd, int n_frames, float scale, int out_f16,
+                         void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st);
+int tf_calc_seq_saliency_wase(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, const uint8_t* bkgd,
+                              int n_frames, float scale, int out_f16, void* flow_out, uint16_t* echo16_out, float* background_out,
+                              tf_stats* st);
 
 /* Mask cleaning of the segmentor modes, `clean_mask` of the reference (calculate_optical_flow.py:90-111 moving_avg_mask, :113-182
  * clean_mask), on the device and exact: for each label l (class id class_ids[l]) and frame,

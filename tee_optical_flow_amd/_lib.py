@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "tf_set_tuning", "tf_dbg_counter", "tf_default_deepflow_params", "tf_create_deepflow", "tf_dbg_df_refine", "tf_dbg_df_blur", "tf_dbg_launch_profile", "tf_dbg_strip_rule", "tf_wase_compensate", "tf_wase_compensate_device", "tf_host_alloc", "tf_host_free",
     "tf_dbg_pyramid", "tf_dbg_resize", "tf_dbg_warp", "tf_dbg_median", "tf_dbg_iterate",
     "tf_calc_seq_rgb_f16", "tf_submit_seq_rgb_f16", "tf_calc_seq_saliency_f16", "tf_echo_frames", "tf_dbg_f16_round",
+    "tf_calc_seq_rgb_wase", "tf_calc_seq_saliency_wase",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -132,6 +133,8 @@ def load():
     L.tf_submit_seq_rgb_f16.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, C.POINTER(i32)]
     L.tf_calc_seq_saliency_f16.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, C.POINTER(TfStats)]
     L.tf_echo_frames.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.tf_calc_seq_rgb_wase.argtypes = [vp, vp, i32, i32, i32, vp, i32, f32, i32, vp, vp, vp, C.POINTER(TfStats)]
+    L.tf_calc_seq_saliency_wase.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, i32, vp, vp, vp, C.POINTER(TfStats)]
     L.tf_dbg_f16_round.argtypes = [vp, vp, C.c_size_t, f32, vp]
     L.tf_radlong_project.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.tf_radlong_hist.argtypes = [vp, i32, vp, i32, vp]

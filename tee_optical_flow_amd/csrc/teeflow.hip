@@ -220,6 +220,7 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "coop_rearms") { v = 0; for (auto& c : all) v += c.rearms; }
     else if (n == "coop_cooldown") { v = 0; for (auto& c : all) v = v > c.cooldown ? v : c.cooldown; }
     else if (n == "saliency_kernel_us") v = (long long)(h->pre_kernel_ms * 1000.0);
+    else if (n == "wase_study_kernel_us") v = (long long)(h->wase_kernel_ms * 1000.0);
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "streams_serialised") v = h->streams_serialised;

@@ -187,11 +187,14 @@ struct tf_handle : Engine {
            PRE_OV_IDX, PRE_OV_ECHO, PRE_OV_OUT, PRE_OV_META,                      // tf_radlong_overlay
            PRE_WA_VALS, PRE_WA_CNT, PRE_WA_OFF, PRE_WA_SUM, PRE_WA_BG,            // WASE: compacted products, block counts / offsets, piece
                                                                                   //   sums, per-flow backgrounds
+           PRE_WS_FLOW, PRE_WS_OUT,                                               // a WASE study call (tf_calc_seq_*_wase): the solver's resident
+                                                                                  //   float32 flows, the compensated output in the call's type
            PRE_SG_IN, PRE_SG_IDX, PRE_SG_MAP,                                     // tf_segmentor_input (tables, LUT, frames), tf_segmentor_classmap
            PRE_ECHO,                                                              // the study's float16 `echo` (tf_echo_frames, the *_f16 calls)
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
+    double wase_kernel_ms = 0;   // device time of the last WASE study call's reduction and output kernels (the same events)
     // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
     // ([0]: upload done) and the device scratch ([1]: kernel done) of the last call may be written again
     void* seg_stage = nullptr; size_t seg_stage_cap = 0; hipEvent_t seg_ev[2] = {};

@@ -950,8 +950,8 @@ TF_API void tf_host_free(void* p)
 
 // ---- WASE background compensation (rows a7 / f2) ---------------------------------------------------------------
 namespace {
-// flows, bkgd: device.  Leaves the backgrounds in (*dbg)[0..P) and the compensated, scaled flows in place.
-int wase_device(tf_handle* h, float* flows, const uint8_t* bkgd, int P, int N, int H, int W, float scale, float** dbg)
+// flows, bkgd: device.  The per-flow reduction -- count, scan, scatter, piece sums, finish -- leaves the backgrounds in (*dbg)[0..P).
+int wase_backgrounds(tf_handle* h, const float* flows, const uint8_t* bkgd, int P, int N, int H, int W, float** dbg)
 {
     const size_t hw2 = (size_t)H * W * 2;
     const int C = (int)((hw2 + WASE_CHUNK - 1) / WASE_CHUNK);
@@ -972,10 +972,20 @@ int wase_device(tf_handle* h, float* flows, const uint8_t* bkgd, int P, int N, i
         hipLaunchKernelGGL(k_wase_piece_sums, dim3((unsigned)npieces), dim3(512), 0, s, wa, woff + ncnt, wsum);
         hipLaunchKernelGGL(k_wase_finish, dim3(1), dim3(64), 0, s, wsum, woff + ncnt, wbg + p);
     }
-    const unsigned gx = (unsigned)std::min<size_t>((hw2 + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_wase_apply, dim3(gx, P), dim3(256), 0, s, flows, wbg, hw2, scale);
     HIPC(h, hipGetLastError());
     *dbg = wbg;
+    return TF_OK;
+}
+
+// the reduction, then the apply: leaves the compensated, scaled flows in place
+int wase_device(tf_handle* h, float* flows, const uint8_t* bkgd, int P, int N, int H, int W, float scale, float** dbg)
+{
+    const int rc = wase_backgrounds(h, flows, bkgd, P, N, H, W, dbg);
+    if (rc) return rc;
+    const size_t hw2 = (size_t)H * W * 2;
+    const unsigned gx = (unsigned)std::min<size_t>((hw2 + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_wase_apply, dim3(gx, P), dim3(256), 0, h->stream, flows, *dbg, hw2, scale);
+    HIPC(h, hipGetLastError());
     return TF_OK;
 }
 
@@ -1023,4 +1033,69 @@ TF_API int tf_wase_compensate(tf_handle* h, float* flows, int n_flows, const uin
     if (!h) return TF_ERR_INVALID_ARG;
     if (!flows || !bkgd || n_flows < 1 || n_frames < 1 || H < 1 || W < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_wase_compensate: bad argument");
     return finish_host_call(h, wase_compensate(h, flows, n_flows, bkgd, n_frames, H, W, scale, background_out));
+}
+
+// ---- a WASE-compensated study in one call: frames and bkgd mask in, (flow - background) * scale out -------------------------------
+namespace {
+// What tf_calc_seq_rgb_wase and tf_calc_seq_saliency_wase share (saliency: the solver's frames are the saliency maps, uint8 or --
+// map_f32 -- float).  The flows never leave the device between the solve and the compensation: the solver writes them, unscaled
+// float32, into PRE_WS_FLOW (the lanes and sub-batches of tf_calc_seq_device), the reduction reads them there, and k_wase_out
+// writes the compensated, scaled flows in the call's output type into PRE_WS_OUT, which is copied to the caller's buffer.
+int calc_seq_wase(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool saliency, bool map_f32, const uint8_t* bkgd,
+                  int n_frames, float scale, bool out_f16, void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st)
+{
+    if (saliency && channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
+    if (echo16_out && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "the echo needs RGB frames (channels == 3), got %d", channels);
+    if (!bkgd || n_frames < 1) return fail(h, TF_ERR_INVALID_ARG, "a wase study needs a bkgd mask of at least 1 frame, got %d", n_frames);
+    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, 1.0f, flow_out, W_HOST, saliency && map_f32, out_f16};
+    int rc = check_call(h, c);
+    if (rc) return rc;
+    if (N > 65535 || n_frames > 65535) return fail(h, TF_ERR_UNSUPPORTED, "a wase study takes at most 65535 frames and mask frames");   // (grid dimensions)
+    const int P = N - 1;
+    const size_t hw2 = (size_t)H * W * 2, elt = out_f16 ? sizeof(uint16_t) : sizeof(float);
+    void* dfr = nullptr;
+    if (saliency) rc = saliency_to_device(h, frames, N, H, W, channels, map_f32, &dfr, echo16_out);
+    else { uint8_t* dgray = nullptr; rc = condition_to_device(h, frames, N, H, W, &dgray, nullptr, echo16_out); dfr = dgray; }
+    if (rc) return rc;
+    Pre pre(h);
+    auto* dflow = pre.get<float>(tf_handle::PRE_WS_FLOW, (size_t)P * hw2);
+    auto* dout = pre.get<uint8_t>(tf_handle::PRE_WS_OUT, (size_t)P * hw2 * elt);
+    auto* dmask = pre.get<uint8_t>(tf_handle::PRE_AN_MASK, (size_t)n_frames * hw2);
+    if (pre.rc) return pre.rc;
+    c.in0 = (const uint8_t*)dfr; c.out = dflow; c.where = W_DEV; c.out_f16 = false;
+    rc = calc_entry(h, c, st);                            // (returns with every lane's stream drained: the flows are there)
+    if (rc) return rc;
+    const hipStream_t s = h->stream;
+    HIPC(h, hipMemcpyAsync(dmask, bkgd, (size_t)n_frames * hw2, hipMemcpyHostToDevice, s));
+    HIPC(h, hipEventRecord(h->ev[0], s));                 // the reduction and the output kernel, without the copies
+    float* wbg = nullptr;
+    rc = wase_backgrounds(h, dflow, dmask, P, n_frames, H, W, &wbg);
+    if (rc) return rc;
+    const Geom g = make_geom(W, H);
+    if (out_f16) hipLaunchKernelGGL(k_wase_out<uint16_t>, out_grid<uint16_t>(g, P), dim3(256), 0, s, dflow, wbg, H, W, scale, (uint16_t*)dout);
+    else hipLaunchKernelGGL(k_wase_out<float>, out_grid<float>(g, P), dim3(256), 0, s, dflow, wbg, H, W, scale, (float*)dout);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipEventRecord(h->ev[1], s));
+    HIPC(h, hipMemcpyAsync(flow_out, dout, (size_t)P * hw2 * elt, hipMemcpyDeviceToHost, s));
+    if (background_out) HIPC(h, hipMemcpyAsync(background_out, wbg, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    float t = 0;
+    HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
+    h->wase_kernel_ms = t;
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_calc_seq_rgb_wase(tf_handle* h, const uint8_t* rgb, int N, int H, int W, const uint8_t* bkgd, int n_frames, float scale, int out_f16,
+                                void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    return finish_host_call(h, calc_seq_wase(h, rgb, N, H, W, 3, false, false, bkgd, n_frames, scale, out_f16 != 0, flow_out, echo16_out, background_out, st));
+}
+TF_API int tf_calc_seq_saliency_wase(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, const uint8_t* bkgd,
+                                     int n_frames, float scale, int out_f16, void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    return finish_host_call(h, calc_seq_wase(h, frames, N, H, W, channels, true, map_f32 != 0, bkgd, n_frames, scale, out_f16 != 0, flow_out, echo16_out,
+                                             background_out, st));
 }

@@ -161,3 +161,24 @@ __global__ __launch_bounds__(256) void k_wase_apply(float* __restrict__ flows, c
     float* f = flows + (size_t)p * hw2;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < hw2; i += (size_t)gridDim.x * 256) f[i] = (f[i] - b) * scale;
 }
+
+// The same values into a buffer of their own, in the call's output type: out[p] = (flows[p] - background[p]) * scale, flows [P][H][W][2]
+// float32 left as they are.  T = float: the difference and the product, each rounded to float32 (no contraction: -ffp-contract=off).
+// T = uint16_t: float16 bits -- that float32 product rounded once more, to half (scaled_half_bits; store_flow_row_f16's aligned
+// 8-byte stores, two pixels per thread): numpy's `((flow - bg) * np.float32(scale)).astype(np.float16)`.  Launched on out_grid<T>.
+template <typename T>
+__global__ __launch_bounds__(256) void k_wase_out(const float* __restrict__ flows, const float* __restrict__ bg, int H, int W, float scale,
+                                                  T* __restrict__ out)
+{
+    const int t = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), p = blockIdx.z;
+    if (y >= H) return;
+    const float b = bg[p];
+    const size_t row = ((size_t)p * H + y) * W;                        // in pixels
+    const float2* f = reinterpret_cast<const float2*>(flows) + row;
+    if constexpr (sizeof(T) == 4) {
+        if (t >= W) return;
+        const float2 v = f[t];
+        reinterpret_cast<float2*>(out)[row + t] = make_float2((v.x - b) * scale, (v.y - b) * scale);
+    } else
+        store_flow_row_f16(out + row * 2, W, t, scale, [&](int px) { const float2 v = f[px]; return make_float2(v.x - b, v.y - b); });
+}

@@ -90,6 +90,7 @@ class DenseFlow:
 
     device_unit_scale = True        # calc_study(scale=, pad_last=) applies the unit scale in the output kernel (pipeline.flow_for_study)
     device_payload = True           # calc_study_payload & co. hand over the study file's float16 `flow` and `echo` (process_folder(payload="device"))
+    device_wase = True              # calc_study_wase & co. solve and compensate a bkgd_comp="WASE" study in one call, float32 or float16
 
     _SETTERS = {"Tau": "tau", "Lambda": "lambda", "Theta": "theta", "ScalesNumber": "nscales",
                 "WarpingsNumber": "warps", "Epsilon": "epsilon", "InnerIterations": "inner_iterations",
@@ -190,7 +191,8 @@ class DenseFlow:
 
     def counter(self, name):
         """Debug counters of the engine (tf_dbg_counter): coop_launches, coop_aborts, coop_disabled, coop_rearms, coop_cooldown, coop_occ16, coop_occ8,
-        queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised."""
+        queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised,
+        saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels)."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
     def _finish(self, st):
@@ -581,6 +583,51 @@ class DenseFlow:
         _lib.check(self._L.tf_wase_compensate(self._h, flows.ctypes.data, P, mask.view(np.uint8).ctypes.data, mask.shape[0], H, W,
                                               float(scale), bg.ctypes.data), self._h, "tf_wase_compensate")
         return flows, bg
+
+    # ---- a bkgd_comp="WASE" study in one call: the flows stay on the device between the solve and the compensation -------------
+    def _wase_study(self, nparr, bkgd_mask, scale, pad_last, f16, echo, saliency, map_dtype="f32"):
+        """-> (flows [N or N-1,H,W,2] float32 or float16, echo16 or None, backgrounds float32 [N-1]), the arrays in pinned host memory"""
+        nparr = self._rgb_study(nparr)
+        N, H, W, _ = nparr.shape
+        mask = np.ascontiguousarray(bkgd_mask)
+        if mask.dtype != np.bool_ or mask.ndim != 4 or mask.shape[0] < 1 or mask.shape[1:] != (H, W, 2):
+            raise OpticalFlowCalculationError(f"bkgd mask must be bool [n>=1,{H},{W},2], got {mask.dtype} {mask.shape}")
+        out = self._pool.empty((N if pad_last else N - 1, H, W, 2), np.float16 if f16 else np.float32)
+        e16 = self._pool.empty((N, H, W), np.float16) if echo else None
+        bg = np.empty(N - 1, np.float32)
+        st = _lib.TfStats()
+        tail = (mask.view(np.uint8).ctypes.data, mask.shape[0], float(scale), 1 if f16 else 0, out.ctypes.data,
+                e16.ctypes.data if echo else None, bg.ctypes.data, C.byref(st))
+        if saliency:
+            _lib.check(self._L.tf_calc_seq_saliency_wase(self._h, nparr.ctypes.data, N, H, W, 3, 1 if self._map_is_f32(map_dtype) else 0, *tail),
+                       self._h, "tf_calc_seq_saliency_wase")
+        else:
+            _lib.check(self._L.tf_calc_seq_rgb_wase(self._h, nparr.ctypes.data, N, H, W, *tail), self._h, "tf_calc_seq_rgb_wase")
+        self._finish(st)
+        if pad_last:
+            out[N - 1] = out[N - 2]
+        return out, e16, bg
+
+    def calc_study_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False):
+        """calc_study, then wase_compensate of its flows, in one device call: RGB study uint8 [N,H,W,3] and bkgd_mask bool [n,H,W,2]
+        (mask_dict['bkgd']) -> ((flow - background[p]) * scale float32 [N-1,H,W,2], backgrounds float32 [N-1]), with the bits of
+        wase_compensate(calc_study(nparr), bkgd_mask, scale).  `pad_last` as in calc_study."""
+        out, _, bg = self._wase_study(nparr, bkgd_mask, scale, pad_last, False, False, False)
+        return out, bg
+
+    def calc_study_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True):
+        """calc_study_wase with the flows rounded to float16 by the output kernel -> (flow16, echo16 | None, backgrounds): flow16 has
+        the bits of calc_study_wase(...)[0].astype(np.float16), echo16 is echo_frames(nparr) from the same upload."""
+        return self._wase_study(nparr, bkgd_mask, scale, pad_last, True, echo, False)
+
+    def calc_study_saliency_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False, map_dtype="f32"):
+        """calc_study_wase with the saliency maps as the solver's frames (calc_study_saliency) -> (flows float32, backgrounds)."""
+        out, _, bg = self._wase_study(nparr, bkgd_mask, scale, pad_last, False, False, True, map_dtype)
+        return out, bg
+
+    def calc_study_saliency_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, map_dtype="f32"):
+        """calc_study_saliency_wase with float16 flows and the `echo` of the RGB frames -> (flow16, echo16 | None, backgrounds)."""
+        return self._wase_study(nparr, bkgd_mask, scale, pad_last, True, echo, True, map_dtype)
 
     def calc_pairs(self, I0s, I1s):
         """B independent pairs: uint8 or float32 [B,H,W] x2 -> float32 [B,H,W,2] (float frames: DualTVL1 scales them by 255 like cv2, DeepFlow

@@ -100,7 +100,14 @@ def flow_for_study(frames_u8, OF_model, mask_dict=None, bkgd_comp="none", conver
         if bkgd_comp == "none":
             # unit scale in the output kernel, last flow repeated inside the pinned result buffer (as the no_saliency=True branch below)
             return OF_model.calc_study_saliency(nparr_rgb, scale=conversion_factor, pad_last=True, map_dtype=saliency_map)
+        if hasattr(OF_model, "calc_study_saliency_wase"):
+            # solve, compensation and unit scale in one device call (as the no_saliency=True branch below)
+            return OF_model.calc_study_saliency_wase(nparr_rgb, mask_dict["bkgd"], scale=conversion_factor, pad_last=True, map_dtype=saliency_map)[0]
         flows = OF_model.calc_study_saliency(nparr_rgb, map_dtype=saliency_map)          # saliency maps (:586) + all pairs on the device
+    elif nparr_rgb is not None and bkgd_comp == "WASE" and hasattr(OF_model, "calc_study_wase"):
+        # the flows stay on the device between the solve and the compensation: (flow - background) * factor comes back once, the last
+        # flow repeated inside the pinned result buffer -- the bits of calc_study + wase_compensate + concatenate below
+        return OF_model.calc_study_wase(nparr_rgb, mask_dict["bkgd"], scale=conversion_factor, pad_last=True)[0]
     elif nparr_rgb is not None and hasattr(OF_model, "calc_study"):
         if bkgd_comp == "none" and getattr(OF_model, "device_unit_scale", False):
             # the unit scale (:600, one float32 multiply per value, the same one numpy makes) is applied by the output kernel and
@@ -130,11 +137,13 @@ def _check_payload(payload):
 
 
 def _device_payload_refused(model, bkgd_comp, nparr=None):
-    """Why payload="device" cannot serve, as (kind, message) (None: it can): the model must offer the float16 study calls (DenseFlow.device_payload), the
-    study must need no background compensation (WASE works on float32 flows), and its frames -- once read -- must be uint8 RGB."""
+    """Why payload="device" cannot serve, as (kind, message) (None: it can): the model must offer the float16 study calls (DenseFlow.device_payload),
+    a study with background compensation needs a model that compensates on the device too (DenseFlow.device_wase; without it WASE works on
+    float32 flows on the host path), and its frames -- once read -- must be uint8 RGB."""
     if model is not None and not getattr(model, "device_payload", False):
         return "model", f"the flow model ({type(model).__name__}) does not offer the float16 study calls"
-    if bkgd_comp != "none":
+    # (no model yet: the walk makes a DenseFlow, which offers both)
+    if bkgd_comp != "none" and not (bkgd_comp == "WASE" and (model is None or getattr(model, "device_wase", False))):
         return "bkgd_comp", f"bkgd_comp={bkgd_comp!r} works on float32 flows"
     if nparr is not None and not (nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8):
         return "frames", f"the frames are not uint8 RGB [N,H,W,3] but {nparr.dtype} {nparr.shape}"
@@ -166,7 +175,8 @@ def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode=
     """Same positional signature as the reference (:478-483).  Keyword-only extras let a caller inject what the
     offline image cannot provide: `nparr` (frames instead of a DICOM), `metadata`, `mask_dict` (segmentation result),
     `flow_model`.  Returns the float32 flow array [N,H,W,2] that was written.  `payload="device"`: the engine hands over the file's
-    float16 `flow` and `echo` (DenseFlow.calc_study_payload; uint8 RGB frames, bkgd_comp="none", a model with `device_payload` --
+    float16 `flow` and `echo` (DenseFlow.calc_study_payload, or calc_study_wase_payload under bkgd_comp="WASE"; uint8 RGB frames, a model with
+    `device_payload` and, for WASE, `device_wase` --
     otherwise the host path, with one logged reason) and the float16 array that was written is returned; the file is the same."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
@@ -235,7 +245,14 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             # (from the upload the conditioning / saliency pass reads) come from the engine; the echo only where a file is written
             kw = dict(scale=conversion_factor, pad_last=True, echo=save_path is not None)
             rgb = np.ascontiguousarray(nparr)
-            if not no_saliency:
+            if bkgd_comp == "WASE":
+                # solve, background compensation, unit scale and rounding in one synchronous device call (the backgrounds are not kept)
+                if not no_saliency:
+                    pair = model.calc_study_saliency_wase_payload(rgb, mask_dict["bkgd"], map_dtype=saliency_map, **kw)[:2]
+                else:
+                    pair = model.calc_study_wase_payload(rgb, mask_dict["bkgd"], **kw)[:2]
+                collect = lambda: pair
+            elif not no_saliency:
                 pair = model.calc_study_saliency_payload(rgb, map_dtype=saliency_map, **kw)
                 collect = lambda: pair
             elif _submit and not own and hasattr(model, "submit_study_payload"):
@@ -624,7 +641,8 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     stage), and makes `echo` in the reader stage or the writer; "device" has the engine hand over both float16 arrays
     (DenseFlow.submit_study_payload / calc_study_payload / calc_study_saliency_payload: rounded by the output kernel, half the download;
     the echo from the frames the conditioning pass uploads anyway) -- the reader stage then makes no echo and the hand-over to the
-    writer stage is a plain copy.  It needs a model with `device_payload`, uint8 RGB frames and bkgd_comp="none"; otherwise the host
+    writer stage is a plain copy.  It needs a model with `device_payload`, uint8 RGB frames and, for bkgd_comp="WASE", a model with `device_wase` (such
+    studies are solved and compensated by one synchronous call, DenseFlow.calc_study_wase_payload); otherwise the host
     path serves, and the reason is logged once.  The files are the same either way.
     Returns the list of (filename, error string)."""
     if otsu_masks not in ("host", "device"):

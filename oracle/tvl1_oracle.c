@@ -16,9 +16,17 @@
  *
  *        >>>>>>>>  PARITY UNPINNED (vs real OpenCV)  <<<<<<<<
  *
- * What IS pinned: operator known-answer tests (tests/test_oracle_kat.py) and the behaviour-level
+ * What IS pinned: operator known-answer tests (tests/test_oracle_kat.py), the behaviour-level
  * KATs of SURVEY.md section 8c (zero flow on identical frames, recovery of a known translation,
- * transpose/flip symmetries).
+ * transpose/flip symmetries), and -- against tests/tvl1_ref64.py, a float64 whole-array reference
+ * written from the algorithm and not from the loops below (tests/test_tvl1_ref64_cpu.py) -- the
+ * iteration (thresholding and its three branches, l_t, taut, divergence, dual update, error sum),
+ * the warp, the pyramid and its truncation, the flow upsampling, the stage order (median before
+ * every outer iteration, duals zeroed per level and kept across warps, both loops under the stop
+ * rule) and whole solves of up to 6 stages with identical iteration counts, for both variants.
+ * What still is NOT pinned: real OpenCV.  The reference and this file were read from the same
+ * description; in particular they agree on the first-row / first-column divergence forms (below),
+ * so only cv2 can settle those against upstream.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  *

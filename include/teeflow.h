@@ -332,7 +332,7 @@ int tf_radlong_hist(tf_handle* h, int which, const double* edges, int nbins, lon
 int tf_radlong_select(tf_handle* h, int which, const long long* ranks, double* values_out);
 
 /* ---- the steps before the projection in calculate_3dhist_radlong(ds, param) (optical_flow/analyze_optical_flow.py:320-343), on the
- *      device.  Both run on the handle's stream and never on a lane's, so they may be called while tf_submit_* jobs of the handle are
+ *      device, and the area loop of the area-based cardiac-cycle detector.  All run on the handle's stream and never on a lane's, so they may be called while tf_submit_* jobs of the handle are
  *      in flight; both are host-synchronous; every argument is checked before any GPU work.
  * tf_av_centroids: calc_AV_centroid's per-frame loop (optical_flow/analyze_optical_flow.py:202-232, find_correct_centroid :202-211).
  *   masks: host uint8 [N][H][W][C], C = 1 or 2; frame n's set is masks[n][.][.][0] != 0, labelled with 8-connectivity
@@ -340,6 +340,15 @@ int tf_radlong_select(tf_handle* h, int which, const long long* ranks, double* v
  *   one whose first pixel in raster order comes first), exactly regionprops' coords.mean(axis=0); area_out[n] = its area, 0 for an
  *   empty frame (centroid (0, 0): the caller applies the reference's empty-frame rule, and the Savitzky-Golay filter).  Device
  *   scratch, grown on demand and kept by the handle: (26 + C) bytes per pixel of a chunk of frames of at most 512 MiB (at least one).
+ * tf_first_region_areas: the per-frame area loop of AreaDetector.detect (optical_flow/cardiac_cycle_detection.py:159-172:
+ *   skimage.measure.label, regionprops, props[0].area).  masks: host uint8 [N][H][W][C], C = 1 or 2; only channel 0 is read.
+ *   area_out[n] = the pixel count of the region labelled 1 in frame n: label joins 8-connected pixels of EQUAL value and numbers the
+ *   regions by their first pixel in raster order, so this is the 8-connected region of {masks[n][.][.][0] == v0} that holds the
+ *   frame's first non-zero pixel, v0 that pixel's value, whatever the sizes of the frame's other regions (tf_av_centroids' area is
+ *   the LARGEST region's, of the set != 0).  0 for an empty frame (a region has at least one pixel: the caller applies the
+ *   reference's empty-frame rule, and its smoother and peak search).  TF_ERR_INVALID_ARG for a null pointer, N, H or W < 1 or C outside
+ *   {1, 2}; TF_ERR_UNSUPPORTED, with a message, for H*W > 2^31 - 1.  Runs on the handle's stream and never on a lane's; host-synchronous.
+ *   Device scratch, grown on demand and kept by the handle: (6 + C) bytes per pixel of a chunk of frames of at most 512 MiB (at least one).
  * tf_radlong_project_param: tf_radlong_project of the parameter field OpticalFlowDataset builds (optical_flow/optical_flow_dataset.py:57,
  *   100-101, 182-228): vel = float32(flow); accel = np.gradient(vel, spacing, axis=0) over all N frames; pwr = vel * accel; each
  *   multiplied by the mask, all float32 as numpy keeps them.  flow: host [N][H][W][2], float16 (flow_is_f16, as the study file holds it)
@@ -352,6 +361,7 @@ int tf_radlong_select(tf_handle* h, int which, const long long* ranks, double* v
 #define TF_PARAM_ACCELERATION 1
 #define TF_PARAM_PWR 2
 int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* centroids_out, long long* area_out);
+int tf_first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, long long* area_out);
 int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask,
                              int mask_C, int param, double spacing, int grad_f64, const double* centroids, double* rad_out,
                              double* long_out, double* minmax, long long* nonzero);
@@ -447,7 +457,8 @@ int tf_device_count(void);
  * Both: "lanes" (contiguous units a call of at most one sub-batch is split into, solved side by side on the queue lanes), "queue_lanes" (lanes
  * that take those units, the sub-batches of larger calls and tf_submit_* jobs from the queue: -1 = 3 for DualTVL1, "lanes" for DeepFlow [default];
  * 0 = no lanes: the handle solves every call alone, sub-batch after sub-batch -- the same flows), "queue_unit" (pairs per queued sub-batch; 0 = equal sub-batches of at most max_batch pairs, a multiple of the lane count of them).
- * tf_radlong_overlay: "overlay_chunk_kib" (tests: the echo and output of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]). */
+ * tf_radlong_overlay: "overlay_chunk_kib" (tests: the echo and output of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]).
+ * tf_first_region_areas: "area_chunk_kib" (tests: the masks and labelling scratch of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]). */
 int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),
  * "coop_aborts" (calls repeated with the tiled form because such a launch gave up waiting), "coop_disabled"; "queue_jobs", "queue_units_done",

@@ -24,6 +24,11 @@ section 2).  With engine= the field, the transform, the angle histogram and mode
 the magnitude / angle statistics come from tf_radlong_hist / tf_radlong_select; without, numpy.  Pinned by
 tests/golden/reference_polar.npz (the reference's own calculate_3dhist and AngleDetector.detect, with cart_to_polar as cv2).
 
+And the other cardiac-cycle detector's per-frame series:
+  cardiac_cycle_detection.py:159-172  AreaDetector.detect's skimage label + regionprops, props[0].area  -> area_series
+With engine= the labelling runs on the device (tf_first_region_areas); without, a scipy twin that needs no skimage.  Pinned by
+tests/golden/reference_area_series.npz (the area_list the reference's own AreaDetector.detect handed to its smoother).
+
 And the overlay video of the rad/long projections:
   analyze_optical_flow.py:488-560  overlay3, visualize_radlong(ds, param, save_dir)                   -> radlong_overlay, visualize_radlong
   visualization.py:241-297, 1045-1051  VisualizationManager.visualize_radlong (other colormaps)       -> the colormap_rad / colormap_long keywords
@@ -569,6 +574,51 @@ def angle_mode_series(ds, param, label, *, engine=None):
     if not np.isfinite(mm).all():
         raise ValueError(f"the field holds NaN or inf (magnitude range [{mm[0]}, {mm[1]}], angle range [{mm[2]}, {mm[3]}])")
     return mode
+
+
+# ---- the area detector's per-frame region area ---------------------------------------------------------------------------------
+def _first_region_area(frame):
+    """props[0].area of skimage.measure.regionprops(skimage.measure.label(frame)), or None for a frame of zeros.  label joins
+    8-connected pixels of equal value and numbers the regions by their first pixel in raster order, so region 1 is the region of
+    {frame == v0} that holds the first non-zero pixel, v0 that pixel's value (checked against skimage 0.18.3 on bool, integer and
+    float masks of one to three non-zero values)."""
+    from scipy import ndimage
+    frame = np.asarray(frame)
+    flat = frame.ravel()
+    nz = np.flatnonzero(flat != 0)
+    if len(nz) == 0:
+        return None
+    lab, _ = ndimage.label(frame == flat[nz[0]], structure=np.ones((3, 3)))
+    return int((lab == lab.ravel()[nz[0]]).sum())
+
+
+def area_series(ds, label, *, engine=None):
+    """The per-frame series AreaDetector.detect (cardiac_cycle_detection.py:159-172) hands to its SpectralSmoother, its area_list:
+    for frames [0, ds.nframes) the area of the first region of ds.get_mask(label)[i, :, :, 0] (skimage label + regionprops,
+    props[0].area), int64; a frame without a region takes the previous frame's value (0 on frame 0) with a warning.  ds: an
+    OpticalFlowDataset, a FlowStudy or anything with get_mask(label) and nframes.  With `engine` (a DenseFlow) the labelling runs on
+    the device (tf_first_region_areas), with the same values; a mask that is neither bool nor uint8, or has other than 1 or 2
+    channels, runs on the host whatever the engine.  The smoother, the baseline and the peak search stay with the caller."""
+    mask_arr = ds.get_mask(label)
+    n = int(ds.nframes)
+    shape = np.shape(mask_arr)
+    if len(shape) != 4:
+        raise ValueError(f"the {label!r} mask must be [N,H,W,C], got shape {shape}")
+    if n > shape[0]:
+        raise IndexError(f"nframes {n} > {shape[0]} mask frames")
+    masks = np.asarray(mask_arr)[:max(n, 0)]
+    if engine is not None and masks.size > 0 and masks.dtype in (np.bool_, np.uint8) and masks.shape[3] in (1, 2):
+        found = [int(a) if a > 0 else None for a in engine.first_region_areas(masks)]
+    else:
+        found = [_first_region_area(masks[i, :, :, 0]) for i in range(n)]
+    out = np.zeros(max(n, 0), np.int64)
+    for i in range(n):
+        if found[i] is not None:
+            out[i] = found[i]
+        else:
+            out[i] = out[i - 1] if i > 0 else 0
+            log.warning("no %s mask at frame %d: area carried over", label, i)
+    return out
 
 
 # ---- the rad/long overlay video: visualize_radlong ---------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include "teeflow_masks.hip.h"
 #include "teeflow_otsu.hip.h"
 #include "teeflow_centroid.hip.h"
+#include "teeflow_area.hip.h"
 #include "teeflow_polar.hip.h"
 #include "teeflow_overlay.hip.h"
 #include "teeflow_segmentor.hip.h"
@@ -197,6 +198,7 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
     else if (n == "df_fuse_ds") h->df_fuse_ds = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (n == "warp_margin") h->warp_margin = value < 0 ? 0 : (value > 40 ? 40 : value);
     else if (n == "overlay_chunk_kib") h->overlay_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);   // never above the 512 MiB rule
+    else if (n == "area_chunk_kib") h->area_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);         // the same
     else return fail(h, TF_ERR_INVALID_ARG, "unknown tuning knob %s", name);
     return TF_OK;
 }

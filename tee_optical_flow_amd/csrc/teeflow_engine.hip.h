@@ -79,6 +79,7 @@ struct TfKnobs {
     int coop_test_mute = 0;      // tests: block 0 of every co-resident launch never raises its flag -> its neighbours give up -> the call is repeated tiled
     int profile = 0;
     int overlay_chunk_kib = 0;   // tests: tf_radlong_overlay's chunk of frames holds at most this many KiB instead of MASK_CHUNK_BYTES (0: that)
+    int area_chunk_kib = 0;      // tests: tf_first_region_areas' chunk of frames likewise
     unsigned sor_coop_arm = 0;   // bumped by tf_set_tuning("sor_coop", non-zero): a lane that sees a new value in a job's knobs re-arms the form
 };
 
@@ -177,10 +178,10 @@ struct tf_handle : Engine {
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
            PRE_LB_PAR, PRE_LB_AUX, PRE_LB_LR,                                     // the labelling's parents, per-root flags / sizes / areas and
-                                                                                  //   tile-local roots: tf_clean_masks, tf_otsu_masks, tf_av_centroids
+                                                                                  //   tile-local roots: tf_clean_masks, tf_otsu_masks, tf_av_centroids, tf_first_region_areas
            PRE_MK_CLS, PRE_MK_OUT, PRE_MK_META,                                   // tf_clean_masks
            PRE_OT_RGB, PRE_OT_CLEAN, PRE_OT_OUT, PRE_OT_META,                     // tf_otsu_masks
-           PRE_CT_MASK, PRE_CT_SUM, PRE_CT_OUT,                                   // tf_av_centroids
+           PRE_CT_MASK, PRE_CT_SUM, PRE_CT_OUT,                                   // tf_av_centroids; tf_first_region_areas (mask, out)
            PRE_AN_FLOW, PRE_AN_MASK, PRE_AN_META,                                 // the projections' uploads (also tf_wase_compensate's) and
            PRE_PO_META, PRE_PO_OUT,                                               //   meta words: rad/long's, polar's
            PRE_AN_HIST, PRE_AN_SEL,                                               // tf_radlong_hist, tf_radlong_select

@@ -1,5 +1,5 @@
 // The study tail's host code: everything around the solver -- frame conditioning, saliency, tf_clean_masks, tf_otsu_masks, the
-// segmentor's frame glue, tf_av_centroids, the rad/long and polar projections, histogram and radix select, the overlay, WASE.  Included by teeflow.hip (one
+// segmentor's frame glue, tf_av_centroids, tf_first_region_areas, the rad/long and polar projections, histogram and radix select, the overlay, WASE.  Included by teeflow.hip (one
 // translation unit); the kernels are in the kernel headers.  The entry points here keep their device scratch in the handle's PRE_*
 // slots (grown on demand, never shrunk, freed with the handle), so they neither allocate nor free once a study's sizes have been seen.
 // The one exception is tf_submit_seq_rgb, whose conditioned frames are a buffer of the queued job (allocated per study, freed with it).
@@ -706,6 +706,42 @@ int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C,
     return label_errors(h, derr, "tf_av_centroids");
 }
 
+// tf_first_region_areas: frames go through in chunks so that the per-chunk scratch (6 B per pixel, the parents and tile-local roots of
+// the PRE_LB_* slots every labelling call uses, + the mask bytes) stays within MASK_CHUNK_BYTES (tests: the area_chunk_kib knob) whatever
+// the study's length
+int first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, long long* area_out)
+{
+    using namespace fra;
+    const size_t HW = (size_t)H * W;
+    if (HW > 0x7fffffffu) return fail(h, TF_ERR_UNSUPPORTED, "tf_first_region_areas: at most 2^31 - 1 pixels per frame");
+    const size_t budget = h->area_chunk_kib > 0 ? (size_t)h->area_chunk_kib << 10 : MASK_CHUNK_BYTES;
+    const int nf = chunk_frames(HW * (6 + (size_t)C), N, 65535, budget);   // frames of a chunk are grid.y
+    HIPC(h, hipSetDevice(h->dev));
+    Pre pre(h);
+    auto* dm = pre.get<uint8_t>(tf_handle::PRE_CT_MASK, (size_t)nf * HW * C);
+    auto* dpar = pre.get<uint32_t>(tf_handle::PRE_LB_PAR, (size_t)nf * HW);
+    auto* dlr = pre.get<uint16_t>(tf_handle::PRE_LB_LR, (size_t)nf * HW);
+    // [0, 64): error word, then areas [N] u64, then the chunk's seeds [nf] u32 and seed values [nf] u8
+    auto* out = pre.get<uint8_t>(tf_handle::PRE_CT_OUT, 64 + (size_t)N * 8 + (size_t)nf * 5);
+    if (pre.rc) return pre.rc;
+    unsigned* derr = (unsigned*)out;
+    unsigned long long* dar = (unsigned long long*)(out + 64);
+    uint32_t* dseed = (uint32_t*)(out + 64 + (size_t)N * 8);
+    uint8_t* dval = (uint8_t*)(dseed + nf);
+    const hipStream_t s = h->stream;
+    HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
+    for (int f0 = 0; f0 < N; f0 += nf) {
+        const int n = std::min(nf, N - f0);
+        HIPC(h, hipMemcpyAsync(dm, masks + (size_t)f0 * HW * C, (size_t)n * HW * C, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_area_seed, dim3((unsigned)n), dim3(256), 0, s, dm, C, HW, dseed, dval, dar + f0);
+        int rc = label_planes<8, true>(h, SeedValueSet{dm, dseed, dval, C, HW}, SeedArea{dseed, dar + f0}, (size_t)n, H, W, dpar, dlr, derr);
+        if (rc) return rc;
+        HIPC(h, hipGetLastError());
+    }
+    HIPC(h, hipMemcpyAsync(area_out, dar, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    return label_errors(h, derr, "tf_first_region_areas");
+}
+
 // calls f(param, flow element, gradient element) with values of the static types that the three run-time codes select: the
 // instantiations of k_radlong_project_param and k_polar_project_param
 template <typename F>
@@ -877,6 +913,12 @@ TF_API int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int
 {
     if (!h || !masks || !centroids_out || !area_out || N < 1 || H < 1 || W < 1 || (C != 1 && C != 2)) return TF_ERR_INVALID_ARG;
     return finish_host_call(h, av_centroids(h, masks, N, H, W, C, centroids_out, area_out));
+}
+
+TF_API int tf_first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, long long* area_out)
+{
+    if (!h || !masks || !area_out || N < 1 || H < 1 || W < 1 || (C != 1 && C != 2)) return TF_ERR_INVALID_ARG;
+    return finish_host_call(h, first_region_areas(h, masks, N, H, W, C, area_out));
 }
 
 TF_API int tf_radlong_project(tf_handle* h, const float* flow, const double* centroids, int N, int H, int W,

@@ -473,6 +473,17 @@ class DenseFlow:
         _lib.check(self._L.tf_av_centroids(self._h, m.ctypes.data, N, H, W, Cm, cent.ctypes.data, area.ctypes.data), self._h, "tf_av_centroids")
         return cent, area
 
+    def first_region_areas(self, masks):
+        """AreaDetector.detect's per-frame step (cardiac_cycle_detection.py:159-172: skimage label, regionprops, props[0].area) on the
+        device, exact: masks bool or uint8 [N,H,W,C] (C = 1 or 2; only channel 0 is read) -> int64 [N], the pixel count of the
+        8-connected region of equal value that holds the frame's first non-zero pixel in raster order, 0 for an empty frame.  May be
+        called while submitted studies are in flight on this engine."""
+        m = _mask_stack(masks, "masks")
+        N, H, W, Cm = m.shape
+        area = np.zeros(N, np.int64)
+        _lib.check(self._L.tf_first_region_areas(self._h, m.ctypes.data, N, H, W, Cm, area.ctypes.data), self._h, "tf_first_region_areas")
+        return area
+
     @staticmethod
     def _project_param_inputs(flow, mask, param, spacing, n_used):
         """what both *_project_param calls check and lay out: -> (flow [N,H,W,2] float16 / float32, mask [n_used,H,W,C] uint8, n_used)"""

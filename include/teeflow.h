@@ -108,7 +108,7 @@ typedef struct tf_stats {
     unsigned long long inner_iters_total;  /* sum over pairs/levels/warps of executed inner iterations */
     unsigned long long outer_iters_total;  /* ... of executed outer iterations (= median passes) */
     /* summed launch durations per stage of the solve, filled like iter_ms only under tf_set_profile(h,1), single lane:
-     * ms_warp (k_warp_lds) and ms_median (k_median2).  ms_misc and ms_sched are always 0 (they belonged to the free-running
+     * ms_warp (k_warp_lds) and ms_median (k_median).  ms_misc and ms_sched are always 0 (they belonged to the free-running
      * scheduler driver removed in round 3; the fields stay so that ABI 2's struct layout does not change). */
     double ms_warp, ms_median, ms_misc, ms_sched;
 } tf_stats;

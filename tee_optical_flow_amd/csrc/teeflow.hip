@@ -13,6 +13,8 @@
 // The host side is cut by what it serves, all of it one translation unit: teeflow_engine.hip.h (Engine, tf_handle), the solvers'
 // teeflow_tvl1_host.hip.h and teeflow_deepflow_host.hip.h, teeflow_queue.hip.h (a call's way to an engine or to the lanes), this file's
 // C ABI entry points, then teeflow_tail.hip.h (the study tail), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
+// The device side is one header per kernel family; teeflow_kernels.hip.h holds what the solvers share and includes DualTVL1's
+// stages (teeflow_tvl1_warp / _iter / _median.hip.h) and the tail's frame conditioning (teeflow_cond.hip.h).
 #include "teeflow_kernels.hip.h"
 #include "teeflow_deepflow.hip.h"
 #include "teeflow_sor_rt.hip.h"

@@ -185,6 +185,7 @@ TF_API int tf_dbg_median(tf_handle* h, const float* src, int w, int hgt, int ksi
     MedArgs ma = {};
     ma.sb.u1[0] = a0.p; ma.sb.u1[1] = a1.p; ma.sb.u2[0] = b0.p; ma.sb.u2[1] = b1.p;
     ma.ctl = ctl.p; ma.err = nullptr; ma.errstride = 0; ma.it = 0; ma.thr_q = 0; ma.utog = 0; ma.g = g;
+    ma.total = 1; ma.step = iter_step(h, false, h->P.inner_iterations);   // the engine's skip test; at it = 0 neither form reads `err`
     const dim3 gm((g.w + 63) / 64, (g.h + 15) / 16, 2);
     if (ksize == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, h->stream, ma);
     else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, h->stream, ma);
@@ -213,7 +214,8 @@ TF_API int tf_dbg_iterate(tf_handle* h, const float* I1wx, const float* I1wy, co
     HIPC(h, hipMemsetAsync(ctl.p, 0, sizeof(PairCtl), h->stream));
     HIPC(h, hipMalloc(&errs.p, (size_t)(nsteps + 1) * sizeof(u64)));
     HIPC(h, hipMemsetAsync(errs.p, 0, (size_t)(nsteps + 1) * sizeof(u64), h->stream));
-    IterArgs ia = {};
+    Iter2Args A = {};
+    IterArgs& ia = A.a;
     ia.wx = cx.p; ia.wy = cy.p; ia.rho = cr.p;
     for (int k = 0; k < 2; ++k) {
         ia.sb.u1[k] = s[0 + k].p; ia.sb.u2[k] = s[2 + k].p; ia.sb.p11[k] = s[4 + k].p;
@@ -221,20 +223,13 @@ TF_API int tf_dbg_iterate(tf_handle* h, const float* I1wx, const float* I1wy, co
     }
     ia.ctl = ctl.p; ia.err = errs.p; ia.errstride = nsteps + 1; ia.thr_q = -1.0; ia.g = g; ia.host_slot = nullptr; ia.B = 1;
     ia.l_t = (float)(h->P.lambda * h->P.theta); ia.theta = (float)h->P.theta; ia.taut = (float)(h->P.tau / h->P.theta);
-    const bool two = two_per_launch(h, false, nsteps);     // (ia.variant = 0: these launches run the CPU form whatever the handle's variant)
+    const int step = iter_step(h, false, nsteps);     // (ia.variant = 0: these launches run the CPU form whatever the handle's variant)
+    A.total = nsteps;
     int launches = 0;
-    if (two) {
-        for (int it = 0; it < nsteps; it += 2, ++launches) {
-            Iter2Args A2;
-            A2.a = ia; A2.a.it = it; A2.a.utog = launches; A2.a.ptog = launches; A2.a.pzero = (p_is_zero && it == 0) ? 1 : 0;
-            A2.utog_prev = A2.ptog_prev = A2.pzero_prev = 0; A2.total = nsteps;
-            launch_iter2(h, A2, 1, h->stream);
-        }
-    } else {
-        for (int it = 0; it < nsteps; ++it, ++launches) {
-            ia.it = it; ia.utog = it; ia.ptog = it; ia.pzero = (p_is_zero && it == 0) ? 1 : 0;
-            launch_iter(h, ia, 1, h->stream);
-        }
+    // run_stage's loop without its last launch: thr_q < 0 keeps the pair in NORMAL mode, so there is never an iteration to REPLAY
+    for (int it = 0; it < nsteps; it += step, ++launches) {
+        ia.it = it; ia.utog = ia.ptog = launches; ia.pzero = (p_is_zero && it == 0) ? 1 : 0;
+        launch_iter(h, A, step, 1, h->stream);
     }
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && err_q && nsteps > 0) {

@@ -1,11 +1,11 @@
 // teeflow_otsu.hip.h -- predict_movie_thres of the reference on the device (/root/reference/optical_flow/calculate_optical_flow.py:184-213;
 // host restatement tee_optical_flow_amd/masks.py).  For every uint8 RGB frame of a study:
-//   g      = rgb2gray(frame)                      float64 luma, luma_f64 of teeflow_kernels.hip.h (never stored: recomputed from the bytes)
+//   g      = rgb2gray(frame)                      float64 luma, luma_f64 of teeflow_cond.hip.h (never stored: recomputed from the bytes)
 //   thr    = skimage.filters.threshold_otsu(g)    256-bin np.histogram over [min g, max g], bin centres, first maximum of var12
 //   m      = g > thr
 //   clean  = remove_small_objects(binary_fill_holes(m), min_size)     the two labellings of clean_mask, the first set from LumaNotAbove
 // and over the stack of cleaned planes, last, moving_avg_mask with its defaults; the store duplicates the channel (0x0101 per pixel).
-//   k_cond_minmax   (teeflow_kernels.hip.h) per-frame min / max of g
+//   k_cond_minmax   (teeflow_cond.hip.h)    per-frame min / max of g
 //   k_otsu_hist     np.histogram's index rule, counts privatised in LDS per wave, one global atomic add per non-empty bin and block
 //   k_otsu_thr      one block per frame: the four cumulative sums in np.cumsum's sequential order, var12, first argmax
 //   k_otsu_keep     after the two labellings of a chunk of frames: one byte per pixel of the cleaned plane, kept for the whole study

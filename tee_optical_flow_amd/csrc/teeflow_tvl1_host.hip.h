@@ -97,11 +97,11 @@ bool rows_ok(const Engine* h, const Geom& g, int B)
     return h->iter_variant >= 1 && g.w <= h->max_strip_width && (long long)g.h * B >= h->min_rows_work;
 }
 
-// two tvl1_iter iterations per launch (k_iter2_rows / k_iter2_tile) for a stage whose medians come every `inner` iterations.
-// TF_VARIANT_CUDA always runs that form (it has no median, and its iteration count is even)
-bool two_per_launch(const Engine* h, bool cuda_variant, int inner)
+// tvl1_iter iterations per launch for a stage whose medians come every `inner` iterations: 2 (k_iter2_rows / k_iter2_tile) or 1.
+// TF_VARIANT_CUDA always runs the two-iteration form (it has no median, and its iteration count is even)
+int iter_step(const Engine* h, bool cuda_variant, int inner)
 {
-    return cuda_variant || (h->iter_variant >= 2 && inner % 2 == 0);
+    return (cuda_variant || (h->iter_variant >= 2 && inner % 2 == 0)) ? 2 : 1;
 }
 
 // Block shape of the row-strip kernels: QX quads per row, RY = floor(256/QX) rows per step, 256 threads.
@@ -120,17 +120,23 @@ void strip_shape(const Engine* h, const Geom& g, int B, int* R, int* QX, int* RY
     *R = ry * (int)n;
 }
 
-// launch one two-iteration tvl1_iter step (k_iter2_rows)
-void launch_iter2(Engine* h, const Iter2Args& A, int B, hipStream_t s)
+// launch `step` (1 or 2) tvl1_iter iterations for pairs [0,B): strips or tiles by rows_ok; the one-iteration kernels take A.a alone
+void launch_iter(Engine* h, const Iter2Args& A, int step, int B, hipStream_t s)
 {
     const Geom& g = A.a.g;
     if (!rows_ok(h, g, B)) {      // small launches and very wide levels: tiles
-        hipLaunchKernelGGL(k_iter2_tile, dim3((g.w + T2_OW - 1) / T2_OW, (g.h + T2_OH - 1) / T2_OH, B), dim3(256), 0, s, A);
+        if (step == 2) hipLaunchKernelGGL(k_iter2_tile, dim3((g.w + T2_OW - 1) / T2_OW, (g.h + T2_OH - 1) / T2_OH, B), dim3(256), 0, s, A);
+        else hipLaunchKernelGGL(k_iter, dim3((g.w + IT_OW - 1) / IT_OW, (g.h + IT_OH - 1) / IT_OH, B), dim3(256), 0, s, A.a);
         return;
     }
     int R, QX, RY, threads;
     strip_shape(h, g, B, &R, &QX, &RY, &threads);
     const int LW = QX * 4 + 4;
+    if (step == 1) {
+        const size_t shmem1 = (size_t)(32 + 8 * RY * LW + 2 * RY * QX) * sizeof(float);
+        hipLaunchKernelGGL(k_iter_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem1, s, A.a, R, QX, RY);
+        return;
+    }
     const size_t shmem = (size_t)(32 + 8 * RY * LW + 2 * (RY + 1) * LW + 2 * RY * QX) * sizeof(float);
     if (B <= 1024) {
         // strips sized on the device from the exact number of pairs still iterating (one round of resident blocks); the grid covers
@@ -155,22 +161,6 @@ void launch_iter2(Engine* h, const Iter2Args& A, int B, hipStream_t s)
     }
     // a sub-batch above 1024 pairs (max_batch > 1024): fixed strips of R rows per pair
     hipLaunchKernelGGL(k_iter2_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem, s, A, R, QX, RY, 0);
-}
-
-// launch one tvl1_iter step for pairs [0,B) in the configured kernel form
-void launch_iter(Engine* h, const IterArgs& ia, int B, hipStream_t s)
-{
-    const Geom& g = ia.g;
-    if (rows_ok(h, g, B)) {
-        int R, QX, RY, threads;
-        strip_shape(h, g, B, &R, &QX, &RY, &threads);
-        const int LW = QX * 4 + 4;
-        const size_t shmem = (size_t)(32 + 8 * RY * LW + 2 * RY * QX) * sizeof(float);
-        hipLaunchKernelGGL(k_iter_rows, dim3((g.h + R - 1) / R, 1, B), dim3(threads), shmem, s, ia, R, QX, RY);
-    } else {
-        const dim3 gi((g.w + IT_OW - 1) / IT_OW, (g.h + IT_OH - 1) / IT_OH, B);
-        hipLaunchKernelGGL(k_iter, gi, dim3(256), 0, s, ia);
-    }
 }
 
 // k_warp_lds is instantiated for a few margins (the staged width is a compile-time constant)
@@ -233,7 +223,8 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
     if (rc) return rc;
     HIPC(h, hipMemsetAsync(h->tv.errs, 0, (size_t)B * h->tv.errstride * sizeof(u64), s));
 
-    IterArgs ia;
+    Iter2Args A;
+    IterArgs& ia = A.a;
     ia.wx = h->tv.cwx; ia.wy = h->tv.cwy; ia.rho = h->tv.crho; ia.sb = h->tv.sb; ia.ctl = h->tv.ctl; ia.err = h->tv.errs;
     ia.errstride = h->tv.errstride; ia.thr_q = thr_q; ia.g = g;
     ia.l_t = (float)(P.lambda * P.theta); ia.theta = (float)P.theta; ia.taut = (float)(P.tau / P.theta);
@@ -245,20 +236,19 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
 
     const dim3 gm((g.w + 63) / 64, (g.h + 15) / 16, 2 * B);
     ia.B = B;
-    // One or two iterations per launch.  Two: launch index it = 0,2,..,total (the last one can only hold REPLAY blocks), and each launch
-    // is also told the ping-pong state of the one before it.
-    const bool two = two_per_launch(h, cuda_variant, inner);
-    int utog = 0, ptog = 0, utog_prev = 0, ptog_prev = 0, pzero_prev = 0;
+    // `step` iterations per launch.  Two: launch index it = 0,2,..,total (the last one can only hold REPLAY blocks), and each launch
+    // is also told the ping-pong state of the one before it (the one-iteration kernels do not read it).
+    const int step = iter_step(h, cuda_variant, inner);
+    ma.total = A.total = total; ma.step = step;
+    A.utog_prev = A.ptog_prev = A.pzero_prev = 0;
+    int utog = 0, ptog = 0;
     bool stop = false;
     unsigned checked = h->tv.launch_seq;          // this stage's launches before `checked` have been read back
-    for (int it = 0; (two ? it <= total : it < total) && !stop; it += two ? 2 : 1) {
+    for (int it = 0; it < total + step - 1 && !stop; it += step) {
         if (it < total && it % inner == 0 && median) {
             ma.it = it; ma.utog = utog;
             rc = profiled(h, s, -5, 0, 0, [&] {
-                if (two) {
-                    if (P.median_filtering == 5) hipLaunchKernelGGL(k_median2<5>, gm, dim3(256), 0, s, ma, total);
-                    else hipLaunchKernelGGL(k_median2<3>, gm, dim3(256), 0, s, ma, total);
-                } else if (P.median_filtering == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
+                if (P.median_filtering == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
                 else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, s, ma);
             });
             if (rc) return rc;
@@ -268,26 +258,16 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
         h->tv.slots_host[q % SLOT_RING] = -1;
         ia.host_slot = h->tv.slots_dev + q % SLOT_RING;
         ia.it = it; ia.utog = utog; ia.ptog = ptog; ia.pzero = (wi == 0 && it == 0) ? 1 : 0;
-        rc = profiled(h, s, l, wi, it, [&] {
-            if (!two) { launch_iter(h, ia, B, s); return; }
-            Iter2Args A2;
-            A2.a = ia;
-            A2.utog_prev = utog_prev; A2.ptog_prev = ptog_prev; A2.pzero_prev = pzero_prev; A2.total = total;
-            launch_iter2(h, A2, B, s);
-        });
+        rc = profiled(h, s, l, wi, it, [&] { launch_iter(h, A, step, B, s); });
         if (rc) return rc;
         ++h->tally.iter_launches;
-        utog_prev = utog; ptog_prev = ptog; pzero_prev = ia.pzero;
+        A.utog_prev = utog; A.ptog_prev = ptog; A.pzero_prev = ia.pzero;
         ++utog; ++ptog;
         rc = read_reports(h, s, q, &checked, &stop);
         if (rc) return rc;
     }
-    if (two)
-        hipLaunchKernelGGL(k_stage_end2, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, h->tv.iters_dev, B,
-                           total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps, P.variant, thr_d);
-    else
-        hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, h->tv.iters_dev, B,
-                           total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps);
+    hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, h->tv.iters_dev, B,
+                       total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps, P.variant, thr_d, step);
     return TF_OK;
 }
 

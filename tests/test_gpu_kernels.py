@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.tvl1_forms import iter_form
+
 
 pytestmark = pytest.mark.gpu
 
@@ -74,9 +76,12 @@ def test_warp_bit_exact(engine, oracle, shape, amp, margin):
     engine.set_tuning("warp_margin", 0)
 
 
-@pytest.mark.parametrize("ksize", [3, 5])
+# (step 1, the skip test this test has always pinned, keeps the case ids it had; step 2 is the one a default solve runs)
+@pytest.mark.parametrize("ksize,step", [pytest.param(3, 1, id="3"), pytest.param(5, 1, id="5"),
+                                        pytest.param(3, 2, id="3-step2"), pytest.param(5, 2, id="5-step2")])
 @pytest.mark.parametrize("shape", [(64, 64), (97, 131), (5, 7), (1, 40), (210, 210)])
-def test_median_bit_exact(engine, oracle, shape, ksize):
+def test_median_bit_exact(engine, oracle, shape, ksize, step):
+    """k_median under both of its skip tests: the one of a solve with one iteration per launch and the one with two"""
     from tee_optical_flow_amd import _lib
     L = _lib.load()
     h, w = shape
@@ -84,7 +89,8 @@ def test_median_bit_exact(engine, oracle, shape, ksize):
     src[::7, ::5] = 0.0  # ties
     ref = oracle.median_blur(src, ksize)
     out = np.empty((h, w), np.float32)
-    _lib.check(L.tf_dbg_median(engine._h, _ptr(src), w, h, ksize, _ptr(out)), engine._h)
+    with iter_form(engine, "strips" if step == 1 else "strips2"):
+        _lib.check(L.tf_dbg_median(engine._h, _ptr(src), w, h, ksize, _ptr(out)), engine._h)
     assert np.array_equal(out, ref)
 
 
@@ -97,13 +103,8 @@ def test_iterate_bit_exact(engine, oracle, shape, pzero, variant):
     iterations per launch (variant 3 = variant 2 on a launch too small for the strips)."""
     from tee_optical_flow_amd import _lib
     L = _lib.load()
-    engine.set_tuning("iter_variant", min(variant, 2))
-    engine.set_tuning("min_rows_work", 0 if variant != 3 else 1 << 30)   # strips even for this single small image | tiles
-    try:
+    with iter_form(engine, variant):
         _iterate_case(engine, oracle, L, shape, pzero)
-    finally:
-        engine.set_tuning("iter_variant", 2)
-        engine.set_tuning("min_rows_work", 8192)
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3])
@@ -130,18 +131,13 @@ def test_iterate_tiny_zero_and_denormal_values_bit_exact(engine, oracle, variant
     wx[40:50] = rng.uniform(-20, 20, (10, w)).astype(np.float32)     # ordinary gradients over tiny flow
     wy[40:50] = rng.uniform(-20, 20, (10, w)).astype(np.float32)
     grad = wx * wx + wy * wy
-    engine.set_tuning("iter_variant", min(variant, 2))
-    engine.set_tuning("min_rows_work", 0 if variant != 3 else 1 << 30)
-    try:
+    with iter_form(engine, variant):
         nsteps = 6
         ref = oracle.iterate(wx, wy, grad, rho, u1, u2, *p, nsteps)
         st = [a.copy() for a in (u1, u2, *p)]
         err = np.zeros(nsteps, np.uint64)
         _lib.check(L.tf_dbg_iterate(engine._h, _ptr(wx), _ptr(wy), _ptr(rho), *[_ptr(a) for a in st], w, h, nsteps, 0,
                                     _ptr(err)), engine._h)
-    finally:
-        engine.set_tuning("iter_variant", 2)
-        engine.set_tuning("min_rows_work", 8192)
     for n, a, r in zip(["u1", "u2", "p11", "p12", "p21", "p22"], st, ref[:6]):
         bad = a.view(np.uint32) != r.view(np.uint32)
         assert not bad.any(), f"{n}: {bad.sum()} bit patterns differ, first at {np.argwhere(bad)[0]}: {a[bad][0]!r} vs {r[bad][0]!r}"

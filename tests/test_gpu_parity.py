@@ -6,6 +6,8 @@ unpinned -- cv2 is not installable here; see oracle/tvl1_oracle.c.)"""
 import numpy as np
 import pytest
 
+from tests.tvl1_forms import iter_form
+
 
 pytestmark = pytest.mark.gpu
 
@@ -99,23 +101,22 @@ def test_non_default_parameters_match_oracle(oracle, params):
     eng.close()
 
 
-@pytest.mark.parametrize("variant", [0, 1, 2])
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
 @pytest.mark.parametrize("params", [dict(), dict(inner_iterations=7, outer_iterations=4), dict(inner_iterations=4, outer_iterations=3, epsilon=0.002),
                                     dict(median_filtering=1, epsilon=0.03), dict(inner_iterations=9, outer_iterations=5, epsilon=0.004),
                                     dict(inner_iterations=3, outer_iterations=4, median_filtering=3)])
 def test_every_iteration_kernel_form_end_to_end(oracle, variant, params):
-    """The three tvl1_iter forms (tiles / row strips / two iterations per launch with per-pair REPLAY of an overshoot)
-    must give the oracle's flow and iteration counts exactly -- including stops on odd iterations, stages that hit the
+    """The four tvl1_iter forms (tiles / row strips / two iterations per launch with per-pair REPLAY of an overshoot, on strips and on
+    tiles) must give the oracle's flow and iteration counts exactly -- including stops on odd iterations, stages that hit the
     iteration cap (tiny epsilon), odd `inner` (falls back to one iteration per launch) and a batch whose pairs stop at
     different iterations."""
     import tee_optical_flow_amd as T
     from tee_optical_flow_amd.synth import speckle_pairs
     I0s, I1s = speckle_pairs(range(70, 76), 72, 88)
     eng = T.DenseFlow(**params)
-    eng.set_tuning("iter_variant", variant)
-    eng.set_tuning("min_rows_work", 0)
-    flows = eng.calc_pairs(I0s, I1s)
-    iters = eng.last_iters()
+    with iter_form(eng, variant):
+        flows = eng.calc_pairs(I0s, I1s)
+        iters = eng.last_iters()
     op = oracle.default_params(**params)
     odd = even = 0
     for b in range(len(I0s)):

@@ -12,10 +12,9 @@ import pytest
 
 from tests import tvl1_ref64 as R
 from tests import tvl1_ref64_cases as K
+from tests.tvl1_forms import iter_form
 
 pytestmark = pytest.mark.gpu
-
-DEFAULT_ITER_KNOBS = {"iter_variant": 2, "min_rows_work": 8192}
 
 
 def _ptr(a):
@@ -70,9 +69,7 @@ def test_iterate_at_other_constants(handles, oracle, form, shape, triple):
     L = _lib.load()
     lam, theta, tau = K.TRIPLES[triple]
     eng = handles(lambda_=lam, theta=theta, tau=tau)
-    eng.set_tuning("iter_variant", min(form, 2))
-    eng.set_tuning("min_rows_work", 0 if form != 3 else 1 << 30)
-    try:
+    with iter_form(eng, form):
         for k in K.GPU_ITER_STEPS:
             for pz in (0, 1):
                 cid = K.iter_id(*shape, k, triple, pz)
@@ -87,9 +84,6 @@ def test_iterate_at_other_constants(handles, oracle, form, shape, triple):
                 for n, a, r in zip(["u1", "u2", "p11", "p12", "p21", "p22"], dev, orc[:6]):
                     assert np.array_equal(a, r), f"{cid} {n}: {np.sum(a != r)} px differ from the oracle, max {np.abs(a - r).max()}"
                 assert np.array_equal(err, orc[6]), cid
-    finally:
-        for name, v in DEFAULT_ITER_KNOBS.items():
-            eng.set_tuning(name, v)
 
 
 # ---- tf_dbg_pyramid, tf_dbg_resize --------------------------------------------------------------------------------------------------
@@ -160,18 +154,16 @@ def test_cuda_class_warp_against_reference(handles, cid):
 
 
 # ---- solves -------------------------------------------------------------------------------------------------------------------------
-def solve_case(oracle, case, iter_variant):
+def solve_case(oracle, case, form):
     import tee_optical_flow_amd as T
     over, _, seeds, _, criterion = K.SOLVE[case]
     I0s, I1s = K.solve_pairs(case)
     eng = T.DenseFlow(**{k: ("cuda" if k == "variant" and v == 1 else v) for k, v in over.items()})
     try:
-        eng.set_tuning("min_rows_work", 0)          # the strip forms, even for this small batch
-        if iter_variant is not None:
-            eng.set_tuning("iter_variant", iter_variant)
-        flows = eng.calc_pairs(I0s, I1s)
-        iters = eng.last_iters()
-        levels = eng.last_stats["nscales_used"]
+        with iter_form(eng, form):
+            flows = eng.calc_pairs(I0s, I1s)
+            iters = eng.last_iters()
+            levels = eng.last_stats["nscales_used"]
     finally:
         eng.close()
     for b in range(len(seeds)):
@@ -187,8 +179,8 @@ def solve_case(oracle, case, iter_variant):
 def test_solve_against_reference(oracle, case):
     """The case's pairs as one batch on the strip forms: the reference's iteration counts and pyramid depth exactly, its flow within the
     case's criterion, and the oracle's flow bit for bit."""
-    solve_case(oracle, case, None)
+    solve_case(oracle, case, "strips2")          # the strip forms, even for this small batch
 
 
 def test_solve_against_reference_on_tiles(oracle):
-    solve_case(oracle, K.GPU_SOLVE_TILES_TOO, 0)
+    solve_case(oracle, K.GPU_SOLVE_TILES_TOO, "tiles")

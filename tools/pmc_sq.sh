@@ -6,7 +6,7 @@
 set -u
 TAG=${1:-r03}
 ALGO=${2:-TVL1}
-KREGEX=${KREGEX:-"k_iter2_rows|k_df_sor_rt"}     # other kernels: KREGEX="k_median2|k_warp" bash tools/pmc_sq.sh r02x
+KREGEX=${KREGEX:-"k_iter2_rows|k_df_sor_rt"}     # other kernels: KREGEX="k_median|k_warp" bash tools/pmc_sq.sh r02x
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_sq_${TAG}_$ALGO
 mkdir -p $OUT
 export TMPDIR=/tmp

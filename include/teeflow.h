@@ -467,6 +467,11 @@ long long tf_dbg_counter(tf_handle* h, const char* name);
 /* DeepFlow hooks: one cv::VariationalRefinement::calcUV on dense float images (u, v updated in place); 3x3 Gaussian blur */
 int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v);
 int tf_dbg_df_blur(tf_handle* h, const float* src, int w, int hgt, float* dst);
+/* level `level` of DeepFlow's pyramid of one frame (uint8, or float32 with is_f32: taken as it is), by the kernels and the level table of a
+ * solve; out may be NULL (the level's size only); a level the pyramid does not have is TF_ERR_INVALID_ARG */
+int tf_dbg_df_pyramid(tf_handle* h, const void* frame, int is_f32, int H, int W, int level, float* out, int* ow, int* oh);
+/* the flow hand-down between two levels of a DeepFlow solve: (u, v) of sw x sh resized to dw x dh, times 1 / downscale_factor */
+int tf_dbg_df_up(tf_handle* h, const float* u, const float* v, int sw, int sh, float* ou, float* ov, int dw, int dh);
 /* the float16 output kernels' value function on caller-chosen values: out[i] = bits of half(float32(in[i] * scale)), n <= 2^30 */
 int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale, uint16_t* out);
 /* Pinned host memory for flow results.  The reference gets a fresh numpy array from cv2 (`flow = OF_model.calc(...)`,

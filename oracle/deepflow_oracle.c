@@ -11,6 +11,8 @@
  * restates the published algorithm from SURVEY.md Appendix B and from the upstream code as the author remembers it:
  *
  *        >>>>>>>>  PARITY UNPINNED (vs real OpenCV), and LOWER CONFIDENCE than the DualTVL1 oracle  <<<<<<<<
+ *   (what checks it: tests/deepflow_ref64.py, a float64 restatement of every stage below and of the solve, written from this description
+ *    and not from these loops -- tests/test_deepflow_ref64_stages_cpu.py; it guards against slips in THIS file, it is no OpenCV pin)
  *
  * What is restated:
  *   OpticalFlowDeepFlow::calc : convertTo(CV_32F) (values stay 0..255); GaussianBlur(3x3, sigma 0.6, REFLECT_101);

@@ -298,6 +298,39 @@ def deepflow_gauss_blur3(src, sigma=0.6):
     return dst
 
 
+def deepflow_gauss3(sigma=0.6):
+    """The two float32 taps (centre, side) of the 3x3 pre-blur."""
+    k = np.empty(2, np.float32)
+    dlib().dfo_gauss3(float(sigma), k)
+    return k
+
+
+def deepflow_resize_linear(src, dw, dh):
+    src = _f32(src)
+    sh, sw = src.shape
+    dst = np.empty((dh, dw), np.float32)
+    dlib().dfo_resize_linear(src, sw, sh, dst, int(dw), int(dh))
+    return dst
+
+
+def deepflow_pyramid_level(img, level, params=None):
+    """Level `level` of the pyramid deepflow_calc builds of one frame: uint8 (values stay 0..255) or float32 taken as it is."""
+    p = params if params is not None else deepflow_default_params()
+    h, w = np.shape(img)
+    sizes = deepflow_pyramid_sizes(w, h, p)
+    a = deepflow_gauss_blur3(_f32(img), p.sigma)
+    for nw, nh in sizes[1:level + 1]:
+        a = deepflow_resize_linear(a, nw, nh)
+    return a
+
+
+def deepflow_upsample(u, v, dw, dh, params=None):
+    """The flow hand-down of deepflow_calc: resize to the next level's size, times 1.0f / downscale_factor."""
+    p = params if params is not None else deepflow_default_params()
+    mul = np.float32(1) / np.float32(p.downscale_factor)
+    return deepflow_resize_linear(u, dw, dh) * mul, deepflow_resize_linear(v, dw, dh) * mul
+
+
 def deepflow_warp_linear(I1, u, v):
     I1, u, v = map(_f32, (I1, u, v))
     h, w = I1.shape

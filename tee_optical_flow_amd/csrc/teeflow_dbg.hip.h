@@ -121,6 +121,66 @@ TF_API int tf_dbg_df_blur(tf_handle* h, const float* src, int w, int hgt, float*
     return dbg_down(h, dst, b.p, g);
 }
 
+// level `level` of DeepFlow's pyramid of one frame, through the kernels and the level table df_solve_resident uses
+TF_API int tf_dbg_df_pyramid(tf_handle* h, const void* frame, int is_f32, int H, int W, int level, float* out, int* ow, int* oh)
+{
+    if (!h || !frame || !ow || !oh || H < 1 || W < 1 || level < 0) return TF_ERR_INVALID_ARG;
+    if (h->P.algo != TF_ALGO_DEEPFLOW) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_df_pyramid needs a handle from tf_create_deepflow");
+    std::vector<Geom> lv(DF_MAXLEV);
+    const int nlev = df_levels(h->DP, H, W, lv.data());
+    if (level >= nlev) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_df_pyramid: level %d of a pyramid of %d", level, nlev);
+    *ow = lv[level].w; *oh = lv[level].h;
+    if (!out) return TF_OK;
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g0 = lv[0];
+    const size_t bytes = (size_t)H * W * (is_f32 ? sizeof(float) : 1);
+    DevBuf<uint8_t> din;
+    HIPC(h, hipMalloc(&din.p, bytes));
+    HIPC(h, hipMemcpyAsync(din.p, frame, bytes, hipMemcpyHostToDevice, h->stream));
+    DBuf tmp, cur;
+    int rc;
+    if ((rc = dbg_up(h, tmp, nullptr, g0)) || (rc = dbg_up(h, cur, nullptr, g0))) return rc;
+    float k0, k1;
+    df_gauss3(h->DP.sigma, &k0, &k1);
+    if (is_f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, 1), dim3(256), 0, h->stream, (const float*)din.p, tmp.p, g0, 0);
+    else hipLaunchKernelGGL(k_u8_to_f32, dim3((g0.w + 255) / 256, g0.h, 1), dim3(256), 0, h->stream, din.p, tmp.p, g0);
+    hipLaunchKernelGGL(k_df_blur, grid64x4(g0, 1), dim3(256), 0, h->stream, tmp.p, cur.p, g0, k0, k1);
+    for (int l = 1; l <= level; ++l) {
+        const Geom gs = lv[l - 1], gd = lv[l];
+        DBuf nxt;
+        if ((rc = dbg_up(h, nxt, nullptr, gd))) return rc;
+        const double sx = 1.0 / ((double)gd.w / gs.w), sy = 1.0 / ((double)gd.h / gs.h);
+        hipLaunchKernelGGL(k_pyr_down, grid64x4(gd, 1), dim3(256), 0, h->stream, cur.p, gs, nxt.p, gd, sx, sy);
+        HIPC(h, hipStreamSynchronize(h->stream));
+        std::swap(cur.p, nxt.p);
+    }
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "deepflow pyramid: %s", hipGetErrorString(e));
+    return dbg_down(h, out, cur.p, lv[level]);
+}
+
+// the flow hand-down of a DeepFlow solve, one level to the next finer one: k_df_up on host planes (u, v) of sw x sh -> dw x dh
+TF_API int tf_dbg_df_up(tf_handle* h, const float* u, const float* v, int sw, int sh, float* ou, float* ov, int dw, int dh)
+{
+    if (!h || !u || !v || !ou || !ov || sw < 1 || sh < 1 || dw < 1 || dh < 1) return TF_ERR_INVALID_ARG;
+    if (h->P.algo != TF_ALGO_DEEPFLOW) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_df_up needs a handle from tf_create_deepflow");
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(sw, sh), gd = make_geom(dw, dh);
+    DBuf su, sv, du, dv;
+    int rc;
+    if ((rc = dbg_up(h, su, u, g)) || (rc = dbg_up(h, sv, v, g)) || (rc = dbg_up(h, du, nullptr, gd)) || (rc = dbg_up(h, dv, nullptr, gd))) return rc;
+    DfBufs d = {};
+    const int cur = 0;
+    d.avg = su.p; d.Iz = sv.p; d.Wu[cur ^ 1] = du.p; d.Wv[cur ^ 1] = dv.p;
+    const float mul = 1.0f / h->DP.downscale_factor;
+    const double sx = 1.0 / ((double)gd.w / g.w), sy = 1.0 / ((double)gd.h / g.h);
+    hipLaunchKernelGGL(k_df_up, grid64x4(gd, 1), dim3(256), 0, h->stream, d, cur, g, gd, sx, sy, mul);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "k_df_up: %s", hipGetErrorString(e));
+    if ((rc = dbg_down(h, ou, du.p, gd))) return rc;
+    return dbg_down(h, ov, dv.p, gd);
+}
+
 TF_API int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale, uint16_t* out)
 {
     if (!h || !in || !out || n < 1) return TF_ERR_INVALID_ARG;

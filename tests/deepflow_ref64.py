@@ -1,4 +1,4 @@
-"""A float64 reference of one VariationalRefinement::calcUV, independent of oracle/deepflow_oracle.c.
+"""A float64 reference of DeepFlow -- one VariationalRefinement::calcUV, and the solve around it -- independent of oracle/deepflow_oracle.c.
 
 Written from the algorithm the oracle's header states, in whole-array numpy / scipy form, not from its loops:
   warp I1 by W (bilinear on float32 maps quantised to 1/32 px, zero outside the image); Iavg = (I0 + Iw) / 2, Iz = Iw - I0;
@@ -11,11 +11,35 @@ Written from the algorithm the oracle's header states, in whole-array numpy / sc
       +/- w (W(q) - W(p)) to their right-hand sides;
     then either `sor` red-black SOR sweeps (red = (x + y) even first; u then v per pixel, v sees the new u) started from the
     current dW, or the exact solution of the same sparse system.
-The result is W + dW in float64.  Only tests use this module.
+The result is W + dW in float64.
+
+And of the solve around it (OpticalFlowDeepFlow::calc), from the same header:
+  frames to floating point without a factor: uint8 frames keep 0..255, float32 frames are taken as they are;
+  a 3 x 3 Gaussian blur: taps exp(-x^2 / (2 sigma^2)), x = -1, 0, 1, of the float32 sigma, normalised in double and THEN rounded to
+    float32 (that rounding is part of the specification); row pass, column pass; BORDER_REFLECT_101 (the neighbour beyond the edge is the
+    pixel one inside it; a side of length 1 reflects onto itself);
+  level sizes: size' = (int)(size * factor + 0.5f) in float32 arithmetic, per side, while both new sides are > min_size, at most 201
+    levels; level l is level l - 1 resized to that size with INTER_LINEAR (half-pixel centres, the scale is the size ratio);
+  the flow starts at zero on the coarsest level; every level is refined (calcUV with alpha 4 alpha, delta / 3, gamma / 3); the refined
+    flow goes to the next finer level by INTER_LINEAR to that level's size, times float32(1) / float32(factor).
+Everything is float64 except where the algorithm itself says float32 (the taps, the size rule, the gain, the warp's sample positions).
+`mutate=` names one deliberate error (MUTATIONS) for the sensitivity test; nothing else may pass it.  Only tests use this module.
 """
 import numpy as np
 from scipy import sparse
 from scipy.sparse import linalg as splinalg
+
+from tests.tvl1_ref64 import resize_cuda, resize_linear      # written from cv::resize's definition, independent of both oracles
+
+MAX_LEVELS = 201
+
+MUTATIONS = ("no_blur", "sigma_plus_0.05", "border_reflect", "sizes_truncated", "sizes_float64", "resize_no_half_pixel", "no_gain",
+             "gain_is_factor", "nonzero_start", "level0_not_refined")
+
+
+def _check(mutate):
+    if mutate is not None and mutate not in MUTATIONS:
+        raise ValueError(f"unknown mutation {mutate!r}")
 
 
 def warp_bilinear(I1, u, v):
@@ -161,3 +185,96 @@ def refine_params(I0, I1, u, v, params, exact=False):
                   gamma=float(f(params.gamma) / f(3)), zeta=float(f(params.zeta)), epsilon=float(f(params.epsilon)),
                   fixed_point_iterations=params.fixed_point_iterations, sor_iterations=params.sor_iterations,
                   omega=float(f(params.omega)), exact=exact)
+
+
+# ---- the solve around the refinement ------------------------------------------------------------------------------------------------
+def gauss3(sigma, mutate=None):
+    """getGaussianKernel(3, sigma, CV_32F) -> (centre, side) as the float32 values they are rounded to."""
+    _check(mutate)
+    s = float(np.float32(sigma)) + (0.05 if mutate == "sigma_plus_0.05" else 0.0)
+    side = np.exp(-1.0 / (2.0 * s * s))
+    total = 1.0 + 2.0 * side
+    return float(np.float32(1.0 / total)), float(np.float32(side / total))
+
+
+def _pad1(a, axis, mutate):
+    """One more sample at each end of an axis: REFLECT_101 (cv2) is numpy's 'reflect'; cv2's REFLECT is numpy's 'symmetric'."""
+    width = [(0, 0), (0, 0)]
+    width[axis] = (1, 1)
+    if a.shape[axis] == 1:
+        return np.pad(a, width, mode="edge")
+    return np.pad(a, width, mode="symmetric" if mutate == "border_reflect" else "reflect")
+
+
+def blur3(img, sigma, mutate=None):
+    """GaussianBlur(img, (3, 3), sigma), BORDER_REFLECT_101."""
+    _check(mutate)
+    a = np.asarray(img, np.float64)
+    if mutate == "no_blur":
+        return a.copy()
+    k0, k1 = gauss3(sigma, mutate)
+    p = _pad1(a, 1, mutate)
+    a = k0 * p[:, 1:-1] + k1 * (p[:, :-2] + p[:, 2:])
+    p = _pad1(a, 0, mutate)
+    return k0 * p[1:-1] + k1 * (p[:-2] + p[2:])
+
+
+def _next_size(n, factor, mutate):
+    if mutate == "sizes_float64":
+        return int(n * float(np.float32(factor)) + 0.5)
+    f = np.float32
+    if mutate == "sizes_truncated":
+        return int(f(n) * f(factor))
+    return int(f(f(n) * f(factor)) + f(0.5))                      # float32 product, float32 sum, truncation
+
+
+def pyramid_sizes(W, H, params, mutate=None):
+    """[(w, h)] of every level, finest first."""
+    _check(mutate)
+    sizes = [(int(W), int(H))]
+    while len(sizes) < MAX_LEVELS:
+        w, h = sizes[-1]
+        nw, nh = _next_size(w, params.downscale_factor, mutate), _next_size(h, params.downscale_factor, mutate)
+        if nw <= params.min_size or nh <= params.min_size:
+            break
+        sizes.append((nw, nh))
+    return sizes
+
+
+def _resize(a, w, h, mutate):
+    return (resize_cuda if mutate == "resize_no_half_pixel" else resize_linear)(a, w, h)
+
+
+def pyramid(img, params, mutate=None):
+    """The levels of one frame, finest first: the blurred frame, then each level resized from the one before."""
+    _check(mutate)
+    lv = [blur3(img, params.sigma, mutate)]
+    for w, h in pyramid_sizes(lv[0].shape[1], lv[0].shape[0], params, mutate)[1:]:
+        lv.append(_resize(lv[-1], w, h, mutate))
+    return lv
+
+
+def upsample(u, v, dw, dh, factor, mutate=None):
+    """The flow handed down to the next finer level, of dw x dh."""
+    _check(mutate)
+    gain = float(np.float32(1) / np.float32(factor))
+    if mutate == "no_gain":
+        gain = 1.0
+    if mutate == "gain_is_factor":
+        gain = float(np.float32(factor))
+    return _resize(u, dw, dh, mutate) * gain, _resize(v, dw, dh, mutate) * gain
+
+
+def solve(I0, I1, params, mutate=None):
+    """OpticalFlowDeepFlow::calc -> (flow float64 [H, W, 2], levels).  `params`: any object with the oracle's field names."""
+    _check(mutate)
+    P0, P1 = pyramid(I0, params, mutate), pyramid(I1, params, mutate)
+    start = 0.5 if mutate == "nonzero_start" else 0.0
+    u, v = np.full(P0[-1].shape, start), np.full(P0[-1].shape, start)
+    for l in range(len(P0) - 1, -1, -1):
+        if not (l == 0 and mutate == "level0_not_refined"):
+            u, v = refine_params(P0[l], P1[l], u, v, params)
+        if l:
+            h, w = P0[l - 1].shape
+            u, v = upsample(u, v, w, h, params.downscale_factor, mutate)
+    return np.stack([u, v], -1), len(P0)

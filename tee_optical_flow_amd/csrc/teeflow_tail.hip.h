@@ -1,5 +1,5 @@
 // The study tail's host code: everything around the solver -- frame conditioning, saliency, tf_clean_masks, tf_otsu_masks, the
-// segmentor's frame glue, tf_av_centroids, tf_first_region_areas, the rad/long and polar projections, histogram and radix select, the overlay, WASE.  Included by teeflow.hip (one
+// segmentor's frame glue, tf_av_centroids, tf_first_region_areas, the rad/long and polar projections, histogram and radix select, the overlay, WASE, the study calls.  Included by teeflow.hip (one
 // translation unit); the kernels are in the kernel headers.  The entry points here keep their device scratch in the handle's PRE_*
 // slots (grown on demand, never shrunk, freed with the handle), so they neither allocate nor free once a study's sizes have been seen.
 // The one exception is tf_submit_seq_rgb, whose conditioned frames are a buffer of the queued job (allocated per study, freed with it).
@@ -33,9 +33,10 @@ struct Pre {
 };
 
 // a failed call leaves nothing of it running: its destinations are host memory the caller may free at once
+// (a call refused for its null handle passes through)
 int finish_host_call(tf_handle* h, int rc)
 {
-    if (rc != TF_OK) {
+    if (rc != TF_OK && h) {
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         (void)hipGetLastError();
     }
@@ -74,7 +75,7 @@ int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* 
 // rgb (host) -> conditioned gray frames in the handle's preprocessing buffer (valid until the handle's next preprocessing call)
 // (`own`: into that caller-owned buffer instead -- a submitted job's frames must outlive the handle's next preprocessing call)
 // echo16_out (host, [N][H][W] halves, or null): also the study's `echo`, from the same upload; complete on return
-int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t** dgray_out, uint8_t* own = nullptr,
+int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, const uint8_t** dgray_out, uint8_t* own = nullptr,
                         uint16_t* echo16_out = nullptr)
 {
     const size_t npx = (size_t)H * W;
@@ -99,7 +100,7 @@ int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, u
 
 int condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t* gray_out)
 {
-    uint8_t* dgray = nullptr;
+    const uint8_t* dgray = nullptr;
     int rc = condition_to_device(h, rgb, N, H, W, &dgray);
     if (rc) return rc;
     HIPC(h, hipMemcpy(gray_out, dgray, (size_t)N * H * W, hipMemcpyDeviceToHost));
@@ -113,56 +114,6 @@ TF_API int tf_condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, i
     return finish_host_call(h, condition_frames(h, rgb, N, H, W, gray_out));
 }
 
-namespace {
-// flows of an RGB study in the call's output type (out_f16: float16, and the study's `echo` to echo16_out if that is given)
-int calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, void* flow_out, bool out_f16, uint16_t* echo16_out, tf_stats* st)
-{
-    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST, false, out_f16};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    uint8_t* dgray = nullptr;
-    rc = finish_host_call(h, condition_to_device(h, rgb, N, H, W, &dgray, nullptr, echo16_out));
-    if (rc) return rc;
-    // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
-    c.in0 = dgray; c.where = W_IN_DEV;
-    return calc_entry(h, c, st);
-}
-// the same without waiting: the frames are conditioned now (on the handle's stream, into a buffer the job owns), the solve is queued
-int submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, void* flow_out, bool out_f16, uint16_t* echo16_out, int* ticket)
-{
-    Call c{MODE_SEQ, rgb, nullptr, N - 1, H, W, scale, flow_out, W_HOST, false, out_f16};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    if (!ticket) return TF_ERR_INVALID_ARG;
-    HIPC(h, hipSetDevice(h->dev));
-    uint8_t* own = nullptr;
-    HIPC(h, hipMalloc(&own, (size_t)N * H * W));
-    uint8_t* dgray = nullptr;
-    rc = finish_host_call(h, condition_to_device(h, rgb, N, H, W, &dgray, own, echo16_out));
-    if (rc) { (void)hipFree(own); return rc; }
-    c.in0 = own; c.where = W_IN_DEV;
-    return submit_entry(h, c, ticket, own);
-}
-}  // namespace
-
-TF_API int tf_calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
-{
-    return calc_seq_rgb(h, rgb, N, H, W, scale, flow_out, false, nullptr, st);
-}
-TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
-{
-    return submit_seq_rgb(h, rgb, N, H, W, scale, flow_out, false, nullptr, ticket);
-}
-TF_API int tf_calc_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
-                               tf_stats* st)
-{
-    return calc_seq_rgb(h, rgb, N, H, W, scale, flow16_out, true, echo16_out, st);
-}
-TF_API int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
-                                 int* ticket)
-{
-    return submit_seq_rgb(h, rgb, N, H, W, scale, flow16_out, true, echo16_out, ticket);
-}
 // the echo alone: rgb uint8 [N][H][W][3] -> float16 [N][H][W] = half(rgb2gray), one rounding
 TF_API int tf_echo_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint16_t* echo16_out)
 {
@@ -188,49 +139,48 @@ namespace {
 // (f32) float = map * (1/255), what computeSaliency() returns in opencv-contrib 4.x.  Frames go through in chunks so that the work
 // buffers (17 B per pixel) stay below ~2.3 GB whatever the study's length; the buffers are the handle's and only ever grow.
 // echo16_out (host, or null; channels == 3 only): also the study's float16 `echo`, from each chunk's upload; complete on return
-int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, void** dout,
+int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, const uint8_t** dout,
                        uint16_t* echo16_out = nullptr)
 {
     const size_t npx = (size_t)H * W, ipx = (size_t)(H + 1) * (W + 1);
     if (H > 65535 || N > 65535) return fail(h, TF_ERR_UNSUPPORTED, "saliency: at most 65535 rows and 65535 frames per call");
-    size_t F = ((size_t)1 << 27) / npx;
-    F = F < 1 ? 1 : (F > (size_t)N ? (size_t)N : F);
+    const int nf = chunk_frames(npx, N, 65535, (size_t)1 << 27);   // (the budget counted in pixels: 2^27 of them per chunk)
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
-    auto* src = pre.get<uint8_t>(tf_handle::PRE_SRC, F * npx * channels);
-    auto* g0 = pre.get<uint8_t>(tf_handle::PRE_G0, F * npx);
-    auto* g1 = pre.get<uint8_t>(tf_handle::PRE_G1, F * npx);
-    auto* ion = pre.get<uint8_t>(tf_handle::PRE_ION, F * npx);
-    auto* ioff = pre.get<uint8_t>(tf_handle::PRE_IOFF, F * npx);
-    auto* P = pre.get<int>(tf_handle::PRE_P, F * npx);
-    auto* I = pre.get<float>(tf_handle::PRE_I, F * ipx);
-    auto* mon = pre.get<uint16_t>(tf_handle::PRE_MON, F * npx);
-    auto* moff = pre.get<uint16_t>(tf_handle::PRE_MOFF, F * npx);
-    auto* mx = pre.get<int>(tf_handle::PRE_MX, F * SAL_MX);
+    auto* src = pre.get<uint8_t>(tf_handle::PRE_SRC, nf * npx * channels);
+    auto* g0 = pre.get<uint8_t>(tf_handle::PRE_G0, nf * npx);
+    auto* g1 = pre.get<uint8_t>(tf_handle::PRE_G1, nf * npx);
+    auto* ion = pre.get<uint8_t>(tf_handle::PRE_ION, nf * npx);
+    auto* ioff = pre.get<uint8_t>(tf_handle::PRE_IOFF, nf * npx);
+    auto* P = pre.get<int>(tf_handle::PRE_P, nf * npx);
+    auto* I = pre.get<float>(tf_handle::PRE_I, nf * ipx);
+    auto* mon = pre.get<uint16_t>(tf_handle::PRE_MON, nf * npx);
+    auto* moff = pre.get<uint16_t>(tf_handle::PRE_MOFF, nf * npx);
+    auto* mx = pre.get<int>(tf_handle::PRE_MX, nf * SAL_MX);
     auto* out = pre.get<uint8_t>(tf_handle::PRE_OUT, (size_t)N * npx * (f32 ? sizeof(float) : 1));
-    auto* decho = echo16_out ? pre.get<uint16_t>(tf_handle::PRE_ECHO, F * npx) : nullptr;
+    auto* decho = echo16_out ? pre.get<uint16_t>(tf_handle::PRE_ECHO, nf * npx) : nullptr;
     if (pre.rc) return pre.rc;
     h->pre_kernel_ms = 0;
-    for (size_t f0 = 0; f0 < (size_t)N; f0 += F) {
-        const int nf = (int)((size_t)N - f0 < F ? (size_t)N - f0 : F);
-        const size_t n = (size_t)nf * npx;
-        const dim3 g2((W + 255) / 256, H, nf), blk(256);
-        HIPC(h, hipMemcpyAsync(src, frames + f0 * npx * channels, n * channels, hipMemcpyHostToDevice, h->stream));
+    for (int f0 = 0; f0 < N; f0 += nf) {
+        const int n = std::min(nf, N - f0);
+        const size_t px = (size_t)n * npx;
+        const dim3 g2((W + 255) / 256, H, n), blk(256);
+        HIPC(h, hipMemcpyAsync(src, frames + f0 * npx * channels, px * channels, hipMemcpyHostToDevice, h->stream));
         HIPC(h, hipEventRecord(h->ev[0], h->stream));       // the eight kernels of the chunk, without the upload
-        HIPC(h, hipMemsetAsync(mx, 0, (size_t)nf * SAL_MX * sizeof(int), h->stream));
-        hipLaunchKernelGGL(sal::k_sal_gray, dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, src, channels, n, g0);
+        HIPC(h, hipMemsetAsync(mx, 0, (size_t)n * SAL_MX * sizeof(int), h->stream));
+        hipLaunchKernelGGL(sal::k_sal_gray, dim3((unsigned)((px + 255) / 256)), blk, 0, h->stream, src, channels, px, g0);
         hipLaunchKernelGGL(sal::k_sal_blur3, g2, blk, 0, h->stream, g0, g1, H, W);
         hipLaunchKernelGGL(sal::k_sal_blur3, g2, blk, 0, h->stream, g1, g0, H, W);
-        hipLaunchKernelGGL(sal::k_sal_rowprefix, dim3(H, nf), dim3(64), 0, h->stream, g0, H, W, P);
-        hipLaunchKernelGGL(sal::k_sal_integral, dim3((W + 1 + 255) / 256, nf), blk, 0, h->stream, P, H, W, I);
-        const dim3 g8((W + 255) / 256, (H + SAL_ROWS - 1) / SAL_ROWS, nf);
+        hipLaunchKernelGGL(sal::k_sal_rowprefix, dim3(H, n), dim3(64), 0, h->stream, g0, H, W, P);
+        hipLaunchKernelGGL(sal::k_sal_integral, dim3((W + 1 + 255) / 256, n), blk, 0, h->stream, P, H, W, I);
+        const dim3 g8((W + 255) / 256, (H + SAL_ROWS - 1) / SAL_ROWS, n);
         hipLaunchKernelGGL(sal::k_sal_scales, g8, blk, 0, h->stream, g0, I, H, W, mon, moff, mx);
         hipLaunchKernelGGL(sal::k_sal_mix_scales, g8, blk, 0, h->stream, mon, moff, H, W, ion, ioff, mx);
         hipLaunchKernelGGL(sal::k_sal_mix_onoff, g2, blk, 0, h->stream, ion, ioff, H, W, mx, f32 ? nullptr : out + f0 * npx,
                            f32 ? (float*)out + f0 * npx : nullptr);
         HIPC(h, hipGetLastError());
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
-        if (echo16_out) { const int rc = echo_from_device_rgb(h, src, n, decho, echo16_out + f0 * npx); if (rc) return rc; }
+        if (echo16_out) { const int rc = echo_from_device_rgb(h, src, px, decho, echo16_out + f0 * npx); if (rc) return rc; }
         HIPC(h, hipStreamSynchronize(h->stream));        // (one chunk holds 2^27 pixels: a study is one chunk; the event pair is read per chunk)
         float t = 0;
         HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
@@ -244,51 +194,21 @@ int saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, in
 {
     if (!h || !frames || !out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
     if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
-    void* d = nullptr;
+    const uint8_t* d = nullptr;
     int rc = saliency_to_device(h, frames, N, H, W, channels, f32, &d);
     if (rc) return rc;
     HIPC(h, hipMemcpy(out, d, (size_t)N * H * W * (f32 ? sizeof(float) : 1), hipMemcpyDeviceToHost));
     return TF_OK;
 }
-
-int calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, float scale, void* flow_out, tf_stats* st,
-                      bool out_f16 = false, uint16_t* echo16_out = nullptr)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
-    if (echo16_out && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "the echo needs RGB frames (channels == 3), got %d", channels);
-    // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are)
-    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, scale, flow_out, W_HOST, f32, out_f16};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    void* dsal = nullptr;
-    rc = finish_host_call(h, saliency_to_device(h, frames, N, H, W, channels, f32, &dsal, echo16_out));
-    if (rc) return rc;
-    c.in0 = (const uint8_t*)dsal; c.where = W_IN_DEV;
-    return calc_entry(h, c, st);
-}
 }  // namespace
 
 TF_API int tf_saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, uint8_t* saliency_out)
 {
-    return h ? finish_host_call(h, saliency_frames(h, frames, N, H, W, channels, false, saliency_out)) : TF_ERR_INVALID_ARG;
+    return finish_host_call(h, saliency_frames(h, frames, N, H, W, channels, false, saliency_out));
 }
 TF_API int tf_saliency_frames_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float* saliency_out)
 {
-    return h ? finish_host_call(h, saliency_frames(h, frames, N, H, W, channels, true, saliency_out)) : TF_ERR_INVALID_ARG;
-}
-TF_API int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
-{
-    return calc_seq_saliency(h, frames, N, H, W, channels, false, scale, flow_out, st);
-}
-TF_API int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
-{
-    return calc_seq_saliency(h, frames, N, H, W, channels, true, scale, flow_out, st);
-}
-TF_API int tf_calc_seq_saliency_f16(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, float scale,
-                                    uint16_t* flow16_out, uint16_t* echo16_out, tf_stats* st)
-{
-    return calc_seq_saliency(h, frames, N, H, W, channels, map_f32 != 0, scale, flow16_out, st, true, echo16_out);
+    return finish_host_call(h, saliency_frames(h, frames, N, H, W, channels, true, saliency_out));
 }
 
 namespace {
@@ -1077,67 +997,136 @@ TF_API int tf_wase_compensate(tf_handle* h, float* flows, int n_flows, const uin
     return finish_host_call(h, wase_compensate(h, flows, n_flows, bkgd, n_frames, H, W, scale, background_out));
 }
 
-// ---- a WASE-compensated study in one call: frames and bkgd mask in, (flow - background) * scale out -------------------------------
+// ---- a study call: the frames of a study in, its `flow` array (and `echo`) out ---------------------------------------------------
 namespace {
-// What tf_calc_seq_rgb_wase and tf_calc_seq_saliency_wase share (saliency: the solver's frames are the saliency maps, uint8 or --
-// map_f32 -- float).  The flows never leave the device between the solve and the compensation: the solver writes them, unscaled
-// float32, into PRE_WS_FLOW (the lanes and sub-batches of tf_calc_seq_device), the reduction reads them there, and k_wase_out
-// writes the compensated, scaled flows in the call's output type into PRE_WS_OUT, which is copied to the caller's buffer.
-int calc_seq_wase(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool saliency, bool map_f32, const uint8_t* bkgd,
-                  int n_frames, float scale, bool out_f16, void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st)
+enum StudyFrames { FR_GRAY, FR_SAL_U8, FR_SAL_F32 };     // what the solver sees: the conditioned gray frames, or the saliency maps
+// what every study entry point fills
+struct Study {
+    const uint8_t* frames; int N, H, W, channels;        // host, uint8 [N][H][W][channels]
+    StudyFrames sees;
+    float scale; bool out_f16;
+    void* flow_out; uint16_t* echo16_out;                // host: [N-1][H][W][2] of the output type; [N][H][W] halves or null
+    bool wase = false;                                   // (flow - background) * scale, from the bkgd mask [n_frames][H][W][2]
+    const uint8_t* bkgd = nullptr; int n_frames = 0; float* background_out = nullptr;   // (host, [N-1] or null)
+};
+
+// the solver's frames of study s on the device (`own`: a submitted job's buffer for them, see condition_to_device)
+int study_frames_to_device(tf_handle* h, const Study& s, uint8_t* own, const uint8_t** dfr)
 {
-    if (saliency && channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
-    if (echo16_out && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "the echo needs RGB frames (channels == 3), got %d", channels);
-    if (!bkgd || n_frames < 1) return fail(h, TF_ERR_INVALID_ARG, "a wase study needs a bkgd mask of at least 1 frame, got %d", n_frames);
-    Call c{MODE_SEQ, frames, nullptr, N - 1, H, W, 1.0f, flow_out, W_HOST, saliency && map_f32, out_f16};
-    int rc = check_call(h, c);
-    if (rc) return rc;
-    if (N > 65535 || n_frames > 65535) return fail(h, TF_ERR_UNSUPPORTED, "a wase study takes at most 65535 frames and mask frames");   // (grid dimensions)
-    const int P = N - 1;
-    const size_t hw2 = (size_t)H * W * 2, elt = out_f16 ? sizeof(uint16_t) : sizeof(float);
-    void* dfr = nullptr;
-    if (saliency) rc = saliency_to_device(h, frames, N, H, W, channels, map_f32, &dfr, echo16_out);
-    else { uint8_t* dgray = nullptr; rc = condition_to_device(h, frames, N, H, W, &dgray, nullptr, echo16_out); dfr = dgray; }
-    if (rc) return rc;
+    return s.sees == FR_GRAY ? condition_to_device(h, s.frames, s.N, s.H, s.W, dfr, own, s.echo16_out)
+                             : saliency_to_device(h, s.frames, s.N, s.H, s.W, s.channels, s.sees == FR_SAL_F32, dfr, s.echo16_out);
+}
+
+// The tail of a WASE study.  The flows never leave the device between the solve and the compensation: the solver has written them,
+// unscaled float32, into dflow (PRE_WS_FLOW); the reduction reads them there, and k_wase_out writes the compensated, scaled flows in
+// the call's output type into PRE_WS_OUT, which is copied to the caller's buffer.
+int wase_study_tail(tf_handle* h, const Study& s, const float* dflow)
+{
+    const int P = s.N - 1, H = s.H, W = s.W;
+    const size_t hw2 = (size_t)H * W * 2, elt = s.out_f16 ? sizeof(uint16_t) : sizeof(float);
     Pre pre(h);
-    auto* dflow = pre.get<float>(tf_handle::PRE_WS_FLOW, (size_t)P * hw2);
     auto* dout = pre.get<uint8_t>(tf_handle::PRE_WS_OUT, (size_t)P * hw2 * elt);
-    auto* dmask = pre.get<uint8_t>(tf_handle::PRE_AN_MASK, (size_t)n_frames * hw2);
+    auto* dmask = pre.get<uint8_t>(tf_handle::PRE_AN_MASK, (size_t)s.n_frames * hw2);
     if (pre.rc) return pre.rc;
-    c.in0 = (const uint8_t*)dfr; c.out = dflow; c.where = W_DEV; c.out_f16 = false;
-    rc = calc_entry(h, c, st);                            // (returns with every lane's stream drained: the flows are there)
-    if (rc) return rc;
-    const hipStream_t s = h->stream;
-    HIPC(h, hipMemcpyAsync(dmask, bkgd, (size_t)n_frames * hw2, hipMemcpyHostToDevice, s));
-    HIPC(h, hipEventRecord(h->ev[0], s));                 // the reduction and the output kernel, without the copies
+    const hipStream_t stream = h->stream;
+    HIPC(h, hipMemcpyAsync(dmask, s.bkgd, (size_t)s.n_frames * hw2, hipMemcpyHostToDevice, stream));
+    HIPC(h, hipEventRecord(h->ev[0], stream));                // the reduction and the output kernel, without the copies
     float* wbg = nullptr;
-    rc = wase_backgrounds(h, dflow, dmask, P, n_frames, H, W, &wbg);
+    const int rc = wase_backgrounds(h, dflow, dmask, P, s.n_frames, H, W, &wbg);
     if (rc) return rc;
     const Geom g = make_geom(W, H);
-    if (out_f16) hipLaunchKernelGGL(k_wase_out<uint16_t>, out_grid<uint16_t>(g, P), dim3(256), 0, s, dflow, wbg, H, W, scale, (uint16_t*)dout);
-    else hipLaunchKernelGGL(k_wase_out<float>, out_grid<float>(g, P), dim3(256), 0, s, dflow, wbg, H, W, scale, (float*)dout);
+    if (s.out_f16) hipLaunchKernelGGL(k_wase_out<uint16_t>, out_grid<uint16_t>(g, P), dim3(256), 0, stream, dflow, wbg, H, W, s.scale, (uint16_t*)dout);
+    else hipLaunchKernelGGL(k_wase_out<float>, out_grid<float>(g, P), dim3(256), 0, stream, dflow, wbg, H, W, s.scale, (float*)dout);
     HIPC(h, hipGetLastError());
-    HIPC(h, hipEventRecord(h->ev[1], s));
-    HIPC(h, hipMemcpyAsync(flow_out, dout, (size_t)P * hw2 * elt, hipMemcpyDeviceToHost, s));
-    if (background_out) HIPC(h, hipMemcpyAsync(background_out, wbg, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPC(h, hipStreamSynchronize(s));
+    HIPC(h, hipEventRecord(h->ev[1], stream));
+    HIPC(h, hipMemcpyAsync(s.flow_out, dout, (size_t)P * hw2 * elt, hipMemcpyDeviceToHost, stream));
+    if (s.background_out) HIPC(h, hipMemcpyAsync(s.background_out, wbg, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIPC(h, hipStreamSynchronize(stream));
     float t = 0;
     HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
     h->wase_kernel_ms = t;
     return TF_OK;
 }
+
+// Every study entry point: the study's own argument checks, check_call (on the host frames, before anything is uploaded), the ticket,
+// the WASE kernels' grid limits -- the order every route had, so each refusal is the one it was (the saliency pass checks its own
+// limits) -- then the frames to the device and the solve.  `submit` (a plain RGB study only): the frames are conditioned now, on the
+// handle's stream, into a buffer the job owns; the solve is queued and *ticket is what tf_wait takes.
+int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr, bool submit = false)
+{
+    struct Owned { uint8_t* p = nullptr; ~Owned() { if (p) (void)hipFree(p); } } own;     // (freed after the failed call has been drained)
+    auto run = [&]() -> int {
+        if (!h) return TF_ERR_INVALID_ARG;
+        if (s.sees != FR_GRAY && s.channels != 1 && s.channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", s.channels);
+        if (s.echo16_out && s.channels != 3) return fail(h, TF_ERR_INVALID_ARG, "the echo needs RGB frames (channels == 3), got %d", s.channels);
+        if (s.wase && (!s.bkgd || s.n_frames < 1)) return fail(h, TF_ERR_INVALID_ARG, "a wase study needs a bkgd mask of at least 1 frame, got %d", s.n_frames);
+        if (submit && (s.sees != FR_GRAY || s.wase)) return fail(h, TF_ERR_UNSUPPORTED, "only a plain RGB study can be submitted");
+        // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are); a WASE study's scale is k_wase_out's
+        Call c{MODE_SEQ, s.frames, nullptr, s.N - 1, s.H, s.W, s.wase ? 1.0f : s.scale, s.flow_out, W_HOST, s.sees == FR_SAL_F32, s.out_f16};
+        int rc = check_call(h, c);
+        if (rc) return rc;
+        if (submit && !ticket) return TF_ERR_INVALID_ARG;
+        if (s.wase && (s.N > 65535 || s.n_frames > 65535)) return fail(h, TF_ERR_UNSUPPORTED, "a wase study takes at most 65535 frames and mask frames");   // (grid dimensions)
+        if (submit) {
+            HIPC(h, hipSetDevice(h->dev));
+            HIPC(h, hipMalloc(&own.p, (size_t)s.N * s.H * s.W));
+        }
+        rc = study_frames_to_device(h, s, own.p, &c.in0);
+        if (rc) return rc;
+        c.where = W_IN_DEV;
+        // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
+        if (submit) { uint8_t* p = own.p; own.p = nullptr; return submit_entry(h, c, ticket, p); }   // (the job's from here on)
+        if (!s.wase) return calc_entry(h, c, st);
+        Pre pre(h);
+        auto* dflow = pre.get<float>(tf_handle::PRE_WS_FLOW, (size_t)c.n_pairs * s.H * s.W * 2);
+        if (pre.rc) return pre.rc;
+        c.out = dflow; c.where = W_DEV; c.out_f16 = false;
+        rc = calc_entry(h, c, st);                            // (returns with every lane's stream drained: the flows are there)
+        return rc ? rc : wase_study_tail(h, s, dflow);
+    };
+    return finish_host_call(h, run());
+}
 }  // namespace
 
+TF_API int tf_calc_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, tf_stats* st)
+{
+    return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, false, flow_out, nullptr}, st);
+}
+TF_API int tf_submit_seq_rgb(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, float* flow_out, int* ticket)
+{
+    return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, false, flow_out, nullptr}, nullptr, ticket, true);
+}
+TF_API int tf_calc_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
+                               tf_stats* st)
+{
+    return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, true, flow16_out, echo16_out}, st);
+}
+TF_API int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
+                                 int* ticket)
+{
+    return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, true, flow16_out, echo16_out}, nullptr, ticket, true);
+}
+TF_API int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
+{
+    return study_call(h, {frames, N, H, W, channels, FR_SAL_U8, scale, false, flow_out, nullptr}, st);
+}
+TF_API int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
+{
+    return study_call(h, {frames, N, H, W, channels, FR_SAL_F32, scale, false, flow_out, nullptr}, st);
+}
+TF_API int tf_calc_seq_saliency_f16(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, float scale,
+                                    uint16_t* flow16_out, uint16_t* echo16_out, tf_stats* st)
+{
+    return study_call(h, {frames, N, H, W, channels, map_f32 ? FR_SAL_F32 : FR_SAL_U8, scale, true, flow16_out, echo16_out}, st);
+}
 TF_API int tf_calc_seq_rgb_wase(tf_handle* h, const uint8_t* rgb, int N, int H, int W, const uint8_t* bkgd, int n_frames, float scale, int out_f16,
                                 void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, calc_seq_wase(h, rgb, N, H, W, 3, false, false, bkgd, n_frames, scale, out_f16 != 0, flow_out, echo16_out, background_out, st));
+    return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, out_f16 != 0, flow_out, echo16_out, true, bkgd, n_frames, background_out}, st);
 }
 TF_API int tf_calc_seq_saliency_wase(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, int map_f32, const uint8_t* bkgd,
                                      int n_frames, float scale, int out_f16, void* flow_out, uint16_t* echo16_out, float* background_out, tf_stats* st)
 {
-    if (!h) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, calc_seq_wase(h, frames, N, H, W, channels, true, map_f32 != 0, bkgd, n_frames, scale, out_f16 != 0, flow_out, echo16_out,
-                                             background_out, st));
+    return study_call(h, {frames, N, H, W, channels, map_f32 ? FR_SAL_F32 : FR_SAL_U8, scale, out_f16 != 0, flow_out, echo16_out, true, bkgd,
+                          n_frames, background_out}, st);
 }

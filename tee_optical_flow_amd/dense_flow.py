@@ -39,9 +39,10 @@ def _mask_stack(a, name):
     return np.ascontiguousarray(a).view(np.uint8)
 
 
-# What a submitted job leaves for wait(): the result array, the frame count whose last flow wait() repeats (0: no repeat), whether
-# the job is a payload one (wait() then returns (out, echo), echo an array or None), and the input arrays the library reads until then
-_Job = namedtuple("_Job", "out pad_n payload echo inputs", defaults=(0, False, None, ()))
+# What a call leaves to be collected (at once, or by wait()): the result array, the frame count whose last flow is repeated (0: no
+# repeat), what the caller gets after the flows (a study's echo -- an array or None -- and / or its backgrounds), and the input arrays
+# the library reads until then
+_Job = namedtuple("_Job", "out pad_n extra inputs", defaults=(0, (), ()))
 
 
 class _PinnedPool:
@@ -103,35 +104,30 @@ class DenseFlow:
         self._jobs = {}                                    # ticket -> what a submitted job reads and writes (kept alive until wait)
         self.algo = algo
         if algo == "deepflow":
-            dp = _lib.TfDeepflowParams()
-            _lib.check(self._L.tf_default_deepflow_params(C.byref(dp)), None, "tf_default_deepflow_params")
-            dp.max_batch = int(max_batch)
+            p, create = _lib.TfDeepflowParams(), "tf_create_deepflow"
+            _lib.check(self._L.tf_default_deepflow_params(C.byref(p)), None, "tf_default_deepflow_params")
+            p.max_batch = int(max_batch)
             for k, v in params.items():
-                if not hasattr(dp, k):
+                if not hasattr(p, k):
                     raise OpticalFlowCalculationError(f"unknown DeepFlow parameter {k!r}")
-                setattr(dp, k, v)
-            h = C.c_void_p()
-            _lib.check(self._L.tf_create_deepflow(C.byref(dp), int(device_id), C.byref(h)), None, "tf_create_deepflow")
-            self._h = h
-            self.device_id = int(device_id)
-            self.last_stats = None
-            return
-        if algo != "TVL1":
+                setattr(p, k, v)
+        elif algo == "TVL1":
+            p, create = _lib.TfParams(), "tf_create"
+            _lib.check(self._L.tf_default_params(C.byref(p)), None, "tf_default_params")
+            p.max_batch = int(max_batch)
+            variant = params.pop("variant", "cpu")
+            if variant not in ("cpu", "cuda", 0, 1):
+                raise OpticalFlowCalculationError(f"variant must be 'cpu' or 'cuda', got {variant!r}")
+            p.variant = 1 if variant in ("cuda", 1) else 0          # TF_VARIANT_CUDA: cv2.cuda.OpticalFlowDual_TVL1 semantics (row a5)
+            for k, v in params.items():
+                key = "lambda_" if k in ("lambda", "lambda_") else k
+                if not hasattr(p, key):
+                    raise OpticalFlowCalculationError(f"unknown DualTVL1 parameter {k!r}")
+                setattr(p, key, v)
+        else:
             raise OpticalFlowCalculationError("OF_algo only supports deepflow or TVL1")
-        p = _lib.TfParams()
-        _lib.check(self._L.tf_default_params(C.byref(p)), None, "tf_default_params")
-        p.max_batch = int(max_batch)
-        variant = params.pop("variant", "cpu")
-        if variant not in ("cpu", "cuda", 0, 1):
-            raise OpticalFlowCalculationError(f"variant must be 'cpu' or 'cuda', got {variant!r}")
-        p.variant = 1 if variant in ("cuda", 1) else 0          # TF_VARIANT_CUDA: cv2.cuda.OpticalFlowDual_TVL1 semantics (row a5)
-        for k, v in params.items():
-            key = "lambda_" if k in ("lambda", "lambda_") else k
-            if not hasattr(p, key):
-                raise OpticalFlowCalculationError(f"unknown DualTVL1 parameter {k!r}")
-            setattr(p, key, v)
         h = C.c_void_p()
-        _lib.check(self._L.tf_create(C.byref(p), int(device_id), C.byref(h)), None, "tf_create")
+        _lib.check(getattr(self._L, create)(C.byref(p), int(device_id), C.byref(h)), None, create)
         self._h = h
         self.device_id = int(device_id)
         self.last_stats = None
@@ -247,36 +243,68 @@ class DenseFlow:
         _lib.check(self._L.tf_condition_frames(self._h, nparr.ctypes.data, N, H, W, out.ctypes.data), self._h, "tf_condition_frames")
         return out
 
+    # ---- a study: RGB frames in, the study file's `flow` array out.  The ten public forms below are cells of one grid -- the solver's
+    # frames (conditioned gray | saliency maps) x the output (float32 | the file's float16 payload, with its echo) x the compensation
+    # (none | WASE) x the collection (waited for | submitted) -- and _study is the one path through it -----------------------------------
+    @staticmethod
+    def _rgb_study(nparr, min_frames=2, channels=(3,)):
+        nparr = _u8_image_stack(nparr, "nparr", 4)
+        if nparr.shape[3] not in channels or nparr.shape[0] < min_frames:
+            raise OpticalFlowCalculationError(f"nparr must be [N>={min_frames},H,W,3], got {nparr.shape}")
+        return nparr
+
+    def _study(self, nparr, scale, pad_last, *, saliency=False, map_dtype="f32", f16=False, echo=False, bkgd_mask=None, submit=False):
+        """One study call: the frame check, the pinned outputs, the C function of the cell and its arguments.  -> what _collect makes of
+        the job, or (`submit`) the ticket wait() collects it by.  Only the float32 saliency form takes one-channel frames."""
+        wase = bkgd_mask is not None
+        nparr = self._rgb_study(nparr, channels=(1, 3) if saliency and not (f16 or wase) else (3,))
+        N, H, W, ch = nparr.shape
+        if wase:
+            mask = np.ascontiguousarray(bkgd_mask)
+            if mask.dtype != np.bool_ or mask.ndim != 4 or mask.shape[0] < 1 or mask.shape[1:] != (H, W, 2):
+                raise OpticalFlowCalculationError(f"bkgd mask must be bool [n>=1,{H},{W},2], got {mask.dtype} {mask.shape}")
+        if submit and (saliency or wase):
+            raise OpticalFlowCalculationError("only a study without saliency and background compensation can be submitted")
+        out = self._pool.empty((N if pad_last else N - 1, H, W, 2), np.float16 if f16 else np.float32)
+        e16 = self._pool.empty((N, H, W), np.float16) if echo else None
+        bg = np.empty(N - 1, np.float32) if wase else None
+        st, t = _lib.TfStats(), C.c_int(-1)
+        map_f32 = saliency and self._map_is_f32(map_dtype)
+        e, last = e16.ctypes.data if echo else None, C.byref(t) if submit else C.byref(st)
+        # tf_{calc,submit}_seq_{rgb,saliency}{,_f32,_f16,_wase}(h, frames, N, H, W[, channels[, map_f32]], <the form's own>)
+        if wase:
+            form, own = "_wase", (mask.view(np.uint8).ctypes.data, mask.shape[0], float(scale), int(f16), out.ctypes.data, e, bg.ctypes.data, last)
+        elif f16:
+            form, own = "_f16", (float(scale), out.ctypes.data, e, last)
+        else:
+            form, own = "_f32" if map_f32 else "", (float(scale), out.ctypes.data, last)
+        name = ("tf_submit_seq_" if submit else "tf_calc_seq_") + ("saliency" if saliency else "rgb") + form
+        frames = (self._h, nparr.ctypes.data, N, H, W)
+        if saliency:
+            frames += (ch, int(map_f32)) if f16 or wase else (ch,)
+        _lib.check(getattr(self._L, name)(*frames, *own), self._h, name)
+        job = _Job(out, N if pad_last else 0, ((e16,) if f16 else ()) + ((bg,) if wase else ()))
+        if submit:
+            self._jobs[t.value] = job
+            return t.value
+        self._finish(st)
+        return self._collect(job)
+
+    @staticmethod
+    def _collect(job):
+        """What a finished job returns: its result array, the last flow repeated (reference :599) inside the pinned buffer where that was
+        asked for -- alone, or a study's (out, echo), (out, bg) or (out, echo, bg)."""
+        if job.pad_n:
+            job.out[job.pad_n - 1] = job.out[job.pad_n - 2]
+        return (job.out,) + job.extra if job.extra else job.out
+
     def calc_study(self, nparr, scale=1.0, pad_last=False):
         """RGB study uint8 [N,H,W,3] -> float32 [N-1,H,W,2]: conditioning and all pair solves stay on the device.
         `pad_last`: the result is [N,H,W,2] with the last flow repeated (reference :599) -- written into one pinned buffer, no
         concatenate on the host; with `scale` = pixel_spacing * frame_rate this is the study's whole flow array (:600)."""
-        nparr = _u8_image_stack(nparr, "nparr", 4)
-        if nparr.shape[3] != 3 or nparr.shape[0] < 2:
-            raise OpticalFlowCalculationError(f"nparr must be [N>=2,H,W,3], got {nparr.shape}")
-        N, H, W, _ = nparr.shape
-        out = self._out((N if pad_last else N - 1, H, W, 2))
-        st = _lib.TfStats()
-        _lib.check(self._L.tf_calc_seq_rgb(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data, C.byref(st)),
-                   self._h, "tf_calc_seq_rgb")
-        self._finish(st)
-        if pad_last:
-            out[N - 1] = out[N - 2]
-        return out
+        return self._study(nparr, scale, pad_last)
 
     # ---- the study file's float16 payload, made on the device (reference :400-404 casts on the host at write time) -------------
-    @staticmethod
-    def _rgb_study(nparr, min_frames=2):
-        nparr = _u8_image_stack(nparr, "nparr", 4)
-        if nparr.shape[3] != 3 or nparr.shape[0] < min_frames:
-            raise OpticalFlowCalculationError(f"nparr must be [N>={min_frames},H,W,3], got {nparr.shape}")
-        return nparr
-
-    def _payload_out(self, N, H, W, pad_last, echo):
-        """(flow16 [N or N-1,H,W,2], echo16 [N,H,W] or None), both float16 in pinned host memory"""
-        return (self._pool.empty((N if pad_last else N - 1, H, W, 2), np.float16),
-                self._pool.empty((N, H, W), np.float16) if echo else None)
-
     def echo_frames(self, nparr):
         """The study file's `echo` dataset on the device: RGB frames uint8 [N,H,W,3] -> float16 [N,H,W] =
         frames.rgb2gray(nparr).astype(np.float16), bit for bit (the float64 luma rounded once to half)."""
@@ -290,42 +318,16 @@ class DenseFlow:
         """calc_study with the flows rounded to float16 by the output kernel: RGB study uint8 [N,H,W,3] -> (flow16, echo16).  flow16 has
         the bits of calc_study(nparr, scale, pad_last).astype(np.float16) -- the study file's `flow` dataset with `scale` = pixel_spacing
         * frame_rate and `pad_last` -- at half the download; echo16 is echo_frames(nparr), made from the same upload, or None."""
-        nparr = self._rgb_study(nparr)
-        N, H, W, _ = nparr.shape
-        out, e16 = self._payload_out(N, H, W, pad_last, echo)
-        st = _lib.TfStats()
-        _lib.check(self._L.tf_calc_seq_rgb_f16(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data,
-                                               e16.ctypes.data if echo else None, C.byref(st)), self._h, "tf_calc_seq_rgb_f16")
-        self._finish(st)
-        if pad_last:
-            out[N - 1] = out[N - 2]
-        return out, e16
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo)
 
     def calc_study_saliency_payload(self, nparr, scale=1.0, pad_last=True, echo=True, map_dtype="f32"):
         """calc_study_saliency with float16 flows, and the `echo` of the RGB frames: -> (flow16, echo16 | None), as calc_study_payload."""
-        nparr = self._rgb_study(nparr)
-        N, H, W, _ = nparr.shape
-        out, e16 = self._payload_out(N, H, W, pad_last, echo)
-        st = _lib.TfStats()
-        _lib.check(self._L.tf_calc_seq_saliency_f16(self._h, nparr.ctypes.data, N, H, W, 3, 1 if self._map_is_f32(map_dtype) else 0, float(scale),
-                                                    out.ctypes.data, e16.ctypes.data if echo else None, C.byref(st)),
-                   self._h, "tf_calc_seq_saliency_f16")
-        self._finish(st)
-        if pad_last:
-            out[N - 1] = out[N - 2]
-        return out, e16
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo)
 
     def submit_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True):
         """calc_study_payload without waiting: -> ticket; `wait(ticket)` returns the (flow16, echo16 | None) pair.  The frames are
         conditioned and the echo is complete before this returns (nparr may be reused at once)."""
-        nparr = self._rgb_study(nparr)
-        N, H, W, _ = nparr.shape
-        out, e16 = self._payload_out(N, H, W, pad_last, echo)
-        t = C.c_int(-1)
-        _lib.check(self._L.tf_submit_seq_rgb_f16(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data,
-                                                 e16.ctypes.data if echo else None, C.byref(t)), self._h, "tf_submit_seq_rgb_f16")
-        self._jobs[t.value] = _Job(out, pad_n=N if pad_last else 0, payload=True, echo=e16)
-        return t.value
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, submit=True)
 
     def saliency_frames(self, nparr, dtype=np.float32):
         """cv2.saliency.StaticSaliencyFineGrained_create().computeSaliency(frame)[1] for every frame, on the device (reference
@@ -360,18 +362,7 @@ class DenseFlow:
         """RGB study uint8 [N,H,W,3] -> float32 [N-1,H,W,2] with the saliency maps as the solver's frames (no_saliency=False).
         map_dtype "f32" (default): the solver receives computeSaliency()'s CV_32F maps in [0,1], as under opencv-contrib >= 4.5 -- DualTVL1
         multiplies them by 255 in float, DeepFlow takes them as they are; "u8": the 8-bit maps.  `scale` / `pad_last` as in calc_study."""
-        nparr = _u8_image_stack(nparr, "nparr", 4)
-        if nparr.shape[3] not in (1, 3) or nparr.shape[0] < 2:
-            raise OpticalFlowCalculationError(f"nparr must be [N>=2,H,W,3], got {nparr.shape}")
-        N, H, W, ch = nparr.shape
-        out = self._out((N if pad_last else N - 1, H, W, 2))
-        st = _lib.TfStats()
-        fn = self._L.tf_calc_seq_saliency_f32 if self._map_is_f32(map_dtype) else self._L.tf_calc_seq_saliency
-        _lib.check(fn(self._h, nparr.ctypes.data, N, H, W, ch, float(scale), out.ctypes.data, C.byref(st)), self._h, "tf_calc_seq_saliency")
-        self._finish(st)
-        if pad_last:
-            out[N - 1] = out[N - 2]
-        return out
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype)
 
     def clean_masks(self, class_map, class_ids, min_size):
         """The reference's clean_mask (calculate_optical_flow.py:90-111, :113-182) on the device, exact: class map uint8 [N,H,W] ->
@@ -596,49 +587,24 @@ class DenseFlow:
         return flows, bg
 
     # ---- a bkgd_comp="WASE" study in one call: the flows stay on the device between the solve and the compensation -------------
-    def _wase_study(self, nparr, bkgd_mask, scale, pad_last, f16, echo, saliency, map_dtype="f32"):
-        """-> (flows [N or N-1,H,W,2] float32 or float16, echo16 or None, backgrounds float32 [N-1]), the arrays in pinned host memory"""
-        nparr = self._rgb_study(nparr)
-        N, H, W, _ = nparr.shape
-        mask = np.ascontiguousarray(bkgd_mask)
-        if mask.dtype != np.bool_ or mask.ndim != 4 or mask.shape[0] < 1 or mask.shape[1:] != (H, W, 2):
-            raise OpticalFlowCalculationError(f"bkgd mask must be bool [n>=1,{H},{W},2], got {mask.dtype} {mask.shape}")
-        out = self._pool.empty((N if pad_last else N - 1, H, W, 2), np.float16 if f16 else np.float32)
-        e16 = self._pool.empty((N, H, W), np.float16) if echo else None
-        bg = np.empty(N - 1, np.float32)
-        st = _lib.TfStats()
-        tail = (mask.view(np.uint8).ctypes.data, mask.shape[0], float(scale), 1 if f16 else 0, out.ctypes.data,
-                e16.ctypes.data if echo else None, bg.ctypes.data, C.byref(st))
-        if saliency:
-            _lib.check(self._L.tf_calc_seq_saliency_wase(self._h, nparr.ctypes.data, N, H, W, 3, 1 if self._map_is_f32(map_dtype) else 0, *tail),
-                       self._h, "tf_calc_seq_saliency_wase")
-        else:
-            _lib.check(self._L.tf_calc_seq_rgb_wase(self._h, nparr.ctypes.data, N, H, W, *tail), self._h, "tf_calc_seq_rgb_wase")
-        self._finish(st)
-        if pad_last:
-            out[N - 1] = out[N - 2]
-        return out, e16, bg
-
     def calc_study_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False):
         """calc_study, then wase_compensate of its flows, in one device call: RGB study uint8 [N,H,W,3] and bkgd_mask bool [n,H,W,2]
         (mask_dict['bkgd']) -> ((flow - background[p]) * scale float32 [N-1,H,W,2], backgrounds float32 [N-1]), with the bits of
         wase_compensate(calc_study(nparr), bkgd_mask, scale).  `pad_last` as in calc_study."""
-        out, _, bg = self._wase_study(nparr, bkgd_mask, scale, pad_last, False, False, False)
-        return out, bg
+        return self._study(nparr, scale, pad_last, bkgd_mask=bkgd_mask)
 
     def calc_study_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True):
         """calc_study_wase with the flows rounded to float16 by the output kernel -> (flow16, echo16 | None, backgrounds): flow16 has
         the bits of calc_study_wase(...)[0].astype(np.float16), echo16 is echo_frames(nparr) from the same upload."""
-        return self._wase_study(nparr, bkgd_mask, scale, pad_last, True, echo, False)
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, bkgd_mask=bkgd_mask)
 
     def calc_study_saliency_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False, map_dtype="f32"):
         """calc_study_wase with the saliency maps as the solver's frames (calc_study_saliency) -> (flows float32, backgrounds)."""
-        out, _, bg = self._wase_study(nparr, bkgd_mask, scale, pad_last, False, False, True, map_dtype)
-        return out, bg
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, bkgd_mask=bkgd_mask)
 
     def calc_study_saliency_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, map_dtype="f32"):
         """calc_study_saliency_wase with float16 flows and the `echo` of the RGB frames -> (flow16, echo16 | None, backgrounds)."""
-        return self._wase_study(nparr, bkgd_mask, scale, pad_last, True, echo, True, map_dtype)
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, bkgd_mask=bkgd_mask)
 
     def calc_pairs(self, I0s, I1s):
         """B independent pairs: uint8 or float32 [B,H,W] x2 -> float32 [B,H,W,2] (float frames: DualTVL1 scales them by 255 like cv2, DeepFlow
@@ -689,15 +655,7 @@ class DenseFlow:
     def submit_study(self, nparr, scale=1.0, pad_last=False):
         """calc_study without waiting: RGB study uint8 [N,H,W,3] -> ticket; `wait(ticket)` returns float32 [N-1,H,W,2] (or [N,H,W,2] with
         the last flow repeated, `pad_last`).  The frames are conditioned on the device before this returns (nparr may be reused at once)."""
-        nparr = _u8_image_stack(nparr, "nparr", 4)
-        if nparr.shape[3] != 3 or nparr.shape[0] < 2:
-            raise OpticalFlowCalculationError(f"nparr must be [N>=2,H,W,3], got {nparr.shape}")
-        N, H, W, _ = nparr.shape
-        out = self._out((N if pad_last else N - 1, H, W, 2))
-        t = C.c_int(-1)
-        _lib.check(self._L.tf_submit_seq_rgb(self._h, nparr.ctypes.data, N, H, W, float(scale), out.ctypes.data, C.byref(t)), self._h, "tf_submit_seq_rgb")
-        self._jobs[t.value] = _Job(out, pad_n=N if pad_last else 0)
-        return t.value
+        return self._study(nparr, scale, pad_last, submit=True)
 
     def submit_pairs(self, I0s, I1s):
         """calc_pairs without waiting: uint8 [B,H,W] x2 -> ticket; `wait(ticket)` returns float32 [B,H,W,2]."""
@@ -721,11 +679,7 @@ class DenseFlow:
         st = _lib.TfStats()
         _lib.check(self._L.tf_wait(self._h, int(ticket), C.byref(st)), self._h, "tf_wait")
         self._finish(st)
-        if job is None:                                                # the device form: nothing of the host's to hand back
-            return self.last_stats
-        if job.pad_n:
-            job.out[job.pad_n - 1] = job.out[job.pad_n - 2]            # the last flow repeated (reference :599), inside the pinned buffer
-        return (job.out, job.echo) if job.payload else job.out         # submit_study_payload: (flow16, echo16 | None)
+        return self.last_stats if job is None else self._collect(job)      # (None: the device form, nothing of the host's to hand back)
 
     def calc_seq_device(self, dframes_ptr, N, H, W, dflow_ptr, scale=1.0):
         st = _lib.TfStats()

@@ -87,44 +87,56 @@ def flow_for_study(frames_u8, OF_model, mask_dict=None, bkgd_comp="none", conver
     device from `nparr_rgb`, are what the solver sees -- `saliency_map` "f32" (default): as CV_32F in [0,1], what computeSaliency()
     returns under the reference's opencv-contrib >= 4.5 (DualTVL1 then scales by 255 in float, DeepFlow takes [0,1] frames as they
     are); "u8": the 8-bit maps (opencv-contrib 3.x).  Parity of the whole branch is UNPINNED (oracle/saliency_oracle.c)."""
+    return _study_solve(OF_model, nparr_rgb, lambda: frames_u8, mask_dict, bkgd_comp, conversion_factor, saliency=saliency, saliency_map=saliency_map)()
+
+
+def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency=False, saliency_map="f32", payload=False, echo=False, submit=False):
+    """The one place that picks a study's call on the model: -> collect, a callable that returns the study's flow array [N,H,W,2], scaled
+    by `factor` and the last flow repeated (`payload`: the pair (float16 flow array, float16 echo or None) of the study file).  rgb: the
+    study's uint8 RGB frames, or None; gray_frames: () -> the conditioned frames, asked for only where calc_batch is the model's all.
+    The model's study methods form a grid, calc_study[_saliency][_wase][_payload] (DenseFlow has every cell).  The cell asked for is
+    used where the model has it: it compensates, scales and repeats the last flow itself -- `submit`: as submit_study[_payload], solved
+    while the caller goes on, where the model offers that form.  Without it, and never under `payload`: the model's unscaled float32
+    cell calc_study[_saliency], or calc_batch on the conditioned frames; then wase_compensate (or numpy's _compensate), the repeat and
+    the scale on the host, in the reference's order (flow - background) * factor."""
     if bkgd_comp not in ("WASE", "none"):
         raise OpticalFlowCalculationError(f"bkgd_comp value must be [WASE, none], got {bkgd_comp}!")
-    if saliency:
-        if nparr_rgb is None or not hasattr(OF_model, "calc_study_saliency"):
+    wase = bkgd_comp == "WASE"
+    plain = "calc_study_saliency" if saliency else "calc_study"
+    cell = plain + ("_wase" if wase else "") + ("_payload" if payload else "")
+    kw = {"map_dtype": saliency_map} if saliency else {}
+    if saliency and not payload:
+        if rgb is None or not hasattr(model, plain):
             raise OpticalFlowCalculationError("no_saliency=False needs the device engine (DenseFlow.calc_study_saliency) and the "
                                               "study's frames; there is no CPU saliency path")
         if not _saliency_warned[0]:
             _saliency_warned[0] = True
             logger.warning("no_saliency=False: the saliency preprocessing (StaticSaliencyFineGrained, map handed over as %s) is a restatement of "
                            "opencv-contrib that no OpenCV output pins; files written on this branch are not verified against the reference's", saliency_map)
-        if bkgd_comp == "none":
-            # unit scale in the output kernel, last flow repeated inside the pinned result buffer (as the no_saliency=True branch below)
-            return OF_model.calc_study_saliency(nparr_rgb, scale=conversion_factor, pad_last=True, map_dtype=saliency_map)
-        if hasattr(OF_model, "calc_study_saliency_wase"):
-            # solve, compensation and unit scale in one device call (as the no_saliency=True branch below)
-            return OF_model.calc_study_saliency_wase(nparr_rgb, mask_dict["bkgd"], scale=conversion_factor, pad_last=True, map_dtype=saliency_map)[0]
-        flows = OF_model.calc_study_saliency(nparr_rgb, map_dtype=saliency_map)          # saliency maps (:586) + all pairs on the device
-    elif nparr_rgb is not None and bkgd_comp == "WASE" and hasattr(OF_model, "calc_study_wase"):
-        # the flows stay on the device between the solve and the compensation: (flow - background) * factor comes back once, the last
-        # flow repeated inside the pinned result buffer -- the bits of calc_study + wase_compensate + concatenate below
-        return OF_model.calc_study_wase(nparr_rgb, mask_dict["bkgd"], scale=conversion_factor, pad_last=True)[0]
-    elif nparr_rgb is not None and hasattr(OF_model, "calc_study"):
-        if bkgd_comp == "none" and getattr(OF_model, "device_unit_scale", False):
-            # the unit scale (:600, one float32 multiply per value, the same one numpy makes) is applied by the output kernel and
-            # the last flow is repeated (:599) inside the pinned result buffer: no 136-MB concatenate and multiply on the host
-            return OF_model.calc_study(nparr_rgb, scale=conversion_factor, pad_last=True)
-        flows = OF_model.calc_study(nparr_rgb)                   # conditioning (:588) + all pairs on the device
+    # (device_unit_scale is asked of the plain gray cell alone: every later cell was born with `scale` and `pad_last`)
+    if payload or (rgb is not None and hasattr(model, cell) and (cell != "calc_study" or getattr(model, "device_unit_scale", False))):
+        if payload:
+            kw["echo"] = echo
+        if submit and cell in ("calc_study", "calc_study_payload") and hasattr(model, cell.replace("calc", "submit")):
+            # conditioning now, the solve queued on the engine's lanes: the next study's solve is on the GPU while this one finishes
+            ticket = getattr(model, cell.replace("calc", "submit"))(rgb, scale=factor, pad_last=True, **kw)
+            return lambda: model.wait(ticket)
+        got = getattr(model, cell)(rgb, *((mask_dict["bkgd"],) if wase else ()), scale=factor, pad_last=True, **kw)
+        if wase:                                                 # (the backgrounds are not kept)
+            got = got[:2] if payload else got[0]
+        return lambda: got
+    if rgb is not None and hasattr(model, plain):
+        flows = getattr(model, plain)(rgb, **kw)                 # conditioning (:588) or saliency maps (:586) + all pairs on the device
     else:
-        flows = OF_model.calc_batch(frames_u8)                   # float32 [N-1,H,W,2]
-    scaled = False
-    if bkgd_comp == "WASE":
-        if hasattr(OF_model, "wase_compensate"):                 # device: O(N^2 H W) products, numpy's summation order kept
-            flows, _ = OF_model.wase_compensate(flows, mask_dict["bkgd"], scale=conversion_factor)   # (flow - background) * factor
-            scaled = True
-        else:
-            flows = np.stack([_compensate(flows[i], mask_dict, "WASE") for i in range(flows.shape[0])])
+        flows = model.calc_batch(gray_frames())                  # float32 [N-1,H,W,2]
+    compensates = wase and hasattr(model, "wase_compensate")
+    if compensates:                                              # device: O(N^2 H W) products, numpy's summation order kept
+        flows, _ = model.wase_compensate(flows, mask_dict["bkgd"], scale=factor)   # (flow - background) * factor
+    elif wase:
+        flows = np.stack([_compensate(flows[i], mask_dict, "WASE") for i in range(flows.shape[0])])
     flows = np.concatenate([flows, flows[-1:]], axis=0)          # copy last optical flow (:599)
-    return flows if scaled else flows * conversion_factor         # (:600)
+    result = flows if compensates else flows * factor            # (:600)
+    return lambda: result
 
 
 _PAYLOADS = ("host", "device")
@@ -223,8 +235,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             raise ConfigurationError(f"Input for mode must be [A4C, otsu, RVIO_2class], not {mode}.")
     own = flow_model is None
     model = make_flow_model(OF_algo, config) if own else flow_model
-    collect = None                                # () -> the study's flow array; payload="device": -> (float16 flow array, float16 echo or None)
-    from_device = False
+    from_device = False                           # payload="device" serves: collect() -> (float16 flow array, float16 echo or None)
     try:
         if mask_dict is None and mode == "otsu":
             # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
@@ -240,49 +251,16 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             if refused is not None:
                 _payload_fallback(refused)
             from_device = refused is None
-        if from_device:
-            # the file's float16 `flow` (unit scale and rounding in the output kernel, last flow repeated in the pinned buffer) and `echo`
-            # (from the upload the conditioning / saliency pass reads) come from the engine; the echo only where a file is written
-            kw = dict(scale=conversion_factor, pad_last=True, echo=save_path is not None)
-            rgb = np.ascontiguousarray(nparr)
-            if bkgd_comp == "WASE":
-                # solve, background compensation, unit scale and rounding in one synchronous device call (the backgrounds are not kept)
-                if not no_saliency:
-                    pair = model.calc_study_saliency_wase_payload(rgb, mask_dict["bkgd"], map_dtype=saliency_map, **kw)[:2]
-                else:
-                    pair = model.calc_study_wase_payload(rgb, mask_dict["bkgd"], **kw)[:2]
-                collect = lambda: pair
-            elif not no_saliency:
-                pair = model.calc_study_saliency_payload(rgb, map_dtype=saliency_map, **kw)
-                collect = lambda: pair
-            elif _submit and not own and hasattr(model, "submit_study_payload"):
-                ticket = model.submit_study_payload(rgb, **kw)
-                collect = lambda: model.wait(ticket)
-            else:
-                pair = model.calc_study_payload(rgb, **kw)
-                collect = lambda: pair
-        elif not no_saliency:
+        if not no_saliency and not rgb_u8:
             # the reference's default branch (:559-560, :586): cv2.saliency.StaticSaliencyFineGrained on every frame
-            if not rgb_u8:
-                raise OpticalFlowCalculationError(f"no_saliency=False needs uint8 RGB frames [N,H,W,3], got {nparr.dtype} {nparr.shape}")
-            flow_arr = flow_for_study(None, model, mask_dict, bkgd_comp, conversion_factor,
-                                      nparr_rgb=np.ascontiguousarray(nparr), saliency=True, saliency_map=saliency_map)
-        else:
-            on_device = hasattr(model, "calc_study") and rgb_u8
-            if (_submit and not own and on_device and bkgd_comp == "none" and hasattr(model, "submit_study")
-                    and getattr(model, "device_unit_scale", False)):
-                # conditioning now, the solve queued on the engine's lanes: the same call as flow_for_study's device branch, not waited for
-                ticket = model.submit_study(np.ascontiguousarray(nparr), scale=conversion_factor, pad_last=True)
-                collect = lambda: model.wait(ticket)
-            else:
-                frames = None if on_device else condition_frames(nparr)
-                flow_arr = flow_for_study(frames, model, mask_dict, bkgd_comp, conversion_factor,
-                                          nparr_rgb=np.ascontiguousarray(nparr) if on_device else None)
+            raise OpticalFlowCalculationError(f"no_saliency=False needs uint8 RGB frames [N,H,W,3], got {nparr.dtype} {nparr.shape}")
+        # the echo (from the upload the conditioning / saliency pass reads) only where a file is written
+        collect = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
+                               conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=from_device,
+                               echo=save_path is not None, submit=_submit and not own)
     finally:
         if own:
             model.close()
-    if collect is None:
-        collect = lambda: flow_arr
 
     def finish():
         flows, echo16 = collect() if from_device else (collect(), None)

@@ -228,7 +228,7 @@ int tf_calc_seq_saliency_f32(tf_handle* h, const uint8_t* frames, int N, int H, 
  * complete when the call -- tf_submit_seq_rgb_f16 included -- returns; the flows of a submitted job are complete at tf_wait.
  * tf_calc_seq_saliency_f16: echo16_out needs channels == 3 (TF_ERR_INVALID_ARG otherwise).  tf_echo_frames is the echo alone
  * (rgb: host uint8 [N][H][W][3]); it runs on the handle's stream and never on a lane's.  Device-pointer float16 destinations are not
- * offered. */
+ * offered (a held study, tf_hold_next below, is the library's own device copy of the payload). */
 int tf_calc_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
                         tf_stats* st);
 int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, uint16_t* flow16_out, uint16_t* echo16_out,
@@ -407,6 +407,52 @@ int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const doub
  * or the last projection was tf_polar_project_param.  No GPU work. */
 int tf_radlong_shape(tf_handle* h, int* shape);
 
+/* ---- a study HELD on the device: the study file's payload put there once, and the consumer's tail reading it there.  The calls above
+ *      take host arrays and upload them on every call; one 65-frame 512 x 512 study's tail (three rad/long params, three polar params,
+ *      angle mode, area series, AV centroids, overlay) uploads the same flow seven times and the same masks eight times.  A held study
+ *      lives in device buffers of the handle's own -- not in the scratch the other calls share, so no other call overwrites it -- until
+ *      the next tf_hold_study / armed study call, tf_release_study or tf_destroy.
+ *      Device memory, allocated per study and freed with it: N H W 4 bytes of flow, n_echo H W 2 of echo, n_frames H W C per mask slot.
+ * tf_hold_study: flow16 host float16 [N][H][W][2] (the file's `flow`), echo16 host float16 [n_echo][H][W] or NULL with n_echo 0.
+ *   Replaces any held study and empties every mask slot.
+ * tf_hold_mask: mask host uint8 [n_frames][H][W][C], C = 1 or 2, H and W the held study's, into slot [0, TF_HELD_SLOTS); replaces
+ *   what the slot held.
+ * tf_hold_next(h, 1): arms the NEXT study call of the handle, which must be a synchronous float16 one (tf_calc_seq_rgb_f16,
+ *   tf_calc_seq_saliency_f16, or a *_wase call with out_f16), to leave its payload held: its N - 1 flows and the last one repeated
+ *   (N frames, what the file holds), and its echo if the call makes one -- copied on the device from what the call wrote there, never
+ *   uploaded; the call's host outputs are the same bytes as without.  The flag is spent by that call whether it succeeds or is
+ *   refused.  Armed, a float32 study call or a submitted one (tf_submit_*) is refused with TF_ERR_UNSUPPORTED and a message.  The
+ *   study held before goes once the armed call's arguments have passed; if the call fails after that, no study is held.
+ * tf_held_shape: out[TF_HELD_SHAPE_LEN] = N, H, W, n_echo (all 0: none held), a generation number that grows with every replacement
+ *   and release, then per slot (n_frames, C), both 0 for an empty slot.  No GPU work.
+ * tf_release_study frees the buffers (tf_destroy does too).
+ * tf_held_*: the call of the same name without `held_`, reading the held flow (float16) / echo and the mask in `slot`; H, W and the
+ *   flow's N are the held study's and the mask's C its slot's; every other argument and every output as the original's (the N of
+ *   tf_held_av_centroids and tf_held_first_region_areas: the mask's first N frames).  Same internal function, same kernels, same
+ *   bits; tf_radlong_hist / _select / _shape act on the planes a held projection leaves.  Like the originals they run on the handle's
+ *   stream and never on a lane's, are host-synchronous, check every argument before any GPU work and may be called while tf_submit_*
+ *   jobs of the handle are in flight.  TF_ERR_INVALID_ARG with a tf_last_error text that names the cause: no held study; a slot that is
+ *   empty or out of range; n_used outside [1, N]; a mask of fewer frames than asked for; no held echo, or one of fewer frames than the
+ *   planes (or of another size); acceleration or PWR with N < 2 or a spacing that is zero or not finite; a null pointer.  A refused
+ *   call leaves the held study and the resident planes as they were.
+ * tf_dbg_counter(h, "tail_upload_bytes"): bytes of flow, mask and echo that tf_av_centroids, tf_first_region_areas, the three
+ *   projections and tf_radlong_overlay have copied host -> device since the handle was made, plus what tf_hold_study and tf_hold_mask
+ *   uploaded; the tf_held_* calls add nothing. */
+#define TF_HELD_SLOTS 12
+#define TF_HELD_SHAPE_LEN (5 + 2 * TF_HELD_SLOTS)
+int tf_hold_study(tf_handle* h, const uint16_t* flow16, int N, int H, int W, const uint16_t* echo16, int n_echo);
+int tf_hold_mask(tf_handle* h, int slot, const uint8_t* mask, int n_frames, int C);
+int tf_hold_next(tf_handle* h, int on);
+int tf_held_shape(tf_handle* h, long long* out);
+int tf_release_study(tf_handle* h);
+int tf_held_av_centroids(tf_handle* h, int slot, int N, double* centroids_out, long long* area_out);
+int tf_held_first_region_areas(tf_handle* h, int slot, int N, long long* area_out);
+int tf_held_radlong_project_param(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, const double* centroids,
+                                  double* rad_out, double* long_out, double* minmax, long long* nonzero);
+int tf_held_polar_project_param(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, float* mag_out, float* ang_out,
+                                float* minmax, long long* nonzero, float* ang_mode);
+int tf_held_radlong_overlay(tf_handle* h, const double* lut_rad, const double* lut_long, uint8_t* out, double* info);
+
 /* ---- multi-GPU: the single exchange step of the path.  The reference's loop is sequential
  *      (calculate_optical_flow.py:584-597); here pairs shard over the GPUs of a node with no data-path traffic during the
  *      solve, and ONE RCCL all-gather of the (u,v) fields over xGMI assembles the result on every rank.  librccl is loaded
@@ -462,7 +508,8 @@ int tf_device_count(void);
 int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),
  * "coop_aborts" (calls repeated with the tiled form because such a launch gave up waiting), "coop_disabled"; "queue_jobs", "queue_units_done",
- * "queue_units_failed", "queue_units_skipped" (sub-batches dropped because an earlier one of their call had failed), "queue_outstanding", "queue_lanes"; -1 for an unknown name */
+ * "queue_units_failed", "queue_units_skipped" (sub-batches dropped because an earlier one of their call had failed), "queue_outstanding", "queue_lanes";
+ * "tail_upload_bytes" (see tf_hold_study); -1 for an unknown name */
 long long tf_dbg_counter(tf_handle* h, const char* name);
 /* DeepFlow hooks: one cv::VariationalRefinement::calcUV on dense float images (u, v updated in place); 3x3 Gaussian blur */
 int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v);

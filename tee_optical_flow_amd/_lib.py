@@ -13,6 +13,8 @@ TF_ERR_INVALID_ARG = 1
 TF_ERR_UNSUPPORTED = 2
 ECHO_F16, ECHO_U8 = 0, 1     # TF_ECHO_*
 COMM_ID_BYTES = 128          # TF_COMM_ID_BYTES
+HELD_SLOTS = 12              # TF_HELD_SLOTS
+HELD_SHAPE_LEN = 5 + 2 * HELD_SLOTS   # TF_HELD_SHAPE_LEN
 PARAM_KEYS = {
     "tau": 0, "lambda": 1, "theta": 2, "nscales": 3, "warps": 4, "epsilon": 5, "inner_iterations": 6,
     "outer_iterations": 7, "scale_step": 8, "gamma": 9, "median_filtering": 10, "use_initial_flow": 11,
@@ -27,6 +29,8 @@ EXPORTED_SYMBOLS = [
     "tf_dbg_pyramid", "tf_dbg_resize", "tf_dbg_warp", "tf_dbg_median", "tf_dbg_iterate", "tf_dbg_df_pyramid", "tf_dbg_df_up",
     "tf_calc_seq_rgb_f16", "tf_submit_seq_rgb_f16", "tf_calc_seq_saliency_f16", "tf_echo_frames", "tf_dbg_f16_round",
     "tf_calc_seq_rgb_wase", "tf_calc_seq_saliency_wase",
+    "tf_hold_study", "tf_hold_mask", "tf_hold_next", "tf_held_shape", "tf_release_study", "tf_held_av_centroids", "tf_held_first_region_areas",
+    "tf_held_radlong_project_param", "tf_held_polar_project_param", "tf_held_radlong_overlay",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -144,6 +148,16 @@ def load():
     L.tf_radlong_select.argtypes = [vp, i32, vp, vp]
     L.tf_radlong_overlay.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.tf_radlong_shape.argtypes = [vp, C.POINTER(i32 * 3)]
+    L.tf_hold_study.argtypes = [vp, vp, i32, i32, i32, vp, i32]
+    L.tf_hold_mask.argtypes = [vp, i32, vp, i32, i32]
+    L.tf_hold_next.argtypes = [vp, i32]
+    L.tf_held_shape.argtypes = [vp, C.POINTER(C.c_longlong * HELD_SHAPE_LEN)]
+    L.tf_release_study.argtypes = [vp]
+    L.tf_held_av_centroids.argtypes = [vp, i32, i32, vp, vp]
+    L.tf_held_first_region_areas.argtypes = [vp, i32, i32, vp]
+    L.tf_held_radlong_project_param.argtypes = [vp, i32, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.tf_held_polar_project_param.argtypes = [vp, i32, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.tf_held_radlong_overlay.argtypes = [vp, vp, vp, vp, vp]
     L.tf_get_iters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.tf_last_error.argtypes = [vp]
     L.tf_last_error.restype = C.c_char_p

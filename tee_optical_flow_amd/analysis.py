@@ -35,6 +35,10 @@ And the overlay video of the rad/long projections:
 With engine= the frames are rendered on the device from the planes tf_radlong_project_param left resident (tf_radlong_overlay), 6 bytes
 per pixel downloaded; without, a numpy twin that keeps index planes instead of RGBA float64 arrays.  Pinned by
 tests/golden/reference_overlay.npz (the frames the reference's own functions handed to their video writer).
+
+A study held on the device (DenseFlow.hold_study, or a study call with hold=True) is analysed through a HeldStudy: the `ds` of the
+functions above whose arrays are not on the host.  With it and its own engine they take the held calls (tf_held_*), which read the
+flow, the masks and the echo where they are; the results are the bits of the same functions on a FlowStudy of the same arrays.
 """
 import ctypes as C
 import logging
@@ -208,14 +212,23 @@ def av_centroids(mask_arr, nframes, filter=True, savgol_window=10, savgol_poly=4
     """calc_AV_centroid (analyze_optical_flow.py:213-244): per frame the centroid (row, col) of the largest 8-connected region of
     mask_arr[i, :, :, 0]; an empty frame copies the previous centroid ((H/2, W/2) on frame 0) with a warning; then, with `filter`,
     scipy.signal.savgol_filter over the frames (an ndarray), unless the list is shorter than the window (logged; the list is
-    returned unfiltered).  With `engine` (a DenseFlow) the labelling runs on the device (tf_av_centroids), with the same bits."""
+    returned unfiltered).  With `engine` (a DenseFlow) the labelling runs on the device (tf_av_centroids), with the same bits.
+    mask_arr may be a HeldStudy (its 'av' mask) or what its get_mask returned: the labelling then reads the held mask."""
     nframes = int(nframes)
-    shape = np.shape(mask_arr)
+    if isinstance(mask_arr, HeldStudy):
+        mask_arr = mask_arr.get_mask("av")
+    held = isinstance(mask_arr, HeldMask)
+    if held:
+        mask_arr.study.check(engine)
+    shape = mask_arr.shape if held else np.shape(mask_arr)
     if len(shape) != 4:
         raise ValueError(f"mask_arr must be [N,H,W,C], got shape {shape}")
     if nframes > shape[0]:
         raise IndexError(f"nframes {nframes} > {shape[0]} mask frames")
-    if nframes > 0 and engine is not None:
+    if held:
+        cent, area = engine.held_av_centroids(mask_arr.label, nframes) if nframes > 0 else (np.zeros((0, 2)), np.zeros(0, np.int64))
+        found = [((float(cent[i, 0]), float(cent[i, 1])), int(area[i])) if area[i] > 0 else None for i in range(nframes)]
+    elif nframes > 0 and engine is not None:
         masks = np.asarray(mask_arr)[:nframes]
         if masks.dtype not in (np.bool_, np.uint8) or masks.shape[3] not in (1, 2):
             masks = np.ascontiguousarray(masks[..., :1] != 0)
@@ -306,12 +319,21 @@ def calculate_3dhist_radlong(ds, param, nbins=1000, perc_lo=1, perc_hi=99, av_fi
     if "RVIO" not in ds.mode:
         log.error("only mode=RVIO_2class is supported for radlong functions, got mode=%s", ds.mode)
         return None
-    flow = getattr(ds, "flow", None)
-    if flow is None:
-        flow = ds.vel_array
+    if isinstance(ds, HeldStudy):
+        ds.check(engine)
     if centroids is None:
         centroids = av_centroids(ds.get_mask("av"), ds.nframes, filter=av_filter_flag, savgol_window=av_savgol_window,
                                  savgol_poly=av_savgol_poly, engine=engine)
+    if isinstance(ds, HeldStudy):
+        n = int(ds.nframes)
+        if len(centroids) != n:
+            raise ValueError(f"{len(centroids)} centroids for {n} frames")
+        mm, nz, _, _ = engine.held_radlong_project_param("rv", PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n,
+                                                         centroids)
+        return _radlong_stats_resident(engine, n, mm, nz, perc_lo, perc_hi, nbins)
+    flow = getattr(ds, "flow", None)
+    if flow is None:
+        flow = ds.vel_array
     return param_radlong_stats(flow, ds.get_mask("rv"), param, ds.frame_rate, ds.nframes, centroids, perc_lo=perc_lo, perc_hi=perc_hi,
                                nbins=nbins, engine=engine)
 
@@ -361,6 +383,80 @@ class FlowStudy:
             echo = f["echo"][()] if "echo" in f else None
             # (OpticalFlowDataset's filename: the base name less its last four characters, whatever the extension)
             return cls(flow, masks, frame_rate, nframes=a["nframes"] - 2, mode=a["mode"], echo=echo, filename=os.path.basename(path)[:-4])
+
+
+class HeldMask:
+    """What HeldStudy.get_mask returns: the name of a mask held on the device, for the functions that take a mask array."""
+
+    def __init__(self, study, label, shape):
+        self.study, self.label, self.shape = study, label, tuple(shape)
+
+
+class HeldStudy:
+    """The `ds` of the analysis functions for the study held on `engine` (a DenseFlow): what FlowStudy is for arrays on the host.
+    Made after the study and its masks are on the device -- DenseFlow.hold_study / hold_mask, or a study call with hold=True and
+    hold_mask -- or by from_study / from_hdf5, which upload the flow, the echo and every mask once.  nframes defaults to N - 2, as
+    FlowStudy's.  calculate_3dhist_radlong, calculate_3dhist, angle_mode_series, area_series, av_centroids, radlong_overlay and
+    visualize_radlong then read the held arrays when they are given this engine as `engine`; with engine=None or another engine
+    they raise, since the arrays are not on the host and nothing falls back to a host path.  The object belongs to the generation of
+    the held study it was made at: once the engine's held study has been replaced or released, using it raises."""
+
+    def __init__(self, engine, frame_rate, nframes=None, mode="RVIO_2class", filename="study"):
+        held = engine.held
+        if held is None:
+            raise ValueError("the engine holds no study (hold_study, or a study call with hold=True)")
+        self.engine = engine
+        self.generation = held.generation
+        self.shape = (held.N, held.H, held.W)
+        self.n_echo = held.n_echo
+        self.frame_rate = frame_rate
+        self.nframes = int(held.N - 2 if nframes is None else nframes)
+        self.mode = mode
+        self.filename = filename
+
+    def check(self, engine):
+        """raises unless `engine` is the one that holds this study, and still holds it"""
+        if engine is None:
+            raise ValueError("a HeldStudy's arrays are on the device: pass engine=<the DenseFlow that holds it> (there is no host path)")
+        if engine is not self.engine:
+            raise ValueError("this HeldStudy is held on another engine; its arrays are not on the host and not on this engine")
+        held = engine.held
+        if held is None or held.generation != self.generation:
+            raise RuntimeError("stale HeldStudy: the engine's held study has been replaced or released since it was made")
+        return held
+
+    @property
+    def accepted_labels(self):
+        held = self.engine.held
+        return list(held.masks) if held is not None and held.generation == self.generation else []
+
+    def get_mask(self, label):
+        held = self.check(self.engine)
+        if label not in held.masks:
+            log.error("%s not a valid key, choose from %s", label, list(held.masks))
+            return None
+        n, Cm = held.masks[label]
+        return HeldMask(self, label, (n, held.H, held.W, Cm))
+
+    @classmethod
+    def from_study(cls, engine, study):
+        """Upload a FlowStudy's flow (float16, as the study file holds it), its echo (float16, or None) and every mask (bool or uint8,
+        1 or 2 channels), once."""
+        flow = np.asarray(study.flow)
+        if flow.dtype != np.float16:
+            raise ValueError(f"a held study's flow is the study file's float16, got {flow.dtype}")
+        echo = study.get_echo()
+        if echo is not None and np.asarray(echo).dtype != np.float16:
+            raise ValueError(f"a held study's echo is the study file's float16, got {np.asarray(echo).dtype}")
+        engine.hold_study(flow, echo)
+        for label, mask in study.masks.items():
+            engine.hold_mask(label, mask)
+        return cls(engine, study.frame_rate, nframes=study.nframes, mode=study.mode, filename=study.filename)
+
+    @classmethod
+    def from_hdf5(cls, engine, path):
+        """A study file in the reference's layout, read as FlowStudy.from_hdf5 reads it and uploaded once.  Needs h5py."""
+        return cls.from_study(engine, FlowStudy.from_hdf5(path))
 
 
 # ---- the polar steps: cv2.cartToPolar, calculate_3dhist, the angle detector's per-frame mode --------------------------------
@@ -533,10 +629,15 @@ def calculate_3dhist(ds, param, label, nbins=1000, percentile=99, *, engine=None
     overflows float32) raises np.histogram's ValueError.  float32 statistics as numpy >= 2 computes them.
     `ds` is the reference's OpticalFlowDataset or a FlowStudy.  With `engine` (a DenseFlow) every per-pixel step runs on the
     device, with the same bits."""
+    if isinstance(ds, HeldStudy):
+        ds.check(engine)
     if not _valid(ds, param, label):
         return None
-    flow, mask = _study_arrays(ds, label)
     n = int(ds.nframes)
+    if isinstance(ds, HeldStudy):
+        mm, nz, _, _, _ = engine.held_polar_project_param(label, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+        return _hist_device(engine, n, mm, nz, nbins, percentile)
+    flow, mask = _study_arrays(ds, label)
     if engine is None:
         mag, ang = polar_field(flow, mask, param, ds.frame_rate, n)
         return _hist_host(mag, ang, n, nbins, percentile)
@@ -561,16 +662,21 @@ def angle_mode_series(ds, param, label, *, engine=None):
     Non-finite input: the host twin lets np.unique count NaN angles; the device path does not imitate that (its bins drop a NaN
     angle, and fminf / fmaxf in its cart_to_polar drop a NaN operand where numpy propagates it) and raises ValueError instead
     whenever a magnitude or an angle of the field is NaN or inf, so it never returns a mode where the twin's differs."""
+    if isinstance(ds, HeldStudy):
+        ds.check(engine)
     if param not in PARAMS:
         raise ValueError(f"param must be one of {PARAMS}, got {param!r}")
     if label not in list(ds.accepted_labels):
         raise ValueError(f"{label!r} not a valid key, choose from {list(ds.accepted_labels)}")
-    flow, mask = _study_arrays(ds, label)
     n = int(ds.nframes)
-    if engine is None:
-        _, ang = polar_field(flow, mask, param, ds.frame_rate, n)
-        return np.asarray([_mode_of_rounded(ang[i]) for i in range(n)], np.float32)
-    mm, _, mode, _, _ = engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+    if isinstance(ds, HeldStudy):
+        mm, _, mode, _, _ = engine.held_polar_project_param(label, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+    else:
+        flow, mask = _study_arrays(ds, label)
+        if engine is None:
+            _, ang = polar_field(flow, mask, param, ds.frame_rate, n)
+            return np.asarray([_mode_of_rounded(ang[i]) for i in range(n)], np.float32)
+        mm, _, mode, _, _ = engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
     if not np.isfinite(mm).all():
         raise ValueError(f"the field holds NaN or inf (magnitude range [{mm[0]}, {mm[1]}], angle range [{mm[2]}, {mm[3]}])")
     return mode
@@ -599,15 +705,20 @@ def area_series(ds, label, *, engine=None):
     OpticalFlowDataset, a FlowStudy or anything with get_mask(label) and nframes.  With `engine` (a DenseFlow) the labelling runs on
     the device (tf_first_region_areas), with the same values; a mask that is neither bool nor uint8, or has other than 1 or 2
     channels, runs on the host whatever the engine.  The smoother, the baseline and the peak search stay with the caller."""
+    if isinstance(ds, HeldStudy):
+        ds.check(engine)
     mask_arr = ds.get_mask(label)
     n = int(ds.nframes)
-    shape = np.shape(mask_arr)
+    held = isinstance(mask_arr, HeldMask)
+    shape = mask_arr.shape if held else np.shape(mask_arr)
     if len(shape) != 4:
         raise ValueError(f"the {label!r} mask must be [N,H,W,C], got shape {shape}")
     if n > shape[0]:
         raise IndexError(f"nframes {n} > {shape[0]} mask frames")
-    masks = np.asarray(mask_arr)[:max(n, 0)]
-    if engine is not None and masks.size > 0 and masks.dtype in (np.bool_, np.uint8) and masks.shape[3] in (1, 2):
+    masks = None if held else np.asarray(mask_arr)[:max(n, 0)]
+    if held:
+        found = [int(a) if a > 0 else None for a in engine.held_first_region_areas(label, n)] if n > 0 else []
+    elif engine is not None and masks.size > 0 and masks.dtype in (np.bool_, np.uint8) and masks.shape[3] in (1, 2):
         found = [int(a) if a > 0 else None for a in engine.first_region_areas(masks)]
     else:
         found = [_first_region_area(masks[i, :, :, 0]) for i in range(n)]
@@ -744,6 +855,9 @@ def radlong_overlay(ds, param, av_filter_flag=True, av_savgol_window=10, av_savg
     lut_rad = colormap_lut(colormap_rad) if isinstance(colormap_rad, str) else colormap_rad
     lut_long = colormap_lut(colormap_long) if isinstance(colormap_long, str) else colormap_long
     lut_rad, lut_long = _check_lut(lut_rad, "colormap_rad"), _check_lut(lut_long, "colormap_long")
+    if isinstance(ds, HeldStudy):
+        out, info = _held_overlay(ds, param, lut_rad, lut_long, engine, centroids, av_filter_flag, av_savgol_window, av_savgol_poly)
+        return (out, info) if return_info else out
     echo = ds.get_echo()
     if echo is None:
         raise ValueError("the study has no echo frames")
@@ -763,18 +877,40 @@ def radlong_overlay(ds, param, av_filter_flag=True, av_savgol_window=10, av_savg
         rad, lon = calculate_comp_magnitude(param_field(flow, mask, param, ds.frame_rate, n), centroids)
         out, info = overlay_host(rad, lon, echo, lut_rad, lut_long)
     else:
-        from .exceptions import OpticalFlowCalculationError
         mask = np.asarray(mask)
         if mask.dtype not in (np.bool_, np.uint8):
             raise ValueError(f"the device path takes a bool or uint8 mask (the study file's), got {mask.dtype}")
         engine.radlong_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n, centroids)
-        try:
-            out, info = engine.radlong_overlay(echo, lut_rad, lut_long)
-        except OpticalFlowCalculationError as e:
-            if getattr(e, "code", None) == _lib.TF_ERR_INVALID_ARG:    # the library's refusals of the data are the twin's ValueErrors
-                raise ValueError(str(e)) from e
-            raise
+        out, info = _device_overlay(lambda: engine.radlong_overlay(echo, lut_rad, lut_long))
     return (out, info) if return_info else out
+
+
+def _device_overlay(render):
+    """render(), the library's refusals of the data raised as the host twin's ValueErrors"""
+    from .exceptions import OpticalFlowCalculationError
+    try:
+        return render()
+    except OpticalFlowCalculationError as e:
+        if getattr(e, "code", None) == _lib.TF_ERR_INVALID_ARG:
+            raise ValueError(str(e)) from e
+        raise
+
+
+def _held_overlay(ds, param, lut_rad, lut_long, engine, centroids, av_filter_flag, av_savgol_window, av_savgol_poly):
+    """radlong_overlay's device branch for a HeldStudy: the held flow, 'rv' mask and echo"""
+    ds.check(engine)
+    n = int(ds.nframes)
+    if ds.n_echo < 1:
+        raise ValueError("the study has no echo frames")
+    if ds.n_echo < n:
+        raise ValueError(f"echo must be [>= {n},{ds.shape[1]},{ds.shape[2]}], the held one has {ds.n_echo} frames")
+    if centroids is None:
+        centroids = av_centroids(ds.get_mask("av"), n, filter=av_filter_flag, savgol_window=av_savgol_window, savgol_poly=av_savgol_poly,
+                                 engine=engine)
+    if len(centroids) != n:
+        raise ValueError(f"{len(centroids)} centroids for {n} frames")
+    engine.held_radlong_project_param("rv", PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n, centroids)
+    return _device_overlay(lambda: engine.held_radlong_overlay(lut_rad, lut_long))
 
 
 def visualize_radlong(ds, param, save_dir, fps=30, av_filter_flag=True, av_savgol_window=10, av_savgol_poly=4, colormap_rad="bwr",

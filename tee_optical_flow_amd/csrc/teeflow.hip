@@ -110,6 +110,7 @@ TF_API void tf_destroy(tf_handle* h)
     if (h->seg_stage) (void)hipHostFree(h->seg_stage);
     for (auto& b : h->pre) if (b.p) (void)hipFree(b.p);
     dev_free(h->an_rad); dev_free(h->an_lon);
+    h->held.release();
     delete h;
 }
 
@@ -227,6 +228,7 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "wase_study_kernel_us") v = (long long)(h->wase_kernel_ms * 1000.0);
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
+    else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {
         v = 0;
@@ -347,6 +349,8 @@ TF_API int tf_wait(tf_handle* h, int ticket, tf_stats* st)
 
 // the study tail: everything around the solver, from frame conditioning to WASE (host code; its kernels are in the kernel headers)
 #include "teeflow_tail.hip.h"
+// a study held on the device and the tail calls that read it there
+#include "teeflow_held.hip.h"
 
 TF_API int tf_get_iters(tf_handle* h, int* out, size_t capacity_ints, size_t* written)
 {

@@ -204,6 +204,24 @@ struct tf_handle : Engine {
     size_t an_cap = 0;           // doubles an_rad and an_lon each hold (grow_an_planes grows them, never shrinks)
     bool an_polar = false;       // the resident planes are tf_polar_project_param's magnitude / angle, not rad / long
     bool an_finite = false;      // ... and hold no NaN or inf (their min / max are finite)
+    // ---- the held study (teeflow_held.hip.h): a study file's payload in device buffers of its own, which no other call writes; lives
+    // until the next tf_hold_study / armed study call, tf_release_study or the handle's end ----
+    struct Held {
+        uint16_t* flow = nullptr; uint16_t* echo = nullptr;  // float16 [N][H][W][2]; float16 [n_echo][H][W] or null
+        int N = 0, H = 0, W = 0, n_echo = 0;                 // N == 0: no study is held
+        long long gen = 0;                                   // grows with every replacement and release
+        struct Mask { uint8_t* p = nullptr; int n_frames = 0, C = 0; } mask[TF_HELD_SLOTS];   // uint8 [n_frames][H][W][C]
+        // frees everything (the caller has drained the streams that read it); the generation moves on if a study was held
+        void release()
+        {
+            if (N) ++gen;
+            (void)hipFree(flow); (void)hipFree(echo);
+            for (auto& m : mask) { (void)hipFree(m.p); m = Mask(); }
+            flow = echo = nullptr; N = H = W = n_echo = 0;
+        }
+    } held;
+    bool hold_next = false;      // tf_hold_next: the next study call leaves its payload held
+    long long tail_upload_bytes = 0;   // bytes of flow, mask and echo the tail calls (and tf_hold_*) have copied host -> device
     // RCCL: one communicator rank per handle, its own stream, a small ring of completion events
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 0;
     hipStream_t comm_stream = nullptr; hipEvent_t comm_ev[8] = {}; hipEvent_t comm_ready = nullptr; unsigned comm_tickets = 0;

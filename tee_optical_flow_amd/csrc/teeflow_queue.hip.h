@@ -13,12 +13,14 @@ struct Call {
     int where = W_HOST;          // W_* bits
     bool f32 = false;            // the frames are float32 in [0,1] (CV_32F) instead of uint8
     bool out_f16 = false;        // the flows are written as float16 (the study file's type) instead of float32
+    void* keep = nullptr;        // device memory that gets a copy of every flow, in the output type, made on the device (a held study's flow)
     size_t frame_bytes() const { return (size_t)H * W * (f32 ? 4 : 1); }
     size_t flow_bytes() const { return (size_t)H * W * 2 * (out_f16 ? 2 : 4); }      // BYTES of one pair's flow
     Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
     {
         Call p = *this; const size_t off = (size_t)c0 * frame_bytes();
         p.in0 += off; if (in1) p.in1 += off; p.out = (uint8_t*)out + (size_t)c0 * flow_bytes(); p.n_pairs = nb;
+        if (keep) p.keep = (uint8_t*)keep + (size_t)c0 * flow_bytes();
         return p;
     }
 };
@@ -128,6 +130,7 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
                   : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16);
         if (rc) return rc;
         HIPC(h, hipEventRecord(h->ev[2], h->stream));
+        if (p.keep) HIPC(h, hipMemcpyAsync(p.keep, dfl, (size_t)nb * flb, hipMemcpyDeviceToDevice, h->stream));   // (byte copy: any offset)
         if (overlap) {
             HIPC(h, hipEventRecord(h->cev[kb & 1], h->stream));
             HIPC(h, hipStreamWaitEvent(h->copy_stream, h->cev[kb & 1], 0));

@@ -62,12 +62,33 @@ std::vector<u64> minmax_seed(size_t pairs)
     return init;
 }
 
+// Where a tail call finds its flow, its mask or its echo: host memory, which the call uploads into its scratch, or device memory
+// that already holds it (a held study's buffers, teeflow_held.hip.h), which the call's kernels read where it is.
+struct Src {
+    const void* host = nullptr; const void* dev = nullptr;
+    static Src on_host(const void* p) { return {p, nullptr}; }
+    static Src on_device(const void* p) { return {nullptr, p}; }
+};
+
+// bytes [off, off + bytes) of src, on the device: *out is the resident bytes themselves, or `scratch` behind their upload on the
+// handle's stream (counted in tail_upload_bytes)
+int src_to_device(tf_handle* h, const Src& src, size_t off, size_t bytes, void* scratch, const uint8_t** out)
+{
+    if (src.dev) { *out = (const uint8_t*)src.dev + off; return TF_OK; }
+    HIPC(h, hipMemcpyAsync(scratch, (const uint8_t*)src.host + off, bytes, hipMemcpyHostToDevice, h->stream));
+    h->tail_upload_bytes += (long long)bytes;
+    *out = (const uint8_t*)scratch;
+    return TF_OK;
+}
+
 // n pixels of uploaded RGB (device) -> their float16 `echo` values in the caller's host buffer, behind what is queued on the handle's
-// stream; the copy is done when the stream has been waited for.  decho: device scratch of at least n halves.
-int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* decho, uint16_t* echo16_out)
+// stream; the copy is done when the stream has been waited for.  decho: device scratch of at least n halves.  keep (device, or null):
+// gets the same halves by a copy on the device (a held study's echo).
+int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* decho, uint16_t* echo16_out, uint16_t* keep = nullptr)
 {
     hipLaunchKernelGGL(k_echo_f16, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, drgb, n, decho);
     HIPC(h, hipGetLastError());
+    if (keep) HIPC(h, hipMemcpyAsync(keep, decho, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, h->stream));
     HIPC(h, hipMemcpyAsync(echo16_out, decho, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
     return TF_OK;
 }
@@ -75,8 +96,9 @@ int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* 
 // rgb (host) -> conditioned gray frames in the handle's preprocessing buffer (valid until the handle's next preprocessing call)
 // (`own`: into that caller-owned buffer instead -- a submitted job's frames must outlive the handle's next preprocessing call)
 // echo16_out (host, [N][H][W] halves, or null): also the study's `echo`, from the same upload; complete on return
+// (echo_keep: device memory that gets the echo too, see echo_from_device_rgb)
 int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, const uint8_t** dgray_out, uint8_t* own = nullptr,
-                        uint16_t* echo16_out = nullptr)
+                        uint16_t* echo16_out = nullptr, uint16_t* echo_keep = nullptr)
 {
     const size_t npx = (size_t)H * W;
     HIPC(h, hipSetDevice(h->dev));
@@ -92,7 +114,7 @@ int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, c
     const int gx = (int)((npx + 255) / 256);
     hipLaunchKernelGGL(k_cond_minmax, dim3(gx < 512 ? gx : 512, N), dim3(256), 0, h->stream, drgb, npx, mm);
     hipLaunchKernelGGL(k_cond_norm, dim3(gx, N), dim3(256), 0, h->stream, drgb, npx, mm, dgray);
-    if (echo16_out) { const int rc = echo_from_device_rgb(h, drgb, (size_t)N * npx, decho, echo16_out); if (rc) return rc; }
+    if (echo16_out) { const int rc = echo_from_device_rgb(h, drgb, (size_t)N * npx, decho, echo16_out, echo_keep); if (rc) return rc; }
     HIPC(h, hipStreamSynchronize(h->stream));            // `init` leaves scope; the solve may run on other streams (lanes)
     *dgray_out = dgray;
     return TF_OK;
@@ -139,8 +161,9 @@ namespace {
 // (f32) float = map * (1/255), what computeSaliency() returns in opencv-contrib 4.x.  Frames go through in chunks so that the work
 // buffers (17 B per pixel) stay below ~2.3 GB whatever the study's length; the buffers are the handle's and only ever grow.
 // echo16_out (host, or null; channels == 3 only): also the study's float16 `echo`, from each chunk's upload; complete on return
+// (echo_keep: device memory that gets the echo too, see echo_from_device_rgb)
 int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, const uint8_t** dout,
-                       uint16_t* echo16_out = nullptr)
+                       uint16_t* echo16_out = nullptr, uint16_t* echo_keep = nullptr)
 {
     const size_t npx = (size_t)H * W, ipx = (size_t)(H + 1) * (W + 1);
     if (H > 65535 || N > 65535) return fail(h, TF_ERR_UNSUPPORTED, "saliency: at most 65535 rows and 65535 frames per call");
@@ -180,7 +203,10 @@ int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W,
                            f32 ? (float*)out + f0 * npx : nullptr);
         HIPC(h, hipGetLastError());
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
-        if (echo16_out) { const int rc = echo_from_device_rgb(h, src, px, decho, echo16_out + f0 * npx); if (rc) return rc; }
+        if (echo16_out) {
+            const int rc = echo_from_device_rgb(h, src, px, decho, echo16_out + f0 * npx, echo_keep ? echo_keep + f0 * npx : nullptr);
+            if (rc) return rc;
+        }
         HIPC(h, hipStreamSynchronize(h->stream));        // (one chunk holds 2^27 pixels: a study is one chunk; the event pair is read per chunk)
         float t = 0;
         HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
@@ -478,13 +504,14 @@ struct Projection {
     tf_handle* h;
     int n, H, W;
     const size_t npx = (size_t)H * W, tot = (size_t)n * npx;
-    uint8_t* dflow = nullptr; uint8_t* dmask = nullptr; uint8_t* meta = nullptr;
+    const uint8_t* dflow = nullptr; const uint8_t* dmask = nullptr; uint8_t* meta = nullptr;
     u64* mm = nullptr; unsigned long long* cnt = nullptr;
     std::vector<u64> seed = minmax_seed(2);
 
     // flow: N frames of float16 (f16) or float32 pairs, of which the field `param` of frames [0, n) reads the first nflow;
-    // mask: C bytes per pixel of frames [0, n), or C == 0 for a call without masks (tf_radlong_project)
-    int begin(const void* flow, int f16, int N, int param, const uint8_t* mask, int C, int meta_slot, size_t meta_bytes)
+    // mask: C bytes per pixel of frames [0, n), or C == 0 for a call without masks (tf_radlong_project).  Either is uploaded, or read
+    // where it is on the device (Src).
+    int begin(const Src& flow, int f16, int N, int param, const Src& mask, int C, int meta_slot, size_t meta_bytes)
     {
         const int nflow = param == RL_PARAM_VELOCITY ? n : (n + 1 < N ? n + 1 : N);   // the gradient of [0, n) reads one frame more
         const size_t flow_bytes = (size_t)nflow * npx * 2 * (f16 ? 2 : 4);
@@ -492,15 +519,15 @@ struct Projection {
         int rc = grow_an_planes(h, tot);
         if (rc) return rc;
         Pre pre(h);
-        dflow = pre.get<uint8_t>(tf_handle::PRE_AN_FLOW, flow_bytes);
-        if (C) dmask = pre.get<uint8_t>(tf_handle::PRE_AN_MASK, tot * C);
+        uint8_t* uflow = flow.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_AN_FLOW, flow_bytes);
+        uint8_t* umask = C && !mask.dev ? pre.get<uint8_t>(tf_handle::PRE_AN_MASK, tot * C) : nullptr;
         meta = pre.get<uint8_t>(meta_slot, meta_bytes);
         if (pre.rc) return pre.rc;
         mm = (u64*)meta;
         cnt = (unsigned long long*)(meta + 32);
         const hipStream_t s = h->stream;
-        HIPC(h, hipMemcpyAsync(dflow, flow, flow_bytes, hipMemcpyHostToDevice, s));
-        if (C) HIPC(h, hipMemcpyAsync(dmask, mask, tot * C, hipMemcpyHostToDevice, s));
+        if ((rc = src_to_device(h, flow, 0, flow_bytes, uflow, &dflow))) return rc;
+        if (C && (rc = src_to_device(h, mask, 0, tot * C, umask, &dmask))) return rc;
         HIPC(h, hipMemcpyAsync(mm, seed.data(), 32, hipMemcpyHostToDevice, s));
         HIPC(h, hipMemsetAsync(cnt, 0, meta_bytes - 32, s));
         return TF_OK;
@@ -593,7 +620,7 @@ TF_API int tf_radlong_select(tf_handle* h, int which, const long long* ranks, do
 namespace {
 // tf_av_centroids: frames go through in chunks so that the per-chunk scratch (26 B per pixel + the mask bytes: 10 B of them the
 // PRE_LB_* slots every labelling call uses, the areas in the sizes' place) stays within MASK_CHUNK_BYTES whatever the study's length
-int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* cent_out, long long* area_out)
+int av_centroids(tf_handle* h, const Src& masks, int N, int H, int W, int C, double* cent_out, long long* area_out)
 {
     using namespace cen;
     const size_t HW = (size_t)H * W;
@@ -601,7 +628,7 @@ int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C,
     const int nf = chunk_frames(HW * (26 + (size_t)C), N);     // frames of a chunk are grid.y
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
-    auto* dm = pre.get<uint8_t>(tf_handle::PRE_CT_MASK, (size_t)nf * HW * C);
+    auto* um = masks.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_CT_MASK, (size_t)nf * HW * C);
     auto* dpar = pre.get<uint32_t>(tf_handle::PRE_LB_PAR, (size_t)nf * HW);
     auto* dlr = pre.get<uint16_t>(tf_handle::PRE_LB_LR, (size_t)nf * HW);
     auto* darea = pre.get<uint32_t>(tf_handle::PRE_LB_AUX, (size_t)nf * HW);
@@ -615,8 +642,10 @@ int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C,
     HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
     for (int f0 = 0; f0 < N; f0 += nf) {
         const int n = std::min(nf, N - f0);
-        HIPC(h, hipMemcpyAsync(dm, masks + (size_t)f0 * HW * C, (size_t)n * HW * C, hipMemcpyHostToDevice, s));
-        int rc = label_planes<8, true>(h, ChannelZeroSet{dm, C, HW}, AreaAndSums{darea, dsum}, (size_t)n, H, W, dpar, dlr, derr);
+        const uint8_t* dm = nullptr;
+        int rc = src_to_device(h, masks, (size_t)f0 * HW * C, (size_t)n * HW * C, um, &dm);
+        if (rc) return rc;
+        rc = label_planes<8, true>(h, ChannelZeroSet{dm, C, HW}, AreaAndSums{darea, dsum}, (size_t)n, H, W, dpar, dlr, derr);
         if (rc) return rc;
         hipLaunchKernelGGL(k_cent_pick, dim3((unsigned)n), dim3(256), 0, s, dpar, darea, dsum, HW, dcent + 2 * (size_t)f0, dar + f0);
         HIPC(h, hipGetLastError());
@@ -629,7 +658,7 @@ int av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C,
 // tf_first_region_areas: frames go through in chunks so that the per-chunk scratch (6 B per pixel, the parents and tile-local roots of
 // the PRE_LB_* slots every labelling call uses, + the mask bytes) stays within MASK_CHUNK_BYTES (tests: the area_chunk_kib knob) whatever
 // the study's length
-int first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, long long* area_out)
+int first_region_areas(tf_handle* h, const Src& masks, int N, int H, int W, int C, long long* area_out)
 {
     using namespace fra;
     const size_t HW = (size_t)H * W;
@@ -638,7 +667,7 @@ int first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, 
     const int nf = chunk_frames(HW * (6 + (size_t)C), N, 65535, budget);   // frames of a chunk are grid.y
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
-    auto* dm = pre.get<uint8_t>(tf_handle::PRE_CT_MASK, (size_t)nf * HW * C);
+    auto* um = masks.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_CT_MASK, (size_t)nf * HW * C);
     auto* dpar = pre.get<uint32_t>(tf_handle::PRE_LB_PAR, (size_t)nf * HW);
     auto* dlr = pre.get<uint16_t>(tf_handle::PRE_LB_LR, (size_t)nf * HW);
     // [0, 64): error word, then areas [N] u64, then the chunk's seeds [nf] u32 and seed values [nf] u8
@@ -652,9 +681,11 @@ int first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, 
     HIPC(h, hipMemsetAsync(derr, 0, sizeof(unsigned), s));
     for (int f0 = 0; f0 < N; f0 += nf) {
         const int n = std::min(nf, N - f0);
-        HIPC(h, hipMemcpyAsync(dm, masks + (size_t)f0 * HW * C, (size_t)n * HW * C, hipMemcpyHostToDevice, s));
+        const uint8_t* dm = nullptr;
+        int rc = src_to_device(h, masks, (size_t)f0 * HW * C, (size_t)n * HW * C, um, &dm);
+        if (rc) return rc;
         hipLaunchKernelGGL(k_area_seed, dim3((unsigned)n), dim3(256), 0, s, dm, C, HW, dseed, dval, dar + f0);
-        int rc = label_planes<8, true>(h, SeedValueSet{dm, dseed, dval, C, HW}, SeedArea{dseed, dar + f0}, (size_t)n, H, W, dpar, dlr, derr);
+        rc = label_planes<8, true>(h, SeedValueSet{dm, dseed, dval, C, HW}, SeedArea{dseed, dar + f0}, (size_t)n, H, W, dpar, dlr, derr);
         if (rc) return rc;
         HIPC(h, hipGetLastError());
     }
@@ -678,7 +709,7 @@ void dispatch_param(int param, int f16, int grad_f64, F f)
 
 // the rad/long calls around their kernel: launch(p, dcent, grid) runs it on the uploads of p and the centroids [n_used][2] at dcent
 template <typename Launch>
-int radlong_project(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
+int radlong_project(tf_handle* h, const Src& flow, int f16, int N, int n_used, int H, int W, const Src& mask, int C, int param,
                     const double* centroids, double* rad_out, double* long_out, double* minmax, long long* nonzero, Launch launch)
 {
     Projection p{h, n_used, H, W};                              // meta: the head, then centroids [n_used][2]
@@ -694,7 +725,7 @@ int radlong_project(tf_handle* h, const void* flow, int f16, int N, int n_used, 
     return p.end(minmax, nonzero, false);
 }
 
-int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
+int radlong_project_param(tf_handle* h, const Src& flow, int f16, int N, int n_used, int H, int W, const Src& mask, int C, int param,
                           double spacing, int grad_f64, const double* centroids, double* rad_out, double* long_out, double* minmax,
                           long long* nonzero)
 {
@@ -708,7 +739,7 @@ int radlong_project_param(tf_handle* h, const void* flow, int f16, int N, int n_
         });
 }
 
-int polar_project_param(tf_handle* h, const void* flow, int f16, int N, int n_used, int H, int W, const uint8_t* mask, int C, int param,
+int polar_project_param(tf_handle* h, const Src& flow, int f16, int N, int n_used, int H, int W, const Src& mask, int C, int param,
                         double spacing, int grad_f64, float* mag_out, float* ang_out, float* minmax, long long* nonzero, float* ang_mode)
 {
     const bool arrays = mag_out || ang_out;
@@ -746,11 +777,10 @@ int polar_project_param(tf_handle* h, const void* flow, int f16, int N, int n_us
 // m2 needs every frame's; the echo upload and the output (eb + 6 B per pixel) go through in chunks of as many frames as fit in
 // MASK_CHUNK_BYTES.  A study of one chunk uploads its echo once; a longer one uploads it a second time for the compose pass.
 template <int KIND>
-int radlong_overlay(tf_handle* h, const void* echo_v, const double* lut_rad, const double* lut_long, uint8_t* out, double* info)
+int radlong_overlay(tf_handle* h, const Src& echo, const double* lut_rad, const double* lut_long, uint8_t* out, double* info)
 {
     using namespace ovl;
     using ET = typename Echo<KIND>::T;
-    const ET* echo = (const ET*)echo_v;
     const int n = h->anN, H = h->anH, W = h->anW;
     const size_t HW = (size_t)H * W, tot = (size_t)n * HW, eb = sizeof(ET);
     const int nf = chunk_frames(HW * (eb + 6), n, (size_t)n, h->overlay_chunk_kib > 0 ? (size_t)h->overlay_chunk_kib << 10 : MASK_CHUNK_BYTES);
@@ -759,7 +789,7 @@ int radlong_overlay(tf_handle* h, const void* echo_v, const double* lut_rad, con
     // meta: [0, 8) half bits, [8, 16) echo max bits + bad flag, [16, 80) used bitsets [2][8], [128, 128 + 12288) colour terms [2][256][3] f64
     Pre pre(h);
     auto* didx = pre.get<uint16_t>(tf_handle::PRE_OV_IDX, tot);
-    auto* decho = pre.get<ET>(tf_handle::PRE_OV_ECHO, (size_t)nf * HW);
+    auto* uecho = echo.dev ? nullptr : pre.get<ET>(tf_handle::PRE_OV_ECHO, (size_t)nf * HW);
     auto* dout = pre.get<unsigned>(tf_handle::PRE_OV_OUT, out_dwords);
     auto* meta = pre.get<uint8_t>(tf_handle::PRE_OV_META, 128 + 2 * 256 * 3 * sizeof(double));
     if (pre.rc) return pre.rc;
@@ -774,10 +804,12 @@ int radlong_overlay(tf_handle* h, const void* echo_v, const double* lut_rad, con
     hipLaunchKernelGGL(k_ov_half, grid(HW, 256), blk, 0, s, h->an_rad, HW, dhalf);
     hipLaunchKernelGGL(k_ov_index, grid(tot, 2048), blk, 0, s, h->an_rad, h->an_lon, tot, dhalf, didx, dused);
     HIPC(h, hipGetLastError());
+    const uint8_t* de = nullptr;                                      // the current chunk's echo
     for (int f0 = 0; f0 < n; f0 += nf) {
         const size_t c = (size_t)std::min(nf, n - f0) * HW;
-        HIPC(h, hipMemcpyAsync(decho, echo + (size_t)f0 * HW, c * eb, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ov_echo<KIND>, grid(c, 1024), blk, 0, s, decho, c, demax);
+        const int rc = src_to_device(h, echo, (size_t)f0 * HW * eb, c * eb, uecho, &de);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_ov_echo<KIND>, grid(c, 1024), blk, 0, s, (const ET*)de, c, demax);
         HIPC(h, hipGetLastError());
     }
     struct { u64 half; unsigned emax, bad; unsigned used[16]; } m;
@@ -803,8 +835,8 @@ int radlong_overlay(tf_handle* h, const void* echo_v, const double* lut_rad, con
     for (int f0 = 0; f0 < n; f0 += nf) {
         const int nc = std::min(nf, n - f0);
         const size_t c = (size_t)nc * HW, slots = 2 * c;                                // nc <= nf: the runs of `slots` fit out_dwords
-        if (n > nf) HIPC(h, hipMemcpyAsync(decho, echo + (size_t)f0 * HW, c * eb, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ov_compose<KIND>, dim3((unsigned)((slots + 1023) / 1024)), blk, 0, s, didx + (size_t)f0 * HW, decho, emax, dcol,
+        if (n > nf) { const int rc = src_to_device(h, echo, (size_t)f0 * HW * eb, c * eb, uecho, &de); if (rc) return rc; }
+        hipLaunchKernelGGL(k_ov_compose<KIND>, dim3((unsigned)((slots + 1023) / 1024)), blk, 0, s, didx + (size_t)f0 * HW, (const ET*)de, emax, dcol,
                            (size_t)nc * H, W, dout);
         HIPC(h, hipGetLastError());
         HIPC(h, hipMemcpyAsync(out + (size_t)f0 * HW * 6, dout, c * 6, hipMemcpyDeviceToHost, s));
@@ -832,20 +864,20 @@ static_assert(TF_PARAM_VELOCITY == RL_PARAM_VELOCITY && TF_PARAM_ACCELERATION ==
 TF_API int tf_av_centroids(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, double* centroids_out, long long* area_out)
 {
     if (!h || !masks || !centroids_out || !area_out || N < 1 || H < 1 || W < 1 || (C != 1 && C != 2)) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, av_centroids(h, masks, N, H, W, C, centroids_out, area_out));
+    return finish_host_call(h, av_centroids(h, Src::on_host(masks), N, H, W, C, centroids_out, area_out));
 }
 
 TF_API int tf_first_region_areas(tf_handle* h, const uint8_t* masks, int N, int H, int W, int C, long long* area_out)
 {
     if (!h || !masks || !area_out || N < 1 || H < 1 || W < 1 || (C != 1 && C != 2)) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, first_region_areas(h, masks, N, H, W, C, area_out));
+    return finish_host_call(h, first_region_areas(h, Src::on_host(masks), N, H, W, C, area_out));
 }
 
 TF_API int tf_radlong_project(tf_handle* h, const float* flow, const double* centroids, int N, int H, int W,
                               double* rad_out, double* long_out, double* minmax, long long* nonzero)
 {
     if (!h || !flow || !centroids || !minmax || !nonzero || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, radlong_project(h, flow, 0, N, N, H, W, nullptr, 0, RL_PARAM_VELOCITY, centroids, rad_out, long_out, minmax, nonzero,
+    return finish_host_call(h, radlong_project(h, Src::on_host(flow), 0, N, N, H, W, Src(), 0, RL_PARAM_VELOCITY, centroids, rad_out, long_out, minmax, nonzero,
         [&](const Projection& p, const double* dcent, dim3 g) {   // the flows as they are: no mask, no param field
             hipLaunchKernelGGL(k_radlong_project, g, dim3(256), 0, h->stream, (const float*)p.dflow, dcent, H, W, h->an_rad, h->an_lon, p.mm, p.cnt);
         }));
@@ -857,7 +889,7 @@ TF_API int tf_radlong_project_param(tf_handle* h, const void* flow, int flow_is_
 {
     if (!centroids) return TF_ERR_INVALID_ARG;
     if (int rc = check_project_param(h, flow, mask, minmax, nonzero, N, n_used, H, W, mask_C, param, spacing)) return rc;
-    return finish_host_call(h, radlong_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
+    return finish_host_call(h, radlong_project_param(h, Src::on_host(flow), flow_is_f16 ? 1 : 0, N, n_used, H, W, Src::on_host(mask), mask_C, param, spacing, grad_f64 ? 1 : 0,
                                                      centroids, rad_out, long_out, minmax, nonzero));
 }
 
@@ -868,16 +900,16 @@ TF_API int tf_polar_project_param(tf_handle* h, const void* flow, int flow_is_f1
     if (!ang_mode) return TF_ERR_INVALID_ARG;
     if (int rc = check_project_param(h, flow, mask, minmax, nonzero, N, n_used, H, W, mask_C, param, spacing)) return rc;
     if ((size_t)H * W > 0xFFFFFFFFu) return TF_ERR_UNSUPPORTED;                         // a frame's counts are 32-bit
-    return finish_host_call(h, polar_project_param(h, flow, flow_is_f16 ? 1 : 0, N, n_used, H, W, mask, mask_C, param, spacing, grad_f64 ? 1 : 0,
+    return finish_host_call(h, polar_project_param(h, Src::on_host(flow), flow_is_f16 ? 1 : 0, N, n_used, H, W, Src::on_host(mask), mask_C, param, spacing, grad_f64 ? 1 : 0,
                                                    mag_out, ang_out, minmax, nonzero, ang_mode));
 }
 
 static_assert(TF_ECHO_F16 == ovl::ECHO_F16 && TF_ECHO_U8 == ovl::ECHO_U8, "echo kinds of the header and the kernel differ");
 
-TF_API int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const double* lut_rad, const double* lut_long, uint8_t* out,
-                              double* info)
+namespace {
+// what tf_radlong_overlay checks of its tables and of the resident planes (h and the tables are not null)
+int check_overlay(tf_handle* h, const double* lut_rad, const double* lut_long)
 {
-    if (!h || !echo || !lut_rad || !lut_long || !out || !info || (echo_kind != TF_ECHO_F16 && echo_kind != TF_ECHO_U8)) return TF_ERR_INVALID_ARG;
     for (int j = 0; j < 256 * 3; ++j)
         if (!(lut_rad[j] >= 0.0 && std::isfinite(lut_rad[j]) && lut_long[j] >= 0.0 && std::isfinite(lut_long[j])))
             return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: a colormap entry is negative or not finite");
@@ -885,8 +917,17 @@ TF_API int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, con
     if (h->an_polar) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the handle's last projection was tf_polar_project_param, not a rad/long one");
     if (!h->an_finite) return fail(h, TF_ERR_INVALID_ARG, "tf_radlong_overlay: the rad/long planes hold NaN or inf");
     if ((size_t)h->anH * h->anW > 0x7fffffffu / 8) return fail(h, TF_ERR_UNSUPPORTED, "tf_radlong_overlay: at most 2^28 - 1 pixels per frame");
-    return finish_host_call(h, echo_kind == TF_ECHO_F16 ? radlong_overlay<ovl::ECHO_F16>(h, echo, lut_rad, lut_long, out, info)
-                                                        : radlong_overlay<ovl::ECHO_U8>(h, echo, lut_rad, lut_long, out, info));
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const double* lut_rad, const double* lut_long, uint8_t* out,
+                              double* info)
+{
+    if (!h || !echo || !lut_rad || !lut_long || !out || !info || (echo_kind != TF_ECHO_F16 && echo_kind != TF_ECHO_U8)) return TF_ERR_INVALID_ARG;
+    if (int rc = check_overlay(h, lut_rad, lut_long)) return rc;
+    return finish_host_call(h, echo_kind == TF_ECHO_F16 ? radlong_overlay<ovl::ECHO_F16>(h, Src::on_host(echo), lut_rad, lut_long, out, info)
+                                                        : radlong_overlay<ovl::ECHO_U8>(h, Src::on_host(echo), lut_rad, lut_long, out, info));
 }
 
 TF_API int tf_radlong_shape(tf_handle* h, int* shape)
@@ -1011,16 +1052,47 @@ struct Study {
 };
 
 // the solver's frames of study s on the device (`own`: a submitted job's buffer for them, see condition_to_device)
-int study_frames_to_device(tf_handle* h, const Study& s, uint8_t* own, const uint8_t** dfr)
+// (echo_keep: device memory that gets the study's echo too, or null)
+int study_frames_to_device(tf_handle* h, const Study& s, uint8_t* own, const uint8_t** dfr, uint16_t* echo_keep)
 {
-    return s.sees == FR_GRAY ? condition_to_device(h, s.frames, s.N, s.H, s.W, dfr, own, s.echo16_out)
-                             : saliency_to_device(h, s.frames, s.N, s.H, s.W, s.channels, s.sees == FR_SAL_F32, dfr, s.echo16_out);
+    return s.sees == FR_GRAY ? condition_to_device(h, s.frames, s.N, s.H, s.W, dfr, own, s.echo16_out, echo_keep)
+                             : saliency_to_device(h, s.frames, s.N, s.H, s.W, s.channels, s.sees == FR_SAL_F32, dfr, s.echo16_out, echo_keep);
+}
+
+// Buffers of the handle's own for a study of N flow frames, and n_echo echo frames, of H x W; whatever was held before goes.  The
+// caller fills them.  A failure leaves no study held.
+int held_alloc(tf_handle* h, int N, int H, int W, int n_echo)
+{
+    HIPC(h, hipSetDevice(h->dev));
+    HIPC(h, hipStreamSynchronize(h->stream));                 // (the tail calls are host-synchronous: nothing reads the old buffers)
+    tf_handle::Held& k = h->held;
+    k.release();
+    const size_t HW = (size_t)H * W;
+    hipError_t e = hipMalloc(&k.flow, (size_t)N * HW * 2 * sizeof(uint16_t));
+    if (e == hipSuccess && n_echo) e = hipMalloc(&k.echo, (size_t)n_echo * HW * sizeof(uint16_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        k.release();
+        return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding a study of %d x %d x %d: hipMalloc failed: %s", N, H, W, hipGetErrorString(e));
+    }
+    k.N = N; k.H = H; k.W = W; k.n_echo = n_echo;
+    ++k.gen;
+    return TF_OK;
+}
+
+// the held flow's last frame: flow N - 2 repeated, as the study file holds it (queued on the handle's stream)
+int held_repeat_last(tf_handle* h)
+{
+    const tf_handle::Held& k = h->held;
+    const size_t hw2 = (size_t)k.H * k.W * 2;
+    HIPC(h, hipMemcpyAsync(k.flow + (size_t)(k.N - 1) * hw2, k.flow + (size_t)(k.N - 2) * hw2, hw2 * sizeof(uint16_t), hipMemcpyDeviceToDevice, h->stream));
+    return TF_OK;
 }
 
 // The tail of a WASE study.  The flows never leave the device between the solve and the compensation: the solver has written them,
 // unscaled float32, into dflow (PRE_WS_FLOW); the reduction reads them there, and k_wase_out writes the compensated, scaled flows in
-// the call's output type into PRE_WS_OUT, which is copied to the caller's buffer.
-int wase_study_tail(tf_handle* h, const Study& s, const float* dflow)
+// the call's output type into PRE_WS_OUT, which is copied to the caller's buffer (and, `hold`, on the device into the held flow).
+int wase_study_tail(tf_handle* h, const Study& s, const float* dflow, bool hold)
 {
     const int P = s.N - 1, H = s.H, W = s.W;
     const size_t hw2 = (size_t)H * W * 2, elt = s.out_f16 ? sizeof(uint16_t) : sizeof(float);
@@ -1040,6 +1112,10 @@ int wase_study_tail(tf_handle* h, const Study& s, const float* dflow)
     HIPC(h, hipGetLastError());
     HIPC(h, hipEventRecord(h->ev[1], stream));
     HIPC(h, hipMemcpyAsync(s.flow_out, dout, (size_t)P * hw2 * elt, hipMemcpyDeviceToHost, stream));
+    if (hold) {                                               // (a held study is float16: study_call has refused the others)
+        HIPC(h, hipMemcpyAsync(h->held.flow, dout, (size_t)P * hw2 * elt, hipMemcpyDeviceToDevice, stream));
+        if (int rc2 = held_repeat_last(h)) return rc2;
+    }
     if (s.background_out) HIPC(h, hipMemcpyAsync(s.background_out, wbg, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, stream));
     HIPC(h, hipStreamSynchronize(stream));
     float t = 0;
@@ -1052,11 +1128,19 @@ int wase_study_tail(tf_handle* h, const Study& s, const float* dflow)
 // the WASE kernels' grid limits -- the order every route had, so each refusal is the one it was (the saliency pass checks its own
 // limits) -- then the frames to the device and the solve.  `submit` (a plain RGB study only): the frames are conditioned now, on the
 // handle's stream, into a buffer the job owns; the solve is queued and *ticket is what tf_wait takes.
+// Armed by tf_hold_next, a synchronous float16 call also leaves its payload held (teeflow_held.hip.h): N flow frames, the last one
+// repeated, and the echo if the call makes one, copied on the device from what the call wrote there.  The flag is spent by the call,
+// refused or not; the old held study goes once the call's arguments have passed, and a call that fails after that holds nothing.
 int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr, bool submit = false)
 {
     struct Owned { uint8_t* p = nullptr; ~Owned() { if (p) (void)hipFree(p); } } own;     // (freed after the failed call has been drained)
+    const bool hold = h && h->hold_next;
+    if (h) h->hold_next = false;
+    bool holding = false;                                    // held_alloc has run for this call
     auto run = [&]() -> int {
         if (!h) return TF_ERR_INVALID_ARG;
+        if (hold && submit) return fail(h, TF_ERR_UNSUPPORTED, "a submitted study cannot be held: tf_hold_next arms a synchronous float16 study call");
+        if (hold && !s.out_f16) return fail(h, TF_ERR_UNSUPPORTED, "only a float16 study call can leave its payload held");
         if (s.sees != FR_GRAY && s.channels != 1 && s.channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", s.channels);
         if (s.echo16_out && s.channels != 3) return fail(h, TF_ERR_INVALID_ARG, "the echo needs RGB frames (channels == 3), got %d", s.channels);
         if (s.wase && (!s.bkgd || s.n_frames < 1)) return fail(h, TF_ERR_INVALID_ARG, "a wase study needs a bkgd mask of at least 1 frame, got %d", s.n_frames);
@@ -1071,20 +1155,33 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
             HIPC(h, hipSetDevice(h->dev));
             HIPC(h, hipMalloc(&own.p, (size_t)s.N * s.H * s.W));
         }
-        rc = study_frames_to_device(h, s, own.p, &c.in0);
+        if (hold) {
+            if ((rc = held_alloc(h, s.N, s.H, s.W, s.echo16_out ? s.N : 0))) return rc;
+            holding = true;
+        }
+        rc = study_frames_to_device(h, s, own.p, &c.in0, hold ? h->held.echo : nullptr);
         if (rc) return rc;
         c.where = W_IN_DEV;
         // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
         if (submit) { uint8_t* p = own.p; own.p = nullptr; return submit_entry(h, c, ticket, p); }   // (the job's from here on)
-        if (!s.wase) return calc_entry(h, c, st);
+        if (!s.wase) {
+            if (hold) c.keep = h->held.flow;                  // each sub-batch's flows, copied on the device by the engine that solved them
+            rc = calc_entry(h, c, st);
+            if (rc || !hold) return rc;
+            if ((rc = held_repeat_last(h))) return rc;
+            HIPC(h, hipStreamSynchronize(h->stream));
+            return TF_OK;
+        }
         Pre pre(h);
         auto* dflow = pre.get<float>(tf_handle::PRE_WS_FLOW, (size_t)c.n_pairs * s.H * s.W * 2);
         if (pre.rc) return pre.rc;
         c.out = dflow; c.where = W_DEV; c.out_f16 = false;
         rc = calc_entry(h, c, st);                            // (returns with every lane's stream drained: the flows are there)
-        return rc ? rc : wase_study_tail(h, s, dflow);
+        return rc ? rc : wase_study_tail(h, s, dflow, hold);
     };
-    return finish_host_call(h, run());
+    const int rc = finish_host_call(h, run());
+    if (rc && holding) h->held.release();
+    return rc;
 }
 }  // namespace
 

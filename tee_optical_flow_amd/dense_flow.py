@@ -45,6 +45,38 @@ def _mask_stack(a, name):
 _Job = namedtuple("_Job", "out pad_n extra inputs", defaults=(0, (), ()))
 
 
+# What DenseFlow.held reports of the study held on the device: the flow's frames and size, the echo's frames (0: none), the generation
+# (it grows with every replacement and release) and {label: (n_frames, C)} of the held masks
+HeldShape = namedtuple("HeldShape", "N H W n_echo generation masks")
+
+
+class _HeldLabels:
+    """The mask labels of one held study and the library's mask slots they sit in, in the order they came; they belong to one
+    generation of the held study and are forgotten with it."""
+
+    def __init__(self, n_slots=_lib.HELD_SLOTS):
+        self.n_slots, self.generation, self.slots = n_slots, None, {}
+
+    def sync(self, generation):
+        """forget the labels of a study that has been replaced or released since"""
+        if generation != self.generation:
+            self.generation, self.slots = generation, {}
+
+    def slot_for(self, label):
+        """the slot a mask under `label` goes to: the label's own, or the next free one; one label more than there are slots raises"""
+        if label not in self.slots:
+            if len(self.slots) >= self.n_slots:
+                raise OpticalFlowCalculationError(f"a held study takes {self.n_slots} masks; no slot left for label {label!r} "
+                                                  f"(held: {list(self.slots)})")
+            self.slots[label] = len(self.slots)
+        return self.slots[label]
+
+    def slot_of(self, label):
+        if label not in self.slots:
+            raise OpticalFlowCalculationError(f"no mask is held under label {label!r} (held: {list(self.slots)})")
+        return self.slots[label]
+
+
 class _PinnedPool:
     """Result arrays backed by pinned host memory (tf_host_alloc): the library then copies flows out at PCIe speed while
     the next sub-batch is still being solved.  A buffer returns to the pool when the numpy array that owns it is garbage
@@ -102,6 +134,7 @@ class DenseFlow:
         self._L = _lib.load()
         self._pool = _PinnedPool(self._L)
         self._jobs = {}                                    # ticket -> what a submitted job reads and writes (kept alive until wait)
+        self._held_labels = _HeldLabels()                  # mask label -> slot of the study held on the device
         self.algo = algo
         if algo == "deepflow":
             p, create = _lib.TfDeepflowParams(), "tf_create_deepflow"
@@ -253,10 +286,14 @@ class DenseFlow:
             raise OpticalFlowCalculationError(f"nparr must be [N>={min_frames},H,W,3], got {nparr.shape}")
         return nparr
 
-    def _study(self, nparr, scale, pad_last, *, saliency=False, map_dtype="f32", f16=False, echo=False, bkgd_mask=None, submit=False):
+    def _study(self, nparr, scale, pad_last, *, saliency=False, map_dtype="f32", f16=False, echo=False, bkgd_mask=None, submit=False,
+               hold=False):
         """One study call: the frame check, the pinned outputs, the C function of the cell and its arguments.  -> what _collect makes of
-        the job, or (`submit`) the ticket wait() collects it by.  Only the float32 saliency form takes one-channel frames."""
+        the job, or (`submit`) the ticket wait() collects it by.  Only the float32 saliency form takes one-channel frames.  `hold` (the
+        float16 forms that are waited for): the call also leaves its payload held on the device (hold_study's doc)."""
         wase = bkgd_mask is not None
+        if hold and (submit or not f16):
+            raise OpticalFlowCalculationError("only a float16 study call that is waited for can leave its payload held")
         nparr = self._rgb_study(nparr, channels=(1, 3) if saliency and not (f16 or wase) else (3,))
         N, H, W, ch = nparr.shape
         if wase:
@@ -282,6 +319,8 @@ class DenseFlow:
         frames = (self._h, nparr.ctypes.data, N, H, W)
         if saliency:
             frames += (ch, int(map_f32)) if f16 or wase else (ch,)
+        if hold:
+            self.hold_next()
         _lib.check(getattr(self._L, name)(*frames, *own), self._h, name)
         job = _Job(out, N if pad_last else 0, ((e16,) if f16 else ()) + ((bg,) if wase else ()))
         if submit:
@@ -314,15 +353,17 @@ class DenseFlow:
         _lib.check(self._L.tf_echo_frames(self._h, nparr.ctypes.data, N, H, W, out.ctypes.data), self._h, "tf_echo_frames")
         return out
 
-    def calc_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True):
+    def calc_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True, hold=False):
         """calc_study with the flows rounded to float16 by the output kernel: RGB study uint8 [N,H,W,3] -> (flow16, echo16).  flow16 has
         the bits of calc_study(nparr, scale, pad_last).astype(np.float16) -- the study file's `flow` dataset with `scale` = pixel_spacing
-        * frame_rate and `pad_last` -- at half the download; echo16 is echo_frames(nparr), made from the same upload, or None."""
-        return self._study(nparr, scale, pad_last, f16=True, echo=echo)
+        * frame_rate and `pad_last` -- at half the download; echo16 is echo_frames(nparr), made from the same upload, or None.
+        `hold`: the payload (all N flow frames, the last one repeated whatever `pad_last`; the echo if made) also stays held on the
+        device, as after hold_study of the returned arrays, without being uploaded again; the returned arrays are the same."""
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, hold=hold)
 
-    def calc_study_saliency_payload(self, nparr, scale=1.0, pad_last=True, echo=True, map_dtype="f32"):
+    def calc_study_saliency_payload(self, nparr, scale=1.0, pad_last=True, echo=True, map_dtype="f32", hold=False):
         """calc_study_saliency with float16 flows, and the `echo` of the RGB frames: -> (flow16, echo16 | None), as calc_study_payload."""
-        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo)
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, hold=hold)
 
     def submit_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True):
         """calc_study_payload without waiting: -> ticket; `wait(ticket)` returns the (flow16, echo16 | None) pair.  The frames are
@@ -571,6 +612,144 @@ class DenseFlow:
                    self._h, "tf_radlong_overlay")
         return out, info
 
+    # ---- a study held on the device (include/teeflow.h, tf_hold_study): the file's payload uploaded once -- or left there by the solve
+    # that made it -- and the consumer's tail reading it there.  The held_* methods are av_centroids, first_region_areas,
+    # radlong_project_param, polar_project_param and radlong_overlay with a mask label in the place of the mask array and no flow or
+    # echo array; results are the same bits --------------------------------------------------------------------------------------------
+    def _held_shape(self):
+        shape = (C.c_longlong * _lib.HELD_SHAPE_LEN)()
+        _lib.check(self._L.tf_held_shape(self._h, C.byref(shape)), self._h, "tf_held_shape")
+        self._held_labels.sync(shape[4])
+        return shape
+
+    @property
+    def held(self):
+        """The study held on the device, a HeldShape(N, H, W, n_echo, generation, masks = {label: (n_frames, C)}), or None."""
+        s = self._held_shape()
+        if s[0] < 1:
+            return None
+        masks = {label: (int(s[5 + 2 * k]), int(s[6 + 2 * k])) for label, k in self._held_labels.slots.items()}
+        return HeldShape(int(s[0]), int(s[1]), int(s[2]), int(s[3]), int(s[4]), masks)
+
+    def hold_study(self, flow16, echo16=None):
+        """Put a study file's payload on the device, where the held_* calls read it: flow16 float16 [N,H,W,2] (the file's `flow`),
+        echo16 float16 [n,H,W] (its `echo`) or None.  Replaces the study held before and forgets its masks.  Device memory: 4 bytes per
+        flow pixel, 2 per echo pixel, until the next hold_study, a study call with hold=True, release_study or close."""
+        flow = np.ascontiguousarray(flow16)
+        if flow.dtype != np.float16 or flow.ndim != 4 or flow.shape[3] != 2 or min(flow.shape) < 1:
+            raise OpticalFlowCalculationError(f"flow16 must be float16 [N,H,W,2] with no empty side, got {flow.dtype} {flow.shape}")
+        N, H, W, _ = flow.shape
+        echo = None if echo16 is None else np.ascontiguousarray(echo16)
+        if echo is not None and (echo.dtype != np.float16 or echo.ndim != 3 or echo.shape[0] < 1 or echo.shape[1:] != (H, W)):
+            raise OpticalFlowCalculationError(f"echo16 must be float16 [n>=1,{H},{W}], got {echo.dtype} {echo.shape}")
+        _lib.check(self._L.tf_hold_study(self._h, flow.ctypes.data, N, H, W, None if echo is None else echo.ctypes.data,
+                                         0 if echo is None else echo.shape[0]), self._h, "tf_hold_study")
+        return self.held
+
+    def hold_mask(self, label, mask):
+        """Put a mask of the held study on the device under `label`: bool or uint8 [n,H,W,C], C = 1 or 2, H and W the held study's.  A
+        label held already is replaced; a held study takes 12 labels, a 13th raises."""
+        shape = self._held_shape()
+        if shape[0] < 1:
+            raise OpticalFlowCalculationError("no study is held (hold_study, or a study call with hold=True)")
+        m = _mask_stack(mask, "mask")
+        if m.shape[1:3] != (shape[1], shape[2]):
+            raise OpticalFlowCalculationError(f"mask must be [n,{shape[1]},{shape[2]},C] (the held study's frames), got {m.shape}")
+        known = label in self._held_labels.slots
+        slot = self._held_labels.slot_for(label)
+        try:
+            _lib.check(self._L.tf_hold_mask(self._h, slot, m.ctypes.data, m.shape[0], m.shape[3]), self._h, "tf_hold_mask")
+        except OpticalFlowCalculationError:
+            if not known:
+                del self._held_labels.slots[label]
+            raise
+
+    def hold_next(self, on=True):
+        """Arm (or disarm) the next study call to leave its payload held: what hold=True does for the calc_study_*_payload calls.  The
+        library spends the flag on the next study call, whatever becomes of it; armed, a submitted or a float32 study is refused."""
+        _lib.check(self._L.tf_hold_next(self._h, 1 if on else 0), self._h, "tf_hold_next")
+
+    def release_study(self):
+        """Free the held study's device memory; held_* calls are refused until a study is held again."""
+        _lib.check(self._L.tf_release_study(self._h), self._h, "tf_release_study")
+        self._held_shape()
+
+    def _held_slot(self, label):
+        self._held_shape()
+        return self._held_labels.slot_of(label)
+
+    def held_av_centroids(self, label, n):
+        """av_centroids of the first n frames of the held mask `label` -> (centroids float64 [n,2], areas int64 [n])."""
+        slot, n = self._held_slot(label), int(n)
+        cent = np.zeros((max(n, 0), 2), np.float64)
+        area = np.zeros(max(n, 0), np.int64)
+        _lib.check(self._L.tf_held_av_centroids(self._h, slot, n, cent.ctypes.data, area.ctypes.data), self._h, "tf_held_av_centroids")
+        return cent, area
+
+    def held_first_region_areas(self, label, n):
+        """first_region_areas of the first n frames of the held mask `label` -> int64 [n]."""
+        slot, n = self._held_slot(label), int(n)
+        area = np.zeros(max(n, 0), np.int64)
+        _lib.check(self._L.tf_held_first_region_areas(self._h, slot, n, area.ctypes.data), self._h, "tf_held_first_region_areas")
+        return area
+
+    def _held_project_sizes(self, n_used):
+        """(n_used, H, W) for the outputs of a held projection; an n_used the library will refuse sizes them as one frame"""
+        s = self._held_shape()
+        n_used = int(n_used)
+        return n_used, (n_used if 1 <= n_used <= s[0] else 1), int(s[1]), int(s[2])
+
+    def held_radlong_project_param(self, label, param, spacing, grad_f64, n_used, centroids, return_arrays=False):
+        """radlong_project_param of the held flow and the held mask `label`: -> (minmax, nonzero, rad, long) as there."""
+        slot = self._held_slot(label)
+        n_used, n, H, W = self._held_project_sizes(n_used)
+        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(-1, 2)
+        if n == n_used and cent.shape[0] != n_used:
+            raise OpticalFlowCalculationError(f"{cent.shape[0]} centroids for {n_used} frames")
+        rad = np.empty((n, H, W), np.float64) if return_arrays else None
+        lon = np.empty((n, H, W), np.float64) if return_arrays else None
+        mm = np.zeros(4, np.float64)
+        nz = np.zeros((n, 2), np.int64)
+        _lib.check(self._L.tf_held_radlong_project_param(self._h, n_used, slot, int(param), float(spacing), 1 if grad_f64 else 0,
+                                                         cent.ctypes.data, rad.ctypes.data if return_arrays else None,
+                                                         lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data),
+                   self._h, "tf_held_radlong_project_param")
+        return mm, nz, rad, lon
+
+    def held_polar_project_param(self, label, param, spacing, grad_f64, n_used, return_arrays=False):
+        """polar_project_param of the held flow and the held mask `label`: -> (minmax, nonzero, ang_mode, mag, ang) as there."""
+        slot = self._held_slot(label)
+        n_used, n, H, W = self._held_project_sizes(n_used)
+        mag = np.empty((n, H, W), np.float32) if return_arrays else None
+        ang = np.empty((n, H, W), np.float32) if return_arrays else None
+        mm = np.zeros(4, np.float32)
+        nz = np.zeros((n, 2), np.int64)
+        mode = np.zeros(n, np.float32)
+        _lib.check(self._L.tf_held_polar_project_param(self._h, n_used, slot, int(param), float(spacing), 1 if grad_f64 else 0,
+                                                       mag.ctypes.data if return_arrays else None, ang.ctypes.data if return_arrays else None,
+                                                       mm.ctypes.data, nz.ctypes.data, mode.ctypes.data),
+                   self._h, "tf_held_polar_project_param")
+        return mm, nz, mode, mag, ang
+
+    def held_radlong_overlay(self, lut_rad, lut_long):
+        """radlong_overlay with the held study's echo, of the planes the last (held_)radlong_project_param call left on the device:
+        -> (out uint8 [n,H,2W,3], info float64 [3])."""
+        luts = []
+        for name, lut in (("lut_rad", lut_rad), ("lut_long", lut_long)):
+            lut = np.ascontiguousarray(lut, dtype=np.float64)
+            if lut.shape != (256, 3):
+                raise OpticalFlowCalculationError(f"{name} must be [256,3], got shape {lut.shape}")
+            luts.append(lut)
+        shape = (C.c_int * 3)()
+        _lib.check(self._L.tf_radlong_shape(self._h, C.byref(shape)), self._h, "tf_radlong_shape")
+        n, H, W = shape
+        # (without rad/long planes the library refuses, and says why, before it writes out)
+        out = self._pool.empty((n, H, 2 * W, 3), np.uint8) if n >= 1 else np.empty(1, np.uint8)
+        info = np.zeros(3, np.float64)
+        _lib.check(self._L.tf_held_radlong_overlay(self._h, luts[0].ctypes.data, luts[1].ctypes.data, out.ctypes.data, info.ctypes.data),
+                   self._h, "tf_held_radlong_overlay")
+        return out, info
+
     def wase_compensate(self, flows, bkgd_mask, scale=1.0):
         """Reference :647-652, 659 for every flow of a study at once, on the device: returns (flows - background[p]) * scale
         and the float32 backgrounds.  flows float32 [P,H,W,2]; bkgd_mask bool [N,H,W,2] (mask_dict['bkgd'])."""
@@ -593,18 +772,20 @@ class DenseFlow:
         wase_compensate(calc_study(nparr), bkgd_mask, scale).  `pad_last` as in calc_study."""
         return self._study(nparr, scale, pad_last, bkgd_mask=bkgd_mask)
 
-    def calc_study_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True):
+    def calc_study_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, hold=False):
         """calc_study_wase with the flows rounded to float16 by the output kernel -> (flow16, echo16 | None, backgrounds): flow16 has
-        the bits of calc_study_wase(...)[0].astype(np.float16), echo16 is echo_frames(nparr) from the same upload."""
-        return self._study(nparr, scale, pad_last, f16=True, echo=echo, bkgd_mask=bkgd_mask)
+        the bits of calc_study_wase(...)[0].astype(np.float16), echo16 is echo_frames(nparr) from the same upload.  `hold` as in
+        calc_study_payload."""
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold)
 
     def calc_study_saliency_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False, map_dtype="f32"):
         """calc_study_wase with the saliency maps as the solver's frames (calc_study_saliency) -> (flows float32, backgrounds)."""
         return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, bkgd_mask=bkgd_mask)
 
-    def calc_study_saliency_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, map_dtype="f32"):
-        """calc_study_saliency_wase with float16 flows and the `echo` of the RGB frames -> (flow16, echo16 | None, backgrounds)."""
-        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, bkgd_mask=bkgd_mask)
+    def calc_study_saliency_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, map_dtype="f32", hold=False):
+        """calc_study_saliency_wase with float16 flows and the `echo` of the RGB frames -> (flow16, echo16 | None, backgrounds).  `hold`
+        as in calc_study_payload."""
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold)
 
     def calc_pairs(self, I0s, I1s):
         """B independent pairs: uint8 or float32 [B,H,W] x2 -> float32 [B,H,W,2] (float frames: DualTVL1 scales them by 255 like cv2, DeepFlow

@@ -5,8 +5,8 @@ Mirrors /root/reference/optical_flow/analysis.py:
   :166-212  calc_bidirectional_hist                                                          -> calc_bidirectional_hist
 Two implementations with identical results: a vectorised numpy one (host) and a device one that keeps the projections in
 HBM and gets the histogram and the exact order statistics np.percentile interpolates between from HIP kernels
-(include/teeflow.h: tf_radlong_project / _hist / _select).  Pinned by tests/golden/reference_analysis.npz, which the
-reference's own functions produced.
+(include/teeflow.h: tf_radlong_project / _hist / _select, as DenseFlow.radlong_project / radlong_hist / radlong_select: every device
+call here is a method of the engine).  Pinned by tests/golden/reference_analysis.npz, which the reference's own functions produced.
 
 The steps before the projection are here too, so that the consumer's call runs whole (/root/reference/optical_flow/analyze_optical_flow.py):
   :202-244  calc_AV_centroid (8-connected labelling, largest region, Savitzky-Golay)                  -> av_centroids
@@ -39,10 +39,11 @@ tests/golden/reference_overlay.npz (the frames the reference's own functions han
 A study held on the device (DenseFlow.hold_study, or a study call with hold=True) is analysed through a HeldStudy: the `ds` of the
 functions above whose arrays are not on the host.  With it and its own engine they take the held calls (tf_held_*), which read the
 flow, the masks and the echo where they are; the results are the bits of the same functions on a FlowStudy of the same arrays.
+Where the arrays are is _Tail's business alone; each function's device path is written once, over either kind.
 """
-import ctypes as C
 import logging
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -108,7 +109,8 @@ def calc_bidirectional_hist(mag_arr, nframes, perc_lo=1, perc_hi=99, nbins=1000)
 
 # ---- device ---------------------------------------------------------------------------------------------------------------
 def _lerp(a, b, t):
-    """numpy's percentile interpolation (numpy/lib/_function_base_impl.py::_lerp) for scalars."""
+    """numpy's percentile interpolation (numpy/lib/_function_base_impl.py::_lerp) for scalars, in their own dtype: a + (b - a) * t, or
+    b - (b - a) * (1 - t) for t >= 0.5"""
     d = b - a
     return b - d * (1 - t) if t >= 0.5 else a + d * t
 
@@ -138,18 +140,8 @@ def radlong_stats_device(engine, OF_arr, centroid_list, perc_lo=1, perc_hi=99, n
     """{'radial': (freq, edges[:-1], hi, lo), 'longitudinal': (...)} as calculate_3dhist_radlong (:289-327) returns after its
     centroid step, computed on the device behind `engine` (a DenseFlow).  return_arrays adds 'rad_arr' / 'long_arr'.  A NaN or
     inf in a plane raises ValueError, as np.histogram does for the host twin."""
-    L = engine._L
-    n = len(centroid_list)
-    OF = np.ascontiguousarray(np.asarray(OF_arr)[:n], dtype=np.float32)
-    N, H, W, _ = OF.shape
-    cent = np.ascontiguousarray(centroid_list, dtype=np.float64).reshape(N, 2)
-    rad = np.empty((N, H, W), np.float64) if return_arrays else None
-    lon = np.empty((N, H, W), np.float64) if return_arrays else None
-    mm = np.zeros(4, np.float64)
-    nz = np.zeros(2 * N, np.int64)
-    _lib.check(L.tf_radlong_project(engine._h, OF.ctypes.data, cent.ctypes.data, N, H, W, rad.ctypes.data if return_arrays else None,
-                                    lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data), engine._h, "tf_radlong_project")
-    return _radlong_stats_resident(engine, N, mm, nz, perc_lo, perc_hi, nbins, rad, lon)
+    mm, nz, rad, lon = engine.radlong_project(OF_arr, centroid_list, return_arrays=return_arrays)
+    return _radlong_stats_resident(engine, len(centroid_list), mm, nz, perc_lo, perc_hi, nbins, rad, lon)
 
 
 def _radlong_stats_resident(engine, N, mm, nz, perc_lo, perc_hi, nbins, rad=None, lon=None):
@@ -157,7 +149,6 @@ def _radlong_stats_resident(engine, N, mm, nz, perc_lo, perc_hi, nbins, rad=None
     order statistics np.percentile interpolates between, and the reference's per-frame loop.  mm / nz as the projection returned.
     Raises the ValueError np.histogram raises in the host twin (a non-finite range, or one too narrow for nbins bins) before the
     device histogram of that component runs."""
-    L = engine._L
     nz = np.asarray(nz).reshape(-1)
     out = {}
     for which, name in ((0, "radial"), (1, "longitudinal")):
@@ -169,16 +160,14 @@ def _radlong_stats_resident(engine, N, mm, nz, perc_lo, perc_hi, nbins, rad=None
         edges = np.linspace(first, last, nbins + 1)
         if cnt.any():
             _check_bins(edges, nbins)
-        freq = np.zeros((N, nbins), np.int64)
-        _lib.check(L.tf_radlong_hist(engine._h, which, edges.ctypes.data, nbins, freq.ctypes.data), engine._h, "tf_radlong_hist")
+        freq = engine.radlong_hist(which, edges, N)
         ranks = np.full((N, 4), -1, np.int64)
         frac = np.zeros((N, 2))
         for i in range(N):
             if cnt[i] > 0:
                 for j, q in enumerate((perc_hi, perc_lo)):
                     ranks[i, 2 * j], ranks[i, 2 * j + 1], frac[i, j] = percentile_rank64(cnt[i], q)
-        vals = np.zeros((N, 4), np.float64)
-        _lib.check(L.tf_radlong_select(engine._h, which, ranks.ctypes.data, vals.ctypes.data), engine._h, "tf_radlong_select")
+        vals = engine.radlong_select(which, ranks)
         per = [None if cnt[i] == 0 else (_lerp(vals[i, 0], vals[i, 1], frac[i, 0]), _lerp(vals[i, 2], vals[i, 3], frac[i, 1]), freq[i])
                for i in range(N)]
         f, e, hi, lo = _finish_hist(N, nbins, mn, mx, cnt, per)
@@ -217,22 +206,14 @@ def av_centroids(mask_arr, nframes, filter=True, savgol_window=10, savgol_poly=4
     nframes = int(nframes)
     if isinstance(mask_arr, HeldStudy):
         mask_arr = mask_arr.get_mask("av")
-    held = isinstance(mask_arr, HeldMask)
-    if held:
-        mask_arr.study.check(engine)
-    shape = mask_arr.shape if held else np.shape(mask_arr)
+    tail = _tail(mask_arr, engine)
+    shape = np.shape(mask_arr)                                # (a HeldMask has the shape of the mask it names)
     if len(shape) != 4:
         raise ValueError(f"mask_arr must be [N,H,W,C], got shape {shape}")
     if nframes > shape[0]:
         raise IndexError(f"nframes {nframes} > {shape[0]} mask frames")
-    if held:
-        cent, area = engine.held_av_centroids(mask_arr.label, nframes) if nframes > 0 else (np.zeros((0, 2)), np.zeros(0, np.int64))
-        found = [((float(cent[i, 0]), float(cent[i, 1])), int(area[i])) if area[i] > 0 else None for i in range(nframes)]
-    elif nframes > 0 and engine is not None:
-        masks = np.asarray(mask_arr)[:nframes]
-        if masks.dtype not in (np.bool_, np.uint8) or masks.shape[3] not in (1, 2):
-            masks = np.ascontiguousarray(masks[..., :1] != 0)
-        cent, area = engine.av_centroids(masks)
+    if tail is not None and nframes > 0:
+        cent, area = tail.centroids(mask_arr, nframes)
         found = [((float(cent[i, 0]), float(cent[i, 1])), int(area[i])) if area[i] > 0 else None for i in range(nframes)]
     else:
         found = [_largest_component(np.asarray(mask_arr[i, :, :, 0])) for i in range(nframes)]
@@ -287,8 +268,7 @@ def param_radlong_stats(flow, mask, param, frame_rate, n_used, centroid_list, pe
     if param not in PARAMS:
         raise ValueError(f"param must be one of {PARAMS}, got {param!r}")
     n_used = int(n_used)
-    if len(centroid_list) != n_used:
-        raise ValueError(f"{len(centroid_list)} centroids for {n_used} frames")
+    centroid_list = _frame_centroids(n_used, centroid_list)
     if engine is None:
         rad, lon = calculate_comp_magnitude(param_field(flow, mask, param, frame_rate, n_used), centroid_list)
         out = {}
@@ -298,12 +278,17 @@ def param_radlong_stats(flow, mask, param, frame_rate, n_used, centroid_list, pe
         if return_arrays:
             out["rad_arr"], out["long_arr"] = rad, lon
         return out
-    mask = np.asarray(mask)
-    if mask.dtype not in (np.bool_, np.uint8):
-        raise ValueError(f"the device path takes a bool or uint8 mask (the study file's), got {mask.dtype}")
-    mm, nz, rad, lon = engine.radlong_project_param(flow, mask, PARAMS.index(param), 1 / frame_rate, gradient_is_f64(frame_rate), n_used,
-                                                    centroid_list, return_arrays=return_arrays)
-    return _radlong_stats_resident(engine, n_used, mm, nz, perc_lo, perc_hi, nbins, rad, lon)
+    ds = SimpleNamespace(flow=flow, vel_array=flow, frame_rate=frame_rate, get_mask=lambda label: mask)      # what _Tail reads of a study
+    return _Tail(ds, engine).radlong_stats(param, n_used, centroid_list, perc_lo, perc_hi, nbins, return_arrays)
+
+
+def _frame_centroids(n, centroids, ds=None, engine=None, **av):
+    """`centroids`, or (None) the centroid step of `ds` with av_centroids' keywords `av`: one centroid per frame, or ValueError"""
+    if centroids is None:
+        centroids = av_centroids(ds.get_mask("av"), n, engine=engine, **av)
+    if len(centroids) != n:
+        raise ValueError(f"{len(centroids)} centroids for {n} frames")
+    return centroids
 
 
 def calculate_3dhist_radlong(ds, param, nbins=1000, perc_lo=1, perc_hi=99, av_filter_flag=True, av_savgol_window=10, av_savgol_poly=4, *,
@@ -319,23 +304,13 @@ def calculate_3dhist_radlong(ds, param, nbins=1000, perc_lo=1, perc_hi=99, av_fi
     if "RVIO" not in ds.mode:
         log.error("only mode=RVIO_2class is supported for radlong functions, got mode=%s", ds.mode)
         return None
-    if isinstance(ds, HeldStudy):
-        ds.check(engine)
-    if centroids is None:
-        centroids = av_centroids(ds.get_mask("av"), ds.nframes, filter=av_filter_flag, savgol_window=av_savgol_window,
-                                 savgol_poly=av_savgol_poly, engine=engine)
-    if isinstance(ds, HeldStudy):
-        n = int(ds.nframes)
-        if len(centroids) != n:
-            raise ValueError(f"{len(centroids)} centroids for {n} frames")
-        mm, nz, _, _ = engine.held_radlong_project_param("rv", PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n,
-                                                         centroids)
-        return _radlong_stats_resident(engine, n, mm, nz, perc_lo, perc_hi, nbins)
-    flow = getattr(ds, "flow", None)
-    if flow is None:
-        flow = ds.vel_array
-    return param_radlong_stats(flow, ds.get_mask("rv"), param, ds.frame_rate, ds.nframes, centroids, perc_lo=perc_lo, perc_hi=perc_hi,
-                               nbins=nbins, engine=engine)
+    tail = _tail(ds, engine)
+    n = int(ds.nframes)
+    centroids = _frame_centroids(n, centroids, ds, engine, filter=av_filter_flag, savgol_window=av_savgol_window, savgol_poly=av_savgol_poly)
+    if tail is None:
+        flow, mask = _study_arrays(ds, "rv")
+        return param_radlong_stats(flow, mask, param, ds.frame_rate, n, centroids, perc_lo=perc_lo, perc_hi=perc_hi, nbins=nbins)
+    return tail.radlong_stats(param, n, centroids, perc_lo, perc_hi, nbins)
 
 
 class FlowStudy:
@@ -459,6 +434,84 @@ class HeldStudy:
         return cls.from_study(engine, FlowStudy.from_hdf5(path))
 
 
+# ---- where a study's arrays are: the one place that knows ------------------------------------------------------------------------
+def _study_arrays(ds, label):
+    flow = getattr(ds, "flow", None)
+    if flow is None:
+        flow = ds.vel_array
+    return flow, ds.get_mask(label)
+
+
+class _Tail:
+    """The device steps of the analysis functions behind `engine` (a DenseFlow), each in two implementations: for a `ds` whose arrays are on
+    the host, which the engine uploads with every call, and (`held`) for the study the engine holds, through the held calls, which upload
+    nothing.  A mask argument is what get_mask returned; the results are the engine's."""
+
+    def __init__(self, ds, engine, held=False):
+        self.ds, self.engine, self.held = ds, engine, held
+
+    def _param(self, param):
+        return PARAMS.index(param), 1 / self.ds.frame_rate, gradient_is_f64(self.ds.frame_rate)
+
+    def centroids(self, mask, n):
+        if self.held:
+            return self.engine.held_av_centroids(mask.label, n)
+        masks = np.asarray(mask)[:n]
+        if masks.dtype not in (np.bool_, np.uint8) or masks.shape[3] not in (1, 2):
+            masks = np.ascontiguousarray(masks[..., :1] != 0)
+        return self.engine.av_centroids(masks)
+
+    def first_region_areas(self, mask, n):
+        """None for a host mask the engine does not take (another dtype or channel count, or empty): that one runs on the host"""
+        if self.held:
+            return self.engine.held_first_region_areas(mask.label, n)
+        masks = np.asarray(mask)[:n]
+        ok = masks.size > 0 and masks.dtype in (np.bool_, np.uint8) and masks.shape[3] in (1, 2)
+        return self.engine.first_region_areas(masks) if ok else None
+
+    def radlong_project(self, param, n, centroids, return_arrays=False):
+        if self.held:
+            return self.engine.held_radlong_project_param("rv", *self._param(param), n, centroids, return_arrays=return_arrays)
+        flow, mask = _study_arrays(self.ds, "rv")
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"the device path takes a bool or uint8 mask (the study file's), got {mask.dtype}")
+        return self.engine.radlong_project_param(flow, mask, *self._param(param), n, centroids, return_arrays=return_arrays)
+
+    def radlong_stats(self, param, n, centroids, perc_lo, perc_hi, nbins, return_arrays=False):
+        """the device part of param_radlong_stats and calculate_3dhist_radlong: the projection, then the statistics of its planes"""
+        mm, nz, rad, lon = self.radlong_project(param, n, centroids, return_arrays)
+        return _radlong_stats_resident(self.engine, n, mm, nz, perc_lo, perc_hi, nbins, rad, lon)
+
+    def polar_project(self, param, label, n):
+        if self.held:
+            return self.engine.held_polar_project_param(label, *self._param(param), n)
+        flow, mask = _study_arrays(self.ds, label)
+        return self.engine.polar_project_param(flow, mask, *self._param(param), n)
+
+    def echo(self, n):
+        """the echo the overlay takes, known to cover n frames: the host array, or None for the held one, which stays where it is"""
+        if not self.held:
+            return _host_echo(self.ds, n)
+        if self.ds.n_echo < 1:
+            raise ValueError("the study has no echo frames")
+        if self.ds.n_echo < n:
+            raise ValueError(f"echo must be [>= {n},{self.ds.shape[1]},{self.ds.shape[2]}], the held one has {self.ds.n_echo} frames")
+
+    def overlay(self, echo, lut_rad, lut_long):
+        return self.engine.held_radlong_overlay(lut_rad, lut_long) if self.held else self.engine.radlong_overlay(echo, lut_rad, lut_long)
+
+
+def _tail(src, engine):
+    """The device side of `src` (a ds, or the mask av_centroids was given): the held one for what is held on the device (it raises unless
+    `engine` holds it: there is no host path), the uploading one for host arrays and an engine, None for host arrays and no engine."""
+    if isinstance(src, (HeldStudy, HeldMask)):
+        ds = src.study if isinstance(src, HeldMask) else src
+        ds.check(engine)
+        return _Tail(ds, engine, held=True)
+    return None if engine is None else _Tail(src, engine)
+
+
 # ---- the polar steps: cv2.cartToPolar, calculate_3dhist, the angle detector's per-frame mode --------------------------------
 _DEG = 180 / np.pi                                            # 180 / CV_PI (CV_PI is the double nearest pi, as np.pi)
 _P1, _P3 = np.float32(0.9997878412794807) * np.float32(_DEG), np.float32(-0.3258083974640975) * np.float32(_DEG)
@@ -514,7 +567,7 @@ def polar_field(flow, mask, param, frame_rate, n_used):
 def percentile_index(n, q, dtype=np.float32):
     """(prev, next, gamma) of np.percentile(a, q) for n values of float dtype: method 'linear' as numpy >= 2 computes it, q / 100
     and the virtual index (n - 1) * q in the data's dtype (numpy 1.x computes both in float64).  The result is
-    _lerp32(sorted(a)[prev], sorted(a)[next], gamma)."""
+    _lerp(sorted(a)[prev], sorted(a)[next], gamma) in that dtype."""
     qq = np.asarray(np.true_divide(q, np.dtype(dtype).type(100)))
     vi = np.asarray((n - 1) * qq)
     prev = int(np.floor(vi))
@@ -525,23 +578,10 @@ def percentile_index(n, q, dtype=np.float32):
     return (prev % n, nxt % n, gamma[()])
 
 
-def _lerp32(a, b, t):
-    """numpy's _lerp in the data's dtype: a + (b - a) * t, or b - (b - a) * (1 - t) for t >= 0.5"""
-    d = b - a
-    return b - d * (1 - t) if t >= 0.5 else a + d * t
-
-
 def _polar_edges(mn, mx, nbins):
     """np.histogram's bin edges for range=(mn, mx) (np.float32 scalars, as np.min / np.max return them) of float32 data, from the
     numpy of this process (numpy 2 runs linspace in float32)"""
     return np.histogram_bin_edges(np.empty(0, np.float32), bins=nbins, range=(mn, mx))
-
-
-def _study_arrays(ds, label):
-    flow = getattr(ds, "flow", None)
-    if flow is None:
-        flow = ds.vel_array
-    return flow, ds.get_mask(label)
 
 
 def _valid(ds, param, label):
@@ -584,39 +624,33 @@ def _hist_host(mag, ang, n, nbins, percentile):
 def _hist_device(engine, n, mm, nz, nbins, percentile):
     """the same from the planes tf_polar_project_param left resident: tf_radlong_hist over numpy's float32 edges (passed as float64,
     exactly) and tf_radlong_select for the order statistics np.percentile interpolates between"""
-    L = engine._L
     mn, mx, amn, amx = (np.float32(v) for v in mm)
     cnt, acnt = nz[:, 0], nz[:, 1]
     if cnt[0] == 0:
         raise IndexError("list index out of range")           # the reference's perc_hi[-1] on an empty first frame
     _check_finite_range(mn, mx)                                # np.histogram's ValueError, before tf_radlong_hist runs
     mag_edges = _polar_edges(mn, mx, nbins)
-    e64 = mag_edges.astype(np.float64)                         # exact; held here while the library reads it
-    freq = np.zeros((n, nbins), np.int64)
     # k_radlong_hist estimates the bin in float64 and fixes it up by one against these edges, as numpy fixes up its float32
     # estimate: both estimates lie within one bin of the edge-defined one, so both end in the same bin
-    _lib.check(L.tf_radlong_hist(engine._h, 0, e64.ctypes.data, nbins, freq.ctypes.data), engine._h, "tf_radlong_hist")
+    freq = engine.radlong_hist(0, mag_edges.astype(np.float64), n)       # (exact)
     ranks = np.full((n, 4), -1, np.int64)
     gam = [None] * n
     for i in range(n):
         if cnt[i] > 0:
             ranks[i, 0], ranks[i, 1], gam[i] = percentile_index(int(cnt[i]), percentile)
-    vals = np.zeros((n, 4), np.float64)
-    _lib.check(L.tf_radlong_select(engine._h, 0, ranks.ctypes.data, vals.ctypes.data), engine._h, "tf_radlong_select")
+    vals = engine.radlong_select(0, ranks)
     mag_freq, hi = [], []
     for i in range(n):
         if cnt[i] == 0:
             hi.append(hi[-1]); mag_freq.append(mag_freq[-1])
         else:
-            hi.append(_lerp32(np.float32(vals[i, 0]), np.float32(vals[i, 1]), gam[i]))
+            hi.append(_lerp(np.float32(vals[i, 0]), np.float32(vals[i, 1]), gam[i]))
             mag_freq.append(freq[i] + 1)
     ang_edges = []
     if acnt.any():
         _check_finite_range(amn, amx)
         ang_edges = _polar_edges(amn, amx, nbins)
-        a64 = ang_edges.astype(np.float64)
-        afreq = np.zeros((n, nbins), np.int64)
-        _lib.check(L.tf_radlong_hist(engine._h, 1, a64.ctypes.data, nbins, afreq.ctypes.data), engine._h, "tf_radlong_hist")
+        afreq = engine.radlong_hist(1, ang_edges.astype(np.float64), n)
     ang_freq = [afreq[i] + 1 if acnt[i] > 0 else mag_freq[-1] for i in range(n)]
     return np.stack(mag_freq), np.stack(ang_freq), mag_edges[:-1], ang_edges[:-1], np.asarray(hi)
 
@@ -629,19 +663,15 @@ def calculate_3dhist(ds, param, label, nbins=1000, percentile=99, *, engine=None
     overflows float32) raises np.histogram's ValueError.  float32 statistics as numpy >= 2 computes them.
     `ds` is the reference's OpticalFlowDataset or a FlowStudy.  With `engine` (a DenseFlow) every per-pixel step runs on the
     device, with the same bits."""
-    if isinstance(ds, HeldStudy):
-        ds.check(engine)
+    tail = _tail(ds, engine)
     if not _valid(ds, param, label):
         return None
     n = int(ds.nframes)
-    if isinstance(ds, HeldStudy):
-        mm, nz, _, _, _ = engine.held_polar_project_param(label, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
-        return _hist_device(engine, n, mm, nz, nbins, percentile)
-    flow, mask = _study_arrays(ds, label)
-    if engine is None:
+    if tail is None:
+        flow, mask = _study_arrays(ds, label)
         mag, ang = polar_field(flow, mask, param, ds.frame_rate, n)
         return _hist_host(mag, ang, n, nbins, percentile)
-    mm, nz, _, _, _ = engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+    mm, nz, _, _, _ = tail.polar_project(param, label, n)
     return _hist_device(engine, n, mm, nz, nbins, percentile)
 
 
@@ -662,21 +692,17 @@ def angle_mode_series(ds, param, label, *, engine=None):
     Non-finite input: the host twin lets np.unique count NaN angles; the device path does not imitate that (its bins drop a NaN
     angle, and fminf / fmaxf in its cart_to_polar drop a NaN operand where numpy propagates it) and raises ValueError instead
     whenever a magnitude or an angle of the field is NaN or inf, so it never returns a mode where the twin's differs."""
-    if isinstance(ds, HeldStudy):
-        ds.check(engine)
+    tail = _tail(ds, engine)
     if param not in PARAMS:
         raise ValueError(f"param must be one of {PARAMS}, got {param!r}")
     if label not in list(ds.accepted_labels):
         raise ValueError(f"{label!r} not a valid key, choose from {list(ds.accepted_labels)}")
     n = int(ds.nframes)
-    if isinstance(ds, HeldStudy):
-        mm, _, mode, _, _ = engine.held_polar_project_param(label, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
-    else:
+    if tail is None:
         flow, mask = _study_arrays(ds, label)
-        if engine is None:
-            _, ang = polar_field(flow, mask, param, ds.frame_rate, n)
-            return np.asarray([_mode_of_rounded(ang[i]) for i in range(n)], np.float32)
-        mm, _, mode, _, _ = engine.polar_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n)
+        _, ang = polar_field(flow, mask, param, ds.frame_rate, n)
+        return np.asarray([_mode_of_rounded(ang[i]) for i in range(n)], np.float32)
+    mm, _, mode, _, _ = tail.polar_project(param, label, n)
     if not np.isfinite(mm).all():
         raise ValueError(f"the field holds NaN or inf (magnitude range [{mm[0]}, {mm[1]}], angle range [{mm[2]}, {mm[3]}])")
     return mode
@@ -705,22 +731,19 @@ def area_series(ds, label, *, engine=None):
     OpticalFlowDataset, a FlowStudy or anything with get_mask(label) and nframes.  With `engine` (a DenseFlow) the labelling runs on
     the device (tf_first_region_areas), with the same values; a mask that is neither bool nor uint8, or has other than 1 or 2
     channels, runs on the host whatever the engine.  The smoother, the baseline and the peak search stay with the caller."""
-    if isinstance(ds, HeldStudy):
-        ds.check(engine)
+    tail = _tail(ds, engine)
     mask_arr = ds.get_mask(label)
     n = int(ds.nframes)
-    held = isinstance(mask_arr, HeldMask)
-    shape = mask_arr.shape if held else np.shape(mask_arr)
+    shape = np.shape(mask_arr)                                # (a HeldMask has the shape of the mask it names)
     if len(shape) != 4:
         raise ValueError(f"the {label!r} mask must be [N,H,W,C], got shape {shape}")
     if n > shape[0]:
         raise IndexError(f"nframes {n} > {shape[0]} mask frames")
-    masks = None if held else np.asarray(mask_arr)[:max(n, 0)]
-    if held:
-        found = [int(a) if a > 0 else None for a in engine.held_first_region_areas(label, n)] if n > 0 else []
-    elif engine is not None and masks.size > 0 and masks.dtype in (np.bool_, np.uint8) and masks.shape[3] in (1, 2):
-        found = [int(a) if a > 0 else None for a in engine.first_region_areas(masks)]
+    areas = tail.first_region_areas(mask_arr, n) if tail is not None and n > 0 else None
+    if areas is not None:
+        found = [int(a) if a > 0 else None for a in areas]
     else:
+        masks = np.asarray(mask_arr) if n > 0 else ()
         found = [_first_region_area(masks[i, :, :, 0]) for i in range(n)]
     out = np.zeros(max(n, 0), np.int64)
     for i in range(n):
@@ -855,34 +878,32 @@ def radlong_overlay(ds, param, av_filter_flag=True, av_savgol_window=10, av_savg
     lut_rad = colormap_lut(colormap_rad) if isinstance(colormap_rad, str) else colormap_rad
     lut_long = colormap_lut(colormap_long) if isinstance(colormap_long, str) else colormap_long
     lut_rad, lut_long = _check_lut(lut_rad, "colormap_rad"), _check_lut(lut_long, "colormap_long")
-    if isinstance(ds, HeldStudy):
-        out, info = _held_overlay(ds, param, lut_rad, lut_long, engine, centroids, av_filter_flag, av_savgol_window, av_savgol_poly)
-        return (out, info) if return_info else out
+    tail = _tail(ds, engine)
+    n = int(ds.nframes)
+    echo = _host_echo(ds, n) if tail is None else tail.echo(n)
+    centroids = _frame_centroids(n, centroids, ds, engine, filter=av_filter_flag, savgol_window=av_savgol_window, savgol_poly=av_savgol_poly)
+    if tail is None:
+        flow, mask = _study_arrays(ds, "rv")
+        rad, lon = calculate_comp_magnitude(param_field(flow, mask, param, ds.frame_rate, n), centroids)
+        out, info = overlay_host(rad, lon, echo, lut_rad, lut_long)
+    else:
+        tail.radlong_project(param, n, centroids)
+        out, info = _device_overlay(lambda: tail.overlay(echo, lut_rad, lut_long))
+    return (out, info) if return_info else out
+
+
+def _host_echo(ds, n):
+    """the echo of a study on the host, float16 or uint8 and covering n frames of the flow's size, or ValueError"""
     echo = ds.get_echo()
     if echo is None:
         raise ValueError("the study has no echo frames")
     echo = np.asarray(echo)
     if echo.dtype not in (np.float16, np.uint8):
         raise ValueError(f"echo must be float16 (the study file's) or uint8, got {echo.dtype}")
-    n = int(ds.nframes)
-    flow, mask = _study_arrays(ds, "rv")
-    if echo.ndim != 3 or echo.shape[0] < n or echo.shape[1:] != np.shape(flow)[1:3]:
-        raise ValueError(f"echo must be [>= {n},{np.shape(flow)[1]},{np.shape(flow)[2]}], got shape {echo.shape}")
-    if centroids is None:
-        centroids = av_centroids(ds.get_mask("av"), n, filter=av_filter_flag, savgol_window=av_savgol_window, savgol_poly=av_savgol_poly,
-                                 engine=engine)
-    if len(centroids) != n:
-        raise ValueError(f"{len(centroids)} centroids for {n} frames")
-    if engine is None:
-        rad, lon = calculate_comp_magnitude(param_field(flow, mask, param, ds.frame_rate, n), centroids)
-        out, info = overlay_host(rad, lon, echo, lut_rad, lut_long)
-    else:
-        mask = np.asarray(mask)
-        if mask.dtype not in (np.bool_, np.uint8):
-            raise ValueError(f"the device path takes a bool or uint8 mask (the study file's), got {mask.dtype}")
-        engine.radlong_project_param(flow, mask, PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n, centroids)
-        out, info = _device_overlay(lambda: engine.radlong_overlay(echo, lut_rad, lut_long))
-    return (out, info) if return_info else out
+    H, W = np.shape(_study_arrays(ds, "rv")[0])[1:3]
+    if echo.ndim != 3 or echo.shape[0] < n or echo.shape[1:] != (H, W):
+        raise ValueError(f"echo must be [>= {n},{H},{W}], got shape {echo.shape}")
+    return echo
 
 
 def _device_overlay(render):
@@ -894,23 +915,6 @@ def _device_overlay(render):
         if getattr(e, "code", None) == _lib.TF_ERR_INVALID_ARG:
             raise ValueError(str(e)) from e
         raise
-
-
-def _held_overlay(ds, param, lut_rad, lut_long, engine, centroids, av_filter_flag, av_savgol_window, av_savgol_poly):
-    """radlong_overlay's device branch for a HeldStudy: the held flow, 'rv' mask and echo"""
-    ds.check(engine)
-    n = int(ds.nframes)
-    if ds.n_echo < 1:
-        raise ValueError("the study has no echo frames")
-    if ds.n_echo < n:
-        raise ValueError(f"echo must be [>= {n},{ds.shape[1]},{ds.shape[2]}], the held one has {ds.n_echo} frames")
-    if centroids is None:
-        centroids = av_centroids(ds.get_mask("av"), n, filter=av_filter_flag, savgol_window=av_savgol_window, savgol_poly=av_savgol_poly,
-                                 engine=engine)
-    if len(centroids) != n:
-        raise ValueError(f"{len(centroids)} centroids for {n} frames")
-    engine.held_radlong_project_param("rv", PARAMS.index(param), 1 / ds.frame_rate, gradient_is_f64(ds.frame_rate), n, centroids)
-    return _device_overlay(lambda: engine.held_radlong_overlay(lut_rad, lut_long))
 
 
 def visualize_radlong(ds, param, save_dir, fps=30, av_filter_flag=True, av_savgol_window=10, av_savgol_poly=4, colormap_rad="bwr",

@@ -494,16 +494,62 @@ class DenseFlow:
                    self._h, "tf_segmentor_classmap")
         return out
 
+    # ---- the consumer's tail.  Five calls have a host-pointer form and a held form (held_*, further down) over one private body; the two
+    # forms differ in the C function they name and in its leading arguments: host pointers and sizes, or the frame count and the slot ----
+    def _centroids(self, fn, lead, n):
+        cent = np.zeros((max(n, 0), 2), np.float64)
+        area = np.zeros(max(n, 0), np.int64)
+        _lib.check(getattr(self._L, fn)(self._h, *lead, cent.ctypes.data, area.ctypes.data), self._h, fn)
+        return cent, area
+
+    def _region_areas(self, fn, lead, n):
+        area = np.zeros(max(n, 0), np.int64)
+        _lib.check(getattr(self._L, fn)(self._h, *lead, area.ctypes.data), self._h, fn)
+        return area
+
+    def _project(self, fn, lead, shape, return_arrays, polar=False):
+        """The outputs of a projection of shape = (n, H, W) and its call: -> (minmax, nonzero, plane, plane) in float64, or (`polar`) in
+        float32 with the angle mode after nonzero; the planes are None without return_arrays."""
+        n, H, W = shape
+        dt = np.float32 if polar else np.float64
+        planes = [np.empty((n, H, W), dt) if return_arrays else None for _ in range(2)]
+        mm = np.zeros(4, dt)
+        nz = np.zeros((n, 2), np.int64)
+        mode = (np.zeros(n, np.float32),) if polar else ()
+        _lib.check(getattr(self._L, fn)(self._h, *lead, *(a.ctypes.data if return_arrays else None for a in planes), mm.ctypes.data,
+                                        nz.ctypes.data, *(a.ctypes.data for a in mode)), self._h, fn)
+        return (mm, nz, *mode, *planes)
+
+    def _overlay(self, fn, lut_rad, lut_long, echo=None):
+        """`echo` (the host form): checked against the planes' shape and passed first"""
+        luts = []
+        for name, lut in (("lut_rad", lut_rad), ("lut_long", lut_long)):
+            lut = np.ascontiguousarray(lut, dtype=np.float64)
+            if lut.shape != (256, 3):
+                raise OpticalFlowCalculationError(f"{name} must be [256,3], got shape {lut.shape}")
+            luts.append(lut)
+        # the library knows the planes' shape; an echo's must be checked against it before the library reads n * H * W values of it
+        shape = (C.c_int * 3)()
+        _lib.check(self._L.tf_radlong_shape(self._h, C.byref(shape)), self._h, "tf_radlong_shape")
+        n, H, W = shape
+        lead = ()
+        if echo is not None:
+            if n >= 1 and (echo.shape[0] < n or echo.shape[1:] != (H, W)):
+                raise OpticalFlowCalculationError(f"echo must be [>= {n},{H},{W}] (the projection's frames), got shape {echo.shape}")
+            echo = np.ascontiguousarray(echo[:max(n, 1)])
+            lead = (echo.ctypes.data, _lib.ECHO_F16 if echo.dtype == np.float16 else _lib.ECHO_U8)
+        # (without rad/long planes the library refuses, and says why, before it reads the echo or writes out)
+        out = self._pool.empty((n, H, 2 * W, 3), np.uint8) if n >= 1 else np.empty(1, np.uint8)
+        info = np.zeros(3, np.float64)
+        _lib.check(getattr(self._L, fn)(self._h, *lead, luts[0].ctypes.data, luts[1].ctypes.data, out.ctypes.data, info.ctypes.data), self._h, fn)
+        return out, info
+
     def av_centroids(self, masks):
         """calc_AV_centroid's per-frame step (analyze_optical_flow.py:202-232) on the device, exact: masks bool or uint8 [N,H,W,C]
         (C = 1 or 2; the set is channel 0 != 0, 8-connected) -> (centroids float64 [N,2] (row, col) of the largest component, areas
         int64 [N], 0 for an empty frame).  May be called while submitted studies are in flight on this engine."""
         m = _mask_stack(masks, "masks")
-        N, H, W, Cm = m.shape
-        cent = np.zeros((N, 2), np.float64)
-        area = np.zeros(N, np.int64)
-        _lib.check(self._L.tf_av_centroids(self._h, m.ctypes.data, N, H, W, Cm, cent.ctypes.data, area.ctypes.data), self._h, "tf_av_centroids")
-        return cent, area
+        return self._centroids("tf_av_centroids", (m.ctypes.data, *m.shape), m.shape[0])
 
     def first_region_areas(self, masks):
         """AreaDetector.detect's per-frame step (cardiac_cycle_detection.py:159-172: skimage label, regionprops, props[0].area) on the
@@ -511,14 +557,11 @@ class DenseFlow:
         8-connected region of equal value that holds the frame's first non-zero pixel in raster order, 0 for an empty frame.  May be
         called while submitted studies are in flight on this engine."""
         m = _mask_stack(masks, "masks")
-        N, H, W, Cm = m.shape
-        area = np.zeros(N, np.int64)
-        _lib.check(self._L.tf_first_region_areas(self._h, m.ctypes.data, N, H, W, Cm, area.ctypes.data), self._h, "tf_first_region_areas")
-        return area
+        return self._region_areas("tf_first_region_areas", (m.ctypes.data, *m.shape), m.shape[0])
 
-    @staticmethod
-    def _project_param_inputs(flow, mask, param, spacing, n_used):
-        """what both *_project_param calls check and lay out: -> (flow [N,H,W,2] float16 / float32, mask [n_used,H,W,C] uint8, n_used)"""
+    def _project_param(self, fn, flow, mask, param, spacing, grad_f64, n_used, centroids, return_arrays, polar=False):
+        """the host-pointer form of a param projection (the polar one takes no centroids): what both check and lay out -- flow [N,H,W,2]
+        float16 / float32, mask [n_used,H,W,C] uint8 -- and the call"""
         flow = np.asarray(flow)
         if flow.dtype not in (np.float16, np.float32):
             flow = flow.astype(np.float32)
@@ -538,26 +581,17 @@ class DenseFlow:
         m = _mask_stack(np.asarray(mask)[:n_used], "mask")
         if m.shape[:3] != (n_used, H, W):
             raise OpticalFlowCalculationError(f"mask must be [>= {n_used},{H},{W},C], got {np.shape(mask)}")
-        return flow, m, n_used
+        cent = () if centroids is None else (np.ascontiguousarray(centroids, dtype=np.float64).reshape(n_used, 2),)
+        lead = (flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W, m.ctypes.data, m.shape[3], int(param), float(spacing),
+                1 if grad_f64 else 0, *(c.ctypes.data for c in cent))
+        return self._project(fn, lead, (n_used, H, W), return_arrays, polar)
 
     def radlong_project_param(self, flow, mask, param, spacing, grad_f64, n_used, centroids, return_arrays=False):
         """tf_radlong_project_param: the rad/long projection of OpticalFlowDataset's param field (param 0 velocity, 1 acceleration,
         2 PWR) for frames [0, n_used), resident on the device for tf_radlong_hist / _select.  flow float16 or float32 [N,H,W,2],
         mask bool or uint8 [>= n_used,H,W,C].  Returns (minmax float64 [4], nonzero int64 [n_used, 2], rad, long): rad / long are
         float64 [n_used,H,W] with return_arrays, else None."""
-        flow, m, n_used = self._project_param_inputs(flow, mask, param, spacing, n_used)
-        N, H, W, _ = flow.shape
-        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(n_used, 2)
-        rad = np.empty((n_used, H, W), np.float64) if return_arrays else None
-        lon = np.empty((n_used, H, W), np.float64) if return_arrays else None
-        mm = np.zeros(4, np.float64)
-        nz = np.zeros((n_used, 2), np.int64)
-        _lib.check(self._L.tf_radlong_project_param(self._h, flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W,
-                                                    m.ctypes.data, m.shape[3], int(param), float(spacing), 1 if grad_f64 else 0,
-                                                    cent.ctypes.data, rad.ctypes.data if return_arrays else None,
-                                                    lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data),
-                   self._h, "tf_radlong_project_param")
-        return mm, nz, rad, lon
+        return self._project_param("tf_radlong_project_param", flow, mask, param, spacing, grad_f64, n_used, centroids, return_arrays)
 
     def polar_project_param(self, flow, mask, param, spacing, grad_f64, n_used, return_arrays=False):
         """tf_polar_project_param: cv2.cartToPolar (analysis.cart_to_polar's arithmetic) of OpticalFlowDataset's param field (param 0
@@ -566,19 +600,7 @@ class DenseFlow:
         (mag min, max, ang min, max), nonzero int64 [n_used, 2] (non-zero mag, ang per frame), ang_mode float32 [n_used] (the angle
         detector's per-frame mode, NaN if none), mag, ang): mag / ang are float32 [n_used,H,W] with return_arrays, else None.  May
         be called while submitted studies are in flight on this engine."""
-        flow, m, n_used = self._project_param_inputs(flow, mask, param, spacing, n_used)
-        N, H, W, _ = flow.shape
-        mag = np.empty((n_used, H, W), np.float32) if return_arrays else None
-        ang = np.empty((n_used, H, W), np.float32) if return_arrays else None
-        mm = np.zeros(4, np.float32)
-        nz = np.zeros((n_used, 2), np.int64)
-        mode = np.zeros(n_used, np.float32)
-        _lib.check(self._L.tf_polar_project_param(self._h, flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W,
-                                                  m.ctypes.data, m.shape[3], int(param), float(spacing), 1 if grad_f64 else 0,
-                                                  mag.ctypes.data if return_arrays else None, ang.ctypes.data if return_arrays else None,
-                                                  mm.ctypes.data, nz.ctypes.data, mode.ctypes.data),
-                   self._h, "tf_polar_project_param")
-        return mm, nz, mode, mag, ang
+        return self._project_param("tf_polar_project_param", flow, mask, param, spacing, grad_f64, n_used, None, return_arrays, polar=True)
 
     def radlong_overlay(self, echo, lut_rad, lut_long):
         """tf_radlong_overlay: the radial / longitudinal overlay frames of visualize_radlong (analyze_optical_flow.py:488-560) from the
@@ -591,26 +613,33 @@ class DenseFlow:
             raise OpticalFlowCalculationError(f"echo must be float16 or uint8, got {echo.dtype}")
         if echo.ndim != 3 or min(echo.shape) < 1:
             raise OpticalFlowCalculationError(f"echo must be [N,H,W] with no empty side, got shape {echo.shape}")
-        luts = []
-        for name, lut in (("lut_rad", lut_rad), ("lut_long", lut_long)):
-            lut = np.ascontiguousarray(lut, dtype=np.float64)
-            if lut.shape != (256, 3):
-                raise OpticalFlowCalculationError(f"{name} must be [256,3], got shape {lut.shape}")
-            luts.append(lut)
-        # the library knows the planes' shape; the echo's must be checked against it before the library reads n * H * W values of it
-        shape = (C.c_int * 3)()
-        _lib.check(self._L.tf_radlong_shape(self._h, C.byref(shape)), self._h, "tf_radlong_shape")
-        n, H, W = shape
-        if n >= 1 and (echo.shape[0] < n or echo.shape[1:] != (H, W)):
-            raise OpticalFlowCalculationError(f"echo must be [>= {n},{H},{W}] (the projection's frames), got shape {echo.shape}")
-        echo = np.ascontiguousarray(echo[:max(n, 1)])
-        # (without rad/long planes the library refuses, and says why, before it reads the echo or writes out)
-        out = self._pool.empty((n, H, 2 * W, 3), np.uint8) if n >= 1 else np.empty(1, np.uint8)
-        info = np.zeros(3, np.float64)
-        _lib.check(self._L.tf_radlong_overlay(self._h, echo.ctypes.data, _lib.ECHO_F16 if echo.dtype == np.float16 else _lib.ECHO_U8,
-                                              luts[0].ctypes.data, luts[1].ctypes.data, out.ctypes.data, info.ctypes.data),
-                   self._h, "tf_radlong_overlay")
-        return out, info
+        return self._overlay("tf_radlong_overlay", lut_rad, lut_long, echo)
+
+    # ---- the statistics of the planes a projection left resident: what analysis.py's glue calls ------------------------------------
+    def radlong_project(self, flow, centroids, return_arrays=False):
+        """tf_radlong_project: the rad/long projection of a field given whole, flow [>= n,H,W,2] (made float32) and n centroids (row, col),
+        resident on the device for radlong_hist / radlong_select.  Returns (minmax, nonzero, rad, long) as radlong_project_param."""
+        n = len(centroids)
+        flow = np.ascontiguousarray(np.asarray(flow)[:n], dtype=np.float32)
+        N, H, W, _ = flow.shape
+        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(N, 2)
+        return self._project("tf_radlong_project", (flow.ctypes.data, cent.ctypes.data, N, H, W), (N, H, W), return_arrays)
+
+    def radlong_hist(self, which, edges, n_frames):
+        """tf_radlong_hist: per frame, the histogram of the non-zero values of resident plane `which` (0 rad / mag, 1 long / ang) over
+        `edges` (passed as float64, exactly): int64 [n_frames, len(edges) - 1].  n_frames is the last projection's frame count."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        freq = np.zeros((int(n_frames), len(edges) - 1), np.int64)
+        _lib.check(self._L.tf_radlong_hist(self._h, int(which), edges.ctypes.data, len(edges) - 1, freq.ctypes.data), self._h, "tf_radlong_hist")
+        return freq
+
+    def radlong_select(self, which, ranks):
+        """tf_radlong_select: the order statistics of the non-zero values of resident plane `which`: ranks int64 [n, 4] per frame of the
+        last projection (a negative rank is skipped) -> float64 [n, 4], sorted(frame's non-zero values)[rank]."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+        vals = np.zeros(ranks.shape, np.float64)
+        _lib.check(self._L.tf_radlong_select(self._h, int(which), ranks.ctypes.data, vals.ctypes.data), self._h, "tf_radlong_select")
+        return vals
 
     # ---- a study held on the device (include/teeflow.h, tf_hold_study): the file's payload uploaded once -- or left there by the solve
     # that made it -- and the consumer's tail reading it there.  The held_* methods are av_centroids, first_region_areas,
@@ -681,74 +710,39 @@ class DenseFlow:
     def held_av_centroids(self, label, n):
         """av_centroids of the first n frames of the held mask `label` -> (centroids float64 [n,2], areas int64 [n])."""
         slot, n = self._held_slot(label), int(n)
-        cent = np.zeros((max(n, 0), 2), np.float64)
-        area = np.zeros(max(n, 0), np.int64)
-        _lib.check(self._L.tf_held_av_centroids(self._h, slot, n, cent.ctypes.data, area.ctypes.data), self._h, "tf_held_av_centroids")
-        return cent, area
+        return self._centroids("tf_held_av_centroids", (slot, n), n)
 
     def held_first_region_areas(self, label, n):
         """first_region_areas of the first n frames of the held mask `label` -> int64 [n]."""
         slot, n = self._held_slot(label), int(n)
-        area = np.zeros(max(n, 0), np.int64)
-        _lib.check(self._L.tf_held_first_region_areas(self._h, slot, n, area.ctypes.data), self._h, "tf_held_first_region_areas")
-        return area
+        return self._region_areas("tf_held_first_region_areas", (slot, n), n)
 
-    def _held_project_sizes(self, n_used):
-        """(n_used, H, W) for the outputs of a held projection; an n_used the library will refuse sizes them as one frame"""
+    def _held_project_param(self, fn, label, param, spacing, grad_f64, n_used, centroids, return_arrays, polar=False):
+        """the held form of a param projection (the polar one takes no centroids); an n_used the library will refuse sizes the outputs as
+        one frame, n = 1, so that the library's message is the one raised"""
+        slot, n_used = self._held_slot(label), int(n_used)
         s = self._held_shape()
-        n_used = int(n_used)
-        return n_used, (n_used if 1 <= n_used <= s[0] else 1), int(s[1]), int(s[2])
+        n = n_used if 1 <= n_used <= s[0] else 1
+        cent = ()
+        if centroids is not None:
+            cent = (np.ascontiguousarray(centroids, dtype=np.float64).reshape(-1, 2),)
+            if n == n_used and cent[0].shape[0] != n_used:
+                raise OpticalFlowCalculationError(f"{cent[0].shape[0]} centroids for {n_used} frames")
+        lead = (n_used, slot, int(param), float(spacing), 1 if grad_f64 else 0, *(c.ctypes.data for c in cent))
+        return self._project(fn, lead, (n, int(s[1]), int(s[2])), return_arrays, polar)
 
     def held_radlong_project_param(self, label, param, spacing, grad_f64, n_used, centroids, return_arrays=False):
         """radlong_project_param of the held flow and the held mask `label`: -> (minmax, nonzero, rad, long) as there."""
-        slot = self._held_slot(label)
-        n_used, n, H, W = self._held_project_sizes(n_used)
-        cent = np.ascontiguousarray(centroids, dtype=np.float64).reshape(-1, 2)
-        if n == n_used and cent.shape[0] != n_used:
-            raise OpticalFlowCalculationError(f"{cent.shape[0]} centroids for {n_used} frames")
-        rad = np.empty((n, H, W), np.float64) if return_arrays else None
-        lon = np.empty((n, H, W), np.float64) if return_arrays else None
-        mm = np.zeros(4, np.float64)
-        nz = np.zeros((n, 2), np.int64)
-        _lib.check(self._L.tf_held_radlong_project_param(self._h, n_used, slot, int(param), float(spacing), 1 if grad_f64 else 0,
-                                                         cent.ctypes.data, rad.ctypes.data if return_arrays else None,
-                                                         lon.ctypes.data if return_arrays else None, mm.ctypes.data, nz.ctypes.data),
-                   self._h, "tf_held_radlong_project_param")
-        return mm, nz, rad, lon
+        return self._held_project_param("tf_held_radlong_project_param", label, param, spacing, grad_f64, n_used, centroids, return_arrays)
 
     def held_polar_project_param(self, label, param, spacing, grad_f64, n_used, return_arrays=False):
         """polar_project_param of the held flow and the held mask `label`: -> (minmax, nonzero, ang_mode, mag, ang) as there."""
-        slot = self._held_slot(label)
-        n_used, n, H, W = self._held_project_sizes(n_used)
-        mag = np.empty((n, H, W), np.float32) if return_arrays else None
-        ang = np.empty((n, H, W), np.float32) if return_arrays else None
-        mm = np.zeros(4, np.float32)
-        nz = np.zeros((n, 2), np.int64)
-        mode = np.zeros(n, np.float32)
-        _lib.check(self._L.tf_held_polar_project_param(self._h, n_used, slot, int(param), float(spacing), 1 if grad_f64 else 0,
-                                                       mag.ctypes.data if return_arrays else None, ang.ctypes.data if return_arrays else None,
-                                                       mm.ctypes.data, nz.ctypes.data, mode.ctypes.data),
-                   self._h, "tf_held_polar_project_param")
-        return mm, nz, mode, mag, ang
+        return self._held_project_param("tf_held_polar_project_param", label, param, spacing, grad_f64, n_used, None, return_arrays, polar=True)
 
     def held_radlong_overlay(self, lut_rad, lut_long):
         """radlong_overlay with the held study's echo, of the planes the last (held_)radlong_project_param call left on the device:
         -> (out uint8 [n,H,2W,3], info float64 [3])."""
-        luts = []
-        for name, lut in (("lut_rad", lut_rad), ("lut_long", lut_long)):
-            lut = np.ascontiguousarray(lut, dtype=np.float64)
-            if lut.shape != (256, 3):
-                raise OpticalFlowCalculationError(f"{name} must be [256,3], got shape {lut.shape}")
-            luts.append(lut)
-        shape = (C.c_int * 3)()
-        _lib.check(self._L.tf_radlong_shape(self._h, C.byref(shape)), self._h, "tf_radlong_shape")
-        n, H, W = shape
-        # (without rad/long planes the library refuses, and says why, before it writes out)
-        out = self._pool.empty((n, H, 2 * W, 3), np.uint8) if n >= 1 else np.empty(1, np.uint8)
-        info = np.zeros(3, np.float64)
-        _lib.check(self._L.tf_held_radlong_overlay(self._h, luts[0].ctypes.data, luts[1].ctypes.data, out.ctypes.data, info.ctypes.data),
-                   self._h, "tf_held_radlong_overlay")
-        return out, info
+        return self._overlay("tf_held_radlong_overlay", lut_rad, lut_long)
 
     def wase_compensate(self, flows, bkgd_mask, scale=1.0):
         """Reference :647-652, 659 for every flow of a study at once, on the device: returns (flows - background[p]) * scale

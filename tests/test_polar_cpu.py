@@ -102,7 +102,7 @@ def test_float32_percentile_mirror_equals_numpy():
         srt = np.sort(a)
         for q in (99, 1, 50, 99.5):
             p, nx, g = A.percentile_index(n, q)
-            got = A._lerp32(srt[p], srt[nx], g)
+            got = A._lerp(srt[p], srt[nx], g)
             want = np.percentile(a, q)
             assert type(got) is type(want) and got.view(np.int32) == want.view(np.int32), (n, q, got, want)
 

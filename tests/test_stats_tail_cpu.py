@@ -1,7 +1,7 @@
 """The device statistics tail without a GPU (tests/stats_cases.py): every generated case has the property its name claims and is
 accepted by numpy; numpy models of the two device algorithms (the histogram rule of k_radlong_hist, the 4-pass radix select of
 k_radlong_sel_hist / k_radlong_sel_scan) equal np.histogram and np.sort on every case; the Python glue (percentile_rank64,
-percentile_index, _lerp, _lerp32) equals np.percentile; and the host twins run every case, so that the expected values of
+percentile_index, _lerp in both dtypes) equals np.percentile; and the host twins run every case, so that the expected values of
 tests/test_gpu_stats_tail.py exist."""
 import numpy as np
 import pytest
@@ -324,6 +324,6 @@ def test_percentile_glue_equals_numpy():
             want = np.percentile(a, q)
             assert type(got) is type(want) and got.view(np.uint64) == want.view(np.uint64), (n, q, got, want)
             p, nx, g = A.percentile_index(n, q)
-            got = A._lerp32(s32[p], s32[nx], g)
+            got = A._lerp(s32[p], s32[nx], g)
             want = np.percentile(a32, q)
             assert type(got) is type(want) and got.view(np.int32) == want.view(np.int32), (n, q, got, want)

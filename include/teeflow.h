@@ -177,7 +177,29 @@ int tf_calc_pairs_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s,
 int tf_calc_seq_device(tf_handle* h, const uint8_t* dframes, int N, int H, int W, float scale,
                        float* dflow_out, tf_stats* st);
 
-/* Asynchronous forms of the four calls above (the loop calculate_optical_flow.py:584-597 for SEVERAL studies / batches at a time):
+/* OF_model.calc(I0, I1, flow) with setUseInitialFlow(true) (TF_PARAM_USE_INITIAL_FLOW; DualTVL1, TF_VARIANT_CPU only): B independent
+ * pairs, each started from the caller's flow instead of zero.  An initial flow is float32 [H][W][2], x then y displacement in pixels
+ * per frame -- the solver's own unit, never multiplied by a call's `scale`.  OpenCV's rule, restated: level 0 of
+ * the flow pyramid is the caller's flow; level s is level s-1 resized by INTER_LINEAR with factors (scaleStep, scaleStep) -- the image
+ * pyramid's rule and sizes -- times (float)scaleStep, each level rounded to float32 before the next is taken from it; the coarsest level
+ * the solve uses starts from its level of that pyramid (with one level: from the flow itself); the duals start at zero and every finer
+ * level starts from the upsampled coarser result, as without the flag.  A zero initial flow gives the plain solve bit for bit;
+ * non-finite initial flows are undefined.
+ *   tf_calc_pairs_init: host pointers.  I0s, I1s: uint8 [B][H][W], or (frames_f32 != 0) float32 [B][H][W] in [0,1] as for
+ *     tf_calc_pairs_f32; init_flows: float32 [B][H][W][2]; flow_out: float32 [B][H][W][2].  init_flows == flow_out is allowed (cv2's in/out
+ *     `flow`); otherwise the two must not overlap.
+ *   tf_calc_pairs_init_device: device pointers, as tf_calc_pairs_device; d_init is unscaled, dflow_out = flow * scale; d_init ==
+ *     dflow_out is allowed.
+ * With the flag off both calls ignore the initial flows (they may be NULL), as cv2 does.  With the flag ON, every call that carries no
+ * initial flow -- tf_calc_pair(s), the _f32 and _device forms, every tf_calc_seq* and tf_submit_* call, the saliency, WASE, float16 and
+ * held-payload study calls, and these two with a NULL initial flow -- returns TF_ERR_UNSUPPORTED before any GPU work.
+ * TF_VARIANT_CUDA handles refuse the flag itself, and gamma != 0 stays refused. */
+int tf_calc_pairs_init(tf_handle* h, const void* I0s, const void* I1s, int frames_f32, const float* init_flows, int B, int H, int W,
+                       float* flow_out, tf_stats* st);
+int tf_calc_pairs_init_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s, const float* d_init, int B, int H, int W, float scale,
+                              float* dflow_out, tf_stats* st);
+
+/* Asynchronous forms of tf_calc_pairs_device, tf_calc_seq_device, tf_calc_pairs and tf_calc_seq (the loop calculate_optical_flow.py:584-597 for SEVERAL studies / batches at a time):
  * the job is queued on the handle's lanes and the call returns with a ticket; every buffer must stay valid and untouched until
  * tf_wait(h, ticket, st) has returned (ticket < 0: all jobs not yet waited for, oldest first; the first failure is returned).
  * Jobs start in submission order; sub-batches of consecutive jobs overlap.  tf_wait leaves the job's iteration counts where

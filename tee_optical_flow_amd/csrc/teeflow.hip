@@ -308,6 +308,24 @@ TF_API int tf_calc_seq_device(tf_handle* h, const uint8_t* dframes, int N, int H
     return calc_entry(h, {MODE_SEQ, dframes, nullptr, N - 1, H, W, scale, dflow_out, W_DEV}, st);
 }
 
+// ---- OF_model.calc(I0, I1, flow) under useInitialFlow: the pairs calls with an initial flow per pair.  The flag decides, as in cv2:
+// off, `init` is not looked at; on, check_call refuses a call without one ----------------------------------------------------------------
+static int calc_init_entry(tf_handle* h, Call c, const float* init, tf_stats* st)
+{
+    if (h && h->P.algo == TF_ALGO_TVL1 && h->P.use_initial_flow) c.init = init;
+    return calc_entry(h, c, st);
+}
+TF_API int tf_calc_pairs_init(tf_handle* h, const void* I0s, const void* I1s, int frames_f32, const float* init_flows, int B, int H, int W,
+                              float* flow_out, tf_stats* st)
+{
+    return calc_init_entry(h, {MODE_PAIRS, (const uint8_t*)I0s, (const uint8_t*)I1s, B, H, W, 1.0f, flow_out, W_HOST, frames_f32 != 0}, init_flows, st);
+}
+TF_API int tf_calc_pairs_init_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s, const float* d_init, int B, int H, int W, float scale,
+                                     float* dflow_out, tf_stats* st)
+{
+    return calc_init_entry(h, {MODE_PAIRS, dI0s, dI1s, B, H, W, scale, dflow_out, W_DEV}, d_init, st);
+}
+
 // ---- asynchronous forms: the job is queued on the handle's lanes and the call returns; tf_wait collects it ----------------------
 TF_API int tf_submit_pairs_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s, int B, int H, int W, float scale, float* dflow_out, int* ticket)
 {

@@ -154,6 +154,7 @@ struct Engine : TfKnobs {
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   // solve done [2], copy done [2]
     uint8_t* st_u8 = nullptr; size_t st_u8_bytes = 0;
     uint8_t* st_flow = nullptr; size_t st_flow_bytes = 0;     // flow staging, in the call's output element type
+    uint8_t* st_init = nullptr; size_t st_init_bytes = 0;     // a sub-batch's initial flows (useInitialFlow, host callers), float32
     hipEvent_t ev[4] = {};
     // profiling of tvl1_iter launches
     std::deque<ProfEv> prof_pool;                            // deque: records keep their address while the pool grows
@@ -279,8 +280,8 @@ template <class T> void dev_free(T*& p) { if (p) { (void)hipFree(p); p = nullptr
 // the staging is sized by the solver's capacity: a solver that re-allocates gives it back, and ensure_staging regrows it
 void release_staging(Engine* e)
 {
-    dev_free(e->st_u8); dev_free(e->st_flow);
-    e->st_u8_bytes = e->st_flow_bytes = 0;
+    dev_free(e->st_u8); dev_free(e->st_flow); dev_free(e->st_init);
+    e->st_u8_bytes = e->st_flow_bytes = e->st_init_bytes = 0;
 }
 
 int grow_staging(Engine* h, uint8_t*& p, size_t& have, size_t want)
@@ -290,10 +291,11 @@ int grow_staging(Engine* h, uint8_t*& p, size_t& have, size_t want)
     HIPC(h, hipMalloc(&p, want)); have = want;
     return TF_OK;
 }
-int ensure_staging(Engine* h, size_t u8_bytes, size_t flow_bytes)
+int ensure_staging(Engine* h, size_t u8_bytes, size_t flow_bytes, size_t init_bytes = 0)
 {
-    const int rc = grow_staging(h, h->st_u8, h->st_u8_bytes, u8_bytes);
-    return rc ? rc : grow_staging(h, h->st_flow, h->st_flow_bytes, flow_bytes);
+    int rc = grow_staging(h, h->st_u8, h->st_u8_bytes, u8_bytes);
+    if (!rc) rc = grow_staging(h, h->st_flow, h->st_flow_bytes, flow_bytes);
+    return rc ? rc : grow_staging(h, h->st_init, h->st_init_bytes, init_bytes);
 }
 
 // The device side of an engine whose P / DP the caller has set and checked: stream, events, the report ring, the bicubic table.  A

@@ -14,6 +14,8 @@ struct Call {
     bool f32 = false;            // the frames are float32 in [0,1] (CV_32F) instead of uint8
     bool out_f16 = false;        // the flows are written as float16 (the study file's type) instead of float32
     void* keep = nullptr;        // device memory that gets a copy of every flow, in the output type, made on the device (a held study's flow)
+    const float* init = nullptr; // useInitialFlow (MODE_PAIRS): every pair's initial flow, float32 [H][W][2] in pixels per frame, where the
+                                 // frames live (W_IN_DEV); may be `out` itself -- a pair's is read before its flow is written
     size_t frame_bytes() const { return (size_t)H * W * (f32 ? 4 : 1); }
     size_t flow_bytes() const { return (size_t)H * W * 2 * (out_f16 ? 2 : 4); }      // BYTES of one pair's flow
     Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
@@ -21,6 +23,7 @@ struct Call {
         Call p = *this; const size_t off = (size_t)c0 * frame_bytes();
         p.in0 += off; if (in1) p.in1 += off; p.out = (uint8_t*)out + (size_t)c0 * flow_bytes(); p.n_pairs = nb;
         if (keep) p.keep = (uint8_t*)keep + (size_t)c0 * flow_bytes();
+        if (init) p.init = init + (size_t)c0 * H * W * 2;
         return p;
     }
 };
@@ -64,7 +67,12 @@ int check_call(Engine* h, const Call& c)
     if (c.H < 1 || c.W < 1 || c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", c.n_pairs, c.H, c.W);
     if ((long long)c.H * c.W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
     if (c.out_f16 && (c.where & W_OUT_DEV)) return fail(h, TF_ERR_UNSUPPORTED, "float16 flows go to host destinations only");
-    return h->P.algo == TF_ALGO_DEEPFLOW ? df_validate(h, h->DP) : validate_params(h, h->P);
+    if (c.init && c.mode == MODE_SEQ) return fail(h, TF_ERR_UNSUPPORTED, "a sequence call takes no initial flow");
+    if (h->P.algo == TF_ALGO_DEEPFLOW) return df_validate(h, h->DP);
+    if (h->P.use_initial_flow && !c.init)
+        return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is set and this call carries no initial flow: only tf_calc_pairs_init and "
+                                            "tf_calc_pairs_init_device take one (or clear the flag)");
+    return validate_params(h, h->P);
 }
 
 // The engine solves call c, sub-batch after sub-batch.  DualTVL1 writes the executed iteration counts to `iters` (tf_get_iters order).
@@ -95,8 +103,10 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
     if (overlap && !h->cev[0])
         for (auto& e : h->cev) HIPC(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const size_t flow_half = (size_t)step * flb;              // BYTES per staging half
+    const size_t inb = (size_t)c.H * c.W * 2 * sizeof(float);   // BYTES per pair's initial flow (useInitialFlow)
     if (!in_dev || !out_dev) {
-        rc = ensure_staging(h, in_dev ? 0 : 2 * (size_t)step * fpx, out_dev ? 0 : (overlap ? 2 : 1) * flow_half);
+        rc = ensure_staging(h, in_dev ? 0 : 2 * (size_t)step * fpx, out_dev ? 0 : (overlap ? 2 : 1) * flow_half,
+                            c.init && !in_dev ? (size_t)step * inb : 0);
         if (rc) return rc;
     }
     int kb = 0;
@@ -122,12 +132,17 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
                 dfr = h->st_u8;
             }
         }
+        const float* dinit = p.init;                      // a device caller's is read where it is
+        if (p.init && !in_dev) {
+            HIPC(h, hipMemcpyAsync(h->st_init, p.init, (size_t)nb * inb, hipMemcpyHostToDevice, h->stream));
+            dinit = (const float*)h->st_init;
+        }
         dfl = out_dev ? p.out : (void*)(h->st_flow + (overlap ? (size_t)(kb & 1) * flow_half : 0));
         if (overlap && kb >= 2) HIPC(h, hipStreamWaitEvent(h->stream, h->cev[2 + (kb & 1)], 0));   // that half's last copy-out
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
         const Engine::Tally snap = h->tally;              // what a repeat of this sub-batch must not count twice (an aborted co-resident attempt is void)
         rc = deep ? df_solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16)
-                  : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16);
+                  : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16, dinit);
         if (rc) return rc;
         HIPC(h, hipEventRecord(h->ev[2], h->stream));
         if (p.keep) HIPC(h, hipMemcpyAsync(p.keep, dfl, (size_t)nb * flb, hipMemcpyDeviceToDevice, h->stream));   // (byte copy: any offset)
@@ -171,7 +186,7 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
             st->iter_pair_steps = (unsigned long long)h->tally.df_sor_px;     // pixels x pairs summed over the SOR launches
         } else {
             for (int b = 0; b < c.n_pairs; ++b)
-                account_bytes(h, iters + (size_t)b * per_pair, &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
+                account_bytes(h, iters + (size_t)b * per_pair, c.init != nullptr, &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
             st->iter_pair_steps = st->inner_iters_total;
         }
         double ims = 0, warp_ms = 0, median_ms = 0;

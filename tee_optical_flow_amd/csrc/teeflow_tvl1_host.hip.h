@@ -16,7 +16,8 @@ int validate_params(Engine* h, const tf_params& p)
     if (p.variant != TF_VARIANT_CPU && p.variant != TF_VARIANT_CUDA) return fail(h, TF_ERR_INVALID_ARG, "variant must be TF_VARIANT_CPU or TF_VARIANT_CUDA, got %d", p.variant);
     if (p.variant == TF_VARIANT_CUDA && (p.inner_iterations * p.outer_iterations) % 2 != 0)
         return fail(h, TF_ERR_UNSUPPORTED, "TF_VARIANT_CUDA needs an even iteration count (inner*outer), got %d", p.inner_iterations * p.outer_iterations);
-    if (p.use_initial_flow) return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is not implemented");
+    if (p.use_initial_flow && p.variant == TF_VARIANT_CUDA)
+        return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is not implemented for TF_VARIANT_CUDA (nothing checks that form bit for bit)");
     if (!(p.scale_step > 0.0 && p.scale_step < 1.0)) return fail(h, TF_ERR_INVALID_ARG, "scaleStep must be in (0,1), got %g", p.scale_step);
     // cv::resize silently runs INTER_AREA instead of INTER_LINEAR when both scale factors are exactly 2 (imgproc/resize.cpp, "in
     // case of scale_x && scale_y is equal to 2"): same value mathematically, not the same float as the bilinear form k_pyr_down
@@ -272,7 +273,9 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
 }
 
 // Solve B pairs whose frames are in device memory: frames[F][H][W] (uint8, or float32 in [0,1] when f32), pair b = (off0+b, off1+b).
-int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16)
+// dinit (useInitialFlow): the pairs' initial flows in device memory, float32 [B][H][W][2] in pixels per frame, or null = start from zero.
+int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16,
+                   const float* dinit = nullptr)
 {
     const tf_params& P = h->P;
     hipStream_t s = h->stream;
@@ -289,8 +292,19 @@ int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, in
             hipLaunchKernelGGL(k_grad, grid64x4(h->tv.lv[l], F), dim3(256), 0, s, h->tv.pyr[l], h->tv.gxl[l], h->tv.gyl[l], h->tv.lv[l]);
     const int L = h->tv.nlev - 1;
     hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.ctl, B, 0);
+    // useInitialFlow: u?s[0] = split(flow), u?s[l] = resize(u?s[l-1], Size(), scaleStep, scaleStep) * scaleStep, every level rounded to
+    // float32 before the next is taken from it.  Level l lives in u buffer (L - l) & 1, so the coarsest one ends in buffer 0, which the
+    // first stage reads (ubase = 0); the levels in between are scratch.  All but the last step run BEFORE the two memsets: a level in
+    // between that sits in buffer 0 would otherwise write into the row padding they clear.
+    const auto seed_step = [&](int l) {         // level l of the chain, from the caller's flow (l == 0) or from level l - 1
+        if (l == 0) hipLaunchKernelGGL(k_init_split, grid64x4(g0, B), dim3(256), 0, s, dinit, h->tv.sb, L & 1, g0);
+        else hipLaunchKernelGGL(k_init_down, grid64x4(h->tv.lv[l], B), dim3(256), 0, s, h->tv.sb, (L - l + 1) & 1, h->tv.lv[l - 1], h->tv.lv[l],
+                                1.0 / P.scale_step, (float)P.scale_step);
+    };
+    if (dinit) for (int l = 0; l < L; ++l) seed_step(l);
     HIPC(h, hipMemset2DAsync(h->tv.sb.u1[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
     HIPC(h, hipMemset2DAsync(h->tv.sb.u2[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
+    if (dinit) seed_step(L);
     for (int l = L; l >= 0; --l) {
         for (int wi = 0; wi < P.warps; ++wi) {
             int rc = run_stage(h, l, wi, B, off0, off1);
@@ -311,7 +325,8 @@ int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, in
 }
 
 // algorithmic (compulsory) HBM bytes of one solved pair from its executed iteration counts
-void account_bytes(const Engine* h, const int* it /* [nlev][warps][2] */, double* iter_bytes, double* total_bytes,
+// seeded: the pair started from a caller's flow (useInitialFlow)
+void account_bytes(const Engine* h, const int* it /* [nlev][warps][2] */, bool seeded, double* iter_bytes, double* total_bytes,
                    unsigned long long* n_in, unsigned long long* n_out)
 {
     const int warps = h->P.warps;
@@ -327,6 +342,8 @@ void account_bytes(const Engine* h, const int* it /* [nlev][warps][2] */, double
         }
         if (l > 0) tb += px * 8.0 + (double)h->tv.lv[l - 1].w * h->tv.lv[l - 1].h * 8.0;          // flow upsample
         if (l > 0) tb += 2.0 * (px * 4.0 + (double)h->tv.lv[l - 1].w * h->tv.lv[l - 1].h * 4.0);  // pyramid level (2 frames)
+        if (seeded) tb += l > 0 ? px * 8.0 + (double)h->tv.lv[l - 1].w * h->tv.lv[l - 1].h * 8.0  // initial flow: one level down,
+                                : px * 16.0;                                                    //   or the split of the caller's
     }
     tb += (double)h->tv.lv[0].w * h->tv.lv[0].h * (2.0 * (1 + 4) + 8.0 + 8.0);  // u8->f32 of 2 frames, output interleave
     *iter_bytes += ib; *total_bytes += tb + ib;

@@ -1,5 +1,5 @@
-// teeflow_tvl1_warp.hip.h -- DualTVL1's flow upsample and warp stage (k_flow_up, k_warp, k_warp_lds; k_grad and k_warp_cuda for
-// TF_VARIANT_CUDA); included by teeflow_kernels.hip.h, which holds the types, helpers and arithmetic contract
+// teeflow_tvl1_warp.hip.h -- DualTVL1's flow upsample, the initial flow's way down the pyramid, and the warp stage (k_flow_up; k_init_split,
+// k_init_down; k_warp, k_warp_lds; k_grad and k_warp_cuda for TF_VARIANT_CUDA); included by teeflow_kernels.hip.h, which holds the types, helpers and arithmetic contract
 #pragma once
 
 // flow: coarse level -> next finer level, times 1/scaleStep (resize + multiply of DualTVL1::calc)
@@ -17,6 +17,29 @@ __global__ __launch_bounds__(256) void k_flow_up(StateBufs sb, const PairCtl* __
     }
     sb.u1[uc ^ 1][di] = resize_px(sb.u1[uc] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale_x, scale_y) * mul;
     sb.u2[uc ^ 1][di] = resize_px(sb.u2[uc] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale_x, scale_y) * mul;
+}
+
+// ---- useInitialFlow: the caller's flow down the pyramid to the coarsest level, where the solve starts from it ---------------------
+// split(flow, u1s[0], u2s[0]): interleaved [B][H][W][2] (any 4-byte alignment) -> level-0 planes of u buffer `k`
+__global__ __launch_bounds__(256) void k_init_split(const float* __restrict__ init, StateBufs sb, int k, Geom g)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
+    if (x >= g.w || y >= g.h) return;
+    const size_t si = (((size_t)b * g.h + y) * g.w + x) * 2;
+    const size_t di = (size_t)b * g.splane + (size_t)y * g.pitch + x;
+    sb.u1[k][di] = init[si];
+    sb.u2[k][di] = init[si + 1];
+}
+
+// k_flow_up's mirror: level s-1 (u buffer `k`) -> level s (the other buffer) by the pyramid's rule, resize(src, Size(), scaleStep,
+// scaleStep) = resize_px with scale 1/scaleStep, times (float)scaleStep.  Reads and writes x < w only.
+__global__ __launch_bounds__(256) void k_init_down(StateBufs sb, int k, Geom gs, Geom gd, double scale, float mul)
+{
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
+    if (dx >= gd.w || dy >= gd.h) return;
+    const size_t di = (size_t)b * gd.splane + (size_t)dy * gd.pitch + dx;
+    sb.u1[k ^ 1][di] = resize_px(sb.u1[k] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale, scale) * mul;
+    sb.u2[k ^ 1][di] = resize_px(sb.u2[k] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale, scale) * mul;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -237,18 +237,41 @@ class DenseFlow:
         return out.reshape(s["n_pairs"], s["nscales_used"], s["warps"], 2)
 
     # ---- cv2 protocol --------------------------------------------------------------------------
+    def _initial_flows(self, init, shape, name):
+        """The initial flows of a pairs call as the library reads them, or None where it reads none.  getUseInitialFlow() decides, as
+        in cv2: off, whatever was passed is ignored; on, `init` must be a float32-convertible array of `shape` = the frames' + (2,),
+        x then y displacement in pixels per frame."""
+        if self.algo != "TVL1" or not self.getUseInitialFlow():
+            return None
+        if init is None:
+            raise OpticalFlowCalculationError(f"useInitialFlow is set: {name} must be the initial flow, got None")
+        try:
+            init = np.ascontiguousarray(init, dtype=np.float32)
+        except (TypeError, ValueError) as e:
+            raise OpticalFlowCalculationError(f"{name} must be convertible to float32: {e}") from None
+        if init.shape != tuple(shape):
+            raise OpticalFlowCalculationError(f"{name} must be float32 {list(shape)} (the frames' size, x and y), got shape {init.shape}")
+        return init
+
     def calc(self, I0, I1, flow=None):
         """flow = OF_model.calc(I0, I1, None): uint8 [H,W] x2 -> float32 [H,W,2] (x, y displacement).  float32 frames
-        (CV_32FC1) are accepted like cv2 does: DualTVL1 scales values in [0,1] by 255, DeepFlow takes them as they are."""
+        (CV_32FC1) are accepted like cv2 does: DualTVL1 scales values in [0,1] by 255, DeepFlow takes them as they are.
+        `flow` is read only after setUseInitialFlow(True), as in cv2: the solve then starts from it (float32 [H,W,2], pixels per frame)
+        and None raises.  It is never written: the result is a fresh array."""
         I0 = _u8_image_stack(I0, "I0", 2, allow_f32=True)
         I1 = _u8_image_stack(I1, "I1", 2, allow_f32=True)
         if I0.shape != I1.shape or I0.dtype != I1.dtype:
             raise OpticalFlowCalculationError(f"I0 and I1 differ: {I0.shape} {I0.dtype} vs {I1.shape} {I1.dtype}")
         H, W = I0.shape
+        init = self._initial_flows(flow, (H, W, 2), "flow")
         out = self._out((H, W, 2))
         st = _lib.TfStats()
-        fn = self._L.tf_calc_pair_f32 if I0.dtype == np.float32 else self._L.tf_calc_pair
-        _lib.check(fn(self._h, I0.ctypes.data, I1.ctypes.data, H, W, out.ctypes.data, C.byref(st)), self._h, "tf_calc_pair")
+        if init is not None:
+            _lib.check(self._L.tf_calc_pairs_init(self._h, I0.ctypes.data, I1.ctypes.data, int(I0.dtype == np.float32), init.ctypes.data, 1, H, W,
+                                                  out.ctypes.data, C.byref(st)), self._h, "tf_calc_pairs_init")
+        else:
+            fn = self._L.tf_calc_pair_f32 if I0.dtype == np.float32 else self._L.tf_calc_pair
+            _lib.check(fn(self._h, I0.ctypes.data, I1.ctypes.data, H, W, out.ctypes.data, C.byref(st)), self._h, "tf_calc_pair")
         self._finish(st)
         return out
 
@@ -781,26 +804,38 @@ class DenseFlow:
         as in calc_study_payload."""
         return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold)
 
-    def calc_pairs(self, I0s, I1s):
+    def calc_pairs(self, I0s, I1s, init=None):
         """B independent pairs: uint8 or float32 [B,H,W] x2 -> float32 [B,H,W,2] (float frames: DualTVL1 scales them by 255 like cv2, DeepFlow
-        takes them as they are like cv2)."""
+        takes them as they are like cv2).  `init`: the pairs' initial flows [B,H,W,2], read under setUseInitialFlow(True) as calc reads
+        `flow`."""
         I0s = _u8_image_stack(I0s, "I0s", 3, allow_f32=True)
         I1s = _u8_image_stack(I1s, "I1s", 3, allow_f32=True)
         if I0s.shape != I1s.shape or I0s.dtype != I1s.dtype:
             raise OpticalFlowCalculationError(f"I0s and I1s differ: {I0s.shape} {I0s.dtype} vs {I1s.shape} {I1s.dtype}")
         B, H, W = I0s.shape
+        init = self._initial_flows(init, (B, H, W, 2), "init")
         out = self._out((B, H, W, 2))
         st = _lib.TfStats()
-        fn = self._L.tf_calc_pairs_f32 if I0s.dtype == np.float32 else self._L.tf_calc_pairs
-        _lib.check(fn(self._h, I0s.ctypes.data, I1s.ctypes.data, B, H, W, out.ctypes.data, C.byref(st)), self._h, "tf_calc_pairs")
+        if init is not None:
+            _lib.check(self._L.tf_calc_pairs_init(self._h, I0s.ctypes.data, I1s.ctypes.data, int(I0s.dtype == np.float32), init.ctypes.data, B, H, W,
+                                                  out.ctypes.data, C.byref(st)), self._h, "tf_calc_pairs_init")
+        else:
+            fn = self._L.tf_calc_pairs_f32 if I0s.dtype == np.float32 else self._L.tf_calc_pairs
+            _lib.check(fn(self._h, I0s.ctypes.data, I1s.ctypes.data, B, H, W, out.ctypes.data, C.byref(st)), self._h, "tf_calc_pairs")
         self._finish(st)
         return out
 
-    def calc_pairs_device(self, dI0s_ptr, dI1s_ptr, B, H, W, dflow_ptr, scale=1.0):
-        """Device-resident form: raw device pointers (e.g. tensor.data_ptr()); result written to dflow_ptr."""
+    def calc_pairs_device(self, dI0s_ptr, dI1s_ptr, B, H, W, dflow_ptr, scale=1.0, dinit_ptr=None):
+        """Device-resident form: raw device pointers (e.g. tensor.data_ptr()); result written to dflow_ptr.  `dinit_ptr`: the pairs'
+        initial flows, device float32 [B,H,W,2] in pixels per frame (not times `scale`), read under setUseInitialFlow(True) -- the
+        library refuses the call when the flag is set and there is none; it may be dflow_ptr itself."""
         st = _lib.TfStats()
-        _lib.check(self._L.tf_calc_pairs_device(self._h, C.c_void_p(dI0s_ptr), C.c_void_p(dI1s_ptr), int(B), int(H), int(W),
-                                                float(scale), C.c_void_p(dflow_ptr), C.byref(st)), self._h, "tf_calc_pairs_device")
+        if dinit_ptr is None:
+            _lib.check(self._L.tf_calc_pairs_device(self._h, C.c_void_p(dI0s_ptr), C.c_void_p(dI1s_ptr), int(B), int(H), int(W),
+                                                    float(scale), C.c_void_p(dflow_ptr), C.byref(st)), self._h, "tf_calc_pairs_device")
+        else:
+            _lib.check(self._L.tf_calc_pairs_init_device(self._h, C.c_void_p(dI0s_ptr), C.c_void_p(dI1s_ptr), C.c_void_p(dinit_ptr), int(B), int(H),
+                                                         int(W), float(scale), C.c_void_p(dflow_ptr), C.byref(st)), self._h, "tf_calc_pairs_init_device")
         self._finish(st)
         return self.last_stats
 

@@ -192,12 +192,29 @@ int tf_calc_seq_device(tf_handle* h, const uint8_t* dframes, int N, int H, int W
  *     dflow_out is allowed.
  * With the flag off both calls ignore the initial flows (they may be NULL), as cv2 does.  With the flag ON, every call that carries no
  * initial flow -- tf_calc_pair(s), the _f32 and _device forms, every tf_calc_seq* and tf_submit_* call, the saliency, WASE, float16 and
- * held-payload study calls, and these two with a NULL initial flow -- returns TF_ERR_UNSUPPORTED before any GPU work.
+ * held-payload study calls, and these two with a NULL initial flow -- returns TF_ERR_UNSUPPORTED before any GPU work (a sequence call
+ * armed by tf_chain_next, below, carries its own: each pair's is the flow before it).
  * TF_VARIANT_CUDA handles refuse the flag itself, and gamma != 0 stays refused. */
 int tf_calc_pairs_init(tf_handle* h, const void* I0s, const void* I1s, int frames_f32, const float* init_flows, int B, int H, int W,
                        float* flow_out, tf_stats* st);
 int tf_calc_pairs_init_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* dI1s, const float* d_init, int B, int H, int W, float scale,
                               float* dflow_out, tf_stats* st);
+
+/* A chained sequence, the video idiom `flow = OF_model.calc(frames[k], frames[k+1], flow)` as ONE call (DualTVL1, TF_VARIANT_CPU, with
+ * TF_PARAM_USE_INITIAL_FLOW set).  tf_chain_next(h, 1) arms the NEXT solve call of the handle; if that is a sequence call -- tf_calc_seq,
+ * tf_calc_seq_device, tf_submit_seq, tf_submit_seq_device, tf_calc_seq_rgb[_f16], tf_submit_seq_rgb[_f16], tf_calc_seq_saliency[_f32|_f16]
+ * and the two *_wase forms -- it is solved as a chain: pair 0 starts from zero (the plain solve bit for bit), pair k >= 1 from pair
+ * k-1's flow as the solver left it: float32, in pixels per frame, before `scale`, before WASE compensation and before any float16
+ * rounding (never read back from the call's output), taken down the pyramid by the rule above; nothing else about a pair's solve
+ * changes, so the result equals the loop of tf_calc_pairs_init calls bit for bit, iteration counts included.  The sequence stays on the
+ * device and every frame's pyramid is built once, but the pairs are solved one after the other: a chained call is one unit of the lane
+ * queue, never split, and costs about N-1 single-pair solves -- several times the batched call (README).  Submitted chains run side by
+ * side, one per lane.  With tf_hold_next also armed, the chained float16 study is left held as usual.  The call spends the flag
+ * whether it is refused or not; tf_chain_next(h, 0) disarms.  Refused, before any GPU work: arming while TF_PARAM_USE_INITIAL_FLOW is
+ * clear (cv2 ignores the flow then: the chain would be the plain solve at N-1 serial steps), or on a DeepFlow or TF_VARIANT_CUDA handle
+ * -> TF_ERR_UNSUPPORTED; an armed pairs call -> TF_ERR_INVALID_ARG.  Unarmed sequence calls stay refused while the flag is set.
+ * tf_dbg_counter(h, "chain_steps"): pairs solved as chain steps. */
+int tf_chain_next(tf_handle* h, int on);
 
 /* Asynchronous forms of tf_calc_pairs_device, tf_calc_seq_device, tf_calc_pairs and tf_calc_seq (the loop calculate_optical_flow.py:584-597 for SEVERAL studies / batches at a time):
  * the job is queued on the handle's lanes and the call returns with a ticket; every buffer must stay valid and untouched until

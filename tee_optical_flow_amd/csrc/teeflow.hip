@@ -237,6 +237,10 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
             v = n == "queue_units_done" ? h->q_units_done : n == "queue_units_skipped" ? h->q_units_skipped : n == "queue_units_failed" ? h->q_units_failed : n == "queue_outstanding" ? h->pool->outstanding : (long long)h->pool->lanes.size();
         }
     }
+    else if (n == "chain_steps") {
+        if (h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); v = h->chain_steps; }
+        else v = h->chain_steps;
+    }
     else if (n == "coop_occ16") v = h->coop.occ16;
     else if (n == "coop_occ8") v = h->coop.occ8;
     return v;
@@ -324,6 +328,22 @@ TF_API int tf_calc_pairs_init_device(tf_handle* h, const uint8_t* dI0s, const ui
                                      float* dflow_out, tf_stats* st)
 {
     return calc_init_entry(h, {MODE_PAIRS, dI0s, dI1s, B, H, W, scale, dflow_out, W_DEV}, d_init, st);
+}
+
+// ---- a chained sequence (the video idiom `flow = calc(frames[k], frames[k+1], flow)`): armed for the handle's next solve call --------
+// (Call::chain; take_chain and study_call spend the flag)
+TF_API int tf_chain_next(tf_handle* h, int on)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    h->chain_next = false;
+    if (!on) return TF_OK;
+    if (h->P.algo == TF_ALGO_DEEPFLOW) return fail(h, TF_ERR_UNSUPPORTED, "a chained sequence is DualTVL1's (useInitialFlow): DeepFlow takes no initial flow");
+    if (h->P.variant == TF_VARIANT_CUDA) return fail(h, TF_ERR_UNSUPPORTED, "a chained sequence needs useInitialFlow, which TF_VARIANT_CUDA does not implement");
+    if (!h->P.use_initial_flow)
+        return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is clear: cv2 then ignores a passed flow, so a chain would be the plain solve at the cost of "
+                                            "N-1 serial steps; set TF_PARAM_USE_INITIAL_FLOW first, or make the plain call");
+    h->chain_next = true;
+    return TF_OK;
 }
 
 // ---- asynchronous forms: the job is queued on the handle's lanes and the call returns; tf_wait collects it ----------------------

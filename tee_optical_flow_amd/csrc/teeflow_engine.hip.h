@@ -164,6 +164,7 @@ struct Engine : TfKnobs {
         double df_sor_bytes = 0;     // DeepFlow: algorithmic bytes of the SOR launches of the current call (40 B per pixel-sweep)
         double df_sor_px = 0;        // DeepFlow: pixels x pairs summed over the SOR launches (a launch's compulsory traffic is 40 B per pixel: 8 planes in, 2 out)
         size_t prof_used = 0;        // records of prof_pool in use
+        long long chain_steps = 0;   // DualTVL1: pairs solved as steps of a chained sequence
     } tally;
     int slots_pct = 100;         // per cent of the resident blocks this engine sizes its strips for (a lane: what its current job says)
     Tvl1State tv;
@@ -222,6 +223,8 @@ struct tf_handle : Engine {
         }
     } held;
     bool hold_next = false;      // tf_hold_next: the next study call leaves its payload held
+    bool chain_next = false;     // tf_chain_next: the next solve call, a sequence call, is solved as a chain (take_chain spends it)
+    long long chain_steps = 0;   // pairs this handle and its lanes have solved as chain steps ("chain_steps" counter; the pool's lock where there is a pool)
     long long tail_upload_bytes = 0;   // bytes of flow, mask and echo the tail calls (and tf_hold_*) have copied host -> device
     // RCCL: one communicator rank per handle, its own stream, a small ring of completion events
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 0;

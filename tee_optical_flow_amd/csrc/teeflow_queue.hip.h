@@ -16,6 +16,8 @@ struct Call {
     void* keep = nullptr;        // device memory that gets a copy of every flow, in the output type, made on the device (a held study's flow)
     const float* init = nullptr; // useInitialFlow (MODE_PAIRS): every pair's initial flow, float32 [H][W][2] in pixels per frame, where the
                                  // frames live (W_IN_DEV); may be `out` itself -- a pair's is read before its flow is written
+    bool chain = false;          // useInitialFlow (MODE_SEQ, armed by tf_chain_next): pair 0 starts from zero, pair k from pair k-1's flow as
+                                 // the solver left it.  Such a call is ONE unit: one engine solves its sub-batches in order, pair after pair
     size_t frame_bytes() const { return (size_t)H * W * (f32 ? 4 : 1); }
     size_t flow_bytes() const { return (size_t)H * W * 2 * (out_f16 ? 2 : 4); }      // BYTES of one pair's flow
     Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
@@ -64,12 +66,17 @@ int check_call(Engine* h, const Call& c)
     if (!h) return TF_ERR_INVALID_ARG;
     if (c.mode == MODE_SEQ && c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", c.n_pairs + 1);
     if (!c.in0 || (c.mode == MODE_PAIRS && !c.in1) || !c.out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
+    if (c.chain && c.mode != MODE_SEQ)
+        return fail(h, TF_ERR_INVALID_ARG, "tf_chain_next arms a sequence call (tf_calc_seq*, tf_submit_seq*): a pairs call takes its initial "
+                                            "flows itself (tf_calc_pairs_init); the flag is spent, call tf_chain_next again before the sequence call");
     if (c.H < 1 || c.W < 1 || c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", c.n_pairs, c.H, c.W);
     if ((long long)c.H * c.W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
     if (c.out_f16 && (c.where & W_OUT_DEV)) return fail(h, TF_ERR_UNSUPPORTED, "float16 flows go to host destinations only");
     if (c.init && c.mode == MODE_SEQ) return fail(h, TF_ERR_UNSUPPORTED, "a sequence call takes no initial flow");
+    if (c.chain && (h->P.algo == TF_ALGO_DEEPFLOW || !h->P.use_initial_flow))      // (tf_chain_next refuses both: the flag was cleared since)
+        return fail(h, TF_ERR_UNSUPPORTED, "a chained sequence needs a DualTVL1 handle with useInitialFlow set: set it, then tf_chain_next, then the call");
     if (h->P.algo == TF_ALGO_DEEPFLOW) return df_validate(h, h->DP);
-    if (h->P.use_initial_flow && !c.init)
+    if (h->P.use_initial_flow && !c.init && !c.chain)
         return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is set and this call carries no initial flow: only tf_calc_pairs_init and "
                                             "tf_calc_pairs_init_device take one (or clear the flag)");
     return validate_params(h, h->P);
@@ -141,8 +148,9 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
         if (overlap && kb >= 2) HIPC(h, hipStreamWaitEvent(h->stream, h->cev[2 + (kb & 1)], 0));   // that half's last copy-out
         HIPC(h, hipEventRecord(h->ev[1], h->stream));
         const Engine::Tally snap = h->tally;              // what a repeat of this sub-batch must not count twice (an aborted co-resident attempt is void)
-        rc = deep ? df_solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16)
-                  : solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16, dinit);
+        if (deep) rc = df_solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16);
+        else if (c.chain) rc = solve_chain_resident(h, dfr, c.f32, nb, c.scale, dfl, c.out_f16, c0 > 0);   // (c0 > 0: the seed is the sub-batch before's)
+        else rc = solve_resident(h, dfr, c.f32, F, nb, off0, off1, c.scale, dfl, c.out_f16, dinit);
         if (rc) return rc;
         HIPC(h, hipEventRecord(h->ev[2], h->stream));
         if (p.keep) HIPC(h, hipMemcpyAsync(p.keep, dfl, (size_t)nb * flb, hipMemcpyDeviceToDevice, h->stream));   // (byte copy: any offset)
@@ -186,7 +194,7 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
             st->iter_pair_steps = (unsigned long long)h->tally.df_sor_px;     // pixels x pairs summed over the SOR launches
         } else {
             for (int b = 0; b < c.n_pairs; ++b)
-                account_bytes(h, iters + (size_t)b * per_pair, c.init != nullptr, &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
+                account_bytes(h, iters + (size_t)b * per_pair, c.init != nullptr || (c.chain && b > 0), &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
             st->iter_pair_steps = st->inner_iters_total;
         }
         double ims = 0, warp_ms = 0, median_ms = 0;
@@ -359,8 +367,10 @@ void lane_worker(tf_handle* owner, LanePool* pool, int k)
                     char where[96]; snprintf(where, sizeof where, "sub-batch %d (pairs %d..%d): ", u, c0, c0 + nb - 1);
                     j->err = std::string(where) + lane->err;
                 }
-            } else if (!skip)
+            } else if (!skip) {
                 merge_stats(&j->st, us);
+                owner->chain_steps += lane->tally.chain_steps;
+            }
             pool->coop[k] = lane->coop.counters();
             last = ++j->done == j->n_units;
             // every lane that worked for this job has drained its streams (a solve is host-synchronous, a failed one drains in
@@ -468,6 +478,7 @@ int queue_submit(tf_handle* h, QJob* j, bool balance, int parts)
         const int U = L * ((n_pairs + L * j->unit - 1) / (L * j->unit));
         j->unit = (n_pairs + U - 1) / U;
     }   // (a submitted job's last units run beside the next job's first: whole sub-batches, which are the more efficient units)
+    if (j->call.chain) j->unit = n_pairs;                    // a chain is one unit: its pairs are solved in order, by one lane
     j->n_units = (n_pairs + j->unit - 1) / j->unit;
     j->fail_unit = h->queue_test_fail_unit; h->queue_test_fail_unit = -1;
     j->t0 = now_ms();
@@ -484,14 +495,16 @@ int queue_submit(tf_handle* h, QJob* j, bool balance, int parts)
 // The one route from an entry point to a solve: call c (checked) becomes job j.  An idle call of at most one sub-batch is split in
 // split_count() contiguous units that the lanes solve side by side, or solved by this handle alone when that count is 1.  A larger one --
 // or any call while tf_submit_* jobs are in flight, and every submitted one -- goes to the queue: whole sub-batches, taken by the lanes as
-// they come free.  An external stream, or "queue_lanes" = 0, has the handle solve every call alone.  A job solved alone, or one that could
+// they come free.  A chained sequence (Call::chain) is never cut: the handle solves it where an idle call of one sub-batch would be split, and
+// in the queue it is one unit, so that one lane solves its sub-batches in order.  An external stream, or "queue_lanes" = 0, has the handle solve every call alone.  A job solved alone, or one that could
 // not be queued, is finished on return and its rc is returned; a queued one is the lanes' until queue_finish has waited for it.
 int start_call(tf_handle* h, const Call& c, QJob* j, bool submitted)
 {
     const bool can_queue = queue_lane_count(h) > 0 && h->stream == h->own_stream;
     bool busy = submitted;                                   // (a submitted job is cut like a call behind others: balance = false, parts = 0)
     if (can_queue && h->pool && !busy) { std::lock_guard<std::mutex> lk(h->pool->m); busy = h->pool->outstanding > 0; }
-    const int parts = !busy && c.n_pairs <= sub_batch_pairs(h) ? split_count(h, c.n_pairs) : 0;
+    // (a chain is never split: idle and within one sub-batch the handle solves it, otherwise it is one unit of the queue)
+    const int parts = !busy && c.n_pairs <= sub_batch_pairs(h) ? (c.chain ? 1 : split_count(h, c.n_pairs)) : 0;
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
     Geom lv[DF_MAXLEV];                                      // (the pyramid calc_common will build: stats, tf_get_iters)
     j->call = c;
@@ -508,6 +521,10 @@ int start_call(tf_handle* h, const Call& c, QJob* j, bool submitted)
         h->coop.share = claim.ok ? h->num_cus : 0;
         j->t0 = now_ms();
         j->rc = calc_common_guarded(h, c, j->iters.data(), &j->st);
+        if (j->rc == TF_OK && h->tally.chain_steps) {
+            if (h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); h->chain_steps += h->tally.chain_steps; }
+            else h->chain_steps += h->tally.chain_steps;
+        }
     }
     if (j->rc != TF_OK) j->err = h->err;
     j->finished = true;
@@ -531,10 +548,18 @@ int queue_finish(tf_handle* h, QJob* j, tf_stats* st)
     return TF_OK;
 }
 
+// tf_chain_next's flag is spent by the next solve call, whatever becomes of it: the call as that flag makes it
+Call take_chain(tf_handle* h, Call c)
+{
+    if (h && h->chain_next) { c.chain = true; h->chain_next = false; }
+    return c;
+}
+
 // Entry used by the C ABI: start_call + queue_finish.  A failed unit stops the job's remaining units from starting; the units already
 // running complete, so nothing of the call is in flight when it returns.
-int calc_entry(tf_handle* h, const Call& c, tf_stats* st)
+int calc_entry(tf_handle* h, const Call& c0, tf_stats* st)
 {
+    const Call c = take_chain(h, c0);
     const int rc = check_call(h, c);
     if (rc) return rc;
     QJob j;
@@ -544,9 +569,10 @@ int calc_entry(tf_handle* h, const Call& c, tf_stats* st)
 
 // tf_submit_*: the same job, not waited for.  Returns a ticket for tf_wait; a job that failed already (solved alone: "queue_lanes" = 0)
 // returns its error and no ticket.
-int submit_entry(tf_handle* h, const Call& c, int* ticket, void* owned_dev = nullptr)
+int submit_entry(tf_handle* h, const Call& c0, int* ticket, void* owned_dev = nullptr)
 {
     struct Guard { void* p; ~Guard() { if (p) (void)hipFree(p); } } guard{owned_dev};
+    const Call c = take_chain(h, c0);
     int rc = check_call(h, c);
     if (rc) return rc;
     if (!ticket) return TF_ERR_INVALID_ARG;

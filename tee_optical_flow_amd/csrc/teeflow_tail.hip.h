@@ -1136,6 +1136,8 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
     struct Owned { uint8_t* p = nullptr; ~Owned() { if (p) (void)hipFree(p); } } own;     // (freed after the failed call has been drained)
     const bool hold = h && h->hold_next;
     if (h) h->hold_next = false;
+    const bool chain = h && h->chain_next;                   // tf_chain_next: spent likewise
+    if (h) h->chain_next = false;
     bool holding = false;                                    // held_alloc has run for this call
     auto run = [&]() -> int {
         if (!h) return TF_ERR_INVALID_ARG;
@@ -1147,6 +1149,7 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
         if (submit && (s.sees != FR_GRAY || s.wase)) return fail(h, TF_ERR_UNSUPPORTED, "only a plain RGB study can be submitted");
         // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are); a WASE study's scale is k_wase_out's
         Call c{MODE_SEQ, s.frames, nullptr, s.N - 1, s.H, s.W, s.wase ? 1.0f : s.scale, s.flow_out, W_HOST, s.sees == FR_SAL_F32, s.out_f16};
+        c.chain = chain;
         int rc = check_call(h, c);
         if (rc) return rc;
         if (submit && !ticket) return TF_ERR_INVALID_ARG;

@@ -206,8 +206,8 @@ int read_reports(Engine* h, hipStream_t s, unsigned q, unsigned* checked, bool* 
     return TF_OK;
 }
 
-// one (level, warp) stage for pairs [0,B)
-int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
+// one (level, warp) stage for pairs [0,B); pair b's executed iteration counts go to iters_dev[b] (a chain step's pair: its own slice)
+int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_dev)
 {
     const tf_params& P = h->P;
     const Geom g = h->tv.lv[l];
@@ -267,15 +267,13 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1)
         rc = read_reports(h, s, q, &checked, &stop);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, h->tv.iters_dev, B,
+    hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, iters_dev, B,
                        total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps, P.variant, thr_d, step);
     return TF_OK;
 }
 
-// Solve B pairs whose frames are in device memory: frames[F][H][W] (uint8, or float32 in [0,1] when f32), pair b = (off0+b, off1+b).
-// dinit (useInitialFlow): the pairs' initial flows in device memory, float32 [B][H][W][2] in pixels per frame, or null = start from zero.
-int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16,
-                   const float* dinit = nullptr)
+// frames[F][H][W] in device memory (uint8, or float32 in [0,1] when f32) -> their pyramids (and, TF_VARIANT_CUDA, the gradients)
+void build_pyramids(Engine* h, const uint8_t* dframes, bool f32, int F)
 {
     const tf_params& P = h->P;
     hipStream_t s = h->stream;
@@ -290,24 +288,45 @@ int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, in
     if (P.variant == TF_VARIANT_CUDA)
         for (int l = 0; l < h->tv.nlev; ++l)
             hipLaunchKernelGGL(k_grad, grid64x4(h->tv.lv[l], F), dim3(256), 0, s, h->tv.pyr[l], h->tv.gxl[l], h->tv.gyl[l], h->tv.lv[l]);
+}
+
+// Where a solve's level-0 initial flow comes from (useInitialFlow): nowhere (start from zero), the caller's interleaved flows, or -- a
+// chained sequence, one pair -- the state planes of slot 0 as the pair solved there before has left them.
+enum Seed { SEED_ZERO, SEED_FLOWS, SEED_STATE };
+
+// Solve B pairs of the pyramids build_pyramids has made, pair b = frames (off0+b, off1+b), in state slots [0,B): the seed, the level /
+// warp stages, the output.  dinit (SEED_FLOWS): device float32 [B][H][W][2] in pixels per frame.  SEED_STATE: B == 1.  The executed
+// iteration counts go to iters_dev[b], the flows, times `scale`, to dflow[b].
+int solve_pairs(Engine* h, int B, int off0, int off1, Seed seed, const float* dinit, int* iters_dev, float scale, void* dflow, bool out_f16)
+{
+    const tf_params& P = h->P;
+    hipStream_t s = h->stream;
+    const Geom g0 = h->tv.lv[0];
     const int L = h->tv.nlev - 1;
-    hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.ctl, B, 0);
     // useInitialFlow: u?s[0] = split(flow), u?s[l] = resize(u?s[l-1], Size(), scaleStep, scaleStep) * scaleStep, every level rounded to
     // float32 before the next is taken from it.  Level l lives in u buffer (L - l) & 1, so the coarsest one ends in buffer 0, which the
     // first stage reads (ubase = 0); the levels in between are scratch.  All but the last step run BEFORE the two memsets: a level in
     // between that sits in buffer 0 would otherwise write into the row padding they clear.
-    const auto seed_step = [&](int l) {         // level l of the chain, from the caller's flow (l == 0) or from level l - 1
-        if (l == 0) hipLaunchKernelGGL(k_init_split, grid64x4(g0, B), dim3(256), 0, s, dinit, h->tv.sb, L & 1, g0);
-        else hipLaunchKernelGGL(k_init_down, grid64x4(h->tv.lv[l], B), dim3(256), 0, s, h->tv.sb, (L - l + 1) & 1, h->tv.lv[l - 1], h->tv.lv[l],
-                                1.0 / P.scale_step, (float)P.scale_step);
+    const auto seed_step = [&](int l) {         // level l of the chain, from the caller's flow or the state (l == 0) or from level l - 1
+        if (l > 0) hipLaunchKernelGGL(k_init_down, grid64x4(h->tv.lv[l], B), dim3(256), 0, s, h->tv.sb, (L - l + 1) & 1, h->tv.lv[l - 1], h->tv.lv[l],
+                                      1.0 / P.scale_step, (float)P.scale_step);
+        else if (seed == SEED_FLOWS) hipLaunchKernelGGL(k_init_split, grid64x4(g0, B), dim3(256), 0, s, dinit, h->tv.sb, L & 1, g0);
     };
-    if (dinit) for (int l = 0; l < L; ++l) seed_step(l);
-    HIPC(h, hipMemset2DAsync(h->tv.sb.u1[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
-    HIPC(h, hipMemset2DAsync(h->tv.sb.u2[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
-    if (dinit) seed_step(L);
+    // A chain step's level 0 is the last pair's flow, in the buffer that pair's ctl names: k_chain_seed reads ctl before k_ctl_set
+    // resets it.  With one level that flow is itself what the first stage reads, in buffer 0: the memsets, which would clear it, are left
+    // out, and the kernel clears the row padding in their place.
+    if (seed == SEED_STATE)
+        hipLaunchKernelGGL(k_chain_seed, dim3((g0.pitch + 63) / 64, (g0.h + 3) / 4, 1), dim3(256), 0, s, h->tv.sb, h->tv.ctl, L & 1, g0, L == 0 ? 1 : 0);
+    hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.ctl, B, 0);
+    if (seed != SEED_ZERO) for (int l = 0; l < L; ++l) seed_step(l);
+    if (!(seed == SEED_STATE && L == 0)) {
+        HIPC(h, hipMemset2DAsync(h->tv.sb.u1[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
+        HIPC(h, hipMemset2DAsync(h->tv.sb.u2[0], (size_t)h->tv.lv[L].splane * sizeof(float), 0, (size_t)h->tv.lv[L].plane * sizeof(float), B, s));
+    }
+    if (seed != SEED_ZERO) seed_step(L);
     for (int l = L; l >= 0; --l) {
         for (int wi = 0; wi < P.warps; ++wi) {
-            int rc = run_stage(h, l, wi, B, off0, off1);
+            int rc = run_stage(h, l, wi, B, off0, off1, iters_dev);
             if (rc) return rc;
         }
         if (l == 0) break;
@@ -321,6 +340,34 @@ int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, in
     if (out_f16) hipLaunchKernelGGL(k_output<uint16_t>, out_grid<uint16_t>(g0, B), dim3(256), 0, s, h->tv.sb, h->tv.ctl, g0, scale, (uint16_t*)dflow);
     else hipLaunchKernelGGL(k_output<float>, out_grid<float>(g0, B), dim3(256), 0, s, h->tv.sb, h->tv.ctl, g0, scale, (float*)dflow);
     HIPC(h, hipGetLastError());
+    return TF_OK;
+}
+
+// Solve B pairs whose frames are in device memory: frames[F][H][W] (uint8, or float32 in [0,1] when f32), pair b = (off0+b, off1+b).
+// dinit (useInitialFlow): the pairs' initial flows in device memory, float32 [B][H][W][2] in pixels per frame, or null = start from zero.
+int solve_resident(Engine* h, const uint8_t* dframes, bool f32, int F, int B, int off0, int off1, float scale, void* dflow, bool out_f16,
+                   const float* dinit = nullptr)
+{
+    build_pyramids(h, dframes, f32, F);
+    return solve_pairs(h, B, off0, off1, dinit ? SEED_FLOWS : SEED_ZERO, dinit, h->tv.iters_dev, scale, dflow, out_f16);
+}
+
+// A chained sequence's sub-batch (useInitialFlow, tf_chain_next): the B pairs (k, k+1) of frames[B+1], solved one after the other in
+// state slot 0, each seeded by the flow the pair before it has left there -- float32, in pixels per frame, before `scale` and before any
+// float16 rounding: never read back from dflow.  The first pair starts from zero, or (`carry`: the call's later sub-batches) from what
+// the sub-batch before has left: nothing between the two writes slot 0's planes or ctl.  Every frame's pyramid is built once; nothing
+// here waits for the stream beyond what a stage's read_reports does.
+int solve_chain_resident(Engine* h, const uint8_t* dframes, bool f32, int B, float scale, void* dflow, bool out_f16, bool carry)
+{
+    build_pyramids(h, dframes, f32, B + 1);
+    const size_t per_pair = (size_t)h->tv.nlev * h->P.warps * 2;
+    const size_t flb = (size_t)h->tv.H * h->tv.W * 2 * (out_f16 ? sizeof(uint16_t) : sizeof(float));
+    for (int k = 0; k < B; ++k) {
+        const int rc = solve_pairs(h, 1, k, k + 1, k > 0 || carry ? SEED_STATE : SEED_ZERO, nullptr, h->tv.iters_dev + (size_t)k * per_pair, scale,
+                                   (uint8_t*)dflow + (size_t)k * flb, out_f16);
+        if (rc) return rc;
+        ++h->tally.chain_steps;
+    }
     return TF_OK;
 }
 

@@ -1,5 +1,5 @@
 // teeflow_tvl1_warp.hip.h -- DualTVL1's flow upsample, the initial flow's way down the pyramid, and the warp stage (k_flow_up; k_init_split,
-// k_init_down; k_warp, k_warp_lds; k_grad and k_warp_cuda for TF_VARIANT_CUDA); included by teeflow_kernels.hip.h, which holds the types, helpers and arithmetic contract
+// k_init_down, k_chain_seed; k_warp, k_warp_lds; k_grad and k_warp_cuda for TF_VARIANT_CUDA); included by teeflow_kernels.hip.h, which holds the types, helpers and arithmetic contract
 #pragma once
 
 // flow: coarse level -> next finer level, times 1/scaleStep (resize + multiply of DualTVL1::calc)
@@ -40,6 +40,26 @@ __global__ __launch_bounds__(256) void k_init_down(StateBufs sb, int k, Geom gs,
     const size_t di = (size_t)b * gd.splane + (size_t)dy * gd.pitch + dx;
     sb.u1[k ^ 1][di] = resize_px(sb.u1[k] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale, scale) * mul;
     sb.u2[k ^ 1][di] = resize_px(sb.u2[k] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale, scale) * mul;
+}
+
+// A chained sequence: pair 0's finished level-0 flow (slot 0, u buffer ctl[0].ubase -- which one depends on the iterations it executed,
+// so only the device knows) becomes the next pair's initial flow, level 0 of the chain above, which k_init_down expects in u buffer `k`:
+// kept where it is, or moved.  `pad` (a one-level solve, where this level is the one the first stage reads and the host's memsets,
+// which would clear it, are left out): the row padding x in [w, pitch) of buffer `k` is cleared, as those memsets leave it.  Reads
+// ctl[0] and never writes it: k_ctl_set follows.  One thread per (x < pitch, y < h); one pair.
+__global__ __launch_bounds__(256) void k_chain_seed(StateBufs sb, const PairCtl* __restrict__ ctl, int k, Geom g, int pad)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.pitch || y >= g.h) return;
+    const size_t i = (size_t)y * g.pitch + x;
+    if (x >= g.w) {
+        if (pad) { sb.u1[k][i] = 0.f; sb.u2[k][i] = 0.f; }
+        return;
+    }
+    const int uc = ctl[0].ubase & 1;
+    if (uc == k) return;
+    sb.u1[k][i] = sb.u1[uc][i];
+    sb.u2[k][i] = sb.u2[uc][i];
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -123,6 +123,7 @@ class DenseFlow:
 
     device_unit_scale = True        # calc_study(scale=, pad_last=) applies the unit scale in the output kernel (pipeline.flow_for_study)
     device_payload = True           # calc_study_payload & co. hand over the study file's float16 `flow` and `echo` (process_folder(payload="device"))
+    device_chain = True             # calc_batch, calc_seq_device, submit_batch and every study form take chain=True (after setUseInitialFlow(True))
     device_wase = True              # calc_study_wase & co. solve and compensate a bkgd_comp="WASE" study in one call, float32 or float16
 
     _SETTERS = {"Tau": "tau", "Lambda": "lambda", "Theta": "theta", "ScalesNumber": "nscales",
@@ -220,7 +221,7 @@ class DenseFlow:
 
     def counter(self, name):
         """Debug counters of the engine (tf_dbg_counter): coop_launches, coop_aborts, coop_disabled, coop_rearms, coop_cooldown, coop_occ16, coop_occ8,
-        queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised,
+        queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised, chain_steps,
         saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels)."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
@@ -276,14 +277,25 @@ class DenseFlow:
         return out
 
     # ---- batched forms (the data-parallel path the reference lacks) ------------------------------
-    def calc_batch(self, frames, scale=1.0):
-        """frames uint8 [N,H,W] -> float32 [N-1,H,W,2]: flow(frame i -> i+1) * scale (reference loop :584-597)."""
+    def chain_next(self, on=True):
+        """Arm (or disarm) the next solve call, a sequence or study call, to be solved as a chain: what chain=True does.  Needs
+        setUseInitialFlow(True) on a DualTVL1 model of the CPU form; the library spends the flag on the next solve call, whatever becomes
+        of it, and refuses an armed pairs call."""
+        _lib.check(self._L.tf_chain_next(self._h, 1 if on else 0), self._h, "tf_chain_next")
+
+    def calc_batch(self, frames, scale=1.0, chain=False):
+        """frames uint8 [N,H,W] -> float32 [N-1,H,W,2]: flow(frame i -> i+1) * scale (reference loop :584-597).
+        `chain` (after setUseInitialFlow(True)): the video idiom `flow = calc(frames[k], frames[k+1], flow)` in one call -- pair 0 starts
+        from zero, pair k from pair k-1's unscaled float32 flow -- with the bits and iteration counts of that loop.  The pairs are solved
+        one after the other on the device: expect about N-1 single-pair solves, several times the batched call."""
         frames = _u8_image_stack(frames, "frames", 3)
         N, H, W = frames.shape
         if N < 2:
             raise OpticalFlowCalculationError("need at least 2 frames")
         out = self._out((N - 1, H, W, 2))
         st = _lib.TfStats()
+        if chain:
+            self.chain_next()
         _lib.check(self._L.tf_calc_seq(self._h, frames.ctypes.data, N, H, W, float(scale), out.ctypes.data, C.byref(st)),
                    self._h, "tf_calc_seq")
         self._finish(st)
@@ -310,10 +322,11 @@ class DenseFlow:
         return nparr
 
     def _study(self, nparr, scale, pad_last, *, saliency=False, map_dtype="f32", f16=False, echo=False, bkgd_mask=None, submit=False,
-               hold=False):
+               hold=False, chain=False):
         """One study call: the frame check, the pinned outputs, the C function of the cell and its arguments.  -> what _collect makes of
         the job, or (`submit`) the ticket wait() collects it by.  Only the float32 saliency form takes one-channel frames.  `hold` (the
-        float16 forms that are waited for): the call also leaves its payload held on the device (hold_study's doc)."""
+        float16 forms that are waited for): the call also leaves its payload held on the device (hold_study's doc).  `chain` (every
+        cell, after setUseInitialFlow(True)): the study's pairs are solved as a chain (calc_batch's doc)."""
         wase = bkgd_mask is not None
         if hold and (submit or not f16):
             raise OpticalFlowCalculationError("only a float16 study call that is waited for can leave its payload held")
@@ -342,6 +355,8 @@ class DenseFlow:
         frames = (self._h, nparr.ctypes.data, N, H, W)
         if saliency:
             frames += (ch, int(map_f32)) if f16 or wase else (ch,)
+        if chain:
+            self.chain_next()                              # (first: a refusal here leaves nothing else armed)
         if hold:
             self.hold_next()
         _lib.check(getattr(self._L, name)(*frames, *own), self._h, name)
@@ -360,11 +375,13 @@ class DenseFlow:
             job.out[job.pad_n - 1] = job.out[job.pad_n - 2]
         return (job.out,) + job.extra if job.extra else job.out
 
-    def calc_study(self, nparr, scale=1.0, pad_last=False):
+    def calc_study(self, nparr, scale=1.0, pad_last=False, chain=False):
         """RGB study uint8 [N,H,W,3] -> float32 [N-1,H,W,2]: conditioning and all pair solves stay on the device.
         `pad_last`: the result is [N,H,W,2] with the last flow repeated (reference :599) -- written into one pinned buffer, no
-        concatenate on the host; with `scale` = pixel_spacing * frame_rate this is the study's whole flow array (:600)."""
-        return self._study(nparr, scale, pad_last)
+        concatenate on the host; with `scale` = pixel_spacing * frame_rate this is the study's whole flow array (:600).
+        `chain` (this and every other study form, after setUseInitialFlow(True)): each pair starts from the flow before it, as in
+        calc_batch."""
+        return self._study(nparr, scale, pad_last, chain=chain)
 
     # ---- the study file's float16 payload, made on the device (reference :400-404 casts on the host at write time) -------------
     def echo_frames(self, nparr):
@@ -376,22 +393,22 @@ class DenseFlow:
         _lib.check(self._L.tf_echo_frames(self._h, nparr.ctypes.data, N, H, W, out.ctypes.data), self._h, "tf_echo_frames")
         return out
 
-    def calc_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True, hold=False):
+    def calc_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True, hold=False, chain=False):
         """calc_study with the flows rounded to float16 by the output kernel: RGB study uint8 [N,H,W,3] -> (flow16, echo16).  flow16 has
         the bits of calc_study(nparr, scale, pad_last).astype(np.float16) -- the study file's `flow` dataset with `scale` = pixel_spacing
         * frame_rate and `pad_last` -- at half the download; echo16 is echo_frames(nparr), made from the same upload, or None.
         `hold`: the payload (all N flow frames, the last one repeated whatever `pad_last`; the echo if made) also stays held on the
         device, as after hold_study of the returned arrays, without being uploaded again; the returned arrays are the same."""
-        return self._study(nparr, scale, pad_last, f16=True, echo=echo, hold=hold)
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, hold=hold, chain=chain)
 
-    def calc_study_saliency_payload(self, nparr, scale=1.0, pad_last=True, echo=True, map_dtype="f32", hold=False):
+    def calc_study_saliency_payload(self, nparr, scale=1.0, pad_last=True, echo=True, map_dtype="f32", hold=False, chain=False):
         """calc_study_saliency with float16 flows, and the `echo` of the RGB frames: -> (flow16, echo16 | None), as calc_study_payload."""
-        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, hold=hold)
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, hold=hold, chain=chain)
 
-    def submit_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True):
+    def submit_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True, chain=False):
         """calc_study_payload without waiting: -> ticket; `wait(ticket)` returns the (flow16, echo16 | None) pair.  The frames are
         conditioned and the echo is complete before this returns (nparr may be reused at once)."""
-        return self._study(nparr, scale, pad_last, f16=True, echo=echo, submit=True)
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, submit=True, chain=chain)
 
     def saliency_frames(self, nparr, dtype=np.float32):
         """cv2.saliency.StaticSaliencyFineGrained_create().computeSaliency(frame)[1] for every frame, on the device (reference
@@ -422,11 +439,11 @@ class DenseFlow:
             return False
         raise OpticalFlowCalculationError(f"saliency map dtype must be float32 ('f32') or uint8 ('u8'), got {dtype!r}")
 
-    def calc_study_saliency(self, nparr, scale=1.0, pad_last=False, map_dtype="f32"):
+    def calc_study_saliency(self, nparr, scale=1.0, pad_last=False, map_dtype="f32", chain=False):
         """RGB study uint8 [N,H,W,3] -> float32 [N-1,H,W,2] with the saliency maps as the solver's frames (no_saliency=False).
         map_dtype "f32" (default): the solver receives computeSaliency()'s CV_32F maps in [0,1], as under opencv-contrib >= 4.5 -- DualTVL1
         multiplies them by 255 in float, DeepFlow takes them as they are; "u8": the 8-bit maps.  `scale` / `pad_last` as in calc_study."""
-        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype)
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, chain=chain)
 
     def clean_masks(self, class_map, class_ids, min_size):
         """The reference's clean_mask (calculate_optical_flow.py:90-111, :113-182) on the device, exact: class map uint8 [N,H,W] ->
@@ -783,26 +800,26 @@ class DenseFlow:
         return flows, bg
 
     # ---- a bkgd_comp="WASE" study in one call: the flows stay on the device between the solve and the compensation -------------
-    def calc_study_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False):
+    def calc_study_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False, chain=False):
         """calc_study, then wase_compensate of its flows, in one device call: RGB study uint8 [N,H,W,3] and bkgd_mask bool [n,H,W,2]
         (mask_dict['bkgd']) -> ((flow - background[p]) * scale float32 [N-1,H,W,2], backgrounds float32 [N-1]), with the bits of
         wase_compensate(calc_study(nparr), bkgd_mask, scale).  `pad_last` as in calc_study."""
-        return self._study(nparr, scale, pad_last, bkgd_mask=bkgd_mask)
+        return self._study(nparr, scale, pad_last, bkgd_mask=bkgd_mask, chain=chain)
 
-    def calc_study_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, hold=False):
+    def calc_study_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, hold=False, chain=False):
         """calc_study_wase with the flows rounded to float16 by the output kernel -> (flow16, echo16 | None, backgrounds): flow16 has
         the bits of calc_study_wase(...)[0].astype(np.float16), echo16 is echo_frames(nparr) from the same upload.  `hold` as in
         calc_study_payload."""
-        return self._study(nparr, scale, pad_last, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold)
+        return self._study(nparr, scale, pad_last, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold, chain=chain)
 
-    def calc_study_saliency_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False, map_dtype="f32"):
+    def calc_study_saliency_wase(self, nparr, bkgd_mask, scale=1.0, pad_last=False, map_dtype="f32", chain=False):
         """calc_study_wase with the saliency maps as the solver's frames (calc_study_saliency) -> (flows float32, backgrounds)."""
-        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, bkgd_mask=bkgd_mask)
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, bkgd_mask=bkgd_mask, chain=chain)
 
-    def calc_study_saliency_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, map_dtype="f32", hold=False):
+    def calc_study_saliency_wase_payload(self, nparr, bkgd_mask, scale=1.0, pad_last=True, echo=True, map_dtype="f32", hold=False, chain=False):
         """calc_study_saliency_wase with float16 flows and the `echo` of the RGB frames -> (flow16, echo16 | None, backgrounds).  `hold`
         as in calc_study_payload."""
-        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold)
+        return self._study(nparr, scale, pad_last, saliency=True, map_dtype=map_dtype, f16=True, echo=echo, bkgd_mask=bkgd_mask, hold=hold, chain=chain)
 
     def calc_pairs(self, I0s, I1s, init=None):
         """B independent pairs: uint8 or float32 [B,H,W] x2 -> float32 [B,H,W,2] (float frames: DualTVL1 scales them by 255 like cv2, DeepFlow
@@ -850,22 +867,25 @@ class DenseFlow:
         self._jobs[t.value] = None
         return t.value
 
-    def submit_batch(self, frames, scale=1.0):
-        """calc_batch without waiting: frames uint8 [N,H,W] -> ticket; `wait(ticket)` returns float32 [N-1,H,W,2]."""
+    def submit_batch(self, frames, scale=1.0, chain=False):
+        """calc_batch without waiting: frames uint8 [N,H,W] -> ticket; `wait(ticket)` returns float32 [N-1,H,W,2].  A chained job is one
+        unit of the lane queue: chains submitted together run side by side, one per lane."""
         frames = _u8_image_stack(frames, "frames", 3)
         N, H, W = frames.shape
         if N < 2:
             raise OpticalFlowCalculationError("need at least 2 frames")
         out = self._out((N - 1, H, W, 2))
         t = C.c_int(-1)
+        if chain:
+            self.chain_next()
         _lib.check(self._L.tf_submit_seq(self._h, frames.ctypes.data, N, H, W, float(scale), out.ctypes.data, C.byref(t)), self._h, "tf_submit_seq")
         self._jobs[t.value] = _Job(out, inputs=(frames,))               # the library reads `frames` and writes `out` until the wait
         return t.value
 
-    def submit_study(self, nparr, scale=1.0, pad_last=False):
+    def submit_study(self, nparr, scale=1.0, pad_last=False, chain=False):
         """calc_study without waiting: RGB study uint8 [N,H,W,3] -> ticket; `wait(ticket)` returns float32 [N-1,H,W,2] (or [N,H,W,2] with
         the last flow repeated, `pad_last`).  The frames are conditioned on the device before this returns (nparr may be reused at once)."""
-        return self._study(nparr, scale, pad_last, submit=True)
+        return self._study(nparr, scale, pad_last, submit=True, chain=chain)
 
     def submit_pairs(self, I0s, I1s):
         """calc_pairs without waiting: uint8 [B,H,W] x2 -> ticket; `wait(ticket)` returns float32 [B,H,W,2]."""
@@ -891,8 +911,11 @@ class DenseFlow:
         self._finish(st)
         return self.last_stats if job is None else self._collect(job)      # (None: the device form, nothing of the host's to hand back)
 
-    def calc_seq_device(self, dframes_ptr, N, H, W, dflow_ptr, scale=1.0):
+    def calc_seq_device(self, dframes_ptr, N, H, W, dflow_ptr, scale=1.0, chain=False):
+        """tf_calc_seq_device: device frames uint8 [N,H,W] -> device float32 [N-1,H,W,2] * scale.  `chain` as in calc_batch."""
         st = _lib.TfStats()
+        if chain:
+            self.chain_next()
         _lib.check(self._L.tf_calc_seq_device(self._h, C.c_void_p(dframes_ptr), int(N), int(H), int(W), float(scale),
                                               C.c_void_p(dflow_ptr), C.byref(st)), self._h, "tf_calc_seq_device")
         self._finish(st)

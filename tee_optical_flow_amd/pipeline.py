@@ -78,19 +78,33 @@ def _compensate(flow, mask_dict, bkgd_comp):
 _saliency_warned = [False]
 
 
+def _check_chain(chain, model=None, OF_algo=None):
+    """chain=True needs DualTVL1 and a model that solves a chained sequence (DenseFlow.device_chain): refused before any work."""
+    if not chain:
+        return
+    if OF_algo == "deepflow" or getattr(model, "algo", None) == "deepflow":
+        raise ConfigurationError("chain=True needs OF_algo='TVL1': DeepFlow takes no initial flow")
+    if model is not None and not getattr(model, "device_chain", False):
+        raise ConfigurationError(f"chain=True: the flow model ({type(model).__name__}) does not solve chained sequences "
+                                 "(DenseFlow with useInitialFlow does)")
+
+
 def flow_for_study(frames_u8, OF_model, mask_dict=None, bkgd_comp="none", conversion_factor=1.0, nparr_rgb=None, saliency=False,
-                   saliency_map="f32"):
+                   saliency_map="f32", chain=False):
     """Reference :584-600 for already-conditioned uint8 frames [N,H,W]: N-1 flows, last one duplicated, scaled.
     All N-1 pairs are solved by ONE batched call (tf_calc_seq); background compensation (per pair) and the unit
     scale are applied in the reference's order: (flow - background) * conversion_factor.
     `saliency=True` is the no_saliency=False branch (:559-560, :586): the frames' fine-grained saliency maps, computed on the
     device from `nparr_rgb`, are what the solver sees -- `saliency_map` "f32" (default): as CV_32F in [0,1], what computeSaliency()
     returns under the reference's opencv-contrib >= 4.5 (DualTVL1 then scales by 255 in float, DeepFlow takes [0,1] frames as they
-    are); "u8": the 8-bit maps (opencv-contrib 3.x).  Parity of the whole branch is UNPINNED (oracle/saliency_oracle.c)."""
-    return _study_solve(OF_model, nparr_rgb, lambda: frames_u8, mask_dict, bkgd_comp, conversion_factor, saliency=saliency, saliency_map=saliency_map)()
+    are); "u8": the 8-bit maps (opencv-contrib 3.x).  Parity of the whole branch is UNPINNED (oracle/saliency_oracle.c).
+    `chain=True`: the video idiom instead of the reference's loop -- every pair starts from the flow of the pair before it (_study_solve)."""
+    return _study_solve(OF_model, nparr_rgb, lambda: frames_u8, mask_dict, bkgd_comp, conversion_factor, saliency=saliency, saliency_map=saliency_map,
+                        chain=chain)()
 
 
-def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency=False, saliency_map="f32", payload=False, echo=False, submit=False):
+def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency=False, saliency_map="f32", payload=False, echo=False, submit=False,
+                 chain=False):
     """The one place that picks a study's call on the model: -> collect, a callable that returns the study's flow array [N,H,W,2], scaled
     by `factor` and the last flow repeated (`payload`: the pair (float16 flow array, float16 echo or None) of the study file).  rgb: the
     study's uint8 RGB frames, or None; gray_frames: () -> the conditioned frames, asked for only where calc_batch is the model's all.
@@ -98,13 +112,25 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
     used where the model has it: it compensates, scales and repeats the last flow itself -- `submit`: as submit_study[_payload], solved
     while the caller goes on, where the model offers that form.  Without it, and never under `payload`: the model's unscaled float32
     cell calc_study[_saliency], or calc_batch on the conditioned frames; then wase_compensate (or numpy's _compensate), the repeat and
-    the scale on the host, in the reference's order (flow - background) * factor."""
+    the scale on the host, in the reference's order (flow - background) * factor.
+    `chain`: the same cell, chained (DenseFlow's chain=True: pair 0 from zero, pair k from pair k-1's flow; about N-1 single-pair solves
+    per study).  The model is used with useInitialFlow set -- set here for the call where it is not, and put back: a submitted job
+    keeps the parameters it was queued with.  DeepFlow, or a model without `device_chain`, raises ConfigurationError."""
+    _check_chain(chain, model)
+    if chain and not model.getUseInitialFlow():
+        model.setUseInitialFlow(True)
+        try:
+            return _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency, saliency_map, payload, echo, submit, True)
+        finally:
+            model.setUseInitialFlow(False)
     if bkgd_comp not in ("WASE", "none"):
         raise OpticalFlowCalculationError(f"bkgd_comp value must be [WASE, none], got {bkgd_comp}!")
     wase = bkgd_comp == "WASE"
     plain = "calc_study_saliency" if saliency else "calc_study"
     cell = plain + ("_wase" if wase else "") + ("_payload" if payload else "")
     kw = {"map_dtype": saliency_map} if saliency else {}
+    ckw = {"chain": True} if chain else {}                       # (a model without the capability never sees the word)
+    kw.update(ckw)
     if saliency and not payload:
         if rgb is None or not hasattr(model, plain):
             raise OpticalFlowCalculationError("no_saliency=False needs the device engine (DenseFlow.calc_study_saliency) and the "
@@ -128,7 +154,7 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
     if rgb is not None and hasattr(model, plain):
         flows = getattr(model, plain)(rgb, **kw)                 # conditioning (:588) or saliency maps (:586) + all pairs on the device
     else:
-        flows = model.calc_batch(gray_frames())                  # float32 [N-1,H,W,2]
+        flows = model.calc_batch(gray_frames(), **ckw)           # float32 [N-1,H,W,2]
     compensates = wase and hasattr(model, "wase_compensate")
     if compensates:                                              # device: O(N^2 H W) products, numpy's summation order kept
         flows, _ = model.wase_compensate(flows, mask_dict["bkgd"], scale=factor)   # (flow - background) * factor
@@ -183,28 +209,31 @@ def _prep_frames(nparr, flipLR):
 def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                   no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                   config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host"):
+                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host", chain=False):
     """Same positional signature as the reference (:478-483).  Keyword-only extras let a caller inject what the
     offline image cannot provide: `nparr` (frames instead of a DICOM), `metadata`, `mask_dict` (segmentation result),
     `flow_model`.  Returns the float32 flow array [N,H,W,2] that was written.  `payload="device"`: the engine hands over the file's
     float16 `flow` and `echo` (DenseFlow.calc_study_payload, or calc_study_wase_payload under bkgd_comp="WASE"; uint8 RGB frames, a model with
     `device_payload` and, for WASE, `device_wase` --
-    otherwise the host path, with one logged reason) and the float16 array that was written is returned; the file is the same."""
+    otherwise the host path, with one logged reason) and the float16 array that was written is returned; the file is the same.
+    `chain=True` (OF_algo="TVL1"): the study's pairs are solved as a chain, each from the flow before it (_study_solve); the file's layout
+    and attributes are those of the plain solve."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
-                                saliency_map=saliency_map, payload=payload)()
+                                saliency_map=saliency_map, payload=payload, chain=chain)()
 
 
 def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                          no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                          config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host"):
+                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host", chain=False):
     """process_video in two halves: everything up to the flow solve, then a callable that collects the flows and does the rest (waveforms,
     hand-over to the HDF5 writer) and returns the flow array.  `_submit` (process_folder): where the engine offers it (gray-frame branch,
     no background compensation, a model the caller holds) the solve is only SUBMITTED here -- DenseFlow.submit_study, tf_submit_seq_rgb --
     so that the next study's solve is on the GPU while this one finishes."""
     _check_payload(payload)
+    _check_chain(chain, flow_model, OF_algo)
     if config is None:
         config = default_optical_flow_config()
     if mode == "otsu":
@@ -257,7 +286,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
         # the echo (from the upload the conditioning / saliency pass reads) only where a file is written
         collect = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
                                conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=from_device,
-                               echo=save_path is not None, submit=_submit and not own)
+                               echo=save_path is not None, submit=_submit and not own, chain=chain)
     finally:
         if own:
             model.close()
@@ -593,7 +622,8 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                    flipLR=False, verbose=True, recalculate=False, no_saliency=True, OF_algo="TVL1", save_mask_subset=None,
                    include_waveforms=False, waveform_folder=None, pixel_spacing=None, frame_rate=None, process_subset=False,
                    file_subset_list=(), *, rank=0, world=1, extensions=("dcm",), reader=read_study, flow_model=None, config=None,
-                   device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host", payload="host"):
+                   device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host", payload="host",
+                   chain=False):
     """Drop-in for the reference's process_folder (:243-290), same positional signature and the same rules:
       * the folder listing is cut into `nchunks` slices of len // nchunks files, this call takes slice `chunk_index`
         (the remainder files are dropped, as the reference does -- SURVEY.md Appendix C.8);
@@ -622,10 +652,13 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     writer stage is a plain copy.  It needs a model with `device_payload`, uint8 RGB frames and, for bkgd_comp="WASE", a model with `device_wase` (such
     studies are solved and compensated by one synchronous call, DenseFlow.calc_study_wase_payload); otherwise the host
     path serves, and the reason is logged once.  The files are the same either way.
+    `chain=True` (OF_algo="TVL1"): every study is solved as a chain (process_video); the walk submits chained studies like plain ones,
+    each one unit of the engine's lanes.
     Returns the list of (filename, error string)."""
     if otsu_masks not in ("host", "device"):
         raise ConfigurationError(f"otsu_masks must be 'host' or 'device', not {otsu_masks!r}")
     _check_payload(payload)
+    _check_chain(chain, flow_model, OF_algo)
     os.makedirs(save_folder, exist_ok=True)
     file_list = sorted(os.listdir(dcm_folder))                      # os.listdir order is arbitrary; sorted = same slices on every rank
     if process_subset:
@@ -654,7 +687,8 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                        prepare_args=(mode, flipLR, config if config is not None else default_optical_flow_config()),
                        video_args=dict(segmentor_model=segmentor_model, verbose=verbose, mode=mode, bkgd_comp=bkgd_comp, flipLR=flipLR,
                                        no_saliency=no_saliency, OF_algo=OF_algo, save_mask_subset=save_mask_subset,
-                                       include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config, payload=payload))
+                                       include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config, payload=payload,
+                                       chain=chain))
     try:
         walk.run()
     finally:

@@ -29,7 +29,9 @@
  * are dropped, the ones running finish, and the call returns the failure with nothing left in flight).
  * tf_submit_* queue the same job without waiting (tf_wait collects it), so that consecutive batches --
  * the studies of a folder, the steps of a stream -- keep the lanes busy across calls.  Flows and
- * tf_get_iters are identical whichever lane solved what.
+ * tf_get_iters are identical whichever lane solved what.  Chained sequences (tf_chain_next) are the
+ * exception to the cutting: a chain is one unit, and several chains of one frame size advance in
+ * lock-step inside one call, cut over time instead (tf_calc_chains).
  * All functions return TF_OK (0) or an error
  * code; tf_last_error() gives the message (the Python layer raises OpticalFlowCalculationError,
  * reference optical_flow/exceptions.py:26-28).
@@ -215,6 +217,37 @@ int tf_calc_pairs_init_device(tf_handle* h, const uint8_t* dI0s, const uint8_t* 
  * -> TF_ERR_UNSUPPORTED; an armed pairs call -> TF_ERR_INVALID_ARG.  Unarmed sequence calls stay refused while the flag is set.
  * tf_dbg_counter(h, "chain_steps"): pairs solved as chain steps. */
 int tf_chain_next(tf_handle* h, int on);
+
+/* Several chained sequences of ONE frame size in lock-step, in one call (DualTVL1, TF_VARIANT_CPU, TF_PARAM_USE_INITIAL_FLOW set; no
+ * tf_chain_next needed).  A chain is sequential in time but independent of the other chains, so step k solves pair k of every chain
+ * still running as ONE batch, through the kernels that solve a batch of independent pairs: every launch, whose cost one pair cannot
+ * fill, carries up to n_chains pairs.  A pair's result does not depend on the batch it is solved in, so chain i gets, bit for bit and
+ * iteration count for iteration count, what a chained tf_calc_seq of its own frames gives.  The chains may differ in length; the
+ * library orders them by length itself (longest first, stable) and hands the results back in the caller's order.
+ *   frames[i]: chain i's gray frames, uint8 [n_frames[i]][H][W]; flows_out[i]: its flows, float32 [n_frames[i]-1][H][W][2] * scale (the
+ *   caller repeats a study's last flow where it wants one).  tf_calc_chains: host pointers; tf_calc_chains_device: device pointers
+ *   (the two pointer arrays themselves are host memory in both).
+ *   tf_calc_chains_rgb: study i as RGB uint8 [n_frames[i]][H][W][3] on the host, conditioned as tf_calc_seq_rgb conditions it; flows to
+ *   host float32, or (out_f16 != 0) float16 as tf_calc_seq_rgb_f16 rounds them; echo16_out (NULL, or one pointer per study, NULL to
+ *   skip one): the study's echo as in that call.
+ * tf_get_iters afterwards: [chain][pair][level][warp][2], chain after chain in the caller's order; tf_stats counts all pairs, and the
+ * "chain_steps" counter grows by them.  One engine solves the whole call: with cap = max_batch pairs per sub-batch, a sub-batch is T
+ * steps of the S chains still running, S * T <= cap; the seeds carry over from one sub-batch to the next on the device.  The call is one
+ * unit of work: it is never split over the lanes (behind submitted jobs it queues as one unit).
+ * Refused before any GPU work, TF_ERR_INVALID_ARG: n_chains < 1, a chain of fewer than 2 frames, a null pointer or array; TF_ERR_UNSUPPORTED:
+ * a DeepFlow or TF_VARIANT_CUDA handle, TF_PARAM_USE_INITIAL_FLOW clear, more chains than one sub-batch holds pairs (n_chains >
+ * max_batch; the message names the limit), images above 2^24 pixels, float16 flows to a device destination, an armed tf_hold_next (a
+ * lock-step call holds nothing).  An armed tf_chain_next or tf_hold_next flag is spent by the call, refused or not; a refused call
+ * queues nothing.  Not offered: submitted (tf_submit_*) lock-step calls, saliency and WASE forms, held payloads.
+ * tf_dbg_chain_order (pure host arithmetic): order_out[s] = the caller's index of the chain the library keeps in state slot s;
+ * first_pair_out[i] (or NULL) = where chain i's pairs start in tf_get_iters' output. */
+int tf_calc_chains(tf_handle* h, const uint8_t* const* frames, const int* n_frames, int n_chains, int H, int W, float scale,
+                   float* const* flows_out, tf_stats* st);
+int tf_calc_chains_device(tf_handle* h, const uint8_t* const* dframes, const int* n_frames, int n_chains, int H, int W, float scale,
+                          float* const* dflows_out, tf_stats* st);
+int tf_calc_chains_rgb(tf_handle* h, const uint8_t* const* rgb, const int* n_frames, int n_chains, int H, int W, float scale, int out_f16,
+                       void* const* flows_out, uint16_t* const* echo16_out, tf_stats* st);
+int tf_dbg_chain_order(const int* n_frames, int n_chains, int* order_out, long long* first_pair_out);
 
 /* Asynchronous forms of tf_calc_pairs_device, tf_calc_seq_device, tf_calc_pairs and tf_calc_seq (the loop calculate_optical_flow.py:584-597 for SEVERAL studies / batches at a time):
  * the job is queued on the handle's lanes and the call returns with a ticket; every buffer must stay valid and untouched until

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "tf_dbg_pyramid", "tf_dbg_resize", "tf_dbg_warp", "tf_dbg_median", "tf_dbg_iterate", "tf_dbg_df_pyramid", "tf_dbg_df_up",
     "tf_calc_seq_rgb_f16", "tf_submit_seq_rgb_f16", "tf_calc_seq_saliency_f16", "tf_echo_frames", "tf_dbg_f16_round",
     "tf_calc_seq_rgb_wase", "tf_calc_seq_saliency_wase",
+    "tf_calc_chains", "tf_calc_chains_device", "tf_calc_chains_rgb", "tf_dbg_chain_order",
     "tf_hold_study", "tf_hold_mask", "tf_hold_next", "tf_held_shape", "tf_release_study", "tf_held_av_centroids", "tf_held_first_region_areas",
     "tf_held_radlong_project_param", "tf_held_polar_project_param", "tf_held_radlong_overlay",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
@@ -154,6 +155,11 @@ def load():
     L.tf_hold_mask.argtypes = [vp, i32, vp, i32, i32]
     L.tf_hold_next.argtypes = [vp, i32]
     L.tf_chain_next.argtypes = [vp, i32]
+    # (the per-chain pointers and frame counts: ctypes arrays of c_void_p / c_int)
+    L.tf_calc_chains.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
+    L.tf_calc_chains_device.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, C.POINTER(TfStats)]
+    L.tf_calc_chains_rgb.argtypes = [vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, C.POINTER(TfStats)]
+    L.tf_dbg_chain_order.argtypes = [vp, i32, vp, vp]
     L.tf_held_shape.argtypes = [vp, C.POINTER(C.c_longlong * HELD_SHAPE_LEN)]
     L.tf_release_study.argtypes = [vp]
     L.tf_held_av_centroids.argtypes = [vp, i32, i32, vp, vp]

@@ -3,6 +3,7 @@
 // adds everything around the solver: the study tail's scratch, the analysis session, RCCL, the lane queue and its tickets.
 // The records an engine is made of are declared here; their functions are next to their solver (teeflow_*_host.hip.h).
 #include <rccl/rccl.h>      // types and prototypes only: librccl is loaded with dlopen when a communicator is first asked for
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -97,6 +98,7 @@ struct Tvl1State {
     PairCtl* ctl = nullptr;
     u64* errs = nullptr; int errstride = 0;
     int* iters_dev = nullptr; size_t iters_cap = 0;
+    const void** chain_src = nullptr; size_t chain_src_cap = 0;     // chains in lock-step: a sub-batch's frame sources (k_chain_gather), grown on demand
     // made with the engine, whatever the geometry (engine_init)
     volatile int* slots_host = nullptr; int* slots_dev = nullptr;   // fine-grained pinned ring (SLOT_RING ints)
     unsigned launch_seq = 0;
@@ -194,6 +196,7 @@ struct tf_handle : Engine {
                                                                                   //   float32 flows, the compensated output in the call's type
            PRE_SG_IN, PRE_SG_IDX, PRE_SG_MAP,                                     // tf_segmentor_input (tables, LUT, frames), tf_segmentor_classmap
            PRE_ECHO,                                                              // the study's float16 `echo` (tf_echo_frames, the *_f16 calls)
+           PRE_CH_GRAY,                                                           // tf_calc_chains_rgb: the conditioned frames of all its studies
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)

@@ -5,6 +5,26 @@
 enum Mode { MODE_PAIRS, MODE_SEQ };
 // where a call's buffers live: bit 0 = the frames are device memory, bit 1 = the flow destination is
 enum { W_HOST = 0, W_IN_DEV = 1, W_OUT_DEV = 2, W_DEV = 3 };
+// Several chained sequences of one frame size solved in lock-step (tf_calc_chains*).  The library's order: by length, longest first,
+// stable -- the chains still running at step k are then the prefix [0, B_k), and state slot s is chain s for the whole call.
+struct ChainSet {
+    std::vector<const uint8_t*> in;      // [s] the chain's frames, [pairs[s] + 1][H][W], where the call's frames live
+    std::vector<void*> out;              // [s] its flows, [pairs[s]][H][W][2] of the call's output type, where the call's flows go
+    std::vector<int> pairs;              // [s] its pairs: never growing with s
+    std::vector<int> order;              // [s] the caller's index of the chain
+    std::vector<size_t> first;           // [s] its first pair's place in the caller's order of all pairs (chain after chain: tf_get_iters)
+    int count() const { return (int)pairs.size(); }
+    int running(int k) const { int n = 0; while (n < count() && pairs[n] > k) ++n; return n; }      // B_k
+};
+// the library's order of chains of n_frames[c] frames each: order[s] = c, by length, longest first, stable
+inline std::vector<int> chain_order(const int* n_frames, int n_chains)
+{
+    std::vector<int> order(n_chains > 0 ? n_chains : 0);
+    for (int c = 0; c < n_chains; ++c) order[c] = c;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n_frames[a] > n_frames[b]; });
+    return order;
+}
+
 // Pair b is frames (in0[b], in1[b]) (MODE_PAIRS) or (in0[b], in0[b+1]) (MODE_SEQ: in1 unused); its flow is H x W x 2 elements of the
 // call's output type -- float32, or float16 (out_f16) -- at out + b * flow_bytes().
 struct Call {
@@ -18,6 +38,8 @@ struct Call {
                                  // frames live (W_IN_DEV); may be `out` itself -- a pair's is read before its flow is written
     bool chain = false;          // useInitialFlow (MODE_SEQ, armed by tf_chain_next): pair 0 starts from zero, pair k from pair k-1's flow as
                                  // the solver left it.  Such a call is ONE unit: one engine solves its sub-batches in order, pair after pair
+    const ChainSet* chains = nullptr;   // (chain) several chains in lock-step: n_pairs is the sum of theirs; in0 and out are the first chain's
+                                 // and the engine reads `chains` instead.  Never submitted: the set lives as long as the synchronous call
     size_t frame_bytes() const { return (size_t)H * W * (f32 ? 4 : 1); }
     size_t flow_bytes() const { return (size_t)H * W * 2 * (out_f16 ? 2 : 4); }      // BYTES of one pair's flow
     Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
@@ -80,6 +102,27 @@ int check_call(Engine* h, const Call& c)
         return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is set and this call carries no initial flow: only tf_calc_pairs_init and "
                                             "tf_calc_pairs_init_device take one (or clear the flag)");
     return validate_params(h, h->P);
+}
+
+// what a solve's stats start from: the call's three phases, its tvl1_iter launches and (tf_set_profile) the profiled launches' times
+int solve_times(Engine* h, tf_stats* st, float ms_h2d, float ms_dev, float ms_d2h)
+{
+    memset(st, 0, sizeof *st);
+    st->ms_h2d = ms_h2d; st->ms_device = ms_dev; st->ms_d2h = ms_d2h;
+    st->iter_launches = h->tally.iter_launches;
+    double ims = 0, warp_ms = 0, median_ms = 0;
+    for (size_t i = 0; i < h->tally.prof_used; ++i) {
+        float t = 0;
+        ProfEv& pe = h->prof_pool[i];
+        HIPC(h, hipEventElapsedTime(&t, pe.a, pe.b));
+        pe.ms = t;
+        if (pe.level == -4) warp_ms += t;
+        else if (pe.level == -5) median_ms += t;
+        else ims += t;
+    }
+    st->iter_ms = ims;
+    st->ms_warp = warp_ms; st->ms_median = median_ms;
+    return TF_OK;
 }
 
 // The engine solves call c, sub-batch after sub-batch.  DualTVL1 writes the executed iteration counts to `iters` (tf_get_iters order).
@@ -186,9 +229,8 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
     }
     if (overlap) HIPC(h, hipStreamSynchronize(h->copy_stream));
     if (st) {
-        memset(st, 0, sizeof *st);
-        st->ms_h2d = ms_h2d; st->ms_device = ms_dev; st->ms_d2h = ms_d2h;
-        st->iter_launches = h->tally.iter_launches;
+        rc = solve_times(h, st, ms_h2d, ms_dev, ms_d2h);
+        if (rc) return rc;
         if (deep) {
             st->total_bytes = df_account_bytes(h) * c.n_pairs; st->iter_bytes = h->tally.df_sor_bytes;
             st->iter_pair_steps = (unsigned long long)h->tally.df_sor_px;     // pixels x pairs summed over the SOR launches
@@ -197,18 +239,82 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
                 account_bytes(h, iters + (size_t)b * per_pair, c.init != nullptr || (c.chain && b > 0), &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
             st->iter_pair_steps = st->inner_iters_total;
         }
-        double ims = 0, warp_ms = 0, median_ms = 0;
-        for (size_t i = 0; i < h->tally.prof_used; ++i) {
-            float t = 0;
-            ProfEv& pe = h->prof_pool[i];
-            HIPC(h, hipEventElapsedTime(&t, pe.a, pe.b));
-            pe.ms = t;
-            if (pe.level == -4) warp_ms += t;
-            else if (pe.level == -5) median_ms += t;
-            else ims += t;
+    }
+    return TF_OK;
+}
+
+// Chains in lock-step (Call::chains): this engine solves the whole call, sub-batch after sub-batch over TIME.  With cap = tv.cap -- 2 cap
+// frame slots, cap iteration slices and cap staged flows -- a sub-batch is T steps of the S chains still running at its first step,
+// S T <= cap (so S (T + 1) <= 2 cap); its last frame row is the next one's first, and the seeds carry over in the state slots.  Host
+// frames are uploaded chain by chain; the flows are staged time-major and copied to each chain's own destination, the iteration counts
+// scattered to the caller's order (`iters`: chain after chain).  In-order copies on the solve stream, whatever the destination.
+int calc_chains_common(Engine* h, const Call& c, int* iters, tf_stats* st)
+{
+    const ChainSet& cs = *c.chains;
+    HIPC(h, hipSetDevice(h->dev));
+    int rc = h->tv.ensure(h, c.H, c.W, c.n_pairs);
+    if (rc) return rc;
+    const int cap = h->tv.cap;
+    if (cs.count() > cap) return fail(h, TF_ERR_UNSUPPORTED, "%d chains in lock-step, and one sub-batch holds %d", cs.count(), cap);   // (check_chains has refused it)
+    const size_t fpx = c.frame_bytes(), flb = c.flow_bytes(), per_pair = (size_t)h->tv.nlev * h->P.warps * 2;
+    const bool in_dev = c.where & W_IN_DEV, out_dev = c.where & W_OUT_DEV;
+    h->tally = {};
+    float ms_h2d = 0, ms_dev = 0, ms_d2h = 0;
+    rc = ensure_staging(h, in_dev ? 0 : 2 * (size_t)cap * fpx, (size_t)cap * flb);
+    if (rc) return rc;
+    if (h->tv.chain_src_cap < 2 * (size_t)cap) {
+        HIPC(h, hipStreamSynchronize(h->stream));
+        dev_free(h->tv.chain_src); h->tv.chain_src_cap = 0;
+        HIPC(h, hipMalloc(&h->tv.chain_src, 2 * (size_t)cap * sizeof(void*)));
+        h->tv.chain_src_cap = 2 * (size_t)cap;
+    }
+    std::vector<const void*> src;                            // (read by an upload: rewritten only after the stream has been waited for)
+    std::vector<int> Bk, got((size_t)cap * per_pair);
+    for (int k0 = 0; k0 < cs.pairs[0];) {
+        const int S = cs.running(k0), T = std::min(cap / S, cs.pairs[0] - k0);
+        src.assign((size_t)(T + 1) * S, nullptr);
+        Bk.assign(T, 0);
+        HIPC(h, hipEventRecord(h->ev[0], h->stream));
+        size_t up = 0;                                       // bytes of the frame staging in use: at most S (T + 1) frames
+        for (int s = 0; s < S; ++s) {
+            const int steps = std::min(cs.pairs[s], k0 + T) - k0;          // of chain s in this sub-batch: frames k0 .. k0 + steps
+            const uint8_t* fr = cs.in[s] + (size_t)k0 * fpx;
+            if (!in_dev) {
+                HIPC(h, hipMemcpyAsync(h->st_u8 + up, fr, (size_t)(steps + 1) * fpx, hipMemcpyHostToDevice, h->stream));
+                fr = h->st_u8 + up; up += (size_t)(steps + 1) * fpx;
+            }
+            for (int t = 0; t <= steps; ++t) src[(size_t)t * S + s] = fr + (size_t)t * fpx;
+            for (int k = 0; k < steps; ++k) ++Bk[k];
         }
-        st->iter_ms = ims;
-        st->ms_warp = warp_ms; st->ms_median = median_ms;
+        HIPC(h, hipMemcpyAsync(h->tv.chain_src, src.data(), src.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipEventRecord(h->ev[1], h->stream));
+        rc = solve_chains_resident(h, h->tv.chain_src, c.f32, S, T, Bk.data(), c.scale, h->st_flow, c.out_f16, k0 > 0);
+        if (rc) return rc;
+        HIPC(h, hipEventRecord(h->ev[2], h->stream));
+        const hipMemcpyKind kind = out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        for (int s = 0; s < S; ++s) {                        // one strided copy per chain: its flows are every S-th of the staged ones
+            const int steps = std::min(cs.pairs[s], k0 + T) - k0;
+            HIPC(h, hipMemcpy2DAsync((uint8_t*)cs.out[s] + (size_t)k0 * flb, flb, h->st_flow + (size_t)s * flb, (size_t)S * flb, flb, steps, kind, h->stream));
+        }
+        HIPC(h, hipMemcpyAsync(got.data(), h->tv.iters_dev, (size_t)T * S * per_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipEventRecord(h->ev[3], h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        for (int k = 0; k < T; ++k)
+            for (int s = 0; s < Bk[k]; ++s)
+                memcpy(iters + (cs.first[s] + (size_t)(k0 + k)) * per_pair, got.data() + ((size_t)k * S + s) * per_pair, per_pair * sizeof(int));
+        float t;
+        HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1])); ms_h2d += t;
+        HIPC(h, hipEventElapsedTime(&t, h->ev[1], h->ev[2])); ms_dev += t;
+        HIPC(h, hipEventElapsedTime(&t, h->ev[2], h->ev[3])); ms_d2h += t;
+        k0 += T;
+    }
+    if (st) {
+        rc = solve_times(h, st, ms_h2d, ms_dev, ms_d2h);
+        if (rc) return rc;
+        for (int s = 0; s < cs.count(); ++s)
+            for (int k = 0; k < cs.pairs[s]; ++k)
+                account_bytes(h, iters + (cs.first[s] + (size_t)k) * per_pair, k > 0, &st->iter_bytes, &st->total_bytes, &st->inner_iters_total, &st->outer_iters_total);
+        st->iter_pair_steps = st->inner_iters_total;
     }
     return TF_OK;
 }
@@ -294,7 +400,7 @@ void merge_stats(tf_stats* st, const tf_stats& sb)
 // copy into flow_out on the copy stream, kernels writing the caller's device buffer): drain every stream of the engine.
 int calc_common_guarded(Engine* h, const Call& c, int* iters, tf_stats* st)
 {
-    const int rc = calc_common(h, c, iters, st);
+    const int rc = c.chains ? calc_chains_common(h, c, iters, st) : calc_common(h, c, iters, st);
     if (rc != TF_OK) {
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
@@ -503,8 +609,9 @@ int start_call(tf_handle* h, const Call& c, QJob* j, bool submitted)
     const bool can_queue = queue_lane_count(h) > 0 && h->stream == h->own_stream;
     bool busy = submitted;                                   // (a submitted job is cut like a call behind others: balance = false, parts = 0)
     if (can_queue && h->pool && !busy) { std::lock_guard<std::mutex> lk(h->pool->m); busy = h->pool->outstanding > 0; }
-    // (a chain is never split: idle and within one sub-batch the handle solves it, otherwise it is one unit of the queue)
-    const int parts = !busy && c.n_pairs <= sub_batch_pairs(h) ? (c.chain ? 1 : split_count(h, c.n_pairs)) : 0;
+    // (a chain is never split: idle and within one sub-batch the handle solves it, otherwise it is one unit of the queue; chains in
+    // lock-step, whose sub-batches are cut over time, are the handle's whenever it is idle, and one unit of the queue behind submitted jobs)
+    const int parts = !busy && (c.chains || c.n_pairs <= sub_batch_pairs(h)) ? (c.chain ? 1 : split_count(h, c.n_pairs)) : 0;
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
     Geom lv[DF_MAXLEV];                                      // (the pyramid calc_common will build: stats, tf_get_iters)
     j->call = c;

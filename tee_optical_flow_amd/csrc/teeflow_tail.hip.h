@@ -1206,6 +1206,34 @@ TF_API int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H,
 {
     return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, true, flow16_out, echo16_out}, nullptr, ticket, true);
 }
+// Several RGB studies of one frame size as chains in lock-step (teeflow.hip, check_chains): each study is conditioned as tf_calc_seq_rgb
+// conditions it, one after the other into one scratch slot that holds all their gray frames; its echo, where asked for, comes from the same
+// upload.  The flags are spent first, the arguments checked on the host pointers before anything is uploaded.
+TF_API int tf_calc_chains_rgb(tf_handle* h, const uint8_t* const* rgb, const int* n_frames, int n_chains, int H, int W, float scale, int out_f16,
+                              void* const* flows_out, uint16_t* const* echo16_out, tf_stats* st)
+{
+    const bool hold = spend_flags(h);
+    auto run = [&]() -> int {
+        ChainSet cs; Call c;
+        int rc = check_chains(h, (const void* const*)rgb, n_frames, n_chains, H, W, scale, flows_out, W_HOST, out_f16 != 0, hold, &cs, &c);
+        if (rc) return rc;
+        HIPC(h, hipSetDevice(h->dev));                        // (the scratch below is this handle's device's, whatever the thread's current one)
+        const size_t npx = (size_t)H * W;
+        Pre pre(h);
+        uint8_t* at = pre.get<uint8_t>(tf_handle::PRE_CH_GRAY, ((size_t)c.n_pairs + (size_t)n_chains) * npx);
+        if (pre.rc) return pre.rc;
+        for (int s = 0; s < cs.count(); ++s) {
+            const int N = cs.pairs[s] + 1;
+            const uint8_t* dgray = nullptr;
+            rc = condition_to_device(h, cs.in[s], N, H, W, &dgray, at, echo16_out ? echo16_out[cs.order[s]] : nullptr);
+            if (rc) return rc;
+            cs.in[s] = dgray; at += (size_t)N * npx;
+        }
+        c.in0 = cs.in[0]; c.where = W_IN_DEV;
+        return run_chains(h, c, st);
+    };
+    return finish_host_call(h, run());
+}
 TF_API int tf_calc_seq_saliency(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, float scale, float* flow_out, tf_stats* st)
 {
     return study_call(h, {frames, N, H, W, channels, FR_SAL_U8, scale, false, flow_out, nullptr}, st);

@@ -48,8 +48,8 @@ void Tvl1State::release()
     for (int l = 0; l < MAXLEV; ++l) { dev_free(pyr[l]); dev_free(gxl[l]); dev_free(gyl[l]); }
     dev_free(cwx); dev_free(cwy); dev_free(crho);
     for (int k = 0; k < 2; ++k) { dev_free(sb.u1[k]); dev_free(sb.u2[k]); dev_free(sb.p11[k]); dev_free(sb.p12[k]); dev_free(sb.p21[k]); dev_free(sb.p22[k]); }
-    dev_free(ctl); dev_free(errs); dev_free(iters_dev);
-    H = W = cap = nlev = 0; iters_cap = 0;
+    dev_free(ctl); dev_free(errs); dev_free(iters_dev); dev_free(chain_src);
+    H = W = cap = nlev = 0; iters_cap = 0; chain_src_cap = 0;
 }
 
 // buffers for B pairs (at most a sub-batch) of H x W frames under the engine's current parameters; kept while they fit
@@ -272,14 +272,11 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_de
     return TF_OK;
 }
 
-// frames[F][H][W] in device memory (uint8, or float32 in [0,1] when f32) -> their pyramids (and, TF_VARIANT_CUDA, the gradients)
-void build_pyramids(Engine* h, const uint8_t* dframes, bool f32, int F)
+// level 0 of F frame slots -> the levels below it (and, TF_VARIANT_CUDA, the gradients)
+void pyramids_below_level0(Engine* h, int F)
 {
     const tf_params& P = h->P;
     hipStream_t s = h->stream;
-    const Geom g0 = h->tv.lv[0];
-    if (f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->tv.pyr[0], g0, 1);
-    else hipLaunchKernelGGL(k_u8_to_f32, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, dframes, h->tv.pyr[0], g0);
     for (int l = 1; l < h->tv.nlev; ++l) {
         const double sc = 1.0 / P.scale_step;   // resize(src, Size(), fx, fy): scale = 1/fx
         hipLaunchKernelGGL(k_pyr_down, grid64x4(h->tv.lv[l], F), dim3(256), 0, s, h->tv.pyr[l - 1], h->tv.lv[l - 1], h->tv.pyr[l], h->tv.lv[l], sc, sc,
@@ -290,12 +287,24 @@ void build_pyramids(Engine* h, const uint8_t* dframes, bool f32, int F)
             hipLaunchKernelGGL(k_grad, grid64x4(h->tv.lv[l], F), dim3(256), 0, s, h->tv.pyr[l], h->tv.gxl[l], h->tv.gyl[l], h->tv.lv[l]);
 }
 
+// frames[F][H][W] in device memory (uint8, or float32 in [0,1] when f32) -> their pyramids
+void build_pyramids(Engine* h, const uint8_t* dframes, bool f32, int F)
+{
+    hipStream_t s = h->stream;
+    const Geom g0 = h->tv.lv[0];
+    if (f32) hipLaunchKernelGGL(k_f32_to_level0, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, (const float*)dframes, h->tv.pyr[0], g0, 1);
+    else hipLaunchKernelGGL(k_u8_to_f32, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, s, dframes, h->tv.pyr[0], g0);
+    pyramids_below_level0(h, F);
+}
+
 // Where a solve's level-0 initial flow comes from (useInitialFlow): nowhere (start from zero), the caller's interleaved flows, or -- a
-// chained sequence, one pair -- the state planes of slot 0 as the pair solved there before has left them.
+// chain step -- the state planes of the pair's own slot as the pair solved there before has left them (a single chain: slot 0; chains in
+// lock-step: slot s is chain s for the whole call).
 enum Seed { SEED_ZERO, SEED_FLOWS, SEED_STATE };
 
 // Solve B pairs of the pyramids build_pyramids has made, pair b = frames (off0+b, off1+b), in state slots [0,B): the seed, the level /
-// warp stages, the output.  dinit (SEED_FLOWS): device float32 [B][H][W][2] in pixels per frame.  SEED_STATE: B == 1.  The executed
+// warp stages, the output.  dinit (SEED_FLOWS): device float32 [B][H][W][2] in pixels per frame.  SEED_STATE: every slot of [0,B) holds
+// the pair solved there before, untouched since; slots >= B are neither read nor written.  The executed
 // iteration counts go to iters_dev[b], the flows, times `scale`, to dflow[b].
 int solve_pairs(Engine* h, int B, int off0, int off1, Seed seed, const float* dinit, int* iters_dev, float scale, void* dflow, bool out_f16)
 {
@@ -312,11 +321,11 @@ int solve_pairs(Engine* h, int B, int off0, int off1, Seed seed, const float* di
                                       1.0 / P.scale_step, (float)P.scale_step);
         else if (seed == SEED_FLOWS) hipLaunchKernelGGL(k_init_split, grid64x4(g0, B), dim3(256), 0, s, dinit, h->tv.sb, L & 1, g0);
     };
-    // A chain step's level 0 is the last pair's flow, in the buffer that pair's ctl names: k_chain_seed reads ctl before k_ctl_set
-    // resets it.  With one level that flow is itself what the first stage reads, in buffer 0: the memsets, which would clear it, are left
-    // out, and the kernel clears the row padding in their place.
+    // A chain step's level 0 is the slot's last pair's flow, in the buffer that pair's ctl names (slot by slot: it depends on the
+    // iterations the pair executed): k_chain_seed reads ctl before k_ctl_set resets it.  With one level that flow is itself what the first
+    // stage reads, in buffer 0: the memsets, which would clear it, are left out, and the kernel clears the row padding in their place.
     if (seed == SEED_STATE)
-        hipLaunchKernelGGL(k_chain_seed, dim3((g0.pitch + 63) / 64, (g0.h + 3) / 4, 1), dim3(256), 0, s, h->tv.sb, h->tv.ctl, L & 1, g0, L == 0 ? 1 : 0);
+        hipLaunchKernelGGL(k_chain_seed, dim3((g0.pitch + 63) / 64, (g0.h + 3) / 4, B), dim3(256), 0, s, h->tv.sb, h->tv.ctl, L & 1, g0, L == 0 ? 1 : 0);
     hipLaunchKernelGGL(k_ctl_set, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.ctl, B, 0);
     if (seed != SEED_ZERO) for (int l = 0; l < L; ++l) seed_step(l);
     if (!(seed == SEED_STATE && L == 0)) {
@@ -367,6 +376,30 @@ int solve_chain_resident(Engine* h, const uint8_t* dframes, bool f32, int B, flo
                                    (uint8_t*)dflow + (size_t)k * flb, out_f16);
         if (rc) return rc;
         ++h->tally.chain_steps;
+    }
+    return TF_OK;
+}
+
+// Chains in lock-step (tf_calc_chains*): a sub-batch of T steps of up to S chains of one frame size.  dsrc: device table of (T+1) * S
+// frame sources, time-major -- row t holds frame t of every chain, null where a chain has ended (k_chain_gather).  Step k solves the
+// pairs (k * S + s, (k+1) * S + s) of the chains still running, s in [0, Bk[k]) -- the chains are ordered longest first, so those are a
+// prefix and Bk never grows -- as one batch through solve_pairs, every pair seeded by the flow its own slot holds (step 0 of the call:
+// from zero; `carry`: this sub-batch continues the one before, whose state nothing has written since).  A pair's solve does not depend
+// on the batch it is in, so chain s gets what a chain of its own would.  Iteration counts go to iters_dev, flows to dflow, both
+// time-major with S slots per step; the slots of ended chains stay unwritten.
+int solve_chains_resident(Engine* h, const void* const* dsrc, bool f32, int S, int T, const int* Bk, float scale, void* dflow, bool out_f16, bool carry)
+{
+    const Geom g0 = h->tv.lv[0];
+    const int F = (T + 1) * S;
+    hipLaunchKernelGGL(k_chain_gather, dim3((g0.w + 255) / 256, g0.h, F), dim3(256), 0, h->stream, dsrc, f32 ? 1 : 0, h->tv.pyr[0], g0);
+    pyramids_below_level0(h, F);
+    const size_t per_pair = (size_t)h->tv.nlev * h->P.warps * 2;
+    const size_t flb = (size_t)h->tv.H * h->tv.W * 2 * (out_f16 ? sizeof(uint16_t) : sizeof(float));
+    for (int k = 0; k < T; ++k) {
+        const int rc = solve_pairs(h, Bk[k], k * S, (k + 1) * S, k > 0 || carry ? SEED_STATE : SEED_ZERO, nullptr,
+                                   h->tv.iters_dev + (size_t)k * S * per_pair, scale, (uint8_t*)dflow + (size_t)k * S * flb, out_f16);
+        if (rc) return rc;
+        h->tally.chain_steps += Bk[k];
     }
     return TF_OK;
 }

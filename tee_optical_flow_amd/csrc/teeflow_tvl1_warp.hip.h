@@ -1,5 +1,5 @@
 // teeflow_tvl1_warp.hip.h -- DualTVL1's flow upsample, the initial flow's way down the pyramid, and the warp stage (k_flow_up; k_init_split,
-// k_init_down, k_chain_seed; k_warp, k_warp_lds; k_grad and k_warp_cuda for TF_VARIANT_CUDA); included by teeflow_kernels.hip.h, which holds the types, helpers and arithmetic contract
+// k_init_down, k_chain_seed, k_chain_gather; k_warp, k_warp_lds; k_grad and k_warp_cuda for TF_VARIANT_CUDA); included by teeflow_kernels.hip.h, which holds the types, helpers and arithmetic contract
 #pragma once
 
 // flow: coarse level -> next finer level, times 1/scaleStep (resize + multiply of DualTVL1::calc)
@@ -42,24 +42,41 @@ __global__ __launch_bounds__(256) void k_init_down(StateBufs sb, int k, Geom gs,
     sb.u2[k ^ 1][di] = resize_px(sb.u2[k] + (size_t)b * gs.splane, gs.w, gs.h, gs.pitch, dx, dy, scale, scale) * mul;
 }
 
-// A chained sequence: pair 0's finished level-0 flow (slot 0, u buffer ctl[0].ubase -- which one depends on the iterations it executed,
-// so only the device knows) becomes the next pair's initial flow, level 0 of the chain above, which k_init_down expects in u buffer `k`:
-// kept where it is, or moved.  `pad` (a one-level solve, where this level is the one the first stage reads and the host's memsets,
-// which would clear it, are left out): the row padding x in [w, pitch) of buffer `k` is cleared, as those memsets leave it.  Reads
-// ctl[0] and never writes it: k_ctl_set follows.  One thread per (x < pitch, y < h); one pair.
+// A chained sequence: the finished level-0 flow of the pair solved last in state slot b (u buffer ctl[b].ubase -- which one depends on
+// the iterations that pair executed, so only the device knows, and it differs from slot to slot) becomes the initial flow of the slot's
+// next pair, level 0 of the chain above, which k_init_down expects in u buffer `k`: kept where it is, or moved, each slot in its own
+// plane.  `pad` (a one-level solve, where this level is the one the first stage reads and the host's memsets, which would clear it, are
+// left out): the row padding x in [w, pitch) of buffer `k` is cleared, as those memsets leave it.  Reads ctl[b] and never writes it:
+// k_ctl_set follows.  One thread per (x < pitch, y < h) and slot blockIdx.z: one slot for a single chain, the step's active slots
+// [0, B) for chains in lock-step; slots beyond the grid are not touched.
 __global__ __launch_bounds__(256) void k_chain_seed(StateBufs sb, const PairCtl* __restrict__ ctl, int k, Geom g, int pad)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
     if (x >= g.pitch || y >= g.h) return;
-    const size_t i = (size_t)y * g.pitch + x;
+    const size_t i = (size_t)b * g.splane + (size_t)y * g.pitch + x;
     if (x >= g.w) {
         if (pad) { sb.u1[k][i] = 0.f; sb.u2[k][i] = 0.f; }
         return;
     }
-    const int uc = ctl[0].ubase & 1;
+    const int uc = ctl[b].ubase & 1;
     if (uc == k) return;
     sb.u1[k][i] = sb.u1[uc][i];
     sb.u2[k][i] = sb.u2[uc][i];
+}
+
+// Chains in lock-step: level 0 of the pyramid, time-major.  Frame slot f = t * S + s holds frame t of chain s, so that a step's pairs
+// are consecutive slots (WarpArgs' off0 + b, off1 + b).  src[f] is that frame, dense [H][W] in device memory -- uint8
+// (k_u8_to_f32's conversion), or float32 in [0,1] when f32 (k_f32_to_level0's, times 255) -- or null where chain s has no frame t:
+// that slot is cleared, so that the pyramid kernels, which sweep every slot, read finite values there.
+__global__ __launch_bounds__(256) void k_chain_gather(const void* const* __restrict__ src, int f32, float* __restrict__ dst, Geom g)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
+    if (x >= g.w) return;
+    const void* p = src[f];
+    const size_t si = (size_t)y * g.w + x;
+    float v = 0.f;
+    if (p) v = f32 ? static_cast<const float*>(p)[si] * 255.0f : (float)static_cast<const uint8_t*>(p)[si];
+    dst[(size_t)f * g.plane + (size_t)y * g.pitch + x] = v;
 }
 
 // ---------------------------------------------------------------------------------------------

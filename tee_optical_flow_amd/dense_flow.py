@@ -29,6 +29,23 @@ def _u8_image_stack(a, name, ndim, allow_f32=False):
     return np.ascontiguousarray(a)
 
 
+def _chain_stacks(stacks, name, ndim):
+    """The arrays of a lock-step call (calc_chains & co.): a non-empty list of uint8 arrays of `ndim` dimensions -- [N,H,W] frames, or
+    [N,H,W,3] RGB studies -- each of N >= 2 frames, all of one frame size -> (C-contiguous arrays, H, W)"""
+    if isinstance(stacks, np.ndarray) or not isinstance(stacks, (list, tuple)) or len(stacks) < 1:
+        raise OpticalFlowCalculationError(f"{name} must be a non-empty list of arrays, one per chain")
+    out = [_u8_image_stack(a, f"{name}[{i}]", ndim) for i, a in enumerate(stacks)]
+    for i, a in enumerate(out):
+        if a.shape[0] < 2:
+            raise OpticalFlowCalculationError(f"{name}[{i}] has {a.shape[0]} frame(s): a chain needs at least 2 frames")
+        if ndim == 4 and a.shape[3] != 3:
+            raise OpticalFlowCalculationError(f"{name}[{i}] must be [N,H,W,3], got {a.shape}")
+        if a.shape[1:] != out[0].shape[1:] or min(a.shape) < 1:
+            raise OpticalFlowCalculationError(f"chains in lock-step need one frame size: {name}[{i}] is {a.shape[1:3]}, {name}[0] is "
+                                              f"{out[0].shape[1:3]}")
+    return out, out[0].shape[1], out[0].shape[2]
+
+
 def _mask_stack(a, name):
     """bool or uint8 [N,H,W,C], C = 1 or 2, as C-contiguous uint8 (a bool array is viewed, not copied)"""
     a = np.asarray(a)
@@ -124,6 +141,7 @@ class DenseFlow:
     device_unit_scale = True        # calc_study(scale=, pad_last=) applies the unit scale in the output kernel (pipeline.flow_for_study)
     device_payload = True           # calc_study_payload & co. hand over the study file's float16 `flow` and `echo` (process_folder(payload="device"))
     device_chain = True             # calc_batch, calc_seq_device, submit_batch and every study form take chain=True (after setUseInitialFlow(True))
+    device_chains = True            # calc_chains, calc_chains_device and calc_study_chains{,_payload} solve several chains of one frame size in lock-step
     device_wase = True              # calc_study_wase & co. solve and compensate a bkgd_comp="WASE" study in one call, float32 or float16
 
     _SETTERS = {"Tau": "tau", "Lambda": "lambda", "Theta": "theta", "ScalesNumber": "nscales",
@@ -225,17 +243,22 @@ class DenseFlow:
         saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels)."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
-    def _finish(self, st):
+    def _finish(self, st, chain_pairs=None):
         self.last_stats = st.as_dict()
+        self._last_chain_pairs = chain_pairs               # a lock-step call: the pairs of each chain, in the caller's order
 
     def last_iters(self):
-        """Executed (inner, outer) iteration counts of the last call: int32 [pairs, levels, warps, 2]."""
+        """Executed (inner, outer) iteration counts of the last call: int32 [pairs, levels, warps, 2]; after a lock-step call
+        (calc_chains & co.) a list of such arrays, one per chain in the order the chains were passed."""
         s = self.last_stats
         n = s["n_pairs"] * s["nscales_used"] * s["warps"] * 2
         out = np.zeros(n, np.int32)
         w = C.c_size_t()
         _lib.check(self._L.tf_get_iters(self._h, out.ctypes.data_as(C.c_void_p), n, C.byref(w)), self._h, "tf_get_iters")
-        return out.reshape(s["n_pairs"], s["nscales_used"], s["warps"], 2)
+        out = out.reshape(s["n_pairs"], s["nscales_used"], s["warps"], 2)
+        if getattr(self, "_last_chain_pairs", None):
+            return np.split(out, np.cumsum(self._last_chain_pairs)[:-1])
+        return out
 
     # ---- cv2 protocol --------------------------------------------------------------------------
     def _initial_flows(self, init, shape, name):
@@ -300,6 +323,57 @@ class DenseFlow:
                    self._h, "tf_calc_seq")
         self._finish(st)
         return out
+
+    # ---- several chains of one frame size in lock-step (include/teeflow.h, tf_calc_chains): step k solves pair k of every chain still
+    # running as one batch.  After setUseInitialFlow(True), like chain=True; last_iters() then returns one array per chain ---------------
+    def _chains_call(self, fn, srcs, n_frames, H, W, own, dsts):
+        """one lock-step call: the per-chain pointer arrays, the C function `fn`, its own arguments between the sizes and the outputs"""
+        S = len(srcs)
+        st = _lib.TfStats()
+        ptrs = lambda ps: (C.c_void_p * S)(*ps)
+        _lib.check(getattr(self._L, fn)(self._h, ptrs(srcs), (C.c_int * S)(*n_frames), S, int(H), int(W), *own, *(ptrs(d) if d is not None else None for d in dsts),
+                                        C.byref(st)), self._h, fn)
+        self._finish(st, [int(n) - 1 for n in n_frames])
+
+    def calc_chains(self, list_of_frames, scale=1.0):
+        """A list of uint8 [N_s,H,W] frame stacks of one H x W (the N_s may differ) -> a list of float32 [N_s-1,H,W,2]: each what
+        calc_batch(frames, scale, chain=True) gives for it, bits and iteration counts, but solved together -- step k solves pair k of
+        every chain that still has one as a single batch, so the launches that one pair cannot fill carry one pair per chain.  At most
+        max_batch chains per call."""
+        frs, H, W = _chain_stacks(list_of_frames, "list_of_frames", 3)
+        outs = [self._out((len(f) - 1, H, W, 2)) for f in frs]
+        self._chains_call("tf_calc_chains", [f.ctypes.data for f in frs], [len(f) for f in frs], H, W, (float(scale),), ([o.ctypes.data for o in outs],))
+        return outs
+
+    def calc_chains_device(self, dframes_ptrs, n_frames, H, W, dflow_ptrs, scale=1.0):
+        """tf_calc_chains_device: calc_chains on raw device pointers, one per chain -- frames uint8 [n_frames[s],H,W], flows float32
+        [n_frames[s]-1,H,W,2] * scale, written where dflow_ptrs[s] points."""
+        if len(dframes_ptrs) < 1 or not len(dframes_ptrs) == len(n_frames) == len(dflow_ptrs):
+            raise OpticalFlowCalculationError("calc_chains_device needs one frame pointer, frame count and flow pointer per chain, at least one chain")
+        if min(int(n) for n in n_frames) < 2:
+            raise OpticalFlowCalculationError("a chain needs at least 2 frames")
+        self._chains_call("tf_calc_chains_device", list(dframes_ptrs), list(n_frames), H, W, (float(scale),), (list(dflow_ptrs),))
+        return self.last_stats
+
+    def _study_chains(self, list_of_rgb, scale, pad_last, f16, echo):
+        studies, H, W = _chain_stacks(list_of_rgb, "list_of_rgb", 4)
+        ns = [len(s) for s in studies]
+        outs = [self._pool.empty((n if pad_last else n - 1, H, W, 2), np.float16 if f16 else np.float32) for n in ns]
+        echos = [self._pool.empty((n, H, W), np.float16) for n in ns] if echo else None
+        self._chains_call("tf_calc_chains_rgb", [s.ctypes.data for s in studies], ns, H, W, (float(scale), int(f16)),
+                          ([o.ctypes.data for o in outs], [e.ctypes.data for e in echos] if echo else None))
+        jobs = [_Job(o, n if pad_last else 0, ((echos[i] if echo else None,) if f16 else ())) for i, (o, n) in enumerate(zip(outs, ns))]
+        return [self._collect(j) for j in jobs]
+
+    def calc_study_chains(self, list_of_rgb, scale=1.0, pad_last=False):
+        """A list of RGB studies uint8 [N_s,H,W,3] of one H x W -> a list of float32 arrays, each what calc_study(study, scale, pad_last,
+        chain=True) gives for it: the studies' chains are solved in lock-step (calc_chains)."""
+        return self._study_chains(list_of_rgb, scale, pad_last, False, False)
+
+    def calc_study_chains_payload(self, list_of_rgb, scale=1.0, pad_last=True, echo=True):
+        """calc_study_chains with the study file's float16 payload: -> a list of (flow16, echo16 | None), each what
+        calc_study_payload(study, scale, pad_last, echo, chain=True) gives for it.  Holds nothing on the device."""
+        return self._study_chains(list_of_rgb, scale, pad_last, True, echo)
 
     def condition_frames(self, nparr):
         """Device version of frames.condition_frames: uint8 [N,H,W,3] -> uint8 [N,H,W] = img2uint8(rgb2gray(frame)) per frame."""

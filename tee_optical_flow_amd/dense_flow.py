@@ -140,7 +140,7 @@ class DenseFlow:
 
     device_unit_scale = True        # calc_study(scale=, pad_last=) applies the unit scale in the output kernel (pipeline.flow_for_study)
     device_payload = True           # calc_study_payload & co. hand over the study file's float16 `flow` and `echo` (process_folder(payload="device"))
-    device_chain = True             # calc_batch, calc_seq_device, submit_batch and every study form take chain=True (after setUseInitialFlow(True))
+    device_chain = True             # calc_batch, calc_seq_device, submit_batch, submit_seq_device and every study form take chain=True (after setUseInitialFlow(True))
     device_chains = True            # calc_chains, calc_chains_device and calc_study_chains{,_payload} solve several chains of one frame size in lock-step
     device_wase = True              # calc_study_wase & co. solve and compensate a bkgd_comp="WASE" study in one call, float32 or float16
 
@@ -938,6 +938,17 @@ class DenseFlow:
         t = C.c_int(-1)
         _lib.check(self._L.tf_submit_pairs_device(self._h, C.c_void_p(dI0s_ptr), C.c_void_p(dI1s_ptr), int(B), int(H), int(W), float(scale),
                                                   C.c_void_p(dflow_ptr), C.byref(t)), self._h, "tf_submit_pairs_device")
+        self._jobs[t.value] = None
+        return t.value
+
+    def submit_seq_device(self, dframes_ptr, N, H, W, dflow_ptr, scale=1.0, chain=False):
+        """tf_submit_seq_device: calc_seq_device without waiting -- device frames uint8 [N,H,W], device float32 [N-1,H,W,2] * scale -> ticket;
+        `wait(ticket)` returns its statistics.  The device buffers must stay untouched until then.  `chain` as in calc_batch."""
+        t = C.c_int(-1)
+        if chain:
+            self.chain_next()
+        _lib.check(self._L.tf_submit_seq_device(self._h, C.c_void_p(dframes_ptr), int(N), int(H), int(W), float(scale), C.c_void_p(dflow_ptr),
+                                                C.byref(t)), self._h, "tf_submit_seq_device")
         self._jobs[t.value] = None
         return t.value
 

@@ -54,7 +54,8 @@ extern "C" {
                               tf_clean_masks, tf_av_centroids, tf_radlong_project_param, tf_polar_project_param, tf_otsu_masks,
                               tf_radlong_overlay, tf_segmentor_input, tf_segmentor_classmap, and the float16 payload calls
                               (tf_calc_seq_rgb_f16, tf_submit_seq_rgb_f16, tf_calc_seq_saliency_f16, tf_echo_frames, tf_dbg_f16_round)
-                              and the WASE study calls (tf_calc_seq_rgb_wase, tf_calc_seq_saliency_wase) */
+                              and the WASE study calls (tf_calc_seq_rgb_wase, tf_calc_seq_saliency_wase), and inflate on the device
+                              (tf_inflate, tf_hold_study_chunks, tf_hold_mask_chunks with the new struct tf_chunked) */
 
 enum {
     TF_OK = 0,
@@ -524,6 +525,46 @@ int tf_held_radlong_project_param(tf_handle* h, int n_used, int slot, int param,
 int tf_held_polar_project_param(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, float* mag_out, float* ang_out,
                                 float* minmax, long long* nonzero, float* ang_mode);
 int tf_held_radlong_overlay(tf_handle* h, const double* lut_rad, const double* lut_long, uint8_t* out, double* info);
+
+/* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
+ *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over
+ *      the bus is the compressed bytes.  The output bytes are zlib's or the stream is refused: stored, fixed and dynamic blocks, any
+ *      window size in the header, the stream's Adler-32 checked; a preset dictionary (FDICT) is refused; bytes after the trailer are
+ *      ignored.  A malformed stream ends with a status and writes nothing outside its own output.
+ * A stream's status: 0, or 1 bad header (FCHECK, CM != 8, CINFO > 7, FDICT), 2 bad block type, 3 bad stored length, 4 bad code
+ *   lengths (over-subscribed or incomplete as zlib judges them, no end-of-block code, or a code the lengths do not define), 5 a distance
+ *   before the start of the output, 6 input truncated, 7 output longer or shorter than expected, 8 checksum mismatch.
+ * tf_inflate: n streams, stream i the len[i] bytes at blob + off[i] (host), each to out_bytes bytes: out_host [n][out_bytes] (host),
+ *   status [n].  raw (or NULL): raw[i] != 0 marks a stream that is not compressed; it is copied as it is and must be out_bytes long.
+ *   TF_OK when every status is 0; otherwise TF_ERR_INVALID_ARG, tf_last_error names the first bad stream and its status, status[] is
+ *   complete and the good streams' outputs are valid; a bad stream's slot holds what it decoded before it failed and is otherwise
+ *   untouched.  Runs on the handle's stream, host-synchronous, like the tail calls.
+ * tf_chunked: one chunked dataset.  n chunks, chunk i the len[i] bytes at blob + off[i], raw[i] (raw may be NULL) set where the file's
+ *   filter mask says the chunk was stored unfiltered, its first element at coord[i * ndim .. ] of the array; shape and chunk: the
+ *   array's and a chunk's extent per dimension (ndim <= 4), elem_bytes 1, 2 or 4, chunk_bytes = the chunk's elements x elem_bytes.  A
+ *   chunk at the array's edge is clipped; where the file wrote no chunk the array is 0 (HDF5's fill value).
+ * tf_hold_study_chunks: flow 4-D with last dimension 2 and 2-byte elements, echo (or NULL) 3-D with 2-byte elements and the flow's
+ *   frame size.  On success the held study is what tf_hold_study of the same arrays leaves.  If any chunk fails to inflate
+ *   (TF_ERR_INVALID_ARG; tf_last_error names the chunk) nothing changes: the study held before, its masks and the resident planes stay.
+ * tf_hold_mask_chunks: mask 4-D [n_frames][H][W][C], C = 1 or 2, 1-byte elements, H and W the held study's, into `slot`; the same contract.
+ * Every argument is checked before any GPU work: null pointers, n < 0, a coord outside the shape, a chunk_bytes that is not the chunk's.
+ * "tail_upload_bytes" grows by the compressed bytes uploaded: max(off + len) - min(off) over the call's chunks.
+ * tf_dbg_counter(h, "inflate_kernel_us" / "unchunk_kernel_us"): device time of the two kernels since the handle was made (HIP events). */
+typedef struct tf_chunked {
+    const uint8_t* blob;
+    const uint64_t* off;
+    const uint32_t* len;
+    const uint8_t* raw;
+    const int64_t* coord;
+    int n, ndim;
+    int64_t shape[4], chunk[4];
+    int elem_bytes;
+    uint32_t chunk_bytes;
+} tf_chunked;
+int tf_inflate(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, const uint8_t* raw, int n, uint32_t out_bytes,
+               uint8_t* out_host, int* status);
+int tf_hold_study_chunks(tf_handle* h, const tf_chunked* flow, const tf_chunked* echo);
+int tf_hold_mask_chunks(tf_handle* h, int slot, const tf_chunked* mask);
 
 /* ---- multi-GPU: the single exchange step of the path.  The reference's loop is sequential
  *      (calculate_optical_flow.py:584-597); here pairs shard over the GPUs of a node with no data-path traffic during the

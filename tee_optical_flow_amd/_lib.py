@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "tf_calc_chains", "tf_calc_chains_device", "tf_calc_chains_rgb", "tf_dbg_chain_order",
     "tf_hold_study", "tf_hold_mask", "tf_hold_next", "tf_held_shape", "tf_release_study", "tf_held_av_centroids", "tf_held_first_region_areas",
     "tf_held_radlong_project_param", "tf_held_polar_project_param", "tf_held_radlong_overlay",
+    "tf_inflate", "tf_hold_study_chunks", "tf_hold_mask_chunks",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -59,6 +60,13 @@ class TfStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved0"}
+
+
+class TfChunked(C.Structure):
+    """tf_chunked: one chunked dataset of a study file (include/teeflow.h)"""
+    _fields_ = [("blob", C.c_void_p), ("off", C.c_void_p), ("len", C.c_void_p), ("raw", C.c_void_p), ("coord", C.c_void_p),
+                ("n", C.c_int), ("ndim", C.c_int), ("shape", C.c_int64 * 4), ("chunk", C.c_int64 * 4), ("elem_bytes", C.c_int),
+                ("chunk_bytes", C.c_uint32)]
 
 
 _lib = None
@@ -167,6 +175,9 @@ def load():
     L.tf_held_radlong_project_param.argtypes = [vp, i32, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.tf_held_polar_project_param.argtypes = [vp, i32, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.tf_held_radlong_overlay.argtypes = [vp, vp, vp, vp, vp]
+    L.tf_inflate.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, vp, vp]
+    L.tf_hold_study_chunks.argtypes = [vp, C.POINTER(TfChunked), C.POINTER(TfChunked)]
+    L.tf_hold_mask_chunks.argtypes = [vp, i32, C.POINTER(TfChunked)]
     L.tf_get_iters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.tf_last_error.argtypes = [vp]
     L.tf_last_error.restype = C.c_char_p

@@ -40,6 +40,11 @@ A study held on the device (DenseFlow.hold_study, or a study call with hold=True
 functions above whose arrays are not on the host.  With it and its own engine they take the held calls (tf_held_*), which read the
 flow, the masks and the echo where they are; the results are the bits of the same functions on a FlowStudy of the same arrays.
 Where the arrays are is _Tail's business alone; each function's device path is written once, over either kind.
+
+A study file reaches the device as arrays (HeldStudy.from_hdf5, inflate="h5py": h5py inflates every gzip chunk on one thread) or as the
+chunks the file stores: study_chunks reads them without inflating them (save_chunks / load_chunks carry the record to an interpreter
+without h5py), and HeldStudy.from_chunks has them inflated by zlib in a thread pool (unchunk_host, inflate="host") or uploaded
+compressed and inflated on the device (DenseFlow.hold_study_chunks / hold_mask_chunks, inflate="device").  The held bytes are the same.
 """
 import logging
 import os
@@ -429,9 +434,158 @@ class HeldStudy:
         return cls(engine, study.frame_rate, nframes=study.nframes, mode=study.mode, filename=study.filename)
 
     @classmethod
-    def from_hdf5(cls, engine, path):
-        """A study file in the reference's layout, read as FlowStudy.from_hdf5 reads it and uploaded once.  Needs h5py."""
+    def from_hdf5(cls, engine, path, inflate="h5py"):
+        """A study file in the reference's layout, held on `engine`.  Needs h5py.  `inflate` says who inflates the file's gzip chunks:
+          "h5py"    h5py does, chunk after chunk on this thread (FlowStudy.from_hdf5), and the arrays are uploaded: the default
+          "host"    the chunks are read as they are stored (study_chunks), inflated by zlib in a thread pool (unchunk_host), uploaded
+          "device"  the chunks are read as they are stored and uploaded compressed; the device inflates and assembles them
+                    (DenseFlow.hold_study_chunks / hold_mask_chunks)
+        The held study is the same bytes whichever way.  A file whose datasets are not plain gzip chunks (contiguous, another filter
+        in the pipeline), or an h5py without the direct-chunk calls, is read the "h5py" way, with one logged reason."""
+        if inflate not in INFLATE_WAYS:
+            raise ValueError(f"inflate must be one of {INFLATE_WAYS}, got {inflate!r}")
+        if inflate != "h5py":
+            try:
+                return cls.from_chunks(engine, study_chunks(path), inflate=inflate)
+            except ChunksUnavailable as e:
+                log.warning("%s: read through h5py instead of inflate=%r: %s", path, inflate, e)
         return cls.from_study(engine, FlowStudy.from_hdf5(path))
+
+    @classmethod
+    def from_chunks(cls, engine, record, inflate="device"):
+        """A study_chunks / load_chunks record held on `engine`: inflate = "device" (the compressed chunks go up) or "host"
+        (unchunk_host, then the arrays).  Each array is held whole or not at all, but the study is held array by array, the flow and
+        echo first: a flow or echo chunk that does not decode raises and leaves the study held before; a mask chunk that does not
+        decode raises with the new study held and the masks before it (the way "host" inflates everything before it holds anything)."""
+        if inflate not in INFLATE_WAYS[1:]:
+            raise ValueError(f"inflate must be one of {INFLATE_WAYS[1:]}, got {inflate!r}")
+        a, ds = record["attrs"], record["datasets"]
+        frame_rate = a["frame_rate"] if a["units_converted"] else 1
+        labels = [str(k) for k in a["labels"]]
+        kw = dict(nframes=int(a["nframes"]) - 2, mode=str(a["mode"]), filename=str(record["filename"]))
+        if inflate == "host":
+            return cls.from_study(engine, FlowStudy(unchunk_host(ds["flow"]), {k: unchunk_host(ds[k]) for k in labels}, frame_rate,
+                                                    echo=unchunk_host(ds["echo"]) if "echo" in ds else None, **kw))
+        engine.hold_study_chunks(ds["flow"], ds.get("echo"))
+        for k in labels:
+            engine.hold_mask_chunks(k, ds[k])
+        return cls(engine, frame_rate, **kw)
+
+
+# ---- a study file's chunks as they are stored -----------------------------------------------------------------------------------
+INFLATE_WAYS = ("h5py", "host", "device")
+_DS_FIELDS = ("shape", "dtype", "chunks", "coord", "filter_mask", "off", "len", "blob")
+_ATTRS = ("frame_rate", "units_converted", "nframes", "mode", "labels")
+
+
+class ChunksUnavailable(ValueError):
+    """study_chunks cannot hand over a file's chunks as they are stored; the message says why"""
+
+
+def chunks_record(shape, dtype, chunks, stored):
+    """A dataset record from its parts: stored = [(coord, filter_mask, bytes)] of the chunks the file wrote, coord the element offset
+    of the chunk's first element, filter_mask HDF5's (bit 0 set: the bytes are the chunk itself, no filter was applied), bytes a
+    zlib stream of the whole chunk (edge chunks are stored whole).  Plain data: tuples, a string and numpy arrays; the chunks' bytes
+    lie end to end in `blob`, chunk i at [off[i], off[i] + len[i])."""
+    ndim = len(shape)
+    lens = np.array([len(b) for _, _, b in stored], np.uint32)
+    off = np.zeros(len(stored), np.uint64)
+    off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return {"shape": tuple(int(v) for v in shape), "dtype": str(np.dtype(dtype)), "chunks": tuple(int(v) for v in chunks),
+            "coord": np.array([c for c, _, _ in stored], np.int64).reshape(len(stored), ndim),
+            "filter_mask": np.array([m for _, m, _ in stored], np.uint32), "off": off, "len": lens,
+            "blob": np.frombuffer(b"".join(bytes(b) for _, _, b in stored), np.uint8)}
+
+
+def _dataset_chunks(ds, name):
+    import h5py
+    if ds.chunks is None:
+        raise ChunksUnavailable(f"dataset {name!r} is contiguous, not chunked")
+    if not all(hasattr(ds.id, f) for f in ("get_num_chunks", "get_chunk_info", "read_direct_chunk")):
+        raise ChunksUnavailable("this h5py has no get_num_chunks / get_chunk_info / read_direct_chunk")
+    plist = ds.id.get_create_plist()
+    filters = [plist.get_filter(i)[0] for i in range(plist.get_nfilters())]
+    if filters not in ([], [h5py.h5z.FILTER_DEFLATE]):
+        raise ChunksUnavailable(f"dataset {name!r} has the filter pipeline {filters}, not gzip alone")
+    stored = []
+    for i in range(ds.id.get_num_chunks()):
+        info = ds.id.get_chunk_info(i)
+        mask, data = ds.id.read_direct_chunk(info.chunk_offset)
+        stored.append((info.chunk_offset, mask if filters else 1, data))       # (no filter at all: every chunk is its own bytes)
+    return chunks_record(ds.shape, ds.dtype, ds.chunks, stored)
+
+
+def study_chunks(path):
+    """What HeldStudy.from_hdf5 needs of a study file, with the chunks of `flow`, `echo` and every mask in attrs['labels'] as the
+    file stores them, not inflated: {'filename', 'attrs': {frame_rate, units_converted, nframes, mode, labels}, 'datasets': {name:
+    chunks_record}}.  h5py and numpy only, no engine.  Raises ChunksUnavailable where a dataset is not plain gzip chunks."""
+    import h5py
+    with h5py.File(path, "r") as f:
+        a = f["flow"].attrs
+        labels = [str(k) for k in a["labels"]]
+        rec = {"filename": os.path.basename(path)[:-4],
+               "attrs": {"frame_rate": float(a["frame_rate"]), "units_converted": bool(a["units_converted"]), "nframes": int(a["nframes"]),
+                         "mode": a["mode"].decode() if isinstance(a["mode"], bytes) else str(a["mode"]), "labels": labels},
+               "datasets": {}}
+        for name in ["flow"] + (["echo"] if "echo" in f else []) + labels:
+            rec["datasets"][name] = _dataset_chunks(f[name], name)
+    return rec
+
+
+def save_chunks(record, npz_path):
+    """a study_chunks record as an .npz of plain arrays (no pickle): one interpreter reads the file, another holds the study"""
+    flat = {"filename": np.array(record["filename"]), "names": np.array(list(record["datasets"]))}
+    for k in _ATTRS:
+        flat[f"attrs/{k}"] = np.array(record["attrs"][k])
+    for name, ds in record["datasets"].items():
+        for k in _DS_FIELDS:
+            flat[f"ds/{name}/{k}"] = np.array(ds[k])
+    np.savez(npz_path, **flat)
+
+
+def load_chunks(npz_path):
+    with np.load(npz_path, allow_pickle=False) as z:
+        a = {k: z[f"attrs/{k}"] for k in _ATTRS}
+        rec = {"filename": str(z["filename"]),
+               "attrs": {"frame_rate": float(a["frame_rate"]), "units_converted": bool(a["units_converted"]), "nframes": int(a["nframes"]),
+                         "mode": str(a["mode"]), "labels": [str(k) for k in a["labels"]]},
+               "datasets": {}}
+        for name in (str(n) for n in z["names"]):
+            ds = {k: z[f"ds/{name}/{k}"] for k in _DS_FIELDS}
+            ds["shape"], ds["chunks"], ds["dtype"] = tuple(int(v) for v in ds["shape"]), tuple(int(v) for v in ds["chunks"]), str(ds["dtype"])
+            rec["datasets"][name] = ds
+    return rec
+
+
+def unchunk_host(ds, workers=None):
+    """A dataset record -> its array, on the host: zlib.decompress of every chunk in a thread pool (zlib releases the GIL; sized like
+    the writer's, hdf5_out._workers; workers=1: no pool, this thread), then assembly; where the file wrote no chunk the array is 0, HDF5's fill value.  The numpy
+    twin of DenseFlow.hold_study_chunks / hold_mask_chunks."""
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    from .hdf5_out import _workers
+    shape, chunks, dt = tuple(ds["shape"]), tuple(ds["chunks"]), np.dtype(str(ds["dtype"]))
+    blob, off, ln, mask = np.asarray(ds["blob"], np.uint8), ds["off"], ds["len"], ds["filter_mask"]
+    out = np.zeros(shape, dt)
+    want = int(np.prod(chunks, dtype=np.int64)) * dt.itemsize
+
+    def one(i):
+        b = blob[int(off[i]):int(off[i]) + int(ln[i])]
+        raw = b.tobytes() if int(mask[i]) & 1 else zlib.decompress(b)
+        if len(raw) != want:
+            raise ValueError(f"chunk {i} inflates to {len(raw)} bytes, a chunk has {want}")
+        at = [int(v) for v in ds["coord"][i]]
+        keep = tuple(slice(0, min(c, s - o)) for o, c, s in zip(at, chunks, shape))
+        out[tuple(slice(o, o + k.stop) for o, k in zip(at, keep))] = np.frombuffer(raw, dt).reshape(chunks)[keep]
+
+    n = len(ln)
+    if workers == 1:                                          # on the calling thread
+        for i in range(n):
+            one(i)
+        return out
+    with ThreadPoolExecutor(workers or _workers()) as pool:
+        list(pool.map(lambda lo: [one(i) for i in range(lo, min(lo + 16, n))], range(0, n, 16)))
+    return out
 
 
 # ---- where a study's arrays are: the one place that knows ------------------------------------------------------------------------

@@ -29,6 +29,7 @@
 #include "teeflow_polar.hip.h"
 #include "teeflow_overlay.hip.h"
 #include "teeflow_segmentor.hip.h"
+#include "teeflow_inflate.hip.h"
 #include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include "teeflow_engine.hip.h"
@@ -226,6 +227,8 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "coop_cooldown") { v = 0; for (auto& c : all) v = v > c.cooldown ? v : c.cooldown; }
     else if (n == "saliency_kernel_us") v = (long long)(h->pre_kernel_ms * 1000.0);
     else if (n == "wase_study_kernel_us") v = (long long)(h->wase_kernel_ms * 1000.0);
+    else if (n == "inflate_kernel_us") v = (long long)(h->inflate_kernel_ms * 1000.0);
+    else if (n == "unchunk_kernel_us") v = (long long)(h->unchunk_kernel_ms * 1000.0);
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;
@@ -479,6 +482,8 @@ TF_API int tf_wait(tf_handle* h, int ticket, tf_stats* st)
 #include "teeflow_tail.hip.h"
 // a study held on the device and the tail calls that read it there
 #include "teeflow_held.hip.h"
+// inflate on the device: tf_inflate, and a study held from the gzip chunks of its file
+#include "teeflow_inflate_host.hip.h"
 
 TF_API int tf_get_iters(tf_handle* h, int* out, size_t capacity_ints, size_t* written)
 {

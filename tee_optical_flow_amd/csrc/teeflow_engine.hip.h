@@ -197,10 +197,12 @@ struct tf_handle : Engine {
            PRE_SG_IN, PRE_SG_IDX, PRE_SG_MAP,                                     // tf_segmentor_input (tables, LUT, frames), tf_segmentor_classmap
            PRE_ECHO,                                                              // the study's float16 `echo` (tf_echo_frames, the *_f16 calls)
            PRE_CH_GRAY,                                                           // tf_calc_chains_rgb: the conditioned frames of all its studies
+           PRE_INF_BLOB, PRE_INF_TABLE, PRE_INF_OUT,                              // tf_inflate, tf_hold_*_chunks: compressed bytes, per-stream table, inflated chunks
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     double wase_kernel_ms = 0;   // device time of the last WASE study call's reduction and output kernels (the same events)
+    double inflate_kernel_ms = 0, unchunk_kernel_ms = 0;   // device time of k_inflate / k_unchunk since the handle was made (the same events)
     // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
     // ([0]: upload done) and the device scratch ([1]: kernel done) of the last call may be written again
     void* seg_stage = nullptr; size_t seg_stage_cap = 0; hipEvent_t seg_ev[2] = {};

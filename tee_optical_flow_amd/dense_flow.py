@@ -240,7 +240,8 @@ class DenseFlow:
     def counter(self, name):
         """Debug counters of the engine (tf_dbg_counter): coop_launches, coop_aborts, coop_disabled, coop_rearms, coop_cooldown, coop_occ16, coop_occ8,
         queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised, chain_steps,
-        saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels)."""
+        saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels),
+        inflate_kernel_us, unchunk_kernel_us (device time of k_inflate / k_unchunk since the engine was made)."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
     def _finish(self, st, chain_pairs=None):
@@ -789,23 +790,104 @@ class DenseFlow:
                                          0 if echo is None else echo.shape[0]), self._h, "tf_hold_study")
         return self.held
 
-    def hold_mask(self, label, mask):
-        """Put a mask of the held study on the device under `label`: bool or uint8 [n,H,W,C], C = 1 or 2, H and W the held study's.  A
-        label held already is replaced; a held study takes 12 labels, a 13th raises."""
+    def _held_or_raise(self):
         shape = self._held_shape()
         if shape[0] < 1:
             raise OpticalFlowCalculationError("no study is held (hold_study, or a study call with hold=True)")
-        m = _mask_stack(mask, "mask")
-        if m.shape[1:3] != (shape[1], shape[2]):
-            raise OpticalFlowCalculationError(f"mask must be [n,{shape[1]},{shape[2]},C] (the held study's frames), got {m.shape}")
+        return shape
+
+    def _hold_mask(self, fn, label, frame_shape, channels, what, call):
+        """what hold_mask and hold_mask_chunks share, for the library's call `fn`: the mask's frames are the held study's, the label
+        gets its slot, and a label that is new goes again if the library refuses the mask.  call(slot) -> the library's return code."""
+        shape = self._held_or_raise()
+        if tuple(frame_shape) != (shape[1], shape[2]) or channels not in (1, 2):
+            raise OpticalFlowCalculationError(f"mask must be [n,{shape[1]},{shape[2]},C] (the held study's frames), C = 1 or 2, got {what}")
         known = label in self._held_labels.slots
         slot = self._held_labels.slot_for(label)
         try:
-            _lib.check(self._L.tf_hold_mask(self._h, slot, m.ctypes.data, m.shape[0], m.shape[3]), self._h, "tf_hold_mask")
+            _lib.check(call(slot), self._h, fn)
         except OpticalFlowCalculationError:
             if not known:
                 del self._held_labels.slots[label]
             raise
+
+    def hold_mask(self, label, mask):
+        """Put a mask of the held study on the device under `label`: bool or uint8 [n,H,W,C], C = 1 or 2, H and W the held study's.  A
+        label held already is replaced; a held study takes 12 labels, a 13th raises."""
+        self._held_or_raise()
+        m = _mask_stack(mask, "mask")
+        self._hold_mask("tf_hold_mask", label, m.shape[1:3], m.shape[3], m.shape, lambda slot: self._L.tf_hold_mask(self._h, slot, m.ctypes.data, m.shape[0], m.shape[3]))
+
+    # ---- inflate on the device (include/teeflow.h, tf_inflate): the gzip chunks of a study file are independent zlib streams; the
+    # device decodes them, one wave per stream, and a study is held from the compressed bytes of its file -------------------------------
+    def inflate(self, streams, out_bytes, out=None):
+        """zlib streams (bytes-like objects), each to out_bytes bytes -> (uint8 [n,out_bytes], status int32 [n]).  A status is 0 or the
+        library's code for what is wrong with the stream (teeflow.h); the call does not raise for a stream that does not decode: its
+        status says so, and its row holds what was decoded before the fault and is otherwise untouched (zeros, or what `out` held:
+        out, a C-contiguous uint8 [n,out_bytes] array of the caller's, is written in place of a fresh one).  A call that fails as a
+        whole -- refused arguments, a HIP error -- raises."""
+        streams = [bytes(s) if not isinstance(s, (bytes, bytearray)) else s for s in streams]
+        n, out_bytes = len(streams), int(out_bytes)
+        if out_bytes < 0:
+            raise OpticalFlowCalculationError(f"out_bytes must be >= 0, got {out_bytes}")
+        if out is None:
+            out = np.zeros((n, out_bytes), np.uint8)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != (n, out_bytes) or not out.flags.c_contiguous:
+            raise OpticalFlowCalculationError(f"out must be a C-contiguous uint8 [{n},{out_bytes}] array")
+        status = np.zeros(n, np.int32)                       # the library's alone: a call that fails as a whole leaves it clear
+        lens = np.array([len(s) for s in streams], np.uint32)
+        offs = np.zeros(n, np.uint64)
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(streams) or b"\0", np.uint8)
+        rc = self._L.tf_inflate(self._h, blob.ctypes.data, offs.ctypes.data, lens.ctypes.data, None, n, out_bytes, out.ctypes.data, status.ctypes.data)
+        if rc != _lib.TF_OK and not status.any():            # not a verdict on a stream: the call itself failed
+            _lib.check(rc, self._h, "tf_inflate")
+        return out, status
+
+    @staticmethod
+    def _chunked(rec, what, ndim, dtypes):
+        """a dataset record of analysis.study_chunks -> (tf_chunked, the arrays it points into)"""
+        shape, chunk = tuple(int(v) for v in rec["shape"]), tuple(int(v) for v in rec["chunks"])
+        dt = np.dtype(str(rec["dtype"]))
+        if dt not in dtypes or len(shape) != ndim or len(chunk) != ndim or min(shape + chunk) < 1:
+            raise OpticalFlowCalculationError(f"{what} chunks must describe a {ndim}-D {' or '.join(str(np.dtype(d)) for d in dtypes)} dataset with no "
+                                              f"empty side, got {dt} {shape} in chunks of {chunk}")
+        coord = np.ascontiguousarray(rec["coord"], np.int64).reshape(-1, ndim)
+        n = coord.shape[0]
+        off, ln = np.ascontiguousarray(rec["off"], np.uint64), np.ascontiguousarray(rec["len"], np.uint32)
+        raw = np.ascontiguousarray((np.asarray(rec["filter_mask"], np.uint32) & 1).astype(np.uint8))
+        blob = np.ascontiguousarray(rec["blob"], np.uint8)
+        if not (off.shape == ln.shape == raw.shape == (n,)):
+            raise OpticalFlowCalculationError(f"{what} chunks: coord, off, len and filter_mask disagree about the number of chunks")
+        if n and int((off + ln.astype(np.uint64)).max()) > blob.size:
+            raise OpticalFlowCalculationError(f"{what} chunks: a chunk ends behind the blob's {blob.size} bytes")
+        if blob.size == 0:
+            blob = np.zeros(1, np.uint8)
+        c = _lib.TfChunked(blob.ctypes.data, off.ctypes.data, ln.ctypes.data, raw.ctypes.data, coord.ctypes.data, n, ndim)
+        for d in range(ndim):
+            c.shape[d], c.chunk[d] = shape[d], chunk[d]
+        c.elem_bytes, c.chunk_bytes = dt.itemsize, int(np.prod(chunk, dtype=np.int64)) * dt.itemsize
+        return c, (blob, off, ln, raw, coord)
+
+    def hold_study_chunks(self, flow_chunks, echo_chunks=None):
+        """hold_study from the file's own chunks: flow_chunks / echo_chunks are the `flow` and `echo` dataset records of
+        analysis.study_chunks (float16 [N,H,W,2] and [n,H,W], gzip chunks as the file holds them).  The compressed bytes are uploaded
+        and inflated on the device; the held study is what hold_study of the arrays leaves.  If a chunk does not decode the call
+        raises and the study held before, with its masks, stays."""
+        f, keep_f = self._chunked(flow_chunks, "flow", 4, (np.float16,))
+        if f.shape[3] != 2:
+            raise OpticalFlowCalculationError(f"flow chunks must describe [N,H,W,2], got {tuple(f.shape)}")
+        e, keep_e = (None, None) if echo_chunks is None else self._chunked(echo_chunks, "echo", 3, (np.float16,))
+        _lib.check(self._L.tf_hold_study_chunks(self._h, C.byref(f), None if e is None else C.byref(e)), self._h, "tf_hold_study_chunks")
+        del keep_f, keep_e
+        return self.held
+
+    def hold_mask_chunks(self, label, chunks):
+        """hold_mask from the file's own chunks: the dataset record of a bool or uint8 [n,H,W,C] mask, C = 1 or 2."""
+        self._held_or_raise()
+        m, keep = self._chunked(chunks, "mask", 4, (np.bool_, np.uint8))
+        self._hold_mask("tf_hold_mask_chunks", label, (m.shape[1], m.shape[2]), m.shape[3], tuple(m.shape), lambda slot: self._L.tf_hold_mask_chunks(self._h, slot, C.byref(m)))
+        del keep
 
     def hold_next(self, on=True):
         """Arm (or disarm) the next study call to leave its payload held: what hold=True does for the calc_study_*_payload calls.  The

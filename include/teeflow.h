@@ -480,6 +480,38 @@ int tf_radlong_overlay(tf_handle* h, const void* echo, int echo_kind, const doub
  * or the last projection was tf_polar_project_param.  No GPU work. */
 int tf_radlong_shape(tf_handle* h, int* shape);
 
+/* ---- the per-pixel part of the reference's other video, the "single component" magnitude overlay (example_peak_plots.py:459-513), on
+ *      the device: the magnitude of get_masked_arr(param, label) through one colormap, blended half and half with the echo.
+ * tf_magnitude_overlay builds the param field itself (flow, flow_is_f16, N, H, W, mask, mask_C, param, spacing, grad_f64 as
+ *   tf_radlong_project_param, except that the mask covers ALL N frames: host uint8 [N][H][W][mask_C]) and leaves the resident rad/long
+ *   or polar planes of the handle's last projection as they are.
+ *   mag = sqrt(x*x + y*y) in float32, every step rounded, nothing fused (np.sqrt(x**2 + y**2); not cv2.cartToPolar's magnitude);
+ *   vmin, vmax = min, max of mag over all N frames, zeros outside the mask included (ONE Normalize for the study);
+ *   frames [0, n_used) are rendered: t = (mag - vmin) / (vmax - vmin) in float32, where the divisor is the float64 difference and the
+ *   quotient is rounded to float32 once (norm_f64 = 1: numpy >= 2 under matplotlib's float64 scalars) or the difference rounded to
+ *   float32 first (norm_f64 = 0: numpy 1.x); 0 everywhere if vmin == vmax; LUT index min(trunc(t * 256), 255);
+ *   per frame: emax = the echo's maximum, cmax = the largest channel among the LUT entries the frame used;
+ *   v = ((0.5 * (echo / emax)) + (0.5 * (lut[index] / cmax))) * 255 in float64, with echo / emax = echo when emax == 0 and
+ *   lut / cmax = lut when cmax == 0.  echo: host [>= n_used][H][W]; TF_ECHO_F16: the echo term is float16 arithmetic as in
+ *   tf_radlong_overlay, and v is stored into a float16 array (rounded to half, nearest-even) before uint8 truncates it, as the
+ *   reference's np.zeros_like(gray2rgb(echo)) output does; TF_ECHO_U8: float64 division, v truncated directly.
+ *   lut: float64 [256][3] RGB, finite and >= 0.  out: host uint8 [n_used][H][W][3].  info[2] = vmin, vmax.
+ *   frame_info[n_used][2] = echo max, colour max of each frame.
+ *   TF_ERR_INVALID_ARG for a null pointer, sizes < 1, n_used > N, mask_C outside {1, 2}, an unknown param or echo kind, acceleration
+ *   or PWR with N < 2 or a spacing that is zero or not finite; with a message: a LUT entry that is negative or not finite; NaN or inf
+ *   in the magnitude; a negative or non-finite echo value (the reference's result in the last two is an undefined cast).
+ *   TF_ERR_UNSUPPORTED, with a message, for H*W >= 2^28 or N > 65535.  Runs on the handle's stream and never on a lane's, so it may be
+ *   called while tf_submit_* jobs of the handle are in flight; host-synchronous; every argument is checked before any GPU work.
+ *   Device scratch, grown on demand and kept by the handle: the flow and mask uploads (the projections' upload scratch, all N
+ *   frames), 1 byte per pixel of the n_used frames (the indices), 64 B + 6 KiB per frame (its words and colour terms), and 5 (float16
+ *   echo) or 4 bytes per pixel of a chunk of frames of at most 512 MiB (at least one frame; tf_set_tuning "overlay_chunk_kib"): the
+ *   echo and the output.
+ * tf_held_magnitude_overlay: the same of the held study's flow and echo and the mask in `slot`, which must cover all N held frames;
+ *   refusals as the other tf_held_* calls', by message. */
+int tf_magnitude_overlay(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask, int mask_C,
+                         int param, double spacing, int grad_f64, int norm_f64, const void* echo, int echo_kind, const double* lut,
+                         uint8_t* out, double* info, double* frame_info);
+
 /* ---- a study HELD on the device: the study file's payload put there once, and the consumer's tail reading it there.  The calls above
  *      take host arrays and upload them on every call; one 65-frame 512 x 512 study's tail (three rad/long params, three polar params,
  *      angle mode, area series, AV centroids, overlay) uploads the same flow seven times and the same masks eight times.  A held study
@@ -525,6 +557,8 @@ int tf_held_radlong_project_param(tf_handle* h, int n_used, int slot, int param,
 int tf_held_polar_project_param(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, float* mag_out, float* ang_out,
                                 float* minmax, long long* nonzero, float* ang_mode);
 int tf_held_radlong_overlay(tf_handle* h, const double* lut_rad, const double* lut_long, uint8_t* out, double* info);
+int tf_held_magnitude_overlay(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, int norm_f64, const double* lut,
+                              uint8_t* out, double* info, double* frame_info);
 
 /* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
  *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over
@@ -616,7 +650,7 @@ int tf_device_count(void);
  * Both: "lanes" (contiguous units a call of at most one sub-batch is split into, solved side by side on the queue lanes), "queue_lanes" (lanes
  * that take those units, the sub-batches of larger calls and tf_submit_* jobs from the queue: -1 = 3 for DualTVL1, "lanes" for DeepFlow [default];
  * 0 = no lanes: the handle solves every call alone, sub-batch after sub-batch -- the same flows), "queue_unit" (pairs per queued sub-batch; 0 = equal sub-batches of at most max_batch pairs, a multiple of the lane count of them).
- * tf_radlong_overlay: "overlay_chunk_kib" (tests: the echo and output of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]).
+ * tf_radlong_overlay, tf_magnitude_overlay: "overlay_chunk_kib" (tests: the echo and output of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]).
  * tf_first_region_areas: "area_chunk_kib" (tests: the masks and labelling scratch of a chunk of frames take at most this many KiB, at least one frame; 0 = 512 MiB [default]). */
 int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),

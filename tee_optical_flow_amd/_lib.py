@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "tf_calc_chains", "tf_calc_chains_device", "tf_calc_chains_rgb", "tf_dbg_chain_order",
     "tf_hold_study", "tf_hold_mask", "tf_hold_next", "tf_held_shape", "tf_release_study", "tf_held_av_centroids", "tf_held_first_region_areas",
     "tf_held_radlong_project_param", "tf_held_polar_project_param", "tf_held_radlong_overlay",
+    "tf_magnitude_overlay", "tf_held_magnitude_overlay",
     "tf_inflate", "tf_hold_study_chunks", "tf_hold_mask_chunks",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
@@ -159,6 +160,7 @@ def load():
     L.tf_radlong_select.argtypes = [vp, i32, vp, vp]
     L.tf_radlong_overlay.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.tf_radlong_shape.argtypes = [vp, C.POINTER(i32 * 3)]
+    L.tf_magnitude_overlay.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, dbl, i32, i32, vp, i32, vp, vp, vp, vp]
     L.tf_hold_study.argtypes = [vp, vp, i32, i32, i32, vp, i32]
     L.tf_hold_mask.argtypes = [vp, i32, vp, i32, i32]
     L.tf_hold_next.argtypes = [vp, i32]
@@ -175,6 +177,7 @@ def load():
     L.tf_held_radlong_project_param.argtypes = [vp, i32, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.tf_held_polar_project_param.argtypes = [vp, i32, i32, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.tf_held_radlong_overlay.argtypes = [vp, vp, vp, vp, vp]
+    L.tf_held_magnitude_overlay.argtypes = [vp, i32, i32, i32, dbl, i32, i32, vp, vp, vp, vp]
     L.tf_inflate.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, vp, vp]
     L.tf_hold_study_chunks.argtypes = [vp, C.POINTER(TfChunked), C.POINTER(TfChunked)]
     L.tf_hold_mask_chunks.argtypes = [vp, i32, C.POINTER(TfChunked)]

@@ -36,6 +36,12 @@ With engine= the frames are rendered on the device from the planes tf_radlong_pr
 per pixel downloaded; without, a numpy twin that keeps index planes instead of RGBA float64 arrays.  Pinned by
 tests/golden/reference_overlay.npz (the frames the reference's own functions handed to their video writer).
 
+And the reference's other video, the single-component magnitude overlay:
+  example_peak_plots.py:459-513  mag of get_masked_arr(param, label) through 'hot', blended with the echo -> magnitude_overlay, visualize_magnitude
+With engine= the field, the study-wide norm, the indices, the per-frame maxima and the frames are made on the device
+(tf_magnitude_overlay), 3 bytes per pixel downloaded; without, a numpy twin that works frame by frame (magnitude_overlay_host).  Pinned by
+tests/golden/reference_single_overlay.npz (the frames the reference's own example handed to its video writer).
+
 A study held on the device (DenseFlow.hold_study, or a study call with hold=True) is analysed through a HeldStudy: the `ds` of the
 functions above whose arrays are not on the host.  With it and its own engine they take the held calls (tf_held_*), which read the
 flow, the masks and the echo where they are; the results are the bits of the same functions on a FlowStudy of the same arrays.
@@ -376,8 +382,8 @@ class HeldStudy:
     """The `ds` of the analysis functions for the study held on `engine` (a DenseFlow): what FlowStudy is for arrays on the host.
     Made after the study and its masks are on the device -- DenseFlow.hold_study / hold_mask, or a study call with hold=True and
     hold_mask -- or by from_study / from_hdf5, which upload the flow, the echo and every mask once.  nframes defaults to N - 2, as
-    FlowStudy's.  calculate_3dhist_radlong, calculate_3dhist, angle_mode_series, area_series, av_centroids, radlong_overlay and
-    visualize_radlong then read the held arrays when they are given this engine as `engine`; with engine=None or another engine
+    FlowStudy's.  calculate_3dhist_radlong, calculate_3dhist, angle_mode_series, area_series, av_centroids, radlong_overlay,
+    visualize_radlong, magnitude_overlay and visualize_magnitude then read the held arrays when they are given this engine as `engine`; with engine=None or another engine
     they raise, since the arrays are not on the host and nothing falls back to a host path.  The object belongs to the generation of
     the held study it was made at: once the engine's held study has been replaced or released, using it raises."""
 
@@ -654,6 +660,15 @@ class _Tail:
 
     def overlay(self, echo, lut_rad, lut_long):
         return self.engine.held_radlong_overlay(lut_rad, lut_long) if self.held else self.engine.radlong_overlay(echo, lut_rad, lut_long)
+
+    def magnitude_overlay(self, param, label, n, echo, lut, norm_f64):
+        if self.held:
+            return self.engine.held_magnitude_overlay(label, *self._param(param), norm_f64, n, lut)
+        flow, mask = _study_arrays(self.ds, label)
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"the device path takes a bool or uint8 mask (the study file's), got {mask.dtype}")
+        return self.engine.magnitude_overlay(flow, mask, *self._param(param), norm_f64, n, echo, lut)
 
 
 def _tail(src, engine):
@@ -1086,6 +1101,181 @@ def visualize_radlong(ds, param, save_dir, fps=30, av_filter_flag=True, av_savgo
         writer_factory = iio.get_writer
     os.makedirs(save_dir, exist_ok=True)
     save_path = os.path.join(save_dir, f"{ds.filename}_{param}_radlong_overlay.mp4")
+    writer = writer_factory(save_path, fps=fps)
+    for i in range(frames.shape[0]):
+        writer.append_data(frames[i])
+    writer.close()
+    return save_path
+
+
+# ---- the single-component video: the magnitude overlay of example_peak_plots.py:459-513 -----------------------------------------
+MAGNITUDE_COLORMAP_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "colormap_luts_magnitude.json")  # tools/make_magnitude_colormap_luts.py writes it
+
+
+def committed_magnitude_luts():
+    """{name: float64 [256,3]} from colormap_luts_magnitude.json, the second table file, in colormap_luts.json's format: 'hot', the
+    reference's colormap for the magnitude overlay (matplotlib's own table; its row 0 is (0.0416, 0, 0), not black)."""
+    import json
+    with open(MAGNITUDE_COLORMAP_FILE) as f:
+        return {name: np.array(rows, np.float64).reshape(256, 3) for name, rows in json.load(f)["luts"].items()}
+
+
+def magnitude_colormap_lut(name):
+    """colormap_lut for the magnitude overlay: from matplotlib when it is importable, else from the committed files, the magnitude
+    overlay's own ('hot') before the rad/long overlay's four.  An unknown name raises ValueError."""
+    try:
+        import matplotlib  # noqa: F401
+    except ImportError:
+        luts = {**committed_colormap_luts(), **committed_magnitude_luts()}
+        if name not in luts:
+            raise ValueError(f"{name!r} is not among the committed colormaps {sorted(luts)} and matplotlib is not importable") from None
+        return luts[name]
+    return colormap_lut(name)
+
+
+def norm_is_f64():
+    """Whether numpy, in this process, divides a float32 array in place by a np.float64 scalar in float64 (NEP 50, numpy >= 2: the
+    quotient is formed in float64 and rounded to float32 once) or rounds the scalar to float32 first (numpy 1.x's value-based
+    casting).  That is matplotlib's Normalize on a float32 frame: `resdat /= (vmax - vmin)` with vmin and vmax float64 scalars.
+    Probed by value: (1 + 2^-22) / (1 + 2^-24) is 1 + 2^-23 by the first rule and 1 + 2^-22 by the second."""
+    a = np.array([1 + 2.0 ** -22], np.float32)
+    a /= np.float64(1 + 2.0 ** -24)
+    return bool(a[0] == np.float32(1 + 2.0 ** -23))
+
+
+def magnitude_norm_index(mag, vmin, vmax, norm_f64):
+    """(t float32, idx uint8) of one float32 magnitude frame under Normalize(vmin, vmax) and a 256-entry colormap's lookup, as the
+    reference's numpy / matplotlib run them: t = (mag - vmin) / (vmax - vmin) with the float32 difference in the numerator and the
+    float64 difference of the extrema as divisor -- the quotient formed in float64 and rounded once (norm_f64) or the divisor rounded
+    to float32 first; t = 0 if vmin == vmax; idx = min(trunc(t * 256), 255) (t is in [0, 1] for a frame within the extrema)."""
+    mag = np.asarray(mag, np.float32)
+    vmin, vmax = np.float32(vmin), np.float32(vmax)
+    if vmin == vmax:
+        return np.zeros(mag.shape, np.float32), np.zeros(mag.shape, np.uint8)
+    d64 = np.float64(vmax) - np.float64(vmin)
+    s = mag - vmin
+    t = (s.astype(np.float64) / d64).astype(np.float32) if norm_f64 else s / np.float32(d64)
+    return t, np.minimum((t * np.float32(256)).astype(np.int64), 255).astype(np.uint8)
+
+
+def _magnitude(frame):
+    """np.sqrt(x**2 + y**2) of one float32 [H,W,2] frame: two rounded squares, a rounded sum, a rounded root"""
+    return np.sqrt(frame[..., 0] ** 2 + frame[..., 1] ** 2)
+
+
+def magnitude_overlay_host(field, n_used, echo, lut, norm_f64=None):
+    """The per-pixel part of the reference's single-component video in numpy, as the reference computes it but frame by frame, without
+    its [N,H,W,4] float64 colour array: (out uint8 [n_used,H,W,3], info float64 [2] = (vmin, vmax), frame_info float64 [n_used,2] =
+    each frame's (echo max, colour max)) from the float32 field [N,H,W,2] = get_masked_arr(param, label) over ALL the frames the
+    file stores, the echo [>= n_used,H,W] (float16 or uint8) and a [256,3] table.
+      mag = sqrt(x**2 + y**2) in float32; ONE Normalize(min mag, max mag) over all N frames, zeros outside the mask included;
+      frames [0, n_used) are rendered: magnitude_norm_index (norm_f64=None: norm_is_f64(), this process's numpy), then per frame
+      ((0.5 * (echo / max echo)) + (0.5 * (colour / max colour))) * 255 with the frame's own maxima, a maximum of 0 leaving its term
+      undivided; a float16 echo keeps float16 through its quotient and the product with 0.5, and the result is stored into a float16
+      array before uint8 truncates it (the reference's output array is np.zeros_like(gray2rgb(echo))); a uint8 echo divides in
+      float64 and truncates directly.
+    ValueError where the reference's cast is undefined: NaN or inf in the magnitude, a negative or non-finite echo value."""
+    field = np.asarray(field)
+    if field.dtype != np.float32 or field.ndim != 4 or field.shape[3] != 2 or min(field.shape) < 1:
+        raise ValueError(f"field must be float32 [N,H,W,2] with no empty side, got {field.dtype} {field.shape}")
+    N, H, W, _ = field.shape
+    n = int(n_used)
+    if not 1 <= n <= N:
+        raise ValueError(f"n_used must be in [1, {N}], got {n_used}")
+    lut = _check_lut(lut, "lut")
+    echo = np.asarray(echo)
+    if echo.dtype not in (np.float16, np.uint8):
+        raise ValueError(f"echo must be float16 or uint8, got {echo.dtype}")
+    if echo.ndim != 3 or echo.shape[0] < n or echo.shape[1:] != (H, W):
+        raise ValueError(f"echo must be [>= {n},{H},{W}], got shape {echo.shape}")
+    echo = echo[:n]
+    if echo.dtype == np.float16 and not (np.isfinite(echo).all() and (echo >= 0).all()):
+        raise ValueError("the echo holds a negative or non-finite value")
+    if norm_f64 is None:
+        norm_f64 = norm_is_f64()
+    vmin, vmax = np.float32(np.inf), np.float32(-np.inf)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for i in range(N):                                          # frame by frame: the float32 temporaries stay one frame large
+            m = _magnitude(field[i])
+            if not np.isfinite(m).all():
+                raise ValueError("the magnitude holds NaN or inf")
+            vmin, vmax = min(vmin, m.min()), max(vmax, m.max())
+    out = np.empty((n, H, W, 3), np.uint8)
+    frame_info = np.zeros((n, 2), np.float64)
+    for i in range(n):
+        _, idx = magnitude_norm_index(_magnitude(field[i]), vmin, vmax, norm_f64)
+        cmax = lut[np.bincount(idx.ravel(), minlength=256) > 0].max()
+        col = 0.5 * (lut / cmax if cmax > 0 else lut)
+        emax = np.max(echo[i])
+        pn = echo[i] / emax if emax > 0 else echo[i]                 # float16 / float16 stays float16; uint8 / uint8 is float64
+        v = ((0.5 * pn).astype(np.float64)[..., None] + col[idx]) * 255   # 0.5 * float16 stays float16
+        out[i] = (v.astype(np.float16) if echo.dtype == np.float16 else v).astype(np.uint8)
+        frame_info[i] = emax, cmax
+    return out, np.array([vmin, vmax], np.float64), frame_info
+
+
+def magnitude_overlay(ds, param, label, colormap="hot", *, engine=None, norm_f64=None, return_info=False):
+    """The frames the reference's example hands to the writer of its single-component video (example_peak_plots.py:459-513): uint8
+    [ds.nframes,H,W,3], the magnitude of get_masked_arr(param, label) through `colormap`, blended half and half with the echo image;
+    or None (logged) for an unknown param or label, mode 'otsu' or a study without echo, the reference's own refusals.  `colormap` is
+    a name (magnitude_colormap_lut; the reference's is 'hot') or a [256,3] table.  `ds` is the reference's OpticalFlowDataset, a
+    FlowStudy or a HeldStudy; the field and the norm's range are over all the frames the file stores (nframes + 2), the frames
+    rendered are the first ds.nframes.  norm_f64 chooses the norm's division rule (magnitude_norm_index); None takes this process's
+    numpy's (norm_is_f64).  Without `engine`, numpy (magnitude_overlay_host); with `engine` (a DenseFlow) everything per pixel runs on
+    the device (tf_magnitude_overlay) and only the frames come back; the resident planes of the engine's last projection stay as they
+    are.  Both give the same bytes, and both raise ValueError for NaN or inf in the magnitude and for a negative or non-finite echo
+    value.  return_info adds (vmin, vmax) and the per-frame (echo max, colour max) as second and third results."""
+    if not _valid(ds, param, label):
+        return None
+    if ds.mode == "otsu":
+        log.error("the magnitude overlay is not supported for mode='otsu'")
+        return None
+    tail = _tail(ds, engine)
+    n = int(ds.nframes)
+    if tail is not None and tail.held:
+        echo = None
+        if ds.n_echo < 1:
+            log.error("the study has no echo frames: no magnitude overlay")
+            return None
+        if ds.n_echo < n:
+            raise ValueError(f"echo must be [>= {n},{ds.shape[1]},{ds.shape[2]}], the held one has {ds.n_echo} frames")
+    else:
+        echo = ds.get_echo()
+        if echo is None:
+            log.error("the study has no echo frames: no magnitude overlay")
+            return None
+        echo = np.asarray(echo)
+        if echo.dtype not in (np.float16, np.uint8):
+            raise ValueError(f"echo must be float16 (the study file's) or uint8, got {echo.dtype}")
+    lut = _check_lut(magnitude_colormap_lut(colormap) if isinstance(colormap, str) else colormap, "colormap")
+    if norm_f64 is None:
+        norm_f64 = norm_is_f64()
+    if tail is None:
+        flow, mask = _study_arrays(ds, label)
+        N = np.shape(flow)[0]
+        if np.shape(mask)[0] < N:
+            raise ValueError(f"the {label!r} mask has {np.shape(mask)[0]} frames, fewer than the flow's {N} (the norm's range is over every frame)")
+        res = magnitude_overlay_host(param_field(flow, mask, param, ds.frame_rate, N), n, echo, lut, norm_f64)
+    else:
+        res = _device_overlay(lambda: tail.magnitude_overlay(param, label, n, echo, lut, norm_f64))
+    return res if return_info else res[0]
+
+
+def visualize_magnitude(ds, param, label, save_dir, fps=30, colormap="hot", *, engine=None, norm_f64=None, writer_factory=None):
+    """The single-component video of the reference's example (example_peak_plots.py:469-513): renders magnitude_overlay's frames and
+    writes them to <save_dir>/<stem>_<label>_<param>_single_overlay.mp4, one append_data call per frame, then close.  <stem> is
+    ds.filename less one trailing dot: OpticalFlowDataset's filename of an .hdf5 file keeps the dot of the extension, the example's
+    name does not.  Returns the path, or None under magnitude_overlay's refusals (nothing is written then).  writer_factory(path,
+    fps=) makes the writer; the default is imageio.v2.get_writer, imported when needed.  The encoding itself is the writer's."""
+    frames = magnitude_overlay(ds, param, label, colormap, engine=engine, norm_f64=norm_f64)
+    if frames is None:
+        return None
+    if writer_factory is None:
+        import imageio.v2 as iio
+        writer_factory = iio.get_writer
+    os.makedirs(save_dir, exist_ok=True)
+    stem = ds.filename[:-1] if ds.filename.endswith(".") else ds.filename
+    save_path = os.path.join(save_dir, f"{stem}_{label}_{param}_single_overlay.mp4")
     writer = writer_factory(save_path, fps=fps)
     for i in range(frames.shape[0]):
         writer.append_data(frames[i])

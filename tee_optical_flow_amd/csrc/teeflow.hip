@@ -28,6 +28,7 @@
 #include "teeflow_area.hip.h"
 #include "teeflow_polar.hip.h"
 #include "teeflow_overlay.hip.h"
+#include "teeflow_magoverlay.hip.h"
 #include "teeflow_segmentor.hip.h"
 #include "teeflow_inflate.hip.h"
 #include "pil_resample_tables.h"

@@ -79,7 +79,7 @@ struct TfKnobs {
     int coop_test_occ16 = -1, coop_test_occ8 = -1;   // tests: pretend the occupancy query answered this
     int coop_test_mute = 0;      // tests: block 0 of every co-resident launch never raises its flag -> its neighbours give up -> the call is repeated tiled
     int profile = 0;
-    int overlay_chunk_kib = 0;   // tests: tf_radlong_overlay's chunk of frames holds at most this many KiB instead of MASK_CHUNK_BYTES (0: that)
+    int overlay_chunk_kib = 0;   // tests: tf_radlong_overlay's and tf_magnitude_overlay's chunk of frames holds at most this many KiB instead of MASK_CHUNK_BYTES (0: that)
     int area_chunk_kib = 0;      // tests: tf_first_region_areas' chunk of frames likewise
     unsigned sor_coop_arm = 0;   // bumped by tf_set_tuning("sor_coop", non-zero): a lane that sees a new value in a job's knobs re-arms the form
 };
@@ -190,6 +190,7 @@ struct tf_handle : Engine {
            PRE_PO_META, PRE_PO_OUT,                                               //   meta words: rad/long's, polar's
            PRE_AN_HIST, PRE_AN_SEL,                                               // tf_radlong_hist, tf_radlong_select
            PRE_OV_IDX, PRE_OV_ECHO, PRE_OV_OUT, PRE_OV_META,                      // tf_radlong_overlay
+           PRE_MO_IDX, PRE_MO_ECHO, PRE_MO_OUT, PRE_MO_META,                      // tf_magnitude_overlay
            PRE_WA_VALS, PRE_WA_CNT, PRE_WA_OFF, PRE_WA_SUM, PRE_WA_BG,            // WASE: compacted products, block counts / offsets, piece
                                                                                   //   sums, per-flow backgrounds
            PRE_WS_FLOW, PRE_WS_OUT,                                               // a WASE study call (tf_calc_seq_*_wase): the solver's resident

@@ -178,3 +178,22 @@ TF_API int tf_held_radlong_overlay(tf_handle* h, const double* lut_rad, const do
     if (k.n_echo < h->anN) return fail(h, TF_ERR_INVALID_ARG, "tf_held_radlong_overlay: the held echo has %d frames, fewer than the planes' %d", k.n_echo, h->anN);
     return finish_host_call(h, radlong_overlay<ovl::ECHO_F16>(h, Src::on_device(k.echo), lut_rad, lut_long, out, info));
 }
+
+// (the field and the norm's range are over all N held frames, so the mask in `slot` must cover them all; n_used frames are rendered)
+TF_API int tf_held_magnitude_overlay(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, int norm_f64, const double* lut,
+                                     uint8_t* out, double* info, double* frame_info)
+{
+    const char* who = "tf_held_magnitude_overlay";
+    if (!h) return TF_ERR_INVALID_ARG;
+    if (!lut || !out || !info || !frame_info) return fail(h, TF_ERR_INVALID_ARG, "%s: null table or output pointer", who);
+    const tf_handle::Held::Mask* m = nullptr;
+    if (int rc = held_project_check(h, who, n_used, slot, param, spacing, &m)) return rc;
+    const tf_handle::Held& k = h->held;
+    if (m->n_frames < k.N)
+        return fail(h, TF_ERR_INVALID_ARG, "%s: the mask in slot %d has %d frames, fewer than the study's %d (the norm's range is over all of them)", who, slot, m->n_frames, k.N);
+    if (!k.echo) return fail(h, TF_ERR_INVALID_ARG, "%s: the held study has no echo", who);
+    if (k.n_echo < n_used) return fail(h, TF_ERR_INVALID_ARG, "%s: the held echo has %d frames, fewer than the %d asked for", who, k.n_echo, n_used);
+    if (int rc = check_magnitude_overlay(h, who, k.N, k.H, k.W, lut)) return rc;
+    return finish_host_call(h, magnitude_overlay<ovl::ECHO_F16>(h, Src::on_device(k.flow), 1, k.N, n_used, k.H, k.W, Src::on_device(m->p), m->C, param, spacing,
+                                                                grad_f64 ? 1 : 0, norm_f64 ? 1 : 0, Src::on_device(k.echo), lut, out, info, frame_info));
+}

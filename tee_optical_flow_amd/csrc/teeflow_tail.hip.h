@@ -1,5 +1,5 @@
 // The study tail's host code: everything around the solver -- frame conditioning, saliency, tf_clean_masks, tf_otsu_masks, the
-// segmentor's frame glue, tf_av_centroids, tf_first_region_areas, the rad/long and polar projections, histogram and radix select, the overlay, WASE, the study calls.  Included by teeflow.hip (one
+// segmentor's frame glue, tf_av_centroids, tf_first_region_areas, the rad/long and polar projections, histogram and radix select, the two overlays, WASE, the study calls.  Included by teeflow.hip (one
 // translation unit); the kernels are in the kernel headers.  The entry points here keep their device scratch in the handle's PRE_*
 // slots (grown on demand, never shrunk, freed with the handle), so they neither allocate nor free once a study's sizes have been seen.
 // The one exception is tf_submit_seq_rgb, whose conditioned frames are a buffer of the queued job (allocated per study, freed with it).
@@ -936,6 +936,120 @@ TF_API int tf_radlong_shape(tf_handle* h, int* shape)
     const bool have = h->anN >= 1 && !h->an_polar;
     shape[0] = have ? h->anN : 0; shape[1] = have ? h->anH : 0; shape[2] = have ? h->anW : 0;
     return TF_OK;
+}
+
+namespace {
+// tf_magnitude_overlay: the flow and the mask of all N frames are on the device for the whole call (uploaded into the projections'
+// upload scratch, or read where a held study keeps them); the indices (1 B per pixel of the n frames rendered), the per-frame words and
+// colour terms (64 B + 6 KiB per frame) are made for all frames at once; the echo upload and the output (eb + 3 B per pixel) go
+// through in chunks of as many frames as fit in MASK_CHUNK_BYTES (tests: the overlay_chunk_kib knob).  A study of one chunk uploads
+// its echo once; a longer one uploads it a second time for the compose pass.  The host waits once between the passes, for the
+// extrema and the flags that decide the refusals; the colour maxima are made on the device (k_mo_scale).  Nothing here touches the
+// resident analysis planes.
+template <int KIND>
+int magnitude_overlay(tf_handle* h, const Src& flow, int f16, int N, int n, int H, int W, const Src& mask, int C, int param, double spacing,
+                      int grad_f64, int norm_f64, const Src& echo, const double* lut, uint8_t* out, double* info, double* frame_info)
+{
+    using namespace mov;
+    using ET = typename ovl::Echo<KIND>::T;
+    const size_t HW = (size_t)H * W, eb = sizeof(ET);
+    const size_t flow_bytes = (size_t)N * HW * 2 * (f16 ? 2 : 4);
+    const int nf = chunk_frames(HW * (eb + 3), n, (size_t)n, h->overlay_chunk_kib > 0 ? (size_t)h->overlay_chunk_kib << 10 : MASK_CHUNK_BYTES);
+    const size_t out_dwords = ((size_t)nf * HW + 3) / 4 * 3;          // 3 dwords per run of 4 slots, whole runs: what k_mo_compose stores
+    HIPC(h, hipSetDevice(h->dev));
+    // meta: [0, 16) the study's Range, [64, 64 + 6144) the table, then FrameMeta [n], then the colour terms [n][256][3] f64
+    const size_t off_lut = 64, off_fm = off_lut + 768 * sizeof(double), off_col = off_fm + (size_t)n * sizeof(FrameMeta);
+    Pre pre(h);
+    uint8_t* uflow = flow.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_AN_FLOW, flow_bytes);
+    uint8_t* umask = mask.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_AN_MASK, (size_t)N * HW * C);
+    auto* didx = pre.get<uint8_t>(tf_handle::PRE_MO_IDX, (size_t)n * HW);
+    auto* uecho = echo.dev ? nullptr : pre.get<ET>(tf_handle::PRE_MO_ECHO, (size_t)nf * HW);
+    auto* dout = pre.get<unsigned>(tf_handle::PRE_MO_OUT, out_dwords);
+    auto* meta = pre.get<uint8_t>(tf_handle::PRE_MO_META, off_col + (size_t)n * 768 * sizeof(double));
+    if (pre.rc) return pre.rc;
+    Range* drng = (Range*)meta;
+    double* dlut = (double*)(meta + off_lut);
+    FrameMeta* dfm = (FrameMeta*)(meta + off_fm);
+    double* dcol = (double*)(meta + off_col);
+    const hipStream_t s = h->stream;
+    const dim3 blk(256);
+    const uint8_t* dflow = nullptr; const uint8_t* dmask = nullptr;
+    int rc;
+    if ((rc = src_to_device(h, flow, 0, flow_bytes, uflow, &dflow))) return rc;
+    if ((rc = src_to_device(h, mask, 0, (size_t)N * HW * C, umask, &dmask))) return rc;
+    const Range seed{~0u, 0u, 0u, 0u};
+    HIPC(h, hipMemcpyAsync(drng, &seed, sizeof seed, hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemcpyAsync(dlut, lut, 768 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPC(h, hipMemsetAsync(dfm, 0, (size_t)n * sizeof(FrameMeta), s));
+    const unsigned gpx = (unsigned)((HW + 255) / 256);
+    dispatch_param(param, f16, grad_f64, [&](auto pc, auto ft, auto gt) {
+        using FT = decltype(ft);
+        hipLaunchKernelGGL((k_mo_range<decltype(pc)::value, FT, decltype(gt)>), dim3(gpx < 256 ? gpx : 256, N), blk, 0, s, (const FT*)dflow, N, dmask, C,
+                           spacing, HW, drng);
+        hipLaunchKernelGGL((k_mo_index<decltype(pc)::value, FT, decltype(gt)>), dim3(gpx < 128 ? gpx : 128, n), blk, 0, s, (const FT*)dflow, N, dmask, C,
+                           spacing, HW, drng, norm_f64, didx, dfm);
+    });
+    HIPC(h, hipGetLastError());
+    const uint8_t* de = nullptr;                                      // the current chunk's echo
+    for (int f0 = 0; f0 < n; f0 += nf) {
+        const int nc = std::min(nf, n - f0);
+        if ((rc = src_to_device(h, echo, (size_t)f0 * HW * eb, (size_t)nc * HW * eb, uecho, &de))) return rc;
+        hipLaunchKernelGGL(k_mo_echo<KIND>, dim3(gpx < 64 ? gpx : 64, nc), blk, 0, s, (const ET*)de, HW, dfm + f0);
+        HIPC(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_mo_scale, dim3(n), blk, 0, s, dlut, dfm, dcol);
+    HIPC(h, hipGetLastError());
+    Range r;
+    std::vector<FrameMeta> fm((size_t)n);
+    HIPC(h, hipMemcpyAsync(&r, drng, sizeof r, hipMemcpyDeviceToHost, s));
+    HIPC(h, hipMemcpyAsync(fm.data(), dfm, fm.size() * sizeof(FrameMeta), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));                                 // (`seed` leaves scope after this, too)
+    if (r.bad) return fail(h, TF_ERR_INVALID_ARG, "tf_magnitude_overlay: the magnitude holds NaN or inf");
+    for (int f = 0; f < n; ++f)
+        if (fm[f].ebad) return fail(h, TF_ERR_INVALID_ARG, "tf_magnitude_overlay: the echo holds a negative or non-finite value");
+    for (int f0 = 0; f0 < n; f0 += nf) {
+        const int nc = std::min(nf, n - f0);
+        const size_t slots = (size_t)nc * HW;                         // nc <= nf: the runs of `slots` fit out_dwords
+        if (n > nf && (rc = src_to_device(h, echo, (size_t)f0 * HW * eb, slots * eb, uecho, &de))) return rc;
+        hipLaunchKernelGGL(k_mo_compose<KIND>, dim3((unsigned)((slots + 1023) / 1024)), blk, 0, s, didx + (size_t)f0 * HW, (const ET*)de, dfm + f0,
+                           dcol + (size_t)f0 * 768, HW, slots, dout);
+        HIPC(h, hipGetLastError());
+        HIPC(h, hipMemcpyAsync(out + (size_t)f0 * HW * 3, dout, slots * 3, hipMemcpyDeviceToHost, s));
+    }
+    HIPC(h, hipStreamSynchronize(s));
+    union { unsigned u; float f; } c;
+    c.u = r.lo; info[0] = (double)c.f;
+    c.u = r.hi; info[1] = (double)c.f;
+    for (int f = 0; f < n; ++f) { c.u = fm[f].emax; frame_info[2 * f] = (double)c.f; frame_info[2 * f + 1] = fm[f].cmax; }
+    return TF_OK;
+}
+
+// what tf_magnitude_overlay and its held twin check of the table and the frame size (h and lut are not null)
+int check_magnitude_overlay(tf_handle* h, const char* who, int N, int H, int W, const double* lut)
+{
+    for (int j = 0; j < 256 * 3; ++j)
+        if (!(lut[j] >= 0.0 && std::isfinite(lut[j]))) return fail(h, TF_ERR_INVALID_ARG, "%s: a colormap entry is negative or not finite", who);
+    if ((size_t)H * W > 0x7fffffffu / 8) return fail(h, TF_ERR_UNSUPPORTED, "%s: at most 2^28 - 1 pixels per frame", who);
+    if (N > 65535) return fail(h, TF_ERR_UNSUPPORTED, "%s: at most 65535 frames", who);                    // frames are grid.y
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_magnitude_overlay(tf_handle* h, const void* flow, int flow_is_f16, int N, int n_used, int H, int W, const uint8_t* mask, int mask_C,
+                                int param, double spacing, int grad_f64, int norm_f64, const void* echo, int echo_kind, const double* lut,
+                                uint8_t* out, double* info, double* frame_info)
+{
+    if (!h || !flow || !mask || !echo || !lut || !out || !info || !frame_info || N < 1 || n_used < 1 || H < 1 || W < 1 || n_used > N)
+        return TF_ERR_INVALID_ARG;
+    if ((mask_C != 1 && mask_C != 2) || param < TF_PARAM_VELOCITY || param > TF_PARAM_PWR) return TF_ERR_INVALID_ARG;
+    if (echo_kind != TF_ECHO_F16 && echo_kind != TF_ECHO_U8) return TF_ERR_INVALID_ARG;
+    if (param != TF_PARAM_VELOCITY && (N < 2 || !std::isfinite(spacing) || spacing == 0.0)) return TF_ERR_INVALID_ARG;   // np.gradient needs 2 frames
+    if (int rc = check_magnitude_overlay(h, "tf_magnitude_overlay", N, H, W, lut)) return rc;
+    const Src f = Src::on_host(flow), m = Src::on_host(mask), e = Src::on_host(echo);
+    const int f16 = flow_is_f16 ? 1 : 0, g64 = grad_f64 ? 1 : 0, n64 = norm_f64 ? 1 : 0;
+    return finish_host_call(h, echo_kind == TF_ECHO_F16
+        ? magnitude_overlay<ovl::ECHO_F16>(h, f, f16, N, n_used, H, W, m, mask_C, param, spacing, g64, n64, e, lut, out, info, frame_info)
+        : magnitude_overlay<ovl::ECHO_U8>(h, f, f16, N, n_used, H, W, m, mask_C, param, spacing, g64, n64, e, lut, out, info, frame_info));
 }
 
 // pinned host memory for results: a destination allocated here makes the host-pointer entry points copy out at PCIe

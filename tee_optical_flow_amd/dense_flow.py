@@ -609,7 +609,7 @@ class DenseFlow:
                    self._h, "tf_segmentor_classmap")
         return out
 
-    # ---- the consumer's tail.  Five calls have a host-pointer form and a held form (held_*, further down) over one private body; the two
+    # ---- the consumer's tail.  Six calls have a host-pointer form and a held form (held_*, further down) over one private body; the two
     # forms differ in the C function they name and in its leading arguments: host pointers and sizes, or the frame count and the slot ----
     def _centroids(self, fn, lead, n):
         cent = np.zeros((max(n, 0), 2), np.float64)
@@ -730,6 +730,56 @@ class DenseFlow:
             raise OpticalFlowCalculationError(f"echo must be [N,H,W] with no empty side, got shape {echo.shape}")
         return self._overlay("tf_radlong_overlay", lut_rad, lut_long, echo)
 
+    def _magnitude_overlay(self, fn, lead, shape, lut):
+        """The outputs of a magnitude overlay of shape = (n, H, W) and its call: -> (out uint8 [n,H,W,3] in pinned host memory, info
+        float64 [2] = (vmin, vmax), frame_info float64 [n,2] = each frame's (echo max, colour max))."""
+        lut = np.ascontiguousarray(lut, dtype=np.float64)
+        if lut.shape != (256, 3):
+            raise OpticalFlowCalculationError(f"lut must be [256,3], got shape {lut.shape}")
+        n, H, W = shape
+        out = self._pool.empty((n, H, W, 3), np.uint8)
+        info = np.zeros(2, np.float64)
+        frame_info = np.zeros((n, 2), np.float64)
+        _lib.check(getattr(self._L, fn)(self._h, *lead, lut.ctypes.data, out.ctypes.data, info.ctypes.data, frame_info.ctypes.data), self._h, fn)
+        return out, info, frame_info
+
+    def magnitude_overlay(self, flow, mask, param, spacing, grad_f64, norm_f64, n_used, echo, lut):
+        """tf_magnitude_overlay: the frames of the reference's single-component video (example_peak_plots.py:459-513): the float32
+        magnitude of OpticalFlowDataset's param field (param 0 velocity, 1 acceleration, 2 PWR) through the table `lut`, one norm over
+        all N frames, frames [0, n_used) rendered and blended half and half with the echo, each frame normalised by its own maxima.
+        flow float16 or float32 [N,H,W,2], mask bool or uint8 [>= N,H,W,C], echo float16 (the study file's) or uint8 [>= n_used,H,W],
+        lut float64 [256,3]; norm_f64 as analysis.norm_is_f64.  Returns (out uint8 [n_used,H,W,3], info, frame_info) as
+        _magnitude_overlay.  Leaves the resident planes of the last projection alone.  May be called while submitted studies are in
+        flight on this engine."""
+        flow = np.asarray(flow)
+        if flow.dtype not in (np.float16, np.float32):
+            flow = flow.astype(np.float32)
+        flow = np.ascontiguousarray(flow)
+        if flow.ndim != 4 or flow.shape[3] != 2 or min(flow.shape) < 1:
+            raise OpticalFlowCalculationError(f"flow must be [N,H,W,2], got {flow.shape}")
+        N, H, W, _ = flow.shape
+        n_used = int(n_used)
+        if not 1 <= n_used <= N:
+            raise OpticalFlowCalculationError(f"n_used must be in [1, {N}], got {n_used}")
+        if param not in (0, 1, 2):
+            raise OpticalFlowCalculationError(f"param must be 0 (velocity), 1 (acceleration) or 2 (PWR), got {param!r}")
+        if param != 0 and N < 2:
+            raise OpticalFlowCalculationError("the gradient needs at least 2 flow frames")
+        if param != 0 and not (np.isfinite(spacing) and spacing != 0):
+            raise OpticalFlowCalculationError(f"spacing must be finite and non-zero for the gradient, got {spacing!r}")
+        m = _mask_stack(np.asarray(mask)[:N], "mask")
+        if m.shape[:3] != (N, H, W):
+            raise OpticalFlowCalculationError(f"mask must be [>= {N},{H},{W},C] (the norm's range is over every frame), got {np.shape(mask)}")
+        echo = np.asarray(echo)
+        if echo.dtype not in (np.float16, np.uint8):
+            raise OpticalFlowCalculationError(f"echo must be float16 or uint8, got {echo.dtype}")
+        if echo.ndim != 3 or echo.shape[0] < n_used or echo.shape[1:] != (H, W):
+            raise OpticalFlowCalculationError(f"echo must be [>= {n_used},{H},{W}], got shape {echo.shape}")
+        echo = np.ascontiguousarray(echo[:n_used])
+        lead = (flow.ctypes.data, 1 if flow.dtype == np.float16 else 0, N, n_used, H, W, m.ctypes.data, m.shape[3], int(param), float(spacing),
+                1 if grad_f64 else 0, 1 if norm_f64 else 0, echo.ctypes.data, _lib.ECHO_F16 if echo.dtype == np.float16 else _lib.ECHO_U8)
+        return self._magnitude_overlay("tf_magnitude_overlay", lead, (n_used, H, W), lut)
+
     # ---- the statistics of the planes a projection left resident: what analysis.py's glue calls ------------------------------------
     def radlong_project(self, flow, centroids, return_arrays=False):
         """tf_radlong_project: the rad/long projection of a field given whole, flow [>= n,H,W,2] (made float32) and n centroids (row, col),
@@ -758,7 +808,7 @@ class DenseFlow:
 
     # ---- a study held on the device (include/teeflow.h, tf_hold_study): the file's payload uploaded once -- or left there by the solve
     # that made it -- and the consumer's tail reading it there.  The held_* methods are av_centroids, first_region_areas,
-    # radlong_project_param, polar_project_param and radlong_overlay with a mask label in the place of the mask array and no flow or
+    # radlong_project_param, polar_project_param, radlong_overlay and magnitude_overlay with a mask label in the place of the mask array and no flow or
     # echo array; results are the same bits --------------------------------------------------------------------------------------------
     def _held_shape(self):
         shape = (C.c_longlong * _lib.HELD_SHAPE_LEN)()
@@ -939,6 +989,16 @@ class DenseFlow:
         """radlong_overlay with the held study's echo, of the planes the last (held_)radlong_project_param call left on the device:
         -> (out uint8 [n,H,2W,3], info float64 [3])."""
         return self._overlay("tf_held_radlong_overlay", lut_rad, lut_long)
+
+    def held_magnitude_overlay(self, label, param, spacing, grad_f64, norm_f64, n_used, lut):
+        """magnitude_overlay of the held flow and echo and the held mask `label` (which covers every held frame): -> (out, info,
+        frame_info) as there.  An n_used the library will refuse sizes the outputs as one frame, so that the library's message is
+        the one raised."""
+        slot, n_used = self._held_slot(label), int(n_used)
+        s = self._held_shape()
+        n = n_used if 1 <= n_used <= s[0] else 1
+        lead = (n_used, slot, int(param), float(spacing), 1 if grad_f64 else 0, 1 if norm_f64 else 0)
+        return self._magnitude_overlay("tf_held_magnitude_overlay", lead, (n, int(s[1]), int(s[2])), lut)
 
     def wase_compensate(self, flows, bkgd_mask, scale=1.0):
         """Reference :647-652, 659 for every flow of a study at once, on the device: returns (flows - background[p]) * scale

@@ -55,7 +55,8 @@ extern "C" {
                               tf_radlong_overlay, tf_segmentor_input, tf_segmentor_classmap, and the float16 payload calls
                               (tf_calc_seq_rgb_f16, tf_submit_seq_rgb_f16, tf_calc_seq_saliency_f16, tf_echo_frames, tf_dbg_f16_round)
                               and the WASE study calls (tf_calc_seq_rgb_wase, tf_calc_seq_saliency_wase), and inflate on the device
-                              (tf_inflate, tf_hold_study_chunks, tf_hold_mask_chunks with the new struct tf_chunked) */
+                              (tf_inflate, tf_hold_study_chunks, tf_hold_mask_chunks with the new struct tf_chunked), and deflate on the
+                              device (tf_deflate, tf_deflate_array, tf_held_deflate) */
 
 enum {
     TF_OK = 0,
@@ -599,6 +600,34 @@ int tf_inflate(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uin
                uint8_t* out_host, int* status);
 int tf_hold_study_chunks(tf_handle* h, const tf_chunked* flow, const tf_chunked* echo);
 int tf_hold_mask_chunks(tf_handle* h, int slot, const tf_chunked* mask);
+
+/* ---- deflate on the device, the mirror of the above: a dataset's chunks, each into the zlib stream that zlib 1.2.11 writes for it at
+ *      level 9 (zlib.compress(chunk, 9): header 78 DA, memLevel 8, default strategy, Adler-32), byte for byte -- what a gzip-9 dataset's
+ *      write_direct_chunk takes, so the file is the one the host writes.  The match search runs one thread per input byte; the parse, the
+ *      Huffman trees and the bits run one thread per chunk.
+ * All three give the same outputs: the streams end to end in blob (host, blob_cap bytes; blob_cap must be at least n x
+ *   compressBound(chunk_bytes), compressBound(b) = b + (b >> 12) + (b >> 14) + (b >> 25) + 13, checked before any work), chunk i's
+ *   stream the len[i] bytes at blob + off[i], off ascending without gaps, status [n].  A status is 0, or 1 the stream passed
+ *   compressBound (zlib's never does), 2 a stored block of more than 65,535 bytes; a non-zero status fails the call (TF_ERR_UNSUPPORTED,
+ *   tf_last_error names the chunk).  A chunk has at most 16 MiB.
+ * tf_deflate: n chunks of chunk_bytes each, packed, in host memory (chunk_bytes 0: n empty streams).
+ * tf_deflate_array: a row-major host array of `ndim` (1..4) dimensions `shape` of elem_bytes (1, 2 or 4) byte elements, cut into chunks
+ *   of `chunk` elements per dimension as HDF5 stores them: whole chunks, zero beyond the array's edge, in row-major order of the chunk
+ *   grid; n must be the number of chunks, the product of ceil(shape[d] / chunk[d]).  coord [n][ndim]: each chunk's first element.  The
+ *   outputs with shape, chunk and elem_bytes are a tf_chunked that tf_hold_study_chunks / tf_hold_mask_chunks take back.
+ * tf_held_deflate: the same for an array of the held study, read where it is (nothing is uploaded, "tail_upload_bytes" stays): what =
+ *   TF_HELD_FLOW ([N][H][W][2], 2-byte elements, chunk[4]), TF_HELD_ECHO ([n_echo][H][W], 2-byte, chunk[3]) or TF_HELD_MASK (the mask
+ *   in `slot`, [n_frames][H][W][C], 1-byte, chunk[4]; slot is ignored otherwise).
+ * Every argument is checked before any GPU work.  Host-synchronous, on the handle's stream, like the tail calls.  Device scratch: about
+ *   12 bytes per input byte plus 192 KiB per chunk, in batches of chunks that keep it under 256 MiB, plus the blob and an uploaded array.
+ * tf_dbg_counter(h, "deflate_match_us" / "deflate_emit_us" / "chunk_kernel_us"): device time of the links and the match search, of the
+ *   parse, trees, bits and compaction, and of the gather into chunks, since the handle was made (HIP events). */
+enum { TF_HELD_FLOW = 0, TF_HELD_ECHO = 1, TF_HELD_MASK = 2 };
+int tf_deflate(tf_handle* h, const uint8_t* chunks, int n, uint32_t chunk_bytes, uint8_t* blob, uint64_t blob_cap, uint64_t* off, uint32_t* len, int* status);
+int tf_deflate_array(tf_handle* h, const void* array, int ndim, const int64_t* shape, const int64_t* chunk, int elem_bytes, int n, uint8_t* blob,
+                     uint64_t blob_cap, uint64_t* off, uint32_t* len, int64_t* coord, int* status);
+int tf_held_deflate(tf_handle* h, int what, int slot, const int64_t* chunk, int n, uint8_t* blob, uint64_t blob_cap, uint64_t* off, uint32_t* len,
+                    int64_t* coord, int* status);
 
 /* ---- multi-GPU: the single exchange step of the path.  The reference's loop is sequential
  *      (calculate_optical_flow.py:584-597); here pairs shard over the GPUs of a node with no data-path traffic during the

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "tf_held_radlong_project_param", "tf_held_polar_project_param", "tf_held_radlong_overlay",
     "tf_magnitude_overlay", "tf_held_magnitude_overlay",
     "tf_inflate", "tf_hold_study_chunks", "tf_hold_mask_chunks",
+    "tf_deflate", "tf_deflate_array", "tf_held_deflate",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -61,6 +62,9 @@ class TfStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved0"}
+
+
+HELD_FLOW, HELD_ECHO, HELD_MASK = 0, 1, 2      # tf_held_deflate's `what`
 
 
 class TfChunked(C.Structure):
@@ -179,6 +183,9 @@ def load():
     L.tf_held_radlong_overlay.argtypes = [vp, vp, vp, vp, vp]
     L.tf_held_magnitude_overlay.argtypes = [vp, i32, i32, i32, dbl, i32, i32, vp, vp, vp, vp]
     L.tf_inflate.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, vp, vp]
+    L.tf_deflate.argtypes = [vp, vp, i32, C.c_uint32, vp, C.c_uint64, vp, vp, vp]
+    L.tf_deflate_array.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, C.c_uint64, vp, vp, vp, vp]
+    L.tf_held_deflate.argtypes = [vp, i32, i32, vp, i32, vp, C.c_uint64, vp, vp, vp, vp]
     L.tf_hold_study_chunks.argtypes = [vp, C.POINTER(TfChunked), C.POINTER(TfChunked)]
     L.tf_hold_mask_chunks.argtypes = [vp, i32, C.POINTER(TfChunked)]
     L.tf_get_iters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]

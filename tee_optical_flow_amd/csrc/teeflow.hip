@@ -31,6 +31,7 @@
 #include "teeflow_magoverlay.hip.h"
 #include "teeflow_segmentor.hip.h"
 #include "teeflow_inflate.hip.h"
+#include "teeflow_deflate.hip.h"
 #include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include "teeflow_engine.hip.h"
@@ -230,6 +231,9 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "wase_study_kernel_us") v = (long long)(h->wase_kernel_ms * 1000.0);
     else if (n == "inflate_kernel_us") v = (long long)(h->inflate_kernel_ms * 1000.0);
     else if (n == "unchunk_kernel_us") v = (long long)(h->unchunk_kernel_ms * 1000.0);
+    else if (n == "deflate_match_us") v = (long long)(h->deflate_match_ms * 1000.0);
+    else if (n == "deflate_emit_us") v = (long long)(h->deflate_emit_ms * 1000.0);
+    else if (n == "chunk_kernel_us") v = (long long)(h->chunk_kernel_ms * 1000.0);
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;
@@ -485,6 +489,7 @@ TF_API int tf_wait(tf_handle* h, int ticket, tf_stats* st)
 #include "teeflow_held.hip.h"
 // inflate on the device: tf_inflate, and a study held from the gzip chunks of its file
 #include "teeflow_inflate_host.hip.h"
+#include "teeflow_deflate_host.hip.h"
 
 TF_API int tf_get_iters(tf_handle* h, int* out, size_t capacity_ints, size_t* written)
 {

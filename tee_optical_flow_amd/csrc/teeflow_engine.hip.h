@@ -199,11 +199,14 @@ struct tf_handle : Engine {
            PRE_ECHO,                                                              // the study's float16 `echo` (tf_echo_frames, the *_f16 calls)
            PRE_CH_GRAY,                                                           // tf_calc_chains_rgb: the conditioned frames of all its studies
            PRE_INF_BLOB, PRE_INF_TABLE, PRE_INF_OUT,                              // tf_inflate, tf_hold_*_chunks: compressed bytes, per-stream table, inflated chunks
+           PRE_DF_WORK, PRE_DF_TABLE, PRE_DF_BLOB, PRE_DF_SRC,                    // tf_deflate, tf_deflate_array, tf_held_deflate: a batch's scratch, per-chunk table,
+                                                                                  //   the streams end to end, an uploaded array
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
     double wase_kernel_ms = 0;   // device time of the last WASE study call's reduction and output kernels (the same events)
     double inflate_kernel_ms = 0, unchunk_kernel_ms = 0;   // device time of k_inflate / k_unchunk since the handle was made (the same events)
+    double deflate_match_ms = 0, deflate_emit_ms = 0, chunk_kernel_ms = 0;   // ... of deflate's links + search, emit + offsets + pack, and k_chunk
     // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
     // ([0]: upload done) and the device scratch ([1]: kernel done) of the last call may be written again
     void* seg_stage = nullptr; size_t seg_stage_cap = 0; hipEvent_t seg_ev[2] = {};

@@ -241,7 +241,9 @@ class DenseFlow:
         """Debug counters of the engine (tf_dbg_counter): coop_launches, coop_aborts, coop_disabled, coop_rearms, coop_cooldown, coop_occ16, coop_occ8,
         queue_jobs, queue_units_done, queue_units_skipped, queue_outstanding, queue_lanes, stream_retries, streams_serialised, chain_steps,
         saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels),
-        inflate_kernel_us, unchunk_kernel_us (device time of k_inflate / k_unchunk since the engine was made)."""
+        inflate_kernel_us, unchunk_kernel_us (device time of k_inflate / k_unchunk since the engine was made),
+        deflate_match_us, deflate_emit_us, chunk_kernel_us (device time of deflate's links and match search, of its parse, trees, bits and
+        compaction, and of k_chunk, since the engine was made)."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
     def _finish(self, st, chain_pairs=None):
@@ -938,6 +940,88 @@ class DenseFlow:
         m, keep = self._chunked(chunks, "mask", 4, (np.bool_, np.uint8))
         self._hold_mask("tf_hold_mask_chunks", label, (m.shape[1], m.shape[2]), m.shape[3], tuple(m.shape), lambda slot: self._L.tf_hold_mask_chunks(self._h, slot, C.byref(m)))
         del keep
+
+    # ---- deflate on the device (include/teeflow.h, tf_deflate): a dataset's chunks, each into the bytes of zlib.compress(chunk, 9) ----
+    @staticmethod
+    def deflate_bound(chunk_bytes):
+        """zlib's compressBound: the most bytes the stream of a chunk of chunk_bytes takes"""
+        b = int(chunk_bytes)
+        return b + (b >> 12) + (b >> 14) + (b >> 25) + 13
+
+    def _deflate_call(self, name, n, chunk_bytes, ndim, call):
+        """the outputs of the three deflate calls: (blob uint8 [total], off uint64 [n], len uint32 [n], coord int64 [n,ndim] or None)"""
+        blob = np.empty(max(n * self.deflate_bound(chunk_bytes), 1), np.uint8)
+        off, ln, status = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        coord = None if ndim is None else np.zeros((n, ndim), np.int64)
+        _lib.check(call(n, blob, off, ln, coord, status), self._h, name)
+        return blob[:int(ln.sum(dtype=np.uint64))].copy(), off, ln, coord
+
+    def deflate(self, chunks):
+        """Equal-sized chunks (a sequence of bytes-like objects of one length, or a C-contiguous uint8 [n,chunk_bytes] array) -> (blob,
+        off, len): chunk i's zlib stream is blob[off[i]:off[i] + len[i]], the bytes of zlib.compress(chunk, 9)."""
+        if isinstance(chunks, np.ndarray):
+            if chunks.dtype != np.uint8 or chunks.ndim != 2 or not chunks.flags.c_contiguous:
+                raise OpticalFlowCalculationError("chunks must be a C-contiguous uint8 [n,chunk_bytes] array or a sequence of bytes")
+            packed = chunks
+        else:
+            chunks = [bytes(c) for c in chunks]
+            if len({len(c) for c in chunks}) > 1:
+                raise OpticalFlowCalculationError("deflate takes chunks of one size per call")
+            packed = np.frombuffer(b"".join(chunks), np.uint8).reshape(len(chunks), len(chunks[0]) if chunks else 0)
+        n, cb = packed.shape
+        keep = packed if packed.size else np.zeros(1, np.uint8)
+        blob, off, ln, _ = self._deflate_call("tf_deflate", n, cb, None, lambda n_, b, o, l, c, s: self._L.tf_deflate(
+            self._h, keep.ctypes.data, n_, cb, b.ctypes.data, b.size, o.ctypes.data, l.ctypes.data, s.ctypes.data))
+        return blob, off, ln
+
+    @staticmethod
+    def _chunk_grid(shape, chunks, what):
+        shape, chunks = tuple(int(v) for v in shape), tuple(int(v) for v in chunks)
+        if not 1 <= len(shape) <= 4 or len(chunks) != len(shape) or min(shape + chunks) < 1:
+            raise OpticalFlowCalculationError(f"{what}: need 1 to 4 dimensions with no empty side and as many chunk extents, got {shape} in chunks of {chunks}")
+        return shape, chunks, int(np.prod([-(-s // c) for s, c in zip(shape, chunks)], dtype=np.int64))
+
+    @staticmethod
+    def _deflated_record(shape, dtype, chunks, blob, off, ln, coord):
+        """the outputs as a dataset record of analysis.chunks_record: what hold_study_chunks / hold_mask_chunks and the writer take"""
+        return {"shape": shape, "dtype": str(np.dtype(dtype)), "chunks": chunks, "coord": coord, "filter_mask": np.zeros(len(ln), np.uint32),
+                "off": off, "len": ln, "blob": blob}
+
+    def deflate_array(self, arr, chunks):
+        """An array of 1 to 4 dimensions with 1-, 2- or 4-byte elements, cut into chunks of `chunks` elements per dimension as HDF5
+        stores them (whole chunks, zero beyond the edge, in h5py's order) -> its dataset record (analysis.chunks_record's layout),
+        every chunk the bytes of zlib.compress(chunk, 9)."""
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype.itemsize not in (1, 2, 4):
+            raise OpticalFlowCalculationError(f"deflate_array takes 1-, 2- or 4-byte elements, got {arr.dtype}")
+        shape, chunks, n = self._chunk_grid(arr.shape, chunks, "deflate_array")
+        sh, ch = np.array(shape, np.int64), np.array(chunks, np.int64)
+        cb = int(np.prod(chunks, dtype=np.int64)) * arr.dtype.itemsize
+        out = self._deflate_call("tf_deflate_array", n, cb, len(shape), lambda n_, b, o, l, c, s: self._L.tf_deflate_array(
+            self._h, arr.ctypes.data, len(shape), sh.ctypes.data, ch.ctypes.data, arr.dtype.itemsize, n_, b.ctypes.data, b.size, o.ctypes.data, l.ctypes.data,
+            c.ctypes.data, s.ctypes.data))
+        return self._deflated_record(shape, arr.dtype, chunks, *out)
+
+    def held_deflate(self, what, chunks):
+        """deflate_array of an array of the held study, read where it is: what = "flow" (float16 [N,H,W,2]), "echo" (float16 [n,H,W]) or
+        the label of a held mask (bool [n,H,W,C]) -> its dataset record.  Nothing is uploaded."""
+        held = self._held_or_raise()
+        N, H, W, n_echo = (int(v) for v in held[:4])
+        if what == "flow":
+            kind, slot, shape, dt = _lib.HELD_FLOW, 0, (N, H, W, 2), np.float16
+        elif what == "echo":
+            if not n_echo:
+                raise OpticalFlowCalculationError("the held study has no echo")
+            kind, slot, shape, dt = _lib.HELD_ECHO, 0, (n_echo, H, W), np.float16
+        else:
+            slot = self._held_slot(what)
+            kind, shape, dt = _lib.HELD_MASK, (int(held[5 + 2 * slot]), H, W, int(held[6 + 2 * slot])), np.bool_
+        shape, chunks, n = self._chunk_grid(shape, chunks, "held_deflate")
+        ch = np.array(chunks, np.int64)
+        cb = int(np.prod(chunks, dtype=np.int64)) * np.dtype(dt).itemsize
+        out = self._deflate_call("tf_held_deflate", n, cb, len(shape), lambda n_, b, o, l, c, s: self._L.tf_held_deflate(
+            self._h, kind, slot, ch.ctypes.data, n_, b.ctypes.data, b.size, o.ctypes.data, l.ctypes.data, c.ctypes.data, s.ctypes.data))
+        return self._deflated_record(shape, dt, chunks, *out)
 
     def hold_next(self, on=True):
         """Arm (or disarm) the next study call to leave its payload held: what hold=True does for the calc_study_*_payload calls.  The

@@ -20,17 +20,41 @@ def _workers():
     return max(1, min(16, n))
 
 
-def create_gzip9(f, name, data, min_parallel_bytes=1 << 20):
+def auto_chunks(shape, dtype):
+    """the chunk shape h5py gives a gzip dataset of this shape and dtype (what create_gzip9's dataset will have), or None; asked of an
+    in-memory file, so that the chunks can be compressed before the study's file exists"""
+    import h5py
+    with h5py.File(f"auto_chunks_{os.getpid()}", "w", driver="core", backing_store=False) as f:
+        return f.create_dataset("d", shape=tuple(shape), dtype=dtype, compression="gzip", compression_opts=9).chunks
+
+
+def create_gzip9(f, name, data, min_parallel_bytes=1 << 20, deflater=None):
     """`f.create_dataset(name, data=data, compression="gzip", compression_opts=9)` (reference :405-472) with the deflate
     work spread over threads: same dataset for any reader (dtype, shape, h5py's auto chunk shape, filter pipeline, values),
     but the chunks are compressed with zlib level 9 in a thread pool (zlib releases the GIL) and handed to HDF5 with
     `write_direct_chunk`.  gzip-9 of a study's float16 flow is the slowest step of process_video once the flow itself
     takes milliseconds (63 MB: 2.4 s in h5py, 0.4 s here on 8 cores).  The effort is the reference's, always: the filter header says
-    gzip 9 and the chunk bytes are level-9 deflate streams (round 4's opt-in lower effort left that contract and is gone)."""
+    gzip 9 and the chunk bytes are level-9 deflate streams (round 4's opt-in lower effort left that contract and is gone).
+    `deflater`: a callable (name, data, chunk shape) -> the dataset's record in analysis.chunks_record's layout, every chunk a level-9
+    zlib stream of the whole chunk (DenseFlow.deflate_array / held_deflate make them on the device), or None where it leaves the
+    dataset to the host.  The record's chunks are written as they are and nothing is compressed here.  It is asked only where the
+    host would hand chunks over itself, from min_parallel_bytes on: a smaller dataset goes through HDF5's own filter either way, so
+    that the file's layout does not depend on who compressed it."""
     data = np.asarray(data)
     ds = f.create_dataset(name, shape=data.shape, dtype=data.dtype, compression="gzip", compression_opts=9)
     ch = ds.chunks
-    if data.nbytes < min_parallel_bytes or ch is None or data.ndim == 0 or not hasattr(ds.id, "write_direct_chunk"):
+    direct = data.nbytes >= min_parallel_bytes and ch is not None and data.ndim > 0 and hasattr(ds.id, "write_direct_chunk")
+    if deflater is not None and direct:
+        rec = deflater(name, data, ch)
+        if rec is not None:
+            if tuple(rec["shape"]) != data.shape or tuple(rec["chunks"]) != ch or np.dtype(rec["dtype"]) != data.dtype:
+                raise OpticalFlowError(f"the deflater's record of {name!r} is {rec['dtype']} {tuple(rec['shape'])} in chunks of {tuple(rec['chunks'])}, "
+                                       f"the dataset {data.dtype} {data.shape} in chunks of {ch}")
+            blob = np.asarray(rec["blob"], np.uint8)
+            for at, o, n in zip(np.asarray(rec["coord"]).reshape(-1, data.ndim), rec["off"], rec["len"]):
+                ds.id.write_direct_chunk(tuple(int(v) for v in at), blob[int(o):int(o) + int(n)].tobytes())
+            return ds
+    if not direct:
         ds[...] = data
         return ds
     offsets = list(itertools.product(*[range(0, s, c) for s, c in zip(data.shape, ch)]))
@@ -55,8 +79,9 @@ def create_gzip9(f, name, data, min_parallel_bytes=1 << 20):
 
 
 def save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, metadata, waveforms, patient_id, heart_rate, config,
-                              mode, no_saliency, include_waveforms, save_mask_subset=None, *, echo=None, nframes=None):
-    """`echo` (float16 [N,H,W] = rgb2gray(nparr).astype(float16), reference :400-402) and `nframes` may be handed over instead of
+                              mode, no_saliency, include_waveforms, save_mask_subset=None, *, echo=None, nframes=None, deflate=None):
+    """`deflate`: create_gzip9's `deflater`, asked for every dataset of the file (None: the host compresses them all).
+    `echo` (float16 [N,H,W] = rgb2gray(nparr).astype(float16), reference :400-402) and `nframes` may be handed over instead of
     `nparr` (process_folder's worker processes: the reader stage makes `echo`, the RGB frames need not travel to the writer)."""
     try:
         import h5py
@@ -68,7 +93,7 @@ def save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, metadata, w
     tmp_path = f"{save_path}.part{os.getpid()}"
     try:
         _write(h5py, tmp_path, flow_arr, nparr, mask_dict, metadata, waveforms, patient_id, heart_rate, config, mode, no_saliency,
-               include_waveforms, save_mask_subset, echo, nframes)
+               include_waveforms, save_mask_subset, echo, nframes, deflate)
         os.replace(tmp_path, save_path)
     finally:
         if os.path.exists(tmp_path):
@@ -76,11 +101,11 @@ def save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, metadata, w
 
 
 def _write(h5py, path, flow_arr, nparr, mask_dict, metadata, waveforms, patient_id, heart_rate, config, mode, no_saliency,
-           include_waveforms, save_mask_subset, echo=None, nframes=None):
+           include_waveforms, save_mask_subset, echo=None, nframes=None, deflate=None):
     nan = float("nan")
     with h5py.File(path, "w") as f:
-        create_gzip9(f, "echo", np.asarray(echo, dtype=np.float16) if echo is not None else rgb2gray(nparr).astype(np.float16))
-        fd = create_gzip9(f, "flow", np.asarray(flow_arr).astype(np.float16))
+        create_gzip9(f, "echo", np.asarray(echo, dtype=np.float16) if echo is not None else rgb2gray(nparr).astype(np.float16), deflater=deflate)
+        fd = create_gzip9(f, "flow", np.asarray(flow_arr).astype(np.float16), deflater=deflate)
         # missing metadata: same attribute names and float64 type as a complete study, value NaN (units_converted says so)
         fd.attrs["frame_rate"] = nan if metadata["frame_rate"] is None else metadata["frame_rate"]
         fd.attrs["nframes"] = int(nframes) if nframes is not None else nparr.shape[0]
@@ -100,13 +125,13 @@ def _write(h5py, path, flow_arr, nparr, mask_dict, metadata, waveforms, patient_
                      "pap": config.pap_sampling_rate}
             for k in ("art", "ecg", "cvp", "pap"):
                 if ex[k]:
-                    d = create_gzip9(f, k, np.asarray(waveforms[k][1]).astype(np.float16))
+                    d = create_gzip9(f, k, np.asarray(waveforms[k][1]).astype(np.float16), deflater=deflate)
                     d.attrs["sampling_rate"] = rates[k]
         if metadata.get("R_wave_data_present"):
-            create_gzip9(f, "RWaveTime", metadata["R_times"])
+            create_gzip9(f, "RWaveTime", metadata["R_times"], deflater=deflate)
         saved = []
         for k in mask_dict.keys():
             if save_mask_subset is None or k in save_mask_subset:
-                create_gzip9(f, k, mask_dict[k])
+                create_gzip9(f, k, mask_dict[k], deflater=deflate)
                 saved.append(k)
         fd.attrs["labels"] = saved

@@ -104,7 +104,7 @@ def flow_for_study(frames_u8, OF_model, mask_dict=None, bkgd_comp="none", conver
 
 
 def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency=False, saliency_map="f32", payload=False, echo=False, submit=False,
-                 chain=False):
+                 chain=False, hold=False):
     """The one place that picks a study's call on the model: -> collect, a callable that returns the study's flow array [N,H,W,2], scaled
     by `factor` and the last flow repeated (`payload`: the pair (float16 flow array, float16 echo or None) of the study file).  rgb: the
     study's uint8 RGB frames, or None; gray_frames: () -> the conditioned frames, asked for only where calc_batch is the model's all.
@@ -115,12 +115,13 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
     the scale on the host, in the reference's order (flow - background) * factor.
     `chain`: the same cell, chained (DenseFlow's chain=True: pair 0 from zero, pair k from pair k-1's flow; about N-1 single-pair solves
     per study).  The model is used with useInitialFlow set -- set here for the call where it is not, and put back: a submitted job
-    keeps the parameters it was queued with.  DeepFlow, or a model without `device_chain`, raises ConfigurationError."""
+    keeps the parameters it was queued with.  DeepFlow, or a model without `device_chain`, raises ConfigurationError.
+    `hold` (with `payload`, never with `submit`): the payload also stays held on the model's device (hold=True of its payload cells)."""
     _check_chain(chain, model)
     if chain and not model.getUseInitialFlow():
         model.setUseInitialFlow(True)
         try:
-            return _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency, saliency_map, payload, echo, submit, True)
+            return _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency, saliency_map, payload, echo, submit, True, hold)
         finally:
             model.setUseInitialFlow(False)
     if bkgd_comp not in ("WASE", "none"):
@@ -143,7 +144,9 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
     if payload or (rgb is not None and hasattr(model, cell) and (cell != "calc_study" or getattr(model, "device_unit_scale", False))):
         if payload:
             kw["echo"] = echo
-        if submit and cell in ("calc_study", "calc_study_payload") and hasattr(model, cell.replace("calc", "submit")):
+            if hold:
+                kw["hold"] = True
+        if submit and not hold and cell in ("calc_study", "calc_study_payload") and hasattr(model, cell.replace("calc", "submit")):
             # conditioning now, the solve queued on the engine's lanes: the next study's solve is on the GPU while this one finishes
             ticket = getattr(model, cell.replace("calc", "submit"))(rgb, scale=factor, pad_last=True, **kw)
             return lambda: model.wait(ticket)
@@ -196,6 +199,39 @@ def _payload_fallback(refused):
         logger.warning(f"payload='device' not used, the host casts flow and echo to float16 instead: {reason}")
 
 
+_DEFLATES = ("host", "device")
+_deflate_fallbacks = set()          # reasons already logged
+
+
+def _check_deflate(deflate, payload):
+    if deflate not in _DEFLATES:
+        raise ConfigurationError(f"deflate must be 'host' or 'device', not {deflate!r}")
+    if deflate == "device" and payload != "device":
+        raise ConfigurationError("deflate='device' compresses the payload the engine holds: it needs payload='device'")
+
+
+def _deflate_fallback(reason):
+    if reason not in _deflate_fallbacks:
+        _deflate_fallbacks.add(reason)
+        logger.warning(f"deflate='device' not used, the host compresses the file's chunks instead: {reason}")
+
+
+def _device_deflater(model, flow16, echo16):
+    """create_gzip9's `deflater` for a study whose payload `model` holds: the records of `flow` and `echo` from the held arrays
+    (held_deflate: nothing is uploaded), made now, while the study is held.  The masks stay with the host's thread pool, like the
+    waveforms and whatever else the file gets: a mask is long runs, where zlib skips what the device's search walks position by
+    position (profiles/r22_deflate.txt: the device is slower on masks than 16 host threads)."""
+    from .hdf5_out import auto_chunks
+    records = {"flow": model.held_deflate("flow", auto_chunks(flow16.shape, np.float16))}
+    if echo16 is not None:
+        records["echo"] = model.held_deflate("echo", auto_chunks(echo16.shape, np.float16))
+
+    def deflater(name, data, chunks):
+        rec = records.get(name)
+        return rec if rec is not None and tuple(rec["shape"]) == data.shape and tuple(rec["chunks"]) == tuple(chunks) and np.dtype(rec["dtype"]) == data.dtype else None
+    return deflater
+
+
 def _prep_frames(nparr, flipLR):
     """Reference :533-548: greyscale stacks become RGB, optional left-right flip."""
     nparr = np.asarray(nparr)
@@ -209,7 +245,7 @@ def _prep_frames(nparr, flipLR):
 def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                   no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                   config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host", chain=False):
+                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host", chain=False, deflate="host"):
     """Same positional signature as the reference (:478-483).  Keyword-only extras let a caller inject what the
     offline image cannot provide: `nparr` (frames instead of a DICOM), `metadata`, `mask_dict` (segmentation result),
     `flow_model`.  Returns the float32 flow array [N,H,W,2] that was written.  `payload="device"`: the engine hands over the file's
@@ -217,22 +253,28 @@ def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode=
     `device_payload` and, for WASE, `device_wase` --
     otherwise the host path, with one logged reason) and the float16 array that was written is returned; the file is the same.
     `chain=True` (OF_algo="TVL1"): the study's pairs are solved as a chain, each from the flow before it (_study_solve); the file's layout
-    and attributes are those of the plain solve."""
+    and attributes are those of the plain solve.
+    `deflate="device"` (needs payload="device"): the study is solved with hold=True and the file's gzip chunks are compressed on the
+    device: `flow` and `echo`, from the held payload (DenseFlow.held_deflate); the masks and the waveforms stay with the host's
+    threads (_device_deflater says why); the chunks are the bytes of zlib level 9 and a dataset under 1 MiB goes through HDF5's own filter
+    either way (create_gzip9), so the file is the one deflate="host" writes.  Where payload="device" does not
+    serve, or the model has no held_deflate, the host compresses, with one logged reason."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
-                                saliency_map=saliency_map, payload=payload, chain=chain)()
+                                saliency_map=saliency_map, payload=payload, chain=chain, deflate=deflate)()
 
 
 def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                          no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                          config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host", chain=False):
+                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host", chain=False, deflate="host"):
     """process_video in two halves: everything up to the flow solve, then a callable that collects the flows and does the rest (waveforms,
     hand-over to the HDF5 writer) and returns the flow array.  `_submit` (process_folder): where the engine offers it (gray-frame branch,
     no background compensation, a model the caller holds) the solve is only SUBMITTED here -- DenseFlow.submit_study, tf_submit_seq_rgb --
     so that the next study's solve is on the GPU while this one finishes."""
     _check_payload(payload)
+    _check_deflate(deflate, payload)
     _check_chain(chain, flow_model, OF_algo)
     if config is None:
         config = default_optical_flow_config()
@@ -265,6 +307,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     own = flow_model is None
     model = make_flow_model(OF_algo, config) if own else flow_model
     from_device = False                           # payload="device" serves: collect() -> (float16 flow array, float16 echo or None)
+    deflater = None                               # deflate="device" serves: the file's chunks are compressed already
     try:
         if mask_dict is None and mode == "otsu":
             # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
@@ -284,9 +327,15 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             # the reference's default branch (:559-560, :586): cv2.saliency.StaticSaliencyFineGrained on every frame
             raise OpticalFlowCalculationError(f"no_saliency=False needs uint8 RGB frames [N,H,W,3], got {nparr.dtype} {nparr.shape}")
         # the echo (from the upload the conditioning / saliency pass reads) only where a file is written
+        device_deflate = deflate == "device" and save_path is not None and _defer_save is None
+        if device_deflate and not (from_device and hasattr(model, "held_deflate")):
+            _deflate_fallback("payload='device' does not serve this study" if not from_device else f"the flow model ({type(model).__name__}) has no held_deflate")
+            device_deflate = False
         collect = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
                                conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=from_device,
-                               echo=save_path is not None, submit=_submit and not own, chain=chain)
+                               echo=save_path is not None, submit=_submit and not own, chain=chain, hold=device_deflate)
+        if device_deflate:                        # now, while the model holds the payload (and before a model of this call's own closes)
+            deflater = _device_deflater(model, *collect())
     finally:
         if own:
             model.close()
@@ -310,7 +359,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
                 _defer_save(job) if echo16 is None else _defer_save(job, echo16)
             else:
                 from .hdf5_out import save_optical_flow_to_hdf5
-                save_optical_flow_to_hdf5(*job, echo=echo16)
+                save_optical_flow_to_hdf5(*job, echo=echo16, deflate=deflater)
         return flows
     return finish
 

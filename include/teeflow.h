@@ -529,6 +529,15 @@ int tf_magnitude_overlay(tf_handle* h, const void* flow, int flow_is_f16, int N,
  *   uploaded; the call's host outputs are the same bytes as without.  The flag is spent by that call whether it succeeds or is
  *   refused.  Armed, a float32 study call or a submitted one (tf_submit_*) is refused with TF_ERR_UNSUPPORTED and a message.  The
  *   study held before goes once the armed call's arguments have passed; if the call fails after that, no study is held.
+ * tf_calc_seq_rgb_held: tf_calc_seq_rgb_f16 after tf_hold_next without the host arrays.  The plain RGB study (host uint8
+ *   [N][H][W][3]) is solved as that call solves it -- either solver, tf_chain_next honoured -- and its payload is left held: N float16
+ *   flow frames, the last one repeated, and (with_echo != 0) N echo frames.  No flow and no echo is copied to the host: each
+ *   sub-batch's flows are copied on the device by the engine that solved them, and the echo kernel writes into the held echo.
+ *   *st, tf_get_iters and every refusal are the float16 call's (N < 2, a null pointer, the solve calls' limits); both flags are
+ *   spent by the call, the study held before goes once the arguments have passed, and a call that fails after that holds nothing.
+ *   There is no submitted form.  tf_dbg_counter(h, "study_download_bytes"): the bytes of flow and echo that the study calls
+ *   (tf_calc_seq_rgb*, tf_calc_seq_saliency*, the *_wase calls) have copied device -> host since the handle was made, counted when
+ *   a synchronous call returns; this call adds nothing.
  * tf_held_shape: out[TF_HELD_SHAPE_LEN] = N, H, W, n_echo (all 0: none held), a generation number that grows with every replacement
  *   and release, then per slot (n_frames, C), both 0 for an empty slot.  No GPU work.
  * tf_release_study frees the buffers (tf_destroy does too).
@@ -549,6 +558,7 @@ int tf_magnitude_overlay(tf_handle* h, const void* flow, int flow_is_f16, int N,
 int tf_hold_study(tf_handle* h, const uint16_t* flow16, int N, int H, int W, const uint16_t* echo16, int n_echo);
 int tf_hold_mask(tf_handle* h, int slot, const uint8_t* mask, int n_frames, int C);
 int tf_hold_next(tf_handle* h, int on);
+int tf_calc_seq_rgb_held(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, int with_echo, tf_stats* st);
 int tf_held_shape(tf_handle* h, long long* out);
 int tf_release_study(tf_handle* h);
 int tf_held_av_centroids(tf_handle* h, int slot, int N, double* centroids_out, long long* area_out);
@@ -685,7 +695,7 @@ int tf_set_tuning(tf_handle* h, const char* name, int value);
 /* counters of the handle for tests and tools: "coop_launches" (launches of the co-resident SOR form since the handle was made),
  * "coop_aborts" (calls repeated with the tiled form because such a launch gave up waiting), "coop_disabled"; "queue_jobs", "queue_units_done",
  * "queue_units_failed", "queue_units_skipped" (sub-batches dropped because an earlier one of their call had failed), "queue_outstanding", "queue_lanes";
- * "tail_upload_bytes" (see tf_hold_study); -1 for an unknown name */
+ * "tail_upload_bytes" (see tf_hold_study), "study_download_bytes" (see tf_calc_seq_rgb_held); -1 for an unknown name */
 long long tf_dbg_counter(tf_handle* h, const char* name);
 /* DeepFlow hooks: one cv::VariationalRefinement::calcUV on dense float images (u, v updated in place); 3x3 Gaussian blur */
 int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v);

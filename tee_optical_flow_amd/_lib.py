@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "tf_calc_seq_rgb_f16", "tf_submit_seq_rgb_f16", "tf_calc_seq_saliency_f16", "tf_echo_frames", "tf_dbg_f16_round",
     "tf_calc_seq_rgb_wase", "tf_calc_seq_saliency_wase",
     "tf_calc_chains", "tf_calc_chains_device", "tf_calc_chains_rgb", "tf_dbg_chain_order",
-    "tf_hold_study", "tf_hold_mask", "tf_hold_next", "tf_held_shape", "tf_release_study", "tf_held_av_centroids", "tf_held_first_region_areas",
+    "tf_hold_study", "tf_hold_mask", "tf_hold_next", "tf_calc_seq_rgb_held", "tf_held_shape", "tf_release_study", "tf_held_av_centroids", "tf_held_first_region_areas",
     "tf_held_radlong_project_param", "tf_held_polar_project_param", "tf_held_radlong_overlay",
     "tf_magnitude_overlay", "tf_held_magnitude_overlay",
     "tf_inflate", "tf_hold_study_chunks", "tf_hold_mask_chunks",
@@ -168,6 +168,7 @@ def load():
     L.tf_hold_study.argtypes = [vp, vp, i32, i32, i32, vp, i32]
     L.tf_hold_mask.argtypes = [vp, i32, vp, i32, i32]
     L.tf_hold_next.argtypes = [vp, i32]
+    L.tf_calc_seq_rgb_held.argtypes = [vp, vp, i32, i32, i32, f32, i32, C.POINTER(TfStats)]
     L.tf_chain_next.argtypes = [vp, i32]
     # (the per-chain pointers and frame counts: ctypes arrays of c_void_p / c_int)
     L.tf_calc_chains.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, C.POINTER(TfStats)]

@@ -237,6 +237,7 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;
+    else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {
         v = 0;

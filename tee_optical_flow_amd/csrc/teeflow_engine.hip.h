@@ -234,6 +234,7 @@ struct tf_handle : Engine {
     bool hold_next = false;      // tf_hold_next: the next study call leaves its payload held
     bool chain_next = false;     // tf_chain_next: the next solve call, a sequence call, is solved as a chain (take_chain spends it)
     long long chain_steps = 0;   // pairs this handle and its lanes have solved as chain steps ("chain_steps" counter; the pool's lock where there is a pool)
+    long long study_download_bytes = 0;   // bytes of flow and echo the synchronous study calls have copied device -> host
     long long tail_upload_bytes = 0;   // bytes of flow, mask and echo the tail calls (and tf_hold_*) have copied host -> device
     // RCCL: one communicator rank per handle, its own stream, a small ring of completion events
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 0;

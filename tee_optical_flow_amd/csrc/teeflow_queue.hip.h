@@ -34,6 +34,7 @@ struct Call {
     bool f32 = false;            // the frames are float32 in [0,1] (CV_32F) instead of uint8
     bool out_f16 = false;        // the flows are written as float16 (the study file's type) instead of float32
     void* keep = nullptr;        // device memory that gets a copy of every flow, in the output type, made on the device (a held study's flow)
+    bool keep_only = false;      // the flows go to `keep` alone: `out` is null and nothing is copied out (tf_calc_seq_rgb_held; never W_OUT_DEV)
     const float* init = nullptr; // useInitialFlow (MODE_PAIRS): every pair's initial flow, float32 [H][W][2] in pixels per frame, where the
                                  // frames live (W_IN_DEV); may be `out` itself -- a pair's is read before its flow is written
     bool chain = false;          // useInitialFlow (MODE_SEQ, armed by tf_chain_next): pair 0 starts from zero, pair k from pair k-1's flow as
@@ -45,7 +46,7 @@ struct Call {
     Call part(int c0, int nb) const      // pairs [c0, c0+nb) of this call (sequence mode: from pair c0's first frame on)
     {
         Call p = *this; const size_t off = (size_t)c0 * frame_bytes();
-        p.in0 += off; if (in1) p.in1 += off; p.out = (uint8_t*)out + (size_t)c0 * flow_bytes(); p.n_pairs = nb;
+        p.in0 += off; if (in1) p.in1 += off; p.out = out ? (uint8_t*)out + (size_t)c0 * flow_bytes() : nullptr; p.n_pairs = nb;
         if (keep) p.keep = (uint8_t*)keep + (size_t)c0 * flow_bytes();
         if (init) p.init = init + (size_t)c0 * H * W * 2;
         return p;
@@ -87,13 +88,14 @@ int check_call(Engine* h, const Call& c)
 {
     if (!h) return TF_ERR_INVALID_ARG;
     if (c.mode == MODE_SEQ && c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "a sequence needs at least 2 frames, got %d", c.n_pairs + 1);
-    if (!c.in0 || (c.mode == MODE_PAIRS && !c.in1) || !c.out) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
+    if (!c.in0 || (c.mode == MODE_PAIRS && !c.in1) || (!c.out && !c.keep_only)) return fail(h, TF_ERR_INVALID_ARG, "null image/flow pointer");
     if (c.chain && c.mode != MODE_SEQ)
         return fail(h, TF_ERR_INVALID_ARG, "tf_chain_next arms a sequence call (tf_calc_seq*, tf_submit_seq*): a pairs call takes its initial "
                                             "flows itself (tf_calc_pairs_init); the flag is spent, call tf_chain_next again before the sequence call");
     if (c.H < 1 || c.W < 1 || c.n_pairs < 1) return fail(h, TF_ERR_INVALID_ARG, "bad sizes: pairs=%d H=%d W=%d", c.n_pairs, c.H, c.W);
     if ((long long)c.H * c.W > (1LL << 24)) return fail(h, TF_ERR_UNSUPPORTED, "images above 2^24 pixels are not supported");
     if (c.out_f16 && (c.where & W_OUT_DEV)) return fail(h, TF_ERR_UNSUPPORTED, "float16 flows go to host destinations only");
+    if (c.keep_only && (c.out || (c.where & W_OUT_DEV) || c.chains)) return fail(h, TF_ERR_INVALID_ARG, "a call that only keeps its flows takes no flow destination");
     if (c.init && c.mode == MODE_SEQ) return fail(h, TF_ERR_UNSUPPORTED, "a sequence call takes no initial flow");
     if (c.chain && (h->P.algo == TF_ALGO_DEEPFLOW || !h->P.use_initial_flow))      // (tf_chain_next refuses both: the flag was cleared since)
         return fail(h, TF_ERR_UNSUPPORTED, "a chained sequence needs a DualTVL1 handle with useInitialFlow set: set it, then tf_chain_next, then the call");
@@ -131,6 +133,7 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
 {
     const bool deep = h->P.algo == TF_ALGO_DEEPFLOW;
     HIPC(h, hipSetDevice(h->dev));
+    if (c.keep_only && !c.keep) return fail(h, TF_ERR_INVALID_ARG, "a call that only keeps its flows has nowhere to keep them");
     int rc = deep ? h->df.ensure(h, c.H, c.W, c.n_pairs) : h->tv.ensure(h, c.H, c.W, c.n_pairs);
     if (rc) return rc;
     const int step = deep ? h->df.cap : h->tv.cap;           // pairs per sub-batch
@@ -141,10 +144,11 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
     float ms_h2d = 0, ms_dev = 0, ms_d2h = 0;
     // Host destinations that are pinned (tf_host_alloc, hipHostMalloc, hipHostRegister) take the overlapped path: each
     // sub-batch is solved into one half of a double staging buffer and copied out on a second stream while the next one
-    // is being solved.  Pageable destinations keep the simple in-order path.
+    // is being solved.  Pageable destinations keep the simple in-order path.  A call that only keeps its flows (keep_only) solves
+    // into the one staging buffer and copies nothing out: the copy to `keep`, on this stream, is all that leaves it.
     bool overlap = false;
     const bool in_dev = c.where & W_IN_DEV, out_dev = c.where & W_OUT_DEV;
-    if (!out_dev) {
+    if (!out_dev && !c.keep_only) {
         hipPointerAttribute_t pa;
         if (hipPointerGetAttributes(&pa, c.out) == hipSuccess && pa.type == hipMemoryTypeHost) overlap = true;
         else (void)hipGetLastError();
@@ -202,7 +206,7 @@ int calc_common(Engine* h, const Call& c, int* iters, tf_stats* st)
             HIPC(h, hipStreamWaitEvent(h->copy_stream, h->cev[kb & 1], 0));
             HIPC(h, hipMemcpyAsync(p.out, dfl, (size_t)nb * flb, hipMemcpyDeviceToHost, h->copy_stream));
             HIPC(h, hipEventRecord(h->cev[2 + (kb & 1)], h->copy_stream));
-        } else if (!out_dev)
+        } else if (!out_dev && !c.keep_only)
             HIPC(h, hipMemcpyAsync(p.out, h->st_flow, (size_t)nb * flb, hipMemcpyDeviceToHost, h->stream));
         if (!deep)
             HIPC(h, hipMemcpyAsync(iters + (size_t)c0 * per_pair, h->tv.iters_dev, (size_t)nb * per_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));

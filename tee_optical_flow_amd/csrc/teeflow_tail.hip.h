@@ -83,11 +83,14 @@ int src_to_device(tf_handle* h, const Src& src, size_t off, size_t bytes, void* 
 
 // n pixels of uploaded RGB (device) -> their float16 `echo` values in the caller's host buffer, behind what is queued on the handle's
 // stream; the copy is done when the stream has been waited for.  decho: device scratch of at least n halves.  keep (device, or null):
-// gets the same halves by a copy on the device (a held study's echo).
+// gets the same halves by a copy on the device (a held study's echo).  Without a host buffer (echo16_out null) the kernel writes
+// straight into `keep`: no scratch, no copy.
 int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* decho, uint16_t* echo16_out, uint16_t* keep = nullptr)
 {
-    hipLaunchKernelGGL(k_echo_f16, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, drgb, n, decho);
+    if (!echo16_out && !keep) return TF_OK;
+    hipLaunchKernelGGL(k_echo_f16, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, drgb, n, echo16_out ? decho : keep);
     HIPC(h, hipGetLastError());
+    if (!echo16_out) return TF_OK;
     if (keep) HIPC(h, hipMemcpyAsync(keep, decho, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, h->stream));
     HIPC(h, hipMemcpyAsync(echo16_out, decho, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
     return TF_OK;
@@ -114,7 +117,7 @@ int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, c
     const int gx = (int)((npx + 255) / 256);
     hipLaunchKernelGGL(k_cond_minmax, dim3(gx < 512 ? gx : 512, N), dim3(256), 0, h->stream, drgb, npx, mm);
     hipLaunchKernelGGL(k_cond_norm, dim3(gx, N), dim3(256), 0, h->stream, drgb, npx, mm, dgray);
-    if (echo16_out) { const int rc = echo_from_device_rgb(h, drgb, (size_t)N * npx, decho, echo16_out, echo_keep); if (rc) return rc; }
+    if (echo16_out || echo_keep) { const int rc = echo_from_device_rgb(h, drgb, (size_t)N * npx, decho, echo16_out, echo_keep); if (rc) return rc; }
     HIPC(h, hipStreamSynchronize(h->stream));            // `init` leaves scope; the solve may run on other streams (lanes)
     *dgray_out = dgray;
     return TF_OK;
@@ -1163,6 +1166,8 @@ struct Study {
     void* flow_out; uint16_t* echo16_out;                // host: [N-1][H][W][2] of the output type; [N][H][W] halves or null
     bool wase = false;                                   // (flow - background) * scale, from the bkgd mask [n_frames][H][W][2]
     const uint8_t* bkgd = nullptr; int n_frames = 0; float* background_out = nullptr;   // (host, [N-1] or null)
+    bool held_only = false;                              // tf_calc_seq_rgb_held: the payload is left held and nothing is copied to the host
+    bool held_echo = false;                              // (flow_out and echo16_out are null); held_echo: with the study's echo
 };
 
 // the solver's frames of study s on the device (`own`: a submitted job's buffer for them, see condition_to_device)
@@ -1245,10 +1250,12 @@ int wase_study_tail(tf_handle* h, const Study& s, const float* dflow, bool hold)
 // Armed by tf_hold_next, a synchronous float16 call also leaves its payload held (teeflow_held.hip.h): N flow frames, the last one
 // repeated, and the echo if the call makes one, copied on the device from what the call wrote there.  The flag is spent by the call,
 // refused or not; the old held study goes once the call's arguments have passed, and a call that fails after that holds nothing.
+// A held-only study (Study::held_only) is such a call without the host copies: the lanes' copy-out is skipped (Call::keep_only) and
+// k_echo_f16 writes into the held echo itself.
 int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr, bool submit = false)
 {
     struct Owned { uint8_t* p = nullptr; ~Owned() { if (p) (void)hipFree(p); } } own;     // (freed after the failed call has been drained)
-    const bool hold = h && h->hold_next;
+    const bool hold = h && (h->hold_next || s.held_only);
     if (h) h->hold_next = false;
     const bool chain = h && h->chain_next;                   // tf_chain_next: spent likewise
     if (h) h->chain_next = false;
@@ -1264,6 +1271,7 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
         // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are); a WASE study's scale is k_wase_out's
         Call c{MODE_SEQ, s.frames, nullptr, s.N - 1, s.H, s.W, s.wase ? 1.0f : s.scale, s.flow_out, W_HOST, s.sees == FR_SAL_F32, s.out_f16};
         c.chain = chain;
+        c.keep_only = s.held_only;
         int rc = check_call(h, c);
         if (rc) return rc;
         if (submit && !ticket) return TF_ERR_INVALID_ARG;
@@ -1273,7 +1281,7 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
             HIPC(h, hipMalloc(&own.p, (size_t)s.N * s.H * s.W));
         }
         if (hold) {
-            if ((rc = held_alloc(h, s.N, s.H, s.W, s.echo16_out ? s.N : 0))) return rc;
+            if ((rc = held_alloc(h, s.N, s.H, s.W, s.echo16_out || s.held_echo ? s.N : 0))) return rc;
             holding = true;
         }
         rc = study_frames_to_device(h, s, own.p, &c.in0, hold ? h->held.echo : nullptr);
@@ -1284,6 +1292,8 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
         if (!s.wase) {
             if (hold) c.keep = h->held.flow;                  // each sub-batch's flows, copied on the device by the engine that solved them
             rc = calc_entry(h, c, st);
+            if (!rc && !s.held_only)                          // what the call has copied to the caller's arrays
+                h->study_download_bytes += (long long)(c.n_pairs * c.flow_bytes() + (s.echo16_out ? (size_t)s.N * s.H * s.W * sizeof(uint16_t) : 0));
             if (rc || !hold) return rc;
             if ((rc = held_repeat_last(h))) return rc;
             HIPC(h, hipStreamSynchronize(h->stream));
@@ -1294,7 +1304,10 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
         if (pre.rc) return pre.rc;
         c.out = dflow; c.where = W_DEV; c.out_f16 = false;
         rc = calc_entry(h, c, st);                            // (returns with every lane's stream drained: the flows are there)
-        return rc ? rc : wase_study_tail(h, s, dflow, hold);
+        if (!rc) rc = wase_study_tail(h, s, dflow, hold);
+        if (!rc) h->study_download_bytes += (long long)((size_t)c.n_pairs * s.H * s.W * 2 * (s.out_f16 ? sizeof(uint16_t) : sizeof(float))
+                                                        + (s.echo16_out ? (size_t)s.N * s.H * s.W * sizeof(uint16_t) : 0));
+        return rc;
     };
     const int rc = finish_host_call(h, run());
     if (rc && holding) h->held.release();
@@ -1319,6 +1332,13 @@ TF_API int tf_submit_seq_rgb_f16(tf_handle* h, const uint8_t* rgb, int N, int H,
                                  int* ticket)
 {
     return study_call(h, {rgb, N, H, W, 3, FR_GRAY, scale, true, flow16_out, echo16_out}, nullptr, ticket, true);
+}
+// tf_calc_seq_rgb_f16 after tf_hold_next without its host arrays: the study is solved into the held payload and nothing is downloaded
+TF_API int tf_calc_seq_rgb_held(tf_handle* h, const uint8_t* rgb, int N, int H, int W, float scale, int with_echo, tf_stats* st)
+{
+    Study s{rgb, N, H, W, 3, FR_GRAY, scale, true, nullptr, nullptr};
+    s.held_only = true; s.held_echo = with_echo != 0;
+    return study_call(h, s, st);
 }
 // Several RGB studies of one frame size as chains in lock-step (teeflow.hip, check_chains): each study is conditioned as tf_calc_seq_rgb
 // conditions it, one after the other into one scratch slot that holds all their gray frames; its echo, where asked for, comes from the same

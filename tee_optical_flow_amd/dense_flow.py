@@ -142,6 +142,7 @@ class DenseFlow:
     device_payload = True           # calc_study_payload & co. hand over the study file's float16 `flow` and `echo` (process_folder(payload="device"))
     device_chain = True             # calc_batch, calc_seq_device, submit_batch, submit_seq_device and every study form take chain=True (after setUseInitialFlow(True))
     device_chains = True            # calc_chains, calc_chains_device and calc_study_chains{,_payload} solve several chains of one frame size in lock-step
+    device_study_chunks = True      # study_chunks solves an RGB study into its `flow` and `echo` gzip-9 chunks, no float16 array downloaded (process_folder(deflate="device"))
     device_wase = True              # calc_study_wase & co. solve and compensate a bkgd_comp="WASE" study in one call, float32 or float16
 
     _SETTERS = {"Tau": "tau", "Lambda": "lambda", "Theta": "theta", "ScalesNumber": "nscales",
@@ -243,7 +244,8 @@ class DenseFlow:
         saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels),
         inflate_kernel_us, unchunk_kernel_us (device time of k_inflate / k_unchunk since the engine was made),
         deflate_match_us, deflate_emit_us, chunk_kernel_us (device time of deflate's links and match search, of its parse, trees, bits and
-        compaction, and of k_chunk, since the engine was made)."""
+        compaction, and of k_chunk, since the engine was made), study_download_bytes (bytes of flow and echo the study calls have
+        copied to the host; calc_study_held and study_chunks add nothing), tail_upload_bytes."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
     def _finish(self, st, chain_pairs=None):
@@ -486,6 +488,27 @@ class DenseFlow:
         """calc_study_payload without waiting: -> ticket; `wait(ticket)` returns the (flow16, echo16 | None) pair.  The frames are
         conditioned and the echo is complete before this returns (nparr may be reused at once)."""
         return self._study(nparr, scale, pad_last, f16=True, echo=echo, submit=True, chain=chain)
+
+    def calc_study_held(self, nparr, scale=1.0, echo=True, chain=False):
+        """calc_study_payload(hold=True) without its arrays: the RGB study uint8 [N,H,W,3] is solved into the held payload (N float16
+        flow frames, the last one repeated; the echo if asked for) and nothing is downloaded.  Returns nothing; `last_stats` and
+        last_iters() are the float16 call's, and `held` describes the study afterwards.  For a consumer that wants the payload's
+        compressed chunks (study_chunks) or its statistics (the held_* calls), not the arrays."""
+        nparr = self._rgb_study(nparr)
+        N, H, W, _ = nparr.shape
+        st = _lib.TfStats()
+        if chain:
+            self.chain_next()
+        _lib.check(self._L.tf_calc_seq_rgb_held(self._h, nparr.ctypes.data, N, H, W, float(scale), 1 if echo else 0, C.byref(st)), self._h,
+                   "tf_calc_seq_rgb_held")
+        self._finish(st)
+
+    def study_chunks(self, nparr, scale, flow_chunks, echo_chunks=None, chain=False):
+        """The study file's `flow` and `echo` datasets as gzip-9 chunks, with no float16 array on the host: calc_study_held, then
+        held_deflate("flow", flow_chunks) and, where echo_chunks is given, held_deflate("echo", echo_chunks).  -> {"flow": record,
+        "echo": record or None}, the records in analysis.chunks_record's layout.  The study stays held."""
+        self.calc_study_held(nparr, scale, echo=echo_chunks is not None, chain=chain)
+        return {"flow": self.held_deflate("flow", flow_chunks), "echo": None if echo_chunks is None else self.held_deflate("echo", echo_chunks)}
 
     def saliency_frames(self, nparr, dtype=np.float32):
         """cv2.saliency.StaticSaliencyFineGrained_create().computeSaliency(frame)[1] for every frame, on the device (reference

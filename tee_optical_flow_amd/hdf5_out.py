@@ -28,7 +28,23 @@ def auto_chunks(shape, dtype):
         return f.create_dataset("d", shape=tuple(shape), dtype=dtype, compression="gzip", compression_opts=9).chunks
 
 
-def create_gzip9(f, name, data, min_parallel_bytes=1 << 20, deflater=None):
+MIN_PARALLEL_BYTES = 1 << 20        # create_gzip9 hands chunks over itself from this size on; a smaller dataset goes through HDF5's own filter
+
+
+class Described:
+    """A dataset that reaches the writer as its deflater's record alone: shape and dtype, no values (process_folder(deflate="device"):
+    the float16 `flow` and `echo` never exist on the host).  create_gzip9 writes it from the record and raises where there is none."""
+
+    def __init__(self, shape, dtype):
+        self.shape, self.dtype = tuple(int(v) for v in shape), np.dtype(dtype)
+        self.ndim = len(self.shape)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+
+    def __repr__(self):
+        return f"Described({self.shape}, {self.dtype})"
+
+
+def create_gzip9(f, name, data, min_parallel_bytes=MIN_PARALLEL_BYTES, deflater=None):
     """`f.create_dataset(name, data=data, compression="gzip", compression_opts=9)` (reference :405-472) with the deflate
     work spread over threads: same dataset for any reader (dtype, shape, h5py's auto chunk shape, filter pipeline, values),
     but the chunks are compressed with zlib level 9 in a thread pool (zlib releases the GIL) and handed to HDF5 with
@@ -39,8 +55,12 @@ def create_gzip9(f, name, data, min_parallel_bytes=1 << 20, deflater=None):
     zlib stream of the whole chunk (DenseFlow.deflate_array / held_deflate make them on the device), or None where it leaves the
     dataset to the host.  The record's chunks are written as they are and nothing is compressed here.  It is asked only where the
     host would hand chunks over itself, from min_parallel_bytes on: a smaller dataset goes through HDF5's own filter either way, so
-    that the file's layout does not depend on who compressed it."""
-    data = np.asarray(data)
+    that the file's layout does not depend on who compressed it.
+    `data` may be a Described (shape and dtype, no values): then the deflater's record is all there is, and a dataset it does not
+    supply, or one that would not be asked of it, raises OpticalFlowError."""
+    described = isinstance(data, Described)
+    if not described:
+        data = np.asarray(data)
     ds = f.create_dataset(name, shape=data.shape, dtype=data.dtype, compression="gzip", compression_opts=9)
     ch = ds.chunks
     direct = data.nbytes >= min_parallel_bytes and ch is not None and data.ndim > 0 and hasattr(ds.id, "write_direct_chunk")
@@ -54,6 +74,10 @@ def create_gzip9(f, name, data, min_parallel_bytes=1 << 20, deflater=None):
             for at, o, n in zip(np.asarray(rec["coord"]).reshape(-1, data.ndim), rec["off"], rec["len"]):
                 ds.id.write_direct_chunk(tuple(int(v) for v in at), blob[int(o):int(o) + int(n)].tobytes())
             return ds
+    if described:
+        raise OpticalFlowError(f"dataset {name!r} ({data.dtype} {data.shape}) came without its values and "
+                               + ("the deflater has no record of it" if deflater is not None and direct else
+                                  "is not one the deflater is asked for" if deflater is not None else "without a deflater"))
     if not direct:
         ds[...] = data
         return ds
@@ -81,6 +105,7 @@ def create_gzip9(f, name, data, min_parallel_bytes=1 << 20, deflater=None):
 def save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, metadata, waveforms, patient_id, heart_rate, config,
                               mode, no_saliency, include_waveforms, save_mask_subset=None, *, echo=None, nframes=None, deflate=None):
     """`deflate`: create_gzip9's `deflater`, asked for every dataset of the file (None: the host compresses them all).
+    `flow_arr` and `echo` may each be a Described (shape and dtype) where `deflate` supplies the dataset's record.
     `echo` (float16 [N,H,W] = rgb2gray(nparr).astype(float16), reference :400-402) and `nframes` may be handed over instead of
     `nparr` (process_folder's worker processes: the reader stage makes `echo`, the RGB frames need not travel to the writer)."""
     try:
@@ -104,8 +129,9 @@ def _write(h5py, path, flow_arr, nparr, mask_dict, metadata, waveforms, patient_
            include_waveforms, save_mask_subset, echo=None, nframes=None, deflate=None):
     nan = float("nan")
     with h5py.File(path, "w") as f:
-        create_gzip9(f, "echo", np.asarray(echo, dtype=np.float16) if echo is not None else rgb2gray(nparr).astype(np.float16), deflater=deflate)
-        fd = create_gzip9(f, "flow", np.asarray(flow_arr).astype(np.float16), deflater=deflate)
+        create_gzip9(f, "echo", echo if isinstance(echo, Described) else np.asarray(echo, dtype=np.float16) if echo is not None
+                     else rgb2gray(nparr).astype(np.float16), deflater=deflate)
+        fd = create_gzip9(f, "flow", flow_arr if isinstance(flow_arr, Described) else np.asarray(flow_arr).astype(np.float16), deflater=deflate)
         # missing metadata: same attribute names and float64 type as a complete study, value NaN (units_converted says so)
         fd.attrs["frame_rate"] = nan if metadata["frame_rate"] is None else metadata["frame_rate"]
         fd.attrs["nframes"] = int(nframes) if nframes is not None else nparr.shape[0]

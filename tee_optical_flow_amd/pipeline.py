@@ -216,20 +216,68 @@ def _deflate_fallback(reason):
         logger.warning(f"deflate='device' not used, the host compresses the file's chunks instead: {reason}")
 
 
+def _held_records(model, flow_shape, echo_shape):
+    """{"flow": record, "echo": record} of the study `model` holds (held_deflate: nothing is uploaded), in the chunks h5py gives the
+    datasets; made now, while the study is held."""
+    from .hdf5_out import auto_chunks
+    records = {"flow": model.held_deflate("flow", auto_chunks(flow_shape, np.float16))}
+    if echo_shape is not None:
+        records["echo"] = model.held_deflate("echo", auto_chunks(echo_shape, np.float16))
+    return records
+
+
 def _device_deflater(model, flow16, echo16):
-    """create_gzip9's `deflater` for a study whose payload `model` holds: the records of `flow` and `echo` from the held arrays
-    (held_deflate: nothing is uploaded), made now, while the study is held.  The masks stay with the host's thread pool, like the
+    """create_gzip9's `deflater` for a study whose payload `model` holds: the records of `flow` and `echo` from the held arrays.  The
+    masks stay with the host's thread pool, like the
     waveforms and whatever else the file gets: a mask is long runs, where zlib skips what the device's search walks position by
     position (profiles/r22_deflate.txt: the device is slower on masks than 16 host threads)."""
-    from .hdf5_out import auto_chunks
-    records = {"flow": model.held_deflate("flow", auto_chunks(flow16.shape, np.float16))}
-    if echo16 is not None:
-        records["echo"] = model.held_deflate("echo", auto_chunks(echo16.shape, np.float16))
+    records = _held_records(model, flow16.shape, None if echo16 is None else echo16.shape)
 
     def deflater(name, data, chunks):
         rec = records.get(name)
         return rec if rec is not None and tuple(rec["shape"]) == data.shape and tuple(rec["chunks"]) == tuple(chunks) and np.dtype(rec["dtype"]) == data.dtype else None
     return deflater
+
+
+def _records_deflater(records):
+    """create_gzip9's `deflater` over records made elsewhere (the walk's writer stage): a dataset's record as it is -- one that does not
+    fit its dataset is create_gzip9's to refuse -- and None for every other dataset (masks, waveforms: the host's threads)."""
+    return lambda name, data, chunks: records.get(name)
+
+
+def _walk_deflate_route(model, from_device, nparr, plain):
+    """How the walk gets a study's `flow` and `echo` chunks from the device: ("chunks", None) -- study_chunks, a plain RGB study on a
+    model with `device_study_chunks`: no float16 array on the host --, ("hold", None) -- the payload call with hold=True, then
+    held_deflate --, or (None, the reason the host compresses this study)."""
+    from .hdf5_out import MIN_PARALLEL_BYTES
+    if not (nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8):
+        return None, "the frames are not uint8 RGB [N,H,W,3]"
+    chunks = plain and getattr(model, "device_study_chunks", False) and hasattr(model, "study_chunks")
+    if not getattr(model, "device_payload", False) or not (chunks or hasattr(model, "held_deflate")):
+        return None, f"the flow model ({type(model).__name__}) has neither study_chunks nor held_deflate"
+    if not from_device:
+        return None, "payload='device' does not serve this study"
+    if int(np.prod(nparr.shape[:3])) * 2 < MIN_PARALLEL_BYTES:      # (`echo`, half of `flow`: the record route has no array for HDF5's filter)
+        return None, "`flow` or `echo` is under create_gzip9's min_parallel_bytes and goes through HDF5's own filter"
+    return ("chunks" if chunks else "hold"), None
+
+
+def _solve_study_chunks(model, rgb, factor, chain):
+    """model.study_chunks in the chunks h5py gives the study's datasets (chain: as _study_solve arms it)"""
+    from .hdf5_out import auto_chunks
+    _check_chain(chain, model)
+    N, H, W = rgb.shape[:3]
+    fc, ec = auto_chunks((N, H, W, 2), np.float16), auto_chunks((N, H, W), np.float16)
+    if not chain:
+        return model.study_chunks(rgb, factor, fc, ec)
+    was = model.getUseInitialFlow()
+    if not was:
+        model.setUseInitialFlow(True)
+    try:
+        return model.study_chunks(rgb, factor, fc, ec, chain=True)
+    finally:
+        if not was:
+            model.setUseInitialFlow(False)
 
 
 def _prep_frames(nparr, flipLR):
@@ -308,6 +356,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     model = make_flow_model(OF_algo, config) if own else flow_model
     from_device = False                           # payload="device" serves: collect() -> (float16 flow array, float16 echo or None)
     deflater = None                               # deflate="device" serves: the file's chunks are compressed already
+    records = None                                # ... in the walk: {"flow": record, "echo": record}, all the writer stage gets of the two
     try:
         if mask_dict is None and mode == "otsu":
             # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
@@ -331,17 +380,35 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
         if device_deflate and not (from_device and hasattr(model, "held_deflate")):
             _deflate_fallback("payload='device' does not serve this study" if not from_device else f"the flow model ({type(model).__name__}) has no held_deflate")
             device_deflate = False
-        collect = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
-                               conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=from_device,
-                               echo=save_path is not None, submit=_submit and not own, chain=chain, hold=device_deflate)
+        # the walk (process_folder(deflate="device")): the study is solved now, synchronously, and its chunks are made while it is held
+        route = None
+        if deflate == "device" and save_path is not None and _defer_save is not None:
+            route, why = _walk_deflate_route(model, from_device, nparr, no_saliency and bkgd_comp == "none")
+            if route is None:
+                _deflate_fallback(why)
+        if route == "chunks":
+            records = _solve_study_chunks(model, np.ascontiguousarray(nparr), conversion_factor, chain)
+            collect = None
+        else:
+            collect = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
+                                   conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=from_device,
+                                   echo=save_path is not None, submit=_submit and not own and route is None, chain=chain,
+                                   hold=device_deflate or route == "hold")
         if device_deflate:                        # now, while the model holds the payload (and before a model of this call's own closes)
             deflater = _device_deflater(model, *collect())
+        elif route == "hold":                     # (the arrays the call returned go here: the writer stage gets the records)
+            records = _held_records(model, nparr.shape[:3] + (2,), nparr.shape[:3])
+            collect = None
     finally:
         if own:
             model.close()
 
     def finish():
-        flows, echo16 = collect() if from_device else (collect(), None)
+        if records is not None:
+            from .hdf5_out import Described
+            flows, echo16 = Described(nparr.shape[:3] + (2,), np.float16), Described(nparr.shape[:3], np.float16)
+        else:
+            flows, echo16 = collect() if from_device else (collect(), None)
         # waveforms (reference :602-620): loaded and validated by the reference's rules unless the caller injected a result dict;
         # without a valid ECG and a valid arterial waveform the whole block is dropped (waveforms_present = False)
         waveform_results, with_waveforms = {}, include_waveforms
@@ -355,8 +422,12 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
                    config, mode, no_saliency, with_waveforms, save_mask_subset)
             if _defer_save is not None:
                 # process_folder: the writer stage takes it while the next study is solved.  The hook is called with the job alone, as
-                # ever, unless the engine made the echo (payload="device"): only then does it get a second argument
-                _defer_save(job) if echo16 is None else _defer_save(job, echo16)
+                # ever, unless the engine made the echo (payload="device"): only then does it get a second argument -- and a third
+                # where the device made the chunks too: then `flows` and the echo are descriptions (hdf5_out.Described), not arrays
+                if records is not None:
+                    _defer_save(job, echo16, records)
+                else:
+                    _defer_save(job) if echo16 is None else _defer_save(job, echo16)
             else:
                 from .hdf5_out import save_optical_flow_to_hdf5
                 save_optical_flow_to_hdf5(*job, echo=echo16, deflate=deflater)
@@ -538,8 +609,10 @@ def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead
     return nparr, md, pid, hr, masks_ahead, echo
 
 
-def _save_study_shm(job, echo, nframes):
-    """Writer stage in a worker process: map what arrived as descriptors, write the file, drop the mappings (the owner unlinks)."""
+def _save_study_shm(job, echo, nframes, records=None):
+    """Writer stage in a worker process: map what arrived as descriptors, write the file, drop the mappings (the owner unlinks).
+    `records` (deflate="device"): the records of `flow` and `echo`, their blobs as descriptors too; flow_arr and echo are then
+    hdf5_out.Described."""
     from .hdf5_out import save_optical_flow_to_hdf5
     blocks = []
     try:
@@ -548,8 +621,12 @@ def _save_study_shm(job, echo, nframes):
         nparr = _shm_get(nparr, blocks)
         mask_dict = {k: _shm_get(v, blocks) for k, v in mask_dict.items()}
         echo = _shm_get(echo, blocks)
-        save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, *rest, echo=echo, nframes=nframes)
-        del flow_arr, nparr, mask_dict, echo
+        deflate = None
+        if records is not None:
+            records = {k: dict(rec, blob=_shm_get(rec["blob"], blocks)) for k, rec in records.items()}
+            deflate = _records_deflater(records)
+        save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, *rest, echo=echo, nframes=nframes, deflate=deflate)
+        del flow_arr, nparr, mask_dict, echo, records, deflate
     finally:
         _shm_release(blocks, unlink=False)
 
@@ -672,7 +749,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                    include_waveforms=False, waveform_folder=None, pixel_spacing=None, frame_rate=None, process_subset=False,
                    file_subset_list=(), *, rank=0, world=1, extensions=("dcm",), reader=read_study, flow_model=None, config=None,
                    device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host", payload="host",
-                   chain=False):
+                   chain=False, deflate="host"):
     """Drop-in for the reference's process_folder (:243-290), same positional signature and the same rules:
       * the folder listing is cut into `nchunks` slices of len // nchunks files, this call takes slice `chunk_index`
         (the remainder files are dropped, as the reference does -- SURVEY.md Appendix C.8);
@@ -703,11 +780,27 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     path serves, and the reason is logged once.  The files are the same either way.
     `chain=True` (OF_algo="TVL1"): every study is solved as a chain (process_video); the walk submits chained studies like plain ones,
     each one unit of the engine's lanes.
+    `deflate`: "host" (default) has the writer stage compress every chunk of the file with zlib level 9; "device" (needs payload="device",
+    else ConfigurationError) has the engine compress `flow` and `echo`, byte for byte what zlib level 9 makes of them, so the files are
+    the same.  A plain RGB study on a model with `device_study_chunks` is solved straight into its chunks (DenseFlow.study_chunks): no
+    float16 array exists on the host.  A saliency or WASE study is solved by its payload call with hold=True and compressed from the held
+    payload (held_deflate).  Either way the writer stage receives the two records and the arrays' shapes and dtypes (in worker processes
+    the compressed bytes travel as shared-memory blocks of the study's), and the masks, the waveforms and RWaveTime stay with the
+    host's threads.  Such a study is solved synchronously, here, before the walk goes on: `studies_in_flight` has no effect for it
+    (logged once).  The host compresses instead, with one logged reason per walk, where the model has neither route, the frames are not
+    uint8 RGB, payload="device" does not serve the study, or `flow` or `echo` is under create_gzip9's min_parallel_bytes and so goes
+    through HDF5's own filter.
     Returns the list of (filename, error string)."""
     if otsu_masks not in ("host", "device"):
         raise ConfigurationError(f"otsu_masks must be 'host' or 'device', not {otsu_masks!r}")
     _check_payload(payload)
+    _check_deflate(deflate, payload)
     _check_chain(chain, flow_model, OF_algo)
+    if deflate == "device":
+        _deflate_fallbacks.clear()                                  # one logged reason per walk
+        if studies_in_flight > 1:
+            logger.info("process_folder: deflate='device' solves a study synchronously and compresses it while it is held: "
+                        "studies_in_flight=%d has no effect for such studies", studies_in_flight)
     os.makedirs(save_folder, exist_ok=True)
     file_list = sorted(os.listdir(dcm_folder))                      # os.listdir order is arbitrary; sorted = same slices on every rank
     if process_subset:
@@ -737,7 +830,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                        video_args=dict(segmentor_model=segmentor_model, verbose=verbose, mode=mode, bkgd_comp=bkgd_comp, flipLR=flipLR,
                                        no_saliency=no_saliency, OF_algo=OF_algo, save_mask_subset=save_mask_subset,
                                        include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config, payload=payload,
-                                       chain=chain))
+                                       chain=chain, deflate=deflate))
     try:
         walk.run()
     finally:
@@ -871,11 +964,29 @@ class _FolderWalk:
         view[...] = arr                                             # float32 -> float16 while copying; float16: a plain copy
         return desc
 
-    def defer(self, study, job, echo16=None):
-        """`echo16`: the study's float16 echo from the engine (payload="device"), else None: the reader stage's, or the writer makes it"""
+    def blob_block(self, study, blob):
+        """a record's blob for the writer process: the descriptor of a new shared-memory block of the study's, or the array itself"""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        view, blk, desc = _shm_new(blob.shape, np.uint8)
+        if blk is None:
+            return blob
+        study.blocks.append(blk)
+        view[...] = blob
+        return desc
+
+    def defer(self, study, job, echo16=None, records=None):
+        """`echo16`: the study's float16 echo from the engine (payload="device"), else None: the reader stage's, or the writer makes it.
+        `records` (deflate="device"): the records of `flow` and `echo` the device made; the job's flow and `echo16` are then
+        hdf5_out.Described -- no float16 array travels, in worker processes the blobs do, as blocks of the study's."""
         from .hdf5_out import save_optical_flow_to_hdf5
         if not self.proc:
-            fut = self.stages.writers.submit(save_optical_flow_to_hdf5, *job, echo=echo16)
+            fut = self.stages.writers.submit(save_optical_flow_to_hdf5, *job, echo=echo16,
+                                             deflate=None if records is None else _records_deflater(records))
+        elif records is not None:
+            save_path, described, nparr, mask_dict, *rest = job
+            packed = {k: dict(rec, blob=self.blob_block(study, rec["blob"])) for k, rec in records.items() if rec is not None}
+            masks = study.mask_descs if study.mask_descs is not None and mask_dict is study.masks else mask_dict
+            fut = self.stages.writers.submit(_save_study_shm, (save_path, described, None, masks, *rest), echo16, int(np.asarray(nparr).shape[0]), packed)
         else:
             # the writer process needs neither the RGB frames (the reader stage or the engine made `echo` from them) nor float32 flow (the
             # file holds float16); what is big travels as shared-memory names: the flow goes straight into a new block (cast on the way

@@ -16,11 +16,13 @@ import os
 import traceback
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
-from contextlib import suppress
+from contextlib import contextmanager, suppress
+from dataclasses import dataclass, field, replace
 from functools import partial
 
 import numpy as np
 
+from . import hdf5_out
 from .config import default_optical_flow_config
 from .dense_flow import DenseFlow
 from .exceptions import ConfigurationError, DICOMReadError, OpticalFlowCalculationError
@@ -103,8 +105,21 @@ def flow_for_study(frames_u8, OF_model, mask_dict=None, bkgd_comp="none", conver
                         chain=chain)()
 
 
+@contextmanager
+def _chain_armed(model, chain):
+    """A chained call on `model` is made with useInitialFlow set: set here where it is not, and put back when the call has returned."""
+    arm = chain and not model.getUseInitialFlow()
+    if arm:
+        model.setUseInitialFlow(True)
+    try:
+        yield
+    finally:
+        if arm:
+            model.setUseInitialFlow(False)
+
+
 def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency=False, saliency_map="f32", payload=False, echo=False, submit=False,
-                 chain=False, hold=False):
+                 chain=False, hold=False, chunks=False):
     """The one place that picks a study's call on the model: -> collect, a callable that returns the study's flow array [N,H,W,2], scaled
     by `factor` and the last flow repeated (`payload`: the pair (float16 flow array, float16 echo or None) of the study file).  rgb: the
     study's uint8 RGB frames, or None; gray_frames: () -> the conditioned frames, asked for only where calc_batch is the model's all.
@@ -114,16 +129,16 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
     cell calc_study[_saliency], or calc_batch on the conditioned frames; then wase_compensate (or numpy's _compensate), the repeat and
     the scale on the host, in the reference's order (flow - background) * factor.
     `chain`: the same cell, chained (DenseFlow's chain=True: pair 0 from zero, pair k from pair k-1's flow; about N-1 single-pair solves
-    per study).  The model is used with useInitialFlow set -- set here for the call where it is not, and put back: a submitted job
-    keeps the parameters it was queued with.  DeepFlow, or a model without `device_chain`, raises ConfigurationError.
-    `hold` (with `payload`, never with `submit`): the payload also stays held on the model's device (hold=True of its payload cells)."""
+    per study).  The model is used with useInitialFlow set -- set for the call on the model where it is not, and put back (_chain_armed):
+    a submitted job keeps the parameters it was queued with.  DeepFlow, or a model without `device_chain`, raises ConfigurationError.
+    `hold` (with `payload`, never with `submit`): the payload also stays held on the model's device (hold=True of its payload cells).
+    `chunks` (with `payload`, never with `submit` or `hold`; a plain RGB study): model.study_chunks in the chunks h5py gives the study's
+    datasets; collect() returns the records {"flow": record, "echo": record} and no array."""
     _check_chain(chain, model)
-    if chain and not model.getUseInitialFlow():
-        model.setUseInitialFlow(True)
-        try:
-            return _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency, saliency_map, payload, echo, submit, True, hold)
-        finally:
-            model.setUseInitialFlow(False)
+
+    def call(name, *args, **kwargs):
+        with _chain_armed(model, chain):
+            return getattr(model, name)(*args, **kwargs)
     if bkgd_comp not in ("WASE", "none"):
         raise OpticalFlowCalculationError(f"bkgd_comp value must be [WASE, none], got {bkgd_comp}!")
     wase = bkgd_comp == "WASE"
@@ -140,6 +155,10 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
             _saliency_warned[0] = True
             logger.warning("no_saliency=False: the saliency preprocessing (StaticSaliencyFineGrained, map handed over as %s) is a restatement of "
                            "opencv-contrib that no OpenCV output pins; files written on this branch are not verified against the reference's", saliency_map)
+    if chunks:
+        shape = rgb.shape[:3]
+        records = call("study_chunks", rgb, factor, hdf5_out.auto_chunks(shape + (2,), np.float16), hdf5_out.auto_chunks(shape, np.float16), **ckw)
+        return lambda: records
     # (device_unit_scale is asked of the plain gray cell alone: every later cell was born with `scale` and `pad_last`)
     if payload or (rgb is not None and hasattr(model, cell) and (cell != "calc_study" or getattr(model, "device_unit_scale", False))):
         if payload:
@@ -148,16 +167,16 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
                 kw["hold"] = True
         if submit and not hold and cell in ("calc_study", "calc_study_payload") and hasattr(model, cell.replace("calc", "submit")):
             # conditioning now, the solve queued on the engine's lanes: the next study's solve is on the GPU while this one finishes
-            ticket = getattr(model, cell.replace("calc", "submit"))(rgb, scale=factor, pad_last=True, **kw)
+            ticket = call(cell.replace("calc", "submit"), rgb, scale=factor, pad_last=True, **kw)
             return lambda: model.wait(ticket)
-        got = getattr(model, cell)(rgb, *((mask_dict["bkgd"],) if wase else ()), scale=factor, pad_last=True, **kw)
+        got = call(cell, rgb, *((mask_dict["bkgd"],) if wase else ()), scale=factor, pad_last=True, **kw)
         if wase:                                                 # (the backgrounds are not kept)
             got = got[:2] if payload else got[0]
         return lambda: got
     if rgb is not None and hasattr(model, plain):
-        flows = getattr(model, plain)(rgb, **kw)                 # conditioning (:588) or saliency maps (:586) + all pairs on the device
+        flows = call(plain, rgb, **kw)                           # conditioning (:588) or saliency maps (:586) + all pairs on the device
     else:
-        flows = model.calc_batch(gray_frames(), **ckw)           # float32 [N-1,H,W,2]
+        flows = call("calc_batch", gray_frames(), **ckw)         # float32 [N-1,H,W,2]
     compensates = wase and hasattr(model, "wase_compensate")
     if compensates:                                              # device: O(N^2 H W) products, numpy's summation order kept
         flows, _ = model.wase_compensate(flows, mask_dict["bkgd"], scale=factor)   # (flow - background) * factor
@@ -168,13 +187,17 @@ def _study_solve(model, rgb, gray_frames, mask_dict, bkgd_comp, factor, saliency
     return lambda: result
 
 
-_PAYLOADS = ("host", "device")
 _payload_fallbacks = set()          # kinds of reason already logged ("model", "bkgd_comp", "frames")
 
 
 def _check_payload(payload):
-    if payload not in _PAYLOADS:
+    if payload not in ("host", "device"):
         raise ConfigurationError(f"payload must be 'host' or 'device', not {payload!r}")
+
+
+def _is_rgb_u8(nparr):
+    """uint8 RGB frames [N,H,W,3]: what the device's study calls take"""
+    return nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8
 
 
 def _device_payload_refused(model, bkgd_comp, nparr=None):
@@ -186,32 +209,33 @@ def _device_payload_refused(model, bkgd_comp, nparr=None):
     # (no model yet: the walk makes a DenseFlow, which offers both)
     if bkgd_comp != "none" and not (bkgd_comp == "WASE" and (model is None or getattr(model, "device_wase", False))):
         return "bkgd_comp", f"bkgd_comp={bkgd_comp!r} works on float32 flows"
-    if nparr is not None and not (nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8):
+    if nparr is not None and not _is_rgb_u8(nparr):
         return "frames", f"the frames are not uint8 RGB [N,H,W,3] but {nparr.dtype} {nparr.shape}"
     return None
 
 
-def _payload_fallback(refused):
-    """One message per kind of reason, whatever the shapes or names in it: a folder of gray studies of many sizes says it once."""
-    kind, reason = refused
-    if kind not in _payload_fallbacks:
-        _payload_fallbacks.add(kind)
-        logger.warning(f"payload='device' not used, the host casts flow and echo to float16 instead: {reason}")
+def _payload_served(payload, model, bkgd_comp, nparr=None):
+    """Whether payload="device" is asked for and serves.  Where it is refused: one message per kind of reason, whatever the shapes or
+    names in it (a folder of gray studies of many sizes says it once)."""
+    refused = _device_payload_refused(model, bkgd_comp, nparr) if payload == "device" else None
+    if refused is not None and refused[0] not in _payload_fallbacks:
+        _payload_fallbacks.add(refused[0])
+        logger.warning(f"payload='device' not used, the host casts flow and echo to float16 instead: {refused[1]}")
+    return payload == "device" and refused is None
 
 
-_DEFLATES = ("host", "device")
 _deflate_fallbacks = set()          # reasons already logged
 
 
 def _check_deflate(deflate, payload):
-    if deflate not in _DEFLATES:
+    if deflate not in ("host", "device"):
         raise ConfigurationError(f"deflate must be 'host' or 'device', not {deflate!r}")
     if deflate == "device" and payload != "device":
         raise ConfigurationError("deflate='device' compresses the payload the engine holds: it needs payload='device'")
 
 
 def _deflate_fallback(reason):
-    if reason not in _deflate_fallbacks:
+    if reason is not None and reason not in _deflate_fallbacks:
         _deflate_fallbacks.add(reason)
         logger.warning(f"deflate='device' not used, the host compresses the file's chunks instead: {reason}")
 
@@ -219,18 +243,16 @@ def _deflate_fallback(reason):
 def _held_records(model, flow_shape, echo_shape):
     """{"flow": record, "echo": record} of the study `model` holds (held_deflate: nothing is uploaded), in the chunks h5py gives the
     datasets; made now, while the study is held."""
-    from .hdf5_out import auto_chunks
-    records = {"flow": model.held_deflate("flow", auto_chunks(flow_shape, np.float16))}
+    records = {"flow": model.held_deflate("flow", hdf5_out.auto_chunks(flow_shape, np.float16))}
     if echo_shape is not None:
-        records["echo"] = model.held_deflate("echo", auto_chunks(echo_shape, np.float16))
+        records["echo"] = model.held_deflate("echo", hdf5_out.auto_chunks(echo_shape, np.float16))
     return records
 
 
 def _device_deflater(model, flow16, echo16):
     """create_gzip9's `deflater` for a study whose payload `model` holds: the records of `flow` and `echo` from the held arrays.  The
-    masks stay with the host's thread pool, like the
-    waveforms and whatever else the file gets: a mask is long runs, where zlib skips what the device's search walks position by
-    position (profiles/r22_deflate.txt: the device is slower on masks than 16 host threads)."""
+    masks stay with the host's thread pool, like the waveforms and whatever else the file gets: a mask is long runs, where zlib skips what
+    the device's search walks position by position (profiles/r22_deflate.txt: the device is slower on masks than 16 host threads)."""
     records = _held_records(model, flow16.shape, None if echo16 is None else echo16.shape)
 
     def deflater(name, data, chunks):
@@ -245,39 +267,63 @@ def _records_deflater(records):
     return lambda name, data, chunks: records.get(name)
 
 
-def _walk_deflate_route(model, from_device, nparr, plain):
-    """How the walk gets a study's `flow` and `echo` chunks from the device: ("chunks", None) -- study_chunks, a plain RGB study on a
-    model with `device_study_chunks`: no float16 array on the host --, ("hold", None) -- the payload call with hold=True, then
-    held_deflate --, or (None, the reason the host compresses this study)."""
-    from .hdf5_out import MIN_PARALLEL_BYTES
-    if not (nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8):
-        return None, "the frames are not uint8 RGB [N,H,W,3]"
-    chunks = plain and getattr(model, "device_study_chunks", False) and hasattr(model, "study_chunks")
-    if not getattr(model, "device_payload", False) or not (chunks or hasattr(model, "held_deflate")):
-        return None, f"the flow model ({type(model).__name__}) has neither study_chunks nor held_deflate"
-    if not from_device:
-        return None, "payload='device' does not serve this study"
-    if int(np.prod(nparr.shape[:3])) * 2 < MIN_PARALLEL_BYTES:      # (`echo`, half of `flow`: the record route has no array for HDF5's filter)
-        return None, "`flow` or `echo` is under create_gzip9's min_parallel_bytes and goes through HDF5's own filter"
-    return ("chunks" if chunks else "hold"), None
+@dataclass
+class _HandOver:
+    """One study on its way to its file: all that save_optical_flow_to_hdf5 needs, from the solve to the writer (process_video writes it
+    in line, process_folder's writer stage in a thread or a worker process).  `flow` and `echo` are arrays, hdf5_out.Described where
+    `records` ({dataset name: record}, deflate="device" in the walk) are all there is of them, or shared-memory descriptors in transit;
+    `echo` None: the writer makes it from `nparr`.  `deflater` (process_video(deflate="device")) writes in line and is never pickled."""
+    save_path: str
+    flow: object
+    nparr: object
+    mask_dict: dict
+    metadata: dict
+    waveforms: dict
+    patient_id: object
+    heart_rate: object
+    config: object
+    mode: str
+    no_saliency: bool
+    include_waveforms: bool
+    save_mask_subset: object = None
+    echo: object = None
+    nframes: object = None
+    records: dict = field(default_factory=dict)
+    deflater: object = None
+
+    def write(self):                              # (the writer is looked up now: tools replace it on its module)
+        deflate = self.deflater or (_records_deflater(self.records) if self.records else None)
+        hdf5_out.save_optical_flow_to_hdf5(self.save_path, self.flow, self.nparr, self.mask_dict, self.metadata, self.waveforms, self.patient_id,
+                                           self.heart_rate, self.config, self.mode, self.no_saliency, self.include_waveforms,
+                                           self.save_mask_subset, echo=self.echo, nframes=self.nframes, deflate=deflate)
+
+    def over_arrays(self, fn):
+        """A copy with fn(value, dtype) in every slot that can be a big array -- the one list of them: the walk packs them into shared
+        memory by it, the worker maps them back.  dtype: what the file stores the slot as, None where that is the value's own."""
+        return replace(self, flow=fn(self.flow, np.float16), echo=fn(self.echo, np.float16), nparr=fn(self.nparr, None),
+                       mask_dict={k: fn(v, None) for k, v in self.mask_dict.items()},
+                       records={k: dict(rec, blob=fn(rec["blob"], np.uint8)) for k, rec in self.records.items() if rec is not None})
 
 
-def _solve_study_chunks(model, rgb, factor, chain):
-    """model.study_chunks in the chunks h5py gives the study's datasets (chain: as _study_solve arms it)"""
-    from .hdf5_out import auto_chunks
-    _check_chain(chain, model)
-    N, H, W = rgb.shape[:3]
-    fc, ec = auto_chunks((N, H, W, 2), np.float16), auto_chunks((N, H, W), np.float16)
-    if not chain:
-        return model.study_chunks(rgb, factor, fc, ec)
-    was = model.getUseInitialFlow()
-    if not was:
-        model.setUseInitialFlow(True)
-    try:
-        return model.study_chunks(rgb, factor, fc, ec, chain=True)
-    finally:
-        if not was:
-            model.setUseInitialFlow(False)
+def _study_route(model, nparr, from_device, deflate, plain, walk):
+    """How a study's `flow` and `echo` get to its file, as (route, reason): "host" -- float32 flows, the host casts --, "device" -- the
+    float16 payload calls (`from_device`: payload="device" serves), the host compresses --, and under `deflate` (deflate="device", a file
+    is written) "hold" -- the payload call with hold=True, then held_deflate -- or, in the walk, "chunks" -- study_chunks, a `plain` RGB
+    study on a model with `device_study_chunks`: no float16 array on the host.  reason: None, or why the host compresses after all, the
+    first that holds in the caller's order (`walk`: process_folder's; else process_video's, which has the arrays anyway)."""
+    name, holds = type(model).__name__, hasattr(model, "held_deflate")
+    chunks = walk and plain and getattr(model, "device_study_chunks", False) and hasattr(model, "study_chunks")
+    unserved = (not from_device, "payload='device' does not serve this study")
+    if walk:
+        reasons = [(not _is_rgb_u8(nparr), "the frames are not uint8 RGB [N,H,W,3]"),
+                   (not (getattr(model, "device_payload", False) and (chunks or holds)), f"the flow model ({name}) has neither study_chunks nor held_deflate"),
+                   unserved,                      # (next: `echo`, half of `flow`; the record route has no array for HDF5's filter)
+                   (int(np.prod(nparr.shape[:3])) * 2 < hdf5_out.MIN_PARALLEL_BYTES,
+                    "`flow` or `echo` is under create_gzip9's min_parallel_bytes and goes through HDF5's own filter")]
+    else:
+        reasons = [unserved, (not holds, f"the flow model ({name}) has no held_deflate")]
+    why = next((text for met, text in reasons if met), None) if deflate else None
+    return ("chunks" if chunks else "hold", None) if deflate and why is None else ("device" if from_device else "host", why)
 
 
 def _prep_frames(nparr, flipLR):
@@ -354,9 +400,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             raise ConfigurationError(f"Input for mode must be [A4C, otsu, RVIO_2class], not {mode}.")
     own = flow_model is None
     model = make_flow_model(OF_algo, config) if own else flow_model
-    from_device = False                           # payload="device" serves: collect() -> (float16 flow array, float16 echo or None)
-    deflater = None                               # deflate="device" serves: the file's chunks are compressed already
-    records = None                                # ... in the walk: {"flow": record, "echo": record}, all the writer stage gets of the two
+    walk = _defer_save is not None                # process_folder: the writer stage takes the study
     try:
         if mask_dict is None and mode == "otsu":
             # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
@@ -366,49 +410,38 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             # reference :549-550; the masks are cleaned on the flow model's device when it offers it (DenseFlow.clean_masks)
             from .masks import predict_movie
             mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config, engine=model)
-        rgb_u8 = nparr.ndim == 4 and nparr.shape[3] == 3 and nparr.dtype == np.uint8
-        if payload == "device":
-            refused = _device_payload_refused(model, bkgd_comp, nparr)
-            if refused is not None:
-                _payload_fallback(refused)
-            from_device = refused is None
+        rgb_u8 = _is_rgb_u8(nparr)
+        from_device = _payload_served(payload, model, bkgd_comp, nparr)
         if not no_saliency and not rgb_u8:
             # the reference's default branch (:559-560, :586): cv2.saliency.StaticSaliencyFineGrained on every frame
             raise OpticalFlowCalculationError(f"no_saliency=False needs uint8 RGB frames [N,H,W,3], got {nparr.dtype} {nparr.shape}")
-        # the echo (from the upload the conditioning / saliency pass reads) only where a file is written
-        device_deflate = deflate == "device" and save_path is not None and _defer_save is None
-        if device_deflate and not (from_device and hasattr(model, "held_deflate")):
-            _deflate_fallback("payload='device' does not serve this study" if not from_device else f"the flow model ({type(model).__name__}) has no held_deflate")
-            device_deflate = False
-        # the walk (process_folder(deflate="device")): the study is solved now, synchronously, and its chunks are made while it is held
-        route = None
-        if deflate == "device" and save_path is not None and _defer_save is not None:
-            route, why = _walk_deflate_route(model, from_device, nparr, no_saliency and bkgd_comp == "none")
-            if route is None:
-                _deflate_fallback(why)
-        if route == "chunks":
-            records = _solve_study_chunks(model, np.ascontiguousarray(nparr), conversion_factor, chain)
-            collect = None
-        else:
-            collect = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
-                                   conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=from_device,
-                                   echo=save_path is not None, submit=_submit and not own and route is None, chain=chain,
-                                   hold=device_deflate or route == "hold")
-        if device_deflate:                        # now, while the model holds the payload (and before a model of this call's own closes)
-            deflater = _device_deflater(model, *collect())
-        elif route == "hold":                     # (the arrays the call returned go here: the writer stage gets the records)
-            records = _held_records(model, nparr.shape[:3] + (2,), nparr.shape[:3])
-            collect = None
+        route, why = _study_route(model, nparr, from_device, deflate == "device" and save_path is not None, no_saliency and bkgd_comp == "none", walk)
+        _deflate_fallback(why)
+        # the echo (from the upload the conditioning / saliency pass reads) only where a file is written; "hold" and "chunks": the study is
+        # solved now, synchronously, and its chunks are made while it is held
+        solved = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
+                              conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=route != "host",
+                              echo=save_path is not None, submit=_submit and not own and route in ("host", "device"), chain=chain,
+                              hold=route == "hold", chunks=route == "chunks")
+        if route == "host":                       # collect(): the solve's result under the hand-over record's names
+            collect = lambda: {"flow": solved()}
+        elif route == "device":
+            collect = lambda: dict(zip(("flow", "echo"), solved()))
+        elif not walk:                            # "hold" in process_video, which returns the arrays: the deflater is made now, while the
+            flow16, echo16 = solved()             # model holds the payload (and before a model of this call's own closes)
+            held = {"flow": flow16, "echo": echo16, "deflater": _device_deflater(model, flow16, echo16)}
+            collect = lambda: held
+        else:                                     # the walk: the writer stage gets the records and what they describe, no array ("hold":
+            shape = nparr.shape[:3]               # the arrays the call returned go here)
+            made = {"flow": hdf5_out.Described(shape + (2,), np.float16), "echo": hdf5_out.Described(shape, np.float16),
+                    "records": solved() if route == "chunks" else _held_records(model, shape + (2,), shape)}
+            collect = lambda: made
     finally:
         if own:
             model.close()
 
     def finish():
-        if records is not None:
-            from .hdf5_out import Described
-            flows, echo16 = Described(nparr.shape[:3] + (2,), np.float16), Described(nparr.shape[:3], np.float16)
-        else:
-            flows, echo16 = collect() if from_device else (collect(), None)
+        got = collect()
         # waveforms (reference :602-620): loaded and validated by the reference's rules unless the caller injected a result dict;
         # without a valid ECG and a valid arterial waveform the whole block is dropped (waveforms_present = False)
         waveform_results, with_waveforms = {}, include_waveforms
@@ -418,20 +451,14 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             if not waveforms_to_write(waveform_results):
                 with_waveforms = False
         if save_path is not None:
-            job = (save_path, flows, nparr, mask_dict, metadata, waveform_results, patient_id, heart_rate,
-                   config, mode, no_saliency, with_waveforms, save_mask_subset)
-            if _defer_save is not None:
-                # process_folder: the writer stage takes it while the next study is solved.  The hook is called with the job alone, as
-                # ever, unless the engine made the echo (payload="device"): only then does it get a second argument -- and a third
-                # where the device made the chunks too: then `flows` and the echo are descriptions (hdf5_out.Described), not arrays
-                if records is not None:
-                    _defer_save(job, echo16, records)
-                else:
-                    _defer_save(job) if echo16 is None else _defer_save(job, echo16)
+            out = _HandOver(save_path=save_path, nparr=nparr, mask_dict=mask_dict, metadata=metadata, waveforms=waveform_results,
+                            patient_id=patient_id, heart_rate=heart_rate, config=config, mode=mode, no_saliency=no_saliency,
+                            include_waveforms=with_waveforms, save_mask_subset=save_mask_subset, **got)
+            if _defer_save is not None:           # process_folder: the writer stage takes it while the next study is solved
+                _defer_save(out)
             else:
-                from .hdf5_out import save_optical_flow_to_hdf5
-                save_optical_flow_to_hdf5(*job, echo=echo16, deflate=deflater)
-        return flows
+                out.write()
+        return got["flow"]
     return finish
 
 
@@ -528,20 +555,24 @@ def _shm_room(nbytes):
     return st.f_bavail * st.f_frsize > 2 * nbytes + _SHM_MARGIN
 
 
-def _shm_put(arr):
-    """ndarray -> ("shm", name, shape, dtype) with the data in a new shared-memory block (this process's mapping is closed, the block
-    stays), or the array itself when it is small / there is no room."""
-    arr = np.ascontiguousarray(arr)
-    view, blk, desc = _shm_new(arr.shape, arr.dtype)
+def _shm_put(arr, dtype=None, keep=None):
+    """ndarray -> ("shm", name, shape, dtype) with the data in a new shared-memory block, or the array itself when it is small / there
+    is no room; as `dtype` where given, cast while copying (float32 flow -> the file's float16).  `keep`: the list that takes the block,
+    still mapped, for its owner to release; without it this process's mapping is closed and the block stays."""
+    arr = np.asarray(arr)
+    view, blk, desc = _shm_new(arr.shape, dtype or arr.dtype)
     if blk is None:
-        return arr
+        return np.ascontiguousarray(arr, dtype)
     try:
         view[...] = arr
     except BaseException:
         _shm_release([blk], unlink=True)
         raise
     del view
-    blk.close()
+    if keep is None:
+        blk.close()
+    else:
+        keep.append(blk)
     return desc
 
 
@@ -609,24 +640,14 @@ def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead
     return nparr, md, pid, hr, masks_ahead, echo
 
 
-def _save_study_shm(job, echo, nframes, records=None):
-    """Writer stage in a worker process: map what arrived as descriptors, write the file, drop the mappings (the owner unlinks).
-    `records` (deflate="device"): the records of `flow` and `echo`, their blobs as descriptors too; flow_arr and echo are then
-    hdf5_out.Described."""
-    from .hdf5_out import save_optical_flow_to_hdf5
+def _save_study_shm(out):
+    """Writer stage in a worker process: map what of the hand-over record arrived as descriptors, write the file, drop the mappings (the
+    owner unlinks)."""
     blocks = []
     try:
-        save_path, flow_arr, nparr, mask_dict, *rest = job
-        flow_arr = _shm_get(flow_arr, blocks)
-        nparr = _shm_get(nparr, blocks)
-        mask_dict = {k: _shm_get(v, blocks) for k, v in mask_dict.items()}
-        echo = _shm_get(echo, blocks)
-        deflate = None
-        if records is not None:
-            records = {k: dict(rec, blob=_shm_get(rec["blob"], blocks)) for k, rec in records.items()}
-            deflate = _records_deflater(records)
-        save_optical_flow_to_hdf5(save_path, flow_arr, nparr, mask_dict, *rest, echo=echo, nframes=nframes, deflate=deflate)
-        del flow_arr, nparr, mask_dict, echo, records, deflate
+        mapped = out.over_arrays(lambda x, dtype: _shm_get(x, blocks))
+        mapped.write()
+        del mapped
     finally:
         _shm_release(blocks, unlink=False)
 
@@ -900,12 +921,7 @@ class _FolderWalk:
         self.proc = isinstance(self.stages, StudyWorkers)
         # payload="device": the engine makes the echo, so the reader stage is asked for none (a study whose frames turn out not to be
         # uint8 RGB still takes the host path: its frames then travel to the writer, which makes the echo)
-        self.device_echo = False
-        if payload == "device":
-            refused = _device_payload_refused(flow_model, video_args["bkgd_comp"])
-            if refused is not None:
-                _payload_fallback(refused)
-            self.device_echo = refused is None
+        self.device_echo = _payload_served(payload, flow_model, video_args["bkgd_comp"])
 
     def failed(self, name, e, trace=False):
         logger.error(f"Error processing {name}: {e}")
@@ -954,49 +970,30 @@ class _FolderWalk:
                 if wait or (not fut.cancel() and fut.done()):
                     _Study(*self.todo[k]).take(fut.result(), mapped=False).release()
 
-    def to_block(self, study, arr):
-        """float16 copy of `arr` for the writer process: the descriptor of a new shared-memory block of the study's, or a plain array"""
-        arr = np.asarray(arr)
-        view, blk, desc = _shm_new(arr.shape, np.float16)
-        if blk is None:
-            return arr.astype(np.float16, copy=False)
-        study.blocks.append(blk)
-        view[...] = arr                                             # float32 -> float16 while copying; float16: a plain copy
-        return desc
+    @staticmethod
+    def to_block(study, x, dtype):
+        """`x` for the writer process: an array as `dtype` in a new shared-memory block of the study's (its descriptor; a plain array
+        without room).  dtype None (frames and masks get no new block) and what is no array (None, hdf5_out.Described) pass through."""
+        return x if dtype is None or x is None or isinstance(x, hdf5_out.Described) else _shm_put(x, dtype, study.blocks)
 
-    def blob_block(self, study, blob):
-        """a record's blob for the writer process: the descriptor of a new shared-memory block of the study's, or the array itself"""
-        blob = np.ascontiguousarray(blob, np.uint8)
-        view, blk, desc = _shm_new(blob.shape, np.uint8)
-        if blk is None:
-            return blob
-        study.blocks.append(blk)
-        view[...] = blob
-        return desc
-
-    def defer(self, study, job, echo16=None, records=None):
-        """`echo16`: the study's float16 echo from the engine (payload="device"), else None: the reader stage's, or the writer makes it.
-        `records` (deflate="device"): the records of `flow` and `echo` the device made; the job's flow and `echo16` are then
-        hdf5_out.Described -- no float16 array travels, in worker processes the blobs do, as blocks of the study's."""
-        from .hdf5_out import save_optical_flow_to_hdf5
-        if not self.proc:
-            fut = self.stages.writers.submit(save_optical_flow_to_hdf5, *job, echo=echo16,
-                                             deflate=None if records is None else _records_deflater(records))
-        elif records is not None:
-            save_path, described, nparr, mask_dict, *rest = job
-            packed = {k: dict(rec, blob=self.blob_block(study, rec["blob"])) for k, rec in records.items() if rec is not None}
-            masks = study.mask_descs if study.mask_descs is not None and mask_dict is study.masks else mask_dict
-            fut = self.stages.writers.submit(_save_study_shm, (save_path, described, None, masks, *rest), echo16, int(np.asarray(nparr).shape[0]), packed)
+    def defer(self, study, out):
+        """The study's hand-over record goes to the writer stage.  A writer process needs neither the RGB frames (the reader stage or the
+        engine made `echo` from them) nor float32 flow (the file holds float16); what is big travels as shared-memory names: the flow
+        goes straight into a new block (cast on the way if the engine handed float32 over), so do the engine's echo and, under
+        deflate="device", the records' blobs (flow and echo are then hdf5_out.Described); the masks and the reader stage's `echo` stay
+        in its blocks."""
+        if self.proc:
+            packed = out.over_arrays(partial(self.to_block, study))
+            packed.nframes = int(np.asarray(out.nparr).shape[0])
+            if packed.echo is None:
+                packed.echo = study.echo_desc
+            if packed.echo is not None:
+                packed.nparr = None
+            if study.mask_descs is not None and out.mask_dict is study.masks:
+                packed.mask_dict = study.mask_descs
+            fut = self.stages.writers.submit(_save_study_shm, packed)
         else:
-            # the writer process needs neither the RGB frames (the reader stage or the engine made `echo` from them) nor float32 flow (the
-            # file holds float16); what is big travels as shared-memory names: the flow goes straight into a new block (cast on the way
-            # if the engine handed float32 over), so does the engine's echo; the masks and the reader stage's `echo` stay in its blocks
-            save_path, flow_arr, nparr, mask_dict, *rest = job
-            flow16 = self.to_block(study, flow_arr)
-            echo = self.to_block(study, echo16) if echo16 is not None else study.echo_desc
-            masks = study.mask_descs if study.mask_descs is not None and mask_dict is study.masks else mask_dict
-            job = (save_path, flow16, None if echo is not None else nparr, masks, *rest)
-            fut = self.stages.writers.submit(_save_study_shm, job, echo, int(np.asarray(nparr).shape[0]))
+            fut = self.stages.writers.submit(out.write)
         self.pending.append((study, fut))
 
     def drop(self, study):

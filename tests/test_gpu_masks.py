@@ -169,5 +169,5 @@ def test_process_video_segmentor_branch_cleans_on_the_flow_model(engine, monkeyp
     assert len(calls) == 2
     assert np.array_equal(dev, ref) and np.array_equal(own, ref)
     for name in ("dev", "own"):
-        _same(jobs[name][3], jobs["ref"][3])
-        assert np.array_equal(jobs[name][1], jobs["ref"][1])
+        _same(jobs[name].mask_dict, jobs["ref"].mask_dict)
+        assert np.array_equal(jobs[name].flow, jobs["ref"].flow)

@@ -176,9 +176,9 @@ def test_process_video_makes_the_otsu_masks_on_the_flow_model(engine, monkeypatc
     assert len(calls) == 2
     assert np.array_equal(dev, ref) and np.array_equal(own, ref)
     for name in ("dev", "own"):
-        assert list(jobs[name][3]) == ["otsu"]
-        _check(np.asarray(jobs[name][3]["otsu"]), host_masks["otsu"])
-        assert np.array_equal(jobs[name][1], jobs["ref"][1])
+        assert list(jobs[name].mask_dict) == ["otsu"]
+        _check(np.asarray(jobs[name].mask_dict["otsu"]), host_masks["otsu"])
+        assert np.array_equal(jobs[name].flow, jobs["ref"].flow)
 
 
 SCRIPT = r"""

@@ -57,8 +57,14 @@ class _Recorder:
     def wait(self, ticket):
         return np.zeros((4, 8, 8, 2), np.float32)
 
+    def study_chunks(self, rgb, scale, flow_chunks, echo_chunks=None, **kw):
+        self.calls.append(("study_chunks", dict(kw, scale=scale, flow_chunks=flow_chunks, echo_chunks=echo_chunks)))
+        self.flag_at_call = self.flag
+        return {"flow": "flow record", "echo": "echo record"}
+
 
 CELLS = [
+    (dict(payload=True, chunks=True), "study_chunks"),
     (dict(), "calc_study"), (dict(payload=True), "calc_study_payload"), (dict(bkgd_comp="WASE"), "calc_study_wase"),
     (dict(bkgd_comp="WASE", payload=True), "calc_study_wase_payload"), (dict(saliency=True), "calc_study_saliency"),
     (dict(saliency=True, bkgd_comp="WASE", payload=True), "calc_study_saliency_wase_payload"), (dict(submit=True), "submit_study"),
@@ -68,18 +74,28 @@ CELLS = [
 
 @pytest.mark.parametrize("kw,cell", CELLS, ids=[c for _, c in CELLS])
 @pytest.mark.parametrize("flag", [False, True])
-def test_study_solve_picks_the_chained_cell(kw, cell, flag):
-    from tee_optical_flow_amd import pipeline
+def test_study_solve_picks_the_chained_cell(monkeypatch, kw, cell, flag):
+    """(the chunks form: study_chunks in the chunks h5py gives the datasets -- asked of a stand-in, the default interpreter has no h5py --
+    and collect() returns the records)"""
+    from tee_optical_flow_amd import hdf5_out, pipeline
+    monkeypatch.setattr(hdf5_out, "auto_chunks", lambda shape, dtype: ("chunks of", tuple(shape), np.dtype(dtype)))
     rgb = np.zeros((4, 8, 8, 3), np.uint8)
     masks = {"bkgd": np.ones((4, 8, 8, 2), bool)}
     kw = dict(kw)
     bkgd = kw.pop("bkgd_comp", "none")
     for chain in (True, False):
         m = _Recorder(flag)
-        pipeline._study_solve(m, rgb, lambda: rgb[..., 0], masks, bkgd, 2.0, chain=chain, **kw)()
+        collect = pipeline._study_solve(m, rgb, lambda: rgb[..., 0], masks, bkgd, 2.0, chain=chain, **kw)
+        assert m.flag is flag, "the model's flag was not put back when the call on the model had returned"
+        result = collect()
         (name, got), = m.calls
         assert name == cell and got.get("chain", False) is chain, (name, got)
-        assert got["scale"] == 2.0 and got["pad_last"] is True
+        assert got["scale"] == 2.0
+        if cell == "study_chunks":
+            assert got["flow_chunks"] == ("chunks of", (4, 8, 8, 2), np.float16) and got["echo_chunks"] == ("chunks of", (4, 8, 8), np.float16)
+            assert result == {"flow": "flow record", "echo": "echo record"}
+        else:
+            assert got["pad_last"] is True
         assert m.flag is flag, "the model's flag was not put back"
         assert m.flag_at_call is (True if chain else flag)
 

@@ -7,6 +7,7 @@ import json
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,13 +119,14 @@ def big_f16(x):
     if isinstance(x, dict): return any(big_f16(v) for v in x.values())
     if isinstance(x, (tuple, list)): return any(big_f16(v) for v in x)
     return False
-real_save = hdf5_out.save_optical_flow_to_hdf5
 def spy(real):
     def submit(self, fn, *args, **kwargs):
-        if fn is pipeline._save_study_shm or fn is real_save:
-            handed.append({"fn": fn.__name__, "f16": big_f16(args) or big_f16(kwargs),
-                           "described": [type(a).__name__ for a in list(args[:2]) + list(args[0][:2] if isinstance(args[0], tuple) else ()) + list(kwargs.values())
-                                         if isinstance(a, hdf5_out.Described)]})
+        # the writer stage's two callables: the hand-over record's write (threads), _save_study_shm of a packed record (processes)
+        rec = args[0] if fn is pipeline._save_study_shm else getattr(fn, "__self__", None) if getattr(fn, "__func__", None) is pipeline._HandOver.write else None
+        if rec is not None:
+            assert isinstance(rec, pipeline._HandOver) and len(args) == (1 if fn is pipeline._save_study_shm else 0) and not kwargs
+            handed.append({"pool": "process" if isinstance(self, ProcessPoolExecutor) else "thread", "f16": big_f16(vars(rec)),
+                           "described": [type(a).__name__ for a in (rec.flow, rec.echo) if isinstance(a, hdf5_out.Described)]})
         return real(self, fn, *args, **kwargs)
     return submit
 ProcessPoolExecutor.submit = spy(ProcessPoolExecutor.submit)
@@ -261,13 +263,13 @@ def test_writer_stage_compresses_the_masks_only(walks):
 
 
 def test_no_float16_array_reaches_the_writer_stage(walks):
-    """What is handed to save_optical_flow_to_hdf5 (threads) or _save_study_shm (processes): two Described and no float16 array or
-    float16 shared-memory block; the blocks the walk creates per study are the two blobs."""
+    """The hand-over record the writer stage gets, in its thread pool or (through _save_study_shm) its process pool: two Described and no
+    float16 array or float16 shared-memory block; the blocks the walk creates per study are the two blobs."""
     for tag in DEV:
         w = walks["walks"][tag]
         assert len(w["handed"]) == 3, (tag, w["handed"])
         for h in w["handed"]:
-            assert h["fn"] == ("_save_study_shm" if tag.endswith("prc") else "save_optical_flow_to_hdf5")
+            assert h["pool"] == ("process" if tag.endswith("prc") else "thread")
             assert not h["f16"] and h["described"] == ["Described", "Described"], (tag, h)
     for k in KINDS:
         w = walks["walks"][f"{k}_dev_prc"]
@@ -311,8 +313,62 @@ def test_a_dead_worker_switches_to_threads_and_leaves_no_block(walks):
     w = walks["walks"]["died"]
     assert w["errors"] == [] and walks["same"]["died"] and w["log"] == ["study_chunks"] * 3
     assert any("continue in threads" in m for m in w["warnings"]), w["warnings"]
-    assert {h["fn"] for h in w["handed"]} == {"_save_study_shm", "save_optical_flow_to_hdf5"}     # mid-walk: both kinds of writer were used
+    assert {h["pool"] for h in w["handed"]} == {"process", "thread"}     # mid-walk: both kinds of writer were used
     assert walks["shm_left"] == [], "shared-memory blocks left behind"
+
+
+class _Model:
+    """a model with the float16 study calls, held_deflate and (chunks=True) study_chunks, in numpy: zeros, and records of no chunks"""
+    device_unit_scale = device_payload = device_wase = True
+
+    def __init__(self, chunks):
+        self.device_study_chunks, self.log = chunks, []
+
+    def calc_batch(self, frames):
+        self.log.append("calc_batch")
+        return np.zeros((len(frames) - 1,) + frames.shape[1:3] + (2,), np.float32)
+
+    def calc_study_payload(self, rgb, scale=1.0, pad_last=True, echo=True, hold=False):
+        self.log.append("calc_study_payload" + ("+hold" if hold else ""))
+        return np.zeros(rgb.shape[:3] + (2,), np.float16), np.zeros(rgb.shape[:3], np.float16)
+
+    def held_deflate(self, what, chunks):
+        self.log.append("held_deflate:" + what)
+        return {"blob": np.zeros(3, np.uint8), "chunks": chunks}
+
+    def study_chunks(self, rgb, scale, flow_chunks, echo_chunks=None, chain=False):
+        self.log.append("study_chunks")
+        return {"flow": {"blob": np.zeros(3, np.uint8), "chunks": flow_chunks}, "echo": {"blob": np.zeros(3, np.uint8), "chunks": echo_chunks}}
+
+
+@pytest.mark.parametrize("route,shape,kw,log", [
+    ("host", (5, 48, 56), dict(payload="host"), ["calc_batch"]),
+    ("device", (5, 48, 56), dict(payload="device"), ["calc_study_payload"]),
+    ("hold", (9, 240, 256), dict(payload="device", deflate="device"), ["calc_study_payload+hold", "held_deflate:flow", "held_deflate:echo"]),
+    ("chunks", (9, 240, 256), dict(payload="device", deflate="device"), ["study_chunks"])])
+def test_the_hook_gets_the_hand_over_record_alone(monkeypatch, route, shape, kw, log):
+    """On every route _defer_save is called once, with exactly one positional argument: the hand-over record.  flow and echo in it are
+    arrays where the host compresses them, and Described beside their two records where the device did (9 x 240 x 256: both past
+    create_gzip9's min_parallel_bytes)."""
+    from tee_optical_flow_amd import hdf5_out, pipeline
+    monkeypatch.setattr(hdf5_out, "auto_chunks", lambda shape, dtype: (1,) + tuple(shape[1:]))
+    calls = []
+    model = _Model(chunks=route == "chunks")
+    rgb = np.full(shape + (3,), 9, np.uint8)
+    flow = pipeline.process_video(None, "unwritten.hdf5", None, verbose=False, mode="otsu", no_saliency=True, nparr=rgb, flow_model=model,
+                                  mask_dict={"otsu": np.zeros(shape + (1,), bool)}, _defer_save=lambda *a, **k: calls.append((a, k)), **kw)
+    assert model.log == log
+    (args, kwargs), = calls
+    assert len(args) == 1 and not kwargs and type(args[0]) is pipeline._HandOver, calls
+    out = args[0]
+    assert out.save_path == "unwritten.hdf5" and out.nparr is rgb and list(out.mask_dict) == ["otsu"] and out.deflater is None and out.flow is flow
+    if route in ("hold", "chunks"):
+        assert sorted(out.records) == ["echo", "flow"] and out.records["flow"]["chunks"] == (1,) + shape[1:] + (2,)
+        assert isinstance(out.flow, hdf5_out.Described) and (out.flow.shape, out.flow.dtype) == (shape + (2,), np.float16)
+        assert isinstance(out.echo, hdf5_out.Described) and (out.echo.shape, out.echo.dtype) == (shape, np.float16)
+    else:
+        assert out.records == {} and out.flow.shape == shape + (2,) and out.flow.dtype == (np.float16 if route == "device" else np.float32)
+        assert (out.echo is None) if route == "host" else (out.echo.shape == shape and out.echo.dtype == np.float16)
 
 
 def test_process_folder_takes_deflate():

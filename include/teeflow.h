@@ -571,6 +571,43 @@ int tf_held_radlong_overlay(tf_handle* h, const double* lut_rad, const double* l
 int tf_held_magnitude_overlay(tf_handle* h, int n_used, int slot, int param, double spacing, int grad_f64, int norm_f64, const double* lut,
                               uint8_t* out, double* info, double* frame_info);
 
+/* ---- FRAMES held on the device: a study's RGB frames put there once, in the form its file stores them, and read there by every call
+ *      that takes frames.  Without this every such call uploads the same 3 bytes per pixel again (tf_otsu_masks or tf_segmentor_input,
+ *      then the study call, then tf_echo_frames ...), and the host prepares them first (the reference's calculate_optical_flow.py:524-548:
+ *      pydicom's YBR -> RGB conversion, gray2rgb, np.flip(axis=2)).  The held frames live in a buffer of the handle's own, separate from
+ *      the held study above: neither touches the other.  All of it runs on the handle's stream (tf_set_stream included) and is waited for.
+ * tf_hold_frames: src host uint8, N frames of H x W in `form`; flip_lr != 0 mirrors the columns (np.flip(axis=2)).  The source bytes
+ *   are uploaded as stored and k_ingest writes uint8 RGB [N][H][W][3]; whatever frames were held before are replaced.
+ *     TF_FRAMES_RGB       [N][H][W][3]   no arithmetic; without flip_lr no kernel either, the upload goes straight into the held buffer
+ *     TF_FRAMES_GRAY      [N][H][W]      gray2rgb: the byte three times
+ *     TF_FRAMES_YBR_FULL  [N][H][W][3] of Y, Cb, Cr (what pydicom's pixel_array is for YBR_FULL and YBR_FULL_422): DICOM PS3.3
+ *       C.7.6.3.1.2's inverse in float32, in one fixed order: (y, cb, cr) = (Y, Cb - 128, Cr - 128); per output channel
+ *       t = y * m0; t = fma(cb, m1, t); t = fma(cr, m2, t); out = uint8(clamp(floor(t + 0.5f), 0, 255)), m the float32 roundings of
+ *       [[1, 1, 1], [0, -0.114 * 1.772 / 0.587, 1.772], [1.402, -0.299 * 1.402 / 0.587, 0]] (row = input, column = output).  The numpy
+ *       twin is frames.ybr_full_to_rgb; parity with pydicom's convert_color_space is NOT pinned (tests/test_pydicom_color_probe.py).
+ * tf_held_frames_shape: out[4] = N, H, W (all 0: none held) and a generation number that grows with every replacement and release.
+ * tf_release_frames frees the buffer (tf_destroy does too).  tf_download_frames: the held RGB to rgb_out, host [N][H][W][3].
+ * tf_frames_next(h, first, count): arms the NEXT frames-taking call of the handle to read held frames [first, first + count) in place
+ *   of its host pointer.  The armed call passes a NULL frame pointer, N == count, H and W of the held frames (and channels == 3 where
+ *   it has a channel count); otherwise it is refused with TF_ERR_INVALID_ARG and a message that names both shapes, as it is when the
+ *   range is outside the held frames or none are held.  The flag is spent by that call, refused or not, and the held frames stay as
+ *   they were.  Calls that honour it: the study calls tf_calc_seq_rgb, _rgb_f16, _rgb_held, _rgb_wase, tf_calc_seq_saliency, _f32,
+ *   _f16, _wase, tf_submit_seq_rgb, tf_submit_seq_rgb_f16 (a submitted study conditions the frames into its own buffer before submit
+ *   returns, so they may be replaced at once), and tf_condition_frames, tf_echo_frames, tf_saliency_frames, tf_saliency_frames_f32,
+ *   tf_otsu_masks, tf_segmentor_input (its kernel reads the held frames on the caller's stream: tf_hold_frames and tf_release_frames
+ *   wait for it).  The lock-step calls (tf_calc_chains*) spend the flag and refuse with TF_ERR_UNSUPPORTED.
+ * tf_dbg_counter(h, "frames_upload_bytes"): bytes of frames that tf_hold_frames and the calls above have copied host -> device since the
+ *   handle was made; "frames_held_reads": armed calls that read the held frames; "ingest_kernel_us", "ingest_bytes": k_ingest's device
+ *   time in the last tf_hold_frames and the bytes it read and wrote (both 0 where no kernel ran). */
+#define TF_FRAMES_RGB      0
+#define TF_FRAMES_GRAY     1
+#define TF_FRAMES_YBR_FULL 2
+int tf_hold_frames(tf_handle* h, const void* src, int form, int flip_lr, int N, int H, int W);
+int tf_held_frames_shape(tf_handle* h, long long* out);
+int tf_release_frames(tf_handle* h);
+int tf_download_frames(tf_handle* h, uint8_t* rgb_out);
+int tf_frames_next(tf_handle* h, int first, int count);
+
 /* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
  *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over
  *      the bus is the compressed bytes.  The output bytes are zlib's or the stream is refused: stored, fixed and dynamic blocks, any

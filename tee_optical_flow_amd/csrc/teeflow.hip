@@ -32,6 +32,7 @@
 #include "teeflow_segmentor.hip.h"
 #include "teeflow_inflate.hip.h"
 #include "teeflow_deflate.hip.h"
+#include "teeflow_ingest.hip.h"
 #include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include "teeflow_engine.hip.h"
@@ -42,6 +43,26 @@
 // =================================================================================================
 // C ABI
 // =================================================================================================
+namespace {
+// tf_frames_next's state: which handles are armed, and with what range.  It is kept beside the handles, not in them, because the
+// entry points that honour it check their arguments before they read the handle -- a call refused for a null pointer or a bad size
+// touches nothing -- and whether a null frame pointer is a mistake or the armed call's is part of that check.
+struct ArmedFrames { bool on = false; int first = 0, count = 0; };
+std::mutex g_frames_next_m;
+std::map<const tf_handle*, ArmedFrames> g_frames_next;
+
+// the handle's armed range, spent: every call that honours or refuses tf_frames_next takes it first, refused or not
+ArmedFrames spend_frames_next(const tf_handle* h)
+{
+    std::lock_guard<std::mutex> lk(g_frames_next_m);
+    const auto f = g_frames_next.find(h);
+    if (f == g_frames_next.end()) return {};
+    const ArmedFrames a = f->second;
+    g_frames_next.erase(f);
+    return a;
+}
+}  // namespace
+
 TF_API int tf_abi_version(void) { return TF_ABI_VERSION; }
 
 TF_API int tf_device_count(void)
@@ -114,6 +135,8 @@ TF_API void tf_destroy(tf_handle* h)
     for (auto& b : h->pre) if (b.p) (void)hipFree(b.p);
     dev_free(h->an_rad); dev_free(h->an_lon);
     h->held.release();
+    h->frames.release();
+    (void)spend_frames_next(h);
     delete h;
 }
 
@@ -237,6 +260,10 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;
+    else if (n == "frames_upload_bytes") v = h->frames_upload_bytes;
+    else if (n == "frames_held_reads") v = h->frames_held_reads;
+    else if (n == "ingest_kernel_us") v = (long long)(h->ingest_kernel_ms * 1000.0);
+    else if (n == "ingest_bytes") v = h->ingest_bytes;
     else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {
@@ -358,12 +385,14 @@ TF_API int tf_chain_next(tf_handle* h, int on)
 // ---- several chains of one frame size in lock-step: step k solves pair k of every chain still running as one batch --------------------
 namespace {
 // The arguments of a lock-step call -> its chains in the library's order and the Call that carries them, or the refusal; before any GPU
-// work.  frames / flows_out: one pointer per chain, in the caller's order, where `where` says.  hold: tf_hold_next was armed.
+// work.  frames / flows_out: one pointer per chain, in the caller's order, where `where` says.  armed: what spend_flags found armed.
+enum { ARMED_HOLD = 1, ARMED_FRAMES = 2 };
 int check_chains(tf_handle* h, const void* const* frames, const int* n_frames, int n_chains, int H, int W, float scale, void* const* flows_out,
-                 int where, bool out_f16, bool hold, ChainSet* cs, Call* c)
+                 int where, bool out_f16, int armed, ChainSet* cs, Call* c)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    if (hold) return fail(h, TF_ERR_UNSUPPORTED, "tf_hold_next was armed: chains in lock-step hold nothing (the flag is spent; a study call holds a study)");
+    if (armed & ARMED_FRAMES) return fail(h, TF_ERR_UNSUPPORTED, "tf_frames_next was armed: chains in lock-step take their frames from the caller's pointers (the flag is spent)");
+    if (armed & ARMED_HOLD) return fail(h, TF_ERR_UNSUPPORTED, "tf_hold_next was armed: chains in lock-step hold nothing (the flag is spent; a study call holds a study)");
     if (n_chains < 1) return fail(h, TF_ERR_INVALID_ARG, "chains in lock-step: n_chains must be >= 1, got %d", n_chains);
     if (!frames || !n_frames || !flows_out) return fail(h, TF_ERR_INVALID_ARG, "chains in lock-step: null frames, n_frames or flows_out array");
     for (int i = 0; i < n_chains; ++i) {
@@ -393,13 +422,14 @@ int check_chains(tf_handle* h, const void* const* frames, const int* n_frames, i
     return check_call(h, *c);
 }
 
-// the flags a lock-step call spends, refused or not: tf_chain_next's (such a call is chained anyway) and tf_hold_next's -> was that one armed?
-bool spend_flags(tf_handle* h)
+// the flags a lock-step call spends, refused or not: tf_chain_next's (such a call is chained anyway), tf_hold_next's and
+// tf_frames_next's -> which of the last two were armed (ARMED_*)
+int spend_flags(tf_handle* h)
 {
-    if (!h) return false;
-    const bool hold = h->hold_next;
+    if (!h) return 0;
+    const int armed = (h->hold_next ? ARMED_HOLD : 0) | (spend_frames_next(h).on ? ARMED_FRAMES : 0);
     h->hold_next = h->chain_next = false;
-    return hold;
+    return armed;
 }
 
 // a checked lock-step call, solved and waited for: tf_get_iters then gives the counts chain after chain in the caller's order

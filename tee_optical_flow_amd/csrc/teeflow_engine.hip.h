@@ -201,6 +201,7 @@ struct tf_handle : Engine {
            PRE_INF_BLOB, PRE_INF_TABLE, PRE_INF_OUT,                              // tf_inflate, tf_hold_*_chunks: compressed bytes, per-stream table, inflated chunks
            PRE_DF_WORK, PRE_DF_TABLE, PRE_DF_BLOB, PRE_DF_SRC,                    // tf_deflate, tf_deflate_array, tf_held_deflate: a batch's scratch, per-chunk table,
                                                                                   //   the streams end to end, an uploaded array
+           PRE_FR_SRC,                                                            // tf_hold_frames: the source bytes as the file stores them, before k_ingest
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
@@ -232,6 +233,19 @@ struct tf_handle : Engine {
         }
     } held;
     bool hold_next = false;      // tf_hold_next: the next study call leaves its payload held
+    // ---- the held frames (teeflow_held.hip.h): a study's uint8 RGB [N][H][W][3] in a device buffer of the handle's own, ingested once
+    // (k_ingest) and read in place by every frames-taking call armed with tf_frames_next; separate from the held study ----
+    struct Frames {
+        uint8_t* rgb = nullptr; size_t cap = 0;              // the buffer only grows; it goes with tf_release_frames or the handle
+        int N = 0, H = 0, W = 0;                             // N == 0: no frames are held
+        long long gen = 0;                                   // grows with every replacement and release
+        void drop() { if (N) ++gen; N = H = W = 0; }         // nothing is held any more (the buffer stays)
+        void release() { drop(); (void)hipFree(rgb); rgb = nullptr; cap = 0; }   // (the caller has drained the streams that read it)
+    } frames;
+    // (tf_frames_next's armed range lives beside the handle, not in it: ArmedFrames in teeflow.hip says why)
+    long long frames_upload_bytes = 0;   // bytes of frames that tf_hold_frames and the frames-taking calls have copied host -> device
+    long long frames_held_reads = 0;     // frames-taking calls that read the held frames in place
+    double ingest_kernel_ms = 0; long long ingest_bytes = 0;   // the last tf_hold_frames: k_ingest's device time and the bytes it read and wrote
     bool chain_next = false;     // tf_chain_next: the next solve call, a sequence call, is solved as a chain (take_chain spends it)
     long long chain_steps = 0;   // pairs this handle and its lanes have solved as chain steps ("chain_steps" counter; the pool's lock where there is a pool)
     long long study_download_bytes = 0;   // bytes of flow and echo the synchronous study calls have copied device -> host

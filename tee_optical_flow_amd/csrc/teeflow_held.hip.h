@@ -3,7 +3,7 @@
 // (tf_hold_next; study_call in teeflow_tail.hip.h), and the tail calls that read it there.  Included by teeflow.hip after
 // teeflow_tail.hip.h: every tf_held_* call is its original's internal function with device sources (Src) in the place of host ones,
 // so there is one copy of every kernel and launch rule.  Nothing else writes the held buffers: the PRE_* scratch and the resident
-// analysis planes stay what they were.
+// analysis planes stay what they were.  The file's second half is the input side's equivalent, the held FRAMES (tf_hold_frames & co.).
 
 namespace {
 // the held study, for a call named `who` that reads it: TF_ERR_INVALID_ARG and why when there is none
@@ -196,4 +196,117 @@ TF_API int tf_held_magnitude_overlay(tf_handle* h, int n_used, int slot, int par
     if (int rc = check_magnitude_overlay(h, who, k.N, k.H, k.W, lut)) return rc;
     return finish_host_call(h, magnitude_overlay<ovl::ECHO_F16>(h, Src::on_device(k.flow), 1, k.N, n_used, k.H, k.W, Src::on_device(m->p), m->C, param, spacing,
                                                                 grad_f64 ? 1 : 0, norm_f64 ? 1 : 0, Src::on_device(k.echo), lut, out, info, frame_info));
+}
+
+// ---- the held frames: a study's RGB frames put on the device once, in the form its file stores them, and read there by every
+// frames-taking call armed with tf_frames_next (take_frames in teeflow_tail.hip.h).  Separate from the held study: neither call
+// touches the other's buffers.  Everything runs on the handle's stream (tf_set_stream included) and is waited for. --------------------
+namespace {
+// nothing queued anywhere still reads the held frames: the handle's stream, and tf_segmentor_input's kernel on a caller's stream
+int frames_quiesce(tf_handle* h)
+{
+    HIPC(h, hipSetDevice(h->dev));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (h->seg_ev[1]) HIPC(h, hipEventSynchronize(h->seg_ev[1]));
+    return TF_OK;
+}
+
+template <int FORM>
+void launch_ingest(tf_handle* h, bool flip, const uint8_t* src, size_t npx, int W, uint8_t* out)
+{
+    const dim3 g((unsigned)(((npx + 3) / 4 + 255) / 256)), blk(256);
+    if (flip) hipLaunchKernelGGL((tfg::k_ingest<FORM, true>), g, blk, 0, h->stream, src, npx, W, out);
+    else hipLaunchKernelGGL((tfg::k_ingest<FORM, false>), g, blk, 0, h->stream, src, npx, W, out);
+}
+
+int hold_frames(tf_handle* h, const uint8_t* src, int form, bool flip, int N, int H, int W)
+{
+    int rc = frames_quiesce(h);
+    if (rc) return rc;
+    tf_handle::Frames& k = h->frames;
+    k.drop();
+    const size_t npx = (size_t)N * H * W, in_bytes = npx * (form == TF_FRAMES_GRAY ? 1 : 3), out_bytes = npx * 3;
+    if (k.cap < out_bytes) {
+        (void)hipFree(k.rgb); k.rgb = nullptr; k.cap = 0;
+        const hipError_t e = hipMalloc(&k.rgb, out_bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding frames of %d x %d x %d: hipMalloc failed: %s", N, H, W, hipGetErrorString(e));
+        }
+        k.cap = out_bytes;
+    }
+    h->ingest_kernel_ms = 0; h->ingest_bytes = 0;
+    if (form == TF_FRAMES_RGB && !flip) {                     // nothing to compute: the upload is the held frames
+        HIPC(h, hipMemcpyAsync(k.rgb, src, in_bytes, hipMemcpyHostToDevice, h->stream));
+    } else {
+        Pre pre(h);
+        auto* dsrc = pre.get<uint8_t>(tf_handle::PRE_FR_SRC, in_bytes);
+        if (pre.rc) return pre.rc;
+        HIPC(h, hipMemcpyAsync(dsrc, src, in_bytes, hipMemcpyHostToDevice, h->stream));
+        HIPC(h, hipEventRecord(h->ev[0], h->stream));
+        if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, dsrc, npx, W, k.rgb);
+        else if (form == TF_FRAMES_YBR_FULL) launch_ingest<tfg::YBR_FULL>(h, flip, dsrc, npx, W, k.rgb);
+        else launch_ingest<tfg::RGB>(h, flip, dsrc, npx, W, k.rgb);
+        HIPC(h, hipGetLastError());
+        HIPC(h, hipEventRecord(h->ev[1], h->stream));
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    h->frames_upload_bytes += (long long)in_bytes;
+    if (!(form == TF_FRAMES_RGB && !flip)) {
+        float t = 0;
+        HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
+        h->ingest_kernel_ms = t; h->ingest_bytes = (long long)(in_bytes + out_bytes);
+    }
+    k.N = N; k.H = H; k.W = W;
+    ++k.gen;
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_hold_frames(tf_handle* h, const void* src, int form, int flip_lr, int N, int H, int W)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    if (!src || N < 1 || H < 1 || W < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_hold_frames: null source or bad sizes: N=%d H=%d W=%d", N, H, W);
+    if (form != TF_FRAMES_RGB && form != TF_FRAMES_GRAY && form != TF_FRAMES_YBR_FULL)
+        return fail(h, TF_ERR_INVALID_ARG, "tf_hold_frames: form %d is none of TF_FRAMES_RGB (0), TF_FRAMES_GRAY (1), TF_FRAMES_YBR_FULL (2)", form);
+    return finish_host_call(h, hold_frames(h, (const uint8_t*)src, form, flip_lr != 0, N, H, W));
+}
+
+TF_API int tf_held_frames_shape(tf_handle* h, long long* out)
+{
+    if (!h || !out) return TF_ERR_INVALID_ARG;
+    const tf_handle::Frames& k = h->frames;
+    out[0] = k.N; out[1] = k.H; out[2] = k.W; out[3] = k.gen;
+    return TF_OK;
+}
+
+TF_API int tf_release_frames(tf_handle* h)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    if (int rc = frames_quiesce(h)) return rc;
+    h->frames.release();
+    return TF_OK;
+}
+
+TF_API int tf_download_frames(tf_handle* h, uint8_t* rgb_out)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    const tf_handle::Frames& k = h->frames;
+    if (k.N < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_download_frames: no frames are held (tf_hold_frames)");
+    if (!rgb_out) return fail(h, TF_ERR_INVALID_ARG, "tf_download_frames: null output pointer");
+    auto run = [&]() -> int {
+        HIPC(h, hipSetDevice(h->dev));
+        HIPC(h, hipMemcpyAsync(rgb_out, k.rgb, (size_t)k.N * k.H * k.W * 3, hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        return TF_OK;
+    };
+    return finish_host_call(h, run());
+}
+
+TF_API int tf_frames_next(tf_handle* h, int first, int count)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(g_frames_next_m);
+    g_frames_next[h] = ArmedFrames{true, first, count};
+    return TF_OK;
 }

@@ -81,6 +81,37 @@ int src_to_device(tf_handle* h, const Src& src, size_t off, size_t bytes, void* 
     return TF_OK;
 }
 
+// The RGB frames of a frames-taking call named `who`: the caller's host pointer, or -- armed by tf_frames_next, `a` being what
+// spend_frames_next gave the call at its start -- frames [first, first + count) of the held frames where they are
+// (teeflow_held.hip.h).  The armed call passes a null pointer, N == count, three channels and the held H x W; anything else is
+// refused with both shapes.  Called once the call's own argument checks have passed: this reads the handle.
+int take_frames(tf_handle* h, const char* who, const ArmedFrames& a, const void* rgb, int N, int H, int W, int channels, Src* out)
+{
+    if (!a.on) { *out = Src::on_host(rgb); return TF_OK; }
+    const tf_handle::Frames& k = h->frames;
+    const int first = a.first, count = a.count;
+    if (k.N < 1) return fail(h, TF_ERR_INVALID_ARG, "%s: tf_frames_next was armed, but no frames are held (tf_hold_frames)", who);
+    if (first < 0 || count < 1 || first > k.N - count)
+        return fail(h, TF_ERR_INVALID_ARG, "%s: tf_frames_next armed frames [%d, %d + %d), outside the %d held frames", who, first, first, count, k.N);
+    if (rgb) return fail(h, TF_ERR_INVALID_ARG, "%s: tf_frames_next was armed: the call reads the held frames and passes a null frame pointer", who);
+    if (N != count || H != k.H || W != k.W || channels != 3)
+        return fail(h, TF_ERR_INVALID_ARG, "%s: the call's frames are %d x %d x %d x %d, the armed range of the held frames %d x %d x %d x 3 "
+                                           "(%d frames held)", who, N, H, W, channels, count, k.H, k.W, k.N);
+    *out = Src::on_device(k.rgb + (size_t)first * k.H * k.W * 3);
+    ++h->frames_held_reads;
+    return TF_OK;
+}
+
+// src_to_device for a call's frames: what is uploaded counts in frames_upload_bytes
+int frames_to_device(tf_handle* h, const Src& src, size_t off, size_t bytes, void* scratch, const uint8_t** out)
+{
+    if (src.dev) { *out = (const uint8_t*)src.dev + off; return TF_OK; }
+    HIPC(h, hipMemcpyAsync(scratch, (const uint8_t*)src.host + off, bytes, hipMemcpyHostToDevice, h->stream));
+    h->frames_upload_bytes += (long long)bytes;
+    *out = (const uint8_t*)scratch;
+    return TF_OK;
+}
+
 // n pixels of uploaded RGB (device) -> their float16 `echo` values in the caller's host buffer, behind what is queued on the handle's
 // stream; the copy is done when the stream has been waited for.  decho: device scratch of at least n halves.  keep (device, or null):
 // gets the same halves by a copy on the device (a held study's echo).  Without a host buffer (echo16_out null) the kernel writes
@@ -96,23 +127,24 @@ int echo_from_device_rgb(tf_handle* h, const uint8_t* drgb, size_t n, uint16_t* 
     return TF_OK;
 }
 
-// rgb (host) -> conditioned gray frames in the handle's preprocessing buffer (valid until the handle's next preprocessing call)
+// rgb (host, or the held frames) -> conditioned gray frames in the handle's preprocessing buffer (valid until the handle's next preprocessing call)
 // (`own`: into that caller-owned buffer instead -- a submitted job's frames must outlive the handle's next preprocessing call)
 // echo16_out (host, [N][H][W] halves, or null): also the study's `echo`, from the same upload; complete on return
 // (echo_keep: device memory that gets the echo too, see echo_from_device_rgb)
-int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, const uint8_t** dgray_out, uint8_t* own = nullptr,
+int condition_to_device(tf_handle* h, const Src& rgb, int N, int H, int W, const uint8_t** dgray_out, uint8_t* own = nullptr,
                         uint16_t* echo16_out = nullptr, uint16_t* echo_keep = nullptr)
 {
     const size_t npx = (size_t)H * W;
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
-    auto* drgb = pre.get<uint8_t>(tf_handle::PRE_SRC, (size_t)N * npx * 3);
+    auto* urgb = rgb.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_SRC, (size_t)N * npx * 3);
     auto* dgray = own ? own : pre.get<uint8_t>(tf_handle::PRE_OUT, (size_t)N * npx);
     auto* mm = pre.get<u64>(tf_handle::PRE_MX, (size_t)N * 2);
     auto* decho = echo16_out ? pre.get<uint16_t>(tf_handle::PRE_ECHO, (size_t)N * npx) : nullptr;
     if (pre.rc) return pre.rc;
     const std::vector<u64> init = minmax_seed((size_t)N);
-    HIPC(h, hipMemcpyAsync(drgb, rgb, (size_t)N * npx * 3, hipMemcpyHostToDevice, h->stream));
+    const uint8_t* drgb = nullptr;
+    if (int rc = frames_to_device(h, rgb, 0, (size_t)N * npx * 3, urgb, &drgb)) return rc;
     HIPC(h, hipMemcpyAsync(mm, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
     const int gx = (int)((npx + 255) / 256);
     hipLaunchKernelGGL(k_cond_minmax, dim3(gx < 512 ? gx : 512, N), dim3(256), 0, h->stream, drgb, npx, mm);
@@ -123,7 +155,7 @@ int condition_to_device(tf_handle* h, const uint8_t* rgb, int N, int H, int W, c
     return TF_OK;
 }
 
-int condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t* gray_out)
+int condition_frames(tf_handle* h, const Src& rgb, int N, int H, int W, uint8_t* gray_out)
 {
     const uint8_t* dgray = nullptr;
     int rc = condition_to_device(h, rgb, N, H, W, &dgray);
@@ -135,23 +167,33 @@ int condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint
 
 TF_API int tf_condition_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint8_t* gray_out)
 {
-    if (!h || !rgb || !gray_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
-    return finish_host_call(h, condition_frames(h, rgb, N, H, W, gray_out));
+    if (!h) return TF_ERR_INVALID_ARG;
+    const ArmedFrames armed = spend_frames_next(h);
+    if ((!rgb && !armed.on) || !gray_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    Src fr;
+    if (int rc = take_frames(h, "tf_condition_frames", armed, rgb, N, H, W, 3, &fr)) return rc;
+    return finish_host_call(h, condition_frames(h, fr, N, H, W, gray_out));
 }
 
 // the echo alone: rgb uint8 [N][H][W][3] -> float16 [N][H][W] = half(rgb2gray), one rounding
 TF_API int tf_echo_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W, uint16_t* echo16_out)
 {
-    if (!h || !rgb || !echo16_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    if (!h) return TF_ERR_INVALID_ARG;
+    const ArmedFrames armed = spend_frames_next(h);
+    if ((!rgb && !armed.on) || !echo16_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    Src fr;
+    if (int rc = take_frames(h, "tf_echo_frames", armed, rgb, N, H, W, 3, &fr)) return rc;
     const size_t n = (size_t)N * H * W;
     auto run = [&]() -> int {
         HIPC(h, hipSetDevice(h->dev));
         Pre pre(h);
-        auto* drgb = pre.get<uint8_t>(tf_handle::PRE_SRC, n * 3);
+        auto* urgb = fr.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_SRC, n * 3);
         auto* decho = pre.get<uint16_t>(tf_handle::PRE_ECHO, n);
         if (pre.rc) return pre.rc;
-        HIPC(h, hipMemcpyAsync(drgb, rgb, n * 3, hipMemcpyHostToDevice, h->stream));
-        const int rc = echo_from_device_rgb(h, drgb, n, decho, echo16_out);
+        const uint8_t* drgb = nullptr;
+        int rc = frames_to_device(h, fr, 0, n * 3, urgb, &drgb);
+        if (rc) return rc;
+        rc = echo_from_device_rgb(h, drgb, n, decho, echo16_out);
         if (rc) return rc;
         HIPC(h, hipStreamSynchronize(h->stream));
         return TF_OK;
@@ -160,12 +202,12 @@ TF_API int tf_echo_frames(tf_handle* h, const uint8_t* rgb, int N, int H, int W,
 }
 
 namespace {
-// frames (host, uint8 [N][H][W][channels]) -> fine-grained saliency maps [N][H][W] in the handle's preprocessing buffer: uint8, or
+// frames (host, or the held frames; uint8 [N][H][W][channels]) -> fine-grained saliency maps [N][H][W] in the handle's preprocessing buffer: uint8, or
 // (f32) float = map * (1/255), what computeSaliency() returns in opencv-contrib 4.x.  Frames go through in chunks so that the work
 // buffers (17 B per pixel) stay below ~2.3 GB whatever the study's length; the buffers are the handle's and only ever grow.
 // echo16_out (host, or null; channels == 3 only): also the study's float16 `echo`, from each chunk's upload; complete on return
 // (echo_keep: device memory that gets the echo too, see echo_from_device_rgb)
-int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, const uint8_t** dout,
+int saliency_to_device(tf_handle* h, const Src& frames, int N, int H, int W, int channels, bool f32, const uint8_t** dout,
                        uint16_t* echo16_out = nullptr, uint16_t* echo_keep = nullptr)
 {
     const size_t npx = (size_t)H * W, ipx = (size_t)(H + 1) * (W + 1);
@@ -173,7 +215,7 @@ int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W,
     const int nf = chunk_frames(npx, N, 65535, (size_t)1 << 27);   // (the budget counted in pixels: 2^27 of them per chunk)
     HIPC(h, hipSetDevice(h->dev));
     Pre pre(h);
-    auto* src = pre.get<uint8_t>(tf_handle::PRE_SRC, nf * npx * channels);
+    auto* usrc = frames.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_SRC, nf * npx * channels);
     auto* g0 = pre.get<uint8_t>(tf_handle::PRE_G0, nf * npx);
     auto* g1 = pre.get<uint8_t>(tf_handle::PRE_G1, nf * npx);
     auto* ion = pre.get<uint8_t>(tf_handle::PRE_ION, nf * npx);
@@ -191,7 +233,8 @@ int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W,
         const int n = std::min(nf, N - f0);
         const size_t px = (size_t)n * npx;
         const dim3 g2((W + 255) / 256, H, n), blk(256);
-        HIPC(h, hipMemcpyAsync(src, frames + f0 * npx * channels, px * channels, hipMemcpyHostToDevice, h->stream));
+        const uint8_t* src = nullptr;
+        if (int rc = frames_to_device(h, frames, f0 * npx * channels, px * channels, usrc, &src)) return rc;
         HIPC(h, hipEventRecord(h->ev[0], h->stream));       // the eight kernels of the chunk, without the upload
         HIPC(h, hipMemsetAsync(mx, 0, (size_t)n * SAL_MX * sizeof(int), h->stream));
         hipLaunchKernelGGL(sal::k_sal_gray, dim3((unsigned)((px + 255) / 256)), blk, 0, h->stream, src, channels, px, g0);
@@ -219,9 +262,13 @@ int saliency_to_device(tf_handle* h, const uint8_t* frames, int N, int H, int W,
     return TF_OK;
 }
 
-int saliency_frames(tf_handle* h, const uint8_t* frames, int N, int H, int W, int channels, bool f32, void* out)
+int saliency_frames(tf_handle* h, const uint8_t* host_frames, int N, int H, int W, int channels, bool f32, void* out)
 {
-    if (!h || !frames || !out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    if (!h) return TF_ERR_INVALID_ARG;
+    const ArmedFrames armed = spend_frames_next(h);
+    if ((!host_frames && !armed.on) || !out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    Src frames;
+    if (int rc = take_frames(h, "tf_saliency_frames", armed, host_frames, N, H, W, channels, &frames)) return rc;
     if (channels != 1 && channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", channels);
     const uint8_t* d = nullptr;
     int rc = saliency_to_device(h, frames, N, H, W, channels, f32, &d);
@@ -328,7 +375,7 @@ namespace {
 // tf_otsu_masks: the frames, one byte per pixel of the cleaned planes and the output stay on the device for the whole study (6 B per
 // pixel and frame); the labelling scratch (10 B per pixel and frame: parents, flags / sizes, tile-local roots) is the PRE_LB_* slots
 // that every labelling call uses, in chunks of as many frames as fit in MASK_CHUNK_BYTES.  The temporal window runs over all cleaned planes after the last chunk.
-int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* out, double* thr_out)
+int otsu_masks(tf_handle* h, const Src& rgb, int N, int H, int W, long long min_size, uint8_t* out, double* thr_out)
 {
     const size_t HW = (size_t)H * W;
     const int nf = chunk_frames(HW * 10, N);
@@ -336,7 +383,7 @@ int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long 
     // meta: [0, 64) error word; then min / max [N][2] u64, thresholds [N] f64, histograms [N][256] u32
     const size_t off_mm = 64, off_thr = off_mm + (size_t)N * 16, off_hist = off_thr + (size_t)N * 8, meta_bytes = off_hist + (size_t)N * otsu::NBINS * 4;
     Pre pre(h);
-    auto* drgb = pre.get<uint8_t>(tf_handle::PRE_OT_RGB, (size_t)N * HW * 3);
+    auto* urgb = rgb.dev ? nullptr : pre.get<uint8_t>(tf_handle::PRE_OT_RGB, (size_t)N * HW * 3);
     auto* dclean = pre.get<uint8_t>(tf_handle::PRE_OT_CLEAN, (size_t)N * HW);
     auto* dout = pre.get<uint16_t>(tf_handle::PRE_OT_OUT, (size_t)N * HW);
     auto* meta = pre.get<uint8_t>(tf_handle::PRE_OT_META, meta_bytes);
@@ -350,7 +397,8 @@ int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long 
     uint32_t* dhist = (uint32_t*)(meta + off_hist);
     const hipStream_t s = h->stream;
     const std::vector<u64> init = minmax_seed((size_t)N);
-    HIPC(h, hipMemcpyAsync(drgb, rgb, (size_t)N * HW * 3, hipMemcpyHostToDevice, s));
+    const uint8_t* drgb = nullptr;
+    if (int rc = frames_to_device(h, rgb, 0, (size_t)N * HW * 3, urgb, &drgb)) return rc;
     HIPC(h, hipMemsetAsync(meta, 0, meta_bytes, s));
     HIPC(h, hipMemcpyAsync(mm, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, s));
     const dim3 blk(256);
@@ -375,16 +423,21 @@ int otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long 
 
 TF_API int tf_otsu_masks(tf_handle* h, const uint8_t* rgb, int N, int H, int W, long long min_size, uint8_t* masks_out, double* thresholds_out)
 {
-    if (!h || !rgb || !masks_out || N < 2 || H < 2 || W < 2) return TF_ERR_INVALID_ARG;
+    if (!h) return TF_ERR_INVALID_ARG;
+    const ArmedFrames armed = spend_frames_next(h);
+    if ((!rgb && !armed.on) || !masks_out || N < 2 || H < 2 || W < 2) return TF_ERR_INVALID_ARG;
     if ((size_t)H * W > 0x7fffffffu || N > 65535) return TF_ERR_UNSUPPORTED;   // (frames are a grid dimension)
-    return finish_host_call(h, otsu_masks(h, rgb, N, H, W, min_size, masks_out, thresholds_out));
+    Src fr;
+    if (int rc = take_frames(h, "tf_otsu_masks", armed, rgb, N, H, W, 3, &fr)) return rc;
+    return finish_host_call(h, otsu_masks(h, fr, N, H, W, min_size, masks_out, thresholds_out));
 }
 
 namespace {
 // tf_segmentor_input: tables, LUT and frames travel as ONE block -- written into pinned staging, copied to device scratch of the same
 // layout, read by the kernel -- so the call returns with everything queued on `s`.  Layout, in 4-byte words: x bounds [ow][2], x
-// coefficients [ow][kxs], y bounds [oh][2], y coefficients [oh][kys], LUT [3][256]; then, 256-byte aligned, the frames.
-int segmentor_input(tf_handle* h, const uint8_t* rgb, int N, int H, int W, int oh, int ow, const float* lut, float* d_out, hipStream_t s)
+// coefficients [ow][kxs], y bounds [oh][2], y coefficients [oh][kys], LUT [3][256]; then, 256-byte aligned, the frames -- unless they are
+// the held frames, which the kernel reads where they are: then the block is its head alone.
+int segmentor_input(tf_handle* h, const Src& rgb, int N, int H, int W, int oh, int ow, const float* lut, float* d_out, hipStream_t s)
 {
     HIPC(h, hipSetDevice(h->dev));
     int kxs = 0, kys = 0;
@@ -392,7 +445,7 @@ int segmentor_input(tf_handle* h, const uint8_t* rgb, int N, int H, int W, int o
     pil_bilinear_tables(W, ow, kxs, bx, cx);
     pil_bilinear_tables(H, oh, kys, by, cy);
     const size_t off_cx = bx.size(), off_by = off_cx + cx.size(), off_cy = off_by + by.size(), off_lut = off_cy + cy.size();
-    const size_t head = ((off_lut + 3 * 256) * 4 + 255) / 256 * 256, frames = (size_t)N * H * W * 3, total = head + frames;
+    const size_t head = ((off_lut + 3 * 256) * 4 + 255) / 256 * 256, frames = rgb.dev ? 0 : (size_t)N * H * W * 3, total = head + frames;
     for (auto& ev : h->seg_ev) if (!ev) HIPC(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIPC(h, hipEventSynchronize(h->seg_ev[0]));          // the last call's upload has left the staging
     if (h->seg_stage_cap < total) {
@@ -407,7 +460,8 @@ int segmentor_input(tf_handle* h, const uint8_t* rgb, int N, int H, int W, int o
     memcpy(st + off_by, by.data(), by.size() * 4);
     memcpy(st + off_cy, cy.data(), cy.size() * 4);
     memcpy(st + off_lut, lut, 3 * 256 * 4);
-    memcpy((uint8_t*)h->seg_stage + head, rgb, frames);
+    if (frames) memcpy((uint8_t*)h->seg_stage + head, rgb.host, frames);
+    h->frames_upload_bytes += (long long)frames;
     if (h->pre[tf_handle::PRE_SG_IN].cap < total) HIPC(h, hipEventSynchronize(h->seg_ev[1]));   // (growing frees what the last kernel reads)
     Pre pre(h);
     auto* din = pre.get<uint8_t>(tf_handle::PRE_SG_IN, total);
@@ -420,10 +474,11 @@ int segmentor_input(tf_handle* h, const uint8_t* rgb, int N, int H, int W, int o
     const float* dlut = (const float*)(dt + off_lut);
     const unsigned gx = (unsigned)(((size_t)oh * ((ow + 3) / 4) + 255) / 256);
     const size_t fin = (size_t)H * W * 3, fout = (size_t)3 * oh * ow;
+    const uint8_t* dfr = rgb.dev ? (const uint8_t*)rgb.dev : din + head;
     for (int f0 = 0; f0 < N; f0 += 65535) {              // frames are a grid dimension
         const dim3 g(gx, (unsigned)std::min(65535, N - f0)), blk(256);
-        if (ow % 4 == 0) hipLaunchKernelGGL(seg::k_seg_input<true>, g, blk, 0, s, din + head + f0 * fin, H, W, oh, ow, ax, ay, dlut, d_out + f0 * fout);
-        else hipLaunchKernelGGL(seg::k_seg_input<false>, g, blk, 0, s, din + head + f0 * fin, H, W, oh, ow, ax, ay, dlut, d_out + f0 * fout);
+        if (ow % 4 == 0) hipLaunchKernelGGL(seg::k_seg_input<true>, g, blk, 0, s, dfr + f0 * fin, H, W, oh, ow, ax, ay, dlut, d_out + f0 * fout);
+        else hipLaunchKernelGGL(seg::k_seg_input<false>, g, blk, 0, s, dfr + f0 * fin, H, W, oh, ow, ax, ay, dlut, d_out + f0 * fout);
     }
     HIPC(h, hipGetLastError());
     HIPC(h, hipEventRecord(h->seg_ev[1], s));
@@ -467,10 +522,14 @@ int finish_stream_call(hipStream_t s, int rc)
 TF_API int tf_segmentor_input(tf_handle* h, const uint8_t* rgb, int N, int H, int W, int out_h, int out_w, const float* lut, float* d_out,
                               void* hip_stream)
 {
-    if (!h || !rgb || !lut || !d_out || N < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return TF_ERR_INVALID_ARG;
+    if (!h) return TF_ERR_INVALID_ARG;
+    const ArmedFrames armed = spend_frames_next(h);
+    if ((!rgb && !armed.on) || !lut || !d_out || N < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) return TF_ERR_INVALID_ARG;
     if ((size_t)H * W > 0x7fffffffu || (size_t)out_h * out_w > 0x7fffffffu) return TF_ERR_UNSUPPORTED;
+    Src fr;
+    if (int rc = take_frames(h, "tf_segmentor_input", armed, rgb, N, H, W, 3, &fr)) return rc;
     const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    return finish_stream_call(s, segmentor_input(h, rgb, N, H, W, out_h, out_w, lut, d_out, s));
+    return finish_stream_call(s, segmentor_input(h, fr, N, H, W, out_h, out_w, lut, d_out, s));
 }
 
 TF_API int tf_segmentor_classmap(tf_handle* h, const float* d_logits, int N, int C, int hh, int ww, int H, int W, uint8_t* class_map_out,
@@ -1172,10 +1231,11 @@ struct Study {
 
 // the solver's frames of study s on the device (`own`: a submitted job's buffer for them, see condition_to_device)
 // (echo_keep: device memory that gets the study's echo too, or null)
-int study_frames_to_device(tf_handle* h, const Study& s, uint8_t* own, const uint8_t** dfr, uint16_t* echo_keep)
+// (fr: where the frames are, the study's host pointer or the held frames)
+int study_frames_to_device(tf_handle* h, const Study& s, const Src& fr, uint8_t* own, const uint8_t** dfr, uint16_t* echo_keep)
 {
-    return s.sees == FR_GRAY ? condition_to_device(h, s.frames, s.N, s.H, s.W, dfr, own, s.echo16_out, echo_keep)
-                             : saliency_to_device(h, s.frames, s.N, s.H, s.W, s.channels, s.sees == FR_SAL_F32, dfr, s.echo16_out, echo_keep);
+    return s.sees == FR_GRAY ? condition_to_device(h, fr, s.N, s.H, s.W, dfr, own, s.echo16_out, echo_keep)
+                             : saliency_to_device(h, fr, s.N, s.H, s.W, s.channels, s.sees == FR_SAL_F32, dfr, s.echo16_out, echo_keep);
 }
 
 // Buffers of the handle's own for a study of N flow frames, and n_echo echo frames, of H x W; whatever was held before goes.  The
@@ -1247,6 +1307,8 @@ int wase_study_tail(tf_handle* h, const Study& s, const float* dflow, bool hold)
 // the WASE kernels' grid limits -- the order every route had, so each refusal is the one it was (the saliency pass checks its own
 // limits) -- then the frames to the device and the solve.  `submit` (a plain RGB study only): the frames are conditioned now, on the
 // handle's stream, into a buffer the job owns; the solve is queued and *ticket is what tf_wait takes.
+// Armed by tf_frames_next, the call reads the held frames in place of its host pointer (take_frames); a submitted study conditions
+// them into its own buffer before it returns, so they may be replaced at once.
 // Armed by tf_hold_next, a synchronous float16 call also leaves its payload held (teeflow_held.hip.h): N flow frames, the last one
 // repeated, and the echo if the call makes one, copied on the device from what the call wrote there.  The flag is spent by the call,
 // refused or not; the old held study goes once the call's arguments have passed, and a call that fails after that holds nothing.
@@ -1260,8 +1322,11 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
     const bool chain = h && h->chain_next;                   // tf_chain_next: spent likewise
     if (h) h->chain_next = false;
     bool holding = false;                                    // held_alloc has run for this call
+    Src fr;                                                  // tf_frames_next: spent likewise
+    const int frames_rc = h ? take_frames(h, "a study call", spend_frames_next(h), s.frames, s.N, s.H, s.W, s.channels, &fr) : TF_OK;
     auto run = [&]() -> int {
         if (!h) return TF_ERR_INVALID_ARG;
+        if (frames_rc) return frames_rc;
         if (hold && submit) return fail(h, TF_ERR_UNSUPPORTED, "a submitted study cannot be held: tf_hold_next arms a synchronous float16 study call");
         if (hold && !s.out_f16) return fail(h, TF_ERR_UNSUPPORTED, "only a float16 study call can leave its payload held");
         if (s.sees != FR_GRAY && s.channels != 1 && s.channels != 3) return fail(h, TF_ERR_INVALID_ARG, "saliency: frames must have 1 or 3 channels, got %d", s.channels);
@@ -1269,7 +1334,7 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
         if (s.wase && (!s.bkgd || s.n_frames < 1)) return fail(h, TF_ERR_INVALID_ARG, "a wase study needs a bkgd mask of at least 1 frame, got %d", s.n_frames);
         if (submit && (s.sees != FR_GRAY || s.wase)) return fail(h, TF_ERR_UNSUPPORTED, "only a plain RGB study can be submitted");
         // float maps reach the solver as CV_32F frames (DualTVL1: x 255; DeepFlow: as they are); a WASE study's scale is k_wase_out's
-        Call c{MODE_SEQ, s.frames, nullptr, s.N - 1, s.H, s.W, s.wase ? 1.0f : s.scale, s.flow_out, W_HOST, s.sees == FR_SAL_F32, s.out_f16};
+        Call c{MODE_SEQ, (const uint8_t*)(fr.dev ? fr.dev : fr.host), nullptr, s.N - 1, s.H, s.W, s.wase ? 1.0f : s.scale, s.flow_out, W_HOST, s.sees == FR_SAL_F32, s.out_f16};
         c.chain = chain;
         c.keep_only = s.held_only;
         int rc = check_call(h, c);
@@ -1284,7 +1349,7 @@ int study_call(tf_handle* h, const Study& s, tf_stats* st, int* ticket = nullptr
             if ((rc = held_alloc(h, s.N, s.H, s.W, s.echo16_out || s.held_echo ? s.N : 0))) return rc;
             holding = true;
         }
-        rc = study_frames_to_device(h, s, own.p, &c.in0, hold ? h->held.echo : nullptr);
+        rc = study_frames_to_device(h, s, fr, own.p, &c.in0, hold ? h->held.echo : nullptr);
         if (rc) return rc;
         c.where = W_IN_DEV;
         // frames on the device, flows to the caller's host buffer: sub-batch by sub-batch through the pinned, overlapped copy-out path
@@ -1346,10 +1411,10 @@ TF_API int tf_calc_seq_rgb_held(tf_handle* h, const uint8_t* rgb, int N, int H, 
 TF_API int tf_calc_chains_rgb(tf_handle* h, const uint8_t* const* rgb, const int* n_frames, int n_chains, int H, int W, float scale, int out_f16,
                               void* const* flows_out, uint16_t* const* echo16_out, tf_stats* st)
 {
-    const bool hold = spend_flags(h);
+    const int armed = spend_flags(h);
     auto run = [&]() -> int {
         ChainSet cs; Call c;
-        int rc = check_chains(h, (const void* const*)rgb, n_frames, n_chains, H, W, scale, flows_out, W_HOST, out_f16 != 0, hold, &cs, &c);
+        int rc = check_chains(h, (const void* const*)rgb, n_frames, n_chains, H, W, scale, flows_out, W_HOST, out_f16 != 0, armed, &cs, &c);
         if (rc) return rc;
         HIPC(h, hipSetDevice(h->dev));                        // (the scratch below is this handle's device's, whatever the thread's current one)
         const size_t npx = (size_t)H * W;
@@ -1359,7 +1424,7 @@ TF_API int tf_calc_chains_rgb(tf_handle* h, const uint8_t* const* rgb, const int
         for (int s = 0; s < cs.count(); ++s) {
             const int N = cs.pairs[s] + 1;
             const uint8_t* dgray = nullptr;
-            rc = condition_to_device(h, cs.in[s], N, H, W, &dgray, at, echo16_out ? echo16_out[cs.order[s]] : nullptr);
+            rc = condition_to_device(h, Src::on_host(cs.in[s]), N, H, W, &dgray, at, echo16_out ? echo16_out[cs.order[s]] : nullptr);
             if (rc) return rc;
             cs.in[s] = dgray; at += (size_t)N * npx;
         }

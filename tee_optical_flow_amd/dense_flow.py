@@ -13,6 +13,7 @@ C ABI in include/teeflow.h; there is no CPU path.
 import ctypes as C
 import weakref
 from collections import namedtuple
+from functools import partial
 
 import numpy as np
 
@@ -65,6 +66,50 @@ _Job = namedtuple("_Job", "out pad_n extra inputs", defaults=(0, (), ()))
 # What DenseFlow.held reports of the study held on the device: the flow's frames and size, the echo's frames (0: none), the generation
 # (it grows with every replacement and release) and {label: (n_frames, C)} of the held masks
 HeldShape = namedtuple("HeldShape", "N H W n_echo generation masks")
+
+
+class HeldFrames:
+    """What DenseFlow.hold_frames returns: the token of the RGB frames held on the engine's device -- their count and size, and the
+    generation they were held under.  Every method that takes `nparr` or `frames` takes the token in their place and reads the held
+    frames where they are; `token[a:b]` is the token of frames [a, b).  Once the engine holds other frames, or none (hold_frames again,
+    release_frames, close), the token is stale and a call that gets it raises OpticalFlowCalculationError."""
+    dtype, ndim = np.dtype(np.uint8), 4
+
+    def __init__(self, engine, N, H, W, generation, first=0, count=None):
+        self._engine = weakref.ref(engine)
+        self.N, self.H, self.W, self.generation, self.first = int(N), int(H), int(W), int(generation), int(first)
+        self.count = self.N if count is None else int(count)
+
+    @property
+    def shape(self):
+        return (self.count, self.H, self.W, 3)
+
+    def __len__(self):
+        return self.count
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice):
+            raise OpticalFlowCalculationError(f"held frames take a frame range token[a:b], got {key!r}")
+        a, b, step = key.indices(self.count)
+        if step != 1 or b <= a:
+            raise OpticalFlowCalculationError(f"held frames take a non-empty contiguous frame range, got {key!r} of {self.count} frames")
+        return HeldFrames(self._engine(), self.N, self.H, self.W, self.generation, self.first + a, b - a)
+
+    def checked(self, engine, held, min_frames=1):
+        """This token, for a call of `engine`, which now holds `held` = (N, H, W, generation) (N == 0: nothing): raises where the token
+        is another engine's, stale, or shorter than the call's `min_frames`.  No device call."""
+        N, H, W, gen = held
+        if self._engine() is not engine:
+            raise OpticalFlowCalculationError(f"{self!r} belongs to another engine")
+        if gen != self.generation or N < 1:
+            raise OpticalFlowCalculationError(f"{self!r} is stale: the engine now holds " +
+                                              (f"{N} x {H} x {W} frames of generation {gen}" if N else "no frames"))
+        if self.count < min_frames:
+            raise OpticalFlowCalculationError(f"the call needs at least {min_frames} frames, got {self!r}")
+        return self
+
+    def __repr__(self):
+        return f"HeldFrames(frames [{self.first}, {self.first + self.count}) of {self.N} x {self.H} x {self.W} x 3, generation {self.generation})"
 
 
 class _HeldLabels:
@@ -380,14 +425,70 @@ class DenseFlow:
         calc_study_payload(study, scale, pad_last, echo, chain=True) gives for it.  Holds nothing on the device."""
         return self._study_chains(list_of_rgb, scale, pad_last, True, echo)
 
-    def condition_frames(self, nparr):
-        """Device version of frames.condition_frames: uint8 [N,H,W,3] -> uint8 [N,H,W] = img2uint8(rgb2gray(frame)) per frame."""
+    # ---- frames held on the device (tf_hold_frames): ingested once in the form the file stores, read in place by every call below that
+    # takes `nparr` or `frames` ------------------------------------------------------------------------------------------------------------
+    def _held_frames_shape(self):
+        out = (C.c_longlong * 4)()
+        _lib.check(self._L.tf_held_frames_shape(self._h, C.byref(out)), self._h, "tf_held_frames_shape")
+        return tuple(int(v) for v in out)
+
+    def hold_frames(self, arr, form="RGB", flip=False):
+        """Puts a study's frames on the device once, as the file stores them: uint8 "RGB" [N,H,W,3], "GRAY" [N,H,W] (gray2rgb on the
+        device) or "YBR_FULL" [N,H,W,3] of Y, Cb, Cr (pydicom's pixel_array for YBR_FULL and YBR_FULL_422; converted on the device, bit
+        for bit frames.ybr_full_to_rgb); `flip`: columns mirrored (np.flip(axis=2), the reference's flipLR).  What is held is
+        frames.ingest_host(arr, form, flip).  -> the HeldFrames token that stands for these frames in calc_study*, submit_study*,
+        calc_study_held, study_chunks, otsu_masks, segmentor_input, saliency_frames, echo_frames and condition_frames.  Replaces the
+        frames held before (their tokens go stale); a held study is untouched."""
+        if form not in _lib.FRAMES_FORMS:
+            raise OpticalFlowCalculationError(f"form must be one of {tuple(_lib.FRAMES_FORMS)}, got {form!r}")
+        a = _u8_image_stack(arr, "arr", 3 if form == "GRAY" else 4)
+        if (form != "GRAY" and a.shape[3] != 3) or min(a.shape) < 1:
+            raise OpticalFlowCalculationError(f"{form} frames must be {'[N,H,W]' if form == 'GRAY' else '[N,H,W,3]'} with no empty side, got {a.shape}")
+        N, H, W = a.shape[:3]
+        _lib.check(self._L.tf_hold_frames(self._h, a.ctypes.data, _lib.FRAMES_FORMS[form], 1 if flip else 0, N, H, W), self._h, "tf_hold_frames")
+        return HeldFrames(self, N, H, W, self._held_frames_shape()[3])
+
+    def download_frames(self):
+        """The held frames as uint8 RGB [N,H,W,3] on the host (for a host segmentor or host Otsu: the conversion has still left the host)."""
+        N, H, W, _ = self._held_frames_shape()
+        if N < 1:
+            raise OpticalFlowCalculationError("no frames are held (hold_frames)")
+        out = np.empty((N, H, W, 3), np.uint8)
+        _lib.check(self._L.tf_download_frames(self._h, out.ctypes.data), self._h, "tf_download_frames")
+        return out
+
+    def release_frames(self):
+        """Frees the held frames; their tokens go stale."""
+        _lib.check(self._L.tf_release_frames(self._h), self._h, "tf_release_frames")
+
+    def _frames_in(self, frames, check, min_frames=1):
+        """A method's `nparr` / `frames` argument: an array goes through `check`; a HeldFrames token is checked for being this engine's
+        current frames and comes back as it is (it has the array's .shape).  Nothing is armed yet: _frames_ptr does that."""
+        if not isinstance(frames, HeldFrames):
+            return check(frames)
+        return frames.checked(self, self._held_frames_shape(), min_frames)
+
+    def _frames_ptr(self, frames):
+        """The frame pointer of the C call that follows at once: an array's data, or None behind tf_frames_next for a token."""
+        if not isinstance(frames, HeldFrames):
+            return frames.ctypes.data
+        _lib.check(self._L.tf_frames_next(self._h, frames.first, frames.count), self._h, "tf_frames_next")
+        return None
+
+    @staticmethod
+    def _rgb_frames(nparr):
         nparr = _u8_image_stack(nparr, "nparr", 4)
         if nparr.shape[3] != 3:
             raise OpticalFlowCalculationError(f"nparr must be [N,H,W,3], got {nparr.shape}")
+        return nparr
+
+    def condition_frames(self, nparr):
+        """Device version of frames.condition_frames: uint8 [N,H,W,3] (or a HeldFrames token) -> uint8 [N,H,W] =
+        img2uint8(rgb2gray(frame)) per frame."""
+        nparr = self._frames_in(nparr, self._rgb_frames)
         N, H, W, _ = nparr.shape
         out = np.empty((N, H, W), np.uint8)
-        _lib.check(self._L.tf_condition_frames(self._h, nparr.ctypes.data, N, H, W, out.ctypes.data), self._h, "tf_condition_frames")
+        _lib.check(self._L.tf_condition_frames(self._h, self._frames_ptr(nparr), N, H, W, out.ctypes.data), self._h, "tf_condition_frames")
         return out
 
     # ---- a study: RGB frames in, the study file's `flow` array out.  The ten public forms below are cells of one grid -- the solver's
@@ -409,7 +510,7 @@ class DenseFlow:
         wase = bkgd_mask is not None
         if hold and (submit or not f16):
             raise OpticalFlowCalculationError("only a float16 study call that is waited for can leave its payload held")
-        nparr = self._rgb_study(nparr, channels=(1, 3) if saliency and not (f16 or wase) else (3,))
+        nparr = self._frames_in(nparr, partial(self._rgb_study, channels=(1, 3) if saliency and not (f16 or wase) else (3,)), 2)
         N, H, W, ch = nparr.shape
         if wase:
             mask = np.ascontiguousarray(bkgd_mask)
@@ -431,14 +532,14 @@ class DenseFlow:
         else:
             form, own = "_f32" if map_f32 else "", (float(scale), out.ctypes.data, last)
         name = ("tf_submit_seq_" if submit else "tf_calc_seq_") + ("saliency" if saliency else "rgb") + form
-        frames = (self._h, nparr.ctypes.data, N, H, W)
+        sizes = (N, H, W)
         if saliency:
-            frames += (ch, int(map_f32)) if f16 or wase else (ch,)
+            sizes += (ch, int(map_f32)) if f16 or wase else (ch,)
         if chain:
             self.chain_next()                              # (first: a refusal here leaves nothing else armed)
         if hold:
             self.hold_next()
-        _lib.check(getattr(self._L, name)(*frames, *own), self._h, name)
+        _lib.check(getattr(self._L, name)(self._h, self._frames_ptr(nparr), *sizes, *own), self._h, name)
         job = _Job(out, N if pad_last else 0, ((e16,) if f16 else ()) + ((bg,) if wase else ()))
         if submit:
             self._jobs[t.value] = job
@@ -466,10 +567,10 @@ class DenseFlow:
     def echo_frames(self, nparr):
         """The study file's `echo` dataset on the device: RGB frames uint8 [N,H,W,3] -> float16 [N,H,W] =
         frames.rgb2gray(nparr).astype(np.float16), bit for bit (the float64 luma rounded once to half)."""
-        nparr = self._rgb_study(nparr, 1)
+        nparr = self._frames_in(nparr, partial(self._rgb_study, min_frames=1))
         N, H, W, _ = nparr.shape
         out = self._pool.empty((N, H, W), np.float16)
-        _lib.check(self._L.tf_echo_frames(self._h, nparr.ctypes.data, N, H, W, out.ctypes.data), self._h, "tf_echo_frames")
+        _lib.check(self._L.tf_echo_frames(self._h, self._frames_ptr(nparr), N, H, W, out.ctypes.data), self._h, "tf_echo_frames")
         return out
 
     def calc_study_payload(self, nparr, scale=1.0, pad_last=True, echo=True, hold=False, chain=False):
@@ -494,12 +595,12 @@ class DenseFlow:
         flow frames, the last one repeated; the echo if asked for) and nothing is downloaded.  Returns nothing; `last_stats` and
         last_iters() are the float16 call's, and `held` describes the study afterwards.  For a consumer that wants the payload's
         compressed chunks (study_chunks) or its statistics (the held_* calls), not the arrays."""
-        nparr = self._rgb_study(nparr)
+        nparr = self._frames_in(nparr, self._rgb_study, 2)
         N, H, W, _ = nparr.shape
         st = _lib.TfStats()
         if chain:
             self.chain_next()
-        _lib.check(self._L.tf_calc_seq_rgb_held(self._h, nparr.ctypes.data, N, H, W, float(scale), 1 if echo else 0, C.byref(st)), self._h,
+        _lib.check(self._L.tf_calc_seq_rgb_held(self._h, self._frames_ptr(nparr), N, H, W, float(scale), 1 if echo else 0, C.byref(st)), self._h,
                    "tf_calc_seq_rgb_held")
         self._finish(st)
 
@@ -515,20 +616,21 @@ class DenseFlow:
         calculate_optical_flow.py:559-560, :586): uint8 [N,H,W,3] or [N,H,W] -> [N,H,W].  dtype float32 (default): the CV_32F map in
         [0,1] that opencv-contrib 4.x returns; uint8: the algorithm's 8-bit map (opencv-contrib 3.x).  Three-channel frames meet
         OpenCV's BGR2GRAY in the order given, as the reference's RGB frames do."""
-        nparr = np.ascontiguousarray(nparr)
-        if nparr.ndim == 3:
-            nparr = _u8_image_stack(nparr, "nparr", 3)
-            ch = 1
-        else:
+        def check(nparr):
+            nparr = np.ascontiguousarray(nparr)
+            if nparr.ndim == 3:
+                return _u8_image_stack(nparr, "nparr", 3)
             nparr = _u8_image_stack(nparr, "nparr", 4)
-            ch = nparr.shape[3]
-            if ch not in (1, 3):
+            if nparr.shape[3] not in (1, 3):
                 raise OpticalFlowCalculationError(f"nparr must be [N,H,W], [N,H,W,1] or [N,H,W,3], got {nparr.shape}")
+            return nparr
+        nparr = self._frames_in(nparr, check)
+        ch = 1 if len(nparr.shape) == 3 else nparr.shape[3]
         N, H, W = nparr.shape[:3]
         f32 = self._map_is_f32(dtype)
         out = np.empty((N, H, W), np.float32 if f32 else np.uint8)
         fn = self._L.tf_saliency_frames_f32 if f32 else self._L.tf_saliency_frames
-        _lib.check(fn(self._h, nparr.ctypes.data, N, H, W, ch, out.ctypes.data), self._h, "tf_saliency_frames")
+        _lib.check(fn(self._h, self._frames_ptr(nparr), N, H, W, ch, out.ctypes.data), self._h, "tf_saliency_frames")
         return out
 
     @staticmethod
@@ -566,13 +668,13 @@ class DenseFlow:
         the moving average with the reference's defaults over the cleaned planes.  A C-contiguous array in pinned host memory.  With
         `return_thresholds` also the per-frame Otsu thresholds, float64 [N].  May be called while submitted studies are in flight on
         this engine."""
-        nparr = _u8_image_stack(nparr, "nparr", 4)
+        nparr = self._frames_in(nparr, partial(_u8_image_stack, name="nparr", ndim=4))
         if nparr.shape[3] != 3 or min(nparr.shape[:3]) < 2:
             raise OpticalFlowCalculationError(f"nparr must be [N>=2,H>=2,W>=2,3], got {nparr.shape}")
         N, H, W = nparr.shape[:3]
         out = self._pool.empty((N, H, W, 2), np.uint8)
         thr = np.empty(N, np.float64) if return_thresholds else None
-        _lib.check(self._L.tf_otsu_masks(self._h, nparr.ctypes.data, N, H, W, int(min_size), out.ctypes.data,
+        _lib.check(self._L.tf_otsu_masks(self._h, self._frames_ptr(nparr), N, H, W, int(min_size), out.ctypes.data,
                                          thr.ctypes.data if return_thresholds else None), self._h, "tf_otsu_masks")
         return (out.view(np.bool_), thr) if return_thresholds else out.view(np.bool_)
 
@@ -597,7 +699,7 @@ class DenseFlow:
         (a process that made the engine first finds no GPU in torch; a model that sits on the GPU is proof of the right order)."""
         import torch
         from .masks import segmentor_lut
-        frames = _u8_image_stack(frames, "frames", 4)
+        frames = self._frames_in(frames, partial(_u8_image_stack, name="frames", ndim=4))
         if frames.shape[3] != 3:
             raise OpticalFlowCalculationError(f"frames must be [N,H,W,3], got {frames.shape}")
         N, H, W, _ = frames.shape
@@ -610,7 +712,7 @@ class DenseFlow:
             x = torch.empty((max(N, 0), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=dev)
         lut = segmentor_lut()
         s, cur = self._torch_stream(torch)
-        _lib.check(self._L.tf_segmentor_input(self._h, frames.ctypes.data, N, H, W, oh, ow, lut.ctypes.data, x.data_ptr(),
+        _lib.check(self._L.tf_segmentor_input(self._h, self._frames_ptr(frames), N, H, W, oh, ow, lut.ctypes.data, x.data_ptr(),
                                               C.c_void_p(s.cuda_stream)), self._h, "tf_segmentor_input")
         if s is not cur:
             x.record_stream(s)

@@ -57,17 +57,28 @@ def moving_avg_mask(arr, n=4, threshold=0.49, config=None):
     return s[n - 1:] / n > threshold
 
 
-def predict_movie_thres(nparr, verbose=False, config=None, *, engine=None):
+def _frames_arg(nparr, engine, host_frames):
+    """(what a device call takes, () -> the frames on the host): an array is both; a HeldFrames token (DenseFlow.hold_frames) is read
+    on the device where it is, and downloaded -- by `host_frames`, or engine.download_frames -- only where the host has to work."""
+    from .dense_flow import HeldFrames
+    if isinstance(nparr, HeldFrames):
+        return nparr, host_frames or engine.download_frames
+    return np.asarray(nparr), lambda: nparr
+
+
+def predict_movie_thres(nparr, verbose=False, config=None, *, engine=None, host_frames=None):
     """{'otsu': bool [N,H,W,2]} -- NB the reference calls moving_avg_mask WITHOUT config (Appendix C.5).
     With an `engine` that has `otsu_masks` (DenseFlow) and uint8 [N,H,W,3] frames with N, H, W >= 2, the work runs on the device
-    (tf_otsu_masks, exact); otherwise, and for the shapes where the reference's np.squeeze changes what it computes, on the host."""
+    (tf_otsu_masks, exact); otherwise, and for the shapes where the reference's np.squeeze changes what it computes, on the host.
+    `nparr` may be the token of frames the engine holds (`host_frames`: () -> their RGB, for the host path)."""
     from scipy.ndimage import binary_fill_holes
     if config is None:
         config = default_optical_flow_config()
-    arr = np.asarray(nparr)
+    arr, on_host = _frames_arg(nparr, engine, host_frames)
     if (engine is not None and hasattr(engine, "otsu_masks") and arr.dtype == np.uint8 and arr.ndim == 4 and arr.shape[3] == 3
             and min(arr.shape[:3]) >= 2):
         return {"otsu": engine.otsu_masks(arr, config.min_mask_size)}
+    nparr = on_host()
     masks = []
     for i in range(nparr.shape[0]):
         g = rgb2gray(np.squeeze(nparr[i]))
@@ -252,18 +263,21 @@ def _predict_classmaps_device(nparr, model, engine, chunk):
     return np.concatenate(maps)
 
 
-def predict_movie(nparr, model, mode="A4C", verbose=False, config=None, *, engine=None, chunk=16):
+def predict_movie(nparr, model, mode="A4C", verbose=False, config=None, *, engine=None, chunk=16, host_frames=None):
     """Reference :215-241: every frame through the segmentor, then clean_mask (on `engine`'s device when it has clean_masks).
     With an `engine` that has `segmentor_input` (DenseFlow), uint8 [N,H,W,3] frames and a model whose parameters sit on that engine's
     GPU, the glue around the model -- both resizes, the normalised tensor, the argmax -- runs on the device too, `chunk` frames per
-    call (exact: tf_segmentor_input, tf_segmentor_classmap); in every other case evaluate_1_slice runs frame by frame on the host."""
+    call (exact: tf_segmentor_input, tf_segmentor_classmap); in every other case evaluate_1_slice runs frame by frame on the host.
+    `nparr` may be the token of frames the engine holds: the device glue reads them in chunks token[a:b]; `host_frames`: () -> their
+    RGB, for the host path."""
     if config is None:
         config = default_optical_flow_config()
-    arr = np.asarray(nparr)
+    arr, on_host = _frames_arg(nparr, engine, host_frames)
     dev = _model_device(model)
     if (engine is not None and hasattr(engine, "segmentor_input") and arr.dtype == np.uint8 and arr.ndim == 4 and arr.shape[3] == 3
             and min(arr.shape[:3]) >= 1 and dev is not None and dev.type == "cuda" and dev.index == engine.device_id):   # (a bare "cuda": host path)
         preds = _predict_classmaps_device(arr, model, engine, chunk)
     else:
+        nparr = on_host()
         preds = np.stack([evaluate_1_slice(nparr[i], model) for i in range(nparr.shape[0])])
     return clean_mask(preds, mode, verbose, config=config, engine=engine)

@@ -26,7 +26,7 @@ from . import hdf5_out
 from .config import default_optical_flow_config
 from .dense_flow import DenseFlow
 from .exceptions import ConfigurationError, DICOMReadError, OpticalFlowCalculationError
-from .frames import condition_frames
+from .frames import PHOTOMETRIC_FORMS, condition_frames, ybr_full_to_rgb
 
 logger = logging.getLogger(__name__)
 
@@ -336,10 +336,63 @@ def _prep_frames(nparr, flipLR):
     return nparr
 
 
+_frames_fallbacks = set()           # reasons already logged
+
+
+def _check_frames(frames):
+    if frames not in ("host", "device"):
+        raise ConfigurationError(f"frames must be 'host' or 'device', not {frames!r}")
+
+
+def _frames_fallback(reason):
+    if reason not in _frames_fallbacks:
+        _frames_fallbacks.add(reason)
+        logger.warning(f"frames='device' not used, the host prepares the frames instead: {reason}")
+
+
+def _stored_form(arr, photometric):
+    """The device form (frames.FRAME_FORMS) of pixel data `arr` as stored under `photometric` (None: by its shape), or None with the
+    reason why the host has to prepare it."""
+    arr = np.asarray(arr)
+    if photometric is None:
+        photometric = "MONOCHROME2" if arr.ndim == 3 else "RGB"
+    form = PHOTOMETRIC_FORMS.get(str(photometric))
+    if form is None:
+        return None, f"PhotometricInterpretation {photometric!r} has no device form"
+    if arr.dtype != np.uint8 or arr.ndim != (3 if form == "GRAY" else 4) or (form != "GRAY" and arr.shape[3] != 3) or min(arr.shape) < 1:
+        return None, f"the pixel data is not uint8 {'[N,H,W]' if form == 'GRAY' else '[N,H,W,3]'}"
+    if form == "GRAY" and arr.shape[0] < 2:
+        return None, "a grey stack of one frame stays grey (reference :533-536)"
+    return form, None
+
+
+def _stored_to_rgb(arr, photometric, path=None):
+    """What read_study gives for pixel data as stored: the twin's conversion for the YBR forms, the data itself for RGB and grey; any
+    other interpretation is the study file's own converter's (read again through read_study)."""
+    if photometric in ("YBR_FULL", "YBR_FULL_422"):
+        return ybr_full_to_rgb(arr)
+    if photometric in (None, "RGB", "MONOCHROME2") or path is None:
+        return arr
+    return read_study(path)[0]
+
+
+class _DeviceFrames:
+    """A study's frames held on the flow model's device (frames="device"): the token every device call takes, and the RGB for what
+    still runs on the host, downloaded once."""
+
+    def __init__(self, model, stored, form, flip):
+        self.model, self.token, self._rgb = model, model.hold_frames(stored, form, flip=flip), None
+
+    def host(self):
+        if self._rgb is None:
+            self._rgb = self.model.download_frames()
+        return self._rgb
+
+
 def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                   no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                   config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host", chain=False, deflate="host"):
+                  mask_dict=None, _defer_save=None, saliency_map="f32", payload="host", chain=False, deflate="host", frames="host"):
     """Same positional signature as the reference (:478-483).  Keyword-only extras let a caller inject what the
     offline image cannot provide: `nparr` (frames instead of a DICOM), `metadata`, `mask_dict` (segmentation result),
     `flow_model`.  Returns the float32 flow array [N,H,W,2] that was written.  `payload="device"`: the engine hands over the file's
@@ -352,17 +405,24 @@ def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode=
     device: `flow` and `echo`, from the held payload (DenseFlow.held_deflate); the masks and the waveforms stay with the host's
     threads (_device_deflater says why); the chunks are the bytes of zlib level 9 and a dataset under 1 MiB goes through HDF5's own filter
     either way (create_gzip9), so the file is the one deflate="host" writes.  Where payload="device" does not
-    serve, or the model has no held_deflate, the host compresses, with one logged reason."""
+    serve, or the model has no held_deflate, the host compresses, with one logged reason.
+    `frames="device"`: the reference's frame preparation (:524-548: colour space, gray2rgb, flipLR) runs on the flow model's device.  The
+    pixel data goes there once, as the file stores it (read_study_stored; DenseFlow.hold_frames), and the masks and the solve read it
+    there: Otsu masks and the segmentor's glue where the model offers them, every study call.  What runs on the host -- a host
+    segmentor, host Otsu, an `echo` the writer makes -- gets the RGB by one download.  YBR_FULL and YBR_FULL_422 convert as
+    frames.ybr_full_to_rgb (parity with pydicom's converter is unpinned); any other interpretation, pixel data that is not uint8, or a
+    model without hold_frames takes the host path with one logged reason per walk.  The file is the one frames="host" writes."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
-                                saliency_map=saliency_map, payload=payload, chain=chain, deflate=deflate)()
+                                saliency_map=saliency_map, payload=payload, chain=chain, deflate=deflate, frames=frames)()
 
 
 def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True, mode="A4C", bkgd_comp="none", flipLR=False,
                          no_saliency=False, OF_algo="TVL1", save_mask_subset=None, include_waveforms=False, waveform_folder=None,
                          config=None, *, nparr=None, metadata=None, patient_id="", heart_rate=0, waveforms=None, flow_model=None,
-                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host", chain=False, deflate="host"):
+                         mask_dict=None, _defer_save=None, saliency_map="f32", _submit=False, payload="host", chain=False, deflate="host",
+                         frames="host", _photometric=None):
     """process_video in two halves: everything up to the flow solve, then a callable that collects the flows and does the rest (waveforms,
     hand-over to the HDF5 writer) and returns the flow array.  `_submit` (process_folder): where the engine offers it (gray-frame branch,
     no background compensation, a model the caller holds) the solve is only SUBMITTED here -- DenseFlow.submit_study, tf_submit_seq_rgb --
@@ -370,6 +430,7 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     _check_payload(payload)
     _check_deflate(deflate, payload)
     _check_chain(chain, flow_model, OF_algo)
+    _check_frames(frames)
     if config is None:
         config = default_optical_flow_config()
     if mode == "otsu":
@@ -380,7 +441,10 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     if nparr is None:
         # the reference's own call shape, process_video(dcm_path, save_path, ...) (:519-531): read the study file.  `.dcm` needs
         # pydicom (DICOMReadError without it, like a failed _read_dicom_file); `.npy` / `.npz` are the offline injection formats.
-        nparr, md_file, pid_file, hr_file = read_study(dcm_path)
+        if frames == "device":                    # the pixel data as stored: converted, made RGB and flipped on the device below
+            nparr, _photometric, md_file, pid_file, hr_file = read_study_stored(dcm_path)
+        else:
+            nparr, md_file, pid_file, hr_file = read_study(dcm_path)
         if metadata is None:
             metadata = md_file
         patient_id = patient_id or pid_file
@@ -388,7 +452,8 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     nparr = np.asarray(nparr)
     if metadata is None:
         metadata = {"pixel_spacing": None, "frame_rate": None, "R_wave_data_present": False, "R_times": None}
-    nparr = _prep_frames(nparr, flipLR)
+    if frames == "host":
+        nparr = _prep_frames(nparr, flipLR)
     ps, fr = metadata["pixel_spacing"], metadata["frame_rate"]
     conversion_factor = 1.0 if ps is None or fr is None else ps * fr
     if mask_dict is None and mode != "otsu":      # (otsu: made below, once the flow model exists -- on its device when it offers otsu_masks)
@@ -401,15 +466,27 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     own = flow_model is None
     model = make_flow_model(OF_algo, config) if own else flow_model
     walk = _defer_save is not None                # process_folder: the writer stage takes the study
+    held = None                                   # frames="device": the study's frames on the model's device
     try:
+        if frames == "device":
+            form, why = _stored_form(nparr, _photometric)
+            if why is None and not hasattr(model, "hold_frames"):
+                why = f"the flow model ({type(model).__name__}) has no hold_frames"
+            if why is None:
+                held = _DeviceFrames(model, nparr, form, flipLR)
+                nparr = held.token                # (stands for the RGB frames in every device call: it has their shape and dtype)
+            else:
+                _frames_fallback(why)
+                nparr = _prep_frames(np.asarray(_stored_to_rgb(nparr, _photometric, dcm_path)), flipLR)
+        via_host = {"host_frames": held.host} if held is not None else {}     # (for what of the masks runs on the host: one download)
         if mask_dict is None and mode == "otsu":
             # reference :184-213, on the flow model's device when it offers it (DenseFlow.otsu_masks), else numpy / scipy on the host
             from .masks import predict_movie_thres
-            mask_dict = predict_movie_thres(nparr, verbose=verbose, config=config, engine=model)
+            mask_dict = predict_movie_thres(nparr, verbose=verbose, config=config, engine=model, **via_host)
         elif mask_dict is None:
             # reference :549-550; the masks are cleaned on the flow model's device when it offers it (DenseFlow.clean_masks)
             from .masks import predict_movie
-            mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config, engine=model)
+            mask_dict = predict_movie(nparr, segmentor_model, mode=mode, verbose=verbose, config=config, engine=model, **via_host)
         rgb_u8 = _is_rgb_u8(nparr)
         from_device = _payload_served(payload, model, bkgd_comp, nparr)
         if not no_saliency and not rgb_u8:
@@ -419,7 +496,8 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
         _deflate_fallback(why)
         # the echo (from the upload the conditioning / saliency pass reads) only where a file is written; "hold" and "chunks": the study is
         # solved now, synchronously, and its chunks are made while it is held
-        solved = _study_solve(model, np.ascontiguousarray(nparr) if rgb_u8 else None, partial(condition_frames, nparr), mask_dict, bkgd_comp,
+        rgb = None if not rgb_u8 else nparr if held is not None else np.ascontiguousarray(nparr)
+        solved = _study_solve(model, rgb, (lambda: condition_frames(held.host())) if held is not None else partial(condition_frames, nparr), mask_dict, bkgd_comp,
                               conversion_factor, saliency=not no_saliency, saliency_map=saliency_map, payload=route != "host",
                               echo=save_path is not None, submit=_submit and not own and route in ("host", "device"), chain=chain,
                               hold=route == "hold", chunks=route == "chunks")
@@ -436,6 +514,8 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             made = {"flow": hdf5_out.Described(shape + (2,), np.float16), "echo": hdf5_out.Described(shape, np.float16),
                     "records": solved() if route == "chunks" else _held_records(model, shape + (2,), shape)}
             collect = lambda: made
+        # (an `echo` the writer makes needs the RGB: fetched now, while these frames are the held ones)
+        host_rgb = held.host() if held is not None and save_path is not None and route == "host" else None
     finally:
         if own:
             model.close()
@@ -451,7 +531,11 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             if not waveforms_to_write(waveform_results):
                 with_waveforms = False
         if save_path is not None:
-            out = _HandOver(save_path=save_path, nparr=nparr, mask_dict=mask_dict, metadata=metadata, waveforms=waveform_results,
+            frames_out, n_out = nparr, None
+            if held is not None:                  # the writer needs the RGB only for an `echo` nobody has made
+                n_out = nparr.shape[0]
+                frames_out = None if got.get("echo") is not None else host_rgb
+            out = _HandOver(save_path=save_path, nparr=frames_out, nframes=n_out, mask_dict=mask_dict, metadata=metadata, waveforms=waveform_results,
                             patient_id=patient_id, heart_rate=heart_rate, config=config, mode=mode, no_saliency=no_saliency,
                             include_waveforms=with_waveforms, save_mask_subset=save_mask_subset, **got)
             if _defer_save is not None:           # process_folder: the writer stage takes it while the next study is solved
@@ -465,15 +549,40 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
 def read_study(path):
     """Frames + metadata of one study file.  `.dcm` needs pydicom (absent in this image -> DICOMReadError, as the
     reference's _read_dicom_file failure, :520-522); `.npy` (uint8 [N,H,W] or [N,H,W,3]) and `.npz` (key `nparr`, optional
-    `pixel_spacing`, `frame_rate`, `patient_id`, `heart_rate`) are the injection formats of the offline image."""
+    `pixel_spacing`, `frame_rate`, `patient_id`, `heart_rate`, `photometric`) are the injection formats of the offline image.
+    `photometric` (RGB, YBR_FULL, YBR_FULL_422, MONOCHROME2; without it the frames are RGB or grey, as ever) says how `nparr` is stored:
+    YBR data is converted here as frames.ybr_full_to_rgb converts it, in pydicom's place."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".npy":
         return np.load(path, allow_pickle=False), None, "", 0
     if ext == ".npz":
         z = np.load(path, allow_pickle=False)
-        md = {"pixel_spacing": float(z["pixel_spacing"]) if "pixel_spacing" in z else None,
-              "frame_rate": float(z["frame_rate"]) if "frame_rate" in z else None, "R_wave_data_present": False, "R_times": None}
-        return z["nparr"], md, str(z["patient_id"]) if "patient_id" in z else "", int(z["heart_rate"]) if "heart_rate" in z else 0
+        arr, photometric = z["nparr"], _npz_photometric(z, path)
+        if photometric in ("YBR_FULL", "YBR_FULL_422"):                   # (the offline stand-in for pydicom's converter: the twin)
+            arr = ybr_full_to_rgb(arr)
+        return (arr,) + _npz_study(z)
+    ds, arr, pydicom = _read_dicom(path)
+    return dicom_to_study(ds, arr, _pydicom_color_converter(pydicom))
+
+
+def _npz_study(z):
+    """(metadata, patient id, heart rate) of an .npz study"""
+    md = {"pixel_spacing": float(z["pixel_spacing"]) if "pixel_spacing" in z else None,
+          "frame_rate": float(z["frame_rate"]) if "frame_rate" in z else None, "R_wave_data_present": False, "R_times": None}
+    return md, str(z["patient_id"]) if "patient_id" in z else "", int(z["heart_rate"]) if "heart_rate" in z else 0
+
+
+def _npz_photometric(z, path):
+    """The optional `photometric` key of an .npz study: how `nparr` is stored (None: as RGB or grey frames, as ever)."""
+    if "photometric" not in z:
+        return None
+    photometric = str(z["photometric"])
+    if photometric not in PHOTOMETRIC_FORMS:
+        raise DICOMReadError(f"Failed to read {path}: photometric must be one of {sorted(PHOTOMETRIC_FORMS)}, got {photometric!r}")
+    return photometric
+
+
+def _read_dicom(path):
     try:
         import pydicom
     except ImportError as e:
@@ -483,7 +592,24 @@ def read_study(path):
         arr = ds.pixel_array
     except (IOError, OSError, KeyError, AttributeError) as e:             # reference _read_dicom_file (:307-312) -> DICOMReadError (:521-522)
         raise DICOMReadError(f"Failed to read DICOM file: {path}") from e
-    return dicom_to_study(ds, arr, _pydicom_color_converter(pydicom))
+    return ds, arr, pydicom
+
+
+def read_study_stored(path):
+    """read_study without the colour-space step: (pixel data as the file stores it, its PhotometricInterpretation or None, metadata,
+    patient id, heart rate), for frames="device".  The interpretation is named only where the data is to be converted: pydicom's own
+    should_change_PhotometricInterpretation_to_RGB(ds) decides that for a DICOM file, the `photometric` key for an .npz; None means RGB
+    or grey frames by their shape."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        return np.load(path, allow_pickle=False), None, None, "", 0
+    if ext == ".npz":
+        z = np.load(path, allow_pickle=False)
+        return (z["nparr"], _npz_photometric(z, path)) + _npz_study(z)
+    ds, arr, pydicom = _read_dicom(path)
+    convert = pydicom.pixel_data_handlers.numpy_handler.should_change_PhotometricInterpretation_to_RGB(ds)
+    _, md, pid, hr = dicom_to_study(ds, arr)
+    return arr, str(ds.PhotometricInterpretation) if convert else None, md, pid, hr
 
 
 def _pydicom_color_converter(pydicom):
@@ -621,9 +747,10 @@ def _shm_unlink_names(descs):
                 _shm_release([shared_memory.SharedMemory(name=d[1])], unlink=True)
 
 
-def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True):
+def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True, frames="host"):
     """_prepare_study in a worker process, the big arrays returned as shared-memory descriptors."""
-    nparr, md, pid, hr, masks_ahead, echo = _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead)
+    nparr, md, pid, hr, masks_ahead, echo, photometric = _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead,
+                                                                                 *(("device",) if frames == "device" else ()))
     made = []
     try:
         nparr = _shm_put(nparr); made.append(nparr)
@@ -637,7 +764,7 @@ def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead
     except BaseException:
         _shm_unlink_names(made)
         raise
-    return nparr, md, pid, hr, masks_ahead, echo
+    return nparr, md, pid, hr, masks_ahead, echo, photometric
 
 
 def _save_study_shm(out):
@@ -706,11 +833,17 @@ class _StageThreads:
     close = StudyWorkers.close
 
 
-def _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True):
+def _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead=True, frames="host"):
     """Reader stage of process_folder (module level: it also runs in worker processes).  Reads the study and -- for the Otsu mode,
     which is pure numpy/scipy -- computes its masks one study ahead of the GPU; with the solver at milliseconds per pair, this host
     work and the gzip-9 write are what a study costs.  `want_echo`: also the `echo` dataset (rgb2gray of the frames as float16,
-    reference :400-402), so that the writer process does not need the RGB frames."""
+    reference :400-402), so that the writer process does not need the RGB frames.
+    frames="device" (the walk asks for it only with the default reader): the pixel data as stored and its PhotometricInterpretation
+    (read_study_stored), nothing converted, flipped or made from it here -- the walk holds it on the device and makes masks and echo there
+    or from one download."""
+    if frames == "device":
+        arr, photometric, md, pid, hr = read_study_stored(path)
+        return arr, md, pid, hr, None, None, photometric
     nparr, md, pid, hr = reader(path)
     masks_ahead = None
     prepped = _prep_frames(nparr, flipLR)
@@ -721,7 +854,7 @@ def _prepare_study(reader, path, mode, flipLR, config, want_echo, otsu_ahead=Tru
     if want_echo:
         from .frames import rgb2gray
         echo = rgb2gray(prepped).astype(np.float16)
-    return nparr, md, pid, hr, masks_ahead, echo
+    return nparr, md, pid, hr, masks_ahead, echo, None
 
 
 def _spawn_unsafe_reason(reader):
@@ -770,7 +903,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                    include_waveforms=False, waveform_folder=None, pixel_spacing=None, frame_rate=None, process_subset=False,
                    file_subset_list=(), *, rank=0, world=1, extensions=("dcm",), reader=read_study, flow_model=None, config=None,
                    device_id=0, workers="auto", n_readers=None, n_writers=None, studies_in_flight=2, otsu_masks="host", payload="host",
-                   chain=False, deflate="host"):
+                   chain=False, deflate="host", frames="host"):
     """Drop-in for the reference's process_folder (:243-290), same positional signature and the same rules:
       * the folder listing is cut into `nchunks` slices of len // nchunks files, this call takes slice `chunk_index`
         (the remainder files are dropped, as the reference does -- SURVEY.md Appendix C.8);
@@ -811,12 +944,18 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     (logged once).  The host compresses instead, with one logged reason per walk, where the model has neither route, the frames are not
     uint8 RGB, payload="device" does not serve the study, or `flow` or `echo` is under create_gzip9's min_parallel_bytes and so goes
     through HDF5's own filter.
-    Returns the list of (filename, error string)."""
+    `frames`: "host" (default) has the reader stage prepare the frames (colour space, gray2rgb, flipLR; the reference's :524-548);
+    "device" has it hand the pixel data over as stored (read_study_stored: the default `reader` only), and the walk holds it on the flow
+    model once per study (DenseFlow.hold_frames), where it is converted, made RGB and flipped and where masks and solve read it
+    (process_video's doc).  The reader stage then makes neither Otsu masks nor `echo` ahead: masks come from the device where
+    otsu_masks="device" or the segmentor sits on the GPU, else from one download of the RGB.  The files are the same either way."""
     if otsu_masks not in ("host", "device"):
         raise ConfigurationError(f"otsu_masks must be 'host' or 'device', not {otsu_masks!r}")
     _check_payload(payload)
     _check_deflate(deflate, payload)
     _check_chain(chain, flow_model, OF_algo)
+    _check_frames(frames)
+    _frames_fallbacks.clear()                                       # one logged reason per walk
     if deflate == "device":
         _deflate_fallbacks.clear()                                  # one logged reason per walk
         if studies_in_flight > 1:
@@ -851,7 +990,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
                        video_args=dict(segmentor_model=segmentor_model, verbose=verbose, mode=mode, bkgd_comp=bkgd_comp, flipLR=flipLR,
                                        no_saliency=no_saliency, OF_algo=OF_algo, save_mask_subset=save_mask_subset,
                                        include_waveforms=include_waveforms, waveform_folder=waveform_folder, config=config, payload=payload,
-                                       chain=chain, deflate=deflate))
+                                       chain=chain, deflate=deflate), frames=frames)
     try:
         walk.run()
     finally:
@@ -868,10 +1007,11 @@ class _Study:
         self.nparr = self.masks = self.echo = None        # frames, Otsu masks, `echo`: views into `blocks`, or plain arrays
         self.mask_descs = self.echo_desc = None           # what the writer stage gets in their place
         self.md = self.pid = self.hr = self.finish = None  # metadata, patient id, heart rate; _process_video_begin's second half
+        self.photometric = None                           # frames="device": how `nparr` is stored (read_study_stored)
 
     def take(self, prepared, mapped):
         """Unpack what _prepare_study / _prepare_study_shm returned (nothing else knows its layout); `mapped`: and map its blocks."""
-        nparr, self.md, self.pid, self.hr, masks, echo = prepared
+        nparr, self.md, self.pid, self.hr, masks, echo, self.photometric = tuple(prepared) + (None,) * (7 - len(prepared))
         self.descs = [d for d in [nparr, echo] + list((masks or {}).values()) if _is_shm(d)]
         if mapped:
             self.echo_desc, self.mask_descs = echo, masks if masks is not None and any(_is_shm(v) for v in masks.values()) else None
@@ -897,7 +1037,7 @@ class _FolderWalk:
     Worker processes (`use_proc`: asked for, and more than one study to do) are started here, before run() creates the flow model."""
 
     def __init__(self, dcm_folder, todo, reader, workers, use_proc, n_readers, n_writers, flow_model, model_args, in_flight, verbose,
-                 otsu_ahead, payload, prepare_args, video_args):
+                 otsu_ahead, payload, prepare_args, video_args, frames="host"):
         self.dcm_folder, self.todo, self.reader, self.in_flight, self.verbose = dcm_folder, todo, reader, in_flight, verbose
         self.otsu_ahead, self.prepare_args, self.video_args = otsu_ahead, prepare_args, video_args
         self.model, self.own_model, self.model_args = flow_model, flow_model is None, model_args
@@ -922,6 +1062,12 @@ class _FolderWalk:
         # payload="device": the engine makes the echo, so the reader stage is asked for none (a study whose frames turn out not to be
         # uint8 RGB still takes the host path: its frames then travel to the writer, which makes the echo)
         self.device_echo = _payload_served(payload, flow_model, video_args["bkgd_comp"])
+        # frames="device": the reader stage hands the pixel data over as stored (read_study_stored).  Only the default reader can: a
+        # reader of the caller's returns frames the host has prepared already
+        self.frames = frames
+        if frames == "device" and reader is not read_study:
+            _frames_fallback(f"reader={getattr(reader, '__name__', reader)!r} returns prepared frames; only the default reader gives the pixel data as stored")
+            self.frames = "host"
 
     def failed(self, name, e, trace=False):
         logger.error(f"Error processing {name}: {e}")
@@ -944,7 +1090,7 @@ class _FolderWalk:
         if k < len(self.todo) and k not in self.futs:
             self.futs[k] = self.stages.readers.submit(_prepare_study_shm if self.proc else _prepare_study, self.reader,
                                                       os.path.join(self.dcm_folder, self.todo[k][0]), *self.prepare_args, self.proc and not self.device_echo,
-                                                      self.otsu_ahead)
+                                                      self.otsu_ahead, *(("device",) if self.frames == "device" else ()))
 
     def read(self, k, study):
         try:
@@ -984,7 +1130,7 @@ class _FolderWalk:
         in its blocks."""
         if self.proc:
             packed = out.over_arrays(partial(self.to_block, study))
-            packed.nframes = int(np.asarray(out.nparr).shape[0])
+            packed.nframes = out.nframes if out.nframes is not None else int(np.asarray(out.nparr).shape[0])
             if packed.echo is None:
                 packed.echo = study.echo_desc
             if packed.echo is not None:
@@ -1035,7 +1181,8 @@ class _FolderWalk:
                     self.model = make_flow_model(*self.model_args)
                 study.finish = _process_video_begin(os.path.join(self.dcm_folder, filename), save_path, nparr=study.nparr, metadata=study.md,
                                                     patient_id=study.pid, heart_rate=study.hr, flow_model=self.model, mask_dict=study.masks,
-                                                    _defer_save=partial(self.defer, study), _submit=self.in_flight > 1, **self.video_args)
+                                                    _defer_save=partial(self.defer, study), _submit=self.in_flight > 1, frames=self.frames,
+                                                    _photometric=study.photometric, **self.video_args)
                 self.begun.append(study)
             except Exception as e:
                 self.failed(filename, e, trace=True)

@@ -56,7 +56,7 @@ extern "C" {
                               (tf_calc_seq_rgb_f16, tf_submit_seq_rgb_f16, tf_calc_seq_saliency_f16, tf_echo_frames, tf_dbg_f16_round)
                               and the WASE study calls (tf_calc_seq_rgb_wase, tf_calc_seq_saliency_wase), and inflate on the device
                               (tf_inflate, tf_hold_study_chunks, tf_hold_mask_chunks with the new struct tf_chunked), and deflate on the
-                              device (tf_deflate, tf_deflate_array, tf_held_deflate) */
+                              device (tf_deflate, tf_deflate_array, tf_held_deflate), and the test hook tf_dbg_luma_stats */
 
 enum {
     TF_OK = 0,
@@ -744,6 +744,11 @@ int tf_dbg_df_pyramid(tf_handle* h, const void* frame, int is_f32, int H, int W,
 int tf_dbg_df_up(tf_handle* h, const float* u, const float* v, int sw, int sh, float* ou, float* ov, int dw, int dh);
 /* the float16 output kernels' value function on caller-chosen values: out[i] = bits of half(float32(in[i] * scale)), n <= 2^30 */
 int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale, uint16_t* out);
+/* what tf_otsu_masks computes of each frame's float64 luma before it labels anything, by the same three launches (per-frame min / max,
+ * the 256-bin histogram over [min, max], Otsu's threshold): RGB frames uint8 [N][H][W][3] (N, H, W >= 1; H * W < 2^31, N <= 65535) ->
+ * minmax_out [N][2] (min, max), hist_out [N][256], thr_out [N].  A one-valued frame has min == max, an all-zero histogram and that
+ * value as its threshold.  The min / max are also what tf_condition_frames normalises with. */
+int tf_dbg_luma_stats(tf_handle* h, const uint8_t* rgb, int N, int H, int W, double* minmax_out, uint32_t* hist_out, double* thr_out);
 /* Pinned host memory for flow results.  The reference gets a fresh numpy array from cv2 (`flow = OF_model.calc(...)`,
  * calculate_optical_flow.py:631,642); handing tf_calc_pair/_seq/_pairs a destination from tf_host_alloc (or any pinned
  * host pointer) lets the library copy results out at PCIe speed while the next sub-batch is being solved.  Pageable

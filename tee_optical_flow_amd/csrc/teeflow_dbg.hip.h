@@ -198,6 +198,33 @@ TF_API int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale
     return TF_OK;
 }
 
+// what tf_otsu_masks knows of each frame's luma before it labels anything: otsu_luma_stats (teeflow_tail.hip.h) on the caller's frames
+TF_API int tf_dbg_luma_stats(tf_handle* h, const uint8_t* rgb, int N, int H, int W, double* minmax_out, uint32_t* hist_out, double* thr_out)
+{
+    if (!h || !rgb || !minmax_out || !hist_out || !thr_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;
+    if ((size_t)H * W > 0x7fffffffu || N > 65535) return TF_ERR_UNSUPPORTED;   // (frames are a grid dimension, as in tf_otsu_masks)
+    HIPC(h, hipSetDevice(h->dev));
+    const size_t HW = (size_t)H * W, hist_bytes = (size_t)N * otsu::NBINS * sizeof(uint32_t);
+    DevBuf<uint8_t> drgb; DevBuf<u64> mm; DevBuf<uint32_t> hist; DevBuf<double> thr;
+    HIPC(h, hipMalloc(&drgb.p, (size_t)N * HW * 3));
+    HIPC(h, hipMalloc(&mm.p, (size_t)N * 2 * sizeof(u64)));
+    HIPC(h, hipMalloc(&hist.p, hist_bytes));
+    HIPC(h, hipMalloc(&thr.p, (size_t)N * sizeof(double)));
+    const std::vector<u64> init = minmax_seed((size_t)N);
+    HIPC(h, hipMemcpyAsync(drgb.p, rgb, (size_t)N * HW * 3, hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(mm.p, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemsetAsync(hist.p, 0, hist_bytes, h->stream));
+    HIPC(h, hipMemsetAsync(thr.p, 0, (size_t)N * sizeof(double), h->stream));
+    otsu_luma_stats(drgb.p, N, HW, mm.p, hist.p, thr.p, h->stream);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipMemcpyAsync(minmax_out, mm.p, (size_t)N * 2 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));   // (the doubles' own bits)
+    HIPC(h, hipMemcpyAsync(hist_out, hist.p, hist_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(thr_out, thr.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_dbg_luma_stats: %s", hipGetErrorString(e));
+    return TF_OK;
+}
+
 TF_API int tf_dbg_df_refine(tf_handle* h, const float* I0, const float* I1, int w, int hgt, float* u, float* v)
 {
     if (!h || !I0 || !I1 || !u || !v || w < 1 || hgt < 1) return TF_ERR_INVALID_ARG;

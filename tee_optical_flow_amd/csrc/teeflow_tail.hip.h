@@ -372,6 +372,17 @@ TF_API int tf_clean_masks(tf_handle* h, const uint8_t* class_map, int N, int H, 
 }
 
 namespace {
+// The three launches tf_otsu_masks opens with (tf_dbg_luma_stats runs them alone and downloads what they leave): per-frame min / max of
+// the luma, its 256-bin histogram, Otsu's threshold.  mm: [N][2], seeded by minmax_seed; dhist: [N][256], zeroed; dthr: [N].
+void otsu_luma_stats(const uint8_t* drgb, int N, size_t HW, u64* mm, uint32_t* dhist, double* dthr, hipStream_t s)
+{
+    const dim3 blk(256);
+    const unsigned gx = (unsigned)((HW + 255) / 256), gr = gx < 512 ? gx : 512;
+    hipLaunchKernelGGL(k_cond_minmax, dim3(gr, N), blk, 0, s, drgb, HW, mm);
+    hipLaunchKernelGGL(otsu::k_otsu_hist, dim3(gr, N), blk, 0, s, drgb, HW, mm, dhist);
+    hipLaunchKernelGGL(otsu::k_otsu_thr, dim3(N), blk, 0, s, mm, dhist, dthr);
+}
+
 // tf_otsu_masks: the frames, one byte per pixel of the cleaned planes and the output stay on the device for the whole study (6 B per
 // pixel and frame); the labelling scratch (10 B per pixel and frame: parents, flags / sizes, tile-local roots) is the PRE_LB_* slots
 // that every labelling call uses, in chunks of as many frames as fit in MASK_CHUNK_BYTES.  The temporal window runs over all cleaned planes after the last chunk.
@@ -402,10 +413,8 @@ int otsu_masks(tf_handle* h, const Src& rgb, int N, int H, int W, long long min_
     HIPC(h, hipMemsetAsync(meta, 0, meta_bytes, s));
     HIPC(h, hipMemcpyAsync(mm, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, s));
     const dim3 blk(256);
-    const unsigned gx = (unsigned)((HW + 255) / 256), gr = gx < 512 ? gx : 512;
-    hipLaunchKernelGGL(k_cond_minmax, dim3(gr, N), blk, 0, s, drgb, HW, mm);
-    hipLaunchKernelGGL(otsu::k_otsu_hist, dim3(gr, N), blk, 0, s, drgb, HW, mm, dhist);
-    hipLaunchKernelGGL(otsu::k_otsu_thr, dim3(N), blk, 0, s, mm, dhist, dthr);
+    const unsigned gx = (unsigned)((HW + 255) / 256);
+    otsu_luma_stats(drgb, N, HW, mm, dhist, dthr, s);
     for (int f0 = 0; f0 < N; f0 += nf) {                       // one plane per frame
         const int n = std::min(nf, N - f0);
         int rc = fill_and_size_planes(h, otsu::LumaNotAbove{drgb, dthr, f0, HW}, (size_t)n, H, W, dpar, daux, dlr, derr);

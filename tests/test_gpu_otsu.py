@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tee_optical_flow_amd import masks
+from tests import luma_cases
 from tests.test_otsu_cpu import _Cfg, fixture_cases
 
 pytestmark = pytest.mark.gpu
@@ -83,13 +84,10 @@ def test_device_equals_host(engine, kind, N, H, W, min_size):
     want = masks.predict_movie_thres(frames, config=_Cfg(min_size))["otsu"]
     got, thr = engine.otsu_masks(frames, min_size, return_thresholds=True)
     _check(got, want)
-    from tee_optical_flow_amd.frames import rgb2gray
     for f in sorted({0, N // 2, N - 1}):
-        # the host luma goes through numpy's BLAS, which may fuse multiply and add: compare the thresholds of
+        # the host luma goes through numpy's BLAS, whose summation order is its own: compare the thresholds of
         # the plain-order luma, which is what the device evaluates
-        a = frames[f].astype(np.float64) / 255.0
-        g = (a[..., 0] * 0.2125 + a[..., 1] * 0.7154) + a[..., 2] * 0.0721
-        assert thr[f] == masks.threshold_otsu(g), f
+        assert thr[f] == masks.threshold_otsu(luma_cases.luma(frames[f])), f
     assert want.any() and not want.all()
 
 

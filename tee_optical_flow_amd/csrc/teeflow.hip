@@ -10,9 +10,9 @@
 // The stop decision lives on the device (per-pair error slots, blocks of stopped pairs exit at once);
 // each tvl1_iter launch publishes "pairs still iterating" to a host-mapped word, which the host reads a few
 // launches later to stop enqueuing a stage -- it never stalls the stream inside the iteration budget.
-// The host side is cut by what it serves, all of it one translation unit: teeflow_engine.hip.h (Engine, tf_handle), the solvers'
-// teeflow_tvl1_host.hip.h and teeflow_deepflow_host.hip.h, teeflow_queue.hip.h (a call's way to an engine or to the lanes), this file's
-// C ABI entry points, then teeflow_tail.hip.h (the study tail), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
+// The host side is cut by what it serves, all of it one translation unit: teeflow_engine.hip.h (Engine, tf_handle, the one-shot flags), the solvers'
+// teeflow_tvl1_host.hip.h and teeflow_deepflow_host.hip.h, teeflow_queue.hip.h (a call's way to an engine or to the lanes), this file's C ABI entry points, then
+// the study tail, a host header per topic beside its kernel header (listed where they are included), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
 // The device side is one header per kernel family; teeflow_kernels.hip.h holds what the solvers share and includes DualTVL1's
 // stages (teeflow_tvl1_warp / _iter / _median.hip.h) and the tail's frame conditioning (teeflow_cond.hip.h).
 #include "teeflow_kernels.hip.h"
@@ -43,26 +43,6 @@
 // =================================================================================================
 // C ABI
 // =================================================================================================
-namespace {
-// tf_frames_next's state: which handles are armed, and with what range.  It is kept beside the handles, not in them, because the
-// entry points that honour it check their arguments before they read the handle -- a call refused for a null pointer or a bad size
-// touches nothing -- and whether a null frame pointer is a mistake or the armed call's is part of that check.
-struct ArmedFrames { bool on = false; int first = 0, count = 0; };
-std::mutex g_frames_next_m;
-std::map<const tf_handle*, ArmedFrames> g_frames_next;
-
-// the handle's armed range, spent: every call that honours or refuses tf_frames_next takes it first, refused or not
-ArmedFrames spend_frames_next(const tf_handle* h)
-{
-    std::lock_guard<std::mutex> lk(g_frames_next_m);
-    const auto f = g_frames_next.find(h);
-    if (f == g_frames_next.end()) return {};
-    const ArmedFrames a = f->second;
-    g_frames_next.erase(f);
-    return a;
-}
-}  // namespace
-
 TF_API int tf_abi_version(void) { return TF_ABI_VERSION; }
 
 TF_API int tf_device_count(void)
@@ -136,7 +116,7 @@ TF_API void tf_destroy(tf_handle* h)
     dev_free(h->an_rad); dev_free(h->an_lon);
     h->held.release();
     h->frames.release();
-    (void)spend_frames_next(h);
+    (void)spend(h, SPEND_FRAMES);                        // (the address may be the next handle's)
     delete h;
 }
 
@@ -367,111 +347,18 @@ TF_API int tf_calc_pairs_init_device(tf_handle* h, const uint8_t* dI0s, const ui
 }
 
 // ---- a chained sequence (the video idiom `flow = calc(frames[k], frames[k+1], flow)`): armed for the handle's next solve call --------
-// (Call::chain; take_chain and study_call spend the flag)
+// (Call::chain; spend() in teeflow_engine.hip.h says which calls take the flag)
 TF_API int tf_chain_next(tf_handle* h, int on)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    h->chain_next = false;
+    h->armed.chain = false;
     if (!on) return TF_OK;
     if (h->P.algo == TF_ALGO_DEEPFLOW) return fail(h, TF_ERR_UNSUPPORTED, "a chained sequence is DualTVL1's (useInitialFlow): DeepFlow takes no initial flow");
     if (h->P.variant == TF_VARIANT_CUDA) return fail(h, TF_ERR_UNSUPPORTED, "a chained sequence needs useInitialFlow, which TF_VARIANT_CUDA does not implement");
     if (!h->P.use_initial_flow)
         return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is clear: cv2 then ignores a passed flow, so a chain would be the plain solve at the cost of "
                                             "N-1 serial steps; set TF_PARAM_USE_INITIAL_FLOW first, or make the plain call");
-    h->chain_next = true;
-    return TF_OK;
-}
-
-// ---- several chains of one frame size in lock-step: step k solves pair k of every chain still running as one batch --------------------
-namespace {
-// The arguments of a lock-step call -> its chains in the library's order and the Call that carries them, or the refusal; before any GPU
-// work.  frames / flows_out: one pointer per chain, in the caller's order, where `where` says.  armed: what spend_flags found armed.
-enum { ARMED_HOLD = 1, ARMED_FRAMES = 2 };
-int check_chains(tf_handle* h, const void* const* frames, const int* n_frames, int n_chains, int H, int W, float scale, void* const* flows_out,
-                 int where, bool out_f16, int armed, ChainSet* cs, Call* c)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (armed & ARMED_FRAMES) return fail(h, TF_ERR_UNSUPPORTED, "tf_frames_next was armed: chains in lock-step take their frames from the caller's pointers (the flag is spent)");
-    if (armed & ARMED_HOLD) return fail(h, TF_ERR_UNSUPPORTED, "tf_hold_next was armed: chains in lock-step hold nothing (the flag is spent; a study call holds a study)");
-    if (n_chains < 1) return fail(h, TF_ERR_INVALID_ARG, "chains in lock-step: n_chains must be >= 1, got %d", n_chains);
-    if (!frames || !n_frames || !flows_out) return fail(h, TF_ERR_INVALID_ARG, "chains in lock-step: null frames, n_frames or flows_out array");
-    for (int i = 0; i < n_chains; ++i) {
-        if (!frames[i] || !flows_out[i]) return fail(h, TF_ERR_INVALID_ARG, "chains in lock-step: null frame or flow pointer of chain %d", i);
-        if (n_frames[i] < 2) return fail(h, TF_ERR_INVALID_ARG, "chain %d has %d frames: a chain needs at least 2 frames", i, n_frames[i]);
-    }
-    if (h->P.algo == TF_ALGO_DEEPFLOW) return fail(h, TF_ERR_UNSUPPORTED, "chains in lock-step are DualTVL1's (useInitialFlow): DeepFlow takes no initial flow");
-    if (h->P.variant == TF_VARIANT_CUDA) return fail(h, TF_ERR_UNSUPPORTED, "chains in lock-step need useInitialFlow, which TF_VARIANT_CUDA does not implement");
-    if (!h->P.use_initial_flow)
-        return fail(h, TF_ERR_UNSUPPORTED, "useInitialFlow is clear: cv2 then ignores a passed flow, so the chains would be plain solves; set "
-                                            "TF_PARAM_USE_INITIAL_FLOW first, or make the plain calls");
-    const int limit = h->P.max_batch > 0 ? h->P.max_batch : DEFAULT_MAX_BATCH;
-    if (n_chains > limit)
-        return fail(h, TF_ERR_UNSUPPORTED, "%d chains in lock-step: a call takes at most %d, the pairs of one sub-batch (max_batch), since a step "
-                                            "solves one pair of every chain together", n_chains, limit);
-    long long total = 0;
-    std::vector<size_t> first(n_chains);
-    for (int i = 0; i < n_chains; ++i) { first[i] = (size_t)total; total += n_frames[i] - 1; }
-    if (total > std::numeric_limits<int>::max()) return fail(h, TF_ERR_INVALID_ARG, "chains in lock-step: %lld pairs in one call", total);
-    cs->order = chain_order(n_frames, n_chains);
-    for (int i : cs->order) {
-        cs->in.push_back((const uint8_t*)frames[i]); cs->out.push_back(flows_out[i]);
-        cs->pairs.push_back(n_frames[i] - 1); cs->first.push_back(first[i]);
-    }
-    *c = Call{MODE_SEQ, cs->in[0], nullptr, (int)total, H, W, scale, cs->out[0], where, false, out_f16};
-    c->chain = true; c->chains = cs;
-    return check_call(h, *c);
-}
-
-// the flags a lock-step call spends, refused or not: tf_chain_next's (such a call is chained anyway), tf_hold_next's and
-// tf_frames_next's -> which of the last two were armed (ARMED_*)
-int spend_flags(tf_handle* h)
-{
-    if (!h) return 0;
-    const int armed = (h->hold_next ? ARMED_HOLD : 0) | (spend_frames_next(h).on ? ARMED_FRAMES : 0);
-    h->hold_next = h->chain_next = false;
-    return armed;
-}
-
-// a checked lock-step call, solved and waited for: tf_get_iters then gives the counts chain after chain in the caller's order
-int run_chains(tf_handle* h, const Call& c, tf_stats* st)
-{
-    QJob j;
-    start_call(h, c, &j, false);
-    return queue_finish(h, &j, st);
-}
-
-int chains_entry(tf_handle* h, const void* const* frames, const int* n_frames, int n_chains, int H, int W, float scale, void* const* flows_out,
-                 int where, tf_stats* st)
-{
-    ChainSet cs; Call c;
-    const int rc = check_chains(h, frames, n_frames, n_chains, H, W, scale, flows_out, where, false, spend_flags(h), &cs, &c);
-    return rc ? rc : run_chains(h, c, st);
-}
-}  // namespace
-
-TF_API int tf_calc_chains(tf_handle* h, const uint8_t* const* frames, const int* n_frames, int n_chains, int H, int W, float scale,
-                          float* const* flows_out, tf_stats* st)
-{
-    return chains_entry(h, (const void* const*)frames, n_frames, n_chains, H, W, scale, (void* const*)flows_out, W_HOST, st);
-}
-TF_API int tf_calc_chains_device(tf_handle* h, const uint8_t* const* dframes, const int* n_frames, int n_chains, int H, int W, float scale,
-                                 float* const* dflows_out, tf_stats* st)
-{
-    return chains_entry(h, (const void* const*)dframes, n_frames, n_chains, H, W, scale, (void* const*)dflows_out, W_DEV, st);
-}
-
-// the library's order of the chains of a lock-step call (pure host arithmetic, no device call): order_out[s] = the caller's index of the
-// chain in state slot s; first_pair_out[i] = where chain i's pairs start in tf_get_iters' output
-TF_API int tf_dbg_chain_order(const int* n_frames, int n_chains, int* order_out, long long* first_pair_out)
-{
-    if (!n_frames || n_chains < 1 || !order_out) return TF_ERR_INVALID_ARG;
-    const std::vector<int> order = chain_order(n_frames, n_chains);
-    long long total = 0;
-    for (int i = 0; i < n_chains; ++i) {
-        order_out[i] = order[i];
-        if (first_pair_out) first_pair_out[i] = total;
-        total += n_frames[i] - 1;
-    }
+    h->armed.chain = true;
     return TF_OK;
 }
 
@@ -514,12 +401,31 @@ TF_API int tf_wait(tf_handle* h, int ticket, tf_stats* st)
     return rc;
 }
 
-// the study tail: everything around the solver, from frame conditioning to WASE (host code; its kernels are in the kernel headers)
-#include "teeflow_tail.hip.h"
-// a study held on the device and the tail calls that read it there
-#include "teeflow_held.hip.h"
-// inflate on the device: tf_inflate, and a study held from the gzip chunks of its file
-#include "teeflow_inflate_host.hip.h"
+// pinned host memory for results: a destination allocated here makes the host-pointer entry points copy out at PCIe
+// speed, overlapped with the solve of the next sub-batch
+TF_API void* tf_host_alloc(size_t bytes)
+{
+    void* p = nullptr;
+    if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return p;
+}
+TF_API void tf_host_free(void* p)
+{
+    if (p) (void)hipHostFree(p);
+}
+
+// ---- the study tail: everything around the solver, from frame conditioning to WASE; host code, a header per topic in the order they build on each other ----
+#include "teeflow_scratch.hip.h"          // the handle's grow-only scratch, chunking, Src: what every tail call shares
+#include "teeflow_frames_host.hip.h"      // a call's frames (tf_frames_next), conditioning, echo, saliency, the held frames
+#include "teeflow_masks_host.hip.h"       // labelling: clean masks, Otsu, AV centroids, first-region areas
+#include "teeflow_segmentor_host.hip.h"
+#include "teeflow_analysis_host.hip.h"    // rad/long and polar projections, histogram, select
+#include "teeflow_overlay_host.hip.h"
+#include "teeflow_wase_host.hip.h"
+#include "teeflow_held.hip.h"             // a study held on the device and the tail calls that read it there
+#include "teeflow_study_host.hip.h"       // the study calls
+#include "teeflow_chains_host.hip.h"      // several chains in lock-step
+#include "teeflow_inflate_host.hip.h"     // tf_inflate, and a study held from the gzip chunks of its file
 #include "teeflow_deflate_host.hip.h"
 
 TF_API int tf_get_iters(tf_handle* h, int* out, size_t capacity_ints, size_t* written)

@@ -198,7 +198,7 @@ TF_API int tf_dbg_f16_round(tf_handle* h, const float* in, size_t n, float scale
     return TF_OK;
 }
 
-// what tf_otsu_masks knows of each frame's luma before it labels anything: otsu_luma_stats (teeflow_tail.hip.h) on the caller's frames
+// what tf_otsu_masks knows of each frame's luma before it labels anything: otsu_luma_stats (teeflow_masks_host.hip.h) on the caller's frames
 TF_API int tf_dbg_luma_stats(tf_handle* h, const uint8_t* rgb, int N, int H, int W, double* minmax_out, uint32_t* hist_out, double* thr_out)
 {
     if (!h || !rgb || !minmax_out || !hist_out || !thr_out || N < 1 || H < 1 || W < 1) return TF_ERR_INVALID_ARG;

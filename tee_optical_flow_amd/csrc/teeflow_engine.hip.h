@@ -178,7 +178,7 @@ struct Engine : TfKnobs {
 struct tf_handle : Engine {
     std::vector<int> last_iters;                             // tf_get_iters: the last call's iteration counts
     // ---- study tail (conditioning, saliency, masks, centroids, projections, statistics, overlay, WASE): every piece of its device
-    // scratch is one of these grow-only slots, freed with the handle (teeflow_tail.hip.h) ----
+    // scratch is one of these grow-only slots, freed with the handle (teeflow_scratch.hip.h) ----
     struct GrowBuf { void* p = nullptr; size_t cap = 0; };
     enum { PRE_SRC, PRE_G0, PRE_G1, PRE_ION, PRE_IOFF, PRE_P, PRE_I, PRE_MON, PRE_MOFF, PRE_MX, PRE_OUT,
            PRE_LB_PAR, PRE_LB_AUX, PRE_LB_LR,                                     // the labelling's parents, per-root flags / sizes / areas and
@@ -232,8 +232,7 @@ struct tf_handle : Engine {
             flow = echo = nullptr; N = H = W = n_echo = 0;
         }
     } held;
-    bool hold_next = false;      // tf_hold_next: the next study call leaves its payload held
-    // ---- the held frames (teeflow_held.hip.h): a study's uint8 RGB [N][H][W][3] in a device buffer of the handle's own, ingested once
+    // ---- the held frames (teeflow_frames_host.hip.h): a study's uint8 RGB [N][H][W][3] in a device buffer of the handle's own, ingested once
     // (k_ingest) and read in place by every frames-taking call armed with tf_frames_next; separate from the held study ----
     struct Frames {
         uint8_t* rgb = nullptr; size_t cap = 0;              // the buffer only grows; it goes with tf_release_frames or the handle
@@ -242,11 +241,13 @@ struct tf_handle : Engine {
         void drop() { if (N) ++gen; N = H = W = 0; }         // nothing is held any more (the buffer stays)
         void release() { drop(); (void)hipFree(rgb); rgb = nullptr; cap = 0; }   // (the caller has drained the streams that read it)
     } frames;
-    // (tf_frames_next's armed range lives beside the handle, not in it: ArmedFrames in teeflow.hip says why)
     long long frames_upload_bytes = 0;   // bytes of frames that tf_hold_frames and the frames-taking calls have copied host -> device
     long long frames_held_reads = 0;     // frames-taking calls that read the held frames in place
     double ingest_kernel_ms = 0; long long ingest_bytes = 0;   // the last tf_hold_frames: k_ingest's device time and the bytes it read and wrote
-    bool chain_next = false;     // tf_chain_next: the next solve call, a sequence call, is solved as a chain (take_chain spends it)
+    // ---- the one-shot flags of the handle's next call, taken with spend(), below: tf_chain_next (a sequence is solved as a chain),
+    // tf_hold_next (a study call leaves its payload held), tf_frames_next (the call reads held frames [first, first + count)).
+    // `armed` holds the first two; tf_frames_next's part of the record is kept beside the handles (g_frames_next says why) ----
+    struct Armed { bool chain = false, hold = false, frames = false; int first = 0, count = 0; } armed;
     long long chain_steps = 0;   // pairs this handle and its lanes have solved as chain steps ("chain_steps" counter; the pool's lock where there is a pool)
     long long study_download_bytes = 0;   // bytes of flow and echo the synchronous study calls have copied device -> host
     long long tail_upload_bytes = 0;   // bytes of flow, mask and echo the tail calls (and tf_hold_*) have copied host -> device
@@ -273,6 +274,37 @@ TF_API const char* tf_last_error(tf_handle* h);
 TF_API int tf_comm_destroy(tf_handle* h);
 
 namespace {
+// What of the flags `which` names was armed on h, and exactly those cleared: nothing on a null handle.  A call spends its family's
+// flags once, at its start, whatever becomes of it (tests/test_gpu_armed_matrix.py pins the table; a handle is not re-entrant):
+//   family                                                                spends               an armed flag it spends is
+//   pairs and sequence calls (calc_entry, submit_entry)                   chain                honoured by a sequence call, refused by a pairs call (check_call)
+//   study calls (study_call), before any argument check                   chain, hold, frames  honoured, or refused with the call
+//   lock-step calls (check_chains), before any argument check             chain, hold, frames  refused, frames first, then hold; the chain flag changes nothing
+//   frames-taking tail calls (call_frames), before their argument checks  frames               honoured (the handle itself is read only once the checks have passed)
+//   everything else: tf_held_*, tf_hold_*, tf_release_*, tf_set_*, ...    nothing              (a refused tf_chain_next(h, 1) has disarmed the chain itself)
+constexpr tf_handle::Armed SPEND_CHAIN{true, false, false}, SPEND_FRAMES{false, false, true}, SPEND_ALL{true, true, true};
+
+// tf_frames_next's flag and range, by handle.  They are kept beside the handles, not in them, because the frames-taking tail calls
+// spend the flag before their argument checks and must not read the handle before those have passed: a call refused for a null
+// pointer or a bad size touches nothing of it (the CPU tests hand such calls a stand-in for the handle that cannot be read), and
+// whether a null frame pointer is a mistake or the armed call's is part of that check.  spend(h, SPEND_FRAMES) never reads *h.
+std::mutex g_frames_next_m;
+std::map<const tf_handle*, tf_handle::Armed> g_frames_next;
+
+tf_handle::Armed spend(tf_handle* h, const tf_handle::Armed& which)
+{
+    tf_handle::Armed got;
+    if (!h) return got;
+    if (which.frames) {
+        std::lock_guard<std::mutex> lk(g_frames_next_m);
+        const auto f = g_frames_next.find(h);
+        if (f != g_frames_next.end()) { got = f->second; g_frames_next.erase(f); }
+    }
+    if (which.chain) { got.chain = h->armed.chain; h->armed.chain = false; }
+    if (which.hold) { got.hold = h->armed.hold; h->armed.hold = false; }
+    return got;
+}
+
 int fail(Engine* e, int code, const char* fmt, ...)
 {
     char buf[512];

@@ -1,11 +1,41 @@
 // A study held on the device: the study file's payload -- float16 flow, optional float16 echo, up to TF_HELD_SLOTS masks -- in buffers of
 // the handle's own (tf_handle::Held), put there once from host arrays (tf_hold_study, tf_hold_mask) or by the solve that made it
-// (tf_hold_next; study_call in teeflow_tail.hip.h), and the tail calls that read it there.  Included by teeflow.hip after
-// teeflow_tail.hip.h: every tf_held_* call is its original's internal function with device sources (Src) in the place of host ones,
-// so there is one copy of every kernel and launch rule.  Nothing else writes the held buffers: the PRE_* scratch and the resident
-// analysis planes stay what they were.  The file's second half is the input side's equivalent, the held FRAMES (tf_hold_frames & co.).
+// (tf_hold_next; study_call in teeflow_study_host.hip.h, which is included after this), and the tail calls that read it there: every
+// tf_held_* call is its original's internal function with device sources (Src) in the place of host ones, so there is one copy of every
+// kernel and launch rule.  Nothing else writes the held buffers: the PRE_* scratch and the resident analysis planes stay what they
+// were.  Relies on teeflow_masks_host / _analysis_host / _overlay_host.hip.h.
 
 namespace {
+// Buffers of the handle's own for a study of N flow frames, and n_echo echo frames, of H x W; whatever was held before goes.  The
+// caller fills them.  A failure leaves no study held.
+int held_alloc(tf_handle* h, int N, int H, int W, int n_echo)
+{
+    HIPC(h, hipSetDevice(h->dev));
+    HIPC(h, hipStreamSynchronize(h->stream));                 // (the tail calls are host-synchronous: nothing reads the old buffers)
+    tf_handle::Held& k = h->held;
+    k.release();
+    const size_t HW = (size_t)H * W;
+    hipError_t e = hipMalloc(&k.flow, (size_t)N * HW * 2 * sizeof(uint16_t));
+    if (e == hipSuccess && n_echo) e = hipMalloc(&k.echo, (size_t)n_echo * HW * sizeof(uint16_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        k.release();
+        return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding a study of %d x %d x %d: hipMalloc failed: %s", N, H, W, hipGetErrorString(e));
+    }
+    k.N = N; k.H = H; k.W = W; k.n_echo = n_echo;
+    ++k.gen;
+    return TF_OK;
+}
+
+// the held flow's last frame: flow N - 2 repeated, as the study file holds it (queued on the handle's stream)
+int held_repeat_last(tf_handle* h)
+{
+    const tf_handle::Held& k = h->held;
+    const size_t hw2 = (size_t)k.H * k.W * 2;
+    HIPC(h, hipMemcpyAsync(k.flow + (size_t)(k.N - 1) * hw2, k.flow + (size_t)(k.N - 2) * hw2, hw2 * sizeof(uint16_t), hipMemcpyDeviceToDevice, h->stream));
+    return TF_OK;
+}
+
 // the held study, for a call named `who` that reads it: TF_ERR_INVALID_ARG and why when there is none
 int held_study(tf_handle* h, const char* who)
 {
@@ -100,7 +130,7 @@ TF_API int tf_hold_mask(tf_handle* h, int slot, const uint8_t* mask, int n_frame
 TF_API int tf_hold_next(tf_handle* h, int on)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    h->hold_next = on != 0;
+    h->armed.hold = on != 0;
     return TF_OK;
 }
 
@@ -196,117 +226,4 @@ TF_API int tf_held_magnitude_overlay(tf_handle* h, int n_used, int slot, int par
     if (int rc = check_magnitude_overlay(h, who, k.N, k.H, k.W, lut)) return rc;
     return finish_host_call(h, magnitude_overlay<ovl::ECHO_F16>(h, Src::on_device(k.flow), 1, k.N, n_used, k.H, k.W, Src::on_device(m->p), m->C, param, spacing,
                                                                 grad_f64 ? 1 : 0, norm_f64 ? 1 : 0, Src::on_device(k.echo), lut, out, info, frame_info));
-}
-
-// ---- the held frames: a study's RGB frames put on the device once, in the form its file stores them, and read there by every
-// frames-taking call armed with tf_frames_next (take_frames in teeflow_tail.hip.h).  Separate from the held study: neither call
-// touches the other's buffers.  Everything runs on the handle's stream (tf_set_stream included) and is waited for. --------------------
-namespace {
-// nothing queued anywhere still reads the held frames: the handle's stream, and tf_segmentor_input's kernel on a caller's stream
-int frames_quiesce(tf_handle* h)
-{
-    HIPC(h, hipSetDevice(h->dev));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    if (h->seg_ev[1]) HIPC(h, hipEventSynchronize(h->seg_ev[1]));
-    return TF_OK;
-}
-
-template <int FORM>
-void launch_ingest(tf_handle* h, bool flip, const uint8_t* src, size_t npx, int W, uint8_t* out)
-{
-    const dim3 g((unsigned)(((npx + 3) / 4 + 255) / 256)), blk(256);
-    if (flip) hipLaunchKernelGGL((tfg::k_ingest<FORM, true>), g, blk, 0, h->stream, src, npx, W, out);
-    else hipLaunchKernelGGL((tfg::k_ingest<FORM, false>), g, blk, 0, h->stream, src, npx, W, out);
-}
-
-int hold_frames(tf_handle* h, const uint8_t* src, int form, bool flip, int N, int H, int W)
-{
-    int rc = frames_quiesce(h);
-    if (rc) return rc;
-    tf_handle::Frames& k = h->frames;
-    k.drop();
-    const size_t npx = (size_t)N * H * W, in_bytes = npx * (form == TF_FRAMES_GRAY ? 1 : 3), out_bytes = npx * 3;
-    if (k.cap < out_bytes) {
-        (void)hipFree(k.rgb); k.rgb = nullptr; k.cap = 0;
-        const hipError_t e = hipMalloc(&k.rgb, out_bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding frames of %d x %d x %d: hipMalloc failed: %s", N, H, W, hipGetErrorString(e));
-        }
-        k.cap = out_bytes;
-    }
-    h->ingest_kernel_ms = 0; h->ingest_bytes = 0;
-    if (form == TF_FRAMES_RGB && !flip) {                     // nothing to compute: the upload is the held frames
-        HIPC(h, hipMemcpyAsync(k.rgb, src, in_bytes, hipMemcpyHostToDevice, h->stream));
-    } else {
-        Pre pre(h);
-        auto* dsrc = pre.get<uint8_t>(tf_handle::PRE_FR_SRC, in_bytes);
-        if (pre.rc) return pre.rc;
-        HIPC(h, hipMemcpyAsync(dsrc, src, in_bytes, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipEventRecord(h->ev[0], h->stream));
-        if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, dsrc, npx, W, k.rgb);
-        else if (form == TF_FRAMES_YBR_FULL) launch_ingest<tfg::YBR_FULL>(h, flip, dsrc, npx, W, k.rgb);
-        else launch_ingest<tfg::RGB>(h, flip, dsrc, npx, W, k.rgb);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipEventRecord(h->ev[1], h->stream));
-    }
-    HIPC(h, hipStreamSynchronize(h->stream));
-    h->frames_upload_bytes += (long long)in_bytes;
-    if (!(form == TF_FRAMES_RGB && !flip)) {
-        float t = 0;
-        HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        h->ingest_kernel_ms = t; h->ingest_bytes = (long long)(in_bytes + out_bytes);
-    }
-    k.N = N; k.H = H; k.W = W;
-    ++k.gen;
-    return TF_OK;
-}
-}  // namespace
-
-TF_API int tf_hold_frames(tf_handle* h, const void* src, int form, int flip_lr, int N, int H, int W)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (!src || N < 1 || H < 1 || W < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_hold_frames: null source or bad sizes: N=%d H=%d W=%d", N, H, W);
-    if (form != TF_FRAMES_RGB && form != TF_FRAMES_GRAY && form != TF_FRAMES_YBR_FULL)
-        return fail(h, TF_ERR_INVALID_ARG, "tf_hold_frames: form %d is none of TF_FRAMES_RGB (0), TF_FRAMES_GRAY (1), TF_FRAMES_YBR_FULL (2)", form);
-    return finish_host_call(h, hold_frames(h, (const uint8_t*)src, form, flip_lr != 0, N, H, W));
-}
-
-TF_API int tf_held_frames_shape(tf_handle* h, long long* out)
-{
-    if (!h || !out) return TF_ERR_INVALID_ARG;
-    const tf_handle::Frames& k = h->frames;
-    out[0] = k.N; out[1] = k.H; out[2] = k.W; out[3] = k.gen;
-    return TF_OK;
-}
-
-TF_API int tf_release_frames(tf_handle* h)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    if (int rc = frames_quiesce(h)) return rc;
-    h->frames.release();
-    return TF_OK;
-}
-
-TF_API int tf_download_frames(tf_handle* h, uint8_t* rgb_out)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    const tf_handle::Frames& k = h->frames;
-    if (k.N < 1) return fail(h, TF_ERR_INVALID_ARG, "tf_download_frames: no frames are held (tf_hold_frames)");
-    if (!rgb_out) return fail(h, TF_ERR_INVALID_ARG, "tf_download_frames: null output pointer");
-    auto run = [&]() -> int {
-        HIPC(h, hipSetDevice(h->dev));
-        HIPC(h, hipMemcpyAsync(rgb_out, k.rgb, (size_t)k.N * k.H * k.W * 3, hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipStreamSynchronize(h->stream));
-        return TF_OK;
-    };
-    return finish_host_call(h, run());
-}
-
-TF_API int tf_frames_next(tf_handle* h, int first, int count)
-{
-    if (!h) return TF_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(g_frames_next_m);
-    g_frames_next[h] = ArmedFrames{true, first, count};
-    return TF_OK;
 }

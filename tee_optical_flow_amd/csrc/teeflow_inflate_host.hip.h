@@ -1,5 +1,5 @@
 // The host side of inflate on the device (kernels: teeflow_inflate.hip.h): tf_inflate, and a study held from the chunks of its file,
-// tf_hold_study_chunks / tf_hold_mask_chunks.  Included by teeflow.hip after teeflow_held.hip.h.  The compressed bytes, the per-stream
+// tf_hold_study_chunks / tf_hold_mask_chunks.  Included by teeflow.hip after teeflow_held.hip.h and teeflow_study_host.hip.h.  The compressed bytes, the per-stream
 // table and the inflated chunk-major bytes live in the handle's PRE_INF_* slots; a held array is inflated and assembled into a fresh
 // buffer and takes the held one's place only when every chunk of the call has decoded, so a failed call changes nothing.
 

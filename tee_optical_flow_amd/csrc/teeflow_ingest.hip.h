@@ -1,5 +1,5 @@
 // teeflow_ingest.hip.h -- k_ingest: a study's frames as the file stores them (RGB, grey, YBR_FULL) -> uint8 RGB [N][H][W][3], columns
-// mirrored on request (tf_hold_frames, teeflow_held.hip.h).  The pixel arithmetic and the lane's loads and stores are
+// mirrored on request (tf_hold_frames, teeflow_frames_host.hip.h).  The pixel arithmetic and the lane's loads and stores are
 // teeflow_ingest_core.h's, the same text the host checker compiles.  Memory-bound: 1 or 3 bytes in, 3 bytes out per pixel.
 #pragma once
 #define TFG_FN __device__ __forceinline__

@@ -662,7 +662,7 @@ int queue_finish(tf_handle* h, QJob* j, tf_stats* st)
 // tf_chain_next's flag is spent by the next solve call, whatever becomes of it: the call as that flag makes it
 Call take_chain(tf_handle* h, Call c)
 {
-    if (h && h->chain_next) { c.chain = true; h->chain_next = false; }
+    if (spend(h, SPEND_CHAIN).chain) c.chain = true;
     return c;
 }
 

@@ -92,7 +92,9 @@ def test_median_networks_proved_by_zero_one_principle(tmp_path):
 
 def test_hip_sources_have_no_compat_layers():
     for f in ("teeflow.hip", "teeflow_engine.hip.h", "teeflow_tvl1_host.hip.h", "teeflow_deepflow_host.hip.h", "teeflow_queue.hip.h",
-              "teeflow_tail.hip.h", "teeflow_comm.hip.h", "teeflow_dbg.hip.h", "teeflow_kernels.hip.h", "teeflow_tvl1_warp.hip.h",
+              "teeflow_scratch.hip.h", "teeflow_frames_host.hip.h", "teeflow_masks_host.hip.h", "teeflow_segmentor_host.hip.h",
+              "teeflow_analysis_host.hip.h", "teeflow_overlay_host.hip.h", "teeflow_wase_host.hip.h", "teeflow_held.hip.h",
+              "teeflow_study_host.hip.h", "teeflow_chains_host.hip.h", "teeflow_comm.hip.h", "teeflow_dbg.hip.h", "teeflow_kernels.hip.h", "teeflow_tvl1_warp.hip.h",
               "teeflow_tvl1_iter.hip.h", "teeflow_tvl1_median.hip.h", "teeflow_cond.hip.h"):
         txt = open(os.path.join(ROOT, "tee_optical_flow_amd", "csrc", f)).read()
         for bad in ("__HIP_PLATFORM_AMD__", "cuda_runtime", "__CUDACC__", "triton"):

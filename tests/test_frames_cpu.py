@@ -158,3 +158,24 @@ def test_library_declares_the_held_frames_calls():
     for name in ("hold_frames", "download_frames", "release_frames"):
         assert callable(getattr(DenseFlow, name))
     assert _lib.FRAMES_FORMS == {"RGB": 0, "GRAY": 1, "YBR_FULL": 2}
+
+
+def test_a_refused_frames_taking_call_spends_tf_frames_next_without_reading_the_handle():
+    """tf_frames_next's state is kept beside the handles: a frames-taking call refused for its arguments spends the flag and never
+    reads the handle (the same 64-byte stand-in as in test_otsu_cpu and test_segmentor_glue_cpu), armed or not"""
+    import ctypes as C
+    from tee_optical_flow_amd import _lib
+    L = _lib.load()
+    fake = C.create_string_buffer(64)            # never dereferenced: every check comes before the handle is used
+    h = C.addressof(fake)
+    rgb, out = np.zeros((2, 4, 4, 3), np.uint8), np.full((2, 4, 4), 7, np.uint16)
+    for armed in (False, True):
+        for call in (lambda p: L.tf_condition_frames(h, p, 2, 0, 4, out.ctypes.data),
+                     lambda p: L.tf_echo_frames(h, p, 2, 4, -1, out.ctypes.data),
+                     lambda p: L.tf_otsu_masks(h, p, 1, 4, 4, 5, out.ctypes.data, None),
+                     lambda p: L.tf_segmentor_input(h, p, 2, 4, 4, 0, 8, out.ctypes.data, out.ctypes.data, None)):
+            if armed:
+                assert L.tf_frames_next(h, 0, 2) == _lib.TF_OK
+            assert call(None if armed else rgb.ctypes.data) == _lib.TF_ERR_INVALID_ARG
+            assert L.tf_echo_frames(h, None, 2, 4, 4, out.ctypes.data) == _lib.TF_ERR_INVALID_ARG   # spent: a null pointer is a mistake again
+    assert (out == 7).all()

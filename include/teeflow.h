@@ -608,6 +608,41 @@ int tf_release_frames(tf_handle* h);
 int tf_download_frames(tf_handle* h, uint8_t* rgb_out);
 int tf_frames_next(tf_handle* h, int first, int count);
 
+/* ---- frames held from DICOM RLE LOSSLESS pixel data (transfer syntax 1.2.840.10008.1.2.5, PS3.5 Annex G), 8-bit samples: the device
+ *      decodes the PackBits segments itself, one wave per (frame, segment), so what goes over the bus is the compressed bytes and no
+ *      host core touches a pixel.  A frame: a 64-byte header (little-endian uint32 segment count, fifteen little-endian uint32 offsets
+ *      from the frame's first byte), then the segments; segment k is sample plane k, H * W bytes, PackBits-coded (control byte c as
+ *      int8: 0..127 copy the next c + 1 bytes; -1..-127 write the next byte 1 - c times; -128 nothing); it ends where the next starts,
+ *      the last at the frame's end.  What Annex G leaves to the decoder, chosen so that the first H * W bytes are what a
+ *      decode-then-trim reader keeps: a segment's decode stops once H * W bytes are produced and the rest of the segment (the
+ *      even-length pad, other padding, trailing garbage) is ignored; runs and literals may cross row ends; a literal cut off by the
+ *      segment's end gives the bytes that exist; a run whose value byte is missing gives nothing; a segment that ends short fails.
+ * A frame's status: 0 ok; 1 bad header (frame shorter than 64 bytes, or segment count != samples); 2 bad offsets (a first offset
+ *   other than 64 is allowed, but each of the `samples` offsets must be >= 64, < the frame's length and strictly ascending); 3 a
+ *   segment decoded short.  A malformed frame ends with a status: byte i of a frame is read only with i < len, nothing is written
+ *   outside the frame's own H * W * samples bytes.  Annex G is the specification; what pydicom's handler makes of a malformed stream is
+ *   NOT pinned.  The core is csrc/teeflow_rle_core.h (the same text on host and device), frames.rle_decode_frame its Python twin.
+ * Both calls: frame i is the len[i] bytes at blob + off[i] (host; nothing about alignment or padding is assumed); samples is 1 or 3.
+ *   Null pointers, N, H or W < 1, H * W > 2^30, a frame of more than 2^32 - 4096 bytes, samples other than 1 or 3 (tf_hold_frames_rle: other than 1 for TF_FRAMES_GRAY and 3 for
+ *   TF_FRAMES_RGB / TF_FRAMES_YBR_FULL, or an unknown form) and an off[i] + len[i] that overflows are TF_ERR_INVALID_ARG before any GPU work.
+ * tf_rle_decode: -> out_host [N][H][W][samples] and status [N] (both host).  TF_OK when every status is 0; otherwise
+ *   TF_ERR_INVALID_ARG, tf_last_error names the first bad frame and its status, status[] is complete, the good frames' outputs are
+ *   valid and a bad frame's output is not written (tf_inflate's contract).
+ * tf_hold_frames_rle: the compressed bytes are uploaded, decoded into scratch of the handle and waited for once; only when every status
+ *   is 0 are the held frames replaced (the generation moves on) and the planes ingested as tf_hold_frames ingests `form` -- RGB / GRAY /
+ *   YBR_FULL, flip_lr -- so that the held frames, tf_frames_next and every frames-taking call behave exactly as after tf_hold_frames of
+ *   the decoded [N][H][W][samples] array.  On any failure (status may be NULL; where given it is complete) the frames held before stay as they were, generation
+ *   and armed range included (tf_hold_study_chunks' rule).
+ * tf_dbg_counter: "frames_upload_bytes" grows by the compressed bytes uploaded (the span of the blob that holds the frames);
+ *   "rle_kernel_us", "rle_bytes": k_rle_decode's device time in the last of these calls and the bytes it read and wrote (compressed +
+ *   decoded); "ingest_kernel_us", "ingest_bytes" as after tf_hold_frames.  tf_rle_stage_bytes(): the bytes of a segment k_rle_decode
+ *   stages at a time (the tests walk a stream across every position of that boundary). */
+int tf_rle_decode(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                  uint8_t* out_host, int* status);
+int tf_hold_frames_rle(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                       int form, int flip_lr, int* status);
+int tf_rle_stage_bytes(void);
+
 /* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
  *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over
  *      the bus is the compressed bytes.  The output bytes are zlib's or the stream is refused: stored, fixed and dynamic blocks, any

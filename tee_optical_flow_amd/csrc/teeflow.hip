@@ -33,6 +33,7 @@
 #include "teeflow_inflate.hip.h"
 #include "teeflow_deflate.hip.h"
 #include "teeflow_ingest.hip.h"
+#include "teeflow_rle.hip.h"
 #include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include "teeflow_engine.hip.h"
@@ -244,6 +245,8 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "frames_held_reads") v = h->frames_held_reads;
     else if (n == "ingest_kernel_us") v = (long long)(h->ingest_kernel_ms * 1000.0);
     else if (n == "ingest_bytes") v = h->ingest_bytes;
+    else if (n == "rle_kernel_us") v = (long long)(h->rle_kernel_ms * 1000.0);
+    else if (n == "rle_bytes") v = h->rle_bytes;
     else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {

@@ -202,6 +202,8 @@ struct tf_handle : Engine {
            PRE_DF_WORK, PRE_DF_TABLE, PRE_DF_BLOB, PRE_DF_SRC,                    // tf_deflate, tf_deflate_array, tf_held_deflate: a batch's scratch, per-chunk table,
                                                                                   //   the streams end to end, an uploaded array
            PRE_FR_SRC,                                                            // tf_hold_frames: the source bytes as the file stores them, before k_ingest
+           PRE_RLE_BLOB, PRE_RLE_TABLE, PRE_RLE_PLANES, PRE_RLE_OUT,              // tf_rle_decode, tf_hold_frames_rle: compressed bytes, per-frame table, the decoded
+                                                                                  //   sample planes; tf_rle_decode's interleaved frames
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
@@ -244,6 +246,7 @@ struct tf_handle : Engine {
     long long frames_upload_bytes = 0;   // bytes of frames that tf_hold_frames and the frames-taking calls have copied host -> device
     long long frames_held_reads = 0;     // frames-taking calls that read the held frames in place
     double ingest_kernel_ms = 0; long long ingest_bytes = 0;   // the last tf_hold_frames: k_ingest's device time and the bytes it read and wrote
+    double rle_kernel_ms = 0; long long rle_bytes = 0;   // the last tf_rle_decode / tf_hold_frames_rle: k_rle_decode's device time, compressed bytes read + plane bytes written
     // ---- the one-shot flags of the handle's next call, taken with spend(), below: tf_chain_next (a sequence is solved as a chain),
     // tf_hold_next (a study call leaves its payload held), tf_frames_next (the call reads held frames [first, first + count)).
     // `armed` holds the first two; tf_frames_next's part of the record is kept beside the handles (g_frames_next says why) ----

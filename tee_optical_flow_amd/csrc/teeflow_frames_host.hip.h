@@ -1,6 +1,7 @@
 // A call's frames: where it finds them (the caller's host pointer, or the held frames behind tf_frames_next), then what is made of
 // them around the solver -- conditioned gray frames, the float16 echo, saliency maps -- and, in the second half, the held frames
-// themselves (tf_hold_frames & co.).  Relies on teeflow_scratch.hip.h, and on the kernels of teeflow_cond / _saliency / _ingest.hip.h.
+// themselves (tf_hold_frames & co.), last the same from RLE Lossless pixel data (tf_rle_decode, tf_hold_frames_rle).  Relies on
+// teeflow_scratch.hip.h, and on the kernels of teeflow_cond / _saliency / _ingest / _rle.hip.h.
 
 namespace {
 // The RGB frames of a frames-taking call named `who`: the caller's host pointer, or -- armed by tf_frames_next, `a` being what
@@ -316,4 +317,205 @@ TF_API int tf_frames_next(tf_handle* h, int first, int count)
     std::lock_guard<std::mutex> lk(g_frames_next_m);
     g_frames_next[h] = tf_handle::Armed{false, false, true, first, count};
     return TF_OK;
+}
+
+// ---- frames held from DICOM RLE Lossless pixel data (kernel: teeflow_rle.hip.h): the compressed bytes go up, k_rle_decode writes the
+// sample planes into the handle's PRE_RLE_* scratch, and only a call whose every frame decoded touches the held frames -----------------
+namespace {
+constexpr uint32_t RLE_MAX_PLANE = 1u << 30;                  // H * W
+constexpr uint32_t RLE_MAX_FRAME = 0xFFFFF000u;               // a frame's bytes: the kernel's 32-bit positions, do not wrap
+
+const char* rle_status_text(int s)
+{
+    static const char* const text[] = {"ok", "bad header", "bad offsets", "a segment decoded short"};
+    return s >= 0 && s <= 3 ? text[s] : "unknown status";
+}
+
+struct RleJob {
+    const uint8_t* blob; const uint64_t* off; const uint32_t* len; int N, H, W, samples;
+    uint64_t lo = 0, hi = 0;                                  // [lo, hi) of the blob holds every frame (rle_check)
+    size_t plane() const { return (size_t)H * W; }
+};
+
+// before any GPU work
+int rle_check(tf_handle* h, const char* who, RleJob& j)
+{
+    if (!j.blob || !j.off || !j.len) return fail(h, TF_ERR_INVALID_ARG, "%s: null blob, off or len", who);
+    if (j.N < 1 || j.H < 1 || j.W < 1) return fail(h, TF_ERR_INVALID_ARG, "%s: bad sizes: N=%d H=%d W=%d", who, j.N, j.H, j.W);
+    if (j.samples != 1 && j.samples != 3) return fail(h, TF_ERR_INVALID_ARG, "%s: samples must be 1 or 3, got %d", who, j.samples);
+    if ((double)j.H * j.W > RLE_MAX_PLANE) return fail(h, TF_ERR_INVALID_ARG, "%s: a plane of %d x %d bytes, at most %u", who, j.H, j.W, RLE_MAX_PLANE);
+    if ((double)j.N * j.samples > std::numeric_limits<int>::max()) return fail(h, TF_ERR_INVALID_ARG, "%s: %d frames of %d segments", who, j.N, j.samples);
+    j.lo = ~0ull; j.hi = 0;
+    for (int i = 0; i < j.N; ++i) {
+        if (j.len[i] > RLE_MAX_FRAME) return fail(h, TF_ERR_INVALID_ARG, "%s: frame %d has %u bytes, at most %u", who, i, j.len[i], RLE_MAX_FRAME);
+        if (j.off[i] > (~0ull >> 1) - j.len[i])
+            return fail(h, TF_ERR_INVALID_ARG, "%s: frame %d: off %llu + len %u overflows", who, i, (unsigned long long)j.off[i], j.len[i]);
+        j.lo = std::min<uint64_t>(j.lo, j.off[i]); j.hi = std::max<uint64_t>(j.hi, j.off[i] + j.len[i]);
+    }
+    return TF_OK;
+}
+
+// what a launched decode left on the device (valid once the handle's stream has run it)
+struct RleDecoded {
+    const uint8_t* planes = nullptr;                          // [N][samples][H * W]
+    int* status = nullptr;                                    // [N]
+    std::vector<uint8_t> table;                               // the host side of the per-frame table: lives until the stream is waited for
+};
+
+// The frames of j onto the device and k_rle_decode behind them on the handle's stream, between ev[0] and ev[1]; not waited for.
+int rle_launch(tf_handle* h, const RleJob& j, RleDecoded* r)
+{
+    const size_t n = (size_t)j.N, skew = (size_t)(j.lo & 15), bytes = (size_t)(j.hi - j.lo);
+    // the table: off [n] u64 | len [n] u32 | status [n] i32 (zero)
+    const size_t o_len = n * 8, o_st = o_len + n * 4, tb = o_st + n * 4;
+    r->table.assign(tb, 0);
+    uint8_t* t = r->table.data();
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned long long o = j.off[i] - j.lo + skew;      // in the device copy, which keeps the blob's alignment mod 16
+        memcpy(t + i * 8, &o, 8);
+    }
+    memcpy(t + o_len, j.len, n * 4);
+    Pre pre(h);
+    auto* dblob = pre.get<uint8_t>(tf_handle::PRE_RLE_BLOB, skew + bytes + 32);   // (padded: a staged 16-byte piece may pass a frame's end)
+    auto* dtab = pre.get<uint8_t>(tf_handle::PRE_RLE_TABLE, tb);
+    auto* dplanes = pre.get<uint8_t>(tf_handle::PRE_RLE_PLANES, n * j.samples * j.plane());
+    if (pre.rc) return pre.rc;
+    if (bytes) HIPC(h, hipMemcpyAsync(dblob + skew, j.blob + j.lo, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(dtab, t, tb, hipMemcpyHostToDevice, h->stream));
+    h->frames_upload_bytes += (long long)bytes;
+    r->planes = dplanes; r->status = (int*)(dtab + o_st);
+    h->rle_kernel_ms = 0; h->rle_bytes = 0;
+    HIPC(h, hipEventRecord(h->ev[0], h->stream));
+    hipLaunchKernelGGL(k_rle_decode, dim3((unsigned)(n * j.samples)), dim3(64), 0, h->stream, (const uint8_t*)dblob, (const unsigned long long*)dtab,
+                       (const uint32_t*)(dtab + o_len), j.N, j.samples, (uint32_t)j.plane(), dplanes, r->status);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipEventRecord(h->ev[1], h->stream));
+    return TF_OK;
+}
+
+// after the stream has been waited for: the kernel's device time and bytes into the handle's counters
+void rle_counters(tf_handle* h, const RleJob& j)
+{
+    float t = 0;
+    if (hipEventElapsedTime(&t, h->ev[0], h->ev[1]) == hipSuccess) h->rle_kernel_ms = t;
+    (void)hipGetLastError();
+    h->rle_bytes = (long long)(j.hi - j.lo) + (long long)((size_t)j.N * j.samples * j.plane());
+}
+
+// the first frame that did not decode -> the call's failure
+int rle_verdict(tf_handle* h, const char* who, const int* status, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (status[i]) {
+            int bad = 0;
+            for (int k = i; k < n; ++k) bad += status[k] != 0;
+            return fail(h, TF_ERR_INVALID_ARG, "%s: frame %d did not decode: status %d (%s); %d of %d failed", who, i, status[i], rle_status_text(status[i]), bad, n);
+        }
+    return TF_OK;
+}
+
+template <int FORM>
+void launch_ingest_planar(tf_handle* h, bool flip, const uint8_t* src, size_t npx, int W, size_t hw, uint8_t* out)
+{
+    const dim3 g((unsigned)(((npx + 3) / 4 + 255) / 256)), blk(256);
+    if (flip) hipLaunchKernelGGL((tfg::k_ingest_planar<FORM, true>), g, blk, 0, h->stream, src, npx, W, hw, out);
+    else hipLaunchKernelGGL((tfg::k_ingest_planar<FORM, false>), g, blk, 0, h->stream, src, npx, W, hw, out);
+}
+
+int rle_decode(tf_handle* h, const RleJob& j, uint8_t* out_host, int* status)
+{
+    HIPC(h, hipSetDevice(h->dev));
+    RleDecoded r;
+    if (int rc = rle_launch(h, j, &r)) return rc;
+    const size_t npx = (size_t)j.N * j.plane(), frame_bytes = j.plane() * j.samples;
+    const uint8_t* dout = r.planes;                           // (one plane a frame is the frame)
+    if (j.samples == 3) {
+        Pre pre(h);
+        auto* d = pre.get<uint8_t>(tf_handle::PRE_RLE_OUT, npx * 3);
+        if (pre.rc) return pre.rc;
+        launch_ingest_planar<tfg::RGB>(h, false, r.planes, npx, j.W, j.plane(), d);   // (a frame that failed: whatever its planes hold; not copied out)
+        HIPC(h, hipGetLastError());
+        dout = d;
+    }
+    HIPC(h, hipMemcpyAsync(status, r.status, (size_t)j.N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    rle_counters(h, j);
+    bool all = true;
+    for (int i = 0; i < j.N && all; ++i) all = status[i] == 0;
+    if (all) HIPC(h, hipMemcpyAsync(out_host, dout, (size_t)j.N * frame_bytes, hipMemcpyDeviceToHost, h->stream));
+    else
+        for (int i = 0; i < j.N; ++i)
+            if (status[i] == 0) HIPC(h, hipMemcpyAsync(out_host + (size_t)i * frame_bytes, dout + (size_t)i * frame_bytes, frame_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return rle_verdict(h, "tf_rle_decode", status, j.N);
+}
+
+int hold_frames_rle(tf_handle* h, const RleJob& j, int form, bool flip, int* status_out)
+{
+    const char* who = "tf_hold_frames_rle";
+    int rc = frames_quiesce(h);
+    if (rc) return rc;
+    RleDecoded r;
+    if ((rc = rle_launch(h, j, &r))) return rc;
+    std::vector<int> status((size_t)j.N);
+    HIPC(h, hipMemcpyAsync(status.data(), r.status, status.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    rle_counters(h, j);
+    if (status_out) memcpy(status_out, status.data(), status.size() * sizeof(int));
+    if ((rc = rle_verdict(h, who, status.data(), j.N))) return rc;
+    // every frame decoded: from here on as hold_frames, the planes in the uploaded source's place
+    tf_handle::Frames& k = h->frames;
+    const size_t npx = (size_t)j.N * j.plane(), in_bytes = npx * j.samples, out_bytes = npx * 3;
+    if (k.cap < out_bytes) {                                  // (the new buffer first: a failed allocation leaves the held frames)
+        uint8_t* p = nullptr;
+        const hipError_t e = hipMalloc(&p, out_bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding frames of %d x %d x %d: hipMalloc failed: %s", j.N, j.H, j.W, hipGetErrorString(e));
+        }
+        (void)hipFree(k.rgb);
+        k.rgb = p; k.cap = out_bytes;
+    }
+    k.drop();
+    h->ingest_kernel_ms = 0; h->ingest_bytes = 0;
+    HIPC(h, hipEventRecord(h->ev[0], h->stream));
+    if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, r.planes, npx, j.W, k.rgb);
+    else if (form == TF_FRAMES_YBR_FULL) launch_ingest_planar<tfg::YBR_FULL>(h, flip, r.planes, npx, j.W, j.plane(), k.rgb);
+    else launch_ingest_planar<tfg::RGB>(h, flip, r.planes, npx, j.W, j.plane(), k.rgb);
+    HIPC(h, hipGetLastError());
+    HIPC(h, hipEventRecord(h->ev[1], h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    float t = 0;
+    HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
+    h->ingest_kernel_ms = t; h->ingest_bytes = (long long)(in_bytes + out_bytes);
+    k.N = j.N; k.H = j.H; k.W = j.W;
+    ++k.gen;
+    return TF_OK;
+}
+}  // namespace
+
+TF_API int tf_rle_stage_bytes(void) { return (int)rle::STAGE; }
+
+TF_API int tf_rle_decode(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                         uint8_t* out_host, int* status)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    RleJob j{blob, off, len, N, H, W, samples};
+    if (int rc = rle_check(h, "tf_rle_decode", j)) return rc;
+    if (!out_host || !status) return fail(h, TF_ERR_INVALID_ARG, "tf_rle_decode: null out_host or status");
+    return finish_host_call(h, rle_decode(h, j, out_host, status));
+}
+
+TF_API int tf_hold_frames_rle(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                              int form, int flip_lr, int* status)
+{
+    if (!h) return TF_ERR_INVALID_ARG;
+    const char* who = "tf_hold_frames_rle";
+    if (form != TF_FRAMES_RGB && form != TF_FRAMES_GRAY && form != TF_FRAMES_YBR_FULL)
+        return fail(h, TF_ERR_INVALID_ARG, "%s: form %d is none of TF_FRAMES_RGB (0), TF_FRAMES_GRAY (1), TF_FRAMES_YBR_FULL (2)", who, form);
+    if (samples != (form == TF_FRAMES_GRAY ? 1 : 3))
+        return fail(h, TF_ERR_INVALID_ARG, "%s: form %d has %d samples a pixel, got samples = %d", who, form, form == TF_FRAMES_GRAY ? 1 : 3, samples);
+    RleJob j{blob, off, len, N, H, W, samples};
+    if (int rc = rle_check(h, who, j)) return rc;
+    return finish_host_call(h, hold_frames_rle(h, j, form, flip_lr != 0, status));
 }

@@ -13,4 +13,11 @@ __global__ __launch_bounds__(256) void k_ingest(const uint8_t* __restrict__ src,
 {
     ingest_lane<FORM, FLIP>(src, npx, W, (size_t)blockIdx.x * 256 + threadIdx.x, out);
 }
+
+// the same from sample planes [N][3][hw], hw = H * W (k_rle_decode's scratch): the interleave is this kernel's, not the decoder's
+template <int FORM, bool FLIP>
+__global__ __launch_bounds__(256) void k_ingest_planar(const uint8_t* __restrict__ src, size_t npx, int W, size_t hw, uint8_t* __restrict__ out)
+{
+    ingest_lane<FORM, FLIP, true>(src, npx, W, (size_t)blockIdx.x * 256 + threadIdx.x, out, hw);
+}
 }  // namespace tfg

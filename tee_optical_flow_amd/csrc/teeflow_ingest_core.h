@@ -68,14 +68,39 @@ TFG_FN void store32(uint8_t* p, uint32_t w) { __builtin_memcpy(__builtin_assume_
 // reads source pixel (row, W - 1 - x) of the same row -- rows are frames' rows back to back, so a run may cross a row's or a frame's
 // end -- through byte loads.  The last lane's run may be short (npx % 4 pixels): byte loads and byte stores, nothing beyond 3 * npx.
 // src and out are dword-aligned (device allocations; malloc'd buffers on the host).
-template <int FORM, bool FLIP>
-TFG_FN void ingest_lane(const uint8_t* src, size_t npx, int W, size_t lane, uint8_t* out)
+// PLANAR (RGB and YBR_FULL; what the RLE decoder leaves, teeflow_rle.hip.h): the source is [N][3][hw] sample planes, hw = H * W bytes
+// each, in place of [N][H][W][3] -- pixel q of frame f has its samples at (3 * f + c) * hw + q.  Where hw is a multiple of 4 a run
+// without FLIP lies in one frame and every plane starts dword-aligned: three dword loads; otherwise byte loads.
+template <int FORM, bool FLIP, bool PLANAR = false>
+TFG_FN void ingest_lane(const uint8_t* src, size_t npx, int W, size_t lane, uint8_t* out, size_t hw = 0)
 {
+    static_assert(!PLANAR || FORM != GRAY, "one grey plane is the interleaved form already");
     const size_t p0 = lane * 4;
     if (p0 >= npx) return;
     const int n = npx - p0 < 4 ? (int)(npx - p0) : 4;
     uint8_t b[12];
-    if (!FLIP && n == 4) {
+    if (PLANAR) {
+        uint8_t s[12];
+        const size_t f0 = p0 / hw, q0 = p0 - f0 * hw;
+        if (!FLIP && n == 4 && (hw & 3) == 0) {
+            for (int c = 0; c < 3; ++c) {
+                const uint32_t w = load32(src + (3 * f0 + (size_t)c) * hw + q0);
+                for (int j = 0; j < 4; ++j) s[3 * j + c] = (uint8_t)(w >> (8 * j));
+            }
+        } else {
+            size_t row = FLIP ? p0 / (size_t)W : 0;
+            int x = FLIP ? (int)(p0 - row * (size_t)W) : 0;
+            size_t f = f0, qo = q0;                                              // output pixel p0 + k is pixel qo of frame f
+            for (int k = 0; k < n; ++k) {
+                // (the mirrored pixel is in the output pixel's row: the same frame)
+                const size_t q = FLIP ? row * (size_t)W + (size_t)(W - 1 - x) - f * hw : qo;
+                for (int c = 0; c < 3; ++c) s[3 * k + c] = src[(3 * f + (size_t)c) * hw + q];
+                if (FLIP && ++x == W) { x = 0; ++row; }
+                if (++qo == hw) { qo = 0; ++f; }
+            }
+        }
+        for (int k = 0; k < n; ++k) pixel<FORM>(s, (size_t)k, b + 3 * k);
+    } else if (!FLIP && n == 4) {
         if (FORM == GRAY) {
             const uint32_t g = load32(src + p0);
             for (int k = 0; k < 4; ++k) b[3 * k] = b[3 * k + 1] = b[3 * k + 2] = (uint8_t)(g >> (8 * k));

@@ -461,6 +461,60 @@ class DenseFlow:
         """Frees the held frames; their tokens go stale."""
         _lib.check(self._L.tf_release_frames(self._h), self._h, "tf_release_frames")
 
+    # ---- DICOM RLE Lossless pixel data (tf_rle_decode, tf_hold_frames_rle): the PackBits segments are decoded on the device, one wave per
+    # (frame, segment); frames.rle_decode_frame is the twin, frames.rle_record makes the record ------------------------------------------
+    @staticmethod
+    def _rle_record(record, H, W, samples):
+        """(blob, off, len) of frames.rle_record, checked -> the three C-contiguous arrays and the sizes as ints"""
+        try:
+            blob, off, ln = record
+        except (TypeError, ValueError):
+            raise OpticalFlowCalculationError("an RLE record is (blob, off, len), as frames.rle_record makes it") from None
+        blob = np.ascontiguousarray(blob, np.uint8).reshape(-1)
+        off, ln = np.ascontiguousarray(off, np.uint64).reshape(-1), np.ascontiguousarray(ln, np.uint32).reshape(-1)
+        H, W, samples = int(H), int(W), int(samples)
+        if off.shape != ln.shape or off.size < 1 or off.size > 2 ** 31 - 1:
+            raise OpticalFlowCalculationError(f"an RLE record needs one off and one len per frame and at least one frame, got {off.size} and {ln.size}")
+        if H < 1 or W < 1 or H * W > 2 ** 30 or samples not in (1, 3):
+            raise OpticalFlowCalculationError(f"RLE frames are H x W x samples with H, W >= 1, H * W <= 2^30 and samples 1 or 3, got {H} x {W} x {samples}")
+        if max(int(o) + int(n) for o, n in zip(off, ln)) > blob.size:
+            raise OpticalFlowCalculationError(f"RLE record: a frame ends behind the blob's {blob.size} bytes")
+        if blob.size == 0:
+            blob = np.zeros(1, np.uint8)
+        return blob, off, ln, H, W, samples
+
+    def rle_decode(self, record, H, W, samples):
+        """RLE Lossless frames -- record = (blob, off, len), frame i the len[i] bytes at blob[off[i]:] (frames.rle_record) -- of H x W
+        pixels of `samples` (1 or 3) 8-bit samples -> (uint8 [N,H,W,samples], or [N,H,W] for samples == 1; status int32 [N]).  A status
+        is 0, 1 bad header, 2 bad offsets or 3 a segment decoded short (frames.rle_decode_frame has the rules); the call does not raise
+        for a frame that does not decode: its status says so and its frame is zeros.  A call that fails as a whole -- refused
+        arguments, a HIP error -- raises."""
+        blob, off, ln, H, W, samples = self._rle_record(record, H, W, samples)
+        N = off.size
+        out = np.zeros((N, H, W) if samples == 1 else (N, H, W, samples), np.uint8)
+        status = np.zeros(N, np.int32)
+        rc = self._L.tf_rle_decode(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, out.ctypes.data, status.ctypes.data)
+        if rc != _lib.TF_OK and not status.any():            # not a verdict on a frame: the call itself failed
+            _lib.check(rc, self._h, "tf_rle_decode")
+        return out, status
+
+    def hold_frames_rle(self, record, H, W, samples, form="RGB", flip=False):
+        """hold_frames from RLE Lossless pixel data as the file stores it: record = (blob, off, len) (frames.rle_record, or
+        pipeline.dicom_rle_frames' fields), H x W pixels of `samples` 8-bit samples -- 1 for form "GRAY", 3 for "RGB" and "YBR_FULL".
+        Only the compressed bytes are uploaded; the device decodes them and ingests the planes as hold_frames ingests `form` and `flip`.
+        -> the HeldFrames token; what is held is frames.ingest_host(decoded, form, flip).  If a frame does not decode the call raises
+        with the first bad frame and its status, and the frames held before, their generation and their tokens stay as they were."""
+        if form not in _lib.FRAMES_FORMS:
+            raise OpticalFlowCalculationError(f"form must be one of {tuple(_lib.FRAMES_FORMS)}, got {form!r}")
+        blob, off, ln, H, W, samples = self._rle_record(record, H, W, samples)
+        if samples != (1 if form == "GRAY" else 3):
+            raise OpticalFlowCalculationError(f"{form} frames have {1 if form == 'GRAY' else 3} samples a pixel, got samples = {samples}")
+        N = off.size
+        status = np.zeros(N, np.int32)
+        _lib.check(self._L.tf_hold_frames_rle(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, _lib.FRAMES_FORMS[form],
+                                              1 if flip else 0, status.ctypes.data), self._h, "tf_hold_frames_rle")
+        return HeldFrames(self, N, H, W, self._held_frames_shape()[3])
+
     def _frames_in(self, frames, check, min_frames=1):
         """A method's `nparr` / `frames` argument: an array goes through `check`; a HeldFrames token is checked for being this engine's
         current frames and comes back as it is (it has the array's .shape).  Nothing is armed yet: _frames_ptr does that."""

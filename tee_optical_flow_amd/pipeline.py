@@ -26,7 +26,8 @@ from . import hdf5_out
 from .config import default_optical_flow_config
 from .dense_flow import DenseFlow
 from .exceptions import ConfigurationError, DICOMReadError, OpticalFlowCalculationError
-from .frames import PHOTOMETRIC_FORMS, condition_frames, ybr_full_to_rgb
+from .frames import (PHOTOMETRIC_FORMS, RLE_STATUS_TEXT, RLE_TRANSFER_SYNTAX, condition_frames, encapsulated_frames, rle_decode_frame, rle_record,
+                     ybr_full_to_rgb)
 
 logger = logging.getLogger(__name__)
 
@@ -376,12 +377,95 @@ def _stored_to_rgb(arr, photometric, path=None):
     return read_study(path)[0]
 
 
+@dataclass(frozen=True)
+class RleFrames:
+    """A study's pixel data as a DICOM RLE Lossless file stores it (transfer syntax 1.2.840.10008.1.2.5, 8-bit samples): frame i is the
+    len[i] bytes at blob[off[i]:] (blob uint8, off uint64, len uint32: frames.rle_record's), `shape` = (N, H, W), `samples` 1 or 3 a
+    pixel.  `photometric`: the dataset's PhotometricInterpretation where dicom_rle_frames read one.  What frames="device" hands to
+    DenseFlow.hold_frames_rle in an array's place; decode() is the host's way to the array (frames.rle_decode_frame, the twin)."""
+    blob: object
+    off: object
+    len: object
+    shape: tuple
+    samples: int
+    photometric: object = None
+
+    @property
+    def record(self):
+        return self.blob, self.off, self.len
+
+    def decode(self):
+        """-> uint8 [N,H,W] (samples == 1) or [N,H,W,samples], as pydicom's pixel_array gives them; DICOMReadError for a frame that does not decode"""
+        N, H, W = self.shape
+        blob = np.asarray(self.blob, np.uint8)
+        out = np.empty((N, H, W) if self.samples == 1 else (N, H, W, self.samples), np.uint8)
+        for i in range(N):
+            a = int(self.off[i])
+            out[i], status = rle_decode_frame(blob[a:a + int(self.len[i])].tobytes(), H, W, self.samples)
+            if status:
+                raise DICOMReadError(f"RLE Lossless frame {i} did not decode: status {status} ({RLE_STATUS_TEXT[status]})")
+        return out
+
+
+def _rle_refusal(ds):
+    """Why a dataset in the RLE Lossless transfer syntax is not decoded from its stored bytes, or None"""
+    bits, samples = int(getattr(ds, "BitsAllocated", 0) or 0), int(getattr(ds, "SamplesPerPixel", 0) or 0)
+    if bits != 8:
+        return f"RLE Lossless pixel data with BitsAllocated = {bits}: only 8-bit samples are decoded from the stored bytes"
+    if samples not in (1, 3):
+        return f"RLE Lossless pixel data with SamplesPerPixel = {samples}: only 1 or 3 samples are decoded from the stored bytes"
+    return None
+
+
+def _is_rle(ds):
+    return str(getattr(getattr(ds, "file_meta", None), "TransferSyntaxUID", "")) == RLE_TRANSFER_SYNTAX
+
+
+def dicom_rle_frames(ds):
+    """The pixel data of an 8-bit RLE Lossless dataset as it is stored -> RleFrames; None for any other dataset (another transfer
+    syntax, samples that are not 8-bit, a sample count other than 1 or 3), which is read through its pixel_array as ever.  A pure
+    function of any dataset-like object: reads file_meta.TransferSyntaxUID, PixelData, Rows, Columns, SamplesPerPixel, NumberOfFrames
+    (1 where absent), BitsAllocated and PhotometricInterpretation; frames.encapsulated_frames cuts PixelData into frames.  No pydicom."""
+    if not _is_rle(ds) or _rle_refusal(ds) is not None:
+        return None
+    N, H, W = int(getattr(ds, "NumberOfFrames", 1) or 1), int(ds.Rows), int(ds.Columns)
+    blob, off, ln = rle_record(encapsulated_frames(ds.PixelData, N))
+    return RleFrames(blob, off, ln, (N, H, W), int(ds.SamplesPerPixel), str(getattr(ds, "PhotometricInterpretation", "")) or None)
+
+
+def _rle_form(rle, photometric):
+    """_stored_form for RLE frames: the device form of their planes under `photometric` (None: by the sample count), or None with the reason"""
+    if photometric is None:
+        photometric = "MONOCHROME2" if rle.samples == 1 else "RGB"
+    form = PHOTOMETRIC_FORMS.get(str(photometric))
+    if form is None:
+        return None, f"PhotometricInterpretation {photometric!r} has no device form"
+    if rle.samples != (1 if form == "GRAY" else 3):
+        return None, f"PhotometricInterpretation {photometric!r} with {rle.samples} samples a pixel"
+    if form == "GRAY" and rle.shape[0] < 2:
+        return None, "a grey stack of one frame stays grey (reference :533-536)"
+    return form, None
+
+
+_rle_fallbacks = set()              # reasons already logged
+
+
+def _rle_fallback(reason):
+    if reason not in _rle_fallbacks:
+        _rle_fallbacks.add(reason)
+        logger.warning(f"RLE Lossless pixel data not decoded on the device, the host decodes it instead: {reason}")
+
+
 class _DeviceFrames:
     """A study's frames held on the flow model's device (frames="device"): the token every device call takes, and the RGB for what
-    still runs on the host, downloaded once."""
+    still runs on the host, downloaded once.  `stored`: the pixel data as an array, or as RleFrames (the device decodes them)."""
 
     def __init__(self, model, stored, form, flip):
-        self.model, self.token, self._rgb = model, model.hold_frames(stored, form, flip=flip), None
+        if isinstance(stored, RleFrames):
+            token = model.hold_frames_rle(stored.record, stored.shape[1], stored.shape[2], stored.samples, form, flip=flip)
+        else:
+            token = model.hold_frames(stored, form, flip=flip)
+        self.model, self.token, self._rgb = model, token, None
 
     def host(self):
         if self._rgb is None:
@@ -411,7 +495,10 @@ def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode=
     there: Otsu masks and the segmentor's glue where the model offers them, every study call.  What runs on the host -- a host
     segmentor, host Otsu, an `echo` the writer makes -- gets the RGB by one download.  YBR_FULL and YBR_FULL_422 convert as
     frames.ybr_full_to_rgb (parity with pydicom's converter is unpinned); any other interpretation, pixel data that is not uint8, or a
-    model without hold_frames takes the host path with one logged reason per walk.  The file is the one frames="host" writes."""
+    model without hold_frames takes the host path with one logged reason per walk.  The file is the one frames="host" writes.
+    8-bit RLE Lossless pixel data (read_study_stored gives it as RleFrames, taken before ds.pixel_array is touched; an .npz study may
+    carry it in `nparr`'s place) is held from its compressed bytes (DenseFlow.hold_frames_rle: the device decodes it); a model without
+    hold_frames_rle gets what frames.rle_decode_frame decodes, with one logged reason per walk, and frames="host" decodes it likewise."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
@@ -449,7 +536,11 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             metadata = md_file
         patient_id = patient_id or pid_file
         heart_rate = heart_rate or hr_file
-    nparr = np.asarray(nparr)
+    rle = nparr if isinstance(nparr, RleFrames) else None   # RLE Lossless pixel data as stored: decoded on the device below, or here
+    if rle is not None and frames == "host":
+        nparr, rle = rle.decode(), None
+    if rle is None:
+        nparr = np.asarray(nparr)
     if metadata is None:
         metadata = {"pixel_spacing": None, "frame_rate": None, "R_wave_data_present": False, "R_times": None}
     if frames == "host":
@@ -468,7 +559,17 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     walk = _defer_save is not None                # process_folder: the writer stage takes the study
     held = None                                   # frames="device": the study's frames on the model's device
     try:
-        if frames == "device":
+        if rle is not None:                       # (frames="device")
+            form, why = _rle_form(rle, _photometric)
+            if why is None and not hasattr(model, "hold_frames_rle"):
+                why = f"the flow model ({type(model).__name__}) has no hold_frames_rle"
+            if why is None:
+                held = _DeviceFrames(model, rle, form, flipLR)
+                nparr = held.token
+            else:                                 # the twin decodes; what it gives goes the way of any stored array, below
+                _rle_fallback(why)
+                nparr = rle.decode()
+        if frames == "device" and held is None:
             form, why = _stored_form(nparr, _photometric)
             if why is None and not hasattr(model, "hold_frames"):
                 why = f"the flow model ({type(model).__name__}) has no hold_frames"
@@ -551,13 +652,17 @@ def read_study(path):
     reference's _read_dicom_file failure, :520-522); `.npy` (uint8 [N,H,W] or [N,H,W,3]) and `.npz` (key `nparr`, optional
     `pixel_spacing`, `frame_rate`, `patient_id`, `heart_rate`, `photometric`) are the injection formats of the offline image.
     `photometric` (RGB, YBR_FULL, YBR_FULL_422, MONOCHROME2; without it the frames are RGB or grey, as ever) says how `nparr` is stored:
-    YBR data is converted here as frames.ybr_full_to_rgb converts it, in pydicom's place."""
+    YBR data is converted here as frames.ybr_full_to_rgb converts it, in pydicom's place.  In `nparr`'s place an .npz may carry RLE
+    Lossless pixel data as stored -- `rle_blob`, `rle_off`, `rle_len`, `rows`, `cols`, `samples` (_npz_stored) -- which is decoded here
+    by frames.rle_decode_frame, in pydicom's place likewise."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".npy":
         return np.load(path, allow_pickle=False), None, "", 0
     if ext == ".npz":
         z = np.load(path, allow_pickle=False)
-        arr, photometric = z["nparr"], _npz_photometric(z, path)
+        arr, photometric = _npz_stored(z, path), _npz_photometric(z, path)
+        if isinstance(arr, RleFrames):                                    # (the offline stand-in for pydicom's RLE handler: the twin)
+            arr = arr.decode()
         if photometric in ("YBR_FULL", "YBR_FULL_422"):                   # (the offline stand-in for pydicom's converter: the twin)
             arr = ybr_full_to_rgb(arr)
         return (arr,) + _npz_study(z)
@@ -572,6 +677,22 @@ def _npz_study(z):
     return md, str(z["patient_id"]) if "patient_id" in z else "", int(z["heart_rate"]) if "heart_rate" in z else 0
 
 
+def _npz_stored(z, path):
+    """The pixel data of an .npz study as it is stored: `nparr`, or, in its place, RLE Lossless frames under `rle_blob`, `rle_off`,
+    `rle_len` (frames.rle_record's) with `rows`, `cols` and `samples` -> RleFrames"""
+    if "rle_blob" not in z:
+        return z["nparr"]
+    try:
+        blob, off, ln = np.ascontiguousarray(z["rle_blob"], np.uint8), np.ascontiguousarray(z["rle_off"], np.uint64), np.ascontiguousarray(z["rle_len"], np.uint32)
+        H, W, samples = int(z["rows"]), int(z["cols"]), int(z["samples"])
+    except KeyError as e:
+        raise DICOMReadError(f"Failed to read {path}: an RLE study needs rle_blob, rle_off, rle_len, rows, cols and samples ({e} is missing)") from e
+    if (blob.ndim != 1 or off.ndim != 1 or off.shape != ln.shape or off.size < 1 or H < 1 or W < 1 or samples not in (1, 3)
+            or int((off + ln.astype(np.uint64)).max()) > blob.size):
+        raise DICOMReadError(f"Failed to read {path}: rle_off / rle_len do not describe frames of {H} x {W} x {samples} inside rle_blob's {blob.size} bytes")
+    return RleFrames(blob, off, ln, (int(off.size), H, W), samples)
+
+
 def _npz_photometric(z, path):
     """The optional `photometric` key of an .npz study: how `nparr` is stored (None: as RGB or grey frames, as ever)."""
     if "photometric" not in z:
@@ -582,14 +703,32 @@ def _npz_photometric(z, path):
     return photometric
 
 
-def _read_dicom(path):
+def _stored_rle(ds, path):
+    """An RLE Lossless dataset's pixel data as RleFrames, cut from PixelData before pixel_array is touched; None for any other dataset,
+    and -- with one logged reason -- for RLE data the stored bytes are not decoded from (samples that are not 8-bit)"""
+    if not _is_rle(ds):
+        return None
+    why = _rle_refusal(ds)
+    if why is not None:
+        _rle_fallback(why)
+        return None
+    try:
+        return dicom_rle_frames(ds)
+    except ValueError as e:
+        raise DICOMReadError(f"Failed to read DICOM file: {path} ({e})") from e
+
+
+def _read_dicom(path, stored=False):
+    """`stored` (read_study_stored): the pixel data as the file stores it where that has a device form (_stored_rle)"""
     try:
         import pydicom
     except ImportError as e:
         raise DICOMReadError(f"Failed to read DICOM file: {path} (pydicom is not installed)") from e
     try:
         ds = pydicom.dcmread(path)
-        arr = ds.pixel_array
+        arr = _stored_rle(ds, path) if stored else None
+        if arr is None:
+            arr = ds.pixel_array
     except (IOError, OSError, KeyError, AttributeError) as e:             # reference _read_dicom_file (:307-312) -> DICOMReadError (:521-522)
         raise DICOMReadError(f"Failed to read DICOM file: {path}") from e
     return ds, arr, pydicom
@@ -599,14 +738,15 @@ def read_study_stored(path):
     """read_study without the colour-space step: (pixel data as the file stores it, its PhotometricInterpretation or None, metadata,
     patient id, heart rate), for frames="device".  The interpretation is named only where the data is to be converted: pydicom's own
     should_change_PhotometricInterpretation_to_RGB(ds) decides that for a DICOM file, the `photometric` key for an .npz; None means RGB
-    or grey frames by their shape."""
+    or grey frames by their shape.  8-bit RLE Lossless pixel data -- a DICOM file in that transfer syntax (dicom_rle_frames, taken
+    before ds.pixel_array is touched), an .npz with `rle_blob` & co. -- comes as RleFrames, not decoded."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".npy":
         return np.load(path, allow_pickle=False), None, None, "", 0
     if ext == ".npz":
         z = np.load(path, allow_pickle=False)
-        return (z["nparr"], _npz_photometric(z, path)) + _npz_study(z)
-    ds, arr, pydicom = _read_dicom(path)
+        return (_npz_stored(z, path), _npz_photometric(z, path)) + _npz_study(z)
+    ds, arr, pydicom = _read_dicom(path, stored=True)
     convert = pydicom.pixel_data_handlers.numpy_handler.should_change_PhotometricInterpretation_to_RGB(ds)
     _, md, pid, hr = dicom_to_study(ds, arr)
     return arr, str(ds.PhotometricInterpretation) if convert else None, md, pid, hr
@@ -753,7 +893,10 @@ def _prepare_study_shm(reader, path, mode, flipLR, config, want_echo, otsu_ahead
                                                                                  *(("device",) if frames == "device" else ()))
     made = []
     try:
-        nparr = _shm_put(nparr); made.append(nparr)
+        if isinstance(nparr, RleFrames):                      # the blob travels as one uint8 array; the small tables go pickled
+            nparr = replace(nparr, blob=_shm_put(nparr.blob)); made.append(nparr.blob)
+        else:
+            nparr = _shm_put(nparr); made.append(nparr)
         if masks_ahead is not None:
             packed = {}
             for k, v in masks_ahead.items():
@@ -956,6 +1099,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     _check_chain(chain, flow_model, OF_algo)
     _check_frames(frames)
     _frames_fallbacks.clear()                                       # one logged reason per walk
+    _rle_fallbacks.clear()
     if deflate == "device":
         _deflate_fallbacks.clear()                                  # one logged reason per walk
         if studies_in_flight > 1:
@@ -1012,10 +1156,11 @@ class _Study:
     def take(self, prepared, mapped):
         """Unpack what _prepare_study / _prepare_study_shm returned (nothing else knows its layout); `mapped`: and map its blocks."""
         nparr, self.md, self.pid, self.hr, masks, echo, self.photometric = tuple(prepared) + (None,) * (7 - len(prepared))
-        self.descs = [d for d in [nparr, echo] + list((masks or {}).values()) if _is_shm(d)]
+        rle = isinstance(nparr, RleFrames)                    # (its blob is the array that travels)
+        self.descs = [d for d in [nparr.blob if rle else nparr, echo] + list((masks or {}).values()) if _is_shm(d)]
         if mapped:
             self.echo_desc, self.mask_descs = echo, masks if masks is not None and any(_is_shm(v) for v in masks.values()) else None
-            nparr = _shm_get(nparr, self.blocks)
+            nparr = replace(nparr, blob=_shm_get(nparr.blob, self.blocks)) if rle else _shm_get(nparr, self.blocks)
             if masks is not None:
                 masks = {k: _shm_get(v, self.blocks) for k, v in masks.items()}
             echo = _shm_get(echo, self.blocks)

@@ -703,7 +703,8 @@ int tf_hold_mask_chunks(tf_handle* h, int slot, const tf_chunked* mask);
  * Every argument is checked before any GPU work.  Host-synchronous, on the handle's stream, like the tail calls.  Device scratch: about
  *   12 bytes per input byte plus 192 KiB per chunk, in batches of chunks that keep it under 256 MiB, plus the blob and an uploaded array.
  * tf_dbg_counter(h, "deflate_match_us" / "deflate_emit_us" / "chunk_kernel_us"): device time of the links and the match search, of the
- *   parse, trees, bits and compaction, and of the gather into chunks, since the handle was made (HIP events). */
+ *   parse, trees, bits and compaction, and of the gather into chunks, since the handle was made (HIP events).
+ * tf_dbg_counter(h, "deflate_batches"): the batches of chunks the three calls have worked through since the handle was made. */
 enum { TF_HELD_FLOW = 0, TF_HELD_ECHO = 1, TF_HELD_MASK = 2 };
 int tf_deflate(tf_handle* h, const uint8_t* chunks, int n, uint32_t chunk_bytes, uint8_t* blob, uint64_t blob_cap, uint64_t* off, uint32_t* len, int* status);
 int tf_deflate_array(tf_handle* h, const void* array, int ndim, const int64_t* shape, const int64_t* chunk, int elem_bytes, int n, uint8_t* blob,

@@ -238,6 +238,7 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "deflate_match_us") v = (long long)(h->deflate_match_ms * 1000.0);
     else if (n == "deflate_emit_us") v = (long long)(h->deflate_emit_ms * 1000.0);
     else if (n == "chunk_kernel_us") v = (long long)(h->chunk_kernel_ms * 1000.0);
+    else if (n == "deflate_batches") v = h->deflate_batches;
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;

@@ -89,6 +89,7 @@ int deflate_run(tf_handle* h, const char* who, const DeflateJob& j)
     for (int d = 0; d < 4; ++d) { dims.shape[d] = j.shape[d]; dims.chunk[d] = j.chunk[d]; }
     for (size_t c0 = 0; c0 < n; c0 += P) {
         const unsigned m = (unsigned)std::min(P, n - c0);
+        ++h->deflate_batches;
         HIPC(h, hipEventRecord(h->ev[3], h->stream));
         if (j.array) {
             const size_t elems = cb / (size_t)j.elem_bytes;

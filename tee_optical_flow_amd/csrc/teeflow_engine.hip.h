@@ -210,6 +210,7 @@ struct tf_handle : Engine {
     double wase_kernel_ms = 0;   // device time of the last WASE study call's reduction and output kernels (the same events)
     double inflate_kernel_ms = 0, unchunk_kernel_ms = 0;   // device time of k_inflate / k_unchunk since the handle was made (the same events)
     double deflate_match_ms = 0, deflate_emit_ms = 0, chunk_kernel_ms = 0;   // ... of deflate's links + search, emit + offsets + pack, and k_chunk
+    long long deflate_batches = 0;                                           // passes of deflate_run's batch loop since the handle was made
     // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
     // ([0]: upload done) and the device scratch ([1]: kernel done) of the last call may be written again
     void* seg_stage = nullptr; size_t seg_stage_cap = 0; hipEvent_t seg_ev[2] = {};

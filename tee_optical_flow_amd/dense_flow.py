@@ -289,7 +289,8 @@ class DenseFlow:
         saliency_kernel_us, wase_study_kernel_us (device time of the last WASE study call's reduction and output kernels),
         inflate_kernel_us, unchunk_kernel_us (device time of k_inflate / k_unchunk since the engine was made),
         deflate_match_us, deflate_emit_us, chunk_kernel_us (device time of deflate's links and match search, of its parse, trees, bits and
-        compaction, and of k_chunk, since the engine was made), study_download_bytes (bytes of flow and echo the study calls have
+        compaction, and of k_chunk, since the engine was made), deflate_batches (the batches of chunks deflate has worked through),
+        study_download_bytes (bytes of flow and echo the study calls have
         copied to the host; calc_study_held and study_chunks add nothing), tail_upload_bytes."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 

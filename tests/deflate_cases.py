@@ -22,15 +22,25 @@ cases() -> [Case(name, raw)], built once.  The families of tests/inflate_cases.p
   fibdist, fibdist-bl         six-byte matches at chosen distances, so that one block's distance codes have frequencies in Fibonacci
                               proportion: in `fibdist` (17 codes, ratio 1.65) the distance tree's unbounded depth is 16, past its
                               limit of 15, and is repaired; in `fibdist-bl` (16 codes) the code-length tree's passes 7 (the corpus'
-                              test computes both depths from the decoded frequencies).  The repair is one routine for all three
-                              trees; the literal/length tree's own overflow is NOT in the corpus.  A block has at most 16,383
-                              symbols; literals that skewed repeat their three-byte strings and turn into matches, and length codes
-                              in exact Fibonacci proportion (built like fibdist) share the tree with the literals that separate the
-                              matches, which flatten it: every input tried ended at depth 14 or less.
+                              test computes both depths from the decoded frequencies).
+  lloverflow-16, -17          the same for the literal/length tree, so that the repair, one routine, is run for all three trees.
+                              32,766 random bytes (two full blocks of literals end where they end), then a last block of matches
+                              alone: pieces copied from 300 to 30,000 back whose lengths are the first of length codes 258, 259, ..
+                              (4, 5, .. 51; not 3, which zlib drops when it lies more than 4,096 back), code i of 17 or 18 taken
+                              round(1.65 ** (codes - 1 - i)) times, shuffled.  A source is drawn again while the piece before it,
+                              with the source's first byte, occurs in the window: that match would grow by a byte and leave a rest
+                              of literals, which flatten the tree.  The block's unbounded depth is 16 and 17, its deepest code 15.
+  collide-N                   bytes (r << 5) | s, r uniform in 0..7 and s one of 2 (N = 4,099) or 3 (73,728) values: hash3 drops the
+                              first byte's top three bits, so every three-byte string shares its hash with seven others, matches
+                              abound, and the 64 positions that the device links in one step hold different strings of one hash
   prefix-slide-N              16,000 random bytes, then a mask to N bytes: the second block begins below 32,768 and is flushed behind
                               the window's slide, when zlib holds no pointer to its first byte any more and cannot store it.  (Its
                               stored form cannot also be the shortest: a block of at most 16,383 symbols over more than 32,507 bytes
                               has matches for more than half of them.  The stored blocks of `random` begin behind the slide.)
+
+sweep(size) -> 1,500 seeded chunks of one size, drawn in turn from seven families (SWEEP_FAMILIES): the randomized comparison with
+zlib, at 61, 512 and 4,000 bytes (SWEEP_SIZES).  Their yardstick is one SHA-256 per size over zlib's streams end to end, under
+"sweeps" in the digests' file; first_difference() names the chunk where a compressor leaves zlib.
 """
 import functools
 import hashlib
@@ -103,6 +113,7 @@ def _slide0(n, p):
     return bytes(raw)
 
 
+@functools.lru_cache(maxsize=None)
 def _fibdist(n_codes, first, ratio):
     """32 KiB of random bytes, then pieces of six bytes copied from P back and one byte that differs from the one P back; P is the
     second distance of distance code first + i, taken round(ratio ** i) times (ratio None: the Fibonacci numbers), in shuffled order"""
@@ -123,8 +134,123 @@ def _fibdist(n_codes, first, ratio):
     return bytes(out)
 
 
+LENGTH_FIRST = [4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51]      # the first length of length codes 258, 259, ..
+
+
+@functools.lru_cache(maxsize=None)
+def _lloverflow(n_codes, ratio):
+    """32,766 random bytes, then pieces of LENGTH_FIRST[i] bytes, i < n_codes, copied from 300 + the length to 30,000 back; length i
+    is taken round(ratio ** (n_codes - 1 - i)) times, in shuffled order.  No piece lets the match before it grow: a source whose first
+    byte, behind the piece before, makes a string the window holds is drawn again."""
+    rng = _rng(19, n_codes)
+    out = bytearray(rng.integers(0, 256, 32766, dtype=np.uint8).tobytes())
+    counts = [int(round(ratio ** (n_codes - 1 - i))) for i in range(n_codes)]
+    pieces = np.repeat(np.array(LENGTH_FIRST[:n_codes]), counts)
+    pieces = pieces[rng.permutation(len(pieces))]
+    prev = None
+    for n in pieces.tolist():
+        while True:
+            src = len(out) - int(rng.integers(n + 300, 30000))
+            if prev is None or out.find(prev + out[src:src + 1], len(out) - 32768) < 0:
+                break
+        prev = bytes(out[src:src + n])
+        out += prev
+    return bytes(out)
+
+
+COLLIDE = {4099: 2, 73728: 3}                           # size: how many values the low five bits take
+
+
+def _collide(rng, n, k):
+    low = rng.choice(32, k, replace=False)
+    return ((rng.integers(0, 8, n) << 5) | low[rng.integers(0, k, n)]).astype(np.uint8).tobytes()
+
+
+def hash3(b, p=0):
+    """zlib's hash of the three bytes at p, as csrc/teeflow_deflate_core.h has it"""
+    return ((b[p] << 10) ^ (b[p + 1] << 5) ^ b[p + 2]) & 32767
+
+
+def colliding_steps(raw):
+    """how many of the 64-position steps of k_deflate_links hold two different three-byte strings of one hash"""
+    found = 0
+    for base in range(0, len(raw) - 2, 64):
+        seen, hit = {}, False
+        for p in range(base, min(base + 64, len(raw) - 2)):
+            hit = hit or seen.setdefault(hash3(raw, p), raw[p:p + 3]) != raw[p:p + 3]
+        found += hit
+    return found
+
+
 def _prefix_slide(n):
     return _random(16000, 13) + FAMILIES["mask"](_rng(13, n), n - 16000)
+
+
+# ---- the sweep: many small seeded inputs, where a byte can differ silently (the run-length corners of the trees' own coding, ties
+# between a stored, a fixed and a dynamic block, the lazy parse on short inputs)
+SWEEP_SIZES, SWEEP_COUNT = [61, 512, 4000], 1500
+
+
+def _sw_geometric(rng, n):
+    k = int(rng.integers(2, 41))
+    return rng.permutation(256)[np.minimum(rng.geometric(rng.uniform(0.05, 0.7), n) - 1, k - 1)]
+
+
+def _sw_runs(rng, n):
+    values = rng.integers(0, 256, int(rng.integers(1, 9)))
+    runs = rng.geometric(1.0 / rng.uniform(1.5, 150.0), n)
+    return np.repeat(values[rng.integers(0, len(values), n)], runs)[:n]
+
+
+def _sw_uniform(rng, n):
+    return rng.permutation(256)[rng.integers(0, int(rng.integers(1, 257)), n)]
+
+
+def _sw_f16(rng, n):
+    v = (rng.standard_normal(n // 2 + 1) * 10.0 ** rng.uniform(-3, 3)).astype(np.float16)
+    return np.frombuffer(v.tobytes(), np.uint8)[:n]
+
+
+def _sw_mask(rng, n):
+    runs = rng.geometric(1.0 / rng.uniform(2.0, 400.0), n)
+    return np.repeat((np.arange(n) + int(rng.integers(0, 2))) & 1, runs)[:n]
+
+
+def _sw_collide(rng, n):
+    return np.frombuffer(_collide(rng, n, int(rng.integers(2, 4))), np.uint8)
+
+
+def _sw_phrases(rng, n):
+    words = [rng.integers(0, 256, int(rng.integers(3, 21))) for _ in range(int(rng.integers(2, 17)))]
+    return np.concatenate([words[i] for i in rng.integers(0, len(words), n // 3 + 1)])[:n]
+
+
+SWEEP_FAMILIES = [_sw_geometric, _sw_runs, _sw_uniform, _sw_f16, _sw_mask, _sw_collide, _sw_phrases]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep(size, count=SWEEP_COUNT):
+    """`count` chunks of `size` bytes: chunk i is of family i % 7, seeded by the size and i alone"""
+    out = []
+    for i in range(count):
+        raw = np.asarray(SWEEP_FAMILIES[i % len(SWEEP_FAMILIES)](_rng(31, size, i), size)).astype(np.uint8).tobytes()
+        assert len(raw) == size
+        out.append(raw)
+    return tuple(out)
+
+
+def sweep_digest(streams):
+    """[length, sha256] of a sweep's streams end to end"""
+    return digest(b"".join(streams))
+
+
+def first_difference(chunks, streams):
+    """of the first chunk whose stream is not the running zlib's: (index, its family, the stream's length, zlib's length), or None"""
+    for i, (c, s) in enumerate(zip(chunks, streams)):
+        z = zlib.compress(c, 9)
+        if bytes(s) != z:
+            return i, SWEEP_FAMILIES[i % len(SWEEP_FAMILIES)].__name__, len(s), len(z)
+    return None
 
 
 @functools.lru_cache(maxsize=None)
@@ -151,10 +277,17 @@ def cases():
         out.append(Case(f"dist-{d}", _dist(d)))
     for n, p in SLIDE0:
         out.append(Case(f"slide0-{n}-{p}", _slide0(n, p)))
-    out.append(Case("fibdist", _fibdist(17, 13, 1.65)))
-    out.append(Case("fibdist-bl", _fibdist(16, 14, None)))
+    out += deep()
+    for n, k in COLLIDE.items():
+        out.append(Case(f"collide-{n}", _collide(_rng(23, n), n, k)))
     assert len({c.name for c in out}) == len(out)
     return tuple(out)
+
+
+def deep():
+    """the cases whose trees pass their depth limit: zlib's streams of them hold codes of 15 bits, the inflate corpus takes them too"""
+    return [Case("fibdist", _fibdist(17, 13, 1.65)), Case("fibdist-bl", _fibdist(16, 14, None)),
+            Case("lloverflow-16", _lloverflow(17, 1.65)), Case("lloverflow-17", _lloverflow(18, 1.65))]
 
 
 def digest(stream):
@@ -166,6 +299,13 @@ def digests():
     """{name: [length, sha256]} of zlib 1.2.11's level-9 stream of every case, as recorded"""
     with open(DIGESTS) as f:
         return json.load(f)["cases"]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_digests():
+    """{size: [length, sha256]} of zlib 1.2.11's level-9 streams of sweep(size), end to end, as recorded"""
+    with open(DIGESTS) as f:
+        return {int(k): v for k, v in json.load(f)["sweeps"].items()}
 
 
 def huffman_depth(freqs):
@@ -181,10 +321,12 @@ def huffman_depth(freqs):
 
 
 def blocks(stream):
-    """[(type, symbols, bytes, lf, df, cf)] of a zlib stream's blocks: 0 stored (symbols: its bytes), 1 fixed, 2 dynamic (symbols without the
-    end-of-block; bytes: what they decode to; lf, df, cf: how often each literal/length, distance and code-length symbol occurs;
-    None for a stored block, cf None for a fixed one), and the deepest literal/length and code-length code of its dynamic blocks.  A plain decoder after RFC 1951, for the corpus' own test."""
-    bits, at, out, deep = int.from_bytes(stream, "little") >> 16, 0, [], [0, 0]
+    """[(type, symbols, bytes, lf, df, cf, depths)] of a zlib stream's blocks: 0 stored (symbols: its bytes), 1 fixed, 2 dynamic (symbols
+    without the end-of-block; bytes: what they decode to; lf, df, cf: how often each literal/length, distance and code-length symbol
+    occurs; None for a stored block, cf None for a fixed one; depths: the block's longest literal/length and distance code, None for
+    a stored block), and the deepest literal/length, code-length and distance code of its dynamic blocks.  A plain decoder after
+    RFC 1951, for the corpus' own test."""
+    bits, at, out, deep = int.from_bytes(stream, "little") >> 16, 0, [], [0, 0, 0]
 
     def take(n):
         nonlocal at
@@ -222,9 +364,9 @@ def blocks(stream):
             n = take(16)
             take(16)
             at += 8 * n
-            out.append((0, n, n, None, None, None))
+            out.append((0, n, n, None, None, None, None))
         else:
-            cf = None
+            cf, depths = None, (9, 5)
             if kind == 1:
                 lt, dt = fixed
             else:
@@ -243,7 +385,8 @@ def blocks(stream):
                     else:
                         lens += [0] * (3 + take(3) if s == 17 else 11 + take(7))
                 lt, dt = table(lens[:nl]), table(lens[nl:])
-                deep = [max(deep[0], max(lens[:nl])), max(deep[1], max(cl))]
+                depths = (max(lens[:nl]), max(lens[nl:]))
+                deep = [max(deep[0], depths[0]), max(deep[1], max(cl)), max(deep[2], depths[1])]
             n = made = 0
             lf, df = [0] * 286, [0] * 30
             lf[256] = 1
@@ -261,6 +404,6 @@ def blocks(stream):
                     d = sym(dt)
                     df[d] += 1
                     take(0 if d < 4 else (d >> 1) - 1)
-            out.append((kind, n, made, lf, df, cf))
+            out.append((kind, n, made, lf, df, cf, depths))
         if last:
             return out, deep

@@ -2,7 +2,8 @@
 zlib streams made with the standard library's zlib alone, from seeded data, and malformed ones.  What is expected of a stream is what
 zlib.decompressobj().decompress does with it here, never an assumption: see verdict().
 
-cases() -> [Case(name, stream, out_bytes)], built once.  verdict(case) -> (kind, out):
+cases() -> [Case(name, stream, out_bytes)], built once; among the good ones zlib's level-9 streams of the deflate corpus' cases whose
+trees pass their depth limit (tests/deflate_cases.deep), the only ones with codes of 14 and 15 bits.  verdict(case) -> (kind, out):
   GOOD   zlib decodes the stream to its end and gives out_bytes bytes: the status must be 0 and the output those bytes
   BAD    zlib raises: the status must not be 0; `out` is what zlib had decoded before it raised (the stream fed byte by byte), and
          what the decoder wrote into its slot must be a prefix of that
@@ -180,6 +181,9 @@ def cases():
     raw = data("f16noise", 32769)
     out.append(Case("flushes", deflate(raw, 6, flushes=((1000, zlib.Z_SYNC_FLUSH), (1000, zlib.Z_SYNC_FLUSH), (20000, zlib.Z_FULL_FLUSH))), len(raw)))
     out.append(Case("flushes-at-start", deflate(raw[:300], 9, flushes=((0, zlib.Z_SYNC_FLUSH), (0, zlib.Z_FULL_FLUSH))), 300))
+    from tests import deflate_cases as DC                 # (it imports this module: hence here)
+    for name, raw in DC.deep():                           # codes of 15 bits, literal/length and distance: behind the one-step tables
+        out.append(Case(f"{name}-L9", deflate(raw, 9), len(raw)))
     out += _malformed()
     assert len({c.name for c in out}) == len(out)
     return tuple(out)

@@ -1,6 +1,6 @@
 """Deflate without a GPU: the recorded digests against the running zlib, the corpus against what it claims to hold, the compressor's
 core (csrc/teeflow_deflate_core.h, the text the device kernels run) in a stand-alone program built with the address and
-undefined-behaviour sanitizers over the whole corpus of tests/deflate_cases.py, the chunk bookkeeping and the writer's deflater hook
+undefined-behaviour sanitizers over the whole corpus of tests/deflate_cases.py and its sweeps, the chunk bookkeeping and the writer's deflater hook
 on a zlib-backed engine, and the refusals that need no device."""
 import json
 import os
@@ -25,6 +25,10 @@ def test_the_running_zlib_reproduces_the_recorded_digests():
     assert sorted(want) == sorted(c.name for c in DC.cases())
     wrong = [c.name for c in DC.cases() if DC.digest(zlib.compress(c.raw, 9)) != want[c.name]]
     assert not wrong, (zlib.ZLIB_RUNTIME_VERSION, wrong[:10])
+    assert sorted(DC.sweep_digests()) == DC.SWEEP_SIZES
+    for n in DC.SWEEP_SIZES:
+        assert len(DC.sweep(n)) == DC.SWEEP_COUNT and {len(c) for c in DC.sweep(n)} == {n}
+        assert DC.sweep_digest([zlib.compress(c, 9) for c in DC.sweep(n)]) == DC.sweep_digests()[n], (zlib.ZLIB_RUNTIME_VERSION, n)
 
 
 def test_corpus_has_every_case_the_compressor_must_meet():
@@ -39,8 +43,8 @@ def test_corpus_has_every_case_the_compressor_must_meet():
     def z(name):
         return zlib.compress(by[name], 9)
     kinds = {name: DC.blocks(z(name)) for name in ("zeros-0", "tiny-19", "tiny-99", "random-259", "f16noise-32505", "counter-16396", "counter-16397",
-                                                   "counter-16398", "counter-16399", "counter-40000", "fibdist", "fibdist-bl", "prefix-slide-73728",
-                                                   "random-140000")}
+                                                   "counter-16398", "counter-16399", "counter-40000", "fibdist", "fibdist-bl", "lloverflow-16",
+                                                   "lloverflow-17", "prefix-slide-73728", "random-140000")}
     for name, (bl, _) in kinds.items():
         assert sum(b[2] for b in bl) == len(by[name]), name
     ks = {name: [b[:2] for b in bl] for name, (bl, _) in kinds.items()}
@@ -60,6 +64,18 @@ def test_corpus_has_every_case_the_compressor_must_meet():
     assert DC.huffman_depth(last[4]) > 15
     last = kinds["fibdist-bl"][0][-1]
     assert DC.huffman_depth(last[5]) > 7 and kinds["fibdist-bl"][1][1] == 7
+    # ... the literal/length tree's: a last block of matches alone, short of a full one, whose deepest code has the limit's 15 bits
+    for name, depth in (("lloverflow-16", 16), ("lloverflow-17", 17)):
+        last = kinds[name][0][-1]
+        assert last[0] == 2 and DC.huffman_depth(last[3]) >= depth and last[6][0] == 15 and last[1] < 16383, (name, DC.huffman_depth(last[3]), last[6], last[1])
+        assert sum(last[3][:256]) == 0 and [b[0] for b in kinds[name][0][:-1]].count(1) == 0, name
+    # different three-byte strings of one hash inside the 64 positions that the device links in one step, in nearly every step
+    for n in DC.COLLIDE:
+        raw = by[f"collide-{n}"]
+        assert len(raw) == n and len({b & 31 for b in raw}) == DC.COLLIDE[n] and len({b >> 5 for b in raw}) == 8
+        assert DC.colliding_steps(raw) >= 1 and DC.colliding_steps(raw) > n // 64 // 2, (n, DC.colliding_steps(raw))
+        assert len(zlib.compress(raw, 9)) < 0.7 * n                                                             # real matches
+    assert DC.colliding_steps(by["seven-73728"]) == 0 == DC.colliding_steps(by["slide0-65400-65274"])         # what the corpus had
     # the window's first position as a chain's head: not a match where the input ends behind it, a match where it goes on
     for n, p in DC.SLIDE0:
         raw = by[f"slide0-{n}-{p}"]
@@ -79,7 +95,10 @@ def test_core_reproduces_zlib_over_the_corpus_under_the_sanitizers(tmp_path):
                            "-static-libubsan", "-std=c++17", "-Wall", "-Wextra", "-Werror",
                            "-I", os.path.join(ROOT, "tee_optical_flow_amd", "csrc"),
                            os.path.join(ROOT, "tests", "csrc", "verify_deflate.cpp"), "-o", str(exe)])
-    cs, want = DC.cases(), DC.digests()
+    corpus, want = DC.cases(), DC.digests()
+    # the corpus, then the sweeps' chunks, which are judged by their size's one digest
+    cs = list(corpus) + [DC.Case((n, i), c) for n in DC.SWEEP_SIZES for i, c in enumerate(DC.sweep(n))]
+    swept = {n: [None] * DC.SWEEP_COUNT for n in DC.SWEEP_SIZES}
     # the search walks up to 4,096 candidates for every byte: the corpus goes through the program in four parts side by side
     order = sorted(range(len(cs)), key=lambda i: -len(cs[i].raw))
     parts = [order[k::4] for k in range(4)]
@@ -103,10 +122,16 @@ def test_core_reproduces_zlib_over_the_corpus_under_the_sanitizers(tmp_path):
             seen += 1
             bound = len(cs[i].raw) + (len(cs[i].raw) >> 12) + (len(cs[i].raw) >> 14) + (len(cs[i].raw) >> 25) + 13
             assert status == 0 and n <= bound and clean == 1, (cs[i].name, status, n, clean)
-            if DC.digest(got) != want[cs[i].name]:
+            if i >= len(corpus):
+                swept[cs[i].name[0]][cs[i].name[1]] = got
+            elif DC.digest(got) != want[cs[i].name]:
                 wrong.append((cs[i].name, n, want[cs[i].name][0]))
         assert at == len(buf)
     assert seen == len(cs) and not wrong, (len(wrong), wrong[:10])
+    for n, streams in swept.items():
+        if DC.sweep_digest(streams) != DC.sweep_digests()[n]:
+            wrong.append((n, DC.first_difference(DC.sweep(n), streams)))
+    assert not wrong, f"sweeps (size, (first differing chunk, its family, bytes made, zlib's bytes)): {wrong}"
 
 
 # ---- 3. chunk bookkeeping and the writer's hook, on a zlib-backed engine ---------------------------------------------------------------

@@ -2,7 +2,9 @@
 level 9, byte for byte: the whole corpus of tests/deflate_cases.py against the recorded digests of zlib's streams (which
 tests/test_deflate_cpu.py holds the running zlib to), the chunking of arrays against tests/inflate_cases.chunked, the round trip
 through the device's own inflate, the held study's arrays read where they are, and every refusal.  A call has one chunk size, so the
-corpus goes up grouped by size."""
+corpus goes up grouped by size.  Calls of more chunks than one batch of the scratch holds ("deflate_batches" counts the batches), and
+the corpus' sweeps of 1,500 seeded chunks against their recorded digests."""
+import time
 import zlib
 
 import numpy as np
@@ -53,8 +55,12 @@ def test_the_whole_corpus_against_zlibs_digests(eng):
     assert eng.counter("deflate_match_us") > c0[0] and eng.counter("deflate_emit_us") > c0[1]
 
 
+# (the last four: chunks of more than 2,048 elements, where k_chunk's grid has a second row and a thread's stride is rows x 256:
+# 16,384 elements, ragged in three dimensions; 6,000 and 4,224; 180,000, where the grid stays at its 64 rows)
 CHUNKINGS = [((5, 37, 53, 2), (2, 16, 16, 1), np.float16), ((5, 37, 53), (3, 10, 27), np.float16), ((4, 6, 8, 2), (4, 6, 8, 2), np.bool_),
-             ((3, 7), (2, 4), np.uint32), ((1000,), (333,), np.uint8)]
+             ((3, 7), (2, 4), np.uint32), ((1000,), (333,), np.uint8),
+             ((3, 70, 90, 2), (2, 64, 64, 2), np.float16), ((5, 50, 60), (2, 50, 60), np.bool_), ((3, 40, 70), (2, 33, 64), np.uint32),
+             ((4, 300, 300), (2, 300, 300), np.uint8)]
 
 
 def _array(shape, dtype):
@@ -71,12 +77,77 @@ def test_deflate_array_equals_the_chunks_zlib_makes(eng, shape, chunks, dtype):
     assert eng.counter("chunk_kernel_us") > c0
 
 
+def _running_sum(off, ln):
+    return off.dtype == np.uint64 and list(off) == list(np.concatenate([[0], np.cumsum(ln[:-1], dtype=np.uint64)]))
+
+
+def test_many_packed_chunks_go_through_several_batches(eng):
+    """3,000 chunks of 16 bytes: more than one batch of deflate_run's scratch holds (1,363 today, so three batches), which the
+    counter shows rather than the constants: the later batches read their coordinates, lengths and offsets from c0 on, carry the
+    blob's total on, and write the scratch again"""
+    t0 = time.perf_counter()
+    chunks = DC.sweep(16, 3000)
+    b0 = eng.counter("deflate_batches")
+    blob, off, ln = eng.deflate(chunks)
+    batches = eng.counter("deflate_batches") - b0
+    print(f"3000 packed chunks of 16 B: {batches} batches")
+    assert batches >= 2
+    assert ln.shape == off.shape == (3000,) and _running_sum(off, ln) and blob.size == int(ln.sum())
+    wrong = [i for i, (c, s) in enumerate(zip(chunks, _streams(blob, off, ln))) if s != zlib.compress(c, 9)]
+    assert not wrong, (len(wrong), wrong[:10])
+    print(f"3000 packed chunks of 16 B: {time.perf_counter() - t0:.2f} s")
+
+
+def test_many_array_chunks_go_through_several_batches(eng):
+    """1,960 chunks of 32 bytes of an array in host memory and of the held study: k_chunk from the batch's first coordinate on"""
+    t0 = time.perf_counter()
+    arr, chunks = _array((7, 37, 53, 2), np.float16), (1, 4, 4, 1)
+    want, _ = IC.chunked(arr, chunks, level=9)
+    assert len(want["len"]) == 1960
+    b0 = eng.counter("deflate_batches")
+    _same_record(eng.deflate_array(arr, chunks), want, "deflate_array")
+    b1 = eng.counter("deflate_batches")
+    eng.hold_study(arr)
+    up = eng.counter("tail_upload_bytes")
+    held = eng.held_deflate("flow", chunks)
+    b2 = eng.counter("deflate_batches")
+    print(f"1960 array chunks of 32 B: {b1 - b0} batches from host memory, {b2 - b1} from the held study")
+    assert eng.counter("tail_upload_bytes") == up
+    _same_record(held, want, "held_deflate")
+    assert b1 - b0 >= 2 and b2 - b1 >= 2
+    eng.release_study()
+    print(f"1960 array chunks of 32 B: {time.perf_counter() - t0:.2f} s")
+
+
+@pytest.mark.parametrize("size", DC.SWEEP_SIZES)
+def test_sweep_against_zlibs_digest(eng, size):
+    """1,500 seeded chunks of one size in one call, against the one recorded digest of zlib's streams of them"""
+    t0 = time.perf_counter()
+    chunks = DC.sweep(size)
+    b0 = eng.counter("deflate_batches")
+    blob, off, ln = eng.deflate(chunks)
+    batches = eng.counter("deflate_batches") - b0
+    print(f"sweep of {len(chunks)} chunks of {size} B: {batches} batches")
+    assert _running_sum(off, ln) and blob.size == int(ln.sum())
+    streams = _streams(blob, off, ln)
+    if DC.sweep_digest(streams) != DC.sweep_digests()[size]:
+        pytest.fail(f"sweep {size}: (first differing chunk, its family, bytes made, zlib's bytes) = {DC.first_difference(chunks, streams)}")
+    assert batches >= (2 if size == 512 else 1)               # (512: about 1,323 chunks to a batch today)
+    print(f"sweep of {len(chunks)} chunks of {size} B: {time.perf_counter() - t0:.2f} s")
+
+
 def test_round_trip_through_the_devices_inflate(eng):
     cs = [c for c in DC.cases() if len(c.raw) == 73728]
     assert len(cs) >= 8
     blob, off, ln = eng.deflate(np.frombuffer(b"".join(c.raw for c in cs), np.uint8).reshape(len(cs), 73728))
     out, status = eng.inflate(_streams(blob, off, ln), 73728)
     assert not status.any() and all(out[i].tobytes() == c.raw for i, c in enumerate(cs))
+    # the device's own streams with codes of 15 bits, distance and literal/length: behind the decoder's one-step tables
+    by = {c.name: c.raw for c in DC.cases()}
+    for name in ("fibdist", "lloverflow-16", "lloverflow-17"):
+        blob, off, ln = eng.deflate([by[name]])
+        out, status = eng.inflate(_streams(blob, off, ln), len(by[name]))
+        assert list(status) == [0] and out[0].tobytes() == by[name], name
     # and a record goes back into a held study as the file's own chunks do
     flow = _array((5, 37, 53, 2), np.float16)
     eng.hold_study_chunks(eng.deflate_array(flow, (2, 16, 16, 1)))

@@ -39,6 +39,15 @@ def test_corpus_has_every_case_the_decoder_must_meet():
     # the good streams hold every block type: stored (00), fixed (01) and dynamic (10) first blocks
     first = {(c.stream[2] >> 1) & 3 for c, k in zip(cs, kinds) if k == IC.GOOD}
     assert first == {0, 1, 2}
+    # and codes of every length the format has: the deepest literal/length code and the deepest distance code of the good streams
+    # have 15 bits, the limit, far behind the decoder's one-step tables (without the four streams below they have 13 and 12)
+    from tests import deflate_cases as DC
+    deep = [0, 0]
+    for name in ("fibdist-L9", "fibdist-bl-L9", "lloverflow-16-L9", "lloverflow-17-L9"):
+        assert by[name] == IC.GOOD, name
+        d = DC.blocks(next(c.stream for c in cs if c.name == name))[1]
+        deep = [max(deep[0], d[0]), max(deep[1], d[2])]
+    assert deep == [15, 15]
 
 
 def test_core_decodes_the_corpus_under_the_sanitizers(tmp_path):

@@ -12,9 +12,11 @@
 // launches later to stop enqueuing a stage -- it never stalls the stream inside the iteration budget.
 // The host side is cut by what it serves, all of it one translation unit: teeflow_engine.hip.h (Engine, tf_handle, the one-shot flags), the solvers'
 // teeflow_tvl1_host.hip.h and teeflow_deepflow_host.hip.h, teeflow_queue.hip.h (a call's way to an engine or to the lanes), this file's C ABI entry points, then
-// the study tail, a host header per topic beside its kernel header (listed where they are included), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
+// the study tail, a host header per topic beside its kernel header (listed where they are included; teeflow_scratch.hip.h and teeflow_streams_host.hip.h, what
+// the topics share, come first), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
 // The device side is one header per kernel family; teeflow_kernels.hip.h holds what the solvers share and includes DualTVL1's
-// stages (teeflow_tvl1_warp / _iter / _median.hip.h) and the tail's frame conditioning (teeflow_cond.hip.h).
+// stages (teeflow_tvl1_warp / _iter / _median.hip.h) and the tail's frame conditioning (teeflow_cond.hip.h); teeflow_wave_stage.hip.h is
+// the staged reader that teeflow_inflate.hip.h and teeflow_rle.hip.h share.
 #include "teeflow_kernels.hip.h"
 #include "teeflow_deepflow.hip.h"
 #include "teeflow_sor_rt.hip.h"
@@ -224,6 +226,8 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     if (!h || !name) return -1;
     const std::string n(name);
     long long v = -1;
+    for (int i = 0; i < tf_handle::DT_COUNT; ++i)
+        if (n == DEV_TIME_NAMES[i]) return (long long)(h->dev_ms[i] * 1000.0);
     std::vector<CoopCounters> all{h->coop.counters()};            // this handle and what its lanes published at the end of their last unit
     if (h->pool) { std::lock_guard<std::mutex> lk(h->pool->m); all.insert(all.end(), h->pool->coop.begin(), h->pool->coop.end()); }
     if (n == "coop_launches") { v = 0; for (auto& c : all) v += c.launches; }
@@ -231,22 +235,13 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "coop_disabled") { v = 0; for (auto& c : all) v |= (long long)c.disabled; }
     else if (n == "coop_rearms") { v = 0; for (auto& c : all) v += c.rearms; }
     else if (n == "coop_cooldown") { v = 0; for (auto& c : all) v = v > c.cooldown ? v : c.cooldown; }
-    else if (n == "saliency_kernel_us") v = (long long)(h->pre_kernel_ms * 1000.0);
-    else if (n == "wase_study_kernel_us") v = (long long)(h->wase_kernel_ms * 1000.0);
-    else if (n == "inflate_kernel_us") v = (long long)(h->inflate_kernel_ms * 1000.0);
-    else if (n == "unchunk_kernel_us") v = (long long)(h->unchunk_kernel_ms * 1000.0);
-    else if (n == "deflate_match_us") v = (long long)(h->deflate_match_ms * 1000.0);
-    else if (n == "deflate_emit_us") v = (long long)(h->deflate_emit_ms * 1000.0);
-    else if (n == "chunk_kernel_us") v = (long long)(h->chunk_kernel_ms * 1000.0);
     else if (n == "deflate_batches") v = h->deflate_batches;
     else if (n == "queue_jobs") v = h->q_jobs;
     else if (n == "stream_retries") v = h->stream_retries;
     else if (n == "tail_upload_bytes") v = h->tail_upload_bytes;
     else if (n == "frames_upload_bytes") v = h->frames_upload_bytes;
     else if (n == "frames_held_reads") v = h->frames_held_reads;
-    else if (n == "ingest_kernel_us") v = (long long)(h->ingest_kernel_ms * 1000.0);
     else if (n == "ingest_bytes") v = h->ingest_bytes;
-    else if (n == "rle_kernel_us") v = (long long)(h->rle_kernel_ms * 1000.0);
     else if (n == "rle_bytes") v = h->rle_bytes;
     else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
@@ -420,6 +415,7 @@ TF_API void tf_host_free(void* p)
 
 // ---- the study tail: everything around the solver, from frame conditioning to WASE; host code, a header per topic in the order they build on each other ----
 #include "teeflow_scratch.hip.h"          // the handle's grow-only scratch, chunking, Src: what every tail call shares
+#include "teeflow_streams_host.hip.h"     // a batch of byte streams: check, upload, verdict (inflate's and RLE's)
 #include "teeflow_frames_host.hip.h"      // a call's frames (tf_frames_next), conditioning, echo, saliency, the held frames
 #include "teeflow_masks_host.hip.h"       // labelling: clean masks, Otsu, AV centroids, first-region areas
 #include "teeflow_segmentor_host.hip.h"

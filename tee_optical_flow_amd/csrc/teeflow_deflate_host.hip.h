@@ -118,11 +118,9 @@ int deflate_run(tf_handle* h, const char* who, const DeflateJob& j)
         HIPC(h, hipGetLastError());
         HIPC(h, hipEventRecord(h->ev[2], h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));             // the next batch writes the same scratch and records the same events
-        float t = 0;
-        if (hipEventElapsedTime(&t, h->ev[3], h->ev[0]) == hipSuccess && j.array) h->chunk_kernel_ms += t;
-        if (hipEventElapsedTime(&t, h->ev[0], h->ev[1]) == hipSuccess) h->deflate_match_ms += t;
-        if (hipEventElapsedTime(&t, h->ev[1], h->ev[2]) == hipSuccess) h->deflate_emit_ms += t;
-        (void)hipGetLastError();
+        if (j.array) (void)dev_time(h, 3, 0, tf_handle::DT_CHUNK, true);
+        (void)dev_time(h, 0, 1, tf_handle::DT_DEFLATE_MATCH, true);
+        (void)dev_time(h, 1, 2, tf_handle::DT_DEFLATE_EMIT, true);
     }
     HIPC(h, hipMemcpyAsync(table.data() + t_off, dtab + t_off, tb - t_off, hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));

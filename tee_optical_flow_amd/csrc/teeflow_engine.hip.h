@@ -206,10 +206,12 @@ struct tf_handle : Engine {
                                                                                   //   sample planes; tf_rle_decode's interleaved frames
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
-    double pre_kernel_ms = 0;    // device time of the last saliency call's kernels (HIP events on the handle's stream)
-    double wase_kernel_ms = 0;   // device time of the last WASE study call's reduction and output kernels (the same events)
-    double inflate_kernel_ms = 0, unchunk_kernel_ms = 0;   // device time of k_inflate / k_unchunk since the handle was made (the same events)
-    double deflate_match_ms = 0, deflate_emit_ms = 0, chunk_kernel_ms = 0;   // ... of deflate's links + search, emit + offsets + pack, and k_chunk
+    // Device time of the tail's kernels in ms, read from the handle's event pairs (dev_time, below); tf_dbg_counter reports slot i in
+    // microseconds under DEV_TIME_NAMES[i].  Of the last call: the saliency kernels, a WASE study call's reduction and output kernels,
+    // k_ingest (tf_hold_frames, tf_hold_frames_rle), k_rle_decode (tf_rle_decode, tf_hold_frames_rle).  Since the handle was made:
+    // k_inflate, k_unchunk, deflate's links + search, its emit + offsets + pack, and k_chunk.
+    enum { DT_SALIENCY, DT_WASE, DT_INGEST, DT_RLE, DT_INFLATE, DT_UNCHUNK, DT_DEFLATE_MATCH, DT_DEFLATE_EMIT, DT_CHUNK, DT_COUNT };
+    double dev_ms[DT_COUNT] = {};
     long long deflate_batches = 0;                                           // passes of deflate_run's batch loop since the handle was made
     // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
     // ([0]: upload done) and the device scratch ([1]: kernel done) of the last call may be written again
@@ -246,8 +248,8 @@ struct tf_handle : Engine {
     } frames;
     long long frames_upload_bytes = 0;   // bytes of frames that tf_hold_frames and the frames-taking calls have copied host -> device
     long long frames_held_reads = 0;     // frames-taking calls that read the held frames in place
-    double ingest_kernel_ms = 0; long long ingest_bytes = 0;   // the last tf_hold_frames: k_ingest's device time and the bytes it read and wrote
-    double rle_kernel_ms = 0; long long rle_bytes = 0;   // the last tf_rle_decode / tf_hold_frames_rle: k_rle_decode's device time, compressed bytes read + plane bytes written
+    long long ingest_bytes = 0;          // the last tf_hold_frames: the bytes k_ingest read and wrote
+    long long rle_bytes = 0;             // the last tf_rle_decode / tf_hold_frames_rle: compressed bytes read + plane bytes written
     // ---- the one-shot flags of the handle's next call, taken with spend(), below: tf_chain_next (a sequence is solved as a chain),
     // tf_hold_next (a study call leaves its payload held), tf_frames_next (the call reads held frames [first, first + count)).
     // `armed` holds the first two; tf_frames_next's part of the record is kept beside the handles (g_frames_next says why) ----
@@ -324,6 +326,21 @@ int fail(Engine* e, int code, const char* fmt, ...)
             return fail(h, e_ == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "%s failed: %s (%s:%d)", #call, \
                         hipGetErrorString(e_), __FILE__, __LINE__);                                \
     } while (0)
+
+constexpr const char* DEV_TIME_NAMES[tf_handle::DT_COUNT] = {"saliency_kernel_us", "wase_study_kernel_us", "ingest_kernel_us", "rle_kernel_us", "inflate_kernel_us",
+                                                             "unchunk_kernel_us", "deflate_match_us", "deflate_emit_us", "chunk_kernel_us"};
+
+// The device time from ev[a] to ev[b] of the handle, both recorded on a stream that has been waited for, into dev_ms[slot]: added to
+// it, or put in its place.  A read-back that fails leaves the slot and is the caller's to judge: HIPC(h, dev_time(...)) fails the
+// call (saliency, a WASE study, a hold's ingest), (void)dev_time(...) drops it where a counter alone depends on it (inflate, deflate, RLE).
+inline hipError_t dev_time(tf_handle* h, int a, int b, int slot, bool add)
+{
+    float t = 0;
+    const hipError_t e = hipEventElapsedTime(&t, h->ev[a], h->ev[b]);
+    if (e == hipSuccess) h->dev_ms[slot] = (add ? h->dev_ms[slot] : 0.0) + t;
+    else (void)hipGetLastError();
+    return e;
+}
 
 inline double now_ms()
 {

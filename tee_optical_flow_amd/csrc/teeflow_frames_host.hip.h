@@ -1,7 +1,8 @@
 // A call's frames: where it finds them (the caller's host pointer, or the held frames behind tf_frames_next), then what is made of
 // them around the solver -- conditioned gray frames, the float16 echo, saliency maps -- and, in the second half, the held frames
 // themselves (tf_hold_frames & co.), last the same from RLE Lossless pixel data (tf_rle_decode, tf_hold_frames_rle).  Relies on
-// teeflow_scratch.hip.h, and on the kernels of teeflow_cond / _saliency / _ingest / _rle.hip.h.
+// teeflow_scratch.hip.h, teeflow_streams_host.hip.h (the RLE frames are a batch of streams), and on the kernels of teeflow_cond /
+// _saliency / _ingest / _rle.hip.h.
 
 namespace {
 // The RGB frames of a frames-taking call named `who`: the caller's host pointer, or -- armed by tf_frames_next, `a` being what
@@ -149,7 +150,7 @@ int saliency_to_device(tf_handle* h, const Src& frames, int N, int H, int W, int
     auto* out = pre.get<uint8_t>(tf_handle::PRE_OUT, (size_t)N * npx * (f32 ? sizeof(float) : 1));
     auto* decho = echo16_out ? pre.get<uint16_t>(tf_handle::PRE_ECHO, nf * npx) : nullptr;
     if (pre.rc) return pre.rc;
-    h->pre_kernel_ms = 0;
+    h->dev_ms[tf_handle::DT_SALIENCY] = 0;
     for (int f0 = 0; f0 < N; f0 += nf) {
         const int n = std::min(nf, N - f0);
         const size_t px = (size_t)n * npx;
@@ -175,9 +176,7 @@ int saliency_to_device(tf_handle* h, const Src& frames, int N, int H, int W, int
             if (rc) return rc;
         }
         HIPC(h, hipStreamSynchronize(h->stream));        // (one chunk holds 2^27 pixels: a study is one chunk; the event pair is read per chunk)
-        float t = 0;
-        HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        h->pre_kernel_ms += t;
+        HIPC(h, dev_time(h, 0, 1, tf_handle::DT_SALIENCY, true));
     }
     *dout = out;
     return TF_OK;
@@ -219,55 +218,85 @@ int frames_quiesce(tf_handle* h)
     return TF_OK;
 }
 
+// k_ingest over npx pixels of src (device): interleaved pixels (hw == 0), or sample planes [N][3][hw] (a grey frame's one plane is the
+// frame: GRAY reads it as interleaved whatever hw says)
 template <int FORM>
-void launch_ingest(tf_handle* h, bool flip, const uint8_t* src, size_t npx, int W, uint8_t* out)
+void launch_ingest(tf_handle* h, bool flip, const uint8_t* src, size_t npx, int W, size_t hw, uint8_t* out)
 {
     const dim3 g((unsigned)(((npx + 3) / 4 + 255) / 256)), blk(256);
+    if constexpr (FORM != tfg::GRAY)
+        if (hw) {
+            if (flip) hipLaunchKernelGGL((tfg::k_ingest_planar<FORM, true>), g, blk, 0, h->stream, src, npx, W, hw, out);
+            else hipLaunchKernelGGL((tfg::k_ingest_planar<FORM, false>), g, blk, 0, h->stream, src, npx, W, hw, out);
+            return;
+        }
     if (flip) hipLaunchKernelGGL((tfg::k_ingest<FORM, true>), g, blk, 0, h->stream, src, npx, W, out);
     else hipLaunchKernelGGL((tfg::k_ingest<FORM, false>), g, blk, 0, h->stream, src, npx, W, out);
+}
+
+// The held frames' buffer made at least `bytes` large, and nothing held any more.  keep_if_refused: the new buffer is allocated
+// before the old one goes, so a refused allocation leaves the held frames as they were (both buffers live for a moment); otherwise the
+// old one goes first and the peak is one buffer.
+int frames_buffer(tf_handle* h, size_t bytes, bool keep_if_refused, int N, int H, int W)
+{
+    tf_handle::Frames& k = h->frames;
+    if (!keep_if_refused) k.drop();
+    if (k.cap < bytes) {
+        if (!keep_if_refused) { (void)hipFree(k.rgb); k.rgb = nullptr; k.cap = 0; }
+        uint8_t* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding frames of %d x %d x %d: hipMalloc failed: %s", N, H, W, hipGetErrorString(e));
+        }
+        (void)hipFree(k.rgb);
+        k.rgb = p; k.cap = bytes;
+    }
+    k.drop();
+    return TF_OK;
+}
+
+// The step every hold ends with, behind frames_buffer: dsrc (device; laid out as launch_ingest says) ingested into the held buffer
+// between ev[0] and ev[1] -- or no kernel at all, dsrc null: the caller has queued a copy of RGB frames straight into the buffer --
+// then the stream waited for, the ingest counters, the shape, the generation.
+int frames_commit(tf_handle* h, const uint8_t* dsrc, size_t hw, int form, bool flip, int N, int H, int W)
+{
+    tf_handle::Frames& k = h->frames;
+    const size_t npx = (size_t)N * H * W;
+    h->dev_ms[tf_handle::DT_INGEST] = 0; h->ingest_bytes = 0;
+    if (dsrc) {
+        HIPC(h, hipEventRecord(h->ev[0], h->stream));
+        if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, dsrc, npx, W, hw, k.rgb);
+        else if (form == TF_FRAMES_YBR_FULL) launch_ingest<tfg::YBR_FULL>(h, flip, dsrc, npx, W, hw, k.rgb);
+        else launch_ingest<tfg::RGB>(h, flip, dsrc, npx, W, hw, k.rgb);
+        HIPC(h, hipGetLastError());
+        HIPC(h, hipEventRecord(h->ev[1], h->stream));
+    }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (dsrc) {
+        HIPC(h, dev_time(h, 0, 1, tf_handle::DT_INGEST, false));
+        h->ingest_bytes = (long long)(npx * (form == TF_FRAMES_GRAY ? 1 : 3) + npx * 3);
+    }
+    k.N = N; k.H = H; k.W = W;
+    ++k.gen;
+    return TF_OK;
 }
 
 int hold_frames(tf_handle* h, const uint8_t* src, int form, bool flip, int N, int H, int W)
 {
     int rc = frames_quiesce(h);
     if (rc) return rc;
-    tf_handle::Frames& k = h->frames;
-    k.drop();
-    const size_t npx = (size_t)N * H * W, in_bytes = npx * (form == TF_FRAMES_GRAY ? 1 : 3), out_bytes = npx * 3;
-    if (k.cap < out_bytes) {
-        (void)hipFree(k.rgb); k.rgb = nullptr; k.cap = 0;
-        const hipError_t e = hipMalloc(&k.rgb, out_bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding frames of %d x %d x %d: hipMalloc failed: %s", N, H, W, hipGetErrorString(e));
-        }
-        k.cap = out_bytes;
-    }
-    h->ingest_kernel_ms = 0; h->ingest_bytes = 0;
-    if (form == TF_FRAMES_RGB && !flip) {                     // nothing to compute: the upload is the held frames
-        HIPC(h, hipMemcpyAsync(k.rgb, src, in_bytes, hipMemcpyHostToDevice, h->stream));
-    } else {
+    const size_t npx = (size_t)N * H * W, in_bytes = npx * (form == TF_FRAMES_GRAY ? 1 : 3);
+    if ((rc = frames_buffer(h, npx * 3, false, N, H, W))) return rc;
+    uint8_t* dsrc = nullptr;                                  // (RGB, no flip: nothing to compute, the upload is the held frames)
+    if (form != TF_FRAMES_RGB || flip) {
         Pre pre(h);
-        auto* dsrc = pre.get<uint8_t>(tf_handle::PRE_FR_SRC, in_bytes);
+        dsrc = pre.get<uint8_t>(tf_handle::PRE_FR_SRC, in_bytes);
         if (pre.rc) return pre.rc;
-        HIPC(h, hipMemcpyAsync(dsrc, src, in_bytes, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipEventRecord(h->ev[0], h->stream));
-        if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, dsrc, npx, W, k.rgb);
-        else if (form == TF_FRAMES_YBR_FULL) launch_ingest<tfg::YBR_FULL>(h, flip, dsrc, npx, W, k.rgb);
-        else launch_ingest<tfg::RGB>(h, flip, dsrc, npx, W, k.rgb);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipEventRecord(h->ev[1], h->stream));
     }
-    HIPC(h, hipStreamSynchronize(h->stream));
+    HIPC(h, hipMemcpyAsync(dsrc ? dsrc : h->frames.rgb, src, in_bytes, hipMemcpyHostToDevice, h->stream));
     h->frames_upload_bytes += (long long)in_bytes;
-    if (!(form == TF_FRAMES_RGB && !flip)) {
-        float t = 0;
-        HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        h->ingest_kernel_ms = t; h->ingest_bytes = (long long)(in_bytes + out_bytes);
-    }
-    k.N = N; k.H = H; k.W = W;
-    ++k.gen;
-    return TF_OK;
+    return frames_commit(h, dsrc, 0, form, flip, N, H, W);
 }
 }  // namespace
 
@@ -332,62 +361,44 @@ const char* rle_status_text(int s)
 }
 
 struct RleJob {
-    const uint8_t* blob; const uint64_t* off; const uint32_t* len; int N, H, W, samples;
-    uint64_t lo = 0, hi = 0;                                  // [lo, hi) of the blob holds every frame (rle_check)
+    tfs::Batch in; int H, W, samples;                         // the frames (checked: rle_check; in.n of them) and their shape
     size_t plane() const { return (size_t)H * W; }
 };
 
 // before any GPU work
 int rle_check(tf_handle* h, const char* who, RleJob& j)
 {
-    if (!j.blob || !j.off || !j.len) return fail(h, TF_ERR_INVALID_ARG, "%s: null blob, off or len", who);
-    if (j.N < 1 || j.H < 1 || j.W < 1) return fail(h, TF_ERR_INVALID_ARG, "%s: bad sizes: N=%d H=%d W=%d", who, j.N, j.H, j.W);
+    if (j.in.n < 1 || j.H < 1 || j.W < 1) return fail(h, TF_ERR_INVALID_ARG, "%s: bad sizes: N=%d H=%d W=%d", who, j.in.n, j.H, j.W);
     if (j.samples != 1 && j.samples != 3) return fail(h, TF_ERR_INVALID_ARG, "%s: samples must be 1 or 3, got %d", who, j.samples);
     if ((double)j.H * j.W > RLE_MAX_PLANE) return fail(h, TF_ERR_INVALID_ARG, "%s: a plane of %d x %d bytes, at most %u", who, j.H, j.W, RLE_MAX_PLANE);
-    if ((double)j.N * j.samples > std::numeric_limits<int>::max()) return fail(h, TF_ERR_INVALID_ARG, "%s: %d frames of %d segments", who, j.N, j.samples);
-    j.lo = ~0ull; j.hi = 0;
-    for (int i = 0; i < j.N; ++i) {
-        if (j.len[i] > RLE_MAX_FRAME) return fail(h, TF_ERR_INVALID_ARG, "%s: frame %d has %u bytes, at most %u", who, i, j.len[i], RLE_MAX_FRAME);
-        if (j.off[i] > (~0ull >> 1) - j.len[i])
-            return fail(h, TF_ERR_INVALID_ARG, "%s: frame %d: off %llu + len %u overflows", who, i, (unsigned long long)j.off[i], j.len[i]);
-        j.lo = std::min<uint64_t>(j.lo, j.off[i]); j.hi = std::max<uint64_t>(j.hi, j.off[i] + j.len[i]);
-    }
-    return TF_OK;
+    if ((double)j.in.n * j.samples > std::numeric_limits<int>::max()) return fail(h, TF_ERR_INVALID_ARG, "%s: %d frames of %d segments", who, j.in.n, j.samples);
+    return streams_check(h, who, j.in, RLE_MAX_FRAME, "frame");
 }
 
 // what a launched decode left on the device (valid once the handle's stream has run it)
 struct RleDecoded {
     const uint8_t* planes = nullptr;                          // [N][samples][H * W]
     int* status = nullptr;                                    // [N]
-    std::vector<uint8_t> table;                               // the host side of the per-frame table: lives until the stream is waited for
+    tfs::Table table;                                         // the host side of the per-frame table: lives until the stream is waited for
 };
 
 // The frames of j onto the device and k_rle_decode behind them on the handle's stream, between ev[0] and ev[1]; not waited for.
 int rle_launch(tf_handle* h, const RleJob& j, RleDecoded* r)
 {
-    const size_t n = (size_t)j.N, skew = (size_t)(j.lo & 15), bytes = (size_t)(j.hi - j.lo);
-    // the table: off [n] u64 | len [n] u32 | status [n] i32 (zero)
-    const size_t o_len = n * 8, o_st = o_len + n * 4, tb = o_st + n * 4;
-    r->table.assign(tb, 0);
-    uint8_t* t = r->table.data();
-    for (size_t i = 0; i < n; ++i) {
-        const unsigned long long o = j.off[i] - j.lo + skew;      // in the device copy, which keeps the blob's alignment mod 16
-        memcpy(t + i * 8, &o, 8);
-    }
-    memcpy(t + o_len, j.len, n * 4);
+    const size_t n = (size_t)j.in.n;
+    enum { OFF, LEN, STATUS };                                // off [n] u64 | len [n] u32 | status [n] i32
+    r->table = tfs::table(j.in, {8, 4, 4}, OFF, LEN);
     Pre pre(h);
-    auto* dblob = pre.get<uint8_t>(tf_handle::PRE_RLE_BLOB, skew + bytes + 32);   // (padded: a staged 16-byte piece may pass a frame's end)
-    auto* dtab = pre.get<uint8_t>(tf_handle::PRE_RLE_TABLE, tb);
     auto* dplanes = pre.get<uint8_t>(tf_handle::PRE_RLE_PLANES, n * j.samples * j.plane());
     if (pre.rc) return pre.rc;
-    if (bytes) HIPC(h, hipMemcpyAsync(dblob + skew, j.blob + j.lo, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPC(h, hipMemcpyAsync(dtab, t, tb, hipMemcpyHostToDevice, h->stream));
-    h->frames_upload_bytes += (long long)bytes;
-    r->planes = dplanes; r->status = (int*)(dtab + o_st);
-    h->rle_kernel_ms = 0; h->rle_bytes = 0;
+    const uint8_t* dblob = nullptr; uint8_t* dtab = nullptr;
+    if (int rc = streams_upload(h, j.in, r->table, tf_handle::PRE_RLE_BLOB, tf_handle::PRE_RLE_TABLE, &tf_handle::frames_upload_bytes, &dblob, &dtab)) return rc;
+    const auto& at = r->table.at;
+    r->planes = dplanes; r->status = (int*)(dtab + at[STATUS]);
+    h->dev_ms[tf_handle::DT_RLE] = 0; h->rle_bytes = 0;
     HIPC(h, hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(k_rle_decode, dim3((unsigned)(n * j.samples)), dim3(64), 0, h->stream, (const uint8_t*)dblob, (const unsigned long long*)dtab,
-                       (const uint32_t*)(dtab + o_len), j.N, j.samples, (uint32_t)j.plane(), dplanes, r->status);
+    hipLaunchKernelGGL(k_rle_decode, dim3((unsigned)(n * j.samples)), dim3(64), 0, h->stream, dblob, (const unsigned long long*)(dtab + at[OFF]),
+                       (const uint32_t*)(dtab + at[LEN]), j.in.n, j.samples, (uint32_t)j.plane(), dplanes, r->status);
     HIPC(h, hipGetLastError());
     HIPC(h, hipEventRecord(h->ev[1], h->stream));
     return TF_OK;
@@ -396,30 +407,8 @@ int rle_launch(tf_handle* h, const RleJob& j, RleDecoded* r)
 // after the stream has been waited for: the kernel's device time and bytes into the handle's counters
 void rle_counters(tf_handle* h, const RleJob& j)
 {
-    float t = 0;
-    if (hipEventElapsedTime(&t, h->ev[0], h->ev[1]) == hipSuccess) h->rle_kernel_ms = t;
-    (void)hipGetLastError();
-    h->rle_bytes = (long long)(j.hi - j.lo) + (long long)((size_t)j.N * j.samples * j.plane());
-}
-
-// the first frame that did not decode -> the call's failure
-int rle_verdict(tf_handle* h, const char* who, const int* status, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (status[i]) {
-            int bad = 0;
-            for (int k = i; k < n; ++k) bad += status[k] != 0;
-            return fail(h, TF_ERR_INVALID_ARG, "%s: frame %d did not decode: status %d (%s); %d of %d failed", who, i, status[i], rle_status_text(status[i]), bad, n);
-        }
-    return TF_OK;
-}
-
-template <int FORM>
-void launch_ingest_planar(tf_handle* h, bool flip, const uint8_t* src, size_t npx, int W, size_t hw, uint8_t* out)
-{
-    const dim3 g((unsigned)(((npx + 3) / 4 + 255) / 256)), blk(256);
-    if (flip) hipLaunchKernelGGL((tfg::k_ingest_planar<FORM, true>), g, blk, 0, h->stream, src, npx, W, hw, out);
-    else hipLaunchKernelGGL((tfg::k_ingest_planar<FORM, false>), g, blk, 0, h->stream, src, npx, W, hw, out);
+    (void)dev_time(h, 0, 1, tf_handle::DT_RLE, false);
+    h->rle_bytes = (long long)j.in.bytes() + (long long)((size_t)j.in.n * j.samples * j.plane());
 }
 
 int rle_decode(tf_handle* h, const RleJob& j, uint8_t* out_host, int* status)
@@ -427,70 +416,45 @@ int rle_decode(tf_handle* h, const RleJob& j, uint8_t* out_host, int* status)
     HIPC(h, hipSetDevice(h->dev));
     RleDecoded r;
     if (int rc = rle_launch(h, j, &r)) return rc;
-    const size_t npx = (size_t)j.N * j.plane(), frame_bytes = j.plane() * j.samples;
+    const int N = j.in.n;
+    const size_t npx = (size_t)N * j.plane(), frame_bytes = j.plane() * j.samples;
     const uint8_t* dout = r.planes;                           // (one plane a frame is the frame)
     if (j.samples == 3) {
         Pre pre(h);
         auto* d = pre.get<uint8_t>(tf_handle::PRE_RLE_OUT, npx * 3);
         if (pre.rc) return pre.rc;
-        launch_ingest_planar<tfg::RGB>(h, false, r.planes, npx, j.W, j.plane(), d);   // (a frame that failed: whatever its planes hold; not copied out)
+        launch_ingest<tfg::RGB>(h, false, r.planes, npx, j.W, j.plane(), d);   // (a frame that failed: whatever its planes hold; not copied out)
         HIPC(h, hipGetLastError());
         dout = d;
     }
-    HIPC(h, hipMemcpyAsync(status, r.status, (size_t)j.N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(status, r.status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     rle_counters(h, j);
     bool all = true;
-    for (int i = 0; i < j.N && all; ++i) all = status[i] == 0;
-    if (all) HIPC(h, hipMemcpyAsync(out_host, dout, (size_t)j.N * frame_bytes, hipMemcpyDeviceToHost, h->stream));
+    for (int i = 0; i < N && all; ++i) all = status[i] == 0;
+    if (all) HIPC(h, hipMemcpyAsync(out_host, dout, (size_t)N * frame_bytes, hipMemcpyDeviceToHost, h->stream));
     else
-        for (int i = 0; i < j.N; ++i)
+        for (int i = 0; i < N; ++i)
             if (status[i] == 0) HIPC(h, hipMemcpyAsync(out_host + (size_t)i * frame_bytes, dout + (size_t)i * frame_bytes, frame_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    return rle_verdict(h, "tf_rle_decode", status, j.N);
+    return streams_verdict(h, "tf_rle_decode", "frame", "decode", rle_status_text, status, N);
 }
 
 int hold_frames_rle(tf_handle* h, const RleJob& j, int form, bool flip, int* status_out)
 {
-    const char* who = "tf_hold_frames_rle";
     int rc = frames_quiesce(h);
     if (rc) return rc;
     RleDecoded r;
     if ((rc = rle_launch(h, j, &r))) return rc;
-    std::vector<int> status((size_t)j.N);
+    std::vector<int> status((size_t)j.in.n);
     HIPC(h, hipMemcpyAsync(status.data(), r.status, status.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     rle_counters(h, j);
     if (status_out) memcpy(status_out, status.data(), status.size() * sizeof(int));
-    if ((rc = rle_verdict(h, who, status.data(), j.N))) return rc;
-    // every frame decoded: from here on as hold_frames, the planes in the uploaded source's place
-    tf_handle::Frames& k = h->frames;
-    const size_t npx = (size_t)j.N * j.plane(), in_bytes = npx * j.samples, out_bytes = npx * 3;
-    if (k.cap < out_bytes) {                                  // (the new buffer first: a failed allocation leaves the held frames)
-        uint8_t* p = nullptr;
-        const hipError_t e = hipMalloc(&p, out_bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, e == hipErrorOutOfMemory ? TF_ERR_NOMEM : TF_ERR_HIP, "holding frames of %d x %d x %d: hipMalloc failed: %s", j.N, j.H, j.W, hipGetErrorString(e));
-        }
-        (void)hipFree(k.rgb);
-        k.rgb = p; k.cap = out_bytes;
-    }
-    k.drop();
-    h->ingest_kernel_ms = 0; h->ingest_bytes = 0;
-    HIPC(h, hipEventRecord(h->ev[0], h->stream));
-    if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, r.planes, npx, j.W, k.rgb);
-    else if (form == TF_FRAMES_YBR_FULL) launch_ingest_planar<tfg::YBR_FULL>(h, flip, r.planes, npx, j.W, j.plane(), k.rgb);
-    else launch_ingest_planar<tfg::RGB>(h, flip, r.planes, npx, j.W, j.plane(), k.rgb);
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipEventRecord(h->ev[1], h->stream));
-    HIPC(h, hipStreamSynchronize(h->stream));
-    float t = 0;
-    HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-    h->ingest_kernel_ms = t; h->ingest_bytes = (long long)(in_bytes + out_bytes);
-    k.N = j.N; k.H = j.H; k.W = j.W;
-    ++k.gen;
-    return TF_OK;
+    if ((rc = streams_verdict(h, "tf_hold_frames_rle", "frame", "decode", rle_status_text, status.data(), j.in.n))) return rc;
+    // every frame decoded: only now are the held frames touched, the decoded planes being the source
+    if ((rc = frames_buffer(h, (size_t)j.in.n * j.plane() * 3, true, j.in.n, j.H, j.W))) return rc;
+    return frames_commit(h, r.planes, j.plane(), form, flip, j.in.n, j.H, j.W);
 }
 }  // namespace
 
@@ -500,7 +464,7 @@ TF_API int tf_rle_decode(tf_handle* h, const uint8_t* blob, const uint64_t* off,
                          uint8_t* out_host, int* status)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    RleJob j{blob, off, len, N, H, W, samples};
+    RleJob j{{blob, off, len, N}, H, W, samples};
     if (int rc = rle_check(h, "tf_rle_decode", j)) return rc;
     if (!out_host || !status) return fail(h, TF_ERR_INVALID_ARG, "tf_rle_decode: null out_host or status");
     return finish_host_call(h, rle_decode(h, j, out_host, status));
@@ -515,7 +479,7 @@ TF_API int tf_hold_frames_rle(tf_handle* h, const uint8_t* blob, const uint64_t*
         return fail(h, TF_ERR_INVALID_ARG, "%s: form %d is none of TF_FRAMES_RGB (0), TF_FRAMES_GRAY (1), TF_FRAMES_YBR_FULL (2)", who, form);
     if (samples != (form == TF_FRAMES_GRAY ? 1 : 3))
         return fail(h, TF_ERR_INVALID_ARG, "%s: form %d has %d samples a pixel, got samples = %d", who, form, form == TF_FRAMES_GRAY ? 1 : 3, samples);
-    RleJob j{blob, off, len, N, H, W, samples};
+    RleJob j{{blob, off, len, N}, H, W, samples};
     if (int rc = rle_check(h, who, j)) return rc;
     return finish_host_call(h, hold_frames_rle(h, j, form, flip_lr != 0, status));
 }

@@ -8,26 +8,23 @@
 // The 32 KiB window is a ring in LDS and the only place back-references read: no lane ever reads back what the wave stored to global
 // memory.  Ring 32 KiB + input stage 1 KiB + tables 3.6 KiB = 37,440 B per block: four blocks per CU.
 //
-// Safety (a malformed stream is an expected input): the decoder asks for input byte i only with i < len, and in_byte stages whole
-// 16-byte pieces only where they overlap [0, len) of the stream (the blob's allocation is padded to whole pieces); put / copy / stored
-// refuse what would pass the slot's out_bytes before writing; flush writes [flushed, flushed + n) with flushed + n <= produced <=
-// out_bytes.  Loop bounds: teeflow_inflate_core.h.
+// Safety (a malformed stream is an expected input): the decoder asks for input byte i only with i < len, and the input is read
+// through the staged reader, whose safety argument is teeflow_wave_stage.hip.h's; put / copy / stored refuse what would pass the
+// slot's out_bytes before writing; flush writes [flushed, flushed + n) with flushed + n <= produced <= out_bytes.  Loop bounds:
+// teeflow_inflate_core.h.
 #pragma once
 #define TFI_FN __device__ inline
 #include "teeflow_inflate_core.h"
+#include "teeflow_wave_stage.hip.h"
 
 namespace inflate {
 constexpr uint32_t RING = tfi::WINDOW, STAGE = 1024, FLUSH = 4096;
 
-struct WaveIO {
-    uint8_t* ring; uint8_t* stage;              // LDS
-    const uint8_t* in;                          // the stream's first byte less `skew`: 16-byte aligned
-    uint32_t skew, in_len;
+struct WaveIO : tfw::WaveStage<STAGE> {
+    uint8_t* ring;                              // LDS
     uint8_t* out; uint32_t cap;                 // the stream's slot (16-byte aligned) and its size
     uint32_t n = 0, flushed = 0;                // bytes produced / written out
-    uint32_t unit = 0xFFFFFFFFu;                // which 1 KiB of the input the stage holds
     uint32_t a = 1, b = 0;                      // Adler-32 of the flushed bytes
-    int ln;
 
     __device__ int lane() const { return ln; }
     __device__ int lanes() const { return 64; }
@@ -37,16 +34,8 @@ struct WaveIO {
     __device__ uint8_t in_byte(uint32_t i)
     {
         const uint32_t at = i + skew;
-        if ((at >> 10) != unit) {
-            unit = at >> 10;
-            __syncthreads();
-            const uint32_t piece = unit * STAGE + (uint32_t)ln * 16;          // this lane's 16 bytes, from `in`
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (piece < skew + in_len) v = *(const uint4*)(in + piece);
-            *(uint4*)(stage + ln * 16) = v;
-            __syncthreads();
-        }
-        return stage[at & (STAGE - 1)];
+        fill(at);
+        return stage[at % STAGE];
     }
 
     // n_ more bytes [flushed, flushed + n_) from the ring to the slot, and into the checksum.  flushed is a multiple of 16.
@@ -104,11 +93,11 @@ struct WaveIO {
     __device__ int stored(uint32_t pos, uint32_t cnt)
     {
         if (cnt > cap - n) return tfi::BAD_OUTPUT_SIZE;
-        while (cnt) {                                                         // piece by piece of what one stage holds
+        while (cnt) {
             const uint32_t at = pos + skew;
-            uint32_t m = STAGE - (at & (STAGE - 1));
+            uint32_t m = within(at);
             if (m > cnt) m = cnt;
-            (void)in_byte(pos);                                               // the stage holds [pos, pos + m)
+            fill(at);                                                         // the stage holds [pos, pos + m)
             for (uint32_t k = (uint32_t)ln; k < m; k += 64) ring[(n + k) & (RING - 1)] = stage[(at + k) & (STAGE - 1)];
             advance(m);
             pos += m; cnt -= m;

@@ -1,5 +1,6 @@
 // The host side of inflate on the device (kernels: teeflow_inflate.hip.h): tf_inflate, and a study held from the chunks of its file,
-// tf_hold_study_chunks / tf_hold_mask_chunks.  Included by teeflow.hip after teeflow_held.hip.h and teeflow_study_host.hip.h.  The compressed bytes, the per-stream
+// tf_hold_study_chunks / tf_hold_mask_chunks.  Included by teeflow.hip after teeflow_streams_host.hip.h (the batch of streams: check, upload, verdict),
+// teeflow_held.hip.h and teeflow_study_host.hip.h.  The compressed bytes, the per-stream
 // table and the inflated chunk-major bytes live in the handle's PRE_INF_* slots; a held array is inflated and assembled into a fresh
 // buffer and takes the held one's place only when every chunk of the call has decoded, so a failed call changes nothing.
 
@@ -14,89 +15,50 @@ const char* inflate_status_text(int s)
 }
 
 struct InflateJob {
-    const uint8_t* blob; const uint64_t* off; const uint32_t* len; const uint8_t* raw; int n; uint32_t out_bytes;
-    uint64_t lo = 0, hi = 0;                                  // [lo, hi) of the blob holds every stream (inflate_check)
+    tfs::Batch in; const uint8_t* raw; uint32_t out_bytes;    // the streams (checked: inflate_check), which of them are stored raw, every slot's size
 };
 
 // before any GPU work
 int inflate_check(tf_handle* h, const char* who, InflateJob& j)
 {
-    if (j.n < 0) return fail(h, TF_ERR_INVALID_ARG, "%s: n = %d streams", who, j.n);
+    if (j.in.n < 0) return fail(h, TF_ERR_INVALID_ARG, "%s: n = %d streams", who, j.in.n);
     if (j.out_bytes > INFLATE_MAX_BYTES) return fail(h, TF_ERR_INVALID_ARG, "%s: %u output bytes per stream, at most %u", who, j.out_bytes, INFLATE_MAX_BYTES);
-    if (j.n && (!j.blob || !j.off || !j.len)) return fail(h, TF_ERR_INVALID_ARG, "%s: null blob, off or len", who);
-    j.lo = ~0ull; j.hi = 0;
-    for (int i = 0; i < j.n; ++i) {
-        if (j.len[i] > INFLATE_MAX_BYTES) return fail(h, TF_ERR_INVALID_ARG, "%s: stream %d has %u bytes, at most %u", who, i, j.len[i], INFLATE_MAX_BYTES);
-        if (j.off[i] > (~0ull >> 1)) return fail(h, TF_ERR_INVALID_ARG, "%s: stream %d starts at byte %llu", who, i, (unsigned long long)j.off[i]);
-        j.lo = std::min<uint64_t>(j.lo, j.off[i]); j.hi = std::max<uint64_t>(j.hi, j.off[i] + j.len[i]);
-    }
-    if (!j.n) j.lo = 0;
-    return TF_OK;
+    return streams_check(h, who, j.in, INFLATE_MAX_BYTES, "stream");
 }
 
 // what a launched inflate left on the device (valid once the handle's stream has run it)
 struct Inflated {
     const uint8_t* bytes = nullptr; size_t stride = 0;        // stream i's output: bytes + i * stride
-    const uint8_t* blob = nullptr;                            // the uploaded [lo, hi), and per stream:
+    const uint8_t* blob = nullptr;                            // the uploaded span, and per stream:
     const unsigned long long* off = nullptr; const uint8_t* raw = nullptr; const long long* coord = nullptr;
     int* status = nullptr; uint32_t* produced = nullptr;
-    std::vector<uint8_t> table;                               // the host side of the per-stream table: lives until the stream is waited for
+    tfs::Table table;                                         // the host side of the per-stream table: lives until the stream is waited for
 };
 
-// The streams of j (n >= 1) onto the device and k_inflate behind them on the handle's stream; not waited for.  coord4: host [n][4]
-// chunk coordinates that go up with the table, or null.
+// The streams of j (n >= 1) onto the device and k_inflate behind them on the handle's stream, between ev[0] and ev[1]; not waited
+// for.  coord4: host [n][4] chunk coordinates that go up with the table, or null.
 int inflate_launch(tf_handle* h, const InflateJob& j, const long long* coord4, Inflated* r)
 {
-    const size_t n = (size_t)j.n, skew = (size_t)(j.lo & 15), bytes = (size_t)(j.hi - j.lo);
+    const size_t n = (size_t)j.in.n;
     r->stride = ((size_t)j.out_bytes + 15) & ~(size_t)15;
-    // the table: coord [n][4] i64 | off [n] u64 | len [n] u32 | status [n] i32 | produced [n] u32 | raw [n] u8
-    const size_t o_off = n * 32, o_len = o_off + n * 8, o_st = o_len + n * 4, o_pr = o_st + n * 4, o_raw = o_pr + n * 4, tb = o_raw + n;
-    r->table.assign(tb, 0);
-    uint8_t* t = r->table.data();
-    if (coord4) memcpy(t, coord4, n * 32);
-    for (size_t i = 0; i < n; ++i) {
-        const unsigned long long o = j.off[i] - j.lo + skew;
-        memcpy(t + o_off + i * 8, &o, 8);
-        if (j.raw) t[o_raw + i] = j.raw[i] ? 1 : 0;
-    }
-    memcpy(t + o_len, j.len, n * 4);
+    enum { COORD, OFF, LEN, STATUS, PRODUCED, RAW };          // coord [n][4] i64 | off [n] u64 | len [n] u32 | status [n] i32 | produced [n] u32 | raw [n] u8
+    r->table = tfs::table(j.in, {32, 8, 4, 4, 4, 1}, OFF, LEN);
+    if (coord4) memcpy(r->table.col(COORD), coord4, n * 32);
+    if (j.raw) for (size_t i = 0; i < n; ++i) r->table.col(RAW)[i] = j.raw[i] ? 1 : 0;
     Pre pre(h);
-    auto* dblob = pre.get<uint8_t>(tf_handle::PRE_INF_BLOB, skew + bytes + 32);
-    auto* dtab = pre.get<uint8_t>(tf_handle::PRE_INF_TABLE, tb);
     auto* dout = pre.get<uint8_t>(tf_handle::PRE_INF_OUT, std::max<size_t>(n * r->stride, 16));
     if (pre.rc) return pre.rc;
-    if (bytes) HIPC(h, hipMemcpyAsync(dblob + skew, j.blob + j.lo, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPC(h, hipMemcpyAsync(dtab, t, tb, hipMemcpyHostToDevice, h->stream));
-    h->tail_upload_bytes += (long long)bytes;
-    r->bytes = dout; r->blob = dblob;
-    r->coord = (const long long*)dtab; r->off = (const unsigned long long*)(dtab + o_off);
-    r->status = (int*)(dtab + o_st); r->produced = (uint32_t*)(dtab + o_pr); r->raw = dtab + o_raw;
+    uint8_t* dtab = nullptr;
+    if (int rc = streams_upload(h, j.in, r->table, tf_handle::PRE_INF_BLOB, tf_handle::PRE_INF_TABLE, &tf_handle::tail_upload_bytes, &r->blob, &dtab)) return rc;
+    const auto& at = r->table.at;
+    r->bytes = dout;
+    r->coord = (const long long*)(dtab + at[COORD]); r->off = (const unsigned long long*)(dtab + at[OFF]);
+    r->status = (int*)(dtab + at[STATUS]); r->produced = (uint32_t*)(dtab + at[PRODUCED]); r->raw = dtab + at[RAW];
     HIPC(h, hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(k_inflate, dim3((unsigned)j.n), dim3(64), 0, h->stream, (const uint8_t*)dblob, r->off, (const uint32_t*)(dtab + o_len), r->raw,
-                       j.n, j.out_bytes, r->stride, dout, r->status, r->produced);
+    hipLaunchKernelGGL(k_inflate, dim3((unsigned)n), dim3(64), 0, h->stream, r->blob, r->off, (const uint32_t*)(dtab + at[LEN]), r->raw,
+                       j.in.n, j.out_bytes, r->stride, dout, r->status, r->produced);
     HIPC(h, hipGetLastError());
     HIPC(h, hipEventRecord(h->ev[1], h->stream));
-    return TF_OK;
-}
-
-// after the stream has been waited for: the kernels' device time into the handle's counters
-void inflate_times(tf_handle* h, bool unchunked)
-{
-    float t = 0;
-    if (hipEventElapsedTime(&t, h->ev[0], h->ev[1]) == hipSuccess) h->inflate_kernel_ms += t;
-    if (unchunked && hipEventElapsedTime(&t, h->ev[1], h->ev[2]) == hipSuccess) h->unchunk_kernel_ms += t;
-    (void)hipGetLastError();
-}
-
-// the first stream that did not decode -> the call's failure
-int inflate_verdict(tf_handle* h, const char* who, const char* what, const int* status, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (status[i]) {
-            int bad = 0;
-            for (int k = i; k < n; ++k) bad += status[k] != 0;
-            return fail(h, TF_ERR_INVALID_ARG, "%s: %s %d did not inflate: status %d (%s); %d of %d failed", who, what, i, status[i], inflate_status_text(status[i]), bad, n);
-        }
     return TF_OK;
 }
 
@@ -123,7 +85,7 @@ int chunks_check(tf_handle* h, const char* who, const char* what, const tf_chunk
     if (total > 64.0 * (1ull << 30)) return fail(h, TF_ERR_INVALID_ARG, "%s: %s: %.0f bytes", who, what, total);
     if ((double)c->chunk_bytes != cb) return fail(h, TF_ERR_INVALID_ARG, "%s: %s: chunk_bytes %u is not the chunk's %.0f bytes", who, what, c->chunk_bytes, cb);
     if (c->n && !c->coord) return fail(h, TF_ERR_INVALID_ARG, "%s: %s: null coord", who, what);
-    *j = InflateJob{c->blob, c->off, c->len, c->raw, c->n, c->chunk_bytes};
+    *j = InflateJob{{c->blob, c->off, c->len, c->n}, c->raw, c->chunk_bytes};
     if (int rc = inflate_check(h, who, *j)) return rc;
     for (int i = 0; i < c->n; ++i)
         for (int d = 0; d < ndim; ++d) {
@@ -156,8 +118,9 @@ int chunks_to_device(tf_handle* h, const char* who, const char* what, const tf_c
     std::vector<int> status((size_t)c.n);
     HIPC(h, hipMemcpyAsync(status.data(), r.status, status.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    inflate_times(h, true);
-    return inflate_verdict(h, who, what, status.data(), c.n);
+    (void)dev_time(h, 0, 1, tf_handle::DT_INFLATE, true);   // (the stream has been waited for; a counter alone depends on the read-back)
+    (void)dev_time(h, 1, 2, tf_handle::DT_UNCHUNK, true);
+    return streams_verdict(h, who, what, "inflate", inflate_status_text, status.data(), c.n);
 }
 }  // namespace
 
@@ -165,7 +128,7 @@ TF_API int tf_inflate(tf_handle* h, const uint8_t* blob, const uint64_t* off, co
                       uint8_t* out_host, int* status)
 {
     if (!h) return TF_ERR_INVALID_ARG;
-    InflateJob j{blob, off, len, raw, n, out_bytes};
+    InflateJob j{{blob, off, len, n}, raw, out_bytes};
     if (int rc = inflate_check(h, "tf_inflate", j)) return rc;
     if (n && (!status || (out_bytes && !out_host))) return fail(h, TF_ERR_INVALID_ARG, "tf_inflate: null out_host or status");
     if (!n) return TF_OK;
@@ -177,7 +140,7 @@ TF_API int tf_inflate(tf_handle* h, const uint8_t* blob, const uint64_t* off, co
         HIPC(h, hipMemcpyAsync(status, r.status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipMemcpyAsync(produced.data(), r.produced, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
-        inflate_times(h, false);
+        (void)dev_time(h, 0, 1, tf_handle::DT_INFLATE, true);
         // a slot gets what its stream produced and nothing else: all of them in one copy when every stream filled its slot
         bool full = out_bytes > 0;
         for (int i = 0; i < n && full; ++i) full = produced[i] == out_bytes && !(raw && raw[i]);
@@ -189,7 +152,7 @@ TF_API int tf_inflate(tf_handle* h, const uint8_t* blob, const uint64_t* off, co
                 else if (produced[i]) HIPC(h, hipMemcpyAsync(slot, r.bytes + (size_t)i * r.stride, produced[i], hipMemcpyDeviceToHost, h->stream));
             }
         HIPC(h, hipStreamSynchronize(h->stream));
-        return inflate_verdict(h, "tf_inflate", "stream", status, n);
+        return streams_verdict(h, "tf_inflate", "stream", "inflate", inflate_status_text, status, n);
     };
     return finish_host_call(h, run());
 }

@@ -9,38 +9,20 @@
 // so the hop chain waits on no store.  Interleaving the planes is k_ingest_planar's (teeflow_ingest.hip.h).
 //
 // Safety (a malformed stream is an expected input): the header is read from the frame's own bytes, byte i only with i < len; the core
-// asks for segment byte i only with i < the segment's length, and fill() stages whole 16-byte pieces only where they overlap the
-// segment (the library's device copy of the blob starts 16-byte aligned and is padded past its end, so such a piece lies inside the
-// copy whatever the caller's blob is); the core clips a literal or run to what the plane still lacks.  Loop bounds: teeflow_rle_core.h.
+// asks for segment byte i only with i < the segment's length, and the segment is read through the staged reader, whose safety
+// argument is teeflow_wave_stage.hip.h's; the core clips a literal or run to what the plane still lacks.  Loop bounds:
+// teeflow_rle_core.h.
 #pragma once
 #define TFR_FN __device__ inline
 #include "teeflow_rle_core.h"
+#include "teeflow_wave_stage.hip.h"
 
 namespace rle {
 constexpr uint32_t STAGE = 1024;            // bytes of a segment the LDS stage holds (tf_rle_stage_bytes tells the tests)
 
-struct WaveIO {
-    uint8_t* stage;                             // LDS
-    const uint8_t* in;                          // the segment's first byte less `skew`: 16-byte aligned
-    uint32_t skew, in_len;
+struct WaveIO : tfw::WaveStage<STAGE> {         // the segment is the stream
     uint8_t* out;                               // the segment's plane
-    uint32_t unit = 0xFFFFFFFFu;                // which STAGE bytes of the input the stage holds
-    int ln;
 
-    // the stage holds the unit of byte `at` of `in` (the host has bounded a frame's length so that none of this wraps, rle_check).
-    // A refill waits for its own load: loading the next unit a refill ahead into registers was tried, with a clipped and with an
-    // unconditional load, and was slower both times (1.17 -> 1.43 ms on the 512 x 512 study of tools/rle_frames_bench.py).
-    __device__ void fill(uint32_t at)
-    {
-        if (at / STAGE == unit) return;
-        unit = at / STAGE;
-        __syncthreads();                                                      // (a block is one wave: this orders the wave's LDS traffic)
-        const uint32_t piece = unit * STAGE + (uint32_t)ln * 16;              // this lane's 16 bytes, from `in`
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (piece < skew + in_len) v = *(const uint4*)(in + piece);
-        *(uint4*)(stage + ln * 16) = v;
-        __syncthreads();
-    }
     __device__ uint8_t in_byte(uint32_t i)
     {
         const uint32_t at = i + skew;
@@ -49,9 +31,9 @@ struct WaveIO {
     }
     __device__ void literal(uint32_t pos, uint32_t made, uint32_t cnt)
     {
-        while (cnt) {                                                         // piece by piece of what one stage holds
+        while (cnt) {
             const uint32_t at = pos + skew;
-            uint32_t m = STAGE - at % STAGE;
+            uint32_t m = within(at);
             if (m > cnt) m = cnt;
             fill(at);                                                         // the stage holds [pos, pos + m)
             for (uint32_t k = (uint32_t)ln; k < m; k += 64) out[made + k] = stage[(at + k) % STAGE];

@@ -53,9 +53,7 @@ int wase_study_tail(tf_handle* h, const Study& s, const float* dflow, bool hold)
     }
     if (s.background_out) HIPC(h, hipMemcpyAsync(s.background_out, wbg, (size_t)P * sizeof(float), hipMemcpyDeviceToHost, stream));
     HIPC(h, hipStreamSynchronize(stream));
-    float t = 0;
-    HIPC(h, hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-    h->wase_kernel_ms = t;
+    HIPC(h, dev_time(h, 0, 1, tf_handle::DT_WASE, false));
     return TF_OK;
 }
 

@@ -294,6 +294,12 @@ class DenseFlow:
         copied to the host; calc_study_held and study_chunks add nothing), tail_upload_bytes."""
         return int(self._L.tf_dbg_counter(self._h, name.encode()))
 
+    def _raise_unless_verdict(self, rc, status, fn):
+        """inflate's and rle_decode's rule: a code other than TF_OK beside all-zero statuses is no verdict on a stream or a frame -- the
+        call itself failed, and raises; with a status set, the statuses are the answer."""
+        if rc != _lib.TF_OK and not status.any():
+            _lib.check(rc, self._h, fn)
+
     def _finish(self, st, chain_pairs=None):
         self.last_stats = st.as_dict()
         self._last_chain_pairs = chain_pairs               # a lock-step call: the pairs of each chain, in the caller's order
@@ -495,8 +501,7 @@ class DenseFlow:
         out = np.zeros((N, H, W) if samples == 1 else (N, H, W, samples), np.uint8)
         status = np.zeros(N, np.int32)
         rc = self._L.tf_rle_decode(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, out.ctypes.data, status.ctypes.data)
-        if rc != _lib.TF_OK and not status.any():            # not a verdict on a frame: the call itself failed
-            _lib.check(rc, self._h, "tf_rle_decode")
+        self._raise_unless_verdict(rc, status, "tf_rle_decode")
         return out, status
 
     def hold_frames_rle(self, record, H, W, samples, form="RGB", flip=False):
@@ -1072,8 +1077,7 @@ class DenseFlow:
         offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
         blob = np.frombuffer(b"".join(streams) or b"\0", np.uint8)
         rc = self._L.tf_inflate(self._h, blob.ctypes.data, offs.ctypes.data, lens.ctypes.data, None, n, out_bytes, out.ctypes.data, status.ctypes.data)
-        if rc != _lib.TF_OK and not status.any():            # not a verdict on a stream: the call itself failed
-            _lib.check(rc, self._h, "tf_inflate")
+        self._raise_unless_verdict(rc, status, "tf_inflate")
         return out, status
 
     @staticmethod

@@ -241,7 +241,7 @@ def write_corpus(path):
 
 # ---- the GPU cases (tests/test_gpu_rle.py runs `python -m tests.rle_cases` once, under a time limit; here every case has its own: a
 # watchdog ends the process when a case is not done in CASE_SECONDS, whatever the main thread waits for) ----------------------------------
-GPU_CASES = ["decode_corpus", "hold_equals_ingest", "study_call_and_otsu", "failed_hold_keeps_frames", "refusals"]
+GPU_CASES = ["decode_corpus", "hold_equals_ingest", "study_call_and_otsu", "failed_hold_keeps_frames", "refusals", "junk_in_front"]
 CASE_SECONDS = 60
 
 
@@ -349,6 +349,31 @@ def _case_refusals(pkg, e):
         except OpticalFlowCalculationError:
             pass
     assert L.tf_abi_version() == 2
+
+
+def _case_junk_in_front(pkg, e):
+    """Three frames of the stage walk (k = T - 1, T, T + 1 no-ops: a refill is crossed) behind g junk bytes, g = 0 .. 15, as a file's
+    pixel data has its frames at an unaligned offset: the span's first byte sits at every offset mod 16 of the blob, and the call
+    gives the bits and statuses of g = 0 and uploads the frames' span, not the junk"""
+    walk, want = _stage_walk(), expected()
+    cases = [walk[k] for k in (T - 1, T, T + 1)]
+    blob, off, ln = _record(cases)
+    first = None
+    for g in range(16):
+        rec = (np.concatenate([np.full(g, 0x3C, np.uint8), blob]), off + np.uint64(g), ln)
+        up = e.counter("frames_upload_bytes")
+        got, status = e.rle_decode(rec, 2, 100, 1)
+        assert e.counter("frames_upload_bytes") - up == blob.size, g
+        if first is None:
+            first = got, status
+            assert not status.any() and all(np.array_equal(got[i], want[c.name][0]) for i, c in enumerate(cases))
+        assert np.array_equal(got, first[0]) and np.array_equal(status, first[1]), g
+    g = 11
+    rec = (np.concatenate([np.full(g, 0x3C, np.uint8), blob]), off + np.uint64(g), ln)
+    up = e.counter("frames_upload_bytes")
+    tok = e.hold_frames_rle(rec, 2, 100, 1, "GRAY", True)
+    assert tok.shape == (3, 2, 100, 3) and e.counter("frames_upload_bytes") - up == blob.size
+    assert np.array_equal(e.download_frames(), F.ingest_host(first[0], "GRAY", True))
 
 
 if __name__ == "__main__":

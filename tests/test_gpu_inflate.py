@@ -107,6 +107,32 @@ def test_a_mixed_call_reports_the_first_bad_stream_and_keeps_the_good_ones(eng):
     assert all(out2[k].tobytes() == plain for k in (0, 1, 3)) and np.array_equal(out2[2], _pattern(1, 259)[0])
 
 
+def test_junk_in_front_of_the_streams_changes_nothing_at_any_alignment(eng):
+    """Four streams of the 259-byte group, good and bad side by side, behind g junk bytes, g = 0 .. 15: the span's first byte sits at
+    every offset mod 16 of the blob, and the call gives the bits and statuses of g = 0 and uploads the streams' span, not the junk."""
+    cs, vs = IC.cases(), IC.verdicts()
+    idx = _groups()[259]
+    take = [idx[(k * 5 + 4) % len(idx)] for k in range(4)]
+    kinds = [vs[i][0] for i in take]
+    assert IC.GOOD in kinds and IC.BAD in kinds
+    streams = [cs[i].stream for i in take]
+    lens = np.array([len(s) for s in streams], np.uint32)
+    first = None
+    for g in range(16):
+        offs = (np.concatenate([[0], np.cumsum(lens[:-1])]) + g).astype(np.uint64)
+        blob = np.frombuffer(b"\xC3" * g + b"".join(streams), np.uint8)
+        out, status = _pattern(4, 259), np.zeros(4, np.int32)
+        c0 = eng.counter("tail_upload_bytes")
+        rc = eng._L.tf_inflate(eng._h, blob.ctypes.data, offs.ctypes.data, lens.ctypes.data, None, 4, 259, out.ctypes.data, status.ctypes.data)
+        assert rc == _lib.TF_ERR_INVALID_ARG and status.any(), (g, rc, status)          # (the verdict on the bad ones)
+        assert eng.counter("tail_upload_bytes") - c0 == int(lens.sum()), g
+        if first is None:
+            first = out.copy(), status.copy()
+            for k, i in enumerate(take):
+                assert IC.check(cs[i], vs[i][0], vs[i][1], int(status[k]), out[k].tobytes()) is None, cs[i].name
+        assert np.array_equal(out, first[0]) and np.array_equal(status, first[1]), g
+
+
 def test_python_form_returns_zeros_behind_a_failed_stream(eng):
     cs, vs = IC.cases(), IC.verdicts()
     idx = _groups()[4099]

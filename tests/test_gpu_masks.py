@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from tee_optical_flow_amd import analysis, masks
-from tests.labelling_cases import stress_frames
+from tests.labelling_cases import corner_diagonals, load_fuzzer, stress_frames
 from tests.test_masks_cpu import _Cfg, fixture_cases
 from tests.test_otsu_cpu import fixture_cases as otsu_fixture_cases
 
@@ -81,6 +81,47 @@ def test_calls_that_share_the_labelling_scratch_do_not_see_each_other(engine):
     assert np.array_equal(got_thr, thr) and np.array_equal(got[..., 0], ref) and np.array_equal(got[..., 1], ref)
     clean("rvio_9x37x53_min5")
     centroids(frames["staircase"])                                            # 70 x 200
+
+
+def test_stress_frames_through_the_four_connected_calls(engine):
+    """The frames made to break a tiled labeller, through the 4-connected instantiation: each frame and its 180-degree flip as a
+    2-frame class map through clean_masks (min_size 1 and 2) and, where it has both levels and H, W >= 2, as a built RGB study through
+    otsu_masks, against the scipy references of tools/fuzz_labelling.py.  The staircases and the tile-corner pixels touch only
+    diagonally: 4-connected they fall apart (min_size 2 drops every staircase pixel), 8-connected (av_centroids) they hold together.
+    tile_corners has 2 x 2 blocks on its corners, which either rule joins, so corner_diagonals() walks with the stress frames."""
+    F = load_fuzzer()
+    rng = np.random.default_rng(11)
+    built = []
+    for name, fr in {**stress_frames(), "corner_diagonals": corner_diagonals()}.items():
+        pair = np.stack([fr, fr[::-1, ::-1]])
+        cmap = pair.astype(np.uint8)
+        for min_size in (1, 2):
+            got = engine.clean_masks(cmap, [1], min_size)
+            F._same_planes(got, F.ref_clean(cmap, [1], min_size), (name, min_size))
+        if name in ("tile_corners", "staircase", "corner_diagonals"):
+            n4, n8 = F.ref_sizes(fr)[1].size - 1, len(F.ref_components(fr))
+            assert n4 > 1 and n4 >= n8 >= 1, (name, n4, n8)
+            cent, area = engine.av_centroids(pair[:, :, :, None])
+            for f in range(2):
+                (r, c), a = F.ref_centroid(pair[f])
+                assert int(area[f]) == a and tuple(cent[f]) == (r, c), (name, f)
+                if name != "tile_corners":                                    # larger than any 4-connected component
+                    assert n4 > n8 and a > F.ref_sizes(pair[f])[1][1:].max(), (name, n4, n8, a)
+        if name in ("staircase", "corner_diagonals"):
+            assert F.ref_clean(cmap, [1], 1)[0, 1].sum() == fr.sum() and not F.ref_clean(cmap, [1], 2)[0, 1].any()
+        if min(fr.shape) < 2:
+            continue
+        frames = [F.build_rgb(rng, m) for m in pair]
+        if any(f is None for f in frames):
+            continue
+        built.append(name)
+        rgb = np.stack(frames)
+        for min_size in (1, 2):
+            got, thr = engine.otsu_masks(rgb, min_size, return_thresholds=True)
+            assert all(F.between_levels(rgb[f], pair[f], thr[f]) for f in range(2)), (name, thr)
+            F._same_planes(got.copy(), F.ref_otsu(pair, min_size), (name, "otsu", min_size))
+    assert built == ["single_pixel", "checkerboard", "snake", "staircase", "tile_corners", "random_17x65", "random_129x63", "random_100x257",
+                     "corner_diagonals"]
 
 
 @pytest.mark.parametrize("N,H,W,mode,min_size", [

@@ -9,7 +9,7 @@ import pytest
 from scipy import ndimage
 
 from tee_optical_flow_amd import analysis as A
-from tests.labelling_cases import stress_frames
+from tests.labelling_cases import load_fuzzer, stress_frames, twins
 
 pytestmark = pytest.mark.gpu
 
@@ -136,6 +136,27 @@ def test_labelling_stress_equals_scipy(engine):
                     assert area[f] == want[1] == host[1], (j, f, area[f], want[1])
                     assert tuple(cent[f]) == host[0], (j, f)
                     np.testing.assert_allclose(cent[f], want[0], rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize("seed,H,W,down_left", [((1, 0), 12, 40, False), ((5, 1), 40, 150, False), ((3, 2), 33, 130, True)])
+def test_equal_largest_areas_pick_the_earliest_first_pixel(engine, seed, H, W, down_left):
+    """k_cent_pick's tie rule on frames whose two largest components are copies of one blob: inside one tile, with first pixels in
+    different tiles, and with the later copy lower and further left, so that it has the smaller column centroid.  Exact."""
+    F = load_fuzzer()
+    m = twins(np.random.default_rng(seed), H, W, down_left=down_left)
+    t = F.ref_components(m)
+    first, later = sorted((r for r in t.tolist() if r[0] == t[:, 0].max()), key=lambda r: r[1])[:2]
+    assert first[0] == later[0] > 1 and first[1] < later[1]
+    tile = lambda r: (r[1] // W // 16, r[1] % W // 64)
+    assert (tile(first) != tile(later)) == (H > 16)
+    assert (later[3] / later[0] < first[3] / first[0]) == down_left
+    want = ((first[2] / first[0], first[3] / first[0]), first[0])
+    assert F.ref_centroid(m) == want == A._largest_component(m)
+    for frames in (m[None, :, :, None], np.stack([m, m[::-1, ::-1], m])[..., None]):          # alone, and between other frames
+        cent, area = engine.av_centroids(frames)
+        for f in range(frames.shape[0]):
+            (r, c), a = F.ref_centroid(frames[f, :, :, 0])
+            assert int(area[f]) == a and float(cent[f, 0]) == r and float(cent[f, 1]) == c, (f, area[f], tuple(cent[f]), a, (r, c))
 
 
 def test_beside_a_submitted_study(z):

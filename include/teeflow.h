@@ -754,7 +754,10 @@ int tf_device_count(void);
  *      with the oracle bit for bit; not part of the drop-in surface) -------------------------------- */
 /* implementation knobs for experiments (results never change).  DualTVL1: "iter_variant" (0 = 64x16 tiles, 1 = full-width row strips,
  * 2 = row strips with two iterations per launch [default]), "min_rows_work" (rows*pairs below which tiles are used), "strip_blocks" (target
- * blocks per tvl1_iter launch of a sub-batch above 1024 pairs), "max_strip_width" (widest level the row strips take), "warp_margin" (pixels of flow the
+ * blocks per tvl1_iter launch of a sub-batch above 1024 pairs), "strip_test_slots" (tests: >= 1 = the resident-block count the two-iteration
+ * row strips of a sub-batch of at most 1024 pairs are sized for on the device is taken to be this, whatever the device and "lane_slots_pct"
+ * say, which picks the strip layout; 0 = off [default]; clamped to [0, 2^20]), "lane_slots_pct" (per cent of the resident blocks a queue lane
+ * sizes those strips for, default 67), "max_strip_width" (widest level the row strips take), "warp_margin" (pixels of flow the
  * LDS-staged warp covers around its tile: 0 = global gathers only, default 8).  DeepFlow: "sor_rt" (0 = one colour per launch, the plain form),
  * "sor_fuse" (sweeps per launch of the tiled register kernel), "sor_rt_shape" (region shape; 3 = chosen per launch), "sor_coop" (1 = all sweeps
  * of a fixed-point iteration in one launch of co-resident regions where a level needs several [default], 2 = always 128x64 regions, 3 = always
@@ -816,6 +819,20 @@ int tf_dbg_median(tf_handle* h, const float* src, int w, int hgt, int ksize, flo
 int tf_dbg_iterate(tf_handle* h, const float* I1wx, const float* I1wy, const float* rho_c,
                    float* u1, float* u2, float* p11, float* p12, float* p21, float* p22,
                    int w, int hgt, int nsteps, int p_is_zero, unsigned long long* err_q);
+/* One (level, warp) stage of a DualTVL1 solve without its warp, for B pairs (1 <= B <= 4096) on the caller's planes: the stage loop a
+ * solve runs (medians every `inner` iterations, the tvl1_iter launches in the handle's current form and strip layout, the active-pair
+ * reports that end the stage early) and the stage's end (iteration counts, ping-pong bookkeeping).  I1wx, I1wy, rho_c: float32
+ * [B][hgt][w]; u1 .. p22: float32 [B][hgt][w], updated in place -- every pair's state as the stage leaves it, read from the ping-pong
+ * half the pair's control word names.  ksize: 0 (no median), 3 or 5.  thr: the stage's threshold epsilon^2 * w * hgt as float32 (the
+ * CUDA variant compares with the same value as a double); thr < 0: no pair ever stops.  variant: TF_VARIANT_CPU or TF_VARIANT_CUDA
+ * (the latter needs an even inner * outer and has no median).  p_is_zero: the stage starts from p == 0 (a level's first warp).
+ * err_q: uint64 [B][inner * outer + 1], the exact error sums of the iterations a pair executed (an overshot iteration's too), 0
+ * elsewhere; iters: int32 [B][2] = (inner iterations, outer iterations) executed.  lambda, theta, tau are the handle's.  A bad
+ * argument is TF_ERR_INVALID_ARG before any GPU work. */
+int tf_dbg_stage(tf_handle* h, const float* I1wx, const float* I1wy, const float* rho_c,
+                 float* u1, float* u2, float* p11, float* p12, float* p21, float* p22,
+                 int B, int w, int hgt, int inner, int outer, int ksize, float thr, int variant, int p_is_zero,
+                 unsigned long long* err_q, int* iters);
 
 #ifdef __cplusplus
 }

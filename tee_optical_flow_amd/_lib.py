@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "tf_get_param", "tf_set_stream", "tf_set_profile", "tf_calc_pair", "tf_calc_seq", "tf_calc_pairs", "tf_calc_pair_f32", "tf_calc_pairs_f32",
     "tf_calc_pairs_init", "tf_calc_pairs_init_device", "tf_chain_next", "tf_calc_pairs_device", "tf_calc_seq_device", "tf_submit_pairs_device", "tf_submit_seq_device", "tf_submit_pairs", "tf_submit_seq", "tf_submit_seq_rgb", "tf_wait", "tf_condition_frames", "tf_calc_seq_rgb", "tf_saliency_frames", "tf_saliency_frames_f32", "tf_calc_seq_saliency", "tf_calc_seq_saliency_f32", "tf_clean_masks", "tf_otsu_masks", "tf_segmentor_input", "tf_segmentor_classmap", "tf_av_centroids", "tf_first_region_areas", "tf_radlong_project", "tf_radlong_project_param", "tf_polar_project_param", "tf_radlong_hist", "tf_radlong_select", "tf_radlong_overlay", "tf_radlong_shape", "tf_get_iters", "tf_last_error",
     "tf_set_tuning", "tf_dbg_counter", "tf_default_deepflow_params", "tf_create_deepflow", "tf_dbg_df_refine", "tf_dbg_df_blur", "tf_dbg_launch_profile", "tf_dbg_strip_rule", "tf_wase_compensate", "tf_wase_compensate_device", "tf_host_alloc", "tf_host_free",
-    "tf_dbg_pyramid", "tf_dbg_resize", "tf_dbg_warp", "tf_dbg_median", "tf_dbg_iterate", "tf_dbg_df_pyramid", "tf_dbg_df_up",
+    "tf_dbg_pyramid", "tf_dbg_resize", "tf_dbg_warp", "tf_dbg_median", "tf_dbg_iterate", "tf_dbg_stage", "tf_dbg_df_pyramid", "tf_dbg_df_up",
     "tf_calc_seq_rgb_f16", "tf_submit_seq_rgb_f16", "tf_calc_seq_saliency_f16", "tf_echo_frames", "tf_dbg_f16_round", "tf_dbg_luma_stats",
     "tf_calc_seq_rgb_wase", "tf_calc_seq_saliency_wase",
     "tf_calc_chains", "tf_calc_chains_device", "tf_calc_chains_rgb", "tf_dbg_chain_order",
@@ -210,6 +210,7 @@ def load():
     L.tf_dbg_warp.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.tf_dbg_median.argtypes = [vp, vp, i32, i32, i32, vp]
     L.tf_dbg_iterate.argtypes = [vp] + [vp] * 9 + [i32, i32, i32, i32, vp]
+    L.tf_dbg_stage.argtypes = [vp] + [vp] * 9 + [i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]
     L.tf_comm_unique_id.argtypes = [vp]
     L.tf_comm_init_rank.argtypes = [vp, i32, i32, vp]
     L.tf_comm_init_all.argtypes = [C.POINTER(vp), i32]

@@ -187,6 +187,7 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
     else if (n == "strip_blocks") h->strip_blocks = value > 0 ? value : 2048;
     else if (n == "min_rows_work") h->min_rows_work = value;
     else if (n == "lane_slots_pct") h->lane_slots_pct = value;
+    else if (n == "strip_test_slots") h->strip_test_slots = value < 0 ? 0 : (value > (1 << 20) ? (1 << 20) : value);
     else if (n == "sor_rt") h->sor_rt = value ? 1 : 0;
     else if (n == "sor_rt_shape") h->sor_rt_shape = value;
     else if (n == "sor_plain_div") h->sor_plain_div = value ? 1 : 0;

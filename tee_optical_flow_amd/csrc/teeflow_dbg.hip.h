@@ -329,3 +329,73 @@ TF_API int tf_dbg_iterate(tf_handle* h, const float* I1wx, const float* I1wy, co
         if ((rc = dbg_down(h, hostp[k], s[2 * k + cur].p, g))) return rc;
     return TF_OK;
 }
+
+// One (level, warp) stage without its warp, for B pairs on the caller's planes: run_stage_loop (teeflow_tvl1_host.hip.h), the loop a
+// solve runs -- medians, tvl1_iter launches in the engine's current form, the active-pair reports that end the stage early -- and
+// k_stage_end.  Pair b's planes sit at b * splane of the geometry, as in a solve; its state comes back from the ping-pong halves its
+// PairCtl names after k_stage_end.
+TF_API int tf_dbg_stage(tf_handle* h, const float* I1wx, const float* I1wy, const float* rho_c,
+                        float* u1, float* u2, float* p11, float* p12, float* p21, float* p22,
+                        int B, int w, int hgt, int inner, int outer, int ksize, float thr, int variant, int p_is_zero,
+                        unsigned long long* err_q, int* iters)
+{
+    if (!h || !I1wx || !I1wy || !rho_c || !u1 || !u2 || !p11 || !p12 || !p21 || !p22 || !err_q || !iters) return TF_ERR_INVALID_ARG;
+    if (B < 1 || B > 4096) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_stage: B must be in [1,4096], got %d", B);
+    if (w < 1 || hgt < 1 || inner < 1 || outer < 1 || (long long)inner * outer > 100000)
+        return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_stage: bad size %d x %d or iteration counts %d / %d", w, hgt, inner, outer);
+    if (ksize != 0 && ksize != 3 && ksize != 5) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_stage: ksize must be 0, 3 or 5, got %d", ksize);
+    if (variant != TF_VARIANT_CPU && variant != TF_VARIANT_CUDA) return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_stage: variant must be 0 or 1, got %d", variant);
+    if (variant == TF_VARIANT_CUDA && (inner * outer) % 2 != 0)
+        return fail(h, TF_ERR_INVALID_ARG, "tf_dbg_stage: TF_VARIANT_CUDA needs an even iteration count (inner*outer), got %d", inner * outer);
+    HIPC(h, hipSetDevice(h->dev));
+    const Geom g = make_geom(w, hgt);
+    const int total = inner * outer, errstride = total + 1;
+    const size_t pl = (size_t)B * (size_t)g.splane * sizeof(float), rowb = (size_t)w * 4, pitchb = (size_t)g.pitch * 4;
+    DBuf cst[3], st[12];
+    // [B][h][w] -> B planes of h pitched rows, one after the other (splane == pitch * h); the padding and the second halves are zero
+    const auto up = [&](DBuf& d, const float* src) -> int {
+        HIPC(h, hipMalloc(&d.p, pl));
+        HIPC(h, hipMemsetAsync(d.p, 0, pl, h->stream));
+        if (src) HIPC(h, hipMemcpy2DAsync(d.p, pitchb, src, rowb, rowb, (size_t)B * hgt, hipMemcpyHostToDevice, h->stream));
+        return TF_OK;
+    };
+    const float* hostc[3] = {I1wx, I1wy, rho_c};
+    float* hostp[6] = {u1, u2, p11, p12, p21, p22};
+    int rc;
+    for (int k = 0; k < 3; ++k) if ((rc = up(cst[k], hostc[k]))) return rc;
+    for (int k = 0; k < 6; ++k) if ((rc = up(st[2 * k], hostp[k])) || (rc = up(st[2 * k + 1], nullptr))) return rc;
+    DevBuf<PairCtl> ctl; DevBuf<u64> errs; DevBuf<int> dit;
+    HIPC(h, hipMalloc(&ctl.p, (size_t)B * sizeof(PairCtl)));
+    HIPC(h, hipMemsetAsync(ctl.p, 0, (size_t)B * sizeof(PairCtl), h->stream));
+    HIPC(h, hipMalloc(&errs.p, (size_t)B * errstride * sizeof(u64)));
+    HIPC(h, hipMalloc(&dit.p, (size_t)B * 2 * sizeof(int)));
+
+    StageRun r;
+    r.wx = cst[0].p; r.wy = cst[1].p; r.rho = cst[2].p;
+    for (int k = 0; k < 2; ++k) {
+        r.sb.u1[k] = st[0 + k].p; r.sb.u2[k] = st[2 + k].p; r.sb.p11[k] = st[4 + k].p;
+        r.sb.p12[k] = st[6 + k].p; r.sb.p21[k] = st[8 + k].p; r.sb.p22[k] = st[10 + k].p;
+    }
+    r.ctl = ctl.p; r.errs = errs.p; r.errstride = errstride; r.iters_dev = dit.p; r.g = g;
+    r.inner = inner; r.total = total; r.ksize = ksize; r.variant = variant;
+    r.thr_f = thr; r.thr_d = (double)thr;
+    r.l_t = (float)(h->P.lambda * h->P.theta); r.theta = (float)h->P.theta; r.taut = (float)(h->P.tau / h->P.theta);
+    r.pzero = p_is_zero ? 1 : 0;
+    r.l = 0; r.wi = 0; r.nlev = 1; r.warps = 1;
+    if ((rc = run_stage_loop(h, r, B))) return rc;
+
+    std::vector<PairCtl> hc((size_t)B);
+    hipError_t e = hipMemcpyAsync(hc.data(), ctl.p, (size_t)B * sizeof(PairCtl), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(err_q, errs.p, (size_t)B * errstride * sizeof(u64), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(iters, dit.p, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, TF_ERR_HIP, "tf_dbg_stage: %s", hipGetErrorString(e));
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < 6; ++k) {
+            const int half = (k < 2 ? hc[b].ubase : hc[b].pbase) & 1;
+            HIPC(h, hipMemcpy2DAsync(hostp[k] + (size_t)b * hgt * w, rowb, st[2 * k + half].p + (size_t)b * g.splane, pitchb, rowb, hgt,
+                                     hipMemcpyDeviceToHost, h->stream));
+        }
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return TF_OK;
+}

@@ -76,6 +76,8 @@ struct TfKnobs {
                                  // lane that cuts its level into one round of ALL resident blocks pays the 3 halo + 2 RY fill rows of short strips for
                                  // parallelism the other lanes already provide (queue form, 384 pairs per call: 100 % 2728-2745, 67 % 2769-2772,
                                  // 50 % 2767-2769, 33 % 2706-2711 pairs/s on one box)
+    int strip_test_slots = 0;    // tests: >= 1 = pretend the resident-block count k_iter2_rows sizes its strips for is this (after lane_slots_pct's
+                                 // scaling), so that a test chooses the strip layout (R, S); 0 = the occupancy query's answer
     int coop_test_occ16 = -1, coop_test_occ8 = -1;   // tests: pretend the occupancy query answered this
     int coop_test_mute = 0;      // tests: block 0 of every co-resident launch never raises its flag -> its neighbours give up -> the call is repeated tiled
     int profile = 0;

@@ -151,6 +151,7 @@ void launch_iter(Engine* h, const Iter2Args& A, int step, int B, hipStream_t s)
         }
         int slots = f->second;
         if (h->slots_pct > 0 && h->slots_pct < 100) slots = slots * h->slots_pct / 100;
+        if (h->strip_test_slots >= 1) slots = h->strip_test_slots;
         int items = 1;
         for (int n = 1; n <= B; ++n) {
             int r, sn;
@@ -206,34 +207,42 @@ int read_reports(Engine* h, hipStream_t s, unsigned q, unsigned* checked, bool* 
     return TF_OK;
 }
 
-// one (level, warp) stage for pairs [0,B); pair b's executed iteration counts go to iters_dev[b] (a chain step's pair: its own slice)
-int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_dev)
-{
-    const tf_params& P = h->P;
-    const Geom g = h->tv.lv[l];
-    const int inner = P.inner_iterations, total = P.inner_iterations * P.outer_iterations;
-    const float thr_f = (float)(P.epsilon * P.epsilon * (double)(g.w * g.h));
-    const double thr_q = (double)thr_f * 1073741824.0;
-    const double thr_d = P.epsilon * P.epsilon * (double)(g.w * g.h);     // TF_VARIANT_CUDA compares in double
-    hipStream_t s = h->stream;
+// What the iteration loop of one (level, warp) stage works on and is told: run_stage fills it from the engine's buffers and parameters,
+// tf_dbg_stage (teeflow_dbg.hip.h) from a caller's planes, so that the hook runs the loop a solve runs.
+struct StageRun {
+    const float *wx, *wy, *rho;          // the stage's warp constants, pair b at b * g.splane
+    StateBufs sb; PairCtl* ctl;          // the ping-pong state and which half of it holds pair b
+    u64* errs; int errstride;            // error slots, errstride >= inner * outer per pair; the loop clears them
+    int* iters_dev;                      // k_stage_end files (n_it, n_out) of pair b at [b][nlev][warps][2], entry (l, wi)
+    Geom g;
+    int inner, total;                    // iterations between two medians; inner * outer
+    int ksize;                           // medianFiltering: 3 or 5, anything else = none
+    int variant;
+    float thr_f; double thr_d;           // the stage's threshold as the CPU class keeps it (float) and as the CUDA class does (double)
+    float l_t, theta, taut;
+    int pzero;                           // the stage starts from p == 0: its first launch does not read the dual planes
+    int l, wi, nlev, warps;
+};
 
-    WarpArgs wa;
-    wa.pyr = h->tv.pyr[l]; wa.off0 = off0; wa.off1 = off1; wa.sb = h->tv.sb; wa.ctl = h->tv.ctl; wa.tab = h->tv.tab;
-    wa.wx = h->tv.cwx; wa.wy = h->tv.cwy; wa.rho = h->tv.crho; wa.g = g;
-    int rc = profiled(h, s, -4, 0, 0, [&] { launch_warp(h, wa, B, s, h->tv.gxl[l], h->tv.gyl[l]); });
-    if (rc) return rc;
-    HIPC(h, hipMemsetAsync(h->tv.errs, 0, (size_t)B * h->tv.errstride * sizeof(u64), s));
+// the iteration loop of one stage for pairs [0,B): medians, tvl1_iter launches, the active-pair reports that end it early, k_stage_end
+int run_stage_loop(Engine* h, const StageRun& r, int B)
+{
+    const Geom g = r.g;
+    const int inner = r.inner, total = r.total;
+    const double thr_q = (double)r.thr_f * 1073741824.0;
+    hipStream_t s = h->stream;
+    HIPC(h, hipMemsetAsync(r.errs, 0, (size_t)B * r.errstride * sizeof(u64), s));
 
     Iter2Args A;
     IterArgs& ia = A.a;
-    ia.wx = h->tv.cwx; ia.wy = h->tv.cwy; ia.rho = h->tv.crho; ia.sb = h->tv.sb; ia.ctl = h->tv.ctl; ia.err = h->tv.errs;
-    ia.errstride = h->tv.errstride; ia.thr_q = thr_q; ia.g = g;
-    ia.l_t = (float)(P.lambda * P.theta); ia.theta = (float)P.theta; ia.taut = (float)(P.tau / P.theta);
-    ia.variant = P.variant; ia.thr_d = thr_d;
-    const bool cuda_variant = P.variant == TF_VARIANT_CUDA;      // one loop, no median, stops only after odd iterations
-    const bool median = P.median_filtering > 1 && !cuda_variant;
+    ia.wx = r.wx; ia.wy = r.wy; ia.rho = r.rho; ia.sb = r.sb; ia.ctl = r.ctl; ia.err = r.errs;
+    ia.errstride = r.errstride; ia.thr_q = thr_q; ia.g = g;
+    ia.l_t = r.l_t; ia.theta = r.theta; ia.taut = r.taut;
+    ia.variant = r.variant; ia.thr_d = r.thr_d;
+    const bool cuda_variant = r.variant == TF_VARIANT_CUDA;      // one loop, no median, stops only after odd iterations
+    const bool median = r.ksize > 1 && !cuda_variant;
     MedArgs ma;
-    ma.sb = h->tv.sb; ma.ctl = h->tv.ctl; ma.err = h->tv.errs; ma.errstride = h->tv.errstride; ma.thr_q = thr_q; ma.g = g;
+    ma.sb = r.sb; ma.ctl = r.ctl; ma.err = r.errs; ma.errstride = r.errstride; ma.thr_q = thr_q; ma.g = g;
 
     const dim3 gm((g.w + 63) / 64, (g.h + 15) / 16, 2 * B);
     ia.B = B;
@@ -248,8 +257,8 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_de
     for (int it = 0; it < total + step - 1 && !stop; it += step) {
         if (it < total && it % inner == 0 && median) {
             ma.it = it; ma.utog = utog;
-            rc = profiled(h, s, -5, 0, 0, [&] {
-                if (P.median_filtering == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
+            int rc = profiled(h, s, -5, 0, 0, [&] {
+                if (r.ksize == 5) hipLaunchKernelGGL(k_median<5>, gm, dim3(256), 0, s, ma);
                 else hipLaunchKernelGGL(k_median<3>, gm, dim3(256), 0, s, ma);
             });
             if (rc) return rc;
@@ -258,8 +267,8 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_de
         const unsigned q = h->tv.launch_seq++;
         h->tv.slots_host[q % SLOT_RING] = -1;
         ia.host_slot = h->tv.slots_dev + q % SLOT_RING;
-        ia.it = it; ia.utog = utog; ia.ptog = ptog; ia.pzero = (wi == 0 && it == 0) ? 1 : 0;
-        rc = profiled(h, s, l, wi, it, [&] { launch_iter(h, A, step, B, s); });
+        ia.it = it; ia.utog = utog; ia.ptog = ptog; ia.pzero = (r.pzero && it == 0) ? 1 : 0;
+        int rc = profiled(h, s, r.l, r.wi, it, [&] { launch_iter(h, A, step, B, s); });
         if (rc) return rc;
         ++h->tally.iter_launches;
         A.utog_prev = utog; A.ptog_prev = ptog; A.pzero_prev = ia.pzero;
@@ -267,9 +276,36 @@ int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_de
         rc = read_reports(h, s, q, &checked, &stop);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, h->tv.errs, h->tv.errstride, h->tv.ctl, iters_dev, B,
-                       total, inner, median ? 1 : 0, thr_q, l, wi, h->tv.nlev, P.warps, P.variant, thr_d, step);
+    hipLaunchKernelGGL(k_stage_end, dim3((B + 255) / 256), dim3(256), 0, s, r.errs, r.errstride, r.ctl, r.iters_dev, B,
+                       total, inner, median ? 1 : 0, thr_q, r.l, r.wi, r.nlev, r.warps, r.variant, r.thr_d, step);
     return TF_OK;
+}
+
+// one (level, warp) stage for pairs [0,B): the warp, then the loop; pair b's executed iteration counts go to iters_dev[b] (a chain
+// step's pair: its own slice)
+int run_stage(Engine* h, int l, int wi, int B, int off0, int off1, int* iters_dev)
+{
+    const tf_params& P = h->P;
+    const Geom g = h->tv.lv[l];
+    hipStream_t s = h->stream;
+
+    WarpArgs wa;
+    wa.pyr = h->tv.pyr[l]; wa.off0 = off0; wa.off1 = off1; wa.sb = h->tv.sb; wa.ctl = h->tv.ctl; wa.tab = h->tv.tab;
+    wa.wx = h->tv.cwx; wa.wy = h->tv.cwy; wa.rho = h->tv.crho; wa.g = g;
+    int rc = profiled(h, s, -4, 0, 0, [&] { launch_warp(h, wa, B, s, h->tv.gxl[l], h->tv.gyl[l]); });
+    if (rc) return rc;
+
+    StageRun r;
+    r.wx = h->tv.cwx; r.wy = h->tv.cwy; r.rho = h->tv.crho; r.sb = h->tv.sb; r.ctl = h->tv.ctl;
+    r.errs = h->tv.errs; r.errstride = h->tv.errstride; r.iters_dev = iters_dev; r.g = g;
+    r.inner = P.inner_iterations; r.total = P.inner_iterations * P.outer_iterations;
+    r.ksize = P.median_filtering; r.variant = P.variant;
+    r.thr_f = (float)(P.epsilon * P.epsilon * (double)(g.w * g.h));
+    r.thr_d = P.epsilon * P.epsilon * (double)(g.w * g.h);     // TF_VARIANT_CUDA compares in double
+    r.l_t = (float)(P.lambda * P.theta); r.theta = (float)P.theta; r.taut = (float)(P.tau / P.theta);
+    r.pzero = wi == 0 ? 1 : 0;
+    r.l = l; r.wi = wi; r.nlev = h->tv.nlev; r.warps = P.warps;
+    return run_stage_loop(h, r, B);
 }
 
 // level 0 of F frame slots -> the levels below it (and, TF_VARIANT_CUDA, the gradients)

@@ -94,7 +94,8 @@ def test_median_bit_exact(engine, oracle, shape, ksize, step):
     assert np.array_equal(out, ref)
 
 
-@pytest.mark.parametrize("shape", [(64, 64), (97, 131), (210, 210), (15, 60), (16, 61), (31, 121), (512, 512), (3, 1021)])
+@pytest.mark.parametrize("shape", [(64, 64), (97, 131), (210, 210), (15, 60), (16, 61), (31, 121), (512, 512), (3, 1021),
+                                   (5, 1100), (4, 2048)])          # 320- and 512-thread row blocks
 @pytest.mark.parametrize("pzero", [0, 1])
 @pytest.mark.parametrize("variant", [0, 1, 2, 3])
 def test_iterate_bit_exact(engine, oracle, shape, pzero, variant):

@@ -1,4 +1,4 @@
-// teeflow_tvl1_iter.hip.h -- DualTVL1's inner iteration: the stop rules, the exact-arithmetic helpers (plain and packed), the four
+// teeflow_tvl1_iter.hip.h -- DualTVL1's inner iteration: the stop rules, the exact-arithmetic helpers, the four
 // tvl1_iter kernels (tiles / strips, one / two iterations per launch) and the control kernels; included by teeflow_kernels.hip.h
 #pragma once
 
@@ -57,110 +57,10 @@ __device__ __forceinline__ void publish_active_count(const IterArgs& a)
 // All of them return the SAME bits as the plain C expressions in the oracle; they only drop work that the
 // generic lowering does for operand ranges that cannot occur here.  tests/test_gpu_kernels.py compares the
 // results with the oracle bit for bit.
-
-// oracle D2: (float)sqrt((double)a*a + (double)b*b).  a*a, b*b are exact in double, so fma(a,a,b*b) is the same
-// single rounding as the sum of the two products.  The square root is the Goldschmidt sequence hipcc emits for
-// sqrt(double) (correctly rounded), without its ldexp rescaling for x < 2^-767: x is 0 or >= 2^-298 here.
-__device__ __forceinline__ float hypot_exact(float a, float b)
-{
-    const double ad = (double)a, bd = (double)b;
-    const double x = __builtin_fma(ad, ad, bd * bd);
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = y * 0.5;
-    const double r = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r, g);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    g = (x == 0.0 || x == __builtin_inf()) ? x : g;
-    return (float)g;
-}
-
-// rint(x) for 0 <= x < 2^43 as uint64 (x = min(t,4096)*2^30): split at 2^32, both halves exact
-__device__ __forceinline__ u64 rint_u64(float x)
-{
-    const float v = __builtin_rintf(x);
-    const float hi = __builtin_floorf(v * 0x1p-32f);
-    const float lo = __builtin_fmaf(hi, -0x1p32f, v);
-    return ((u64)(unsigned)hi << 32) | (u64)(unsigned)lo;
-}
-
-// estimateV + divergence + estimateU for the 4 pixels of one quad.  `ytop` is uniform per row; only the first pixel of
-// the first quad (x == 0) has no left neighbour.
-struct QuadU {
-    float u1k[4], u2k[4], wx[4], wy[4], r[4];       // current flow and warp constants
-    float p11[4], p12[4], p21[4], p22[4];           // dual variable at the pixel
-    float p12u[4], p22u[4];                         // ... one row up
-    float l11, l21;                                 // ... p11/p21 of the pixel left of the quad
-};
-
-__device__ __forceinline__ void tv_u_quad(float l_t, float theta, const QuadU& q, bool ytop, bool x0, float* u1n, float* u2n)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        // estimateV, branch-free: the three cases of the thresholding step become selects (the quotient is computed
-        // in every lane and discarded where it does not apply; straight-line code lets the 4 pixels interleave)
-        const float Ix2 = q.wx[i] * q.wx[i], Iy2 = q.wy[i] * q.wy[i];
-        const float grad = Ix2 + Iy2;
-        const float rho = q.r[i] + (q.wx[i] * q.u1k[i] + q.wy[i] * q.u2k[i]);
-        const float lg = l_t * grad;
-        const bool c1 = rho < -lg, c2 = rho > lg, c3 = grad > FLT_EPSILON;
-        const float fi = -rho / grad;
-        const float k = c1 ? l_t : (c2 ? -l_t : fi);
-        const bool any = c1 || c2 || c3;
-        const float d1 = any ? k * q.wx[i] : 0.f, d2 = any ? k * q.wy[i] : 0.f;
-        const float v1 = q.u1k[i] + d1, v2 = q.u2k[i] + d2;
-        const float p11l = i == 0 ? q.l11 : q.p11[i - 1], p21l = i == 0 ? q.l21 : q.p21[i - 1];
-        // divergence: backward differences with upstream's first-row / first-column forms
-        float div1, div2;
-        if (!ytop) {
-            div1 = (q.p11[i] - p11l) + (q.p12[i] - q.p12u[i]); div2 = (q.p21[i] - p21l) + (q.p22[i] - q.p22u[i]);
-            if (i == 0) {
-                const float b1 = (q.p11[i] + q.p12[i]) - q.p12u[i], b2 = (q.p21[i] + q.p22[i]) - q.p22u[i];
-                div1 = x0 ? b1 : div1; div2 = x0 ? b2 : div2;
-            }
-        } else {
-            div1 = (q.p11[i] - p11l) + q.p12[i]; div2 = (q.p21[i] - p21l) + q.p22[i];
-            if (i == 0) {
-                const float b1 = q.p11[i] + q.p12[i], b2 = q.p21[i] + q.p22[i];
-                div1 = x0 ? b1 : div1; div2 = x0 ? b2 : div2;
-            }
-        }
-        u1n[i] = v1 + theta * div1;
-        u2n[i] = v2 + theta * div2;
-    }
-}
-
-__device__ __forceinline__ u64 tv_err_q(float u1n, float u1k, float u2n, float u2k)
-{
-    const float e1 = u1n - u1k, e2 = u2n - u2k;
-    const float t = e1 * e1 + e2 * e2;
-    return rint_u64(fminf(t, ERR_CAP_F) * ERR_SCALE_F);
-}
-
-// estimateDualVariables for the 4 pixels of a quad, both flow components.  (A hand-rolled division sharing the
-// reciprocal between the two quotients by the same 1 + taut*|grad u| was bit-exact but 15 % SLOWER: the wave vote that
-// guards its operand range splits the basic block and stops the 16 divisions from interleaving.)
-__device__ __forceinline__ void tv_p_quad(float taut, const float* u1x, const float* u1y, const float* u2x, const float* u2y,
-                                          const float* p11, const float* p12, const float* p21, const float* p22,
-                                          float* o11, float* o12, float* o21, float* o22)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float ng1 = 1.0f + taut * hypot_exact(u1x[i], u1y[i]);
-        const float ng2 = 1.0f + taut * hypot_exact(u2x[i], u2y[i]);
-        o11[i] = (p11[i] + taut * u1x[i]) / ng1; o12[i] = (p12[i] + taut * u1y[i]) / ng1;
-        o21[i] = (p21[i] + taut * u2x[i]) / ng2; o22[i] = (p22[i] + taut * u2y[i]) / ng2;
-    }
-}
-
-// ---- packed forms used by k_iter2_rows ------------------------------------------------------------------------
-// The iteration kernel is VALU-bound (non-packed fp32 issues one wave64 instruction per 4 cycles), so the pointwise part
+// The iteration kernels are VALU-bound (non-packed fp32 issues one wave64 instruction per 4 cycles), so the pointwise part
 // of the quad helpers is written on float2 values spanning two NEIGHBOURING PIXELS: they sit in adjacent registers of the
-// dwordx4 loads, so v_pk_mul/add/fma_f32 apply without shuffles.  Same operations in the same order as the scalar forms
-// above, hence the same bits.
+// dwordx4 loads, so v_pk_mul/add/fma_f32 apply without shuffles.  Each lane does the oracle's operations in the oracle's
+// order, hence the same bits.
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 mk2(float a, float b) { f2 r; r.x = a; r.y = b; return r; }
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
@@ -189,9 +89,12 @@ __device__ __forceinline__ f2 div2s(f2 a, f2 b, f2 bs, f2 rs)
     return mk2(__builtin_amdgcn_div_fixupf(q.x, b.x, a.x), __builtin_amdgcn_div_fixupf(q.y, b.y, a.y));
 }
 
-// hypot_exact without the x == inf test (a, b are floats: x <= 2^257) and with the x == 0 case folded into a clamp
-// (the smallest non-zero x is 2^-298; sqrt(2^-400) converts to 0.0f like sqrt(0))
-__device__ __forceinline__ float hypot_exact2(float a, float b)
+// oracle D2: (float)sqrt((double)a*a + (double)b*b).  a*a, b*b are exact in double, so fma(a,a,b*b) is the same
+// single rounding as the sum of the two products.  The square root is the Goldschmidt sequence hipcc emits for
+// sqrt(double) (correctly rounded), without its ldexp rescaling for x < 2^-767 (x is 0 or >= 2^-298 here), without its
+// x == inf test (a, b are floats: x <= 2^257) and with the x == 0 case folded into a clamp (sqrt(2^-400) converts to
+// 0.0f like sqrt(0)).
+__device__ __forceinline__ float hypot_exact(float a, float b)
 {
     const double ad = (double)a, bd = (double)b;
     const double x = __builtin_fmax(__builtin_fma(ad, ad, bd * bd), 0x1p-400);
@@ -207,11 +110,22 @@ __device__ __forceinline__ float hypot_exact2(float a, float b)
     return (float)g;
 }
 
+// estimateV + divergence + estimateU for the 4 pixels of one quad.  `ytop` is uniform per row; only the first pixel of
+// the first quad (x == 0) has no left neighbour.
+struct QuadU {
+    float u1k[4], u2k[4], wx[4], wy[4], r[4];       // current flow and warp constants
+    float p11[4], p12[4], p21[4], p22[4];           // dual variable at the pixel
+    float p12u[4], p22u[4];                         // ... one row up
+    float l11, l21;                                 // ... p11/p21 of the pixel left of the quad
+};
+
 // estimateV + divergence + estimateU for two neighbouring pixels; `first` = this is the pair that holds pixel x == 0 of
 // the row when x0 is set (only that pixel uses the first-column form of the divergence)
 __device__ __forceinline__ void tv_u_pair(float l_t, float theta, f2 u1k, f2 u2k, f2 wx, f2 wy, f2 rc, f2 p11, f2 p12, f2 p21,
                                           f2 p22, f2 p12u, f2 p22u, float l11, float l21, bool ytop, bool x0, f2& u1n, f2& u2n)
 {
+    // estimateV, branch-free: the three cases of the thresholding step become selects (the quotient is computed in
+    // every lane and discarded where it does not apply; straight-line code lets the pixels interleave)
     const f2 Ix2 = wx * wx, Iy2 = wy * wy;
     const f2 grad = Ix2 + Iy2;
     const f2 rho = rc + (wx * u1k + wy * u2k);
@@ -225,6 +139,7 @@ __device__ __forceinline__ void tv_u_pair(float l_t, float theta, f2 u1k, f2 u2k
     const bool anyx = c1x || c2x || c3x, anyy = c1y || c2y || c3y;
     const f2 d1 = mk2(anyx ? kd1.x : 0.f, anyy ? kd1.y : 0.f), d2 = mk2(anyx ? kd2.x : 0.f, anyy ? kd2.y : 0.f);
     const f2 v1 = u1k + d1, v2 = u2k + d2;
+    // divergence: backward differences with upstream's first-row / first-column forms
     const f2 dx1 = mk2(p11.x - l11, p11.y - p11.x), dx2 = mk2(p21.x - l21, p21.y - p21.x);
     f2 div1, div2_;
     if (!ytop) {
@@ -240,7 +155,7 @@ __device__ __forceinline__ void tv_u_pair(float l_t, float theta, f2 u1k, f2 u2k
     u2n = v2 + theta * div2_;
 }
 
-__device__ __forceinline__ void tv_u_quad_pk(float l_t, float theta, const QuadU& q, bool ytop, bool x0, float* u1n, float* u2n)
+__device__ __forceinline__ void tv_u_quad(float l_t, float theta, const QuadU& q, bool ytop, bool x0, float* u1n, float* u2n)
 {
     f2 a1, a2, b1, b2;
     tv_u_pair(l_t, theta, mk2(q.u1k[0], q.u1k[1]), mk2(q.u2k[0], q.u2k[1]), mk2(q.wx[0], q.wx[1]), mk2(q.wy[0], q.wy[1]),
@@ -254,15 +169,15 @@ __device__ __forceinline__ void tv_u_quad_pk(float l_t, float theta, const QuadU
 }
 
 // convergence terms of a quad, added to a double accumulator: every term is an integer below 2^43, so the sum is exact
-// while it stays below 2^53 (the caller folds the accumulator into a u64 every 256 steps)
+// while it stays below 2^53 (the row march folds its accumulator into a u64 every 256 steps, the other kernels per quad).
 // `keep[i]` is all-ones for a pixel that counts and 0 for one that does not (halo rows, columns >= W).  Masks, not
 // selects: a v_cndmask whose VCC was produced by the scalar unit (row predicate AND column predicate) costs ~23 cycles on
 // gfx950 against 2.5 for a v_and.
 __device__ __forceinline__ unsigned opaque_u(unsigned m) { asm volatile("" : "+v"(m)); return m; }
 __device__ __forceinline__ float mask_f(float v, unsigned m) { return __uint_as_float(__float_as_uint(v) & m); }
 
-__device__ __forceinline__ double tv_err_quad_pk(const float* u1n, const float* u1k, const float* u2n, const float* u2k,
-                                                 const unsigned* keep)
+__device__ __forceinline__ double tv_err_quad(const float* u1n, const float* u1k, const float* u2n, const float* u2k,
+                                              const unsigned* keep)
 {
     const f2 e1a = mk2(u1n[0], u1n[1]) - mk2(u1k[0], u1k[1]), e2a = mk2(u2n[0], u2n[1]) - mk2(u2k[0], u2k[1]);
     const f2 e1b = mk2(u1n[2], u1n[3]) - mk2(u1k[2], u1k[3]), e2b = mk2(u2n[2], u2n[3]) - mk2(u2k[2], u2k[3]);
@@ -277,11 +192,15 @@ __device__ __forceinline__ double tv_err_quad_pk(const float* u1n, const float* 
     return acc;
 }
 
+// estimateDualVariables for two neighbouring pixels, both flow components.  The two quotients by the same
+// 1 + taut*|grad u| share one reciprocal; div2s scales unconditionally so that this needs no guard.  (A shared-reciprocal
+// division that kept v_div_scale's operand range with a wave vote was bit-exact but 15 % SLOWER than the compiler's IEEE
+// `/`: the vote splits the basic block and stops the 16 divisions of a quad from interleaving.)
 __device__ __forceinline__ void tv_p_pair(float taut, f2 u1x, f2 u1y, f2 u2x, f2 u2y, f2 p11, f2 p12, f2 p21, f2 p22,
                                           f2& o11, f2& o12, f2& o21, f2& o22)
 {
-    const f2 g1 = mk2(hypot_exact2(u1x.x, u1y.x), hypot_exact2(u1x.y, u1y.y));
-    const f2 g2 = mk2(hypot_exact2(u2x.x, u2y.x), hypot_exact2(u2x.y, u2y.y));
+    const f2 g1 = mk2(hypot_exact(u1x.x, u1y.x), hypot_exact(u1x.y, u1y.y));
+    const f2 g2 = mk2(hypot_exact(u2x.x, u2y.x), hypot_exact(u2x.y, u2y.y));
     const f2 ng1 = 1.0f + taut * g1, ng2 = 1.0f + taut * g2;
     const f2 ns1 = ng1 * 0x1p64f, ns2 = ng2 * 0x1p64f;
     const f2 r1 = rcp2s(ns1), r2 = rcp2s(ns2);
@@ -289,9 +208,9 @@ __device__ __forceinline__ void tv_p_pair(float taut, f2 u1x, f2 u1y, f2 u2x, f2
     o21 = div2s(p21 + taut * u2x, ng2, ns2, r2); o22 = div2s(p22 + taut * u2y, ng2, ns2, r2);
 }
 
-__device__ __forceinline__ void tv_p_quad_pk(float taut, const float* u1x, const float* u1y, const float* u2x, const float* u2y,
-                                             const float* p11, const float* p12, const float* p21, const float* p22,
-                                             float* o11, float* o12, float* o21, float* o22)
+__device__ __forceinline__ void tv_p_quad(float taut, const float* u1x, const float* u1y, const float* u2x, const float* u2y,
+                                          const float* p11, const float* p12, const float* p21, const float* p22,
+                                          float* o11, float* o12, float* o21, float* o22)
 {
 #pragma unroll
     for (int h = 0; h < 4; h += 2) {
@@ -300,6 +219,20 @@ __device__ __forceinline__ void tv_p_quad_pk(float taut, const float* u1x, const
                   mk2(p11[h], p11[h + 1]), mk2(p12[h], p12[h + 1]), mk2(p21[h], p21[h + 1]), mk2(p22[h], p22[h + 1]), a, b, c, d);
         o11[h] = a.x; o11[h + 1] = a.y; o12[h] = b.x; o12[h + 1] = b.y;
         o21[h] = c.x; o21[h + 1] = c.y; o22[h] = d.x; o22[h + 1] = d.y;
+    }
+}
+
+// exact convergence sum of a block of `nwaves` waves: shuffle reduction -> one partial per wave in LDS -> one atomic per block
+__device__ __forceinline__ void block_err_add(u64 q, u64* sred, int nwaves, u64* slot)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
+    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = q;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 tot = 0;
+        for (int w = 0; w < nwaves; ++w) tot += sred[w];
+        atomicAdd(slot, tot);
     }
 }
 
@@ -342,9 +275,10 @@ __global__ __launch_bounds__(256) void k_iter(IterArgs a)
         qu.l11 = l11; qu.l21 = l21;
         UNPACK4(p11c, a11) UNPACK4(p12c, a12) UNPACK4(p21c, a21) UNPACK4(p22c, a22)
         tv_u_quad(a.l_t, a.theta, qu, y == 0, x == 0, u1n, u2n);
+        unsigned keep[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (outr && x + i < W) q += tv_err_q(u1n[i], qu.u1k[i], u2n[i], qu.u2k[i]);
+        for (int i = 0; i < 4; ++i) keep[i] = outr && x + i < W ? ~0u : 0u;
+        q += (u64)tv_err_quad(u1n, qu.u1k, u2n, qu.u2k, keep);
         st4(&su1[ty][tx * 4], make_float4(u1n[0], u1n[1], u1n[2], u1n[3]));
         st4(&su2[ty][tx * 4], make_float4(u2n[0], u2n[1], u2n[2], u2n[3]));
     }
@@ -370,15 +304,7 @@ __global__ __launch_bounds__(256) void k_iter(IterArgs a)
         st4(a.sb.p21[pc ^ 1] + row, make_float4(o21[0], o21[1], o21[2], o21[3]));
         st4(a.sb.p22[pc ^ 1] + row, make_float4(o22[0], o22[1], o22[2], o22[3]));
     }
-    // exact convergence sum: wave shuffle reduction -> 4 partials in LDS -> one atomic per block
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const u64 tot = sred[0] + sred[1] + sred[2] + sred[3];
-        atomicAdd(&errb[a.it], tot);
-    }
+    block_err_add(q, sred, 4, &errb[a.it]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -470,9 +396,10 @@ __global__ __launch_bounds__(512) void k_iter_rows(IterArgs a, int R, int QX, in
             UNPACK4(qu.p12u, up12) UNPACK4(qu.p22u, up22)
             qu.l11 = l11; qu.l21 = l21;
             tv_u_quad(a.l_t, a.theta, qu, y == 0, x == 0, u1n, u2n);
+            unsigned keep[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (is_out && x + i < W) q += tv_err_q(u1n[i], qu.u1k[i], u2n[i], qu.u2k[i]);
+            for (int i = 0; i < 4; ++i) keep[i] = is_out && x + i < W ? ~0u : 0u;
+            q += (u64)tv_err_quad(u1n, qu.u1k, u2n, qu.u2k, keep);
             st4(su1 + (cur * RY + ty) * LW + x, make_float4(u1n[0], u1n[1], u1n[2], u1n[3]));
             st4(su2 + (cur * RY + ty) * LW + x, make_float4(u2n[0], u2n[1], u2n[2], u2n[3]));
             // keep this row's old p for its deferred dual update (after the previous row's update below)
@@ -517,15 +444,7 @@ __global__ __launch_bounds__(512) void k_iter_rows(IterArgs a, int R, int QX, in
         q21[0] = a21.x; q21[1] = a21.y; q21[2] = a21.z; q21[3] = a21.w;
         q22[0] = a22.x; q22[1] = a22.y; q22[2] = a22.z; q22[3] = a22.w;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
-    if ((tid & 63) == 0) sred[tid >> 6] = q;
-    __syncthreads();
-    if (tid == 0) {
-        u64 tot = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += sred[w];
-        atomicAdd(&errb[a.it], tot);
-    }
+    block_err_add(q, sred, (int)(blockDim.x >> 6), &errb[a.it]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -791,10 +710,10 @@ __device__ __forceinline__ void iter2_rows_body(const IterArgs& a, const Iter2Bl
             UNPACK4(qu.p12u, up12) UNPACK4(qu.p22u, up22)
             qu.l11 = l11; qu.l21 = l21;
             const bool isout = y >= y0 && y <= yout_hi;
-            tv_u_quad_pk(a.l_t, a.theta, qu, y == 0, x == 0, n_u1, n_u2);
+            tv_u_quad(a.l_t, a.theta, qu, y == 0, x == 0, n_u1, n_u2);
             const unsigned mrow = opaque_u(!replay && isout ? ~0u : 0u);
             const unsigned keep[4] = {inw[0] & mrow, inw[1] & mrow, inw[2] & mrow, inw[3] & mrow};
-            accA += tv_err_quad_pk(n_u1, qu.u1k, n_u2, qu.u2k, keep);
+            accA += tv_err_quad(n_u1, qu.u1k, n_u2, qu.u2k, keep);
             st4(U1a + ((s & 1) * RY + ty) * LW + x, PACK4(n_u1));
             st4(U1b + ((s & 1) * RY + ty) * LW + x, PACK4(n_u2));
         }
@@ -829,7 +748,7 @@ __device__ __forceinline__ void iter2_rows_body(const IterArgs& a, const Iter2Bl
                 u1y[i] = mask_f(dv1[i] - s1_u1[i], mnl);          // 0 in the last row
                 u2y[i] = mask_f(dv2[i] - s1_u2[i], mnl);
             }
-            tv_p_quad_pk(a.taut, u1x, u1y, u2x, u2y, s1_11, s1_12, s1_21, s1_22, p1_11, p1_12, p1_21, p1_22);
+            tv_p_quad(a.taut, u1x, u1y, u2x, u2y, s1_11, s1_12, s1_21, s1_22, p1_11, p1_12, p1_21, p1_22);
             if (replay) {
                 if (yb >= y0 && yb <= yout_hi) {
                     const size_t prow = (size_t)yb * pitch + x;
@@ -866,10 +785,10 @@ __device__ __forceinline__ void iter2_rows_body(const IterArgs& a, const Iter2Bl
                 UNPACK4(qu.p12u, up12) UNPACK4(qu.p22u, up22)
                 qu.l11 = l11; qu.l21 = l21;
                 const bool isout = yb <= yout_hi;
-                tv_u_quad_pk(a.l_t, a.theta, qu, yb == 0, x == 0, m_u1, m_u2);
+                tv_u_quad(a.l_t, a.theta, qu, yb == 0, x == 0, m_u1, m_u2);
                 const unsigned mrow = opaque_u(isout ? ~0u : 0u);
                 const unsigned keep[4] = {inw[0] & mrow, inw[1] & mrow, inw[2] & mrow, inw[3] & mrow};
-                accB += tv_err_quad_pk(m_u1, s1_u1, m_u2, s1_u2, keep);
+                accB += tv_err_quad(m_u1, s1_u1, m_u2, s1_u2, keep);
                 st4(U2a + (((s - 1) & 1) * RY + ty) * LW + x, PACK4(m_u1));
                 st4(U2b + (((s - 1) & 1) * RY + ty) * LW + x, PACK4(m_u2));
             }
@@ -902,7 +821,7 @@ __device__ __forceinline__ void iter2_rows_body(const IterArgs& a, const Iter2Bl
                     u1y[i] = mask_f(dv1[i] - s2_u1[i], mnl);
                     u2y[i] = mask_f(dv2[i] - s2_u2[i], mnl);
                 }
-                tv_p_quad_pk(a.taut, u1x, u1y, u2x, u2y, s2_11, s2_12, s2_21, s2_22, r11, r12, r21, r22);
+                tv_p_quad(a.taut, u1x, u1y, u2x, u2y, s2_11, s2_12, s2_21, s2_22, r11, r12, r21, r22);
                 const size_t prow = (size_t)yc * pitch + x;
                 st4(ou1 + prow, PACK4(s2_u1)); st4(ou2 + prow, PACK4(s2_u2));
                 st4(o11 + prow, PACK4(r11)); st4(o12 + prow, PACK4(r12));
@@ -1005,8 +924,8 @@ __global__ __launch_bounds__(256) void k_iter2_tile(Iter2Args A)
         qu.l11 = l11; qu.l21 = l21;
         UNPACK4(u0_1, u1q) UNPACK4(u0_2, u2q) UNPACK4(wx, wxq) UNPACK4(wy, wyq) UNPACK4(rc, rq)
         UNPACK4(p0_11, a11) UNPACK4(p0_12, a12) UNPACK4(p0_21, a21) UNPACK4(p0_22, a22)
-        tv_u_quad_pk(a.l_t, a.theta, qu, y == 0, x == 0, u1_1, u1_2);
-        if (!replay) accA += tv_err_quad_pk(u1_1, u0_1, u1_2, u0_2, keep);
+        tv_u_quad(a.l_t, a.theta, qu, y == 0, x == 0, u1_1, u1_2);
+        if (!replay) accA += tv_err_quad(u1_1, u0_1, u1_2, u0_2, keep);
         st4(&sA[ty][tx * 4], PACK4(u1_1));
         st4(&sB[ty][tx * 4], PACK4(u1_2));
     }
@@ -1025,7 +944,7 @@ __global__ __launch_bounds__(256) void k_iter2_tile(Iter2Args A)
             u1x[i] = mask_f(e1 - u1_1[i], inw[i + 1]); u2x[i] = mask_f(e2 - u1_2[i], inw[i + 1]);
             u1y[i] = mask_f(dv1[i] - u1_1[i], mnl); u2y[i] = mask_f(dv2[i] - u1_2[i], mnl);
         }
-        tv_p_quad_pk(a.taut, u1x, u1y, u2x, u2y, p0_11, p0_12, p0_21, p0_22, p1_11, p1_12, p1_21, p1_22);
+        tv_p_quad(a.taut, u1x, u1y, u2x, u2y, p0_11, p0_12, p0_21, p0_22, p1_11, p1_12, p1_21, p1_22);
         if (replay) {
             if (outq) {
                 st4(a.sb.u1[uc ^ 1] + row, PACK4(u1_1)); st4(a.sb.u2[uc ^ 1] + row, PACK4(u1_2));
@@ -1054,8 +973,8 @@ __global__ __launch_bounds__(256) void k_iter2_tile(Iter2Args A)
         }
         UNPACK4(qu.p12u, up12) UNPACK4(qu.p22u, up22)
         qu.l11 = s11w[ty][tx - 1]; qu.l21 = s21w[ty][tx - 1];                   // unused for the first image column
-        tv_u_quad_pk(a.l_t, a.theta, qu, y == 0, x == 0, u2_1, u2_2);
-        accB += tv_err_quad_pk(u2_1, u1_1, u2_2, u1_2, keep);
+        tv_u_quad(a.l_t, a.theta, qu, y == 0, x == 0, u2_1, u2_2);
+        accB += tv_err_quad(u2_1, u1_1, u2_2, u1_2, keep);
         st4(&sA[ty][tx * 4], PACK4(u2_1));                                      // the first iterate's LDS copy was last read before the barrier above
         st4(&sB[ty][tx * 4], PACK4(u2_2));
     }
@@ -1072,7 +991,7 @@ __global__ __launch_bounds__(256) void k_iter2_tile(Iter2Args A)
             u1x[i] = mask_f(e1 - u2_1[i], inw[i + 1]); u2x[i] = mask_f(e2 - u2_2[i], inw[i + 1]);
             u1y[i] = mask_f(dv1[i] - u2_1[i], mnl); u2y[i] = mask_f(dv2[i] - u2_2[i], mnl);
         }
-        tv_p_quad_pk(a.taut, u1x, u1y, u2x, u2y, p1_11, p1_12, p1_21, p1_22, o11, o12, o21, o22);
+        tv_p_quad(a.taut, u1x, u1y, u2x, u2y, p1_11, p1_12, p1_21, p1_22, o11, o12, o21, o22);
         st4(a.sb.u1[uc ^ 1] + row, PACK4(u2_1)); st4(a.sb.u2[uc ^ 1] + row, PACK4(u2_2));
         st4(a.sb.p11[pc ^ 1] + row, PACK4(o11)); st4(a.sb.p12[pc ^ 1] + row, PACK4(o12));
         st4(a.sb.p21[pc ^ 1] + row, PACK4(o21)); st4(a.sb.p22[pc ^ 1] + row, PACK4(o22));

@@ -146,6 +146,48 @@ def test_iterate_tiny_zero_and_denormal_values_bit_exact(engine, oracle, variant
     assert np.any((np.abs(ref[2]) < 1e-38) & (ref[2] != 0)), "case no longer reaches the denormal range"
 
 
+@pytest.fixture(scope="module")
+def cap_case(oracle):
+    """17 x 61 state whose dual variable is in the hundreds on a block that holds the last column and the last row, three
+    oracle iterations of it, and the assertion that the block's error terms pass the cap."""
+    h, w = 17, 61
+    rng = np.random.default_rng(28)
+    def plane(a):
+        return rng.uniform(-a, a, (h, w)).astype(np.float32)
+    u1, u2 = plane(1), plane(1)
+    p = [plane(0.5) for _ in range(4)]
+    wx, wy, rho = plane(20), plane(20), plane(3)
+    for a in p:
+        a[9:, 48:] = rng.uniform(-400, 400, (h - 9, w - 48)).astype(np.float32)
+    grad = wx * wx + wy * wy
+    first = oracle.iterate(wx, wy, grad, rho, u1, u2, *p, 1)
+    e1, e2 = first[0] - u1, first[1] - u2
+    capped = e1 * e1 + e2 * e2 > np.float32(4096.0)
+    assert capped[-1].any() and capped[:, -1].any() and not capped[:8, :44].any(), "case no longer drives terms past the cap"
+    return (wx, wy, rho, u1, u2, *p), oracle.iterate(wx, wy, grad, rho, u1, u2, *p, 3)
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+def test_iterate_error_term_at_its_cap_bit_exact(engine, cap_case, variant):
+    """A pixel's convergence term is min(|u' - u|^2, 4096) * 2^30.  Where theta * div p moves u by more than 64 px the term
+    sits at the cap; the 17 x 61 level ends in a partial quad (masked columns), a partial tile and a partial strip, and the
+    odd step count makes the two-per-launch forms end on their one-iteration kernels."""
+    from tee_optical_flow_amd import _lib
+    L = _lib.load()
+    (wx, wy, rho, *state), ref = cap_case
+    h, w = wx.shape
+    nsteps = len(ref[6])
+    with iter_form(engine, variant):
+        st = [a.copy() for a in state]
+        err = np.zeros(nsteps, np.uint64)
+        _lib.check(L.tf_dbg_iterate(engine._h, _ptr(wx), _ptr(wy), _ptr(rho), *[_ptr(a) for a in st], w, h, nsteps, 0,
+                                    _ptr(err)), engine._h)
+    for n, a, r in zip(["u1", "u2", "p11", "p12", "p21", "p22"], st, ref[:6]):
+        bad = a.view(np.uint32) != r.view(np.uint32)
+        assert not bad.any(), f"{n}: {bad.sum()} bit patterns differ, first at {np.argwhere(bad)[0]}: {a[bad][0]!r} vs {r[bad][0]!r}"
+    assert np.array_equal(err, ref[6])
+
+
 def _iterate_case(engine, oracle, L, shape, pzero):
     from tee_optical_flow_amd import _lib
     h, w = shape

@@ -46,8 +46,8 @@ template <int HYP>
 __device__ __forceinline__ void hyp4(f2 u1x, f2 u1y, f2 u2x, f2 u2y, f2& g1, f2& g2)
 {
     if (HYP == 0) {
-        g1 = mk2(hypot_exact2(u1x.x, u1y.x), hypot_exact2(u1x.y, u1y.y));
-        g2 = mk2(hypot_exact2(u2x.x, u2y.x), hypot_exact2(u2x.y, u2y.y));
+        g1 = mk2(hypot_exact(u1x.x, u1y.x), hypot_exact(u1x.y, u1y.y));
+        g2 = mk2(hypot_exact(u2x.x, u2y.x), hypot_exact(u2x.y, u2y.y));
     } else if (HYP == 1) {
         g1 = mk2(__builtin_amdgcn_sqrtf(__builtin_fmaf(u1x.x, u1x.x, u1y.x * u1y.x)), __builtin_amdgcn_sqrtf(__builtin_fmaf(u1x.y, u1x.y, u1y.y * u1y.y)));
         g2 = mk2(__builtin_amdgcn_sqrtf(__builtin_fmaf(u2x.x, u2x.x, u2y.x * u2y.x)), __builtin_amdgcn_sqrtf(__builtin_fmaf(u2x.y, u2x.y, u2y.y * u2y.y)));
@@ -61,8 +61,8 @@ __device__ __forceinline__ void hyp4(f2 u1x, f2 u1y, f2 u2x, f2 u2y, f2& g1, f2&
             g2 = mk2(hypot_short64(u2x.x, u2y.x, zone), hypot_short64(u2x.y, u2y.y, zone));
         }
         if (__builtin_expect(__any((int)zone), 0)) {
-            g1 = mk2(hypot_exact2(u1x.x, u1y.x), hypot_exact2(u1x.y, u1y.y));
-            g2 = mk2(hypot_exact2(u2x.x, u2y.x), hypot_exact2(u2x.y, u2y.y));
+            g1 = mk2(hypot_exact(u1x.x, u1y.x), hypot_exact(u1x.y, u1y.y));
+            g2 = mk2(hypot_exact(u2x.x, u2y.x), hypot_exact(u2x.y, u2y.y));
         }
     }
 }
@@ -158,7 +158,7 @@ __device__ __forceinline__ void u_quad_v(float l_t, float theta, const QuadU& q,
 template <int ERR>
 __device__ __forceinline__ double err_v(const float* u1n, const float* u1k, const float* u2n, const float* u2k, const unsigned* keep)
 {
-    if (ERR == 0) return tv_err_quad_pk(u1n, u1k, u2n, u2k, keep);
+    if (ERR == 0) return tv_err_quad(u1n, u1k, u2n, u2k, keep);
     return 0.0;
 }
 
@@ -288,7 +288,7 @@ __global__ void k_check(unsigned long long* out /* [6]: n, zone2, bad2, zone3, b
             a = (float)(int)(ra % 4096) * 0x1p-6f;
             b = (float)(int)(rb % 4096) * 0x1p-6f;
         }
-        const float ref = hypot_exact2(a, b);
+        const float ref = hypot_exact(a, b);
         unsigned zn2 = 0, zn3 = 0;
         const float c2 = hypot_seed32(a, b, zn2), c3 = hypot_short64(a, b, zn3);
         // what matters downstream is ng = 1 + taut*g; a result below 2^-60 cannot change it, so such differences do not count

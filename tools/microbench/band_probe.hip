@@ -36,8 +36,8 @@ void k_probe(const float* __restrict__ in, float* __restrict__ out, int rows, in
         for (int i = 0; i < 4; ++i) { qu.p12u[i] = pp12[i]; qu.p22u[i] = pp22[i]; }
         qu.l11 = __shfl_up(qu.p11[3], 1, 64); qu.l21 = __shfl_up(qu.p21[3], 1, 64);
         float u1a[4], u2a[4], u1b[4], u2b[4], q11[4], q12[4], q21[4], q22[4], s11[4], s12[4], s21[4], s22[4];
-        tv_u_quad_pk(l_t, theta, qu, r == 0, lane == 0, u1a, u2a);
-        accA += tv_err_quad_pk(u1a, qu.u1k, u2a, qu.u2k, keep);
+        tv_u_quad(l_t, theta, qu, r == 0, lane == 0, u1a, u2a);
+        accA += tv_err_quad(u1a, qu.u1k, u2a, qu.u2k, keep);
         float ux1[4], uy1[4], ux2[4], uy2[4];
         const float rr1 = __shfl_down(u1a[0], 1, 64), rr2 = __shfl_down(u2a[0], 1, 64);
 #pragma unroll
@@ -46,7 +46,7 @@ void k_probe(const float* __restrict__ in, float* __restrict__ out, int rows, in
             ux1[i] = mask_f(e1 - u1a[i], inw[i + 1]); ux2[i] = mask_f(e2 - u2a[i], inw[i + 1]);
             uy1[i] = mask_f(u1a[i] - pu1[i], inw[0]); uy2[i] = mask_f(u2a[i] - pu2[i], inw[0]);
         }
-        tv_p_quad_pk(taut, ux1, uy1, ux2, uy2, qu.p11, qu.p12, qu.p21, qu.p22, q11, q12, q21, q22);
+        tv_p_quad(taut, ux1, uy1, ux2, uy2, qu.p11, qu.p12, qu.p21, qu.p22, q11, q12, q21, q22);
         QuadU q2;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -54,8 +54,8 @@ void k_probe(const float* __restrict__ in, float* __restrict__ out, int rows, in
             q2.p11[i] = q11[i]; q2.p12[i] = q12[i]; q2.p21[i] = q21[i]; q2.p22[i] = q22[i]; q2.p12u[i] = pp12[i]; q2.p22u[i] = pp22[i];
         }
         q2.l11 = __shfl_up(q11[3], 1, 64); q2.l21 = __shfl_up(q21[3], 1, 64);
-        tv_u_quad_pk(l_t, theta, q2, r == 0, lane == 0, u1b, u2b);
-        accB += tv_err_quad_pk(u1b, u1a, u2b, u2a, keep);
+        tv_u_quad(l_t, theta, q2, r == 0, lane == 0, u1b, u2b);
+        accB += tv_err_quad(u1b, u1a, u2b, u2a, keep);
         const float t1 = __shfl_down(u1b[0], 1, 64), t2 = __shfl_down(u2b[0], 1, 64);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -63,7 +63,7 @@ void k_probe(const float* __restrict__ in, float* __restrict__ out, int rows, in
             ux1[i] = mask_f(e1 - u1b[i], inw[i + 1]); ux2[i] = mask_f(e2 - u2b[i], inw[i + 1]);
             uy1[i] = mask_f(u1b[i] - pu1[i], inw[0]); uy2[i] = mask_f(u2b[i] - pu2[i], inw[0]);
         }
-        tv_p_quad_pk(taut, ux1, uy1, ux2, uy2, q11, q12, q21, q22, s11, s12, s21, s22);
+        tv_p_quad(taut, ux1, uy1, ux2, uy2, q11, q12, q21, q22, s11, s12, s21, s22);
         st4(out + 0 * plane + row, PACK4(u1b)); st4(out + 1 * plane + row, PACK4(u2b));
         st4(out + 2 * plane + row, PACK4(s11)); st4(out + 3 * plane + row, PACK4(s12));
         st4(out + 4 * plane + row, PACK4(s21)); st4(out + 5 * plane + row, PACK4(s22));

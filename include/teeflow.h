@@ -643,6 +643,43 @@ int tf_hold_frames_rle(tf_handle* h, const uint8_t* blob, const uint64_t* off, c
                        int form, int flip_lr, int* status);
 int tf_rle_stage_bytes(void);
 
+/* ---- frames held from DICOM JPEG BASELINE pixel data (Process 1, transfer syntax 1.2.840.10008.1.2.4.50), 8-bit samples: the device
+ *      parses the entropy data, dequantises, runs the IDCT and upsamples the chroma itself, so what goes over the bus is the compressed
+ *      bytes.  Exact: on every valid stream the samples equal libjpeg-turbo's as Pillow drives it (slow-integer IDCT, fancy
+ *      upsampling).  The arithmetic, what is accepted and the statuses are fixed in csrc/teeflow_jpeg_core.h (the same text on host and
+ *      device); frames.jpeg_decode_frame is the Python twin.  What libjpeg or pydicom make of a MALFORMED stream is NOT pinned: they
+ *      repair and warn where this decoder gives a status.
+ * A frame is a full interchange stream from SOI on (EOI is not required): SOF0, one component or three with sampling 4:4:4, 4:2:2 or
+ *   4:2:0, one interleaved scan, 8-bit quantisation tables, DRI / RSTn; tables may differ from frame to frame.  Per-frame status: 0 ok,
+ *   1 bad header, 2 a process that is not decoded, 3 entropy data that does not decode.  Nothing is written outside a frame's own scratch
+ *   and output, whatever the stream holds, and no frame's output is written unless its status is 0.
+ * Both calls: frame i is the len[i] bytes at blob + off[i] (host; nothing about alignment or padding is assumed); samples is 1 or 3.
+ *   Null pointers, N, H or W < 1, H or W > 65535, H * W > 2^30, a frame of more than 2^32 - 4096 bytes, samples other than 1 or 3
+ *   (tf_hold_frames_jpeg: other than 1 for TF_FRAMES_GRAY and 3 for TF_FRAMES_RGB / TF_FRAMES_YBR_FULL, an unknown form or color,
+ *   TF_JPEG_COLOR_LIBJPEG with a form other than TF_FRAMES_YBR_FULL) and an off[i] + len[i] that overflows are TF_ERR_INVALID_ARG
+ *   before any GPU work.
+ * tf_jpeg_decode: -> out_host [N][H][W][samples], the stream's own components upsampled, no colour transform, and status [N] (both
+ *   host).  TF_OK when every status is 0; otherwise TF_ERR_INVALID_ARG, tf_last_error names the first bad frame and its status,
+ *   status[] is complete, the good frames' outputs are valid and a bad frame's output is not written (tf_rle_decode's contract).
+ * tf_hold_frames_jpeg: the compressed bytes are uploaded, decoded into scratch of the handle and waited for; only when every status is 0
+ *   are the held frames replaced (the generation moves on).  color TF_JPEG_COLOR_NONE: the samples are ingested as tf_hold_frames
+ *   ingests `form`, and what is held equals tf_hold_frames of the decoded frames bit for bit.  TF_JPEG_COLOR_LIBJPEG (samples 3, form
+ *   TF_FRAMES_YBR_FULL): Y, Cb, Cr go through libjpeg's fixed-point colour tables, and what is held equals tf_hold_frames of the RGB a
+ *   libjpeg-backed reader returns, as TF_FRAMES_RGB.  If a frame does not decode the call fails as tf_jpeg_decode does and the frames
+ *   held before, their generation, their tokens and an armed range stay as they were.  status (host, [N]) may be null.
+ * tf_dbg_counter: "frames_upload_bytes" grows by the compressed bytes uploaded; "jpeg_marks_us", "jpeg_entropy_us", "jpeg_idct_us",
+ *   "jpeg_finish_us": the four kernels' device time in the last of these calls; "jpeg_bytes": the compressed bytes read and the sample
+ *   bytes written; "jpeg_batches": the batches of frames worked through since the handle was made (a batch's coefficient scratch stays
+ *   under 256 MiB; tf_set_tuning "jpeg_batch_kib" lowers that for tests).  tf_jpeg_stage_bytes(): the bytes of a frame the kernels
+ *   stage at a time (the tests walk a stream across every position of that boundary). */
+#define TF_JPEG_COLOR_NONE 0
+#define TF_JPEG_COLOR_LIBJPEG 1
+int tf_jpeg_decode(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                   uint8_t* out_host, int* status);
+int tf_hold_frames_jpeg(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                        int form, int color, int flip_lr, int* status);
+int tf_jpeg_stage_bytes(void);
+
 /* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
  *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over
  *      the bus is the compressed bytes.  The output bytes are zlib's or the stream is refused: stored, fixed and dynamic blocks, any

@@ -17,6 +17,8 @@ HELD_SLOTS = 12              # TF_HELD_SLOTS
 HELD_SHAPE_LEN = 5 + 2 * HELD_SLOTS   # TF_HELD_SHAPE_LEN
 FRAMES_FORMS = {"RGB": 0, "GRAY": 1, "YBR_FULL": 2}   # TF_FRAMES_*
 RLE_STAGE_BYTES = 1024       # tf_rle_stage_bytes(): the bytes of a segment k_rle_decode stages at a time (rle::STAGE)
+JPEG_STAGE_BYTES = 1024      # tf_jpeg_stage_bytes(): the bytes of a frame the k_jpeg_* kernels stage at a time (jpeg::STAGE)
+JPEG_COLORS = {"none": 0, "libjpeg": 1}   # TF_JPEG_COLOR_*
 PARAM_KEYS = {
     "tau": 0, "lambda": 1, "theta": 2, "nscales": 3, "warps": 4, "epsilon": 5, "inner_iterations": 6,
     "outer_iterations": 7, "scale_step": 8, "gamma": 9, "median_filtering": 10, "use_initial_flow": 11,
@@ -39,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "tf_deflate", "tf_deflate_array", "tf_held_deflate",
     "tf_hold_frames", "tf_held_frames_shape", "tf_release_frames", "tf_download_frames", "tf_frames_next",
     "tf_rle_decode", "tf_hold_frames_rle", "tf_rle_stage_bytes",
+    "tf_jpeg_decode", "tf_hold_frames_jpeg", "tf_jpeg_stage_bytes",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -200,6 +203,9 @@ def load():
     L.tf_rle_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.tf_hold_frames_rle.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.tf_rle_stage_bytes.restype = i32
+    L.tf_jpeg_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.tf_hold_frames_jpeg.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.tf_jpeg_stage_bytes.restype = i32
     L.tf_hold_study_chunks.argtypes = [vp, C.POINTER(TfChunked), C.POINTER(TfChunked)]
     L.tf_hold_mask_chunks.argtypes = [vp, i32, C.POINTER(TfChunked)]
     L.tf_get_iters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]

@@ -16,7 +16,7 @@
 // the topics share, come first), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
 // The device side is one header per kernel family; teeflow_kernels.hip.h holds what the solvers share and includes DualTVL1's
 // stages (teeflow_tvl1_warp / _iter / _median.hip.h) and the tail's frame conditioning (teeflow_cond.hip.h); teeflow_wave_stage.hip.h is
-// the staged reader that teeflow_inflate.hip.h and teeflow_rle.hip.h share.
+// the staged reader that teeflow_inflate.hip.h, teeflow_rle.hip.h and teeflow_jpeg.hip.h share.
 #include "teeflow_kernels.hip.h"
 #include "teeflow_deepflow.hip.h"
 #include "teeflow_sor_rt.hip.h"
@@ -36,6 +36,7 @@
 #include "teeflow_deflate.hip.h"
 #include "teeflow_ingest.hip.h"
 #include "teeflow_rle.hip.h"
+#include "teeflow_jpeg.hip.h"
 #include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include "teeflow_engine.hip.h"
@@ -212,6 +213,7 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
     else if (n == "warp_margin") h->warp_margin = value < 0 ? 0 : (value > 40 ? 40 : value);
     else if (n == "overlay_chunk_kib") h->overlay_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);   // never above the 512 MiB rule
     else if (n == "area_chunk_kib") h->area_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);         // the same
+    else if (n == "jpeg_batch_kib") h->jpeg_batch_kib = value < 0 ? 0 : (value > (256 << 10) ? (256 << 10) : value);           // never above the 256 MiB rule
     else return fail(h, TF_ERR_INVALID_ARG, "unknown tuning knob %s", name);
     return TF_OK;
 }
@@ -244,6 +246,8 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "frames_held_reads") v = h->frames_held_reads;
     else if (n == "ingest_bytes") v = h->ingest_bytes;
     else if (n == "rle_bytes") v = h->rle_bytes;
+    else if (n == "jpeg_bytes") v = h->jpeg_bytes;
+    else if (n == "jpeg_batches") v = h->jpeg_batches;
     else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {
@@ -418,6 +422,7 @@ TF_API void tf_host_free(void* p)
 #include "teeflow_scratch.hip.h"          // the handle's grow-only scratch, chunking, Src: what every tail call shares
 #include "teeflow_streams_host.hip.h"     // a batch of byte streams: check, upload, verdict (inflate's and RLE's)
 #include "teeflow_frames_host.hip.h"      // a call's frames (tf_frames_next), conditioning, echo, saliency, the held frames
+#include "teeflow_jpeg_host.hip.h"        // frames held from JPEG Baseline pixel data
 #include "teeflow_masks_host.hip.h"       // labelling: clean masks, Otsu, AV centroids, first-region areas
 #include "teeflow_segmentor_host.hip.h"
 #include "teeflow_analysis_host.hip.h"    // rad/long and polar projections, histogram, select

@@ -268,6 +268,7 @@ int frames_commit(tf_handle* h, const uint8_t* dsrc, size_t hw, int form, bool f
         HIPC(h, hipEventRecord(h->ev[0], h->stream));
         if (form == TF_FRAMES_GRAY) launch_ingest<tfg::GRAY>(h, flip, dsrc, npx, W, hw, k.rgb);
         else if (form == TF_FRAMES_YBR_FULL) launch_ingest<tfg::YBR_FULL>(h, flip, dsrc, npx, W, hw, k.rgb);
+        else if (form == tfg::YBR_LIBJPEG) launch_ingest<tfg::YBR_LIBJPEG>(h, flip, dsrc, npx, W, hw, k.rgb);   // (internal: tf_hold_frames_jpeg alone passes it)
         else launch_ingest<tfg::RGB>(h, flip, dsrc, npx, W, hw, k.rgb);
         HIPC(h, hipGetLastError());
         HIPC(h, hipEventRecord(h->ev[1], h->stream));

@@ -23,9 +23,24 @@
 namespace tfg {
 // the source forms (TF_FRAMES_* of include/teeflow.h)
 enum : int { RGB = 0, GRAY = 1, YBR_FULL = 2 };
+// An internal form, no TF_FRAMES_* value and refused by tf_hold_frames and tf_hold_frames_rle: Y, Cb, Cr as a JPEG stream holds them ->
+// RGB with libjpeg's fixed-point tables (jdcolor.c, SCALEBITS 16), what a libjpeg-backed reader returns for such a stream.  With
+// cb = Cb - 128, cr = Cr - 128, signed 32-bit and an arithmetic shift:
+//     R = Y + ((91881 * cr + 32768) >> 16);   G = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);   B = Y + ((116130 * cb + 32768) >> 16)
+// each clamped to [0, 255] (tf_hold_frames_jpeg with TF_JPEG_COLOR_LIBJPEG; frames.ycc_to_rgb_libjpeg is the numpy twin).
+enum : int { YBR_LIBJPEG = 3 };
 
 // bytes per source pixel
 TFG_FN int src_channels(int form) { return form == GRAY ? 1 : 3; }
+
+TFG_FN uint8_t clamp255(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+TFG_FN void ybr_libjpeg_pixel(uint8_t Y, uint8_t Cb, uint8_t Cr, uint8_t* rgb)
+{
+    const int y = Y, cb = (int)Cb - 128, cr = (int)Cr - 128;
+    rgb[0] = clamp255(y + ((91881 * cr + 32768) >> 16));
+    rgb[1] = clamp255(y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+    rgb[2] = clamp255(y + ((116130 * cb + 32768) >> 16));
+}
 
 constexpr float M_CB_G = (float)(-0.114 * 1.772 / 0.587), M_CB_B = (float)1.772;
 constexpr float M_CR_R = (float)1.402, M_CR_G = (float)(-0.299 * 1.402 / 0.587);
@@ -51,6 +66,7 @@ TFG_FN void pixel(const uint8_t* src, size_t s, uint8_t* rgb)
 {
     if (FORM == GRAY) rgb[0] = rgb[1] = rgb[2] = src[s];
     else if (FORM == YBR_FULL) ybr_pixel(src[3 * s], src[3 * s + 1], src[3 * s + 2], rgb);
+    else if (FORM == YBR_LIBJPEG) ybr_libjpeg_pixel(src[3 * s], src[3 * s + 1], src[3 * s + 2], rgb);
     else { rgb[0] = src[3 * s]; rgb[1] = src[3 * s + 1]; rgb[2] = src[3 * s + 2]; }
 }
 

@@ -521,6 +521,54 @@ class DenseFlow:
                                               1 if flip else 0, status.ctypes.data), self._h, "tf_hold_frames_rle")
         return HeldFrames(self, N, H, W, self._held_frames_shape()[3])
 
+    # ---- DICOM JPEG Baseline pixel data (tf_jpeg_decode, tf_hold_frames_jpeg): Huffman decode, dequantisation, IDCT and chroma upsampling
+    # on the device; frames.jpeg_decode_frame is the twin, frames.jpeg_record makes the record --------------------------------------------
+    @staticmethod
+    def _jpeg_record(record, H, W, samples):
+        """(blob, off, len) of frames.jpeg_record, checked -> the three C-contiguous arrays and the sizes as ints"""
+        H, W = int(H), int(W)
+        if H > 65535 or W > 65535:
+            raise OpticalFlowCalculationError(f"a JPEG frame has at most 65535 rows and columns, got {H} x {W}")
+        return DenseFlow._rle_record(record, H, W, samples)
+
+    def jpeg_decode(self, record, H, W, samples):
+        """JPEG Baseline frames -- record = (blob, off, len), frame i the len[i] bytes at blob[off[i]:] (frames.jpeg_record), each a full
+        interchange stream -- of H x W pixels of `samples` (1 or 3) components -> (uint8 [N,H,W,samples], or [N,H,W] for samples == 1;
+        status int32 [N]): the stream's own components, upsampled, no colour transform; on a valid stream what libjpeg-turbo gives.  A
+        status is 0, 1 bad header, 2 a process that is not decoded or 3 entropy data that does not decode (frames.jpeg_decode_frame has
+        the rules); the call does not raise for a frame that does not decode: its status says so and its frame is zeros.  A call that
+        fails as a whole -- refused arguments, a HIP error -- raises."""
+        blob, off, ln, H, W, samples = self._jpeg_record(record, H, W, samples)
+        N = off.size
+        out = np.zeros((N, H, W) if samples == 1 else (N, H, W, samples), np.uint8)
+        status = np.zeros(N, np.int32)
+        rc = self._L.tf_jpeg_decode(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, out.ctypes.data, status.ctypes.data)
+        self._raise_unless_verdict(rc, status, "tf_jpeg_decode")
+        return out, status
+
+    def hold_frames_jpeg(self, record, H, W, samples, form="RGB", color="none", flip=False):
+        """hold_frames from JPEG Baseline pixel data as the file stores it: record = (blob, off, len) (frames.jpeg_record, or
+        pipeline.dicom_jpeg_frames' fields), H x W pixels of `samples` components -- 1 for form "GRAY", 3 for "RGB" and "YBR_FULL".  Only
+        the compressed bytes are uploaded.  color "none": the decoded samples are ingested as hold_frames ingests `form` and `flip`, and
+        what is held is frames.ingest_host(decoded, form, flip).  color "libjpeg" (form "YBR_FULL"): Y, Cb, Cr go through libjpeg's
+        colour tables, and what is held is frames.ingest_host(frames.ycc_to_rgb_libjpeg(decoded), "RGB", flip): the RGB a Pillow-backed
+        reader returns.  -> the HeldFrames token.  If a frame does not decode the call raises with the first bad frame and its status, and
+        the frames held before, their generation and their tokens stay as they were."""
+        if form not in _lib.FRAMES_FORMS:
+            raise OpticalFlowCalculationError(f"form must be one of {tuple(_lib.FRAMES_FORMS)}, got {form!r}")
+        if color not in _lib.JPEG_COLORS:
+            raise OpticalFlowCalculationError(f"color must be one of {tuple(_lib.JPEG_COLORS)}, got {color!r}")
+        if color == "libjpeg" and form != "YBR_FULL":
+            raise OpticalFlowCalculationError(f"color 'libjpeg' converts Y, Cb, Cr: it needs form 'YBR_FULL', got {form!r}")
+        blob, off, ln, H, W, samples = self._jpeg_record(record, H, W, samples)
+        if samples != (1 if form == "GRAY" else 3):
+            raise OpticalFlowCalculationError(f"{form} frames have {1 if form == 'GRAY' else 3} samples a pixel, got samples = {samples}")
+        N = off.size
+        status = np.zeros(N, np.int32)
+        _lib.check(self._L.tf_hold_frames_jpeg(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, _lib.FRAMES_FORMS[form],
+                                               _lib.JPEG_COLORS[color], 1 if flip else 0, status.ctypes.data), self._h, "tf_hold_frames_jpeg")
+        return HeldFrames(self, N, H, W, self._held_frames_shape()[3])
+
     def _frames_in(self, frames, check, min_frames=1):
         """A method's `nparr` / `frames` argument: an array goes through `check`; a HeldFrames token is checked for being this engine's
         current frames and comes back as it is (it has the array's .shape).  Nothing is armed yet: _frames_ptr does that."""

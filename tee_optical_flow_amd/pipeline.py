@@ -26,8 +26,8 @@ from . import hdf5_out
 from .config import default_optical_flow_config
 from .dense_flow import DenseFlow
 from .exceptions import ConfigurationError, DICOMReadError, OpticalFlowCalculationError
-from .frames import (PHOTOMETRIC_FORMS, RLE_STATUS_TEXT, RLE_TRANSFER_SYNTAX, condition_frames, encapsulated_frames, rle_decode_frame, rle_record,
-                     ybr_full_to_rgb)
+from .frames import (JPEG_BASELINE_TRANSFER_SYNTAX, JPEG_STATUS_TEXT, PHOTOMETRIC_FORMS, RLE_STATUS_TEXT, RLE_TRANSFER_SYNTAX, condition_frames,
+                     encapsulated_frames, jpeg_decode_frame, jpeg_record, rle_decode_frame, rle_record, ybr_full_to_rgb, ycc_to_rgb_libjpeg)
 
 logger = logging.getLogger(__name__)
 
@@ -456,12 +456,126 @@ def _rle_fallback(reason):
         logger.warning(f"RLE Lossless pixel data not decoded on the device, the host decodes it instead: {reason}")
 
 
+# ---- JPEG Baseline pixel data as stored (transfer syntax 1.2.840.10008.1.2.4.50, 8-bit samples) ----------------------------------------
+JPEG_COLOR_ROUTES = ("libjpeg", "dicom")
+
+
+@dataclass(frozen=True)
+class JpegFrames(RleFrames):
+    """A study's pixel data as a DICOM JPEG Baseline file stores it: RleFrames' fields, each frame a full interchange stream
+    (frames.jpeg_record's record).  `color`: how Y, Cb, Cr become RGB under PhotometricInterpretation YBR_FULL / YBR_FULL_422 --
+    "libjpeg" (the default: libjpeg's fixed-point tables, what a Pillow-backed reader yields) or "dicom" (the float inverse of PS3.3
+    C.7.6.3.1.2, frames.ybr_full_to_rgb).  Which of the two equals pydicom's ds.pixel_array depends on the handler pydicom picks:
+    unpinned.  What frames="device" hands to DenseFlow.hold_frames_jpeg in an array's place; decode() is the host's way."""
+    color: str = "libjpeg"
+
+    def decode(self):
+        """-> the streams' own components, upsampled, no colour transform: uint8 [N,H,W] (samples == 1) or [N,H,W,samples]; by PIL
+        where it imports and takes the stream, otherwise by the twin frames.jpeg_decode_frame (slow); DICOMReadError for a frame that
+        does not decode"""
+        N, H, W = self.shape
+        blob = np.asarray(self.blob, np.uint8)
+        out = np.empty((N, H, W) if self.samples == 1 else (N, H, W, self.samples), np.uint8)
+        for i in range(N):
+            a = int(self.off[i])
+            buf = blob[a:a + int(self.len[i])].tobytes()
+            arr = _pil_components(buf, out.shape[1:])
+            if arr is None:
+                arr, status = jpeg_decode_frame(buf, H, W, self.samples)
+                if status:
+                    raise DICOMReadError(f"JPEG Baseline frame {i} did not decode: status {status} ({JPEG_STATUS_TEXT[status]})")
+            out[i] = arr
+        return out
+
+
+def _pil_components(buf, shape):
+    """One JPEG stream's own components by PIL on libjpeg-turbo (the decoder the device equals), or None where PIL does not import, is
+    built on another libjpeg (libjpeg 9 upsamples the chroma differently: measured, up to 88 counts on a 4:2:0 stream), does not take
+    the stream or gives another shape -- the twin decides then"""
+    try:
+        import io
+        from PIL import Image, features
+        if not features.check_feature("libjpeg_turbo"):
+            return None
+        im = Image.open(io.BytesIO(buf))
+        if im.format != "JPEG" or im.mode not in ("L", "RGB", "YCbCr"):
+            return None
+        if im.mode != "L":
+            im.draft("YCbCr", None)
+            if im.mode != "YCbCr":
+                return None
+        arr = np.asarray(im)
+    except Exception:                                                      # (whatever PIL makes of a malformed stream: the twin's status is the answer)
+        return None
+    return arr if arr.shape == tuple(shape) and arr.dtype == np.uint8 else None
+
+
+def _jpeg_refusal(ds):
+    """Why a dataset in the JPEG Baseline transfer syntax is not decoded from its stored bytes, or None"""
+    bits, samples = int(getattr(ds, "BitsAllocated", 0) or 0), int(getattr(ds, "SamplesPerPixel", 0) or 0)
+    if bits != 8:
+        return f"JPEG Baseline pixel data with BitsAllocated = {bits}: only 8-bit samples are decoded from the stored bytes"
+    if samples not in (1, 3):
+        return f"JPEG Baseline pixel data with SamplesPerPixel = {samples}: only 1 or 3 samples are decoded from the stored bytes"
+    return None
+
+
+def _is_jpeg(ds):
+    return str(getattr(getattr(ds, "file_meta", None), "TransferSyntaxUID", "")) == JPEG_BASELINE_TRANSFER_SYNTAX
+
+
+def dicom_jpeg_frames(ds, jpeg_color="libjpeg"):
+    """The pixel data of an 8-bit JPEG Baseline dataset as it is stored -> JpegFrames; None for any other dataset (another transfer
+    syntax, samples that are not 8-bit, a sample count other than 1 or 3), which is read through its pixel_array as ever.  A pure
+    function of any dataset-like object, as dicom_rle_frames: frames.encapsulated_frames cuts PixelData into frames.  No pydicom."""
+    if jpeg_color not in JPEG_COLOR_ROUTES:
+        raise ConfigurationError(f"jpeg_color must be one of {JPEG_COLOR_ROUTES}, not {jpeg_color!r}")
+    if not _is_jpeg(ds) or _jpeg_refusal(ds) is not None:
+        return None
+    N, H, W = int(getattr(ds, "NumberOfFrames", 1) or 1), int(ds.Rows), int(ds.Columns)
+    blob, off, ln = jpeg_record(encapsulated_frames(ds.PixelData, N))
+    return JpegFrames(blob, off, ln, (N, H, W), int(ds.SamplesPerPixel), str(getattr(ds, "PhotometricInterpretation", "")) or None, jpeg_color)
+
+
+def _jpeg_form(jf, photometric):
+    """-> (device form, colour route of hold_frames_jpeg, None) for JPEG frames under `photometric` (None: the frames' own, else by the
+    sample count), or (None, None, the reason).  MONOCHROME2 -> GRAY; RGB -> RGB, no transform; YBR_FULL / YBR_FULL_422 -> YBR_FULL,
+    through libjpeg's tables (jf.color "libjpeg") or the DICOM float inverse ("dicom")."""
+    photometric = photometric or jf.photometric or ("MONOCHROME2" if jf.samples == 1 else "RGB")
+    form, why = _rle_form(jf, photometric)
+    if why is not None:
+        return None, None, why
+    return form, ("libjpeg" if form == "YBR_FULL" and jf.color == "libjpeg" else "none"), None
+
+
+def _jpeg_host(jf, photometric):
+    """JPEG frames decoded on the host -> (array, the photometric it is now stored under): under the libjpeg route YBR data comes
+    back as RGB (None), as a Pillow-backed reader returns it; otherwise the components under their interpretation"""
+    photometric = photometric or jf.photometric
+    arr = jf.decode()
+    if jf.color == "libjpeg" and photometric in ("YBR_FULL", "YBR_FULL_422") and jf.samples == 3:
+        return ycc_to_rgb_libjpeg(arr), None
+    return arr, (photometric if photometric in PHOTOMETRIC_FORMS else None)
+
+
+_jpeg_fallbacks = set()             # reasons already logged
+
+
+def _jpeg_fallback(reason):
+    if reason not in _jpeg_fallbacks:
+        _jpeg_fallbacks.add(reason)
+        logger.warning(f"JPEG Baseline pixel data not decoded on the device, the host decodes it instead: {reason}")
+
+
 class _DeviceFrames:
     """A study's frames held on the flow model's device (frames="device"): the token every device call takes, and the RGB for what
-    still runs on the host, downloaded once.  `stored`: the pixel data as an array, or as RleFrames (the device decodes them)."""
+    still runs on the host, downloaded once.  `stored`: the pixel data as an array, or as RleFrames / JpegFrames (the device decodes
+    them)."""
 
-    def __init__(self, model, stored, form, flip):
-        if isinstance(stored, RleFrames):
+    def __init__(self, model, stored, form, flip, color="none"):
+        if isinstance(stored, JpegFrames):
+            token = model.hold_frames_jpeg(stored.record, stored.shape[1], stored.shape[2], stored.samples, form, color=color, flip=flip)
+        elif isinstance(stored, RleFrames):
             token = model.hold_frames_rle(stored.record, stored.shape[1], stored.shape[2], stored.samples, form, flip=flip)
         else:
             token = model.hold_frames(stored, form, flip=flip)
@@ -498,7 +612,12 @@ def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode=
     model without hold_frames takes the host path with one logged reason per walk.  The file is the one frames="host" writes.
     8-bit RLE Lossless pixel data (read_study_stored gives it as RleFrames, taken before ds.pixel_array is touched; an .npz study may
     carry it in `nparr`'s place) is held from its compressed bytes (DenseFlow.hold_frames_rle: the device decodes it); a model without
-    hold_frames_rle gets what frames.rle_decode_frame decodes, with one logged reason per walk, and frames="host" decodes it likewise."""
+    hold_frames_rle gets what frames.rle_decode_frame decodes, with one logged reason per walk, and frames="host" decodes it likewise.
+    8-bit JPEG Baseline pixel data (JpegFrames: dicom_jpeg_frames, or an .npz with `jpeg_blob`, `jpeg_off`, `jpeg_len`, `rows`, `cols`,
+    `samples`, `photometric`) is held likewise by DenseFlow.hold_frames_jpeg (_jpeg_form says in which form and by which colour
+    route); a model without it, a refused dataset and a frame the device gives a status for take the host's decode (PIL where it
+    imports, else frames.jpeg_decode_frame), with one logged reason per walk.  frames="host" and read_study read a DICOM file through
+    ds.pixel_array as ever."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
@@ -536,9 +655,14 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             metadata = md_file
         patient_id = patient_id or pid_file
         heart_rate = heart_rate or hr_file
-    rle = nparr if isinstance(nparr, RleFrames) else None   # RLE Lossless pixel data as stored: decoded on the device below, or here
+    rle = nparr if isinstance(nparr, RleFrames) else None   # RLE Lossless or JPEG Baseline pixel data as stored: decoded on the device below, or here
     if rle is not None and frames == "host":
-        nparr, rle = rle.decode(), None
+        if isinstance(rle, JpegFrames):
+            nparr, still = _jpeg_host(rle, _photometric)
+            nparr = ybr_full_to_rgb(nparr) if still in ("YBR_FULL", "YBR_FULL_422") else nparr
+        else:
+            nparr = rle.decode()
+        rle = None
     if rle is None:
         nparr = np.asarray(nparr)
     if metadata is None:
@@ -559,7 +683,20 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
     walk = _defer_save is not None                # process_folder: the writer stage takes the study
     held = None                                   # frames="device": the study's frames on the model's device
     try:
-        if rle is not None:                       # (frames="device")
+        if isinstance(rle, JpegFrames):           # (frames="device")
+            form, color, why = _jpeg_form(rle, _photometric)
+            if why is None and not hasattr(model, "hold_frames_jpeg"):
+                why = f"the flow model ({type(model).__name__}) has no hold_frames_jpeg"
+            if why is None:
+                try:
+                    held = _DeviceFrames(model, rle, form, flipLR, color)
+                    nparr = held.token
+                except OpticalFlowCalculationError as e:                  # a frame whose status is not 0: the held frames are as they were
+                    why = f"the device did not decode it ({e})"
+            if why is not None:                   # the host decodes; what it gives goes the way of any stored array, below
+                _jpeg_fallback(why)
+                nparr, _photometric = _jpeg_host(rle, _photometric)
+        elif rle is not None:                     # (frames="device")
             form, why = _rle_form(rle, _photometric)
             if why is None and not hasattr(model, "hold_frames_rle"):
                 why = f"the flow model ({type(model).__name__}) has no hold_frames_rle"
@@ -661,7 +798,9 @@ def read_study(path):
     if ext == ".npz":
         z = np.load(path, allow_pickle=False)
         arr, photometric = _npz_stored(z, path), _npz_photometric(z, path)
-        if isinstance(arr, RleFrames):                                    # (the offline stand-in for pydicom's RLE handler: the twin)
+        if isinstance(arr, JpegFrames):                                   # (the offline stand-in for a Pillow-backed handler: PIL, or the twin)
+            arr, photometric = _jpeg_host(arr, photometric)
+        elif isinstance(arr, RleFrames):                                  # (the offline stand-in for pydicom's RLE handler: the twin)
             arr = arr.decode()
         if photometric in ("YBR_FULL", "YBR_FULL_422"):                   # (the offline stand-in for pydicom's converter: the twin)
             arr = ybr_full_to_rgb(arr)
@@ -680,6 +819,8 @@ def _npz_study(z):
 def _npz_stored(z, path):
     """The pixel data of an .npz study as it is stored: `nparr`, or, in its place, RLE Lossless frames under `rle_blob`, `rle_off`,
     `rle_len` (frames.rle_record's) with `rows`, `cols` and `samples` -> RleFrames"""
+    if "jpeg_blob" in z:
+        return _npz_jpeg(z, path)
     if "rle_blob" not in z:
         return z["nparr"]
     try:
@@ -691,6 +832,21 @@ def _npz_stored(z, path):
             or int((off + ln.astype(np.uint64)).max()) > blob.size):
         raise DICOMReadError(f"Failed to read {path}: rle_off / rle_len do not describe frames of {H} x {W} x {samples} inside rle_blob's {blob.size} bytes")
     return RleFrames(blob, off, ln, (int(off.size), H, W), samples)
+
+
+def _npz_jpeg(z, path):
+    """JPEG Baseline frames of an .npz study under `jpeg_blob`, `jpeg_off`, `jpeg_len` (frames.jpeg_record's) with `rows`, `cols`,
+    `samples` and, optionally, `photometric` and `jpeg_color` -> JpegFrames"""
+    try:
+        blob, off, ln = np.ascontiguousarray(z["jpeg_blob"], np.uint8), np.ascontiguousarray(z["jpeg_off"], np.uint64), np.ascontiguousarray(z["jpeg_len"], np.uint32)
+        H, W, samples = int(z["rows"]), int(z["cols"]), int(z["samples"])
+    except KeyError as e:
+        raise DICOMReadError(f"Failed to read {path}: a JPEG study needs jpeg_blob, jpeg_off, jpeg_len, rows, cols and samples ({e} is missing)") from e
+    color = str(z["jpeg_color"]) if "jpeg_color" in z else "libjpeg"
+    if (blob.ndim != 1 or off.ndim != 1 or off.shape != ln.shape or off.size < 1 or H < 1 or W < 1 or samples not in (1, 3)
+            or int((off + ln.astype(np.uint64)).max()) > blob.size or color not in JPEG_COLOR_ROUTES):
+        raise DICOMReadError(f"Failed to read {path}: jpeg_off / jpeg_len / jpeg_color do not describe frames of {H} x {W} x {samples} inside jpeg_blob's {blob.size} bytes")
+    return JpegFrames(blob, off, ln, (int(off.size), H, W), samples, _npz_photometric(z, path), color)
 
 
 def _npz_photometric(z, path):
@@ -718,6 +874,20 @@ def _stored_rle(ds, path):
         raise DICOMReadError(f"Failed to read DICOM file: {path} ({e})") from e
 
 
+def _stored_jpeg(ds, path):
+    """_stored_rle for a JPEG Baseline dataset: JpegFrames, or None -- with one logged reason where the stored bytes are not decoded"""
+    if not _is_jpeg(ds):
+        return None
+    why = _jpeg_refusal(ds)
+    if why is not None:
+        _jpeg_fallback(why)
+        return None
+    try:
+        return dicom_jpeg_frames(ds)
+    except ValueError as e:
+        raise DICOMReadError(f"Failed to read DICOM file: {path} ({e})") from e
+
+
 def _read_dicom(path, stored=False):
     """`stored` (read_study_stored): the pixel data as the file stores it where that has a device form (_stored_rle)"""
     try:
@@ -727,6 +897,8 @@ def _read_dicom(path, stored=False):
     try:
         ds = pydicom.dcmread(path)
         arr = _stored_rle(ds, path) if stored else None
+        if arr is None and stored:
+            arr = _stored_jpeg(ds, path)
         if arr is None:
             arr = ds.pixel_array
     except (IOError, OSError, KeyError, AttributeError) as e:             # reference _read_dicom_file (:307-312) -> DICOMReadError (:521-522)
@@ -1100,6 +1272,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     _check_frames(frames)
     _frames_fallbacks.clear()                                       # one logged reason per walk
     _rle_fallbacks.clear()
+    _jpeg_fallbacks.clear()
     if deflate == "device":
         _deflate_fallbacks.clear()                                  # one logged reason per walk
         if studies_in_flight > 1:

@@ -680,6 +680,37 @@ int tf_hold_frames_jpeg(tf_handle* h, const uint8_t* blob, const uint64_t* off, 
                         int form, int color, int flip_lr, int* status);
 int tf_jpeg_stage_bytes(void);
 
+/* ---- frames held from DICOM JPEG LOSSLESS pixel data (T.81 Process 14, frame marker SOF3; transfer syntaxes 1.2.840.10008.1.2.4.70,
+ *      "first-order prediction", and its parent 1.2.840.10008.1.2.4.57), 8-bit samples.  The Huffman-coded value of such a scan is the
+ *      prediction difference, so the device's serial entropy pass emits differences only and, with predictor 1, the reconstruction is
+ *      prefix sums modulo 2^16: down the first column of a restart interval, then along every row, each row on its own.  Exact by
+ *      construction: a valid stream has exactly one decoding, the encoded array.  What is accepted, the rules and the statuses are
+ *      fixed in csrc/teeflow_jpegll_core.h (the same text on host and device); frames.jpegll_decode_frame is the Python twin.  What
+ *      libjpeg or pydicom make of a MALFORMED stream is NOT pinned: they mask a sample to its precision where this decoder gives a status.
+ * A frame is a full interchange stream from SOI on (EOI is not required): SOF3 of precision 8, one component or three sampled 1 x 1,
+ *   one interleaved scan with Ss = 1, Se = Ah = Al = 0, Huffman tables of class 0 with ids 0..3, DRI / RSTn with an interval that is a
+ *   multiple of W; tables may differ from frame to frame.  Per-frame status: 0 ok, 1 bad header, 2 a process that is not decoded (any
+ *   other frame marker, predictor or point transform), 3 data that does not decode -- a reconstructed sample outside 0..255 included.
+ *   Nothing is written outside a frame's own scratch and output, whatever the stream holds.
+ * Both calls take tf_jpeg_decode's arguments with tf_jpeg_decode's refusals (TF_ERR_INVALID_ARG before any GPU work); tf_jpeg_decode
+ *   itself still answers status 2 for an SOF3 stream.
+ * tf_jpegll_decode: -> out_host [N][H][W][samples], no colour transform, and status [N] (both host), under tf_jpeg_decode's contract:
+ *   TF_OK when every status is 0; otherwise TF_ERR_INVALID_ARG, status[] is complete, the good frames' outputs are valid and a bad
+ *   frame's output is not written.
+ * tf_hold_frames_jpegll: form TF_FRAMES_GRAY (samples 1), TF_FRAMES_RGB or TF_FRAMES_YBR_FULL (samples 3); the codec applies no colour
+ *   transform.  The compressed bytes are uploaded, decoded into scratch of the handle and waited for; only when every status is 0 are
+ *   the held frames replaced, and what is held equals tf_hold_frames of the decoded frames bit for bit.  If a frame does not decode the
+ *   call fails as tf_jpegll_decode does and the frames held before, their generation, their tokens and an armed range stay as they
+ *   were.  status (host, [N]) may be null.
+ * tf_dbg_counter: "frames_upload_bytes" grows by the compressed bytes uploaded; "jpegll_entropy_us" (k_jpeg_marks and
+ *   k_jpegll_entropy) and "jpegll_restore_us" (k_jpegll_col and k_jpegll_rows): device time in the last of these calls; "jpegll_bytes":
+ *   the compressed bytes read and the sample bytes written; "jpegll_batches": the batches of frames worked through since the handle
+ *   was made (a batch's differences, 2 bytes a sample, stay under 256 MiB; tf_set_tuning "jpeg_batch_kib" lowers that for tests). */
+int tf_jpegll_decode(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                     uint8_t* out_host, int* status);
+int tf_hold_frames_jpegll(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
+                          int form, int flip_lr, int* status);
+
 /* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
  *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over
  *      the bus is the compressed bytes.  The output bytes are zlib's or the stream is refused: stored, fixed and dynamic blocks, any

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "tf_hold_frames", "tf_held_frames_shape", "tf_release_frames", "tf_download_frames", "tf_frames_next",
     "tf_rle_decode", "tf_hold_frames_rle", "tf_rle_stage_bytes",
     "tf_jpeg_decode", "tf_hold_frames_jpeg", "tf_jpeg_stage_bytes",
+    "tf_jpegll_decode", "tf_hold_frames_jpegll",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -206,6 +207,8 @@ def load():
     L.tf_jpeg_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.tf_hold_frames_jpeg.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.tf_jpeg_stage_bytes.restype = i32
+    L.tf_jpegll_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.tf_hold_frames_jpegll.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.tf_hold_study_chunks.argtypes = [vp, C.POINTER(TfChunked), C.POINTER(TfChunked)]
     L.tf_hold_mask_chunks.argtypes = [vp, i32, C.POINTER(TfChunked)]
     L.tf_get_iters.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]

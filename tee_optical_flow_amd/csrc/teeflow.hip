@@ -16,7 +16,7 @@
 // the topics share, come first), teeflow_comm.hip.h (RCCL) and teeflow_dbg.hip.h (test hooks).
 // The device side is one header per kernel family; teeflow_kernels.hip.h holds what the solvers share and includes DualTVL1's
 // stages (teeflow_tvl1_warp / _iter / _median.hip.h) and the tail's frame conditioning (teeflow_cond.hip.h); teeflow_wave_stage.hip.h is
-// the staged reader that teeflow_inflate.hip.h, teeflow_rle.hip.h and teeflow_jpeg.hip.h share.
+// the staged reader that teeflow_inflate.hip.h, teeflow_rle.hip.h, teeflow_jpeg.hip.h and teeflow_jpegll.hip.h share.
 #include "teeflow_kernels.hip.h"
 #include "teeflow_deepflow.hip.h"
 #include "teeflow_sor_rt.hip.h"
@@ -37,6 +37,7 @@
 #include "teeflow_ingest.hip.h"
 #include "teeflow_rle.hip.h"
 #include "teeflow_jpeg.hip.h"
+#include "teeflow_jpegll.hip.h"
 #include "pil_resample_tables.h"
 #include "../../include/teeflow.h"
 #include "teeflow_engine.hip.h"
@@ -248,6 +249,8 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "rle_bytes") v = h->rle_bytes;
     else if (n == "jpeg_bytes") v = h->jpeg_bytes;
     else if (n == "jpeg_batches") v = h->jpeg_batches;
+    else if (n == "jpegll_bytes") v = h->jpegll_bytes;
+    else if (n == "jpegll_batches") v = h->jpegll_batches;
     else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {
@@ -423,6 +426,7 @@ TF_API void tf_host_free(void* p)
 #include "teeflow_streams_host.hip.h"     // a batch of byte streams: check, upload, verdict (inflate's and RLE's)
 #include "teeflow_frames_host.hip.h"      // a call's frames (tf_frames_next), conditioning, echo, saliency, the held frames
 #include "teeflow_jpeg_host.hip.h"        // frames held from JPEG Baseline pixel data
+#include "teeflow_jpegll_host.hip.h"      // frames held from JPEG Lossless pixel data (SOF3, predictor 1)
 #include "teeflow_masks_host.hip.h"       // labelling: clean masks, Otsu, AV centroids, first-region areas
 #include "teeflow_segmentor_host.hip.h"
 #include "teeflow_analysis_host.hip.h"    // rad/long and polar projections, histogram, select

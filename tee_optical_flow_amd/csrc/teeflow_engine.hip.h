@@ -207,16 +207,18 @@ struct tf_handle : Engine {
            PRE_RLE_BLOB, PRE_RLE_TABLE, PRE_RLE_PLANES, PRE_RLE_OUT,              // tf_rle_decode, tf_hold_frames_rle: compressed bytes, per-frame table, the decoded
                                                                                   //   sample planes; tf_rle_decode's interleaved frames
            PRE_JPEG_BLOB, PRE_JPEG_TABLE, PRE_JPEG_RST, PRE_JPEG_COEF, PRE_JPEG_PLANES, PRE_JPEG_OUT,   // tf_jpeg_decode, tf_hold_frames_jpeg: compressed bytes, per-frame
-                                                                                  //   table, RSTn positions, a batch's coefficients and component planes; the frames
+                                                                                  //   table, RSTn positions, a batch's coefficients and component planes; the frames.
+                                                                                  //   tf_jpegll_decode, tf_hold_frames_jpegll use the same slots (COEF: a batch's differences)
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     // Device time of the tail's kernels in ms, read from the handle's event pairs (dev_time, below); tf_dbg_counter reports slot i in
     // microseconds under DEV_TIME_NAMES[i].  Of the last call: the saliency kernels, a WASE study call's reduction and output kernels,
     // k_ingest (tf_hold_frames, tf_hold_frames_rle), k_rle_decode (tf_rle_decode, tf_hold_frames_rle).  Since the handle was made:
     // k_inflate, k_unchunk, deflate's links + search, its emit + offsets + pack, and k_chunk.  Of the last tf_jpeg_decode /
-    // tf_hold_frames_jpeg: the four k_jpeg_* kernels.
+    // tf_hold_frames_jpeg: the four k_jpeg_* kernels.  Of the last tf_jpegll_decode / tf_hold_frames_jpegll: k_jpeg_marks + k_jpegll_entropy,
+    // and k_jpegll_col + k_jpegll_rows.
     enum { DT_SALIENCY, DT_WASE, DT_INGEST, DT_RLE, DT_INFLATE, DT_UNCHUNK, DT_DEFLATE_MATCH, DT_DEFLATE_EMIT, DT_CHUNK,
-           DT_JPEG_MARKS, DT_JPEG_ENTROPY, DT_JPEG_IDCT, DT_JPEG_FINISH, DT_COUNT };
+           DT_JPEG_MARKS, DT_JPEG_ENTROPY, DT_JPEG_IDCT, DT_JPEG_FINISH, DT_JPEGLL_ENTROPY, DT_JPEGLL_RESTORE, DT_COUNT };
     double dev_ms[DT_COUNT] = {};
     long long deflate_batches = 0;                                           // passes of deflate_run's batch loop since the handle was made
     // tf_segmentor_input does not wait for its work: pinned staging its upload reads from, and the events that say when the staging
@@ -258,7 +260,9 @@ struct tf_handle : Engine {
     long long rle_bytes = 0;             // the last tf_rle_decode / tf_hold_frames_rle: compressed bytes read + plane bytes written
     long long jpeg_bytes = 0;            // the last tf_jpeg_decode / tf_hold_frames_jpeg: compressed bytes read + sample bytes written
     long long jpeg_batches = 0;          // the batches of frames the JPEG decoder has worked through since the handle was made
-    int jpeg_batch_kib = 0;              // tuning: the coefficient scratch of a batch in KiB (0: 256 MiB); the tests cut a call into batches with it
+    long long jpegll_bytes = 0;          // the last tf_jpegll_decode / tf_hold_frames_jpegll: compressed bytes read + sample bytes written
+    long long jpegll_batches = 0;        // the batches of frames the JPEG Lossless decoder has worked through since the handle was made
+    int jpeg_batch_kib = 0;              // tuning: the coefficient scratch of a batch in KiB (0: 256 MiB), the lossless decoder's difference scratch too; the tests cut a call into batches with it
     // ---- the one-shot flags of the handle's next call, taken with spend(), below: tf_chain_next (a sequence is solved as a chain),
     // tf_hold_next (a study call leaves its payload held), tf_frames_next (the call reads held frames [first, first + count)).
     // `armed` holds the first two; tf_frames_next's part of the record is kept beside the handles (g_frames_next says why) ----
@@ -338,7 +342,8 @@ int fail(Engine* e, int code, const char* fmt, ...)
 
 constexpr const char* DEV_TIME_NAMES[tf_handle::DT_COUNT] = {"saliency_kernel_us", "wase_study_kernel_us", "ingest_kernel_us", "rle_kernel_us", "inflate_kernel_us",
                                                              "unchunk_kernel_us", "deflate_match_us", "deflate_emit_us", "chunk_kernel_us",
-                                                             "jpeg_marks_us", "jpeg_entropy_us", "jpeg_idct_us", "jpeg_finish_us"};
+                                                             "jpeg_marks_us", "jpeg_entropy_us", "jpeg_idct_us", "jpeg_finish_us",
+                                                             "jpegll_entropy_us", "jpegll_restore_us"};
 
 // The device time from ev[a] to ev[b] of the handle, both recorded on a stream that has been waited for, into dev_ms[slot]: added to
 // it, or put in its place.  A read-back that fails leaves the slot and is the caller's to judge: HIPC(h, dev_time(...)) fails the

@@ -569,6 +569,40 @@ class DenseFlow:
                                                _lib.JPEG_COLORS[color], 1 if flip else 0, status.ctypes.data), self._h, "tf_hold_frames_jpeg")
         return HeldFrames(self, N, H, W, self._held_frames_shape()[3])
 
+    # ---- DICOM JPEG Lossless pixel data (SOF3, predictor 1; tf_jpegll_decode, tf_hold_frames_jpegll): the Huffman decode emits
+    # prediction differences, the reconstruction is prefix sums on the device; frames.jpegll_decode_frame is the twin ------------------------
+    def jpeg_lossless_decode(self, record, H, W, samples):
+        """JPEG Lossless frames -- record = (blob, off, len), frame i the len[i] bytes at blob[off[i]:] (frames.jpegll_record), each a
+        full interchange stream with an SOF3 frame header and predictor 1 -- of H x W pixels of `samples` (1 or 3) components -> (uint8
+        [N,H,W,samples], or [N,H,W] for samples == 1; status int32 [N]): the encoded array, no colour transform.  A status is 0, 1 bad
+        header, 2 a process that is not decoded or 3 data that does not decode, a sample outside 0..255 included
+        (frames.jpegll_decode_frame has the rules); the call does not raise for a frame that does not decode: its status says so and
+        its frame is zeros.  A call that fails as a whole -- refused arguments, a HIP error -- raises."""
+        blob, off, ln, H, W, samples = self._jpeg_record(record, H, W, samples)
+        N = off.size
+        out = np.zeros((N, H, W) if samples == 1 else (N, H, W, samples), np.uint8)
+        status = np.zeros(N, np.int32)
+        rc = self._L.tf_jpegll_decode(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, out.ctypes.data, status.ctypes.data)
+        self._raise_unless_verdict(rc, status, "tf_jpegll_decode")
+        return out, status
+
+    def hold_frames_jpeg_lossless(self, record, H, W, samples, form="RGB", flip=False):
+        """hold_frames from JPEG Lossless pixel data as the file stores it: record = (blob, off, len) (frames.jpegll_record, or
+        pipeline.dicom_jpegll_frames' fields), H x W pixels of `samples` components -- 1 for form "GRAY", 3 for "RGB" and "YBR_FULL".
+        Only the compressed bytes are uploaded; the codec applies no colour transform, and what is held is
+        frames.ingest_host(decoded, form, flip).  -> the HeldFrames token.  If a frame does not decode the call raises with the first bad
+        frame and its status, and the frames held before, their generation and their tokens stay as they were."""
+        if form not in _lib.FRAMES_FORMS:
+            raise OpticalFlowCalculationError(f"form must be one of {tuple(_lib.FRAMES_FORMS)}, got {form!r}")
+        blob, off, ln, H, W, samples = self._jpeg_record(record, H, W, samples)
+        if samples != (1 if form == "GRAY" else 3):
+            raise OpticalFlowCalculationError(f"{form} frames have {1 if form == 'GRAY' else 3} samples a pixel, got samples = {samples}")
+        N = off.size
+        status = np.zeros(N, np.int32)
+        _lib.check(self._L.tf_hold_frames_jpegll(self._h, blob.ctypes.data, off.ctypes.data, ln.ctypes.data, N, H, W, samples, _lib.FRAMES_FORMS[form],
+                                                 1 if flip else 0, status.ctypes.data), self._h, "tf_hold_frames_jpegll")
+        return HeldFrames(self, N, H, W, self._held_frames_shape()[3])
+
     def _frames_in(self, frames, check, min_frames=1):
         """A method's `nparr` / `frames` argument: an array goes through `check`; a HeldFrames token is checked for being this engine's
         current frames and comes back as it is (it has the array's .shape).  Nothing is armed yet: _frames_ptr does that."""

@@ -26,8 +26,9 @@ from . import hdf5_out
 from .config import default_optical_flow_config
 from .dense_flow import DenseFlow
 from .exceptions import ConfigurationError, DICOMReadError, OpticalFlowCalculationError
-from .frames import (JPEG_BASELINE_TRANSFER_SYNTAX, JPEG_STATUS_TEXT, PHOTOMETRIC_FORMS, RLE_STATUS_TEXT, RLE_TRANSFER_SYNTAX, condition_frames,
-                     encapsulated_frames, jpeg_decode_frame, jpeg_record, rle_decode_frame, rle_record, ybr_full_to_rgb, ycc_to_rgb_libjpeg)
+from .frames import (JPEG_BASELINE_TRANSFER_SYNTAX, JPEG_LOSSLESS_TRANSFER_SYNTAXES, JPEG_STATUS_TEXT, PHOTOMETRIC_FORMS, RLE_STATUS_TEXT,
+                     RLE_TRANSFER_SYNTAX, condition_frames, encapsulated_frames, jpeg_decode_frame, jpeg_record, jpegll_decode_frame, jpegll_record,
+                     rle_decode_frame, rle_record, ybr_full_to_rgb, ycc_to_rgb_libjpeg)
 
 logger = logging.getLogger(__name__)
 
@@ -567,14 +568,97 @@ def _jpeg_fallback(reason):
         logger.warning(f"JPEG Baseline pixel data not decoded on the device, the host decodes it instead: {reason}")
 
 
+# ---- JPEG Lossless pixel data as stored (SOF3, predictor 1; transfer syntaxes 1.2.840.10008.1.2.4.70 and .57, 8-bit samples) ------------
+@dataclass(frozen=True)
+class JpegLosslessFrames(RleFrames):
+    """A study's pixel data as a DICOM JPEG Lossless file stores it: RleFrames' fields, each frame a full interchange stream with an
+    SOF3 frame header (frames.jpegll_record's record).  The codec applies no colour transform: the samples are what
+    PhotometricInterpretation says, as RLE Lossless planes are.  What frames="device" hands to DenseFlow.hold_frames_jpeg_lossless in an
+    array's place; decode() is the host's way."""
+
+    def decode(self):
+        """-> the encoded arrays: uint8 [N,H,W] (samples == 1) or [N,H,W,samples]; by PIL where it imports on libjpeg-turbo, takes the
+        stream and gives the right shape and mode, otherwise by the twin frames.jpegll_decode_frame (slow); DICOMReadError for a frame
+        that does not decode"""
+        N, H, W = self.shape
+        blob = np.asarray(self.blob, np.uint8)
+        out = np.empty((N, H, W) if self.samples == 1 else (N, H, W, self.samples), np.uint8)
+        for i in range(N):
+            a = int(self.off[i])
+            buf = blob[a:a + int(self.len[i])].tobytes()
+            arr = _pil_lossless(buf, out.shape[1:])
+            if arr is None:
+                arr, status = jpegll_decode_frame(buf, H, W, self.samples)
+                if status:
+                    raise DICOMReadError(f"JPEG Lossless frame {i} did not decode: status {status} ({JPEG_STATUS_TEXT[status]})")
+            out[i] = arr
+        return out
+
+
+def _pil_lossless(buf, shape):
+    """One JPEG Lossless stream's samples by PIL on libjpeg-turbo (3.0 and later decode SOF3), or None where PIL does not import, is
+    built on another libjpeg, does not take the stream, or gives another mode (L for one sample, RGB -- the samples as stored, no colour
+    transform -- for three) or shape: the twin decides then.  On a valid stream the two agree, there being one decoding; what libjpeg makes
+    of a malformed one (it masks a sample to 8 bits where the twin gives status 3) is not pinned."""
+    try:
+        import io
+        from PIL import Image, features
+        if not features.check_feature("libjpeg_turbo"):
+            return None
+        im = Image.open(io.BytesIO(buf))
+        if im.format != "JPEG" or im.mode != ("L" if len(shape) == 2 else "RGB"):
+            return None
+        arr = np.asarray(im)
+    except Exception:                                                      # (whatever PIL makes of a malformed stream: the twin's status is the answer)
+        return None
+    return arr if arr.shape == tuple(shape) and arr.dtype == np.uint8 else None
+
+
+def _jpegll_refusal(ds):
+    """Why a dataset in a JPEG Lossless transfer syntax is not decoded from its stored bytes, or None"""
+    bits, samples = int(getattr(ds, "BitsAllocated", 0) or 0), int(getattr(ds, "SamplesPerPixel", 0) or 0)
+    if bits != 8:
+        return f"JPEG Lossless pixel data with BitsAllocated = {bits}: only 8-bit samples are decoded from the stored bytes"
+    if samples not in (1, 3):
+        return f"JPEG Lossless pixel data with SamplesPerPixel = {samples}: only 1 or 3 samples are decoded from the stored bytes"
+    return None
+
+
+def _is_jpegll(ds):
+    return str(getattr(getattr(ds, "file_meta", None), "TransferSyntaxUID", "")) in JPEG_LOSSLESS_TRANSFER_SYNTAXES
+
+
+def dicom_jpegll_frames(ds):
+    """The pixel data of an 8-bit JPEG Lossless dataset (either transfer syntax of frames.JPEG_LOSSLESS_TRANSFER_SYNTAXES) as it is
+    stored -> JpegLosslessFrames; None for any other dataset (another transfer syntax, samples that are not 8-bit, a sample count other
+    than 1 or 3), which is read through its pixel_array as ever.  A pure function of any dataset-like object, as dicom_jpeg_frames:
+    frames.encapsulated_frames cuts PixelData into frames.  No pydicom."""
+    if not _is_jpegll(ds) or _jpegll_refusal(ds) is not None:
+        return None
+    N, H, W = int(getattr(ds, "NumberOfFrames", 1) or 1), int(ds.Rows), int(ds.Columns)
+    blob, off, ln = jpegll_record(encapsulated_frames(ds.PixelData, N))
+    return JpegLosslessFrames(blob, off, ln, (N, H, W), int(ds.SamplesPerPixel), str(getattr(ds, "PhotometricInterpretation", "")) or None)
+
+
+_jpegll_fallbacks = set()           # reasons already logged
+
+
+def _jpegll_fallback(reason):
+    if reason not in _jpegll_fallbacks:
+        _jpegll_fallbacks.add(reason)
+        logger.warning(f"JPEG Lossless pixel data not decoded on the device, the host decodes it instead: {reason}")
+
+
 class _DeviceFrames:
     """A study's frames held on the flow model's device (frames="device"): the token every device call takes, and the RGB for what
-    still runs on the host, downloaded once.  `stored`: the pixel data as an array, or as RleFrames / JpegFrames (the device decodes
-    them)."""
+    still runs on the host, downloaded once.  `stored`: the pixel data as an array, or as RleFrames / JpegFrames / JpegLosslessFrames
+    (the device decodes them)."""
 
     def __init__(self, model, stored, form, flip, color="none"):
         if isinstance(stored, JpegFrames):
             token = model.hold_frames_jpeg(stored.record, stored.shape[1], stored.shape[2], stored.samples, form, color=color, flip=flip)
+        elif isinstance(stored, JpegLosslessFrames):
+            token = model.hold_frames_jpeg_lossless(stored.record, stored.shape[1], stored.shape[2], stored.samples, form, flip=flip)
         elif isinstance(stored, RleFrames):
             token = model.hold_frames_rle(stored.record, stored.shape[1], stored.shape[2], stored.samples, form, flip=flip)
         else:
@@ -617,7 +701,10 @@ def process_video(dcm_path, save_path, segmentor_model=None, verbose=True, mode=
     `samples`, `photometric`) is held likewise by DenseFlow.hold_frames_jpeg (_jpeg_form says in which form and by which colour
     route); a model without it, a refused dataset and a frame the device gives a status for take the host's decode (PIL where it
     imports, else frames.jpeg_decode_frame), with one logged reason per walk.  frames="host" and read_study read a DICOM file through
-    ds.pixel_array as ever."""
+    ds.pixel_array as ever.
+    8-bit JPEG Lossless pixel data (JpegLosslessFrames: dicom_jpegll_frames, or an .npz with `jpegll_blob`, `jpegll_off`, `jpegll_len`,
+    `rows`, `cols`, `samples`, `photometric`) is held by DenseFlow.hold_frames_jpeg_lossless in the form _rle_form names, with the same
+    three host fallbacks (PIL where it imports and takes the stream, else frames.jpegll_decode_frame), one logged reason per walk."""
     return _process_video_begin(dcm_path, save_path, segmentor_model, verbose, mode, bkgd_comp, flipLR, no_saliency, OF_algo, save_mask_subset,
                                 include_waveforms, waveform_folder, config, nparr=nparr, metadata=metadata, patient_id=patient_id,
                                 heart_rate=heart_rate, waveforms=waveforms, flow_model=flow_model, mask_dict=mask_dict, _defer_save=_defer_save,
@@ -696,6 +783,19 @@ def _process_video_begin(dcm_path, save_path, segmentor_model=None, verbose=True
             if why is not None:                   # the host decodes; what it gives goes the way of any stored array, below
                 _jpeg_fallback(why)
                 nparr, _photometric = _jpeg_host(rle, _photometric)
+        elif isinstance(rle, JpegLosslessFrames):  # (frames="device")
+            form, why = _rle_form(rle, _photometric)
+            if why is None and not hasattr(model, "hold_frames_jpeg_lossless"):
+                why = f"the flow model ({type(model).__name__}) has no hold_frames_jpeg_lossless"
+            if why is None:
+                try:
+                    held = _DeviceFrames(model, rle, form, flipLR)
+                    nparr = held.token
+                except OpticalFlowCalculationError as e:                  # a frame whose status is not 0: the held frames are as they were
+                    why = f"the device did not decode it ({e})"
+            if why is not None:                   # the host decodes; what it gives goes the way of any stored array, below
+                _jpegll_fallback(why)
+                nparr = rle.decode()
         elif rle is not None:                     # (frames="device")
             form, why = _rle_form(rle, _photometric)
             if why is None and not hasattr(model, "hold_frames_rle"):
@@ -821,6 +921,8 @@ def _npz_stored(z, path):
     `rle_len` (frames.rle_record's) with `rows`, `cols` and `samples` -> RleFrames"""
     if "jpeg_blob" in z:
         return _npz_jpeg(z, path)
+    if "jpegll_blob" in z:
+        return _npz_jpegll(z, path)
     if "rle_blob" not in z:
         return z["nparr"]
     try:
@@ -847,6 +949,21 @@ def _npz_jpeg(z, path):
             or int((off + ln.astype(np.uint64)).max()) > blob.size or color not in JPEG_COLOR_ROUTES):
         raise DICOMReadError(f"Failed to read {path}: jpeg_off / jpeg_len / jpeg_color do not describe frames of {H} x {W} x {samples} inside jpeg_blob's {blob.size} bytes")
     return JpegFrames(blob, off, ln, (int(off.size), H, W), samples, _npz_photometric(z, path), color)
+
+
+def _npz_jpegll(z, path):
+    """JPEG Lossless frames of an .npz study under `jpegll_blob`, `jpegll_off`, `jpegll_len` (frames.jpegll_record's) with `rows`,
+    `cols`, `samples` and, optionally, `photometric` -> JpegLosslessFrames"""
+    try:
+        blob, off, ln = (np.ascontiguousarray(z["jpegll_blob"], np.uint8), np.ascontiguousarray(z["jpegll_off"], np.uint64),
+                         np.ascontiguousarray(z["jpegll_len"], np.uint32))
+        H, W, samples = int(z["rows"]), int(z["cols"]), int(z["samples"])
+    except KeyError as e:
+        raise DICOMReadError(f"Failed to read {path}: a JPEG Lossless study needs jpegll_blob, jpegll_off, jpegll_len, rows, cols and samples ({e} is missing)") from e
+    if (blob.ndim != 1 or off.ndim != 1 or off.shape != ln.shape or off.size < 1 or H < 1 or W < 1 or samples not in (1, 3)
+            or int((off + ln.astype(np.uint64)).max()) > blob.size):
+        raise DICOMReadError(f"Failed to read {path}: jpegll_off / jpegll_len do not describe frames of {H} x {W} x {samples} inside jpegll_blob's {blob.size} bytes")
+    return JpegLosslessFrames(blob, off, ln, (int(off.size), H, W), samples, _npz_photometric(z, path))
 
 
 def _npz_photometric(z, path):
@@ -888,8 +1005,22 @@ def _stored_jpeg(ds, path):
         raise DICOMReadError(f"Failed to read DICOM file: {path} ({e})") from e
 
 
+def _stored_jpegll(ds, path):
+    """_stored_rle for a JPEG Lossless dataset: JpegLosslessFrames, or None -- with one logged reason where the stored bytes are not decoded"""
+    if not _is_jpegll(ds):
+        return None
+    why = _jpegll_refusal(ds)
+    if why is not None:
+        _jpegll_fallback(why)
+        return None
+    try:
+        return dicom_jpegll_frames(ds)
+    except ValueError as e:
+        raise DICOMReadError(f"Failed to read DICOM file: {path} ({e})") from e
+
+
 def _read_dicom(path, stored=False):
-    """`stored` (read_study_stored): the pixel data as the file stores it where that has a device form (_stored_rle)"""
+    """`stored` (read_study_stored): the pixel data as the file stores it where that has a device form (_stored_rle, _stored_jpeg, _stored_jpegll, tried in that order)"""
     try:
         import pydicom
     except ImportError as e:
@@ -899,6 +1030,8 @@ def _read_dicom(path, stored=False):
         arr = _stored_rle(ds, path) if stored else None
         if arr is None and stored:
             arr = _stored_jpeg(ds, path)
+        if arr is None and stored:
+            arr = _stored_jpegll(ds, path)
         if arr is None:
             arr = ds.pixel_array
     except (IOError, OSError, KeyError, AttributeError) as e:             # reference _read_dicom_file (:307-312) -> DICOMReadError (:521-522)
@@ -911,7 +1044,8 @@ def read_study_stored(path):
     patient id, heart rate), for frames="device".  The interpretation is named only where the data is to be converted: pydicom's own
     should_change_PhotometricInterpretation_to_RGB(ds) decides that for a DICOM file, the `photometric` key for an .npz; None means RGB
     or grey frames by their shape.  8-bit RLE Lossless pixel data -- a DICOM file in that transfer syntax (dicom_rle_frames, taken
-    before ds.pixel_array is touched), an .npz with `rle_blob` & co. -- comes as RleFrames, not decoded."""
+    before ds.pixel_array is touched), an .npz with `rle_blob` & co. -- comes as RleFrames, not decoded; JPEG Baseline and JPEG Lossless pixel data likewise as JpegFrames and
+    JpegLosslessFrames."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".npy":
         return np.load(path, allow_pickle=False), None, None, "", 0
@@ -1273,6 +1407,7 @@ def process_folder(dcm_folder, save_folder, segmentor_model=None, nchunks=10, ch
     _frames_fallbacks.clear()                                       # one logged reason per walk
     _rle_fallbacks.clear()
     _jpeg_fallbacks.clear()
+    _jpegll_fallbacks.clear()
     if deflate == "device":
         _deflate_fallbacks.clear()                                  # one logged reason per walk
         if studies_in_flight > 1:

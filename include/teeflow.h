@@ -705,11 +705,24 @@ int tf_jpeg_stage_bytes(void);
  * tf_dbg_counter: "frames_upload_bytes" grows by the compressed bytes uploaded; "jpegll_entropy_us" (k_jpeg_marks and
  *   k_jpegll_entropy) and "jpegll_restore_us" (k_jpegll_col and k_jpegll_rows): device time in the last of these calls; "jpegll_bytes":
  *   the compressed bytes read and the sample bytes written; "jpegll_batches": the batches of frames worked through since the handle
- *   was made (a batch's differences, 2 bytes a sample, stay under 256 MiB; tf_set_tuning "jpeg_batch_kib" lowers that for tests). */
+ *   was made (a batch's differences, 2 bytes a sample, stay under 256 MiB; tf_set_tuning "jpeg_batch_kib" lowers that for tests).
+ * The entropy pass of a restart interval has two forms with the same result, frame for frame and status for status.  The serial one is
+ *   one wave an interval.  The split one (csrc/teeflow_jpegll_sync_core.h) cuts the interval's data into pieces of
+ *   tf_jpegll_segment_bytes() bytes, one lane a piece: every piece is decoded from a guessed start, then handed the exit of the piece
+ *   before it round after round -- Huffman streams self-synchronise -- and an interval that a round still changed after the last round
+ *   is decoded by the serial form.  tf_set_tuning "jpegll_split": 0 (default) the host picks per frame, before the first launch, by the
+ *   bytes of entropy data an interval of the frame holds on average (a frame whose components name different codes stays serial: its
+ *   pieces agree on the component only as fast as the truth travels, a block of 256 pieces a round); 1 the serial form only; 2 the split form for every interval (frames
+ *   of 128 MiB or more stay serial); any other value is refused.  "jpegll_sync_rounds": the rounds a batch launches, 0..64 (0: the
+ *   speculation only; default 8, twice what the measured study needs).  tf_dbg_counter "jpegll_split_intervals": the intervals sent
+ *   down the split form since the handle was made; "jpegll_serial_fallbacks": those of them that did not converge and were decoded
+ *   serially; "jpegll_sync_rounds": the rounds launched in the last call, all its batches.  "jpegll_entropy_us" covers all entropy work
+ *   of either form.  The split form's scratch, 20 bytes a piece, counts into a batch's 256 MiB. */
 int tf_jpegll_decode(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
                      uint8_t* out_host, int* status);
 int tf_hold_frames_jpegll(tf_handle* h, const uint8_t* blob, const uint64_t* off, const uint32_t* len, int N, int H, int W, int samples,
                           int form, int flip_lr, int* status);
+int tf_jpegll_segment_bytes(void);
 
 /* ---- a study held from the CHUNKS of its file: the gzip chunks of a study file's datasets are independent zlib streams (RFC 1950
  *      around RFC 1951), which the device inflates itself, one wave per stream, and assembles into the row-major arrays; what goes over

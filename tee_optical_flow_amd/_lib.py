@@ -17,6 +17,8 @@ HELD_SLOTS = 12              # TF_HELD_SLOTS
 HELD_SHAPE_LEN = 5 + 2 * HELD_SLOTS   # TF_HELD_SHAPE_LEN
 FRAMES_FORMS = {"RGB": 0, "GRAY": 1, "YBR_FULL": 2}   # TF_FRAMES_*
 RLE_STAGE_BYTES = 1024       # tf_rle_stage_bytes(): the bytes of a segment k_rle_decode stages at a time (rle::STAGE)
+JPEGLL_SEGMENT_BYTES = 32    # tf_jpegll_segment_bytes(): the bytes of a piece of the split JPEG Lossless entropy decode (tfsync::SEG)
+JPEGLL_SYNC_ROUNDS = 8       # the library's default of the tuning knob "jpegll_sync_rounds"
 JPEG_STAGE_BYTES = 1024      # tf_jpeg_stage_bytes(): the bytes of a frame the k_jpeg_* kernels stage at a time (jpeg::STAGE)
 JPEG_COLORS = {"none": 0, "libjpeg": 1}   # TF_JPEG_COLOR_*
 PARAM_KEYS = {
@@ -42,7 +44,7 @@ EXPORTED_SYMBOLS = [
     "tf_hold_frames", "tf_held_frames_shape", "tf_release_frames", "tf_download_frames", "tf_frames_next",
     "tf_rle_decode", "tf_hold_frames_rle", "tf_rle_stage_bytes",
     "tf_jpeg_decode", "tf_hold_frames_jpeg", "tf_jpeg_stage_bytes",
-    "tf_jpegll_decode", "tf_hold_frames_jpegll",
+    "tf_jpegll_decode", "tf_hold_frames_jpegll", "tf_jpegll_segment_bytes",
     "tf_comm_unique_id", "tf_comm_init_rank", "tf_comm_init_all", "tf_allgather_flows", "tf_allgather_flows_all", "tf_comm_wait", "tf_comm_destroy",
 ]
 
@@ -207,6 +209,7 @@ def load():
     L.tf_jpeg_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.tf_hold_frames_jpeg.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.tf_jpeg_stage_bytes.restype = i32
+    L.tf_jpegll_segment_bytes.restype = i32
     L.tf_jpegll_decode.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.tf_hold_frames_jpegll.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.tf_hold_study_chunks.argtypes = [vp, C.POINTER(TfChunked), C.POINTER(TfChunked)]

@@ -215,6 +215,11 @@ TF_API int tf_set_tuning(tf_handle* h, const char* name, int value)
     else if (n == "overlay_chunk_kib") h->overlay_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);   // never above the 512 MiB rule
     else if (n == "area_chunk_kib") h->area_chunk_kib = value < 0 ? 0 : (value > (512 << 10) ? (512 << 10) : value);         // the same
     else if (n == "jpeg_batch_kib") h->jpeg_batch_kib = value < 0 ? 0 : (value > (256 << 10) ? (256 << 10) : value);           // never above the 256 MiB rule
+    else if (n == "jpegll_split") {
+        if (value < 0 || value > 2) return fail(h, TF_ERR_INVALID_ARG, "jpegll_split must be 0 (automatic), 1 (the serial kernel only) or 2 (the split decode for every interval), got %d", value);
+        h->jpegll_split = value;
+    }
+    else if (n == "jpegll_sync_rounds") h->jpegll_sync_rounds = value < 0 ? 0 : (value > 64 ? 64 : value);
     else return fail(h, TF_ERR_INVALID_ARG, "unknown tuning knob %s", name);
     return TF_OK;
 }
@@ -251,6 +256,9 @@ TF_API long long tf_dbg_counter(tf_handle* h, const char* name)
     else if (n == "jpeg_batches") v = h->jpeg_batches;
     else if (n == "jpegll_bytes") v = h->jpegll_bytes;
     else if (n == "jpegll_batches") v = h->jpegll_batches;
+    else if (n == "jpegll_split_intervals") v = h->jpegll_split_intervals;
+    else if (n == "jpegll_serial_fallbacks") v = h->jpegll_serial_fallbacks;
+    else if (n == "jpegll_sync_rounds") v = h->jpegll_rounds_launched;
     else if (n == "study_download_bytes") v = h->study_download_bytes;
     else if (n == "streams_serialised") v = h->streams_serialised;
     else if (n == "queue_units_done" || n == "queue_units_skipped" || n == "queue_units_failed" || n == "queue_outstanding" || n == "queue_lanes") {

@@ -206,9 +206,10 @@ struct tf_handle : Engine {
            PRE_FR_SRC,                                                            // tf_hold_frames: the source bytes as the file stores them, before k_ingest
            PRE_RLE_BLOB, PRE_RLE_TABLE, PRE_RLE_PLANES, PRE_RLE_OUT,              // tf_rle_decode, tf_hold_frames_rle: compressed bytes, per-frame table, the decoded
                                                                                   //   sample planes; tf_rle_decode's interleaved frames
-           PRE_JPEG_BLOB, PRE_JPEG_TABLE, PRE_JPEG_RST, PRE_JPEG_COEF, PRE_JPEG_PLANES, PRE_JPEG_OUT,   // tf_jpeg_decode, tf_hold_frames_jpeg: compressed bytes, per-frame
+           PRE_JPEG_BLOB, PRE_JPEG_TABLE, PRE_JPEG_RST, PRE_JPEG_COEF, PRE_JPEG_PLANES, PRE_JPEG_OUT, PRE_JPEG_SYNC,   // tf_jpeg_decode, tf_hold_frames_jpeg: compressed bytes, per-frame
                                                                                   //   table, RSTn positions, a batch's coefficients and component planes; the frames.
-                                                                                  //   tf_jpegll_decode, tf_hold_frames_jpegll use the same slots (COEF: a batch's differences)
+                                                                                  //   tf_jpegll_decode, tf_hold_frames_jpegll use the same slots (COEF: a batch's differences;
+                                                                                  //   SYNC: the split entropy decode's per-piece and per-interval scratch of a batch)
            PRE_COUNT };
     GrowBuf pre[PRE_COUNT];
     // Device time of the tail's kernels in ms, read from the handle's event pairs (dev_time, below); tf_dbg_counter reports slot i in
@@ -262,6 +263,11 @@ struct tf_handle : Engine {
     long long jpeg_batches = 0;          // the batches of frames the JPEG decoder has worked through since the handle was made
     long long jpegll_bytes = 0;          // the last tf_jpegll_decode / tf_hold_frames_jpegll: compressed bytes read + sample bytes written
     long long jpegll_batches = 0;        // the batches of frames the JPEG Lossless decoder has worked through since the handle was made
+    long long jpegll_split_intervals = 0;   // restart intervals sent down the split entropy decode since the handle was made
+    long long jpegll_serial_fallbacks = 0;  // ... of which did not converge within the rounds and were decoded serially
+    long long jpegll_rounds_launched = 0;   // the last tf_jpegll_decode / tf_hold_frames_jpegll: synchronisation rounds launched, all batches
+    int jpegll_split = 0;                // tuning: 0 the split decode where the host's rule picks it, 1 the serial kernel only, 2 the split decode for every interval
+    int jpegll_sync_rounds = 8;          // tuning: synchronisation rounds a batch launches (0: speculation only)
     int jpeg_batch_kib = 0;              // tuning: the coefficient scratch of a batch in KiB (0: 256 MiB), the lossless decoder's difference scratch too; the tests cut a call into batches with it
     // ---- the one-shot flags of the handle's next call, taken with spend(), below: tf_chain_next (a sequence is solved as a chain),
     // tf_hold_next (a study call leaves its payload held), tf_frames_next (the call reads held frames [first, first + count)).

@@ -262,6 +262,20 @@ template <class IO> TFJ_FN int decode(IO& io, Bits& b, const Huff& t)         //
     return -1;
 }
 
+// decode for lanes that each read a stream of their own: the same steps with every table entry read per lane (TFJ_UNIFORM would hand
+// all lanes the first lane's entry)
+template <class IO> TFJ_FN int decode_any(IO& io, Bits& b, const Huff& t)
+{
+    refill(io, b);
+    const uint32_t e = t.look[(b.acc >> (b.cnt - 8)) & 0xFF];
+    if (e) { b.cnt -= (int)(e >> 8); return (int)(e & 0xFF); }
+    for (int l = 9; l <= 16; ++l) {
+        const int32_t c = (int32_t)((b.acc >> (b.cnt - l)) & ((1u << l) - 1));
+        if (c <= t.maxcode[l]) { b.cnt -= l; return (int)t.vals[(t.valoff[l] + c) & 255]; }
+    }
+    return -1;
+}
+
 template <class IO> TFJ_FN int receive_extend(IO& io, Bits& b, int s)        // 1 <= s <= 15
 {
     refill(io, b);
